@@ -2,6 +2,8 @@
 """bench.py -- headline benchmark of the hot path (BASELINE.json): PPO-update samples/s.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus 1 --steps K --warmup W --full   (the headline, then every extra leg below on the same line)
+    ... --dump-outputs DIR                                 (also writes what the last timed step computed as DIR/<name>.npy)
 
 Workload = BASELINE.json configs[1] ("1xMI355X: 4096 parallel agents, obs=107 f32, |A|=90 discrete, 256x3 MLP,
 512k-sample buffer"): a 524,288-sample device-resident ExperienceBuffer (4096 agents x 128 steps), ppo_batch_size
@@ -14,7 +16,8 @@ evaluates its consecutive slices in one fused pass: the minibatches of a batch a
 before the one optimiser step, ppo_learner.py:134-193) and one RCCL all-reduce of the flat gradient arena precedes the optimiser
 step (total work fixed: strong scaling).
 
-Extra objects on the same JSON line (N=1 only): `roofline` for the dominant kernel of the timed region, `gae` =
+A plain run sets up, warms up, times the K steps and prints the headline line, nothing more.
+Extra objects on the same JSON line (N=1 and --full only): `roofline` for the dominant kernel of the timed region, `gae` =
 the GAE scan (BASELINE configs[2]: 8192 x 256, HBM-bound) with its own roofline, `rollout` = policy inference
 obs/s at 4096 x 107, `cpu_baseline` = the CPU oracle (a port of the reference's op sequence; kind "port") timed on
 this box's host cores on a bounded sample.
@@ -1088,6 +1091,21 @@ def fit_line(out, limit=LINE_LIMIT):
     return dumps(out)
 
 
+def dump_outputs(learner, report, out_dir):
+    """--dump-outputs: what the last timed learn() handed its caller, as out_dir/<name>.npy -- the parameters it left in the policy
+    and the critic (flat float32, parameters() order) and every number of its report (float64), except the wall time the report
+    measures itself.  The workload is seeded (build_workload), so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"policy_params": torch.nn.utils.parameters_to_vector(learner.policy.parameters()).detach().float().cpu().numpy(),
+              "value_params": torch.nn.utils.parameters_to_vector(learner.value_net.parameters()).detach().float().cpu().numpy()}
+    for k, v in report.items():
+        if k != "PPO Batch Consumption Time":
+            arrays["report_" + k.lower().replace(" ", "_")] = np.array([v], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("bench.py: wrote %d arrays (%.1f MB) to %s" % (len(arrays), sum(a.nbytes for a in arrays.values()) / 1e6, out_dir))
+
+
 # ---------------------------------------------------------------------------------------------------- main
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -1095,7 +1113,14 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--epochs", type=int, default=10)
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / gae / rollout / cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every extra leg (roofline + kernel_breakdown, non_gemm_tail, update_x3, gae, "
+                         "rollout, iteration, cfg5, cpu_baseline, ref_defaults, process_collect; for --config cfg5 the kernel rooflines) "
+                         "and put them on the line; off by default: a plain run times the headline alone")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra legs (a plain run has none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed learn() computed -- the policy's and the critic's "
+                         "parameters (float32) and the numbers of its report (float64) -- as DIR/<name>.npy")
     ap.add_argument("--config", choices=("cfg2", "cfg5"), default="cfg2",
                     help="cfg2 = BASELINE configs[1] (the headline metric); cfg5 = configs[4] shape (Gaussian policy, obs 231, "
                          "512x4 nets) -- update throughput only, no extra legs")
@@ -1108,7 +1133,10 @@ def parse_args(argv=None):
                          "librlppo's own RCCL communicator, or 'ab' = the timed region uses torch.distributed, the JSON line is printed, "
                          "and a short A/B of both routes follows on stderr (opt-in: the direct communicator has never run with more "
                          "than one rank on this pool, so it stays out of the line the driver records)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -1305,6 +1333,8 @@ def main():
                         all=[round(x / args.steps * 1e3, 3) for x in ts])
         if rank == 0:
             log("per-rank ms per step: " + ", ".join("%.3f" % x for x in per_rank["all"]) + " (value uses the max)")
+    if args.dump_outputs and rank == 0:  # (the replicas are identical after every optimiser step)
+        dump_outputs(learner, report, args.dump_outputs)
 
     samples = args.steps * args.epochs * (N_SAMPLES // BATCH) * BATCH
     value = samples / dt
@@ -1373,9 +1403,10 @@ def main():
         signal.signal(signal.SIGTERM, signal.SIG_DFL)
         if rank == 0:
             log("exchange A/B: " + json.dumps(ab))
-    if rank == 0 and world == 1 and not args.no_extras and args.config == "cfg5":
+    extras = args.full and not args.no_extras
+    if rank == 0 and world == 1 and extras and args.config == "cfg5":
         out.update(cfg5_rooflines(value, bf16, learner))
-    if rank == 0 and world == 1 and not args.no_extras and args.config == "cfg2":
+    if rank == 0 and world == 1 and extras and args.config == "cfg2":
         rows, dom, M = kernel_breakdown(learner)
         for r in rows:
             log("  %-24s x%d  %8.4f ms  %7.2f TFLOP/s (algorithmic), %7.2f executed" % (r["kernel"], r["n"], r["ms"], r["tflops"], r["exec_tflops"]))

@@ -8,10 +8,10 @@ rm -rf $OUT/cfg5_stats $OUT/cfg5_fetch $OUT/cfg5_write $OUT/cfg5_sq $OUT/stats $
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ "$2" != "profiles-only" ]; then
-python bench.py --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.log
+python bench.py --steps 5 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.log
 head -c 400 $OUT/bench.json; echo
-python bench.py --config cfg5 --precision fp32 --steps 3 --warmup 1 > $OUT/bench_cfg5_fp32.json 2> $OUT/bench_cfg5_fp32.log
-python bench.py --config cfg5 --precision bf16 --steps 3 --warmup 1 > $OUT/bench_cfg5_bf16.json 2> $OUT/bench_cfg5_bf16.log
+python bench.py --config cfg5 --precision fp32 --steps 3 --warmup 1 --full > $OUT/bench_cfg5_fp32.json 2> $OUT/bench_cfg5_fp32.log
+python bench.py --config cfg5 --precision bf16 --steps 3 --warmup 1 --full > $OUT/bench_cfg5_bf16.json 2> $OUT/bench_cfg5_bf16.log
 fi
 if [ "$2" == "bench-only" ]; then exit 0; fi
 # a third argument splits the profile passes over two GPU-box calls of <= 20 minutes: stage-a = kernel traces + PMC passes, stage-b = the tools
