@@ -203,7 +203,8 @@ int rlppo_categorical_select(void *stream, const float *probs, int64_t ld_p, int
 /* ContinuousPolicy.get_action (continuous_policy.py:75-98): tanh head, std = y*var_m + var_b
  * (torch_functions.py:30-33), action = clamp(mean + std*eps, -1, 1) with the caller's N(0,1) noise
  * eps[n][k], logp = sum_k logpdf(action) with the reference's 4-term formula (continuous_policy.py:54-63).
- * dims[n_layers] == 2k.  actions: float[n][k]; logp: float[n]. */
+ * dims[n_layers] == 2k, any k >= 1 (above 32 action dimensions the float terms of logp are summed in double, here and in the
+ * update's loss kernel).  actions: float[n][k]; logp: float[n]. */
 int rlppo_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed,
                        const float *obs, int64_t ld_obs, int64_t n, const float *noise_eps, float var_m, float var_b,
                        float *actions, float *logp, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts);

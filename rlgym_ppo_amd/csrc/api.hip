@@ -975,7 +975,11 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
         return RLPPO_ERR_WORKSPACE;
     }
     const int n_out = pol.L[pol.n_layers - 1].out;
-    if (a->head == RLPPO_HEAD_DISCRETE) RLPPO_CHECK_ARG(a->act_dim == 1, "discrete head: act_dim must be 1");
+    if (a->head == RLPPO_HEAD_DISCRETE) {  // (the loss kernel's width checked here too: before anything is enqueued)
+        RLPPO_CHECK_ARG(a->act_dim == 1, "discrete head: act_dim must be 1");
+        RLPPO_CHECK_ARG(pol.L[pol.n_layers - 1].pout <= DISCRETE_LOSS_MAX_LD, "discrete head: padded width %ld too large",
+                        (long)pol.L[pol.n_layers - 1].pout);
+    }
     if (a->head == RLPPO_HEAD_GAUSSIAN)
         RLPPO_CHECK_ARG(n_out % 2 == 0 && a->act_dim == n_out / 2, "gaussian head: act_dim=%d, outputs=%d", a->act_dim, n_out);
     if (a->head == RLPPO_HEAD_MULTIDISCRETE)

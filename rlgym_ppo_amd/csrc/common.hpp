@@ -220,6 +220,7 @@ int launch_multidiscrete_sample(hipStream_t, const float *, int64_t, int64_t, co
                                 unsigned *done_words = nullptr, unsigned done_value = 0);
 int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const int64_t *idx, const float *targets, int64_t mb,
                       const LossCfg &cfg, double *stats);
+constexpr int64_t DISCRETE_LOSS_MAX_LD = 64 * 32;  // padded logits per row of the widest discrete loss kernel (one wave, 32 per lane)
 int launch_discrete_loss(hipStream_t, float *, int64_t, int, float *, int64_t, const int64_t *, const float *, const float *,
                          const float *, const float *, int64_t, const LossCfg &, double *);
 int launch_gaussian_loss(hipStream_t, float *, int64_t, int, float *, int64_t, const int64_t *, const float *, const float *,

@@ -465,7 +465,7 @@ int launch_discrete_loss(hipStream_t st, float *logits, int64_t ld, int A, float
                          const LossCfg &cfg, double *stats) {
     if (mb <= 0) return 0;
     dim3 grid((unsigned)(cdiv(mb, 4) < 2048 ? cdiv(mb, 4) : 2048)), block(256);
-    RLPPO_CHECK_ARG(ld <= 64 * 32, "discrete head: padded width %ld too large", (long)ld);
+    RLPPO_CHECK_ARG(ld <= DISCRETE_LOSS_MAX_LD, "discrete head: padded width %ld too large", (long)ld);
     if (ld <= 128) {  // 16 lanes per row, DPP reductions
         dim3 grid16((unsigned)(cdiv(mb, 16) < 2048 ? cdiv(mb, 16) : 2048));
         hipLaunchKernelGGL(discrete_loss16_kernel, grid16, block, 0, st, logits, ld, A, vout, ldv, idx, actions, old_logp, targets, adv, mb, cfg, stats);
@@ -478,7 +478,10 @@ int launch_discrete_loss(hipStream_t st, float *logits, int64_t ld, int A, float
 }
 
 // --------------------------------------------------------------------------------------------- gaussian
-constexpr int MAX_K = 32;  // action dimensions supported by the one-thread-per-row kernels
+// Up to FLOAT_SUM_K action dimensions a row's log-probability (and entropy) is summed in float, in j order.  A serial float sum
+// of more terms drifts past the reference's own float32 (torch sums over k with partial sums): at k = 64 the update's gradients
+// miss float64 by 1.5e-5.  Wider heads therefore sum the same float terms in double and round once.
+constexpr int FLOAT_SUM_K = 32;
 
 __device__ __forceinline__ float gauss_logpdf(float x, float mean, float sd) {
     // the reference's four terms, in its order (continuous_policy.py:54-63)
@@ -510,15 +513,19 @@ __global__ __launch_bounds__(256) void gaussian_sample_kernel(const float *__res
     if (row < n) {
         const float *yr = y + row * ld;
         float lp = 0.f;
+        double lpd = 0.0;  // (k > FLOAT_SUM_K)
         for (int j = 0; j < k; ++j) {
             const float mean = yr[j];
             const float sd = yr[k + j] * var_m + var_b;
             float a = eps[row * k + j] * sd + mean;  // at::normal: output.mul_(std).add_(mean)
             a = fminf(fmaxf(a, -1.f), 1.f);
             actions[row * k + j] = a;
-            lp += gauss_logpdf(a, mean, sd);
+            if (k <= FLOAT_SUM_K)
+                lp += gauss_logpdf(a, mean, sd);
+            else
+                lpd += (double)gauss_logpdf(a, mean, sd);
         }
-        logp[row] = lp;
+        logp[row] = k <= FLOAT_SUM_K ? lp : (float)lpd;
     }
     block_done_words(done_words, done_value, n);
 }
@@ -547,15 +554,25 @@ __global__ __launch_bounds__(256) void gaussian_loss_kernel(float *__restrict__ 
     if (active) {
         const int64_t src = idx ? ring_row(idx[row], cfg.ring_base, cfg.ring_cap) : row;  // idx == null: per-row data already gathered
         float *yr = y + row * ld;
-        float mean[MAX_K], sd[MAX_K], x[MAX_K];
+        const float *xr = actions + src * k;
         float lp = 0.f, ent = 0.f;
+        if (k <= FLOAT_SUM_K) {
 #pragma unroll 4
-        for (int j = 0; j < k; ++j) {
-            mean[j] = yr[j];
-            sd[j] = yr[k + j] * cfg.var_m + cfg.var_b;
-            x[j] = actions[src * k + j];
-            lp += gauss_logpdf(x[j], mean[j], sd[j]);
-            ent += 1.4189385332046727f + logf(sd[j]);  // 0.5 + 0.5*log(2*pi) + log(sd): Normal.entropy()
+            for (int j = 0; j < k; ++j) {
+                const float mean = yr[j], sd = yr[k + j] * cfg.var_m + cfg.var_b;
+                lp += gauss_logpdf(xr[j], mean, sd);
+                ent += 1.4189385332046727f + logf(sd);  // 0.5 + 0.5*log(2*pi) + log(sd): Normal.entropy()
+            }
+        } else {  // the same terms, summed in double (FLOAT_SUM_K)
+            double lpd = 0.0, entd = 0.0;
+#pragma unroll 4
+            for (int j = 0; j < k; ++j) {
+                const float mean = yr[j], sd = yr[k + j] * cfg.var_m + cfg.var_b;
+                lpd += (double)gauss_logpdf(xr[j], mean, sd);
+                entd += (double)(1.4189385332046727f + logf(sd));
+            }
+            lp = (float)lpd;
+            ent = (float)entd;
         }
         const float old = old_logp[src], adv = advantages[src];
         const float lr = lp - old;
@@ -564,13 +581,15 @@ __global__ __launch_bounds__(256) void gaussian_loss_kernel(float *__restrict__ 
         const float w = surrogate_weight(ratio, adv, cfg, smin);
         const float g_logp = cfg.mb_ratio * (-(adv * w * ratio) * cfg.inv_mb);
         const float g_ent = -cfg.mb_ratio * cfg.ent_coef * cfg.inv_mb / (float)k;  // d(-c_H * H)/d log sd
+        // (no per-row arrays, so any k: the second pass re-reads mean / sd / x -- element j is overwritten only after its own reads)
 #pragma unroll 4
         for (int j = 0; j < k; ++j) {
-            const float d = x[j] - mean[j];
-            const float s2 = sd[j] * sd[j];
-            const float d_mu = g_logp * d / s2;
-            const float d_sd = g_logp * (d * d / (s2 * sd[j]) - 1.f / sd[j]) + g_ent / sd[j];
             const float ym = yr[j], ys = yr[k + j];
+            const float sd = ys * cfg.var_m + cfg.var_b;
+            const float d = xr[j] - ym;
+            const float s2 = sd * sd;
+            const float d_mu = g_logp * d / s2;
+            const float d_sd = g_logp * (d * d / (s2 * sd) - 1.f / sd) + g_ent / sd;
             yr[j] = d_mu * (1.f - ym * ym);
             yr[k + j] = d_sd * cfg.var_m * (1.f - ys * ys);
         }
@@ -587,7 +606,7 @@ int launch_gaussian_loss(hipStream_t st, float *y, int64_t ld, int k, float *vou
                          const float *actions, const float *old_logp, const float *targets, const float *adv, int64_t mb,
                          const LossCfg &cfg, double *stats) {
     if (mb <= 0) return 0;
-    RLPPO_CHECK_ARG(k >= 1 && k <= MAX_K, "gaussian head: action dim %d not in [1, %d]", k, MAX_K);
+    RLPPO_CHECK_ARG(k >= 1, "gaussian head: action dim %d < 1", k);
     hipLaunchKernelGGL(gaussian_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, y, ld, k, vout, ldv, idx,
                        actions, old_logp, targets, adv, mb, cfg, stats);
     RLPPO_LAUNCH_CHECK();

@@ -1096,18 +1096,23 @@ def test_g9_gaussian_and_multidiscrete_act(L, golden):
 
 # ---------------------------------------------------------------------------------------- PPO minibatch
 def run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var=(0.1, 1.0),
-                  precision="fp32"):
+                  precision="fp32", ring=None):
+    """ring = base: the experience arrays are handed over as a ring of capacity len(obs_all) -- stored rotated so that logical row i
+    lives at physical row (i + base) % cap, with ring_base / ring_cap set; idx stays logical."""
     from rlgym_ppo_amd import _native as N
+    if ring is not None and precision in ("fp32", "bf16", "x3"):
+        rot = lambda x: np.roll(np.asarray(x), ring, axis=0)
+        obs_all, acts_all, old_all, tgt_all, adv_all = (rot(x) for x in (obs_all, acts_all, old_all, tgt_all, adv_all))
     if precision == "bf16":  # the bf16-operand forward (rlppo_set_update_precision): same call with the rounded weight images
         check(L, L.rlppo_set_update_precision(1))
         try:
-            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "bf16*")
+            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "bf16*", ring)
         finally:
             check(L, L.rlppo_set_update_precision(0))
     if precision == "x3":  # [r4] the split-bf16 hidden products (rlppo_set_update_precision(2)): same call with the three-plane images
         check(L, L.rlppo_set_update_precision(2))
         try:
-            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "x3*")
+            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "x3*", ring)
         finally:
             check(L, L.rlppo_set_update_precision(0))
     P_, V_ = Net(L, pol), Net(L, val)
@@ -1143,6 +1148,8 @@ def run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_al
         a.pol_wb16, a.val_wb16 = (t.data_ptr() for t in imgs)
     a.states, a.ld_states, a.n_rows, a.actions = states.data_ptr(), states.shape[1], states.shape[0], acts.data_ptr()
     a.old_logp, a.targets, a.advantages, a.idx, a.mb = old.data_ptr(), tgt.data_ptr(), adv.data_ptr(), idxd.data_ptr(), mb
+    if ring is not None:
+        a.ring_base, a.ring_cap = ring, len(obs_all)
     a.clip_range, a.ent_coef, a.mb_ratio = clip, ent, mb_ratio
     a.var_m, a.var_b = nets.var_map(*var)
     a.stats, a.workspace, a.ws_bytes = stats.data_ptr(), ws.data_ptr(), ws.numel()

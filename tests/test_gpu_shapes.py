@@ -1,5 +1,6 @@
 """Generality of the kernel paths: odd layer widths (padding to 32 / 64 / 96 / 128 / k*128), one hidden layer, wide
-discrete heads (EPL = 8 and 32 register variants of the wave-per-row kernels), tiny and ragged batches, empty calls."""
+discrete heads (the 16-lane kernel up to its full 128 columns, EPL = 8 and 32 register variants of the wave-per-row kernels up to
+2048 columns, an argument error beyond), tiny and ragged batches, empty calls."""
 import ctypes
 
 import numpy as np
@@ -14,7 +15,8 @@ from test_gpu_kernels import L, Net, P, check, dev, relerr, run_minibatch, strea
 
 
 @pytest.mark.parametrize("d,hidden,A,n,mb", [(50, (100, 40), 300, 700, 333), (7, (33,), 5, 64, 64), (300, (130, 257, 64), 1500, 400, 129),
-                                             (107, (256, 256, 256), 90, 1300, 1100)])
+                                             (107, (256, 256, 256), 90, 1300, 1100), (64, (128,), 110, 900, 777), (40, (96, 64), 128, 600, 513),
+                                             (64, (128,), 2048, 700, 600)])
 def test_discrete_odd_shapes(L, d, hidden, A, n, mb):
     torch.manual_seed(d + A)
     pol = nets.init_mlp(d, hidden, A)
@@ -41,6 +43,22 @@ def test_discrete_odd_shapes(L, d, hidden, A, n, mb):
     got = run_minibatch(L, "discrete", pol, val, obs, oact.numpy(), old, tgt, adv, idx, 0.2, 0.005, 1.0)
     fp64_gate.gate(L, "discrete", pol, val, obs[idx], oact.numpy()[idx], old[idx], adv[idx], tgt[idx], 0.2, 0.005, 1.0, got,
                    label=f"odd shape d={d} hidden={hidden} A={A}")
+
+
+def test_discrete_head_wider_than_the_loss_kernel_is_an_argument_error(L):
+    """2049 actions pad to 2176 outputs, beyond the 2048 columns of discrete_loss_kernel<32>: the minibatch call reports it (with the
+    library's error text) before anything is enqueued: the call never reaches its pass."""
+    torch.manual_seed(8)
+    pol, val = nets.init_mlp(32, (64,), 2049), nets.init_mlp(32, (64,), 1)
+    rs = np.random.RandomState(8)
+    n = 300
+    obs = rs.randn(n, 32).astype(np.float32)
+    acts = rs.randint(0, 2049, n).astype(np.float32)
+    passes = L.rlppo_dbg_counter(2)
+    with pytest.raises(AssertionError, match="padded width 2176 too large"):
+        run_minibatch(L, "discrete", pol, val, obs, acts, np.full(n, -7.6, np.float32), rs.randn(n).astype(np.float32),
+                      rs.randn(n).astype(np.float32), np.arange(n), 0.2, 0.005, 1.0)
+    assert L.rlppo_dbg_counter(2) == passes
 
 
 def test_single_row_and_empty_calls(L):

@@ -197,3 +197,69 @@ def test_init_consumes_rng_like_the_reference(golden):
         assert torch.equal(w, rw) and torch.equal(b, rb)
     for (w, b), (rw, rb) in zip(val, nets.params_from_state(g, "v0.")):
         assert torch.equal(w, rw) and torch.equal(b, rb)
+
+
+def _analytic_vs_autograd(head, pol, val, obs, acts, old, adv, tgt, var_range):
+    """minibatch_analytic against minibatch_autograd run on float64 tensors: the same ATen op sequence, differentiated by autograd, at
+    the precision of the hand-derived formulas -- so a wrong term shows at its own size, not hidden under float32 rounding (the
+    four-term Gaussian log-density at sd = 0.05 loses ~1e-5 of its ratio in float32 alone).  Tolerance 1e-9, far inside the 2e-5 of
+    the fixture checks."""
+    D64 = lambda t: torch.as_tensor(np.asarray(t), dtype=torch.float64)
+    p64 = lambda ps: [(w.double(), b.double()) for w, b in ps]
+    args = (head, p64(pol), p64(val), D64(obs), D64(acts), D64(old), D64(adv), D64(tgt), 0.2, 0.005, 0.5, var_range)
+    r = ppo.minibatch_autograd(*args)
+    a = ppo.minibatch_analytic(*args)
+    for key in ("entropy", "kl", "policy_loss", "value_loss"):
+        assert abs(a[key] - r[key]) <= 1e-9 * max(abs(r[key]), 1e-3), (key, a[key], r[key])
+    assert abs(a["clip_fraction"] - r["clip_fraction"]) < 1e-7  # (the reference's mean of a .float() mask: a float32 number)
+    assert relerr(a["logp"], r["logp"]) < 1e-9
+    for (aw, ab), (gw, gb) in zip(a["grad_policy"] + a["grad_value"], r["grad_policy"] + r["grad_value"]):
+        assert relerr(aw, gw) < 1e-9 and relerr(ab, gb) < 1e-9, (relerr(aw, gw), relerr(ab, gb))
+    return r
+
+
+@pytest.mark.parametrize("k", [1, 3, 40])
+def test_analytic_gaussian_widths_var_range_and_saturated_sd(k):
+    """The float64 hand-derived Gaussian gradients (the GPU gates' yardstick) against autograd at widths the fixtures never had, a
+    non-default var range, sd units whose tanh is saturated (sd == var_min exactly, 1 - y^2 == 0) on every row, clamped actions
+    and ratios beyond both clip edges."""
+    torch.manual_seed(k)
+    rs = np.random.RandomState(k)
+    n, d, var = 300, 24, (0.05, 2.0)
+    pol, val = nets.init_mlp(d, (32, 32), 2 * k), nets.init_mlp(d, (32,), 1)
+    w, b = pol[-1]
+    b = b.clone()
+    b[k] = -30.0
+    pol = pol[:-1] + [(w, b)]
+    obs = rs.randn(n, d).astype(np.float32)
+    with torch.no_grad():
+        assert (nets.mlp(pol, obs, out_act="tanh")[:, k] == -1.0).all()
+        mean, std = nets.gauss_out(pol, obs, *var)
+        eps = rs.randn(n, k).astype(np.float32) * 3
+        eps[: n // 10] *= 10
+        act, logp = nets.gauss_sample(mean, std, T(eps))
+    assert (act.abs() == 1.0).any()
+    old = (logp.numpy() + 0.3 * rs.randn(n)).astype(np.float32)
+    r = _analytic_vs_autograd("gaussian", pol, val, obs, act.numpy(), old, rs.randn(n).astype(np.float32), rs.randn(n).astype(np.float32),
+                              var)
+    ratio = np.exp(r["logp"].numpy().astype(np.float64) - old)
+    assert (ratio < 0.8).any() and (ratio > 1.2).any()
+
+
+def test_analytic_multidiscrete_saturated_logits():
+    """... and the multi-discrete gradients with logits scaled to +-30 (near one-hot heads) and actions of tiny probability."""
+    torch.manual_seed(2)
+    rs = np.random.RandomState(2)
+    n, d = 300, 24
+    pol, val = nets.init_mlp(d, (32, 32), 21), nets.init_mlp(d, (32,), 1)
+    obs = rs.randn(n, d).astype(np.float32)
+    with torch.no_grad():
+        s = 30.0 / nets.mlp(pol, obs).abs().max().item()
+        pol = pol[:-1] + [(pol[-1][0] * s, pol[-1][1] * s)]
+        lsm, _ = nets.md_dist(pol, obs)
+        act = (T(rs.rand(n, 8)) * T(np.array(nets.MD_BINS))).long()
+        logp = lsm.gather(-1, act[..., None]).squeeze(-1).sum(-1)
+    assert logp.min() < -50
+    old = (logp.numpy() + np.where(rs.rand(n) < 0.5, -0.5, 0.5)).astype(np.float32)
+    _analytic_vs_autograd("multidiscrete", pol, val, obs, act.numpy().astype(np.float32), old, rs.randn(n).astype(np.float32),
+                          rs.randn(n).astype(np.float32), (0.1, 1.0))
