@@ -35,7 +35,7 @@ extern "C" {
  * the matching pop have default visibility (`nm -D` shows them and nothing else of the library's own; tests/test_abi_and_layout.py). */
 #pragma GCC visibility push(default)
 
-#define RLPPO_ABI_VERSION 6
+#define RLPPO_ABI_VERSION 7
 #define RLPPO_MAX_LAYERS 16
 
 #define RLPPO_OK 0
@@ -285,6 +285,15 @@ typedef struct rlppo_minibatch_args {
     double *stats;                /* [RLPPO_N_STATS] device accumulators, += */
     void *workspace;
     size_t ws_bytes;
+    /* [ABI 7] options beyond the reference; zero / NULL = the reference's update ("Options beyond the reference") */
+    const float *adv_norm;        /* device {mean, scale} of the current batch (rlppo_adv_stats): the surrogate reads
+                                     (A - mean) * scale instead of A; NULL = the stored advantages */
+    float value_clip;             /* > 0: Stable-Baselines3's clipped value prediction, v_old = fl32(target - A) (the buffer holds
+                                     V + A and A), v_pred = v_old + clamp(v - v_old, -c, c), loss (v_pred - target)^2; 0 = off */
+    double *kl_slots;             /* this pass's region of rlppo_kl_slots_doubles(mb) doubles: [0] <- workgroups of the policy loss
+                                     launch, [1] <- mb_ratio, [2 + w] <- workgroup w's sum of the RLPPO_STAT_KL term (read by
+                                     rlppo_kl_gate); NULL = not armed */
+    const uint32_t *stop_word;    /* device; once non-zero, the pass adds nothing to `stats`; NULL = never */
 } rlppo_minibatch_args;
 
 #define RLPPO_STAT_ENTROPY 0     /* += entropy of this minibatch (mean over rows)            ppo_learner.py:184 */
@@ -309,6 +318,42 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *args);
  * (one add per element and launch), so they may overlap; each launch is short (50-100 us at 65,536 rows), and overlapping
  * chains fill the CUs that one chain's ramp-up and tail leave idle. */
 int rlppo_ppo_join(void *stream);
+
+/* [ABI 7] rlppo_minibatch_args.kl_slots: doubles one pass of `mb` rows needs (the policy loss launch's widest grid + 2). */
+int64_t rlppo_kl_slots_doubles(int64_t mb);
+
+/* [ABI 7] Advantage normalisation of one batch (Stable-Baselines3's normalize_advantage, over the ref's batch = one optimiser step):
+ * out[0] <- mean, out[1] <- 1 / (std + 1e-8) of advantages[idx[0 .. n)] (logical rows mapped through the ring as in
+ * rlppo_ppo_minibatch), std the unbiased (n - 1) deviation; n == 1: out = {0, 1} (the row is used as it is).  One launch: sums of
+ * (A - A_first) and its square in double per workgroup, the last arriving workgroup adds the slots in a fixed order
+ * (bit-reproducible; a constant batch gives exactly mean = A, scale * (A - mean) = 0).  ws: RLPPO_ADV_STATS_WS_BYTES of device
+ * memory zeroed once by its owner (every call leaves it armed). */
+#define RLPPO_ADV_STATS_WS_BYTES 4096
+int rlppo_adv_stats(void *stream, const int64_t *idx, int64_t n, const float *advantages, int64_t ring_base, int64_t ring_cap,
+                    float *out, void *ws);
+
+/* [ABI 7] The target-KL gate of one optimiser step.  KL_b = sum over the batch's passes of mb_ratio x (sum of the pass's
+ * kl_slots), added in a fixed order (bit-reproducible).
+ *   phase 0 (one rank): decide from KL_b;
+ *   phase 1 (several ranks, before the gradient exchange): write KL_b as two floats hi + lo to exchange[0..1], no decision;
+ *   phase 2 (after the exchange): decide from (double)exchange[0] + (double)exchange[1], the sum over the ranks.
+ * Deciding: if *stop_word == 0 and KL_b > threshold, *stop_word <- batch + 1 (it is never cleared by the call).  Phases 0 and 2
+ * then store *stop_word to host_words[0] and done_value to host_words[1], with release semantics at system scope
+ * (rlppo_host_wait_words polls it).  host_words is HOST-VISIBLE (pinned) memory.  The optimiser step of the batch passes the same
+ * stop word as rlppo_opt_net.skip_word. */
+typedef struct rlppo_kl_gate_args {
+    const double *kl_slots;   /* the batch's pass regions, one every slot_stride doubles */
+    int64_t slot_stride;
+    int32_t n_passes;
+    int32_t phase;
+    double threshold;         /* 1.5 x target_kl */
+    float *exchange;
+    uint32_t *stop_word;      /* device */
+    uint32_t batch;
+    uint32_t *host_words;     /* pinned [2] */
+    uint32_t done_value;
+} rlppo_kl_gate_args;
+int rlppo_kl_gate(void *stream, const rlppo_kl_gate_args *args);
 
 /* clip_grad_norm_(max_norm) + torch.optim.Adam.step() on one flat arena (ppo_learner.py:187-193).
  * Hyper-parameters are doubles (python floats in the reference); `step` is the 1-based Adam step count of
@@ -344,6 +389,8 @@ typedef struct rlppo_opt_net {
     double *gnorm2;       /* receives the squared gradient norm before clipping */
     double max_norm, lr, beta1, beta2, eps;
     int64_t step;         /* 1-based Adam step count of THIS update */
+    const uint32_t *skip_word;  /* [ABI 7] device; non-zero when the call runs: it touches no parameter, moment or packed image of
+                                   this network (both forms; rlppo_kl_gate's stop word); NULL = never skip */
 } rlppo_opt_net;
 int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws);
 

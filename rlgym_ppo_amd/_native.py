@@ -11,13 +11,14 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_siz
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RLPPO_LIB") or os.path.join(HERE, "librlppo.so")  # RLPPO_LIB: an alternative build (A/B of compile-time variants)
-ABI_VERSION = 6
+ABI_VERSION = 7
 COMM_ID_BYTES = 128  # RLPPO_COMM_ID_BYTES
 MAX_LAYERS = 16
 N_STATS = 8
 OPT_SYNC_BYTES = 16384  # RLPPO_OPT_SYNC_BYTES
 OPT_SYNC_TIMEOUT_WORD = 2  # uint32 index of the barrier-timeout counter in the sync block
 REPORT_WS_BYTES = 4096  # RLPPO_REPORT_WS_BYTES
+ADV_STATS_WS_BYTES = 4096  # RLPPO_ADV_STATS_WS_BYTES
 REPORT_OUT_DOUBLES = N_STATS + 4  # RLPPO_REPORT_OUT_DOUBLES
 EXP_LINK_HEADER = 64  # RLPPO_EXP_LINK_HEADER
 MAX_SLOTS = 8
@@ -38,7 +39,7 @@ class OptNet(ctypes.Structure):
         ("params", c_void_p), ("grads", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
         ("packed", c_void_p), ("gnorm2", c_void_p),
         ("max_norm", c_double), ("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double),
-        ("step", c_int64),
+        ("step", c_int64), ("skip_word", c_void_p),
     ]
 
 
@@ -76,6 +77,15 @@ class MinibatchArgs(ctypes.Structure):
         ("ring_base", c_int64), ("ring_cap", c_int64),
         ("clip_range", c_float), ("ent_coef", c_float), ("mb_ratio", c_float), ("var_m", c_float), ("var_b", c_float),
         ("stats", c_void_p), ("workspace", c_void_p), ("ws_bytes", c_size_t),
+        ("adv_norm", c_void_p), ("value_clip", c_float), ("kl_slots", c_void_p), ("stop_word", c_void_p),
+    ]
+
+
+class KlGateArgs(ctypes.Structure):
+    """struct rlppo_kl_gate_args (include/rlppo.h)."""
+    _fields_ = [
+        ("kl_slots", c_void_p), ("slot_stride", c_int64), ("n_passes", c_int32), ("phase", c_int32), ("threshold", c_double),
+        ("exchange", c_void_p), ("stop_word", c_void_p), ("batch", c_uint32), ("host_words", c_void_p), ("done_value", c_uint32),
     ]
 
 
@@ -127,6 +137,9 @@ SIGNATURES = {
     "rlppo_minibatch_workspace_bytes_for": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
     "rlppo_ppo_minibatch": (c_int32, [c_void_p, POINTER(MinibatchArgs)]),
     "rlppo_ppo_join": (c_int32, [c_void_p]),
+    "rlppo_kl_slots_doubles": (c_int64, [c_int64]),
+    "rlppo_adv_stats": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "rlppo_kl_gate": (c_int32, [c_void_p, POINTER(KlGateArgs)]),
     "rlppo_clip_adam": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double,
                                   c_double, c_double, c_double, c_int64, c_void_p]),
     "rlppo_clip_adam_pack2": (c_int32, [c_void_p, POINTER(OptNet), POINTER(OptNet), c_void_p]),

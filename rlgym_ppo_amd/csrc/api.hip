@@ -967,6 +967,7 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
                         a->old_logp && a->targets && a->advantages && a->idx && a->stats && a->workspace,
                     "ppo_minibatch: null pointer");
     RLPPO_CHECK_ARG(val.L[val.n_layers - 1].out == 1, "ppo_minibatch: critic must have one output");
+    RLPPO_CHECK_ARG(a->value_clip >= 0.f && a->value_clip < INFINITY, "ppo_minibatch: value_clip=%g", (double)a->value_clip);
     RLPPO_CHECK_ARG(pol.L[0].in == val.L[0].in, "ppo_minibatch: policy and critic observe different sizes");
     RLPPO_CHECK_ARG(a->ld_states >= pol.L[0].pin && a->ld_states % 4 == 0, "ppo_minibatch: ld_states=%ld < %d",
                     (long)a->ld_states, pol.L[0].pin);
@@ -1198,13 +1199,17 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
         cfg.var_b = a->var_b;
         cfg.ring_base = ring_base;
         cfg.ring_cap = ring_cap;
+        cfg.adv_norm = a->adv_norm;
+        cfg.vclip = a->value_clip;
+        cfg.kl_slots = a->kl_slots;
+        cfg.stop_word = a->stop_word;
         float *pout = pact[H];
         const int64_t ldp = pol.L[H].pout;
         if (!fold_v) {
             rc = head_forward(hs, val, val_w, xv, ldx, mb, 0, vout);
             if (rc) return rc;
         }
-        rc = launch_value_loss(hs, vout, ldv, nullptr, g_tgt, mb, cfg, a->stats);
+        rc = launch_value_loss(hs, vout, ldv, nullptr, g_tgt, g_adv, mb, cfg, a->stats);
         if (rc) return rc;
         // The critic's head kernels are matrix-vector products: HBM-bound, like the policy's loss kernel, unlike the policy head's
         // GEMMs.  Ordered so that the two HBM-bound stretches do not meet: critic forward + loss beside the policy head's forward
@@ -1306,9 +1311,13 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
     cfg.var_b = a->var_b;
     cfg.ring_base = ring_base;
     cfg.ring_cap = ring_cap;
+    cfg.adv_norm = a->adv_norm;
+    cfg.vclip = a->value_clip;
+    cfg.kl_slots = a->kl_slots;
+    cfg.stop_word = a->stop_word;
     float *pout = pact[pol.n_layers - 1], *vout = vact[val.n_layers - 1];
     const int64_t ldp = pol.L[pol.n_layers - 1].pout, ldv = v_folded ? 1 : val.L[val.n_layers - 1].pout;
-    rc = launch_value_loss(side, vout, ldv, nullptr, g_tgt, mb, cfg, a->stats);
+    rc = launch_value_loss(side, vout, ldv, nullptr, g_tgt, g_adv, mb, cfg, a->stats);
     if (rc) return rc;
     float *vjoint = nullptr;  // the loss kernels' joint form (policy + value in one launch) is not used by this entry point
     if (a->head == RLPPO_HEAD_DISCRETE)
@@ -1386,7 +1395,9 @@ int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_
     double *gn[2];
     int64_t n[2];
     float max_norm[2], step_size[2], bc2_sqrt[2], omb1[2], beta2[2], omb2[2], eps[2];
+    const unsigned *skip[2];
     for (int k = 0; k < 2; ++k) {
+        skip[k] = d[k]->skip_word;
         int rc = make_layout(d[k]->dims, d[k]->n_layers, &nets[k]);
         if (rc) return rc;
         RLPPO_CHECK_ARG(d[k]->params && d[k]->grads && d[k]->exp_avg && d[k]->exp_avg_sq && d[k]->packed && d[k]->gnorm2 &&
@@ -1403,7 +1414,25 @@ int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_
         eps[k] = (float)d[k]->eps;
     }
     return launch_clip_adam_pack2((hipStream_t)stream, nets, p, g, m, v, packed, gn, n, max_norm, step_size, bc2_sqrt, omb1, beta2,
-                                  omb2, eps, sync_ws);
+                                  omb2, eps, sync_ws, skip);
+}
+
+int64_t rlppo_kl_slots_doubles(int64_t mb) { return kl_slots_doubles(mb); }
+
+int rlppo_adv_stats(void *stream, const int64_t *idx, int64_t n, const float *advantages, int64_t ring_base, int64_t ring_cap,
+                    float *out, void *ws) {
+    RLPPO_CHECK_ARG(n >= 1 && idx && advantages && out && ws, "adv_stats: bad argument");
+    const int64_t cap = ring_cap > 0 ? ring_cap : INT64_MAX, base = ring_cap > 0 ? ring_base : 0;
+    RLPPO_CHECK_ARG(base >= 0 && base < cap, "adv_stats: ring_base=%ld not in [0, ring_cap=%ld)", (long)ring_base, (long)ring_cap);
+    return launch_adv_stats((hipStream_t)stream, idx, n, advantages, base, cap, out, ws);
+}
+
+int rlppo_kl_gate(void *stream, const rlppo_kl_gate_args *a) {
+    RLPPO_CHECK_ARG(a && a->kl_slots && a->n_passes >= 0 && a->slot_stride >= 3 && a->phase >= 0 && a->phase <= 2 && a->stop_word,
+                    "kl_gate: bad argument");
+    RLPPO_CHECK_ARG(a->phase == 0 || a->exchange, "kl_gate: phases 1 and 2 need the exchange words");
+    RLPPO_CHECK_ARG(a->phase == 1 || a->host_words, "kl_gate: host_words missing");
+    return launch_kl_gate((hipStream_t)stream, *a);
 }
 
 int rlppo_learn_report(void *stream, const rlppo_report_args *a) {

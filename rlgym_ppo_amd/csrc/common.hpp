@@ -204,6 +204,11 @@ struct LossCfg {
     float clip, clip_lo, clip_hi, ent_coef, mb_ratio, inv_mb;
     float var_m, var_b;
     int64_t ring_base, ring_cap;  // ExperienceBuffer ring: logical row i lives at physical row (i + ring_base) mod ring_cap
+    // [ABI 7] options beyond the reference (rlppo_minibatch_args): all off = the reference's loss, instruction for instruction
+    const float *adv_norm = nullptr;      // {mean, scale}: the surrogate reads (A - mean) * scale
+    float vclip = 0.f;                    // > 0: clipped value prediction around v_old = target - A
+    double *kl_slots = nullptr;           // per-workgroup sums of the KL term of the policy loss launch (rlppo_kl_gate)
+    const unsigned *stop_word = nullptr;  // non-zero: the launch adds nothing to the report statistics
 };
 // logical -> physical row of the ring-resident experience (i < cap, base < cap: one conditional subtraction)
 __host__ __device__ __forceinline__ int64_t ring_row(int64_t i, int64_t base, int64_t cap) {
@@ -218,8 +223,9 @@ int launch_gaussian_sample(hipStream_t, const float *, int64_t, int64_t, int, co
                            unsigned *done_words = nullptr, unsigned done_value = 0);
 int launch_multidiscrete_sample(hipStream_t, const float *, int64_t, int64_t, const float *, int64_t *, float *,
                                 unsigned *done_words = nullptr, unsigned done_value = 0);
-int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const int64_t *idx, const float *targets, int64_t mb,
+int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const int64_t *idx, const float *targets, const float *adv, int64_t mb,
                       const LossCfg &cfg, double *stats);
+int64_t kl_slots_doubles(int64_t mb);  // rlppo_kl_slots_doubles
 constexpr int64_t DISCRETE_LOSS_MAX_LD = 64 * 32;  // padded logits per row of the widest discrete loss kernel (one wave, 32 per lane)
 int launch_discrete_loss(hipStream_t, float *, int64_t, int, float *, int64_t, const int64_t *, const float *, const float *,
                          const float *, const float *, int64_t, const LossCfg &, double *);
@@ -276,7 +282,10 @@ int launch_clip_adam(hipStream_t, float *p, float *g, float *m, float *v, int64_
 int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *p, float *const *g, float *const *m, float *const *v,
                            float *const *packed, double *const *gnorm2, const int64_t *n, const float *max_norm,
                            const float *step_size, const float *bc2_sqrt, const float *omb1, const float *beta2, const float *omb2,
-                           const float *eps, void *sync_ws = nullptr);
+                           const float *eps, void *sync_ws = nullptr, const unsigned *const *skip = nullptr);
+int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float *adv, int64_t ring_base, int64_t ring_cap, float *out,
+                     void *ws);                             // [ABI 7] rlppo_adv_stats
+int launch_kl_gate(hipStream_t st, const rlppo_kl_gate_args &a);  // [ABI 7] rlppo_kl_gate
 int launch_welford(hipStream_t st, const float *x, int64_t ld, int64_t n, int d, void *mean, void *m2, long long count0, int state_f64);
 int launch_welford_merge(hipStream_t st, int d, void *mean, void *m2, long long count, const float *omean, const float *om2,
                          long long ocount, int state_f64);

@@ -217,8 +217,11 @@ __device__ __forceinline__ float surrogate_weight(float ratio, float adv, const 
     return s1 < s2 ? 1.f : (s1 > s2 ? inr : 0.5f + 0.5f * inr);
 }
 
-// block-level accumulation of per-row statistics into the double accumulators
-__device__ __forceinline__ void block_stats_add(double *stats, const float (&v)[5], bool active) {
+// block-level accumulation of per-row statistics into the double accumulators.  [ABI 7] kl_slots (the policy loss launches of an
+// armed pass): the workgroup's KL sum -- the value it adds to stats[KL] -- also lands in slot 2 + blockIdx.x, fixed for a given
+// grid, so rlppo_kl_gate adds the same numbers in the same order every run; a set stop word keeps the launch out of the report.
+__device__ __forceinline__ void block_stats_add(double *stats, const float (&v)[5], bool active, const LossCfg &c,
+                                                double *kl_slots = nullptr) {
     __shared__ float red[5][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -230,13 +233,32 @@ __device__ __forceinline__ void block_stats_add(double *stats, const float (&v)[
     if (threadIdx.x < 5) {
         const int k = threadIdx.x;
         const double s = (double)red[k][0] + (double)red[k][1] + (double)red[k][2] + (double)red[k][3];
-        atomicAdd(stats + k, s);
+        if (k == RLPPO_STAT_KL && kl_slots) {
+            kl_slots[2 + blockIdx.x] = s;
+            if (blockIdx.x == 0) {
+                kl_slots[0] = (double)gridDim.x;
+                kl_slots[1] = (double)c.mb_ratio;
+            }
+        }
+        if (!(c.stop_word && *c.stop_word)) atomicAdd(stats + k, s);
     }
 }
 
-// value loss for one row: writes dL/dv in place, returns (v - t)^2
-__device__ __forceinline__ float value_row(float *vout_row, float target, const LossCfg &c) {
+// [ABI 7] the advantage the surrogate sees: the stored one, or (A - mean) * scale of the batch (rlppo_adv_stats)
+__device__ __forceinline__ float surrogate_adv(float adv, const LossCfg &c) { return c.adv_norm ? (adv - c.adv_norm[0]) * c.adv_norm[1] : adv; }
+
+// value loss for one row: writes dL/dv in place, returns (v - t)^2.  [ABI 7] vclip > 0: Stable-Baselines3's clipped prediction
+// v_pred = v_old + clamp(v - v_old, -c, c) around v_old = target - A (the buffer's target is V + A), loss (v_pred - t)^2, gradient
+// where |v - v_old| <= c (torch.clamp passes it at its bounds)
+__device__ __forceinline__ float value_row(float *vout_row, float target, float adv, const LossCfg &c) {
     const float v = vout_row[0];
+    if (c.vclip > 0.f) {
+        const float v_old = target - adv;
+        const float dv = v - v_old;
+        const float d = (v_old + fminf(fmaxf(dv, -c.vclip), c.vclip)) - target;
+        vout_row[0] = fabsf(dv) <= c.vclip ? c.mb_ratio * (2.f * d * c.inv_mb) : 0.f;
+        return d * d;
+    }
     const float d = v - target;
     vout_row[0] = c.mb_ratio * (2.f * d * c.inv_mb);
     return d * d;
@@ -276,7 +298,7 @@ __global__ __launch_bounds__(256) void discrete_loss_kernel(float *__restrict__ 
         ent = wave_sum(ent);
         lpa = wave_sum(lpa);  // exactly one lane holds a non-zero term
         pca = wave_sum(pca);
-        const float old = old_logp[src], adv = advantages[src];
+        const float old = old_logp[src], adv_raw = advantages[src], adv = surrogate_adv(adv_raw, cfg);
         const float lr = lpa - old;
         const float ratio = expf(lr);
         float smin;
@@ -308,10 +330,10 @@ __global__ __launch_bounds__(256) void discrete_loss_kernel(float *__restrict__ 
             st[RLPPO_STAT_KL] += ((ratio - 1.f) - lr) * cfg.inv_mb;
             st[RLPPO_STAT_CLIPFRAC] += (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
             st[RLPPO_STAT_PLOSS] += -smin * cfg.inv_mb;
-            if (vout) st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[src], cfg) * cfg.inv_mb;
+            if (vout) st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[src], adv_raw, cfg) * cfg.inv_mb;
         }
     }
-    block_stats_add(stats, st, true);
+    block_stats_add(stats, st, true, cfg, cfg.kl_slots);
 }
 
 // ---- 16 lanes per row (padded width <= 128): a wave works on 4 rows at once, a lane holds 8 CONSECUTIVE logits (two
@@ -365,7 +387,7 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
                 p[4 + e] = z1[e];
             }
         }
-        const float old = old_logp[src], adv = advantages[src];
+        const float old = old_logp[src], adv_raw = advantages[src], adv = surrogate_adv(adv_raw, cfg);
         const int a = (int)actions[src];  // acts.long() of a float-encoded index (discrete_policy.py:71)
         float mx = -INFINITY;
 #pragma unroll
@@ -433,31 +455,39 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
             st[RLPPO_STAT_KL] += ((ratio - 1.f) - lr) * cfg.inv_mb;
             st[RLPPO_STAT_CLIPFRAC] += (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
             st[RLPPO_STAT_PLOSS] += -smin * cfg.inv_mb;
-            if (vout) st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[src], cfg) * cfg.inv_mb;
+            if (vout) st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[src], adv_raw, cfg) * cfg.inv_mb;
         }
     }
-    block_stats_add(stats, st, true);
+    block_stats_add(stats, st, true, cfg, cfg.kl_slots);
 }
 
 // Value loss on its own (value_estimator + ppo_learner.py:163-166: MSE(vals, target_values)): v -> d loss / d v in place,
 // VLOSS statistic.  A separate launch so that the critic's launch chain never has to meet the policy's between the
 // forward and the backward pass: the two chains only join at the end of the minibatch.
 __global__ __launch_bounds__(256) void value_loss_kernel(float *__restrict__ vout, int64_t ldv, const int64_t *__restrict__ idx,
-                                                         const float *__restrict__ targets, int64_t mb, LossCfg cfg,
-                                                         double *__restrict__ stats) {
+                                                         const float *__restrict__ targets, const float *__restrict__ advantages,
+                                                         int64_t mb, LossCfg cfg, double *__restrict__ stats) {
     float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < mb; row += (int64_t)gridDim.x * 256)
-        st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[idx ? ring_row(idx[row], cfg.ring_base, cfg.ring_cap) : row], cfg) * cfg.inv_mb;
-    block_stats_add(stats, st, true);
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < mb; row += (int64_t)gridDim.x * 256) {
+        const int64_t src = idx ? ring_row(idx[row], cfg.ring_base, cfg.ring_cap) : row;
+        st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[src], cfg.vclip > 0.f ? advantages[src] : 0.f, cfg) * cfg.inv_mb;
+    }
+    block_stats_add(stats, st, true, cfg);
 }
 
-int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const int64_t *idx, const float *targets, int64_t mb,
+int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const int64_t *idx, const float *targets, const float *adv, int64_t mb,
                       const LossCfg &cfg, double *stats) {
     if (mb <= 0) return 0;
+    RLPPO_CHECK_ARG(!(cfg.vclip > 0.f) || adv, "value loss: clipping needs the advantages");
     dim3 grid((unsigned)(cdiv(mb, 256) < 1024 ? cdiv(mb, 256) : 1024));
-    hipLaunchKernelGGL(value_loss_kernel, grid, dim3(256), 0, st, vout, ldv, idx, targets, mb, cfg, stats);
+    hipLaunchKernelGGL(value_loss_kernel, grid, dim3(256), 0, st, vout, ldv, idx, targets, adv, mb, cfg, stats);
     RLPPO_LAUNCH_CHECK();
     return 0;
+}
+
+int64_t kl_slots_doubles(int64_t mb) {  // grids: discrete <= 2048 workgroups, gaussian / multi-discrete cdiv(mb, 256)
+    const int64_t g = cdiv(mb > 0 ? mb : 1, 256);
+    return 2 + (g > 2048 ? g : 2048);
 }
 
 int launch_discrete_loss(hipStream_t st, float *logits, int64_t ld, int A, float *vout, int64_t ldv, const int64_t *idx,
@@ -574,7 +604,7 @@ __global__ __launch_bounds__(256) void gaussian_loss_kernel(float *__restrict__ 
             lp = (float)lpd;
             ent = (float)entd;
         }
-        const float old = old_logp[src], adv = advantages[src];
+        const float old = old_logp[src], adv_raw = advantages[src], adv = surrogate_adv(adv_raw, cfg);
         const float lr = lp - old;
         const float ratio = expf(lr);
         float smin;
@@ -597,9 +627,9 @@ __global__ __launch_bounds__(256) void gaussian_loss_kernel(float *__restrict__ 
         st[RLPPO_STAT_KL] = ((ratio - 1.f) - lr) * cfg.inv_mb;
         st[RLPPO_STAT_CLIPFRAC] = (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
         st[RLPPO_STAT_PLOSS] = -smin * cfg.inv_mb;
-        st[RLPPO_STAT_VLOSS] = vout ? value_row(vout + row * ldv, targets[src], cfg) * cfg.inv_mb : 0.f;
+        st[RLPPO_STAT_VLOSS] = vout ? value_row(vout + row * ldv, targets[src], adv_raw, cfg) * cfg.inv_mb : 0.f;
     }
-    block_stats_add(stats, st, active);
+    block_stats_add(stats, st, active, cfg, cfg.kl_slots);
 }
 
 int launch_gaussian_loss(hipStream_t st, float *y, int64_t ld, int k, float *vout, int64_t ldv, const int64_t *idx,
@@ -704,7 +734,7 @@ __global__ __launch_bounds__(256) void multidiscrete_loss_kernel(float *__restri
             act[h] = (int)actions[src * 8 + h];
             lp += ls[s + act[h]];
         }
-        const float old = old_logp[src], adv = advantages[src];
+        const float old = old_logp[src], adv_raw = advantages[src], adv = surrogate_adv(adv_raw, cfg);
         const float lr = lp - old;
         const float ratio = expf(lr);
         float smin;
@@ -724,9 +754,9 @@ __global__ __launch_bounds__(256) void multidiscrete_loss_kernel(float *__restri
         st[RLPPO_STAT_KL] = ((ratio - 1.f) - lr) * cfg.inv_mb;
         st[RLPPO_STAT_CLIPFRAC] = (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
         st[RLPPO_STAT_PLOSS] = -smin * cfg.inv_mb;
-        st[RLPPO_STAT_VLOSS] = vout ? value_row(vout + row * ldv, targets[src], cfg) * cfg.inv_mb : 0.f;
+        st[RLPPO_STAT_VLOSS] = vout ? value_row(vout + row * ldv, targets[src], adv_raw, cfg) * cfg.inv_mb : 0.f;
     }
-    block_stats_add(stats, st, active);
+    block_stats_add(stats, st, active, cfg, cfg.kl_slots);
 }
 
 int launch_multidiscrete_loss(hipStream_t st, float *logits, int64_t ld, float *vout, int64_t ldv, const int64_t *idx,

@@ -488,13 +488,16 @@ struct OptNet {
     int64_t n;
     float max_norm, step_size, bc2_sqrt, omb1, beta2, omb2, eps;
     PackJobs jobs;
+    const unsigned *skip;  // [ABI 7] rlppo_opt_net.skip_word: non-zero = leave this network as it is (NULL: never)
 };
+__device__ __forceinline__ bool opt_skipped(const OptNet &N) { return N.skip && *N.skip; }
 struct OptPair {
     OptNet net[2];
 };
 
 __global__ __launch_bounds__(256) void sqnorm2_kernel(OptPair o) {
     const int k = blockIdx.y;
+    if (opt_skipped(o.net[k])) return;
     const float *g = o.net[k].g;
     const int64_t n = o.net[k].n;
     double acc = 0.0;
@@ -512,6 +515,7 @@ __global__ __launch_bounds__(256) void sqnorm2_kernel(OptPair o) {
 
 __global__ __launch_bounds__(256) void adam_pack2_kernel(OptPair o) {
     const OptNet &N = o.net[blockIdx.y];
+    if (opt_skipped(N)) return;
     const float total = (float)sqrt(*N.gnorm2);
     float coef = N.max_norm / (total + 1e-6f);
     coef = coef > 1.f ? 1.f : coef;
@@ -707,6 +711,8 @@ __global__ __launch_bounds__(256) void adam_fused_kernel(OptPair o, FusedSync *_
     }
     __syncthreads();
     if (!s_ok) return;  // given up: parameters, moments and gradients stay as they were (the timeout word says so)
+    // [ABI 7] a skipped network still took part in the barrier (every workgroup arrives, whatever the other network does)
+    if (opt_skipped(N)) return;
     // ---- phase 2: adam_pack2_kernel, element for element
     const float total = s_total;
     float coef = N.max_norm / (total + 1e-6f);
@@ -733,7 +739,7 @@ static void fill_jobs(const NetLayout &net, PackJobs *jobs) {
 int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *p, float *const *g, float *const *m, float *const *v,
                            float *const *packed, double *const *gnorm2, const int64_t *n, const float *max_norm,
                            const float *step_size, const float *bc2_sqrt, const float *omb1, const float *beta2, const float *omb2,
-                           const float *eps, void *sync_ws) {
+                           const float *eps, void *sync_ws, const unsigned *const *skip) {
     OptPair o;
     int64_t nmax = 0;
     for (int k = 0; k < 2; ++k) {
@@ -741,6 +747,7 @@ int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *
         N.p = p[k]; N.g = g[k]; N.m = m[k]; N.v = v[k]; N.packed = packed[k]; N.gnorm2 = gnorm2[k]; N.n = n[k];
         N.max_norm = max_norm[k]; N.step_size = step_size[k]; N.bc2_sqrt = bc2_sqrt[k]; N.omb1 = omb1[k]; N.beta2 = beta2[k];
         N.omb2 = omb2[k]; N.eps = eps[k];
+        N.skip = skip ? skip[k] : nullptr;
         fill_jobs(nets[k], &N.jobs);
         nmax = n[k] > nmax ? n[k] : nmax;
     }
@@ -864,6 +871,120 @@ __global__ __launch_bounds__(256) void learn_report_kernel(rlppo_report_args r) 
 
 int launch_learn_report(hipStream_t st, const rlppo_report_args &r) {
     hipLaunchKernelGGL(learn_report_kernel, dim3(REPORT_BLOCKS), dim3(256), 0, st, r);
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------- [ABI 7] options beyond the reference
+// Advantage statistics of one batch (rlppo_adv_stats): the ticket pattern of learn_report_kernel.  Every workgroup sums
+// (A - A_first) and (A - A_first)^2 in double over its grid-stride share of the batch's rows (shifted sums: no cancellation, and a
+// constant batch gives exactly zero), parks the pair in its slot and takes a ticket; the last arriver adds the slots in slot order.
+namespace {
+constexpr int ADV_BLOCKS = 128;
+struct AdvWs {
+    unsigned tickets;
+    unsigned pad[3];
+    double partial[ADV_BLOCKS][2];
+};
+static_assert(sizeof(AdvWs) <= RLPPO_ADV_STATS_WS_BYTES, "adv stats workspace");
+}  // namespace
+
+__global__ __launch_bounds__(256) void adv_stats_kernel(const int64_t *__restrict__ idx, int64_t n, const float *__restrict__ adv,
+                                                        int64_t ring_base, int64_t ring_cap, float *__restrict__ out, AdvWs *__restrict__ ws) {
+    const double k0 = (double)adv[ring_row(idx[0], ring_base, ring_cap)];
+    double s[2] = {0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double d = (double)adv[ring_row(idx[i], ring_base, ring_cap)] - k0;
+        s[0] += d;
+        s[1] += d * d;
+    }
+    __shared__ double red[4][2];
+    __shared__ int last;
+    for (int k = 0; k < 2; ++k) {
+        double v = s[k];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ws->partial[blockIdx.x][0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+        ws->partial[blockIdx.x][1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+        __threadfence();
+        last = atomicAdd(&ws->tickets, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    // the last arriver's threads fetch the slots side by side, thread 0 adds them in slot order (as learn_report_kernel)
+    __shared__ double slots[ADV_BLOCKS][2];
+    __threadfence();
+    if (threadIdx.x < 2 * gridDim.x)
+        slots[threadIdx.x >> 1][threadIdx.x & 1] = __hip_atomic_load(&ws->partial[threadIdx.x >> 1][threadIdx.x & 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double t0 = 0.0, t1 = 0.0;
+    for (unsigned b = 0; b < gridDim.x; ++b) {
+        t0 += slots[b][0];
+        t1 += slots[b][1];
+    }
+    float mean = 0.f, scale = 1.f;  // one row: used as it is
+    if (n > 1) {
+        const double m = t0 / (double)n;
+        double var = (t1 - t0 * m) / (double)(n - 1);
+        var = var > 0.0 ? var : 0.0;
+        mean = (float)(k0 + m);
+        scale = (float)(1.0 / (sqrt(var) + 1e-8));
+    }
+    out[0] = mean;
+    out[1] = scale;
+    __hip_atomic_store(&ws->tickets, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float *adv, int64_t ring_base, int64_t ring_cap, float *out,
+                     void *ws) {
+    const int64_t blocks = cdiv(n, 256 * 2) < ADV_BLOCKS ? cdiv(n, 256 * 2) : ADV_BLOCKS;  // the row gathers are latency-bound: spread them
+    hipLaunchKernelGGL(adv_stats_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, st, idx, n, adv, ring_base, ring_cap, out,
+                       reinterpret_cast<AdvWs *>(ws));
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
+// The target-KL gate (rlppo_kl_gate): one workgroup.  Thread t adds slots t, t + 256, ... of every pass region in order, a fixed
+// shuffle tree and a fixed sum over the four waves follow, the pass totals are weighted by their mb_ratio in pass order.
+__global__ __launch_bounds__(256) void kl_gate_kernel(rlppo_kl_gate_args g) {
+    __shared__ double red[4];
+    double kl = 0.0;
+    for (int p = 0; p < g.n_passes; ++p) {
+        const double *r = g.kl_slots + (int64_t)p * g.slot_stride;
+        const int nw = (int)r[0];
+        double a = 0.0;
+        for (int w = threadIdx.x; w < nw; w += 256) a += r[2 + w];
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) a += __shfl_xor(a, s);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+        __syncthreads();
+        kl += r[1] * ((red[0] + red[1]) + (red[2] + red[3]));
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    if (g.phase == 1) {  // this rank's share travels in the tail of the exchanged gradient tensor
+        const float hi = (float)kl;
+        g.exchange[0] = hi;
+        g.exchange[1] = (float)(kl - (double)hi);
+        return;
+    }
+    if (g.phase == 2) kl = (double)g.exchange[0] + (double)g.exchange[1];
+    unsigned stop = *g.stop_word;
+    if (stop == 0 && kl > g.threshold) {
+        stop = g.batch + 1;
+        *g.stop_word = stop;
+    }
+    __hip_atomic_store(g.host_words, stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    __hip_atomic_store(g.host_words + 1, g.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+int launch_kl_gate(hipStream_t st, const rlppo_kl_gate_args &a) {
+    hipLaunchKernelGGL(kl_gate_kernel, dim3(1), dim3(256), 0, st, a);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }

@@ -40,7 +40,8 @@ class Learner(object):
             checkpoints_save_folder=None, add_unix_timestamp: bool = True, checkpoint_load_folder="latest",
             save_every_ts: int = 1_000_000, instance_launch_delay=None, random_seed: int = 123,
             n_checkpoints_to_keep: int = 5, shm_buffer_size: int = 8192, device: str = "auto",
-            vector_env: bool = False, per_feature_obs_standardization: bool = False):
+            vector_env: bool = False, per_feature_obs_standardization: bool = False,
+            ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
         assert env_create_function is not None, "MUST PROVIDE A FUNCTION TO CREATE RLGYM FUNCTIONS TO INITIALIZE RLGYM-PPO"
         if checkpoints_save_folder is None:
             checkpoints_save_folder = os.path.join("data", "checkpoints", "rlgym-ppo-run")
@@ -101,7 +102,9 @@ class Learner(object):
             obs_space_size, act_space_size, device=self.device, batch_size=ppo_batch_size,
             mini_batch_size=ppo_minibatch_size, n_epochs=ppo_epochs, continuous_var_range=continuous_var_range,
             policy_type=action_space_type, policy_layer_sizes=policy_layer_sizes, critic_layer_sizes=critic_layer_sizes,
-            policy_lr=policy_lr, critic_lr=critic_lr, clip_range=ppo_clip_range, ent_coef=ppo_ent_coef)
+            policy_lr=policy_lr, critic_lr=critic_lr, clip_range=ppo_clip_range, ent_coef=ppo_ent_coef,
+            normalize_advantages=ppo_normalize_advantages, value_clip_range=ppo_value_clip_range, target_kl=ppo_target_kl,
+            max_grad_norm=ppo_max_grad_norm)
         self.agent.policy = self.ppo_learner.policy
 
         self.config = {

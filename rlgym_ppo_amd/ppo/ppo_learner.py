@@ -14,6 +14,10 @@ state_dict layouts).  What changed underneath:
   * data-parallel: the minibatch slices of a batch are dealt round-robin to the ranks of the default
     torch.distributed group and ONE RCCL all-reduce of the flat gradient arena precedes clipping -- algebraically
     the reference's own gradient accumulation (ppo_learner.py:134-193) with slice j living on rank j % world.
+
+Four opt-in options go beyond the reference (trailing keyword arguments; DESIGN.md, "Options beyond the reference"): per-batch
+advantage normalisation, Stable-Baselines3's clipped value loss, a target-KL stop of the optimiser steps and the gradient-norm
+limit.  Their defaults are the reference's update, launch for launch.
 """
 import ctypes
 import os
@@ -117,7 +121,7 @@ class OptimizerBarrierTimeout(RuntimeError):
 class PPOLearner(object):
     def __init__(self, obs_space_size, act_space_size, policy_type, policy_layer_sizes, critic_layer_sizes,
                  continuous_var_range, batch_size, n_epochs, policy_lr, critic_lr, clip_range, ent_coef, mini_batch_size,
-                 device):
+                 device, normalize_advantages=False, value_clip_range=None, target_kl=None, max_grad_norm=MAX_GRAD_NORM):
         self.device = device
         self._dev = require_gpu(device)
         N.lib()  # fail here, loudly, if the HIP library is missing
@@ -169,7 +173,9 @@ class PPOLearner(object):
 
         # one contiguous gradient buffer [policy | critic] so that data-parallel needs a single all-reduce
         pa, va = self.policy.arena, self.value_net.arena
-        self._grad_all = torch.zeros(pa.n_flat + va.n_flat, dtype=torch.float32, device=self._dev)
+        # (+ 2 floats: with target_kl set, the exchanged tensor carries this rank's KL partial of the batch in its tail)
+        self._grad_ex = torch.zeros(pa.n_flat + va.n_flat + 2, dtype=torch.float32, device=self._dev)
+        self._grad_all = self._grad_ex[:pa.n_flat + va.n_flat]
         pa.grad = self._grad_all[:pa.n_flat]
         va.grad = self._grad_all[pa.n_flat:]
         pa.bind()
@@ -198,6 +204,13 @@ class PPOLearner(object):
         # [r5] update precision of THIS learner (rlppo_minibatch_args.precision): None = the process default chosen with
         # engine.set_update_precision, else "fp32" / "bf16" / "x3" -- two learners of one process may differ
         self.update_precision = None
+        # options beyond the reference (plain attributes, read by every learn(); None / False = the reference's update)
+        self.normalize_advantages = normalize_advantages
+        self.value_clip_range = value_clip_range
+        self.target_kl = target_kl
+        self.max_grad_norm = max_grad_norm
+        self._opt = None      # their device state, allocated on first use
+        self._kl_seq = 0
 
     # --------------------------------------------------------------------------------------------- learn
     def _minibatch_args(self, exp, rank=0, world=1):
@@ -245,6 +258,41 @@ class PPOLearner(object):
         a.workspace, a.ws_bytes = self._slot_ws[0], nbytes
         return a
 
+    def _check_options(self):
+        if self.value_clip_range is not None and not float(self.value_clip_range) > 0:
+            raise ValueError(f"value_clip_range must be > 0 or None, got {self.value_clip_range!r}")
+        if self.target_kl is not None and not float(self.target_kl) > 0:
+            raise ValueError(f"target_kl must be > 0 or None, got {self.target_kl!r}")
+        if self.max_grad_norm is None or not float(self.max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm must be > 0, got {self.max_grad_norm!r}")
+        if self.target_kl is not None and not self.fused_optimizer_step:
+            raise ValueError("target_kl needs the library's optimiser step (RLPPO_FUSED_OPT=1): the FusedAdam.step form cannot skip a step "
+                             "on the device")
+
+    def _option_state(self, kl_slot_doubles=0):
+        """Device buffers of the options: advantage statistics {mean, scale} + their ticket block, the stop word, the KL slots,
+        pinned decision words (4 batches x {stop, done})."""
+        if self._opt is None:
+            self._opt = dict(adv=torch.zeros(2, dtype=torch.float32, device=self._dev),
+                             adv_ws=torch.zeros(N.ADV_STATS_WS_BYTES, dtype=torch.uint8, device=self._dev),
+                             stop=torch.zeros(1, dtype=torch.int32, device=self._dev),
+                             kl=torch.zeros(0, dtype=torch.float64, device=self._dev),
+                             host=torch.zeros(8, dtype=torch.int32).pin_memory())
+            self._opt["host_np"] = self._opt["host"].numpy().view(np.uint32)
+        o = self._opt
+        if o["kl"].numel() < kl_slot_doubles:
+            o["kl"] = torch.zeros(kl_slot_doubles, dtype=torch.float64, device=self._dev)
+        return o
+
+    def _kl_decision(self, g, done_value):
+        """The stop word after batch g's gate (0 = running, else trigger + 1): waits for the gate's pinned words."""
+        L, words = N.lib(), self._opt["host"].data_ptr() + 8 * (g % 4)
+        if L.rlppo_host_wait_words(words + 4, 1, done_value, 5000) != 0:
+            torch.cuda.current_stream(self._dev).synchronize()
+            if L.rlppo_host_wait_words(words + 4, 1, done_value, 1000000) != 0:
+                raise RuntimeError("rlppo_kl_gate: the decision word did not arrive")
+        return int(self._opt["host_np"][2 * (g % 4)])
+
     def learn(self, exp):
         """Compute PPO updates with an experience buffer; returns the reference's report dictionary
         (ppo_learner.py:225-234)."""
@@ -265,9 +313,14 @@ class PPOLearner(object):
         drives it with torch.distributed's all-reduce; dp.run_virtual_ranks drives the generators of N replicas in ONE process
         (the 8-way partition of BASELINE configs[3] on a one-GPU box).  With world == 1 it never yields."""
         L = N.lib()
+        self._check_options()
         pa, va = self.policy.arena, self.value_net.arena
         B, MB = self.batch_size, self.mini_batch_size
         n_slices = B // MB
+        max_norm = float(self.max_grad_norm)
+        kl_on = self.target_kl is not None
+        stopped_at = None   # target_kl: the batch whose KL stopped this learn() (its step and every later one not applied)
+        gate_values = {}    # batch -> done value of its gate
 
         # [r6] nothing is enqueued before the first pass that the pass does not need: the report sums were zeroed by the previous
         # learn()'s report kernel, and the "before" copies of the parameters (ppo_learner.py:111-116) follow the first pass's launches
@@ -289,15 +342,41 @@ class PPOLearner(object):
                 raise ValueError("experience buffer action width does not match the policy head")
             args = self._minibatch_args(exp, rank, world)
             st = stream_ptr()
+            runs = fuse_runs(slices_for_rank(n_slices, rank, world), self.max_fused_minibatches)
+            if self.value_clip_range is not None:
+                args.value_clip = float(self.value_clip_range)
+            if self.normalize_advantages or kl_on:
+                stride = int(L.rlppo_kl_slots_doubles(self._fused_rows))
+                o = self._option_state(stride * max(len(runs), 1) if kl_on else 0)
+                if self.normalize_advantages:
+                    args.adv_norm = o["adv"].data_ptr()
+                if kl_on:
+                    o["stop"].zero_()
+                    args.stop_word = o["stop"].data_ptr()
+                    gate = N.KlGateArgs()
+                    gate.kl_slots, gate.slot_stride, gate.n_passes = o["kl"].data_ptr(), stride, len(runs)
+                    gate.threshold = 1.5 * float(self.target_kl)
+                    gate.exchange = self._grad_ex.data_ptr() + 4 * self._grad_all.numel()
+                    gate.stop_word = o["stop"].data_ptr()
             # The legacy-MT19937 permutation is inherently serial host work.  The buffer's shuffle pipeline draws it on
             # helper threads several epochs ahead (also across learn() calls) and uploads every index vector on its own
             # stream (engine.LegacyPermutation / DeviceIndexRing): here an epoch only orders the stream after that copy.
             # With 8 ranks the GPU share of an epoch is ~1.1 ms; the serial stream phase (~0.8 ms per 512k indices) is
             # the only part of the shuffle that cannot be spread over threads.
             for epoch in range(self.n_epochs):
+                if stopped_at is not None:   # a stopped learn() still consumes every epoch's permutation
+                    exp.epoch_indices()
+                    continue
                 idx_dev = exp.epoch_indices_device(refill=False)   # (the look-ahead is topped up behind the epoch's first launches)
                 refilled = False
                 for b in range(n_batches):
+                    g = epoch * n_batches + b
+                    if kl_on and g >= 2:
+                        # at most one undecided batch beyond the executing one: batch g waits for the decision of batch g - 2
+                        v = self._kl_decision(g - 2, gate_values[g - 2])
+                        if v:
+                            stopped_at = v - 1
+                            break
                     if not grads_zero:
                         self._grad_all.zero_()
                     grads_zero = False
@@ -309,7 +388,12 @@ class PPOLearner(object):
                     if self._x3:    # re-split them (two small launches per covered layer)
                         pa.ensure_packed_x3()
                         va.ensure_packed_x3()
-                    for k, (j, cnt) in enumerate(fuse_runs(slices_for_rank(n_slices, rank, world), self.max_fused_minibatches)):
+                    if self.normalize_advantages:   # mean and 1 / (std + 1e-8) of this batch's advantages, before its first pass
+                        N.check(L.rlppo_adv_stats(st, idx_dev.data_ptr() + 8 * b * B, B, args.advantages, args.ring_base, args.ring_cap,
+                                                  args.adv_norm, self._opt["adv_ws"].data_ptr()))
+                    for k, (j, cnt) in enumerate(runs):
+                        if kl_on:
+                            args.kl_slots = gate.kl_slots + 8 * k * stride
                         args.slot = k % self.n_slots
                         args.workspace = self._slot_ws[args.slot]
                         off = b * B + j * MB
@@ -327,26 +411,53 @@ class PPOLearner(object):
                         self._before[1].copy_(va.flat)
                         have_before = True
                     n_minibatch_iterations += n_slices
+                    if kl_on:
+                        self._kl_seq = self._kl_seq % 0x7FFFFFFF + 1
+                        gate_values[g] = self._kl_seq
+                        gate.batch, gate.done_value = g, self._kl_seq
+                        gate.host_words = self._opt["host"].data_ptr() + 8 * (g % 4)
+                        if world > 1:  # this rank's KL share rides in the tail of the ONE exchange of the step
+                            gate.phase = 1
+                            N.check(L.rlppo_kl_gate(st, ctypes.byref(gate)))
                     if world > 1:
-                        yield self._grad_all  # summed over the ranks (RCCL over xGMI) before clipping
+                        yield self._grad_ex if kl_on else self._grad_all  # summed over the ranks (RCCL over xGMI) before clipping
+                    if kl_on:
+                        gate.phase = 2 if world > 1 else 0
+                        N.check(L.rlppo_kl_gate(st, ctypes.byref(gate)))
                     if self.grad_probe is not None:  # test hook: the batch gradient clip_grad_norm_ / Adam are about to see
                         self.grad_probe(self._grad_all)
                     if self.fused_optimizer_step:
                         # both clip + Adam steps, the re-pack of both weight copies and the next batch's zero_grad: 3 stream
                         # operations instead of 9 (csrc/optim.hip)
-                        dv = self.value_optimizer.fused_descriptor(MAX_GRAD_NORM)
-                        dp_ = self.policy_optimizer.fused_descriptor(MAX_GRAD_NORM)
+                        dv = self.value_optimizer.fused_descriptor(max_norm)
+                        dp_ = self.policy_optimizer.fused_descriptor(max_norm)
+                        if kl_on:   # (a step after the stop touches nothing: the gate's stop word)
+                            dv.skip_word = dp_.skip_word = gate.stop_word
                         N.check(L.rlppo_clip_adam_pack2(st, ctypes.byref(dv), ctypes.byref(dp_),
                                                         ptr(self._opt_sync) if self.one_launch_optimizer else None))
                         va.mark_repacked()
                         pa.mark_repacked()
                         grads_zero = True
                     else:
-                        self.value_optimizer.step(max_norm=MAX_GRAD_NORM)
-                        self.policy_optimizer.step(max_norm=MAX_GRAD_NORM)
+                        self.value_optimizer.step(max_norm=max_norm)
+                        self.policy_optimizer.step(max_norm=max_norm)
                     n_iterations += 1
                 if not refilled:
                     exp.refill_shuffle()
+            if kl_on:
+                if stopped_at is None and n_iterations > 0:   # a trigger among the last two batches
+                    v = self._kl_decision(n_iterations - 1, gate_values[n_iterations - 1])
+                    stopped_at = v - 1 if v else None
+                if stopped_at is not None:
+                    # launches from the trigger on were skipped on the device: Adam's step counts rewind by them (as after a give-up),
+                    # the gradient arena holds the unapplied batches' sums, and only the evaluated batches' passes are in the report
+                    for opt in (self.policy_optimizer, self.value_optimizer):
+                        opt.step_count -= n_iterations - stopped_at
+                    n_iterations = stopped_at
+                    n_passes = len(runs) * (stopped_at + 1)
+                    n_minibatch_iterations = n_slices * (stopped_at + 1)
+                    self._grad_all.zero_()
+                    grads_zero = True
         else:
             for _ in range(self.n_epochs):
                 exp.epoch_indices()  # the reference consumes one permutation per epoch even if no batch fits
@@ -433,7 +544,7 @@ class PPOLearner(object):
         n_iter_r = max(n_iterations, 1)
         n_mb_r = max(float(stats[N.STAT_PASSES]), 1.0)
         policy_update_magnitude, critic_update_magnitude = float(stats[N.N_STATS]), float(stats[N.N_STATS + 1])
-        self.cumulative_model_updates += n_iter_r
+        self.cumulative_model_updates += n_iterations if kl_on else n_iter_r   # (with target_kl: applied steps only)
 
         report = {
             "PPO Batch Consumption Time": elapsed / n_iter_r,
@@ -445,6 +556,9 @@ class PPOLearner(object):
             "Policy Update Magnitude": policy_update_magnitude,
             "Value Function Update Magnitude": critic_update_magnitude,
         }
+        if kl_on:
+            report["PPO Optimizer Steps"] = n_iterations
+            report["KL Early Stopped"] = 1.0 if stopped_at is not None else 0.0
         if not grads_zero:  # the fused optimiser step leaves the arena zeroed
             self._grad_all.zero_()
         return report

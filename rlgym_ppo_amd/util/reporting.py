@@ -11,10 +11,20 @@ GROUPS = (
     ("Cumulative Model Updates", "Cumulative Timesteps"),
     ("Timesteps Collected",),
 )
+# keys of the options beyond the reference: printed (as one more group) only when the report has them -- PPOLearner adds them
+# when target_kl is set
+OPTIONAL_GROUPS = (
+    ("PPO Optimizer Steps", "KL Early Stopped"),
+)
 
 
 def _form_printable_groups(report):
-    return [{k: report[k] for k in keys} for keys in GROUPS]  # KeyError if the hot path forgot a key
+    groups = [{k: report[k] for k in keys} for keys in GROUPS]  # KeyError if the hot path forgot a key
+    for keys in OPTIONAL_GROUPS:
+        present = {k: report[k] for k in keys if k in report}
+        if present:
+            groups.append(present)
+    return groups
 
 
 def _fmt(val):
