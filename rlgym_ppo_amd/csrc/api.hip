@@ -97,22 +97,29 @@ static void x3_layout(const NetLayout &net, X3Layout *o) {
 
 static int g_fold_vhead = 1;  // rlppo_dbg_set(32, 0/1): a one-output head inside the last hidden layer's forward epilogue (update passes)
 
+// Where a first layer finds its rows: a row-major matrix x [n][ld], or -- rowtab != nullptr, the fused gather [r3] -- the
+// experience buffer's state matrix x (src_rows rows), row r of the pass being x[rowtab[r]].
+struct RowSource {
+    const float *x;
+    int64_t ld;
+    const unsigned *rowtab = nullptr;
+    int64_t src_rows = 0;
+};
+
 // Forward pass.  acts[l] receives the output of layer l ([n][pout_l]); for inference the caller passes two
 // ping-pong buffers, for training one buffer per layer (they are the saved activations of the backward pass).
 // Training only: bits[l] (may be null) receives the ReLU bitmask of hidden layer l and have_bits[l] says whether it was
 // written (csrc/gemm.hip, launch_gemm_nt_bits); backward() then masks dX with it instead of re-reading acts[l].
-// rowtab != nullptr: `obs` is the experience buffer's state matrix (src_rows rows) and row r of the batch is obs[rowtab[r]]
-// (the first layer fetches its rows through the table: nt_gather_ok must hold for it).
-static int forward(hipStream_t st, const NetLayout &net, const float *packed, const float *obs, int64_t ld_obs, int64_t n,
-                   int out_tanh, float *const *acts, int bf16_operands = 0, unsigned long long *const *bits = nullptr,
-                   bool *have_bits = nullptr, const unsigned *rowtab = nullptr, int64_t src_rows = 0, bool *head_folded = nullptr,
-                   const unsigned short *x3 = nullptr, bool head_prezeroed = false) {
+// in.rowtab != nullptr: the first layer fetches its rows through the table (nt_gather_ok must hold for it).
+static int forward(hipStream_t st, const NetLayout &net, const float *packed, const RowSource &in, int64_t n, int out_tanh,
+                   float *const *acts, int bf16_operands = 0, unsigned long long *const *bits = nullptr, bool *have_bits = nullptr,
+                   bool *head_folded = nullptr, const unsigned short *x3 = nullptr, bool head_prezeroed = false) {
     X3Layout xl;
     if (x3) x3_layout(net, &xl);
     if (have_bits)
         for (int l = 0; l < net.n_layers; ++l) have_bits[l] = false;
-    const float *x = obs;
-    int64_t ldx = ld_obs;
+    const float *x = in.x;
+    int64_t ldx = in.ld;
     // head_folded != nullptr (update passes): a one-output head may be computed in the epilogue of the hidden layer that feeds it
     // (NtDot, csrc/gemm.hip) -- acts[last] then holds the outputs COMPACT ([n], stride 1) and *head_folded says so
     const int hl = net.n_layers - 1;
@@ -143,11 +150,11 @@ static int forward(hipStream_t st, const NetLayout &net, const float *packed, co
                     dots[0].out = acts[hl];
                 }
                 rc = launch_gemm_nt_bits(st, x, ldx, packed + L.off_w, L.pin, packed + L.off_b, acts[l], L.pout, n, L.pout, L.pin,
-                                         EPI_BIAS_RELU, bits[l], l == 0 ? rowtab : nullptr, src_rows, nullptr, fold_here ? dots : nullptr);
+                                         EPI_BIAS_RELU, bits[l], l == 0 ? in.rowtab : nullptr, in.src_rows, nullptr, fold_here ? dots : nullptr);
                 if (rc == 0) have_bits[l] = true;
                 if (fold_here) *head_folded = rc == 0;  // (rc == -1: the layer has no bitmask form; the values stay zero-filled but unused)
             }
-            if (l == 0 && rowtab && rc != 0) {
+            if (l == 0 && in.rowtab && rc != 0) {
                 if (rc == -1) set_error("forward: the gathered first layer needs the bitmask form");
                 return rc == -1 ? RLPPO_ERR_ARG : rc;
             }
@@ -254,7 +261,7 @@ static int forward_pingpong(hipStream_t st, const NetLayout &net, const float *p
     float *acts[RLPPO_MAX_LAYERS];
     for (int l = 0; l < net.n_layers; ++l) acts[l] = (l & 1) ? b1 : b0;
     if (final_out) acts[net.n_layers - 1] = final_out;
-    int rc = forward(st, net, packed, obs, ld_obs, n, out_tanh, acts, bf16_operands);  // inference only
+    int rc = forward(st, net, packed, RowSource{obs, ld_obs}, n, out_tanh, acts, bf16_operands);  // inference only
     if (rc) return rc;
     *out = acts[net.n_layers - 1];
     *ld_out = net.L[net.n_layers - 1].pout;
@@ -665,11 +672,11 @@ static int g_group_dw = 1;  // rlppo_dbg_set(37, 0/1)
 struct DwList {
     TnProduct p[2 * RLPPO_MAX_LAYERS];
     int n = 0;
-    void add(const float *dY, int64_t ldy, int ny, const float *X, int64_t ldx, int kx, float *dW, float *db, int out, int in,
-             const unsigned *rowtab = nullptr, int64_t src_rows = 0) {
+    void add(const LayerLayout &L, const float *dY, const RowSource &X, float *grad) {  // dW / db of layer L = dY^T . X into grad
         TnProduct &q = p[n++];
-        q.dY = dY; q.ldy = ldy; q.ny_valid = ny; q.X = X; q.ldx = ldx; q.kx_valid = kx; q.dW = dW; q.db = db; q.out = out; q.in = in;
-        q.rowtab = rowtab; q.src_rows = src_rows;
+        q.dY = dY; q.ldy = L.pout; q.ny_valid = L.pout; q.X = X.x; q.ldx = X.ld; q.kx_valid = L.pin;
+        q.dW = grad + L.off_flat_w; q.db = grad + L.off_flat_b; q.out = L.out; q.in = L.in;
+        q.rowtab = X.rowtab; q.src_rows = X.src_rows;
     }
 };
 static bool dw_is_gemv(const NetLayout &net, int l) { return l == net.n_layers - 1 && l > 0 && gemv_head_ok(net.L[l].out, net.L[l].pin); }
@@ -686,26 +693,80 @@ static size_t tn_region_floats(const NetLayout &pol, const NetLayout &val, int64
     return chains > group ? chains : group;
 }
 
-static size_t train_ws_floats(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec) {
-    size_t per_row = 0;
-    for (int l = 0; l < pol.n_layers; ++l) per_row += pol.L[l].pout;
-    for (int l = 0; l < val.n_layers; ++l) per_row += val.L[l].pout;
-    int m = max_pout(pol) > max_pout(val) ? max_pout(pol) : max_pout(val);
-    per_row += (size_t)(pol.n_layers - 1 + val.n_layers - 1) * (size_t)m;  // one dX buffer per layer and net
-    per_row += (size_t)pol.L[0].pin;                                         // the gathered minibatch states
-    per_row += 4 + (size_t)pol.L[pol.n_layers - 1].pout;                      // gathered old log-prob, advantage, target, actions
-                                                                             // (act_dim <= the policy's output width) + the row table
-    size_t bits = 0;                                                         // ReLU bitmasks of the hidden layers (1/32 of h)
-    for (int l = 0; l + 1 < pol.n_layers; ++l) bits += nt_bits_floats(mb, pol.L[l].pout);
-    for (int l = 0; l + 1 < val.n_layers; ++l) bits += nt_bits_floats(mb, val.L[l].pout);
-    size_t b16 = 0;  // bf16 update precision: the gathered states, every hidden activation and its gradient as bf16 (2 B/element)
+// The workspace of one pass, region by region (plan_workspace).  Per network:
+struct NetWs {
+    float *act[RLPPO_MAX_LAYERS] = {};                // the saved output of every layer, [mb][pout]
+    float *dx[RLPPO_MAX_LAYERS] = {};                 // dL/d(act[l]) of every hidden layer, [mb][widest pout of both nets]
+    unsigned long long *bits[RLPPO_MAX_LAYERS] = {};  // the ReLU bitmask of every hidden layer that has that form (1/32 of act[l])
+    unsigned short *actb[RLPPO_MAX_LAYERS] = {};      // bf16 update precision: the hidden activations ...
+    unsigned short *dxb[RLPPO_MAX_LAYERS] = {};       // ... and their gradients as bf16
+    float *tn = nullptr;                              // the partial dW tiles of the net's chain
+};
+struct WsPlan {
+    NetWs pol, val;
+    size_t tn_floats = 0;  // the region from pol.tn on: both chains' partial buffers, one region for the grouped dW launch
+    float *states = nullptr;  // the gathered minibatch rows, [mb][policy pin]
+    float *g_old = nullptr, *g_adv = nullptr, *g_tgt = nullptr, *g_act = nullptr;  // the gathered per-row scalars (act_dim per row)
+    unsigned *rowtab = nullptr;  // the physical buffer row of every row of the pass (gather_meta_kernel)
+    unsigned short *states_b = nullptr;  // bf16 update precision: the gathered rows as bf16
+};
+// Pads in front of the two aligned regions: the bitmasks (8-byte words) and the bf16 region (16-byte loads).  The layout aligns
+// them from the address (the base is 256-byte aligned by contract); the size reserves the largest pad.
+constexpr size_t BITS_PAD_RESERVE = 2, B16_PAD_RESERVE = 4;
+// Lays out the workspace of a pass from `base` into *w and returns its size in floats: the size the host is told and the layout
+// the pass uses come from this one walk.
+static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec, void *base, WsPlan *w) {
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
+    const size_t rows = (size_t)mb;
+    size_t off = 0, slack = 0;  // floats from the base; the unused part of the pad reserves
+    auto take = [&](size_t floats) {
+        off += floats;
+        return reinterpret_cast<float *>(addr + (off - floats) * sizeof(float));
+    };
+    auto align = [&](size_t floats, size_t reserve) {  // the next region starts on a boundary of `floats` floats
+        const size_t pad = (floats - (addr / sizeof(float) + off) % floats) % floats;
+        off += pad;
+        slack += reserve - pad;
+    };
+    const NetLayout *nets[2] = {&pol, &val};
+    NetWs *ws[2] = {&w->pol, &w->val};
+    for (int i = 0; i < 2; ++i)
+        for (int l = 0; l < nets[i]->n_layers; ++l) ws[i]->act[l] = take(rows * nets[i]->L[l].pout);
+    const size_t m = max_pout(pol) > max_pout(val) ? max_pout(pol) : max_pout(val);
+    for (int i = 0; i < 2; ++i)
+        for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->dx[l] = take(rows * m);
+    w->tn_floats = tn_region_floats(pol, val, mb, prec);
+    w->pol.tn = take(w->tn_floats);
+    w->val.tn = w->pol.tn + tn_ws_floats(pol, mb, prec);
+    align(2, BITS_PAD_RESERVE);
+    for (int i = 0; i < 2; ++i)
+        for (int l = 0; l + 1 < nets[i]->n_layers; ++l) {
+            const size_t f = nt_bits_floats(mb, nets[i]->L[l].pout);
+            ws[i]->bits[l] = f ? reinterpret_cast<unsigned long long *>(take(f)) : nullptr;
+        }
+    w->states = take(rows * pol.L[0].pin);
+    w->g_old = take(rows);
+    w->g_adv = take(rows);
+    w->g_tgt = take(rows);
+    w->g_act = take(rows * pol.L[pol.n_layers - 1].pout);  // (every head's act_dim is at most the policy's output width)
+    w->rowtab = reinterpret_cast<unsigned *>(take(rows));
     if (prec == 1) {
-        size_t el = pol.L[0].pin;  // + per hidden layer: the activation and its gradient
-        for (int l = 0; l + 1 < pol.n_layers; ++l) el += 2 * (size_t)pol.L[l].pout;
-        for (int l = 0; l + 1 < val.n_layers; ++l) el += 2 * (size_t)val.L[l].pout;
-        b16 = (el * (size_t)mb + 1) / 2 + 4;
+        align(4, B16_PAD_RESERVE);
+        size_t el = pol.L[0].pin;  // bf16 elements per row: the gathered row, and per hidden layer the activation and its gradient
+        for (int i = 0; i < 2; ++i)
+            for (int l = 0; l + 1 < nets[i]->n_layers; ++l) el += 2 * (size_t)nets[i]->L[l].pout;
+        unsigned short *hb = reinterpret_cast<unsigned short *>(take((el * rows + 1) / 2));
+        auto take16 = [&](size_t n) {
+            hb += n;
+            return hb - n;
+        };
+        w->states_b = take16(rows * pol.L[0].pin);
+        for (int i = 0; i < 2; ++i)
+            for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->actb[l] = take16(rows * nets[i]->L[l].pout);
+        for (int i = 0; i < 2; ++i)
+            for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->dxb[l] = take16(rows * nets[i]->L[l].pout);
     }
-    return per_row * (size_t)mb + tn_region_floats(pol, val, mb, prec) + bits + b16 + 2;  // + one partial-tile buffer per chain (one region for the grouped launch)
+    return off + slack;
 }
 
 // update precision of a call: RLPPO_PRECISION_DEFAULT = what rlppo_set_update_precision chose for the process, else 1 + mode
@@ -719,26 +780,19 @@ size_t rlppo_minibatch_workspace_bytes_for(const int32_t *pol_dims, int32_t pol_
     NetLayout pol, val;
     int prec = 0;
     if (make_layout(pol_dims, pol_layers, &pol) || make_layout(val_dims, val_layers, &val) || resolve_precision(precision, &prec)) return 0;
-    return train_ws_floats(pol, val, mb > 0 ? mb : 0, prec) * sizeof(float) + 256;
+    WsPlan unused;
+    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused) * sizeof(float) + 256;
 }
 size_t rlppo_minibatch_workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims,
                                        int32_t val_layers, int64_t mb) {
     return rlppo_minibatch_workspace_bytes_for(pol_dims, pol_layers, val_dims, val_layers, mb, RLPPO_PRECISION_DEFAULT);
 }
 
-// How a chain's first layer finds its rows [r3].
-struct ChainCtx {
-    const unsigned *rowtab = nullptr;  // fused gather: row r of the pass is src[rowtab[r]] (first-layer dW)
-    const float *src = nullptr;
-    int64_t ld_src = 0, src_rows = 0;
-};
-
 // backward of one net: acts[l] = saved output of layer l, acts[last] holds dL/d(out) on entry; dx[l-1] receives
 // dL/d(acts[l-1]) = dY of layer l-1 (one buffer per layer: the dW launches read them later)
-static int backward(hipStream_t st, const NetLayout &net, const float *packed, const float *states, int64_t ld_states,
-                    int64_t mb, float *const *acts, float *const *dx, float *grad, float *tn_ws,
-                    unsigned long long *const *bits, const bool *have_bits, const ChainCtx &cx, bool head_folded = false,
-                    const unsigned short *x3 = nullptr, DwList *defer = nullptr) {
+static int backward(hipStream_t st, const NetLayout &net, const float *packed, const RowSource &in, int64_t mb, float *const *acts,
+                    float *const *dx, float *grad, float *tn_ws, unsigned long long *const *bits, const bool *have_bits,
+                    bool head_folded = false, const unsigned short *x3 = nullptr, DwList *defer = nullptr) {
     const int last = net.n_layers - 1;
     int rc = 0;
     X3Layout xl;
@@ -747,22 +801,16 @@ static int backward(hipStream_t st, const NetLayout &net, const float *packed, c
         const LayerLayout &L = net.L[l];
         const float *dY = l == last ? acts[last] : dx[l];
         const int64_t ld_hy = head_folded ? 1 : L.pout;  // stride of a one-output head's dY (compact when it was folded, forward())
-        const float *X = l > 0 ? acts[l - 1] : states;
-        const int64_t ldx = l > 0 ? net.L[l - 1].pout : ld_states;
+        const RowSource X = l > 0 ? RowSource{acts[l - 1], net.L[l - 1].pout} : in;
         const bool gemv = l == last && l > 0 && gemv_head_ok(L.out, L.pin);  // one-output head (gemv.hip)
         const size_t floats = tn_layer_floats(net, l, mb, 0);  // (fp32 / split-bf16 precisions: the bf16 one has backward_b16)
         if (gemv)
-            rc = launch_gemv_dw(st, dY, ld_hy, X, ldx, grad + L.off_flat_w, grad + L.off_flat_b, L.in, L.pin, mb, tn_ws, floats);
-        else if (defer && l == 0 && cx.rowtab)  // [r5] collected: launched with every other product of the pass once the chains have joined
-            defer->add(dY, L.pout, L.pout, cx.src, cx.ld_src, L.pin, grad + L.off_flat_w, grad + L.off_flat_b, L.out, L.in, cx.rowtab, cx.src_rows);
-        else if (defer)
-            defer->add(dY, L.pout, L.pout, X, ldx, L.pin, grad + L.off_flat_w, grad + L.off_flat_b, L.out, L.in);
-        else if (l == 0 && cx.rowtab)
-            rc = launch_gemm_tn(st, dY, L.pout, L.pout, cx.src, cx.ld_src, L.pin, grad + L.off_flat_w, grad + L.off_flat_b, L.out, L.in,
-                                mb, tn_ws, floats, cx.rowtab, cx.src_rows);
+            rc = launch_gemv_dw(st, dY, ld_hy, X.x, X.ld, grad + L.off_flat_w, grad + L.off_flat_b, L.in, L.pin, mb, tn_ws, floats);
+        else if (defer)  // [r5] collected: launched with every other product of the pass once the chains have joined
+            defer->add(L, dY, X, grad);
         else
-            rc = launch_gemm_tn(st, dY, L.pout, L.pout, X, ldx, L.pin, grad + L.off_flat_w, grad + L.off_flat_b, L.out, L.in, mb,
-                                tn_ws, floats);
+            rc = launch_gemm_tn(st, dY, L.pout, L.pout, X.x, X.ld, L.pin, grad + L.off_flat_w, grad + L.off_flat_b, L.out, L.in, mb,
+                                tn_ws, floats, X.rowtab, X.src_rows);
         if (rc) return rc;
         if (l == 0) break;
         // dX[mb][pin] = (dY[mb][pout] . W[pout][pin]) masked by relu'(acts[l-1]); B operand = W^T [pin][pout].  The mask is the
@@ -907,7 +955,6 @@ static int backward_b16(hipStream_t st, const NetLayout &net, const float *packe
 static int g_head_order = 1;  // rlppo_dbg_set(31, 0/1): the critic's output-layer backward waits for the policy's loss kernel (both HBM-bound)
 static int g_paired = 1;  // rlppo_dbg_set(29, 0 / 1 / 2): never / from PAIRED_MIN_ROWS rows / always (tests)
 constexpr int64_t PAIRED_MIN_ROWS = 262144;
-constexpr int64_t FUSED_GATHER_MIN_ROWS = 262144;
 static bool twin_ok(const NetLayout &p, const NetLayout &v, int64_t mb) {
     if (p.n_layers != v.n_layers || p.n_layers < 2) return false;
     for (int l = 0; l + 1 < p.n_layers; ++l) {
@@ -938,7 +985,7 @@ static int head_backward(hipStream_t st, const NetLayout &net, const float *pack
     if (!ld_dy) ld_dy = L.pout;  // (a one-output head folded into the last hidden layer's epilogue keeps its outputs compact: 1)
     int rc = 0;
     if (gemv) rc = launch_gemv_dw(st, dY, ld_dy, X, ldx, grad + L.off_flat_w, grad + L.off_flat_b, L.in, L.pin, mb, tn_ws, floats);
-    else if (defer) defer->add(dY, L.pout, L.pout, X, ldx, L.pin, grad + L.off_flat_w, grad + L.off_flat_b, L.out, L.in);
+    else if (defer) defer->add(L, dY, RowSource{X, ldx}, grad);
     else rc = launch_gemm_tn(st, dY, L.pout, L.pout, X, ldx, L.pin, grad + L.off_flat_w, grad + L.off_flat_b, L.out, L.in, mb, tn_ws, floats);
     if (rc) return rc;
     if (gemv) return launch_gemv_dx_bits(st, dY, ld_dy, packed + L.off_w, bits_prev, dx_prev, L.pin, L.pin, mb);
@@ -951,17 +998,272 @@ static int head_backward(hipStream_t st, const NetLayout &net, const float *pack
     return rc;
 }
 
-int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
-    RLPPO_CHECK_ARG(a != nullptr, "ppo_minibatch: null args");
+// [r3] fp32 precision: the four first-layer launches (two forwards, two dW) fetch their rows straight from the experience
+// buffer through the row table (the gather fused into the load stage) when their shapes have that form; the
+// separate gather pass into the workspace remains for the others.
+// [r5] ... from FUSED_GATHER_MIN_ROWS rows per pass: with the weight gradients grouped (section 4.6) a 65,536-row pass is 1 % FASTER
+// with the 10 us gather pass and contiguous first-layer operands than with rows fetched through the table inside four of its
+// launches (11.59 against 11.71 ms per 10-epoch learn() at the 8-rank share, tools/ab_update.py, profiles/r05_ab_update_final.txt);
+// at 524,288 rows per pass the two are equal and the fused form saves the 268 MB copy.  rlppo_dbg_set(26, 2): at every size (tests).
+constexpr int64_t FUSED_GATHER_MIN_ROWS = 262144;
+static RowSource first_layer_rows(const rlppo_minibatch_args &a, const NetLayout &pol, const NetLayout &val, int prec, const WsPlan &w) {
+    const int64_t src_rows = a.ring_cap > 0 ? a.ring_cap : a.n_rows;
+    auto gather_form = [&](const NetLayout &n) {
+        return n.n_layers > 1 && nt_gather_ok(a.ld_states, src_rows, n.L[0].pout, n.L[0].pin) && tn_gather_ok(a.ld_states, src_rows) &&
+               !(n.L[0].out > 64 && n.L[0].out <= 96 && !(n.L[0].in > 96 && n.L[0].in <= 112));
+    };
+    if (prec != 1 && (g_fused_gather == 2 || (g_fused_gather == 1 && a.mb >= FUSED_GATHER_MIN_ROWS)) && src_rows > 0 &&
+        gather_form(pol) && gather_form(val))
+        return RowSource{a.states, a.ld_states, w.rowtab, src_rows};
+    return RowSource{w.states, pol.L[0].pin};
+}
+
+// One validated call of rlppo_ppo_minibatch, as its forms see it
+struct Pass {
+    const rlppo_minibatch_args *a;
     NetLayout pol, val;
-    int rc = make_layout(a->pol_dims, a->pol_layers, &pol);
+    int64_t mb;
+    int prec;  // update precision: 0 fp32, 1 bf16, 2 split-bf16
+    int64_t ring_base, ring_cap;
+    WsPlan w;
+    RowSource rows;  // the first layers' operand
+    LossCfg cfg;
+    const float *pol_w, *val_w;  // the packed weights the products read (bf16 precision: their rounded images)
+    hipStream_t st, side;        // the policy's and the critic's chain (one stream: rlppo_dbg_set(4, 0))
+    DwList *defer;               // [r5] the grouped weight gradients, or null
+};
+
+static LossCfg loss_cfg(const rlppo_minibatch_args &a) {
+    LossCfg c;
+    c.clip = a.clip_range;
+    c.clip_lo = (float)(1.0 - (double)a.clip_range);
+    c.clip_hi = (float)(1.0 + (double)a.clip_range);
+    c.ent_coef = a.ent_coef;
+    c.mb_ratio = a.mb_ratio;
+    c.inv_mb = 1.0f / (float)a.mb;
+    c.var_m = a.var_m;
+    c.var_b = a.var_b;
+    c.adv_norm = a.adv_norm;
+    c.vclip = a.value_clip;
+    c.kl_slots = a.kl_slots;
+    c.stop_word = a.stop_word;
+    return c;
+}
+
+// the head's loss kernel on the policy's outputs, in place (the head was validated before the first launch)
+static int policy_loss(hipStream_t st, const Pass &p) {
+    const rlppo_minibatch_args &a = *p.a;
+    const int last = p.pol.n_layers - 1;
+    const LayerLayout &L = p.pol.L[last];
+    const WsPlan &w = p.w;
+    if (a.head == RLPPO_HEAD_DISCRETE)
+        return launch_discrete_loss(st, w.pol.act[last], L.pout, L.out, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
+    if (a.head == RLPPO_HEAD_GAUSSIAN)
+        return launch_gaussian_loss(st, w.pol.act[last], L.pout, L.out / 2, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
+    return launch_multidiscrete_loss(st, w.pol.act[last], L.pout, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
+}
+
+// The minibatch gather (experience_buffer.py:82-87), once for both nets: the per-row scalars, and the rows unless the first
+// layers fetch them through the row table
+static int gather(const Pass &p) {
+    const rlppo_minibatch_args &a = *p.a;
+    const WsPlan &w = p.w;
+    const int width = p.pol.L[0].pin;
+    float *const vout = w.val.act[p.val.n_layers - 1];
+    if (p.prec == 1) {  // the rows as bf16 too
+        // the fp32 form of the gathered rows only if a first layer takes the fp32 kernels (the predicates of forward_b16 / backward_b16)
+        auto lean0 = [](const NetLayout &n) {
+            return n.n_layers > 1 && nt_b16_ok(n.L[0].pout, n.L[0].pin, true) && tn_b16_ok(n.L[0].pout, n.L[0].pin);
+        };
+        const int rc = launch_gather_rows_round(p.st, a.states, a.ld_states, a.idx, lean0(p.pol) && lean0(p.val) ? nullptr : w.states,
+                                                w.states_b, width, p.mb, p.ring_base, p.ring_cap);
+        if (rc) return rc;
+    } else if (!p.rows.rowtab) {  // (the per-row scalars ride in the same launch)
+        GatherMeta gm;
+        gm.actions = a.actions; gm.old_logp = a.old_logp; gm.adv = a.advantages; gm.targets = a.targets;
+        gm.g_old = w.g_old; gm.g_adv = w.g_adv; gm.g_tgt = w.g_tgt; gm.g_act = w.g_act;
+        gm.zero_n = vout;
+        gm.act_dim = a.act_dim;
+        return launch_gather_rows(p.st, a.states, a.ld_states, a.idx, w.states, width, p.mb, p.ring_base, p.ring_cap, &gm);
+    }
+    // ... and writes the row table the fused first layers read.  ([r5] It also zeroes the first mb floats of the critic's output
+    // buffer: a folded value head accumulates into them; when the rows were gathered by a pass of their own, that launch has done
+    // all of this already.)
+    return launch_gather_meta(p.st, a.idx, a.actions, a.act_dim, a.old_logp, a.advantages, a.targets, w.g_act, w.g_old, w.g_adv, w.g_tgt,
+                              p.mb, p.ring_base, p.ring_cap, p.rows.rowtab ? w.rowtab : nullptr, vout);
+}
+
+// The paired pass ([r3] paired launches, above).  It joins the critic's stream itself, before the hidden layers' backward.
+static int paired_pass(const Pass &p, SlotBank &bk, int slot) {
+    const rlppo_minibatch_args &a = *p.a;
+    const NetLayout &pol = p.pol, &val = p.val;
+    const WsPlan &w = p.w;
+    const int64_t mb = p.mb;
+    const hipStream_t st = p.st, hs = p.side;
+    const int H = pol.n_layers - 1;  // hidden layers (the same number in both networks)
+    int rc;
+    // [r3] The critic's output layer is a dot product per row of activations this launch has in registers: folded into the last
+    // hidden layer's forward epilogue (NtDot) it costs no pass over the 4 x 256 B per row the matrix-vector kernel re-read
+    // (537 MB per 524,288-row pass, in the stretch of the pass that is HBM-bound).  Values land compact ([mb], stride 1).
+    const LayerLayout &Lvh = val.L[H];
+    const bool fold_v = g_fold_vhead && gemv_head_ok(Lvh.out, Lvh.pin) && val.L[H - 1].pout / 128 <= 2;
+    float *vout = w.val.act[H], *pout = w.pol.act[H];
+    const int64_t ldv = fold_v ? 1 : Lvh.pout;
+    const float *xp = p.rows.x, *xv = xp;
+    int64_t ldx = p.rows.ld;
+    for (int l = 0; l < H; ++l) {
+        const LayerLayout &Lp = pol.L[l], &Lv = val.L[l];
+        NtAlt alt;
+        alt.A = xv;
+        alt.B = p.val_w + Lv.off_w;
+        alt.bias = p.val_w + Lv.off_b;
+        alt.C = w.val.act[l];
+        alt.bits = w.val.bits[l];
+        NtDot dots[2];
+        const bool fold_here = fold_v && l == H - 1;
+        if (fold_here) {  // (vout was zeroed by gather_meta_kernel)
+            dots[1].w = p.val_w + Lvh.off_w;
+            dots[1].out = vout;
+            dots[1].b = p.val_w + Lvh.off_b;
+        }
+        rc = launch_gemm_nt_bits(st, xp, ldx, p.pol_w + Lp.off_w, Lp.pin, p.pol_w + Lp.off_b, w.pol.act[l], Lp.pout, mb, Lp.pout, Lp.pin,
+                                 EPI_BIAS_RELU, w.pol.bits[l], l == 0 ? p.rows.rowtab : nullptr, p.rows.src_rows, &alt,
+                                 fold_here ? dots : nullptr);
+        if (rc) {
+            if (rc == -1) set_error("paired pass: a hidden layer does not have the bitmask form");
+            return rc == -1 ? RLPPO_ERR_ARG : rc;
+        }
+        xp = w.pol.act[l];
+        xv = w.val.act[l];
+        ldx = Lp.pout;
+    }
+    // the two heads: forward, loss, output-layer backward -- critic on the side stream
+    if (hs != st) {
+        rc = order_after(hs, st, bk.ev_fork[slot]);
+        if (rc) return rc;
+    }
+    if (!fold_v) {
+        rc = head_forward(hs, val, p.val_w, xv, ldx, mb, 0, vout);
+        if (rc) return rc;
+    }
+    rc = launch_value_loss(hs, vout, ldv, w.g_tgt, w.g_adv, mb, p.cfg, a.stats);
     if (rc) return rc;
-    rc = make_layout(a->val_dims, a->val_layers, &val);
+    // The critic's head kernels are matrix-vector products: HBM-bound, like the policy's loss kernel, unlike the policy head's
+    // GEMMs.  Ordered so that the two HBM-bound stretches do not meet: critic forward + loss beside the policy head's forward
+    // GEMM, the critic's output-layer backward only after the policy's loss, beside the policy head's dW / dX GEMMs.
+    const bool ordered = g_head_order && hs != st;
+    if (!ordered) {
+        rc = head_backward(hs, val, p.val_w, vout, xv, mb, w.val.dx[H - 1], a.val_grad, w.val.tn, w.val.bits[H - 1], ldv, p.defer);
+        if (rc) return rc;
+    }
+    rc = head_forward(st, pol, p.pol_w, xp, ldx, mb, a.head == RLPPO_HEAD_GAUSSIAN, pout);
     if (rc) return rc;
-    const int64_t mb = a->mb;
+    rc = policy_loss(st, p);
+    if (rc) return rc;
+    if (ordered) {
+        rc = order_after(hs, st, bk.ev_mid[slot]);
+        if (rc) return rc;
+        rc = head_backward(hs, val, p.val_w, vout, xv, mb, w.val.dx[H - 1], a.val_grad, w.val.tn, w.val.bits[H - 1], ldv, p.defer);
+        if (rc) return rc;
+    }
+    rc = head_backward(st, pol, p.pol_w, pout, xp, mb, w.pol.dx[H - 1], a.pol_grad, w.pol.tn, w.pol.bits[H - 1], 0, p.defer);
+    if (rc) return rc;
+    if (hs != st) {
+        rc = order_after(st, hs, bk.ev_join[slot]);
+        if (rc) return rc;
+    }
+    // hidden layers, backward: dW (+ reduction) of both networks, then dX of both
+    for (int l = H - 1; l >= 0; --l) {
+        const LayerLayout &Lp = pol.L[l], &Lv = val.L[l];
+        const RowSource Xp = l > 0 ? RowSource{w.pol.act[l - 1], pol.L[l - 1].pout} : p.rows;
+        const RowSource Xv = l > 0 ? RowSource{w.val.act[l - 1], val.L[l - 1].pout} : p.rows;
+        if (p.defer) {
+            p.defer->add(Lp, w.pol.dx[l], Xp, a.pol_grad);
+            p.defer->add(Lv, w.val.dx[l], Xv, a.val_grad);
+        } else {
+            TnPair pr;
+            pr.dY = w.val.dx[l];
+            pr.X = Xv.x;
+            pr.dW = a.val_grad + Lv.off_flat_w;
+            pr.db = a.val_grad + Lv.off_flat_b;
+            pr.ws = w.val.tn;
+            rc = launch_gemm_tn(st, w.pol.dx[l], Lp.pout, Lp.pout, Xp.x, Xp.ld, Lp.pin, a.pol_grad + Lp.off_flat_w, a.pol_grad + Lp.off_flat_b,
+                                Lp.out, Lp.in, mb, w.pol.tn, tn_layer_floats(pol, l, mb, 0), Xp.rowtab, Xp.src_rows, &pr);
+            if (rc) return rc;
+        }
+        if (l == 0) break;
+        NtAlt alt;
+        alt.A = w.val.dx[l];
+        alt.B = p.val_w + Lv.off_wt;
+        alt.C = w.val.dx[l - 1];
+        alt.bits = w.val.bits[l - 1];
+        rc = launch_gemm_nt_bits(st, w.pol.dx[l], Lp.pout, p.pol_w + Lp.off_wt, Lp.pout, nullptr, w.pol.dx[l - 1], Lp.pin, mb, Lp.pin,
+                                 Lp.pout, EPI_MASK, w.pol.bits[l - 1], nullptr, 0, &alt);
+        if (rc) return rc == -1 ? RLPPO_ERR_ARG : rc;
+    }
+    return 0;
+}
+
+// One launch chain per network: the policy's on p.st, the critic's on p.side
+static int two_chain_pass(const Pass &p) {
+    const rlppo_minibatch_args &a = *p.a;
+    const NetLayout &pol = p.pol, &val = p.val;
+    const WsPlan &w = p.w;
+    const int64_t mb = p.mb;
+    const bool b16 = p.prec == 1;
+    const unsigned short *pol_wb16 = reinterpret_cast<const unsigned short *>(a.pol_wb16);
+    const unsigned short *val_wb16 = reinterpret_cast<const unsigned short *>(a.val_wb16);
+    const unsigned short *pol_x3 = p.prec == 2 ? pol_wb16 : nullptr, *val_x3 = p.prec == 2 ? val_wb16 : nullptr;  // [r4] split-bf16
+    bool phave[RLPPO_MAX_LAYERS] = {}, vhave[RLPPO_MAX_LAYERS] = {};
+    bool pf32[RLPPO_MAX_LAYERS] = {}, vf32[RLPPO_MAX_LAYERS] = {};  // bf16 precision: which activations also exist as fp32
+    bool v_folded = false;  // the critic's one-output head was computed in its last hidden layer's epilogue: compact outputs
+    int rc;
+    if (b16) {
+        rc = forward_b16(p.side, val, p.val_w, val_wb16, p.rows.x, w.states_b, p.rows.ld, mb, 0, w.val.act, w.val.actb, w.val.bits, vhave,
+                         vf32);
+        if (rc) return rc;
+        rc = forward_b16(p.st, pol, p.pol_w, pol_wb16, p.rows.x, w.states_b, p.rows.ld, mb, a.head == RLPPO_HEAD_GAUSSIAN, w.pol.act,
+                         w.pol.actb, w.pol.bits, phave, pf32);
+    } else {
+        rc = forward(p.side, val, p.val_w, p.rows, mb, 0, w.val.act, 0, w.val.bits, vhave, &v_folded, val_x3, true);
+        if (rc) return rc;
+        rc = forward(p.st, pol, p.pol_w, p.rows, mb, a.head == RLPPO_HEAD_GAUSSIAN, w.pol.act, 0, w.pol.bits, phave, nullptr, pol_x3);
+    }
+    if (rc) return rc;
+    // loss epilogue: outputs -> output gradients in place, report statistics accumulated on device.  The value loss only
+    // needs the critic's output and the policy loss only the policy's, so each chain runs its own loss kernel and the chains
+    // do not meet until the end of the minibatch.
+    const int64_t ldv = v_folded ? 1 : val.L[val.n_layers - 1].pout;
+    rc = launch_value_loss(p.side, w.val.act[val.n_layers - 1], ldv, w.g_tgt, w.g_adv, mb, p.cfg, a.stats);
+    if (rc) return rc;
+    rc = policy_loss(p.st, p);
+    if (rc) return rc;
+    if (b16) {
+        rc = backward_b16(p.side, val, p.val_w, val_wb16, p.rows.x, w.states_b, p.rows.ld, mb, w.val.act, w.val.actb, w.val.dx, w.val.dxb,
+                          a.val_grad, w.val.tn, tn_ws_floats(val, mb, p.prec), w.val.bits, vhave, vf32);
+        if (rc) return rc;
+        return backward_b16(p.st, pol, p.pol_w, pol_wb16, p.rows.x, w.states_b, p.rows.ld, mb, w.pol.act, w.pol.actb, w.pol.dx, w.pol.dxb,
+                            a.pol_grad, w.pol.tn, tn_ws_floats(pol, mb, p.prec), w.pol.bits, phave, pf32);
+    }
+    rc = backward(p.side, val, p.val_w, p.rows, mb, w.val.act, w.val.dx, a.val_grad, w.val.tn, w.val.bits, vhave, v_folded, val_x3, p.defer);
+    if (rc) return rc;
+    return backward(p.st, pol, p.pol_w, p.rows, mb, w.pol.act, w.pol.dx, a.pol_grad, w.pol.tn, w.pol.bits, phave, false, pol_x3, p.defer);
+}
+
+int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
+    // ---- validation: every argument error is reported here, before the first HIP call
+    RLPPO_CHECK_ARG(a != nullptr, "ppo_minibatch: null args");
+    Pass p;
+    p.a = a;
+    int rc = make_layout(a->pol_dims, a->pol_layers, &p.pol);
+    if (rc) return rc;
+    rc = make_layout(a->val_dims, a->val_layers, &p.val);
+    if (rc) return rc;
+    const NetLayout &pol = p.pol, &val = p.val;
+    const int64_t mb = p.mb = a->mb;
     if (mb == 0) return 0;
-    int prec = 0;  // [r5] the precision is an argument of the call (two learners of one process may differ); the process-wide switch is its default
-    rc = resolve_precision(a->precision, &prec);
+    // [r5] the precision is an argument of the call (two learners of one process may differ); the process-wide switch is its default
+    rc = resolve_precision(a->precision, &p.prec);
     if (rc) return rc;
     RLPPO_CHECK_ARG(mb > 0 && a->pol_packed && a->val_packed && a->pol_grad && a->val_grad && a->states && a->actions &&
                         a->old_logp && a->targets && a->advantages && a->idx && a->stats && a->workspace,
@@ -971,12 +1273,16 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
     RLPPO_CHECK_ARG(pol.L[0].in == val.L[0].in, "ppo_minibatch: policy and critic observe different sizes");
     RLPPO_CHECK_ARG(a->ld_states >= pol.L[0].pin && a->ld_states % 4 == 0, "ppo_minibatch: ld_states=%ld < %d",
                     (long)a->ld_states, pol.L[0].pin);
-    if (a->ws_bytes < train_ws_floats(pol, val, mb, prec) * sizeof(float)) {
-        set_error("ppo_minibatch: workspace %zu < %zu bytes", a->ws_bytes, train_ws_floats(pol, val, mb, prec) * sizeof(float));
+    const size_t ws_bytes = plan_workspace(pol, val, mb, p.prec, a->workspace, &p.w) * sizeof(float);
+    if (a->ws_bytes < ws_bytes) {
+        set_error("ppo_minibatch: workspace %zu < %zu bytes", a->ws_bytes, ws_bytes);
         return RLPPO_ERR_WORKSPACE;
     }
+    // every head pins act_dim to at most the policy's output width (the gathered actions' slots); the loss kernel's width too
     const int n_out = pol.L[pol.n_layers - 1].out;
-    if (a->head == RLPPO_HEAD_DISCRETE) {  // (the loss kernel's width checked here too: before anything is enqueued)
+    RLPPO_CHECK_ARG(a->head == RLPPO_HEAD_DISCRETE || a->head == RLPPO_HEAD_GAUSSIAN || a->head == RLPPO_HEAD_MULTIDISCRETE,
+                    "ppo_minibatch: unknown head %d", a->head);
+    if (a->head == RLPPO_HEAD_DISCRETE) {
         RLPPO_CHECK_ARG(a->act_dim == 1, "discrete head: act_dim must be 1");
         RLPPO_CHECK_ARG(pol.L[pol.n_layers - 1].pout <= DISCRETE_LOSS_MAX_LD, "discrete head: padded width %ld too large",
                         (long)pol.L[pol.n_layers - 1].pout);
@@ -985,377 +1291,65 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
         RLPPO_CHECK_ARG(n_out % 2 == 0 && a->act_dim == n_out / 2, "gaussian head: act_dim=%d, outputs=%d", a->act_dim, n_out);
     if (a->head == RLPPO_HEAD_MULTIDISCRETE)
         RLPPO_CHECK_ARG(n_out == 21 && a->act_dim == 8, "multi-discrete head: needs 21 outputs and act_dim 8");
-
+    RLPPO_CHECK_ARG(p.prec != 1 || (a->pol_packed_r && a->val_packed_r && a->pol_wb16 && a->val_wb16),
+                    "ppo_minibatch: the bf16 update precision needs the rlppo_net_pack_bf16 images of both networks (pol_packed_r / val_packed_r / pol_wb16 / val_wb16)");
+    RLPPO_CHECK_ARG(p.prec != 2 || (a->pol_wb16 && a->val_wb16),
+                    "ppo_minibatch: the split-bf16 update precision needs the rlppo_net_pack_x3 images of both networks (pol_wb16 / val_wb16)");
     // ring-resident experience: ring_cap == 0 means "not a ring" (logical row == physical row)
-    const int64_t ring_cap = a->ring_cap > 0 ? a->ring_cap : INT64_MAX, ring_base = a->ring_cap > 0 ? a->ring_base : 0;
-    RLPPO_CHECK_ARG(ring_base >= 0 && ring_base < ring_cap, "ppo_minibatch: ring_base=%ld not in [0, ring_cap=%ld)", (long)a->ring_base,
-                    (long)a->ring_cap);
+    p.ring_cap = a->ring_cap > 0 ? a->ring_cap : INT64_MAX;
+    p.ring_base = a->ring_cap > 0 ? a->ring_base : 0;
+    RLPPO_CHECK_ARG(p.ring_base >= 0 && p.ring_base < p.ring_cap, "ppo_minibatch: ring_base=%ld not in [0, ring_cap=%ld)",
+                    (long)a->ring_base, (long)a->ring_cap);
     const int slot = a->slot;
     RLPPO_CHECK_ARG(slot >= 0 && slot < RLPPO_MAX_SLOTS, "ppo_minibatch: slot %d not in [0, %d)", slot, RLPPO_MAX_SLOTS);
+
+    // ---- plan: the first layers' rows, the form, the loss settings
+    p.rows = first_layer_rows(*a, pol, val, p.prec, p.w);
+    const bool twin = p.prec == 0 && (g_paired == 2 || (g_paired == 1 && mb >= PAIRED_MIN_ROWS)) && twin_ok(pol, val, mb);
+    p.cfg = loss_cfg(*a);
+    p.pol_w = p.prec == 1 ? a->pol_packed_r : a->pol_packed;
+    p.val_w = p.prec == 1 ? a->val_packed_r : a->val_packed;
+    DwList dws;
+    p.defer = (g_group_dw && p.prec != 1) ? &dws : nullptr;
+
     SlotBank *bank = nullptr;
     rc = slot_bank(&bank);
     if (rc) return rc;
     SlotBank &bk = *bank;
     rc = ensure_slot(bk, slot);
     if (rc) return rc;
-    hipStream_t caller = (hipStream_t)stream;
-    hipStream_t st = caller;
+    const hipStream_t caller = (hipStream_t)stream;
+    p.st = caller;
     if (slot > 0) {  // this minibatch's chains run beside the caller's stream; rlppo_ppo_join() brings them back
-        st = bk.main[slot];
-        rc = order_after(st, caller, bk.ev_slot[slot]);
+        p.st = bk.main[slot];
+        rc = order_after(p.st, caller, bk.ev_slot[slot]);
         if (rc) return rc;
         bk.pending[slot] = true;
     }
-    float *w = reinterpret_cast<float *>(a->workspace);
-    float *pact[RLPPO_MAX_LAYERS], *vact[RLPPO_MAX_LAYERS];
-    for (int l = 0; l < pol.n_layers; ++l) {
-        pact[l] = w;
-        w += (size_t)mb * pol.L[l].pout;
-    }
-    for (int l = 0; l < val.n_layers; ++l) {
-        vact[l] = w;
-        w += (size_t)mb * val.L[l].pout;
-    }
-    const int m = max_pout(pol) > max_pout(val) ? max_pout(pol) : max_pout(val);
-    float *pdx[RLPPO_MAX_LAYERS], *vdx[RLPPO_MAX_LAYERS];
-    for (int l = 0; l + 1 < pol.n_layers; ++l) {
-        pdx[l] = w;
-        w += (size_t)mb * m;
-    }
-    for (int l = 0; l + 1 < val.n_layers; ++l) {
-        vdx[l] = w;
-        w += (size_t)mb * m;
-    }
-
-    float *pol_tn_ws = w;  // partial dW tiles, one buffer per chain; the grouped launch takes the whole region
-    float *val_tn_ws = w + tn_ws_floats(pol, mb, prec);
-    const size_t tn_region = tn_region_floats(pol, val, mb, prec);
-    w += tn_region;
-    DwList dws;
-    DwList *defer = (g_group_dw && prec != 1) ? &dws : nullptr;
-    // ReLU bitmasks of the hidden layers, 8-byte aligned (the workspace base is 256-byte aligned by contract of the host)
-    if ((reinterpret_cast<uintptr_t>(w) & 7) != 0) ++w;
-    unsigned long long *pbits[RLPPO_MAX_LAYERS] = {}, *vbits[RLPPO_MAX_LAYERS] = {};
-    bool phave[RLPPO_MAX_LAYERS] = {}, vhave[RLPPO_MAX_LAYERS] = {};
-    bool pf32[RLPPO_MAX_LAYERS] = {}, vf32[RLPPO_MAX_LAYERS] = {};  // bf16 precision: which activations also exist as fp32
-    for (int l = 0; l + 1 < pol.n_layers; ++l) {
-        const size_t f = nt_bits_floats(mb, pol.L[l].pout);
-        pbits[l] = f ? reinterpret_cast<unsigned long long *>(w) : nullptr;
-        w += f;
-    }
-    for (int l = 0; l + 1 < val.n_layers; ++l) {
-        const size_t f = nt_bits_floats(mb, val.L[l].pout);
-        vbits[l] = f ? reinterpret_cast<unsigned long long *>(w) : nullptr;
-        w += f;
-    }
-    // the minibatch gather (experience_buffer.py:82-87): one pass into the workspace, shared by both nets
-    float *const states = w;
-    const int64_t ld_states = pol.L[0].pin;
-    w += (size_t)mb * pol.L[0].pin;
-    float *const wmeta = w;
-    w += (size_t)mb * (3 + (size_t)pol.L[pol.n_layers - 1].pout);
-    unsigned *const rowtab = reinterpret_cast<unsigned *>(w);  // physical buffer row of every row of the pass (gather_meta_kernel)
-    w += (size_t)mb;
-    // bf16 update precision: bf16 copies of the gathered rows and of the hidden activations, and the rounded weight images
-    const bool b16 = prec == 1;
-    const bool x3 = prec == 2;  // [r4] split-bf16 hidden forward / dX (csrc/gemm_split.hip); everything else as fp32
-    unsigned short *states_b = nullptr, *pactb[RLPPO_MAX_LAYERS] = {}, *vactb[RLPPO_MAX_LAYERS] = {};
-    unsigned short *pdxb[RLPPO_MAX_LAYERS] = {}, *vdxb[RLPPO_MAX_LAYERS] = {};
-    if (b16) {
-        RLPPO_CHECK_ARG(a->pol_packed_r && a->val_packed_r && a->pol_wb16 && a->val_wb16,
-                        "ppo_minibatch: the bf16 update precision needs the rlppo_net_pack_bf16 images of both networks");
-        if ((reinterpret_cast<uintptr_t>(w) & 15) != 0) w += 4 - ((reinterpret_cast<uintptr_t>(w) >> 2) & 3);
-        unsigned short *hb = reinterpret_cast<unsigned short *>(w);
-        states_b = hb;
-        hb += (size_t)mb * pol.L[0].pin;
-        for (int l = 0; l + 1 < pol.n_layers; ++l) {
-            pactb[l] = hb;
-            hb += (size_t)mb * pol.L[l].pout;
-        }
-        for (int l = 0; l + 1 < val.n_layers; ++l) {
-            vactb[l] = hb;
-            hb += (size_t)mb * val.L[l].pout;
-        }
-        for (int l = 0; l + 1 < pol.n_layers; ++l) {
-            pdxb[l] = hb;
-            hb += (size_t)mb * pol.L[l].pout;
-        }
-        for (int l = 0; l + 1 < val.n_layers; ++l) {
-            vdxb[l] = hb;
-            hb += (size_t)mb * val.L[l].pout;
-        }
-        // the fp32 form of the gathered rows only if a first layer takes the fp32 kernels (the predicates of forward_b16 / backward_b16)
-        auto lean0 = [](const NetLayout &n) {
-            return n.n_layers > 1 && nt_b16_ok(n.L[0].pout, n.L[0].pin, true) && tn_b16_ok(n.L[0].pout, n.L[0].pin);
-        };
-        rc = launch_gather_rows_round(st, a->states, a->ld_states, a->idx, lean0(pol) && lean0(val) ? nullptr : states, states_b,
-                                      pol.L[0].pin, mb, ring_base, ring_cap);
-    }
-    // [r3] fp32 precision: the four first-layer launches (two forwards, two dW) fetch their rows straight from the experience
-    // buffer through the row table (the gather fused into the load stage) when their shapes have that form; the
-    // separate gather pass into the workspace remains for the others.
-    const int64_t src_rows = a->ring_cap > 0 ? a->ring_cap : a->n_rows;
-    auto gather_form = [&](const NetLayout &n) {
-        return n.n_layers > 1 && nt_gather_ok(a->ld_states, src_rows, n.L[0].pout, n.L[0].pin) && tn_gather_ok(a->ld_states, src_rows) &&
-               !(n.L[0].out > 64 && n.L[0].out <= 96 && !(n.L[0].in > 96 && n.L[0].in <= 112));
-    };
-    // [r5] ... from FUSED_GATHER_MIN_ROWS rows per pass: with the weight gradients grouped (section 4.6) a 65,536-row pass is 1 % FASTER
-    // with the 10 us gather pass and contiguous first-layer operands than with rows fetched through the table inside four of its
-    // launches (11.59 against 11.71 ms per 10-epoch learn() at the 8-rank share, tools/ab_update.py, profiles/r05_ab_update_final.txt);
-    // at 524,288 rows per pass the two are equal and the fused form saves the 268 MB copy.  rlppo_dbg_set(26, 2): at every size (tests).
-    const bool fused_gather = !b16 && (g_fused_gather == 2 || (g_fused_gather == 1 && mb >= FUSED_GATHER_MIN_ROWS)) && src_rows > 0 &&
-                              gather_form(pol) && gather_form(val);
-    // (the per-row scalars -- old log-prob, advantage, target, actions -- ride in the same launch: wmeta below)
-    if (!b16 && !fused_gather) {
-        RLPPO_CHECK_ARG(a->act_dim >= 1 && a->act_dim <= pol.L[pol.n_layers - 1].pout, "ppo_minibatch: act_dim=%d", a->act_dim);
-        GatherMeta gm;
-        gm.actions = a->actions; gm.old_logp = a->old_logp; gm.adv = a->advantages; gm.targets = a->targets;
-        gm.g_old = wmeta; gm.g_adv = wmeta + mb; gm.g_tgt = wmeta + 2 * (size_t)mb; gm.g_act = wmeta + 3 * (size_t)mb;  // (= g_old, g_adv, g_tgt, g_act below)
-        gm.zero_n = vact[val.n_layers - 1];
-        gm.act_dim = a->act_dim;
-        rc = launch_gather_rows(st, a->states, a->ld_states, a->idx, states, pol.L[0].pin, mb, ring_base, ring_cap, &gm);
-    }
+    rc = gather(p);
     if (rc) return rc;
-    const float *pol_w = b16 ? a->pol_packed_r : a->pol_packed, *val_w = b16 ? a->val_packed_r : a->val_packed;
-    // the minibatch's per-row scalars, gathered once (the loss kernels stream them)
-    RLPPO_CHECK_ARG(a->act_dim >= 1 && a->act_dim <= pol.L[pol.n_layers - 1].pout, "ppo_minibatch: act_dim=%d", a->act_dim);
-    float *g_old = wmeta, *g_adv = wmeta + mb, *g_tgt = wmeta + 2 * (size_t)mb, *g_act = wmeta + 3 * (size_t)mb;
-    // ([r5] it also zeroes the first mb floats of the critic's output buffer: a folded value head accumulates into them; when the
-    // rows were gathered by a pass of their own, that launch has done all of this already)
-    if (b16 || fused_gather)
-        rc = launch_gather_meta(st, a->idx, a->actions, a->act_dim, a->old_logp, a->advantages, a->targets, g_act, g_old, g_adv, g_tgt, mb,
-                                ring_base, ring_cap, fused_gather ? rowtab : nullptr, vact[val.n_layers - 1]);
-    if (rc) return rc;
-    // forward of both nets
     // The two networks are independent until the loss epilogue and again after it, so their launch chains run on
     // two streams (the caller's + one library-owned side stream, forked/joined with events: capturable).  Each
     // launch is only 50-100 us long at K <= 256, so letting one chain's kernels fill the CUs that the other chain's
     // ramp-up / tail leaves idle is worth more than any single-kernel tweak.
-    hipStream_t side = st;
+    p.side = p.st;
     if (g_two_streams) {
-        side = bk.side[slot];
-        rc = order_after(side, st, bk.ev_fork[slot]);
+        p.side = bk.side[slot];
+        rc = order_after(p.side, p.st, bk.ev_fork[slot]);
         if (rc) return rc;
     }
-    const bool twin = !b16 && !x3 && (g_paired == 2 || (g_paired == 1 && mb >= PAIRED_MIN_ROWS)) && twin_ok(pol, val, mb);
-    const unsigned short *pol_x3 = x3 ? reinterpret_cast<const unsigned short *>(a->pol_wb16) : nullptr;
-    const unsigned short *val_x3 = x3 ? reinterpret_cast<const unsigned short *>(a->val_wb16) : nullptr;
-    if (x3) RLPPO_CHECK_ARG(pol_x3 && val_x3, "ppo_minibatch: the split-bf16 update precision needs the rlppo_net_pack_x3 images of both networks (pol_wb16 / val_wb16)");
     ++g_cnt_pass;
     if (twin) ++g_cnt_paired_pass;
-    if (fused_gather) ++g_cnt_gather_fused_pass;
-    if (twin) {
-        const int H = pol.n_layers - 1;  // hidden layers (the same number in both networks)
-        const float *xp = fused_gather ? a->states : states, *xv = xp;
-        int64_t ldx = fused_gather ? a->ld_states : ld_states;
-        // [r3] The critic's output layer is a dot product per row of activations this launch has in registers: folded into the last
-        // hidden layer's forward epilogue (NtDot) it costs no pass over the 4 x 256 B per row the matrix-vector kernel re-read
-        // (537 MB per 524,288-row pass, in the stretch of the pass that is HBM-bound).  Values land compact ([mb], stride 1).
-        const LayerLayout &Lvh = val.L[H];
-        const bool fold_v = g_fold_vhead && gemv_head_ok(Lvh.out, Lvh.pin) && val.L[H - 1].pout / 128 <= 2;
-        float *vout = vact[H];
-        const int64_t ldv = fold_v ? 1 : Lvh.pout;
-        for (int l = 0; l < H; ++l) {
-            const LayerLayout &Lp = pol.L[l], &Lv = val.L[l];
-            NtAlt alt;
-            alt.A = xv;
-            alt.B = val_w + Lv.off_w;
-            alt.bias = val_w + Lv.off_b;
-            alt.C = vact[l];
-            alt.bits = vbits[l];
-            NtDot dots[2];
-            const bool fold_here = fold_v && l == H - 1;
-            if (fold_here) {  // (vout was zeroed by gather_meta_kernel)
-                dots[1].w = val_w + Lvh.off_w;
-                dots[1].out = vout;
-                dots[1].b = val_w + Lvh.off_b;
-            }
-            rc = launch_gemm_nt_bits(st, xp, ldx, pol_w + Lp.off_w, Lp.pin, pol_w + Lp.off_b, pact[l], Lp.pout, mb, Lp.pout, Lp.pin,
-                                     EPI_BIAS_RELU, pbits[l], l == 0 && fused_gather ? rowtab : nullptr, src_rows, &alt,
-                                     fold_here ? dots : nullptr);
-            if (rc) {
-                if (rc == -1) set_error("paired pass: a hidden layer does not have the bitmask form");
-                return rc == -1 ? RLPPO_ERR_ARG : rc;
-            }
-            xp = pact[l];
-            xv = vact[l];
-            ldx = Lp.pout;
-        }
-        // the two heads: forward, loss, output-layer backward -- critic on the side stream
-        hipStream_t hs = st;
-        if (g_two_streams) {
-            hs = bk.side[slot];
-            rc = order_after(hs, st, bk.ev_fork[slot]);
-            if (rc) return rc;
-        }
-        LossCfg cfg;
-        cfg.clip = a->clip_range;
-        cfg.clip_lo = (float)(1.0 - (double)a->clip_range);
-        cfg.clip_hi = (float)(1.0 + (double)a->clip_range);
-        cfg.ent_coef = a->ent_coef;
-        cfg.mb_ratio = a->mb_ratio;
-        cfg.inv_mb = 1.0f / (float)mb;
-        cfg.var_m = a->var_m;
-        cfg.var_b = a->var_b;
-        cfg.ring_base = ring_base;
-        cfg.ring_cap = ring_cap;
-        cfg.adv_norm = a->adv_norm;
-        cfg.vclip = a->value_clip;
-        cfg.kl_slots = a->kl_slots;
-        cfg.stop_word = a->stop_word;
-        float *pout = pact[H];
-        const int64_t ldp = pol.L[H].pout;
-        if (!fold_v) {
-            rc = head_forward(hs, val, val_w, xv, ldx, mb, 0, vout);
-            if (rc) return rc;
-        }
-        rc = launch_value_loss(hs, vout, ldv, nullptr, g_tgt, g_adv, mb, cfg, a->stats);
+    if (p.rows.rowtab) ++g_cnt_gather_fused_pass;
+    rc = twin ? paired_pass(p, bk, slot) : two_chain_pass(p);
+    if (rc) return rc;
+    if (!twin && p.side != p.st) {  // (the paired pass has joined already)
+        rc = order_after(p.st, p.side, bk.ev_join[slot]);
         if (rc) return rc;
-        // The critic's head kernels are matrix-vector products: HBM-bound, like the policy's loss kernel, unlike the policy head's
-        // GEMMs.  Ordered so that the two HBM-bound stretches do not meet: critic forward + loss beside the policy head's forward
-        // GEMM, the critic's output-layer backward only after the policy's loss, beside the policy head's dW / dX GEMMs.
-        const bool ordered = g_head_order && hs != st;
-        if (!ordered) {
-            rc = head_backward(hs, val, val_w, vout, xv, mb, vdx[H - 1], a->val_grad, val_tn_ws, vbits[H - 1], ldv, defer);
-            if (rc) return rc;
-        }
-        rc = head_forward(st, pol, pol_w, xp, ldx, mb, a->head == RLPPO_HEAD_GAUSSIAN, pout);
-        if (rc) return rc;
-        if (a->head == RLPPO_HEAD_DISCRETE)
-            rc = launch_discrete_loss(st, pout, ldp, n_out, nullptr, ldv, nullptr, g_act, g_old, g_tgt, g_adv, mb, cfg, a->stats);
-        else if (a->head == RLPPO_HEAD_GAUSSIAN)
-            rc = launch_gaussian_loss(st, pout, ldp, n_out / 2, nullptr, ldv, nullptr, g_act, g_old, g_tgt, g_adv, mb, cfg, a->stats);
-        else if (a->head == RLPPO_HEAD_MULTIDISCRETE)
-            rc = launch_multidiscrete_loss(st, pout, ldp, nullptr, ldv, nullptr, g_act, g_old, g_tgt, g_adv, mb, cfg, a->stats);
-        else {
-            set_error("ppo_minibatch: unknown head %d", a->head);
-            rc = RLPPO_ERR_ARG;
-        }
-        if (rc) return rc;
-        if (ordered) {
-            rc = order_after(hs, st, bk.ev_mid[slot]);
-            if (rc) return rc;
-            rc = head_backward(hs, val, val_w, vout, xv, mb, vdx[H - 1], a->val_grad, val_tn_ws, vbits[H - 1], ldv, defer);
-            if (rc) return rc;
-        }
-        rc = head_backward(st, pol, pol_w, pout, xp, mb, pdx[H - 1], a->pol_grad, pol_tn_ws, pbits[H - 1], 0, defer);
-        if (rc) return rc;
-        if (hs != st) {
-            rc = order_after(st, hs, bk.ev_join[slot]);
-            if (rc) return rc;
-        }
-        // hidden layers, backward: dW (+ reduction) of both networks, then dX of both
-        for (int l = H - 1; l >= 0; --l) {
-            const LayerLayout &Lp = pol.L[l], &Lv = val.L[l];
-            const bool g0 = l == 0 && fused_gather;
-            const float *Xp = l > 0 ? pact[l - 1] : (g0 ? a->states : states), *Xv = l > 0 ? vact[l - 1] : Xp;
-            const int64_t ldxb = l > 0 ? pol.L[l - 1].pout : (g0 ? a->ld_states : ld_states);
-            TnPair pr;
-            pr.dY = vdx[l];
-            pr.X = Xv;
-            pr.dW = a->val_grad + Lv.off_flat_w;
-            pr.db = a->val_grad + Lv.off_flat_b;
-            pr.ws = val_tn_ws;
-            if (defer) {
-                defer->add(pdx[l], Lp.pout, Lp.pout, Xp, ldxb, Lp.pin, a->pol_grad + Lp.off_flat_w, a->pol_grad + Lp.off_flat_b, Lp.out, Lp.in,
-                           g0 ? rowtab : nullptr, g0 ? src_rows : 0);
-                defer->add(vdx[l], Lv.pout, Lv.pout, Xv, ldxb, Lv.pin, a->val_grad + Lv.off_flat_w, a->val_grad + Lv.off_flat_b, Lv.out, Lv.in,
-                           g0 ? rowtab : nullptr, g0 ? src_rows : 0);
-            } else
-                rc = launch_gemm_tn(st, pdx[l], Lp.pout, Lp.pout, Xp, ldxb, Lp.pin, a->pol_grad + Lp.off_flat_w, a->pol_grad + Lp.off_flat_b,
-                                    Lp.out, Lp.in, mb, pol_tn_ws, tn_layer_floats(pol, l, mb, 0), g0 ? rowtab : nullptr, src_rows, &pr);
-            if (rc) return rc;
-            if (l == 0) break;
-            NtAlt alt;
-            alt.A = vdx[l];
-            alt.B = val_w + Lv.off_wt;
-            alt.C = vdx[l - 1];
-            alt.bits = vbits[l - 1];
-            rc = launch_gemm_nt_bits(st, pdx[l], Lp.pout, pol_w + Lp.off_wt, Lp.pout, nullptr, pdx[l - 1], Lp.pin, mb, Lp.pin, Lp.pout,
-                                     EPI_MASK, pbits[l - 1], nullptr, 0, &alt);
-            if (rc) return rc == -1 ? RLPPO_ERR_ARG : rc;
-        }
-        if (defer && dws.n) {
-            ++g_cnt_group_dw;
-            return launch_gemm_tn_group(st, dws.p, dws.n, mb, pol_tn_ws, tn_region);
-        }
-        return 0;
     }
-    bool v_folded = false;  // the critic's one-output head was computed in its last hidden layer's epilogue: compact outputs
-    if (b16) {
-        rc = forward_b16(side, val, val_w, reinterpret_cast<const unsigned short *>(a->val_wb16), states, states_b, ld_states, mb, 0,
-                         vact, vactb, vbits, vhave, vf32);
-        if (rc) return rc;
-        rc = forward_b16(st, pol, pol_w, reinterpret_cast<const unsigned short *>(a->pol_wb16), states, states_b, ld_states, mb,
-                         a->head == RLPPO_HEAD_GAUSSIAN, pact, pactb, pbits, phave, pf32);
-    } else {
-        const float *x0 = fused_gather ? a->states : states;
-        const int64_t ld0 = fused_gather ? a->ld_states : ld_states;
-        const unsigned *rt = fused_gather ? rowtab : nullptr;
-        rc = forward(side, val, val_w, x0, ld0, mb, 0, vact, 0, vbits, vhave, rt, src_rows, &v_folded, val_x3, true);
-        if (rc) return rc;
-        rc = forward(st, pol, pol_w, x0, ld0, mb, a->head == RLPPO_HEAD_GAUSSIAN, pact, 0, pbits, phave, rt, src_rows, nullptr, pol_x3);
-    }
-    if (rc) return rc;
-    // loss epilogue: outputs -> output gradients in place, report statistics accumulated on device.  The value loss only
-    // needs the critic's output and the policy loss only the policy's, so each chain runs its own loss kernel and the chains
-    // do not meet until the end of the minibatch.
-    LossCfg cfg;
-    cfg.clip = a->clip_range;
-    cfg.clip_lo = (float)(1.0 - (double)a->clip_range);
-    cfg.clip_hi = (float)(1.0 + (double)a->clip_range);
-    cfg.ent_coef = a->ent_coef;
-    cfg.mb_ratio = a->mb_ratio;
-    cfg.inv_mb = 1.0f / (float)mb;
-    cfg.var_m = a->var_m;
-    cfg.var_b = a->var_b;
-    cfg.ring_base = ring_base;
-    cfg.ring_cap = ring_cap;
-    cfg.adv_norm = a->adv_norm;
-    cfg.vclip = a->value_clip;
-    cfg.kl_slots = a->kl_slots;
-    cfg.stop_word = a->stop_word;
-    float *pout = pact[pol.n_layers - 1], *vout = vact[val.n_layers - 1];
-    const int64_t ldp = pol.L[pol.n_layers - 1].pout, ldv = v_folded ? 1 : val.L[val.n_layers - 1].pout;
-    rc = launch_value_loss(side, vout, ldv, nullptr, g_tgt, g_adv, mb, cfg, a->stats);
-    if (rc) return rc;
-    float *vjoint = nullptr;  // the loss kernels' joint form (policy + value in one launch) is not used by this entry point
-    if (a->head == RLPPO_HEAD_DISCRETE)
-        rc = launch_discrete_loss(st, pout, ldp, n_out, vjoint, ldv, nullptr, g_act, g_old, g_tgt, g_adv, mb, cfg, a->stats);
-    else if (a->head == RLPPO_HEAD_GAUSSIAN)
-        rc = launch_gaussian_loss(st, pout, ldp, n_out / 2, vjoint, ldv, nullptr, g_act, g_old, g_tgt, g_adv, mb, cfg, a->stats);
-    else if (a->head == RLPPO_HEAD_MULTIDISCRETE)
-        rc = launch_multidiscrete_loss(st, pout, ldp, vjoint, ldv, nullptr, g_act, g_old, g_tgt, g_adv, mb, cfg, a->stats);
-    else {
-        set_error("ppo_minibatch: unknown head %d", a->head);
-        rc = RLPPO_ERR_ARG;
-    }
-    if (rc) return rc;
-
-    if (b16) {
-        rc = backward_b16(side, val, val_w, reinterpret_cast<const unsigned short *>(a->val_wb16), states, states_b, ld_states, mb, vact,
-                          vactb, vdx, vdxb, a->val_grad, val_tn_ws, tn_ws_floats(val, mb, prec), vbits, vhave, vf32);
-        if (rc) return rc;
-        rc = backward_b16(st, pol, pol_w, reinterpret_cast<const unsigned short *>(a->pol_wb16), states, states_b, ld_states, mb, pact,
-                          pactb, pdx, pdxb, a->pol_grad, pol_tn_ws, tn_ws_floats(pol, mb, prec), pbits, phave, pf32);
-    } else {
-        ChainCtx cp, cv;
-        if (fused_gather) {
-            cp.rowtab = cv.rowtab = rowtab;
-            cp.src = cv.src = a->states;
-            cp.ld_src = cv.ld_src = a->ld_states;
-            cp.src_rows = cv.src_rows = src_rows;
-        }
-        rc = backward(side, val, val_w, states, ld_states, mb, vact, vdx, a->val_grad, val_tn_ws, vbits, vhave, cv, v_folded, val_x3, defer);
-        if (rc) return rc;
-        rc = backward(st, pol, pol_w, states, ld_states, mb, pact, pdx, a->pol_grad, pol_tn_ws, pbits, phave, cp, false, pol_x3, defer);
-    }
-    if (rc) return rc;
-    if (side != st) rc = order_after(st, side, bk.ev_join[slot]);
-    if (rc) return rc;
-    if (defer && dws.n) {  // [r5] every GEMM-shaped weight gradient of the pass: one launch + one reduction, after the chains have joined
+    if (p.defer && dws.n) {  // [r5] every GEMM-shaped weight gradient of the pass: one launch + one reduction, after the chains have joined
         ++g_cnt_group_dw;
-        rc = launch_gemm_tn_group(st, dws.p, dws.n, mb, pol_tn_ws, tn_region);
+        rc = launch_gemm_tn_group(p.st, dws.p, dws.n, mb, p.w.pol.tn, p.w.tn_floats);
     }
     return rc;
 }

@@ -203,7 +203,6 @@ int launch_gemv_dw(hipStream_t st, const float *dy, int64_t ldy, const float *x,
 struct LossCfg {
     float clip, clip_lo, clip_hi, ent_coef, mb_ratio, inv_mb;
     float var_m, var_b;
-    int64_t ring_base, ring_cap;  // ExperienceBuffer ring: logical row i lives at physical row (i + ring_base) mod ring_cap
     // [ABI 7] options beyond the reference (rlppo_minibatch_args): all off = the reference's loss, instruction for instruction
     const float *adv_norm = nullptr;      // {mean, scale}: the surrogate reads (A - mean) * scale
     float vclip = 0.f;                    // > 0: clipped value prediction around v_old = target - A
@@ -223,16 +222,14 @@ int launch_gaussian_sample(hipStream_t, const float *, int64_t, int64_t, int, co
                            unsigned *done_words = nullptr, unsigned done_value = 0);
 int launch_multidiscrete_sample(hipStream_t, const float *, int64_t, int64_t, const float *, int64_t *, float *,
                                 unsigned *done_words = nullptr, unsigned done_value = 0);
-int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const int64_t *idx, const float *targets, const float *adv, int64_t mb,
-                      const LossCfg &cfg, double *stats);
+int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const float *targets, const float *adv, int64_t mb, const LossCfg &cfg,
+                      double *stats);
 int64_t kl_slots_doubles(int64_t mb);  // rlppo_kl_slots_doubles
 constexpr int64_t DISCRETE_LOSS_MAX_LD = 64 * 32;  // padded logits per row of the widest discrete loss kernel (one wave, 32 per lane)
-int launch_discrete_loss(hipStream_t, float *, int64_t, int, float *, int64_t, const int64_t *, const float *, const float *,
-                         const float *, const float *, int64_t, const LossCfg &, double *);
-int launch_gaussian_loss(hipStream_t, float *, int64_t, int, float *, int64_t, const int64_t *, const float *, const float *,
-                         const float *, const float *, int64_t, const LossCfg &, double *);
-int launch_multidiscrete_loss(hipStream_t, float *, int64_t, float *, int64_t, const int64_t *, const float *, const float *,
-                              const float *, const float *, int64_t, const LossCfg &, double *);
+// the policy loss of one head on its outputs [mb][ld], in place, from the gathered per-row actions, old log-probabilities and advantages
+int launch_discrete_loss(hipStream_t, float *, int64_t, int, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
+int launch_gaussian_loss(hipStream_t, float *, int64_t, int, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
+int launch_multidiscrete_loss(hipStream_t, float *, int64_t, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
 
 // fused_act.hip: the whole rollout step of the discrete policy in one launch ----------------
 struct FusedActIO {

@@ -265,25 +265,21 @@ __device__ __forceinline__ float value_row(float *vout_row, float target, float 
 }
 
 // ----------------------------------------------------------------------------------- discrete: loss + grad
-// One wave per row.  logits[row][0:A] is overwritten with dL/dlogits, vout[row][0] with dL/dv.
+// One wave per row.  logits[row][0:A] is overwritten with dL/dlogits.
 template <int EPL>
 __global__ __launch_bounds__(256) void discrete_loss_kernel(float *__restrict__ logits, int64_t ld, int A,
-                                                             float *__restrict__ vout, int64_t ldv,
-                                                             const int64_t *__restrict__ idx,
                                                              const float *__restrict__ actions,
                                                              const float *__restrict__ old_logp,
-                                                             const float *__restrict__ targets,
                                                              const float *__restrict__ advantages, int64_t mb,
                                                              LossCfg cfg, double *__restrict__ stats) {
     const int lane = threadIdx.x & 63;
     float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     // grid-stride over rows: statistics stay in registers, so a launch issues 5 atomics per BLOCK, not per 4 rows
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < mb; row += (int64_t)gridDim.x * 4) {
-        const int64_t src = idx ? ring_row(idx[row], cfg.ring_base, cfg.ring_cap) : row;  // idx == null: per-row data already gathered
         float *z = logits + row * ld;
         float p[EPL], pc[EPL], lp[EPL];
         row_softmax<EPL>(z, A, lane, p, pc);
-        const int a = (int)actions[src];  // acts.long() of a float-encoded index (discrete_policy.py:71)
+        const int a = (int)actions[row];  // acts.long() of a float-encoded index (discrete_policy.py:71)
         float ent = 0.f, lpa = 0.f, pca = 0.f;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
@@ -298,7 +294,7 @@ __global__ __launch_bounds__(256) void discrete_loss_kernel(float *__restrict__ 
         ent = wave_sum(ent);
         lpa = wave_sum(lpa);  // exactly one lane holds a non-zero term
         pca = wave_sum(pca);
-        const float old = old_logp[src], adv_raw = advantages[src], adv = surrogate_adv(adv_raw, cfg);
+        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
         const float lr = lpa - old;
         const float ratio = expf(lr);
         float smin;
@@ -330,7 +326,6 @@ __global__ __launch_bounds__(256) void discrete_loss_kernel(float *__restrict__ 
             st[RLPPO_STAT_KL] += ((ratio - 1.f) - lr) * cfg.inv_mb;
             st[RLPPO_STAT_CLIPFRAC] += (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
             st[RLPPO_STAT_PLOSS] += -smin * cfg.inv_mb;
-            if (vout) st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[src], adv_raw, cfg) * cfg.inv_mb;
         }
     }
     block_stats_add(stats, st, true, cfg, cfg.kl_slots);
@@ -361,11 +356,8 @@ __device__ __forceinline__ float row16_max(float v) {
 }
 
 __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict__ logits, int64_t ld, int A,
-                                                               float *__restrict__ vout, int64_t ldv,
-                                                               const int64_t *__restrict__ idx,
                                                                const float *__restrict__ actions,
                                                                const float *__restrict__ old_logp,
-                                                               const float *__restrict__ targets,
                                                                const float *__restrict__ advantages, int64_t mb,
                                                                LossCfg cfg, double *__restrict__ stats) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -376,7 +368,6 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
     for (int64_t base = (int64_t)blockIdx.x * 16; base < mb; base += (int64_t)gridDim.x * 16) {
         const bool live = base + grp < mb;
         const int64_t row = live ? base + grp : mb - 1;  // idle groups of the last pass shadow the last row (no stores)
-        const int64_t src = idx ? ring_row(idx[row], cfg.ring_base, cfg.ring_cap) : row;  // idx == null: per-row data already gathered
         float *z = logits + row * ld + c0;
         float p[8], pc[8], lp[8];
         if (in_row) {
@@ -387,8 +378,8 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
                 p[4 + e] = z1[e];
             }
         }
-        const float old = old_logp[src], adv_raw = advantages[src], adv = surrogate_adv(adv_raw, cfg);
-        const int a = (int)actions[src];  // acts.long() of a float-encoded index (discrete_policy.py:71)
+        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
+        const int a = (int)actions[row];  // acts.long() of a float-encoded index (discrete_policy.py:71)
         float mx = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -455,7 +446,6 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
             st[RLPPO_STAT_KL] += ((ratio - 1.f) - lr) * cfg.inv_mb;
             st[RLPPO_STAT_CLIPFRAC] += (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
             st[RLPPO_STAT_PLOSS] += -smin * cfg.inv_mb;
-            if (vout) st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[src], adv_raw, cfg) * cfg.inv_mb;
         }
     }
     block_stats_add(stats, st, true, cfg, cfg.kl_slots);
@@ -464,23 +454,21 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
 // Value loss on its own (value_estimator + ppo_learner.py:163-166: MSE(vals, target_values)): v -> d loss / d v in place,
 // VLOSS statistic.  A separate launch so that the critic's launch chain never has to meet the policy's between the
 // forward and the backward pass: the two chains only join at the end of the minibatch.
-__global__ __launch_bounds__(256) void value_loss_kernel(float *__restrict__ vout, int64_t ldv, const int64_t *__restrict__ idx,
-                                                         const float *__restrict__ targets, const float *__restrict__ advantages,
-                                                         int64_t mb, LossCfg cfg, double *__restrict__ stats) {
+__global__ __launch_bounds__(256) void value_loss_kernel(float *__restrict__ vout, int64_t ldv, const float *__restrict__ targets,
+                                                         const float *__restrict__ advantages, int64_t mb, LossCfg cfg,
+                                                         double *__restrict__ stats) {
     float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < mb; row += (int64_t)gridDim.x * 256) {
-        const int64_t src = idx ? ring_row(idx[row], cfg.ring_base, cfg.ring_cap) : row;
-        st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[src], cfg.vclip > 0.f ? advantages[src] : 0.f, cfg) * cfg.inv_mb;
-    }
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < mb; row += (int64_t)gridDim.x * 256)
+        st[RLPPO_STAT_VLOSS] += value_row(vout + row * ldv, targets[row], cfg.vclip > 0.f ? advantages[row] : 0.f, cfg) * cfg.inv_mb;
     block_stats_add(stats, st, true, cfg);
 }
 
-int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const int64_t *idx, const float *targets, const float *adv, int64_t mb,
-                      const LossCfg &cfg, double *stats) {
+int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const float *targets, const float *adv, int64_t mb, const LossCfg &cfg,
+                      double *stats) {
     if (mb <= 0) return 0;
     RLPPO_CHECK_ARG(!(cfg.vclip > 0.f) || adv, "value loss: clipping needs the advantages");
     dim3 grid((unsigned)(cdiv(mb, 256) < 1024 ? cdiv(mb, 256) : 1024));
-    hipLaunchKernelGGL(value_loss_kernel, grid, dim3(256), 0, st, vout, ldv, idx, targets, adv, mb, cfg, stats);
+    hipLaunchKernelGGL(value_loss_kernel, grid, dim3(256), 0, st, vout, ldv, targets, adv, mb, cfg, stats);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }
@@ -490,19 +478,18 @@ int64_t kl_slots_doubles(int64_t mb) {  // grids: discrete <= 2048 workgroups, g
     return 2 + (g > 2048 ? g : 2048);
 }
 
-int launch_discrete_loss(hipStream_t st, float *logits, int64_t ld, int A, float *vout, int64_t ldv, const int64_t *idx,
-                         const float *actions, const float *old_logp, const float *targets, const float *adv, int64_t mb,
-                         const LossCfg &cfg, double *stats) {
+int launch_discrete_loss(hipStream_t st, float *logits, int64_t ld, int A, const float *actions, const float *old_logp, const float *adv,
+                         int64_t mb, const LossCfg &cfg, double *stats) {
     if (mb <= 0) return 0;
     dim3 grid((unsigned)(cdiv(mb, 4) < 2048 ? cdiv(mb, 4) : 2048)), block(256);
     RLPPO_CHECK_ARG(ld <= DISCRETE_LOSS_MAX_LD, "discrete head: padded width %ld too large", (long)ld);
     if (ld <= 128) {  // 16 lanes per row, DPP reductions
         dim3 grid16((unsigned)(cdiv(mb, 16) < 2048 ? cdiv(mb, 16) : 2048));
-        hipLaunchKernelGGL(discrete_loss16_kernel, grid16, block, 0, st, logits, ld, A, vout, ldv, idx, actions, old_logp, targets, adv, mb, cfg, stats);
+        hipLaunchKernelGGL(discrete_loss16_kernel, grid16, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats);
     } else if (ld <= 512)  // one wave per row
-        hipLaunchKernelGGL((discrete_loss_kernel<8>), grid, block, 0, st, logits, ld, A, vout, ldv, idx, actions, old_logp, targets, adv, mb, cfg, stats);
+        hipLaunchKernelGGL((discrete_loss_kernel<8>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats);
     else
-        hipLaunchKernelGGL((discrete_loss_kernel<32>), grid, block, 0, st, logits, ld, A, vout, ldv, idx, actions, old_logp, targets, adv, mb, cfg, stats);
+        hipLaunchKernelGGL((discrete_loss_kernel<32>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }
@@ -571,20 +558,16 @@ int launch_gaussian_sample(hipStream_t st, const float *y, int64_t ld, int64_t n
 
 // y[row][0:2k] (tanh outputs) is overwritten with dL/d(pre-tanh) ; entropy = mean over ALL mb*k elements (quirk Q8)
 __global__ __launch_bounds__(256) void gaussian_loss_kernel(float *__restrict__ y, int64_t ld, int k,
-                                                             float *__restrict__ vout, int64_t ldv,
-                                                             const int64_t *__restrict__ idx,
                                                              const float *__restrict__ actions,
                                                              const float *__restrict__ old_logp,
-                                                             const float *__restrict__ targets,
                                                              const float *__restrict__ advantages, int64_t mb,
                                                              LossCfg cfg, double *__restrict__ stats) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = row < mb;
     float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     if (active) {
-        const int64_t src = idx ? ring_row(idx[row], cfg.ring_base, cfg.ring_cap) : row;  // idx == null: per-row data already gathered
         float *yr = y + row * ld;
-        const float *xr = actions + src * k;
+        const float *xr = actions + row * k;
         float lp = 0.f, ent = 0.f;
         if (k <= FLOAT_SUM_K) {
 #pragma unroll 4
@@ -604,7 +587,7 @@ __global__ __launch_bounds__(256) void gaussian_loss_kernel(float *__restrict__ 
             lp = (float)lpd;
             ent = (float)entd;
         }
-        const float old = old_logp[src], adv_raw = advantages[src], adv = surrogate_adv(adv_raw, cfg);
+        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
         const float lr = lp - old;
         const float ratio = expf(lr);
         float smin;
@@ -627,18 +610,16 @@ __global__ __launch_bounds__(256) void gaussian_loss_kernel(float *__restrict__ 
         st[RLPPO_STAT_KL] = ((ratio - 1.f) - lr) * cfg.inv_mb;
         st[RLPPO_STAT_CLIPFRAC] = (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
         st[RLPPO_STAT_PLOSS] = -smin * cfg.inv_mb;
-        st[RLPPO_STAT_VLOSS] = vout ? value_row(vout + row * ldv, targets[src], adv_raw, cfg) * cfg.inv_mb : 0.f;
     }
     block_stats_add(stats, st, active, cfg, cfg.kl_slots);
 }
 
-int launch_gaussian_loss(hipStream_t st, float *y, int64_t ld, int k, float *vout, int64_t ldv, const int64_t *idx,
-                         const float *actions, const float *old_logp, const float *targets, const float *adv, int64_t mb,
-                         const LossCfg &cfg, double *stats) {
+int launch_gaussian_loss(hipStream_t st, float *y, int64_t ld, int k, const float *actions, const float *old_logp, const float *adv,
+                         int64_t mb, const LossCfg &cfg, double *stats) {
     if (mb <= 0) return 0;
     RLPPO_CHECK_ARG(k >= 1, "gaussian head: action dim %d < 1", k);
-    hipLaunchKernelGGL(gaussian_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, y, ld, k, vout, ldv, idx,
-                       actions, old_logp, targets, adv, mb, cfg, stats);
+    hipLaunchKernelGGL(gaussian_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, y, ld, k, actions, old_logp, adv, mb,
+                       cfg, stats);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }
@@ -699,18 +680,14 @@ int launch_multidiscrete_sample(hipStream_t st, const float *logits, int64_t ld,
 }
 
 __global__ __launch_bounds__(256) void multidiscrete_loss_kernel(float *__restrict__ logits, int64_t ld,
-                                                                  float *__restrict__ vout, int64_t ldv,
-                                                                  const int64_t *__restrict__ idx,
                                                                   const float *__restrict__ actions,
                                                                   const float *__restrict__ old_logp,
-                                                                  const float *__restrict__ targets,
                                                                   const float *__restrict__ advantages, int64_t mb,
                                                                   LossCfg cfg, double *__restrict__ stats) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = row < mb;
     float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     if (active) {
-        const int64_t src = idx ? ring_row(idx[row], cfg.ring_base, cfg.ring_cap) : row;  // idx == null: per-row data already gathered
         float *z = logits + row * ld;
         float ls[21], ph[21], eh[8];
         int act[8];
@@ -731,10 +708,10 @@ __global__ __launch_bounds__(256) void multidiscrete_loss_kernel(float *__restri
             }
             eh[h] = e;
             ent += e;
-            act[h] = (int)actions[src * 8 + h];
+            act[h] = (int)actions[row * 8 + h];
             lp += ls[s + act[h]];
         }
-        const float old = old_logp[src], adv_raw = advantages[src], adv = surrogate_adv(adv_raw, cfg);
+        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
         const float lr = lp - old;
         const float ratio = expf(lr);
         float smin;
@@ -754,17 +731,15 @@ __global__ __launch_bounds__(256) void multidiscrete_loss_kernel(float *__restri
         st[RLPPO_STAT_KL] = ((ratio - 1.f) - lr) * cfg.inv_mb;
         st[RLPPO_STAT_CLIPFRAC] = (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
         st[RLPPO_STAT_PLOSS] = -smin * cfg.inv_mb;
-        st[RLPPO_STAT_VLOSS] = vout ? value_row(vout + row * ldv, targets[src], adv_raw, cfg) * cfg.inv_mb : 0.f;
     }
     block_stats_add(stats, st, active, cfg, cfg.kl_slots);
 }
 
-int launch_multidiscrete_loss(hipStream_t st, float *logits, int64_t ld, float *vout, int64_t ldv, const int64_t *idx,
-                              const float *actions, const float *old_logp, const float *targets, const float *adv,
+int launch_multidiscrete_loss(hipStream_t st, float *logits, int64_t ld, const float *actions, const float *old_logp, const float *adv,
                               int64_t mb, const LossCfg &cfg, double *stats) {
     if (mb <= 0) return 0;
-    hipLaunchKernelGGL(multidiscrete_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, logits, ld, vout, ldv,
-                       idx, actions, old_logp, targets, adv, mb, cfg, stats);
+    hipLaunchKernelGGL(multidiscrete_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, logits, ld, actions, old_logp,
+                       adv, mb, cfg, stats);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }

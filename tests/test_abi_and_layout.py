@@ -64,6 +64,71 @@ def test_minibatch_args_struct_matches_header_field_order():
     assert fields == [f[0] for f in N.MinibatchArgs._fields_]
 
 
+# rlppo_minibatch_workspace_bytes_for, bytes per (policy dims, critic dims) and mb: fp32 / bf16 / split-bf16 (precision 1 / 2 / 3; 0, the
+# process default, is fp32).  The values of the library before its workspace plan became one function: size and layout may not drift.
+WORKSPACE_BYTES = [
+    ([107, 256, 256, 256, 90], [107, 256, 256, 256, 1], {1: (1421400, 1427784, 1421400), 1500: (83491272, 93043288, 83491272),
+                                                         65536: (1041760520, 1459093784, 1041760520),
+                                                         524288: (7390888200, 10729554200, 7390888200)}),
+    ([231, 512, 512, 512, 512, 16], [231, 512, 512, 512, 512, 1], {1: (7719064, 7735976, 7719064), 1500: (113027272, 138371288, 113027272),
+                                                                   65536: (2409103624, 3516399896, 2409103624),
+                                                                   524288: (18697749768, 27556119832, 18697749768)}),
+    ([107, 64, 64, 90], [107, 64, 64, 1], {1: (301656, 302920, 301656), 1500: (19861448, 21733464, 19861448),
+                                           65536: (317149960, 398938904, 317149960), 524288: (2122842376, 2777153816, 2122842376)}),
+    ([21, 32, 8], [21, 32, 1], {1: (199448, 199784, 199448), 1500: (10873032, 11353048, 10873032),
+                                65536: (126213896, 147185432, 126213896), 524288: (612892936, 780665112, 612892936)}),
+    ([107, 256, 256, 90], [107, 512, 512, 1], {1: (1800280, 1806664, 1800280), 1500: (66073032, 75625048, 66073032),
+                                               65536: (1175847176, 1593180440, 1175847176)}),
+    ([107, 90], [107, 1], {1: (133720, 133960, 133720), 1500: (8248776, 8584792, 8248776), 65536: (148373768, 163053848, 148373768)}),
+    ([40, 128, 12], [40, 128, 1], {1: (205144, 206280, 205144), 1500: (13322184, 15002200, 13322184),
+                                   65536: (233168648, 306568984, 233168648)}),
+]
+
+
+def test_minibatch_workspace_bytes_are_pinned():
+    from rlgym_ppo_amd import _native as N
+    L = N.lib()
+    for pol, val, sizes in WORKSPACE_BYTES:
+        for mb, want in sizes.items():
+            got = tuple(L.rlppo_minibatch_workspace_bytes_for(N.dims_array(pol), len(pol) - 1, N.dims_array(val), len(val) - 1, mb, prec)
+                        for prec in (N.PRECISION_FP32, N.PRECISION_BF16, N.PRECISION_X3))
+            assert got == want, (pol, val, mb)
+            assert L.rlppo_minibatch_workspace_bytes_for(N.dims_array(pol), len(pol) - 1, N.dims_array(val), len(val) - 1, mb,
+                                                         N.PRECISION_DEFAULT) == want[0]
+
+
+def test_ppo_minibatch_rejects_bad_arguments_before_any_launch():
+    """An unknown head and a missing weight image are argument errors (1001, a message naming the argument) found before the first
+    HIP call: the host never dereferences the device pointers, so placeholders do, and no GPU is needed."""
+    from rlgym_ppo_amd import _native as N
+    L = N.lib()
+    pol, val = N.dims_array([107, 256, 256, 256, 90]), N.dims_array([107, 256, 256, 256, 1])
+
+    def call(precision, head=N.HEAD_DISCRETE, images=False):
+        a = N.MinibatchArgs()
+        a.head, a.pol_layers, a.val_layers, a.act_dim, a.slot, a.precision = head, 4, 4, 1, 0, precision
+        a.pol_dims = ctypes.cast(pol, ctypes.POINTER(ctypes.c_int32))
+        a.val_dims = ctypes.cast(val, ctypes.POINTER(ctypes.c_int32))
+        fake = iter(range(0x10000, 0x1000000, 0x1000))  # distinct, never dereferenced
+        for f in ("pol_packed", "val_packed", "pol_grad", "val_grad", "states", "actions", "old_logp", "targets", "advantages", "idx",
+                  "stats", "workspace"):
+            setattr(a, f, next(fake))
+        if images:
+            a.pol_packed_r, a.val_packed_r, a.pol_wb16, a.val_wb16 = next(fake), next(fake), next(fake), next(fake)
+        a.ld_states, a.n_rows, a.mb = 112, 5000, 1500
+        a.clip_range, a.ent_coef, a.mb_ratio, a.var_m, a.var_b = 0.2, 0.005, 1.0, 1.0, 0.0
+        a.ws_bytes = L.rlppo_minibatch_workspace_bytes_for(pol, 4, val, 4, a.mb, precision)
+        assert a.ws_bytes > 0
+        return L.rlppo_ppo_minibatch(None, ctypes.byref(a)), L.rlppo_last_error().decode()
+
+    rc, msg = call(N.PRECISION_FP32, head=99, images=True)
+    assert rc == 1001 and "head 99" in msg, (rc, msg)
+    rc, msg = call(N.PRECISION_X3)
+    assert rc == 1001 and "pol_wb16" in msg, (rc, msg)
+    rc, msg = call(N.PRECISION_BF16)
+    assert rc == 1001 and "rlppo_net_pack_bf16" in msg, (rc, msg)
+
+
 def test_mt19937_permutation_is_numpys_legacy_stream(golden):
     from rlgym_ppo_amd import _native as N
     from rlgym_ppo_amd.engine import LegacyPermutation

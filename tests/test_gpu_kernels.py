@@ -1095,10 +1095,15 @@ def test_g9_gaussian_and_multidiscrete_act(L, golden):
 
 
 # ---------------------------------------------------------------------------------------- PPO minibatch
+CANARY_BYTES = 4096
+
+
 def run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var=(0.1, 1.0),
-                  precision="fp32", ring=None):
+                  precision="fp32", ring=None, canary=False):
     """ring = base: the experience arrays are handed over as a ring of capacity len(obs_all) -- stored rotated so that logical row i
-    lives at physical row (i + base) % cap, with ring_base / ring_cap set; idx stays logical."""
+    lives at physical row (i + base) % cap, with ring_base / ring_cap set; idx stays logical.
+    canary: the workspace allocation carries CANARY_BYTES of a fixed pattern behind the bytes the pass is given, and the pass must
+    leave them as they were."""
     from rlgym_ppo_amd import _native as N
     if ring is not None and precision in ("fp32", "bf16", "x3"):
         rot = lambda x: np.roll(np.asarray(x), ring, axis=0)
@@ -1106,13 +1111,15 @@ def run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_al
     if precision == "bf16":  # the bf16-operand forward (rlppo_set_update_precision): same call with the rounded weight images
         check(L, L.rlppo_set_update_precision(1))
         try:
-            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "bf16*", ring)
+            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "bf16*", ring,
+                                 canary)
         finally:
             check(L, L.rlppo_set_update_precision(0))
     if precision == "x3":  # [r4] the split-bf16 hidden products (rlppo_set_update_precision(2)): same call with the three-plane images
         check(L, L.rlppo_set_update_precision(2))
         try:
-            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "x3*", ring)
+            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "x3*", ring,
+                                 canary)
         finally:
             check(L, L.rlppo_set_update_precision(0))
     P_, V_ = Net(L, pol), Net(L, val)
@@ -1129,7 +1136,11 @@ def run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_al
     idxd = dev(idx, torch.int64)
     stats = torch.zeros(8, dtype=torch.float64, device="cuda")
     mb = len(idx)
-    ws = torch.empty(int(L.rlppo_minibatch_workspace_bytes(P_.dims_c, P_.nl, V_.dims_c, V_.nl, mb)), dtype=torch.uint8, device="cuda")
+    ws_bytes = int(L.rlppo_minibatch_workspace_bytes(P_.dims_c, P_.nl, V_.dims_c, V_.nl, mb))
+    ws = torch.empty(ws_bytes + (CANARY_BYTES if canary else 0), dtype=torch.uint8, device="cuda")
+    tail = (torch.arange(CANARY_BYTES) * 37 % 251).to(torch.uint8)
+    if canary:
+        ws[ws_bytes:] = tail.cuda()
     a.pol_packed, a.val_packed, a.pol_grad, a.val_grad = P_.packed.data_ptr(), V_.packed.data_ptr(), gp.data_ptr(), gv.data_ptr()
     if precision == "bf16*":
         imgs = []
@@ -1152,9 +1163,11 @@ def run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_al
         a.ring_base, a.ring_cap = ring, len(obs_all)
     a.clip_range, a.ent_coef, a.mb_ratio = clip, ent, mb_ratio
     a.var_m, a.var_b = nets.var_map(*var)
-    a.stats, a.workspace, a.ws_bytes = stats.data_ptr(), ws.data_ptr(), ws.numel()
+    a.stats, a.workspace, a.ws_bytes = stats.data_ptr(), ws.data_ptr(), ws_bytes
     check(L, L.rlppo_ppo_minibatch(stream(), ctypes.byref(a)))
     torch.cuda.synchronize()
+    if canary:
+        assert torch.equal(ws[ws_bytes:].cpu(), tail), "the pass wrote behind the workspace it was given"
     return nets.unflatten(gp.cpu(), pol), nets.unflatten(gv.cpu(), val), stats.cpu().numpy()
 
 
@@ -1309,6 +1322,43 @@ def test_fused_gather_and_paired_launches_are_bitwise_neutral(L):
     for key in ("fused", "folded_value_head", "per_layer_dw"):
         fp64_gate.gate(L, "discrete", pol, val, obs[idx], acts[idx], old[idx], adv[idx], tgt[idx], 0.2, 0.005, 0.25, runs[key],
                        label=key + ", ragged 1500-row minibatch")
+
+
+def test_minibatch_stays_inside_its_workspace(L):
+    """The workspace size the library asks for (rlppo_minibatch_workspace_bytes) bounds what a pass writes: a fixed pattern behind
+    the bytes handed over survives one pass of every form -- fused gather + paired launches, separate gather + two chains,
+    split-bf16, bf16 -- for the discrete and the Gaussian head, and the gradients equal those of the same call without it."""
+    rs = np.random.RandomState(17)
+    d, n, mb, k = 107, 5000, 1500, 8
+    forms = dict(fused_paired=(2, 2, "fp32"), separate_two_chains=(0, 0, "fp32"), x3=(1, 1, "x3"), bf16=(1, 1, "bf16"))
+    for head, n_out in (("discrete", 90), ("gaussian", 2 * k)):
+        torch.manual_seed(17)
+        pol, val = nets.init_mlp(d, (256, 256, 256), n_out), nets.init_mlp(d, (256, 256, 256), 1)
+        obs = np.clip(rs.randn(n, d), -5, 5).astype(np.float32)
+        with torch.no_grad():
+            if head == "discrete":
+                act, logp = nets.discrete_sample(nets.discrete_probs(pol, obs), nets.draw_exp_noise(n, n_out))
+            else:
+                mean, std = nets.gauss_out(pol, obs, 0.1, 1.0)
+                act, logp = nets.gauss_sample(mean, std, torch.as_tensor(rs.randn(n, k).astype(np.float32)))
+        acts = act.numpy().astype(np.float32)
+        old = (logp.numpy() + 0.2 * rs.randn(n)).astype(np.float32)
+        tgt, adv = rs.randn(n).astype(np.float32), rs.randn(n).astype(np.float32)
+        idx = rs.randint(0, n, mb)
+        for form, (k26, k29, precision) in forms.items():
+            paired, fused = L.rlppo_dbg_counter(3), L.rlppo_dbg_counter(4)
+            check(L, L.rlppo_dbg_set(26, k26))
+            check(L, L.rlppo_dbg_set(29, k29))
+            try:
+                plain = run_minibatch(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.25, precision=precision)
+                fenced = run_minibatch(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.25, precision=precision, canary=True)
+            finally:
+                check(L, L.rlppo_dbg_set(26, 1))
+                check(L, L.rlppo_dbg_set(29, 1))
+            if form == "fused_paired":
+                assert L.rlppo_dbg_counter(3) == paired + 2 and L.rlppo_dbg_counter(4) == fused + 2, head
+            for (a, b), (c, e) in zip(plain[0] + plain[1], fenced[0] + fenced[1]):
+                assert torch.equal(a, c) and torch.equal(b, e), (head, form)
 
 
 def test_minibatch_full_size_cfg2(L):
