@@ -35,7 +35,7 @@ extern "C" {
  * the matching pop have default visibility (`nm -D` shows them and nothing else of the library's own; tests/test_abi_and_layout.py). */
 #pragma GCC visibility push(default)
 
-#define RLPPO_ABI_VERSION 7
+#define RLPPO_ABI_VERSION 8
 #define RLPPO_MAX_LAYERS 16
 
 #define RLPPO_OK 0
@@ -122,6 +122,18 @@ typedef struct rlppo_act_opts {
     uint32_t done_value;
     uint32_t *done_words;
     uint32_t *noise_ctl;
+    /* [ABI 8] invalid-action masking (discrete head: rlppo_discrete_act / _step / _probs; any other entry point answers
+     * RLPPO_ERR_ARG).  action_mask: DEVICE [n][mask_words] words, mask_words == ceil(n_actions / 32), bit c % 32 of word c / 32 set =
+     * action c is valid in that row; bits at and beyond n_actions are ignored; NULL = no mask (the call is the unmasked one, launch
+     * for launch).  Semantics: an invalid action's logit is -inf (what the padded columns c >= n_actions always were), so
+     * p = softmax(z') is exactly 0 on it; pc = clamp(p, 1e-11, 1) on valid actions; action = first arg-max over VALID c of
+     * pc_c / q_c (the clamp's floor never makes an invalid action selectable), logp = log(pc_action).  noise_q stays
+     * [n][n_actions]: the entries of invalid actions are ignored.  probs_out / rlppo_discrete_probs (with and without clamp_probs)
+     * hold 0 on invalid actions and flat_argmax runs over valid entries only.  A row without a valid action is treated as all-valid
+     * (hosts reject such rows before they get here).  An all-valid mask gives the unmasked results bit for bit.  Not together with
+     * noise_ctl (rlppo_discrete_step_one_launch answers 0 for that pair, rlppo_discrete_step RLPPO_ERR_ARG). */
+    const uint32_t *action_mask;
+    int32_t mask_words;
 } rlppo_act_opts;
 int64_t rlppo_act_done_words(int64_t n);
 /* HOST: spins until words[0..count) all hold `value` (acquire loads) or timeout_us has passed; 0 = all there, 1 = timed out,
@@ -294,6 +306,17 @@ typedef struct rlppo_minibatch_args {
                                      launch, [1] <- mb_ratio, [2 + w] <- workgroup w's sum of the RLPPO_STAT_KL term (read by
                                      rlppo_kl_gate); NULL = not armed */
     const uint32_t *stop_word;    /* device; once non-zero, the pass adds nothing to `stats`; NULL = never */
+    /* [ABI 8] invalid-action masking, discrete head only (another head: RLPPO_ERR_ARG).  action_mask: [N][mask_words] words, a
+     * buffer field like `actions` (row idx[r] through the ring map), mask_words == ceil(n_actions / 32), encoding as in
+     * rlppo_act_opts; NULL = off (the parent's launches).  The loss kernel reads the words ITSELF through idx / ring_base / ring_cap --
+     * they do not travel with the minibatch gather, so the workspace of a pass (rlppo_minibatch_workspace_bytes) and its gather
+     * launches are those of the unmasked pass in every form.  Loss: log p_a, ratio, surrogate, KL and clip fraction as without a
+     * mask on the masked pc; entropy = -sum over valid c of pc_c log pc_c; dL/dz_c = 0 exactly on invalid actions, on valid ones the
+     * unmasked chain (softmax Jacobian, the clamp's zero-gradient region, torch.min's tie rule) restricted to the valid set.  A stored
+     * action its own mask marks invalid is a caller error: pc_a = 1e-11, zero gradient, finite.  A row without a valid action
+     * counts as all-valid. */
+    const uint32_t *action_mask;
+    int32_t mask_words;
 } rlppo_minibatch_args;
 
 #define RLPPO_STAT_ENTROPY 0     /* += entropy of this minibatch (mean over rows)            ppo_learner.py:184 */

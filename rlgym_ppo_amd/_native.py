@@ -11,7 +11,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_siz
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RLPPO_LIB") or os.path.join(HERE, "librlppo.so")  # RLPPO_LIB: an alternative build (A/B of compile-time variants)
-ABI_VERSION = 7
+ABI_VERSION = 8
 COMM_ID_BYTES = 128  # RLPPO_COMM_ID_BYTES
 MAX_LAYERS = 16
 N_STATS = 8
@@ -45,7 +45,8 @@ class OptNet(ctypes.Structure):
 
 class ActOpts(ctypes.Structure):
     """struct rlppo_act_opts (include/rlppo.h)."""
-    _fields_ = [("precision", c_int32), ("done_value", c_uint32), ("done_words", c_void_p), ("noise_ctl", c_void_p)]
+    _fields_ = [("precision", c_int32), ("done_value", c_uint32), ("done_words", c_void_p), ("noise_ctl", c_void_p),
+                ("action_mask", c_void_p), ("mask_words", c_int32)]
 
 
 class ReportArgs(ctypes.Structure):
@@ -78,6 +79,7 @@ class MinibatchArgs(ctypes.Structure):
         ("clip_range", c_float), ("ent_coef", c_float), ("mb_ratio", c_float), ("var_m", c_float), ("var_b", c_float),
         ("stats", c_void_p), ("workspace", c_void_p), ("ws_bytes", c_size_t),
         ("adv_norm", c_void_p), ("value_clip", c_float), ("kl_slots", c_void_p), ("stop_word", c_void_p),
+        ("action_mask", c_void_p), ("mask_words", c_int32),
     ]
 
 

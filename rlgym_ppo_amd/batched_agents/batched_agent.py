@@ -5,6 +5,7 @@ side of the protocol can be swapped for the reference's."""
 import pickle
 import socket
 import time
+import warnings
 
 import numpy as np
 
@@ -66,6 +67,10 @@ def batched_agent_process(proc_id, endpoint, shm_buffer, shm_offset, shm_size, s
                 env = build_env_fn()
         if hasattr(env.action_space, "seed"):
             env.action_space.seed(seed)
+        if proc_id == 0 and hasattr(env, "action_masks"):  # (said once: by the first worker)
+            warnings.warn("the environment offers action_masks(), but process-mode collection has no room for a mask in its wire "
+                          "format (the reference's, byte for byte): running UNMASKED.  Invalid-action masking needs "
+                          "Learner(..., vector_env=True).")
         obs = np.asarray(env.reset(), dtype=np.float32)
         shape = [float(d) for d in obs.shape]
         n_agents = int(shape[0]) if len(shape) > 1 else 1

@@ -18,12 +18,16 @@ is its own trajectory stream (tests/test_gpu_vector_rollout.py compares with a n
 
 Environment interface: `reset() -> obs [n, d]`; `step(actions [n, k]) -> (obs [n, d], rewards [n], dones [n],
 truncated [n], info)` with auto-reset of finished agents; `observation_space.shape`, `action_space` as in the reference.
+Optional (the sb3-contrib convention, discrete policy only): `action_masks() -> [n, n_actions]` booleans for the observation
+the agents act on next, called after `reset()` and after every `step()`; the policy then samples valid actions only and the
+masks leave the collect trajectory-major as `self.action_mask_rows` (next to `value_input_rows`).
 """
 import time
 
 import numpy as np
 import torch
 
+from ..util import action_mask as AM
 from ..util.running_stats import WelfordRunningStat
 from .batched_agent import describe_action_space
 
@@ -46,6 +50,29 @@ class VectorAgentManager(object):
         self._next_rows = None        # padded device rows of the observation the agents act on next
         self._pending_obs = None      # fused collect: (raw device observations, standardisation scalars) the agents act on next
         self._ep_rews = None
+        self.action_mask_rows = None  # util.action_mask.Packed [N, W] of the last collect (trajectory-major), or None: env without masks
+        self._pending_mask = None     # packed device words [n_agents, W] of the observation the agents act on next
+
+    def _env_mask(self):
+        """The environment's action_masks() for the observation the agents act on next, packed on the device; None without it."""
+        fn = getattr(self.env, "action_masks", None)
+        if fn is None:
+            return None
+        from ..ppo.discrete_policy import DiscreteFF
+        if not isinstance(self.policy, DiscreteFF):
+            raise ValueError("the environment offers action_masks(): invalid-action masking is an option of the discrete head "
+                             f"(DiscreteFF), not of {type(self.policy).__name__}")
+        return AM.pack(np.asarray(fn()), self.policy.n_actions, self.policy.arena.device)
+
+    def _masks_out(self, M, na, T):
+        """Time-major words [T, na, W] -> self.action_mask_rows, trajectory-major (row a * T + t)."""
+        self.action_mask_rows = None if M is None else AM.Packed(M.transpose(0, 1).reshape(na * T, M.shape[2]).contiguous(),
+                                                                 self.policy.n_actions)
+
+    @property
+    def action_masks(self):
+        """bool [N, n_actions] of the last collect, trajectory-major; None when the environment has no action_masks()."""
+        return None if self.action_mask_rows is None else self.action_mask_rows.unpack()
 
     # same signature as BatchedAgentManager.init_processes (learner.py:140-150); n_processes is ignored
     def init_processes(self, n_processes, build_env_fn, collect_metrics_fn=None, spawn_delay=None, render=False,
@@ -62,6 +89,7 @@ class VectorAgentManager(object):
             self.obs_stats = WelfordRunningStat(shape=d)                      # (batched_agent_manager.py:366-384)
             self.obs_stats.increment(obs, obs.shape[0])
         self._initial_obs = obs
+        self._initial_mask_pending = hasattr(self.env, "action_masks")  # read once the policy exists (first collect)
         n_acts, code = describe_action_space(self.env.action_space)
         return int(np.prod(self.env.observation_space.shape)), int(n_acts), int(code)
 
@@ -113,15 +141,25 @@ class VectorAgentManager(object):
             self._pending_obs = (torch.from_numpy(np.ascontiguousarray(self._initial_obs)).to(dev), None)
         obs_dev, scalars = self._pending_obs
         stage = self._obs_staging(na, arena.d_in)
+        mask, M = self._first_mask(), None
         for t in range(T):
-            a_host, _ = self.policy.step(obs_dev, standardize=scalars, rows_out=S[t], actions_f32=acts_tm[t], logp_out=logp_tm[t],
-                                         to_host="actions")
+            if mask is not None:
+                if M is None:
+                    M = torch.empty((T, na, mask.shape[1]), dtype=torch.int32, device=dev)
+                M[t].copy_(mask)
+                a_host, _ = self.policy.step(obs_dev, standardize=scalars, rows_out=S[t], actions_f32=acts_tm[t], logp_out=logp_tm[t],
+                                             to_host="actions", action_mask=AM.Packed(M[t], self.policy.n_actions))
+            else:
+                a_host, _ = self.policy.step(obs_dev, standardize=scalars, rows_out=S[t], actions_f32=acts_tm[t], logp_out=logp_tm[t],
+                                             to_host="actions")
             step = self.env.step(a_host.numpy().astype(np.float32).reshape(na, -1))
             if len(step) == 4:
                 obs, r, d, info = step
                 tr = 0.0
             else:
                 obs, r, d, tr, info = step
+            if mask is not None:
+                mask = self._env_mask()             # describes `obs`, the observation of step t + 1
             pin_t, pin_np = stage[t % len(stage)]   # (reused three steps later: every step ends in a stream synchronisation)
             np.copyto(pin_np, obs, casting="unsafe")
             obs_dev = pin_t.to(dev, non_blocking=True)                         # raw observations: one asynchronous upload per step
@@ -139,6 +177,8 @@ class VectorAgentManager(object):
             self._track_rewards(row[0], (row[1] + row[2]) > 0)
         arena.stage_obs(obs_dev, scalars, out=S[T])          # the rows the agents act on next = next_states of the last step
         self._pending_obs = (obs_dev, scalars)
+        self._pending_mask = mask
+        self._masks_out(M, na, T)
         if getattr(self.policy, "noise_mode", None) == "host" and hasattr(self.policy, "prefetch_noise"):
             # the NEXT collect's T draws of the reference's CPU noise stream, produced on the helper threads while the value pass,
             # the GAE scan and PPOLearner.learn run (none of them touches torch's CPU generator; if anything does, the chain is
@@ -184,8 +224,15 @@ class VectorAgentManager(object):
         if self._next_rows is None:
             self._next_rows = arena.stage_obs(self._initial_obs)
         rows = self._next_rows
+        mask, M = self._first_mask(), None
         for t in range(T):
-            a_dev, lp_dev = self.policy.act_padded(rows)
+            if mask is not None:
+                if M is None:
+                    M = torch.empty((T, na, mask.shape[1]), dtype=torch.int32, device=dev)
+                M[t].copy_(mask)
+                a_dev, lp_dev = self.policy.act_padded(rows, action_mask=AM.Packed(M[t], self.policy.n_actions))
+            else:
+                a_dev, lp_dev = self.policy.act_padded(rows)
             if acts is None:
                 k = 1 if a_dev.dim() == 1 else a_dev.shape[1]
                 acts = torch.empty((na, T, k), dtype=torch.float32, device=dev)
@@ -199,6 +246,8 @@ class VectorAgentManager(object):
                 tr = np.zeros(na, np.float32)
             else:
                 obs, r, d, tr, info = step
+            if mask is not None:
+                mask = self._env_mask()             # describes `obs`, the observation of step t + 1
             obs = np.asarray(obs, dtype=np.float32)
             obs_dev = torch.from_numpy(np.ascontiguousarray(obs)).to(dev)   # raw observations: one upload per step
             rews[:, t], dones[:, t], trunc[:, t] = r, d, tr
@@ -219,9 +268,19 @@ class VectorAgentManager(object):
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x.reshape(-1))).to(dev)
         self.value_input_rows = flat
         self._next_rows = rows
+        self._pending_mask = mask
+        self._masks_out(M, na, T)
         self.cumulative_timesteps += N_
         experience = (flat[:N_], acts.view(N_, -1), logp.view(N_), up(rews), nxt_flat, up(dones), up(trunc))
         return experience, metrics, N_, time.perf_counter() - t1
+
+    def _first_mask(self):
+        """The mask of the observation a collect starts on: the one left by the previous collect, or -- first collect -- the
+        environment's answer after its reset()."""
+        if self._initial_mask_pending:
+            self._initial_mask_pending = False
+            self._pending_mask = self._env_mask()
+        return self._pending_mask
 
     def _increment_obs_stats(self, obs_dev):
         """WelfordRunningStat.increment(obs, n) on the device (bit-exact with the host class's sample-by-sample update in the

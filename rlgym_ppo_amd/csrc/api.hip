@@ -287,9 +287,12 @@ struct ActCtx {
     unsigned *done = nullptr;
     unsigned done_value = 0;
     unsigned *noise_ctl = nullptr;
+    const unsigned *mask = nullptr;  // [ABI 8] rlppo_act_opts.action_mask / mask_words
+    int mask_words = 0;
 };
 // late_noise: the entry point can take its noise while it runs (rlppo_act_opts.noise_ctl; rlppo_discrete_step alone)
-static int act_ctx(const rlppo_act_opts *o, ActCtx *c, bool late_noise = false) {
+// mask_for: nullptr = the entry point samples the discrete head and takes an action mask; else the name of what it runs instead
+static int act_ctx(const rlppo_act_opts *o, ActCtx *c, bool late_noise = false, const char *mask_for = nullptr) {
     c->bf16 = get_infer_bf16();
     if (!o) return 0;
     RLPPO_CHECK_ARG(o->precision == RLPPO_PRECISION_DEFAULT || o->precision == RLPPO_PRECISION_FP32 || o->precision == RLPPO_PRECISION_BF16,
@@ -298,9 +301,18 @@ static int act_ctx(const rlppo_act_opts *o, ActCtx *c, bool late_noise = false) 
     c->done = o->done_words;
     c->done_value = o->done_value;
     c->noise_ctl = o->noise_ctl;
+    c->mask = o->action_mask;
+    c->mask_words = o->mask_words;
+    RLPPO_CHECK_ARG(!o->action_mask || !mask_for, "act options: action_mask is an option of the discrete head, not of %s", mask_for ? mask_for : "");
     RLPPO_CHECK_ARG(!o->noise_ctl || late_noise, "act options: noise_ctl is an option of rlppo_discrete_step");
     RLPPO_CHECK_ARG(!o->noise_ctl || (o->done_words && !(o->done_value & 0x80000000u)),
                     "act options: noise_ctl needs done_words (a kernel that gives up on the noise reports it there) and done_value < 2^31");
+    return 0;
+}
+// [ABI 8] a call's mask has the width its action count needs
+static int act_mask_check(const ActCtx &c, int n_actions) {
+    RLPPO_CHECK_ARG(!c.mask || c.mask_words == (n_actions + 31) / 32, "act options: mask_words=%d, but n_actions=%d needs %d words per row",
+                    c.mask_words, n_actions, (n_actions + 31) / 32);
     return 0;
 }
 // the completion words of a call whose last launch does not write them itself: one more (tiny) launch behind it
@@ -365,7 +377,7 @@ int rlppo_mlp_forward(void *stream, const int32_t *dims, int32_t n_layers, const
     int rc = make_layout(dims, n_layers, &net);
     if (rc) return rc;
     ActCtx cx;
-    rc = act_ctx(opts, &cx);
+    rc = act_ctx(opts, &cx, false, "rlppo_mlp_forward");
     if (rc) return rc;
     if (n == 0) return 0;
     RLPPO_CHECK_ARG(n > 0 && packed && obs && out && workspace, "mlp_forward: bad argument");
@@ -388,6 +400,8 @@ int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     if (rc) return rc;
     if (n == 0) return 0;
     RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_q && actions && logp && workspace, "discrete_act: bad argument");
+    rc = act_mask_check(cx, dims[n_layers]);
+    if (rc) return rc;
     // [r3] one launch for the whole step when the network has the form fused_act.hip covers (fp32 inference precision); the
     // layer-by-layer chain below otherwise -- bit-identical results either way
     if (g_fused_act && !cx.bf16 && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS && ld_obs >= net.L[0].pin && ld_obs % 4 == 0 &&
@@ -401,6 +415,8 @@ int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, cons
         io.probs_out = probs_out;
         io.done_words = cx.done;
         io.done_value = cx.done_value;
+        io.mask = cx.mask;
+        io.mask_words = cx.mask_words;
         ++g_cnt_fused_act;
         return launch_discrete_act_fused((hipStream_t)stream, net, packed, io, n);
     }
@@ -409,7 +425,7 @@ int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     int64_t ldo;
     rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
     if (rc) return rc;
-    rc = launch_discrete_sample_logits((hipStream_t)stream, o, ldo, n, dims[n_layers], noise_q, actions, logp, probs_out);
+    rc = launch_discrete_sample_logits((hipStream_t)stream, o, ldo, n, dims[n_layers], noise_q, actions, logp, probs_out, cx.mask, cx.mask_words);
     return rc ? rc : act_done((hipStream_t)stream, cx, n);
 }
 
@@ -451,6 +467,7 @@ int rlppo_discrete_step_one_launch(const int32_t *dims, int32_t n_layers, int64_
     if (make_layout(dims, n_layers, &net)) return -1;
     ActCtx cx;
     if (act_ctx(opts, &cx, true)) return -1;
+    if (cx.mask && cx.noise_ctl) return 0;  // [ABI 8] a masked call has no late-noise form: the general path
     return g_fused_act && !cx.bf16 && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
 }
 
@@ -470,6 +487,9 @@ int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, con
     RLPPO_CHECK_ARG(ld_obs >= d && standardize >= 0 && standardize <= 2 && (standardize != 2 || (mean_v && std_v)),
                     "discrete_step: ld_obs=%ld standardize=%d", (long)ld_obs, standardize);
     RLPPO_CHECK_ARG(!rows_out || ld_rows_out >= pin, "discrete_step: ld_rows_out=%ld < padded width %d", (long)ld_rows_out, pin);
+    rc = act_mask_check(cx, dims[n_layers]);
+    if (rc) return rc;
+    RLPPO_CHECK_ARG(!(cx.mask && cx.noise_ctl), "discrete_step: action_mask and noise_ctl exclude each other (a masked call takes its noise before the launch)");
     hipStream_t st = (hipStream_t)stream;
     if (g_fused_act && !cx.bf16 && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
         FusedActIO io;
@@ -490,6 +510,8 @@ int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, con
         io.done_words = cx.done;
         io.done_value = cx.done_value;
         io.noise_ctl = cx.noise_ctl;
+        io.mask = cx.mask;
+        io.mask_words = cx.mask_words;
         ++g_cnt_fused_act;
         return launch_discrete_act_fused(st, net, packed, io, n);
     }
@@ -516,7 +538,7 @@ int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, con
     int64_t ldo;
     rc = forward_pingpong(st, net, packed, rows, ld_rows, n, 0, ws, ws_bytes, nullptr, &o, &ldo, cx.bf16);
     if (rc) return rc;
-    rc = launch_discrete_sample_logits(st, o, ldo, n, dims[n_layers], noise_q, actions, logp, nullptr);
+    rc = launch_discrete_sample_logits(st, o, ldo, n, dims[n_layers], noise_q, actions, logp, nullptr, cx.mask, cx.mask_words);
     if (rc == 0 && actions_f32) rc = launch_i64_to_f32(st, actions, actions_f32, n);
     return rc ? rc : act_done(st, cx, n);
 }
@@ -534,11 +556,14 @@ int rlppo_discrete_probs(void *stream, const int32_t *dims, int32_t n_layers, co
     RLPPO_CHECK_ARG(n > 0 && packed && obs && workspace && (probs_out || flat_argmax), "discrete_probs: bad argument");
     RLPPO_CHECK_ARG(!probs_out || ld_probs >= dims[n_layers], "discrete_probs: ld_probs %lld < n_actions %d", (long long)ld_probs,
                     dims[n_layers]);
+    rc = act_mask_check(cx, dims[n_layers]);
+    if (rc) return rc;
     const float *o;
     int64_t ldo;
     rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
     if (rc) return rc;
-    rc = launch_discrete_probs((hipStream_t)stream, o, ldo, n, dims[n_layers], clamp_probs != 0, probs_out, ld_probs, flat_argmax);
+    rc = launch_discrete_probs((hipStream_t)stream, o, ldo, n, dims[n_layers], clamp_probs != 0, probs_out, ld_probs, flat_argmax, cx.mask,
+                               cx.mask_words);
     return rc ? rc : act_done((hipStream_t)stream, cx, n);
 }
 
@@ -556,7 +581,7 @@ int rlppo_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     int rc = make_layout(dims, n_layers, &net);
     if (rc) return rc;
     ActCtx cx;
-    rc = act_ctx(opts, &cx);
+    rc = act_ctx(opts, &cx, false, "the Gaussian head (rlppo_gaussian_act)");
     if (rc) return rc;
     if (n == 0) return 0;
     RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_eps && actions && logp && workspace, "gaussian_act: bad argument");
@@ -576,7 +601,7 @@ int rlppo_multidiscrete_act(void *stream, const int32_t *dims, int32_t n_layers,
     int rc = make_layout(dims, n_layers, &net);
     if (rc) return rc;
     ActCtx cx;
-    rc = act_ctx(opts, &cx);
+    rc = act_ctx(opts, &cx, false, "the multi-discrete head (rlppo_multidiscrete_act)");
     if (rc) return rc;
     if (n == 0) return 0;
     RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_q && actions && logp && workspace, "multidiscrete_act: bad argument");
@@ -1056,8 +1081,15 @@ static int policy_loss(hipStream_t st, const Pass &p) {
     const int last = p.pol.n_layers - 1;
     const LayerLayout &L = p.pol.L[last];
     const WsPlan &w = p.w;
-    if (a.head == RLPPO_HEAD_DISCRETE)
-        return launch_discrete_loss(st, w.pol.act[last], L.pout, L.out, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
+    if (a.head == RLPPO_HEAD_DISCRETE) {
+        MaskRows mr;  // [ABI 8] the masked loss reads the buffer's mask rows through idx and the ring map itself
+        mr.mask = a.action_mask;
+        mr.W = a.mask_words;
+        mr.idx = a.idx;
+        mr.ring_base = p.ring_base;
+        mr.ring_cap = p.ring_cap;
+        return launch_discrete_loss(st, w.pol.act[last], L.pout, L.out, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, a.action_mask ? &mr : nullptr);
+    }
     if (a.head == RLPPO_HEAD_GAUSSIAN)
         return launch_gaussian_loss(st, w.pol.act[last], L.pout, L.out / 2, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
     return launch_multidiscrete_loss(st, w.pol.act[last], L.pout, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
@@ -1282,6 +1314,11 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
     const int n_out = pol.L[pol.n_layers - 1].out;
     RLPPO_CHECK_ARG(a->head == RLPPO_HEAD_DISCRETE || a->head == RLPPO_HEAD_GAUSSIAN || a->head == RLPPO_HEAD_MULTIDISCRETE,
                     "ppo_minibatch: unknown head %d", a->head);
+    // [ABI 8] action masks: the discrete head alone, ceil(A / 32) words per buffer row
+    RLPPO_CHECK_ARG(!a->action_mask || a->head == RLPPO_HEAD_DISCRETE, "ppo_minibatch: action_mask is an option of the discrete head, not of the %s head",
+                    a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : "multi-discrete");
+    RLPPO_CHECK_ARG(!a->action_mask || a->mask_words == (n_out + 31) / 32, "ppo_minibatch: mask_words=%d, but n_actions=%d needs %d words per row",
+                    a->mask_words, n_out, (n_out + 31) / 32);
     if (a->head == RLPPO_HEAD_DISCRETE) {
         RLPPO_CHECK_ARG(a->act_dim == 1, "discrete head: act_dim must be 1");
         RLPPO_CHECK_ARG(pol.L[pol.n_layers - 1].pout <= DISCRETE_LOSS_MAX_LD, "discrete head: padded width %ld too large",

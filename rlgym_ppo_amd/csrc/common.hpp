@@ -214,9 +214,19 @@ __host__ __device__ __forceinline__ int64_t ring_row(int64_t i, int64_t base, in
     const int64_t r = i + base;
     return r >= cap ? r - cap : r;
 }
-int launch_discrete_sample_logits(hipStream_t, const float *, int64_t, int64_t, int, const float *, int64_t *, float *, float *);
+// [ABI 8] action masks: mask (optional) = [n][mask_words] words, bit c % 32 of word c / 32 set = action c valid
+int launch_discrete_sample_logits(hipStream_t, const float *, int64_t, int64_t, int, const float *, int64_t *, float *, float *,
+                                  const unsigned *mask = nullptr, int mask_words = 0);
 int launch_discrete_probs(hipStream_t st, const float *logits, int64_t ld, int64_t n, int A, int clamp, float *probs,
-                          int64_t ld_p, int64_t *flat_argmax);
+                          int64_t ld_p, int64_t *flat_argmax, const unsigned *mask = nullptr, int mask_words = 0);
+// [ABI 8] where the masked loss kernels find a pass's mask words: row r of the pass = the buffer's physical row
+// ring_row(idx[r], ring_base, ring_cap) of mask[N][W] -- read in the loss kernel itself, not brought along by the gather
+struct MaskRows {
+    const unsigned *mask = nullptr;
+    int W = 0;
+    const int64_t *idx = nullptr;
+    int64_t ring_base = 0, ring_cap = INT64_MAX;
+};
 int launch_categorical_select(hipStream_t, const float *, int64_t, int64_t, int, const float *, int64_t *, float *);
 int launch_gaussian_sample(hipStream_t, const float *, int64_t, int64_t, int, const float *, float, float, float *, float *,
                            unsigned *done_words = nullptr, unsigned done_value = 0);
@@ -227,7 +237,8 @@ int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const float *tar
 int64_t kl_slots_doubles(int64_t mb);  // rlppo_kl_slots_doubles
 constexpr int64_t DISCRETE_LOSS_MAX_LD = 64 * 32;  // padded logits per row of the widest discrete loss kernel (one wave, 32 per lane)
 // the policy loss of one head on its outputs [mb][ld], in place, from the gathered per-row actions, old log-probabilities and advantages
-int launch_discrete_loss(hipStream_t, float *, int64_t, int, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
+int launch_discrete_loss(hipStream_t, float *, int64_t, int, const float *, const float *, const float *, int64_t, const LossCfg &, double *,
+                         const MaskRows *mask_rows = nullptr);
 int launch_gaussian_loss(hipStream_t, float *, int64_t, int, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
 int launch_multidiscrete_loss(hipStream_t, float *, int64_t, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
 
@@ -249,6 +260,8 @@ struct FusedActIO {
     unsigned *done_words = nullptr;  // [r5] optional, host-visible: word b <- done_value once the outputs of rows 16 b .. 16 b + 15 are visible
     unsigned done_value = 0;
     unsigned *noise_ctl = nullptr;  // [r5] optional control words of noise the host writes after the launch (rlppo_act_opts)
+    const unsigned *mask = nullptr;  // [ABI 8] optional action mask [n][mask_words] (not together with noise_ctl)
+    int mask_words = 0;
 };
 bool fused_act_ok(const NetLayout &net);
 }  // namespace rlppo

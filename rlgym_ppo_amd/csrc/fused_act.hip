@@ -11,6 +11,8 @@
 //     ahead, ACROSS layer boundaries (weights do not depend on activations) and waits with counted vmcnt -- no workgroup barrier
 //     in the K loop, one per layer for the activations;
 //   * the head's logits go to LDS and the waves sample 16 / NW rows each with the code of discrete_sample_kernel.
+// [ABI 8] MASKED instantiations: the sampling stage reads the (<= 4) mask words of its rows -- requested with the noise, before the
+// layers -- and treats invalid actions as the padded columns c >= A (heads.hip); no late-noise form (a.noise_ctl is NULL there).
 // Arithmetic is that of the chain, operation for operation (accumulators start from the bias, k in tiles of 16 through the same
 // v_mfma_f32_16x16x4_f32 sequence, relu as v_med3, the same softmax / division / arg-max order): logits, actions and
 // log-probabilities are BIT-identical to the layer-by-layer path (tests/test_gpu_kernels.py).
@@ -58,6 +60,8 @@ struct FusedActArgs {
     // [r5] noise that arrives WHILE the kernel runs (rlppo_act_opts.noise_ctl): {sequence of this call, rows that are sampled,
     // sequence of the noise that is complete in `noise`, 2 statistics words} in memory the host writes directly
     unsigned *noise_ctl;
+    const unsigned *mask;    // [ABI 8] MASKED instantiations: [n][mask_words] action-mask words (bit c % 32 of word c / 32 = action c valid)
+    int mask_words;
 };
 
 // 20 ms of the 100 MHz wall clock (100-1000 x what the host needs for the draw): a host that is held up between launch and publish --
@@ -85,7 +89,7 @@ __device__ __forceinline__ float fa_xor_f(float v) { return __int_as_float(fa_xo
 // H = 256 runs 8 waves x 2 blocks: with one wave per SIMD (4 x 4) a K-step was LDS-DMA issue (4 pieces, ~100 cycles each) + fragment
 // reads + 16 MFMAs one after the other, ~1350 cycles for 512 cycles of MFMA (36 us per 4096-row step); two waves per SIMD take
 // turns on the MFMA pipe.
-template <int JH, int NW>
+template <int JH, int NW, bool MASKED = false>
 __global__ __launch_bounds__(64 * NW, 1) void discrete_act_fused_kernel(FusedActArgs a) {
     constexpr int H = 16 * JH * NW, NT = 64 * NW, RPWV = FA_ROWS / NW;  // rows each wave samples
     constexpr int TILE = JH * 16 * 16;  // floats of one wave's weight tile (JH*16 rows x 16 k)
@@ -171,6 +175,17 @@ __global__ __launch_bounds__(64 * NW, 1) void discrete_act_fused_kernel(FusedAct
             const int c = lane + 64 * e;
             qn[rr][e] = (!a.noise_ctl && row < a.n && c < a.A) ? a.noise[row * a.A + c] : 1.f;
         }
+    // [ABI 8] the mask word of each of this lane's two elements (c = lane + 64 e sits in word (lane >> 5) + 2 e, bit lane & 31)
+    unsigned mw[RPWV][2];
+    if (MASKED) {
+#pragma unroll
+        for (int rr = 0; rr < RPWV; ++rr)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int64_t row = row0 + wave * RPWV + rr;
+                mw[rr][e] = (row < a.n && lane + 64 * e < a.A) ? a.mask[row * a.mask_words + (lane >> 5) + 2 * e] : 0u;
+            }
+    }
     // ---- stage the 16 observation rows into act0 (K-step-major image), zero rows past n
     if (a.rows) {
         const int cpr = a.k[0] / 4;  // 16-byte chunks per row
@@ -391,6 +406,20 @@ __global__ __launch_bounds__(64 * NW, 1) void discrete_act_fused_kernel(FusedAct
         float p[RPWV][2], pc[RPWV][2], mx[RPWV], sm[RPWV], best[RPWV], bestp[RPWV];
         int besti[RPWV];
         bool live[RPWV];
+        // (MASKED) element c takes part: c < A and its action is valid -- a row without a valid action is all-valid; the unmasked
+        // instantiations test c < A where they always did
+        bool ok[RPWV][2];
+        if (MASKED) {
+#pragma unroll
+            for (int rr = 0; rr < RPWV; ++rr) {
+                const bool i0 = lane < A, i1 = lane + 64 < A;
+                const bool v0 = i0 && ((mw[rr][0] >> (lane & 31)) & 1u), v1 = i1 && ((mw[rr][1] >> (lane & 31)) & 1u);
+                const bool any = __ballot(v0 || v1) != 0;  // (wave-uniform)
+                ok[rr][0] = any ? v0 : i0;
+                ok[rr][1] = any ? v1 : i1;
+            }
+        }
+#define FA_IN(rr, e, c) (MASKED ? ok[rr][e] : (c) < A)
 #pragma unroll
         for (int rr = 0; rr < RPWV; ++rr) {
             const int r = wave * RPWV + rr;
@@ -400,7 +429,7 @@ __global__ __launch_bounds__(64 * NW, 1) void discrete_act_fused_kernel(FusedAct
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int c = lane + 64 * e;
-                p[rr][e] = c < A ? z[c] : -INFINITY;
+                p[rr][e] = FA_IN(rr, e, c) ? z[c] : -INFINITY;
                 mx[rr] = fmaxf(mx[rr], p[rr][e]);
             }
         }
@@ -414,7 +443,7 @@ __global__ __launch_bounds__(64 * NW, 1) void discrete_act_fused_kernel(FusedAct
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int c = lane + 64 * e;
-                p[rr][e] = c < A ? expf(p[rr][e] - mx[rr]) : 0.f;
+                p[rr][e] = FA_IN(rr, e, c) ? expf(p[rr][e] - mx[rr]) : 0.f;
                 sm[rr] += p[rr][e];
             }
         }
@@ -435,7 +464,7 @@ __global__ __launch_bounds__(64 * NW, 1) void discrete_act_fused_kernel(FusedAct
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int c = lane + 64 * e;
-                if (c < A) {
+                if (FA_IN(rr, e, c)) {
                     const float v = pc[rr][e] / qn[rr][e];  // IEEE fp32 division, as at::div
                     if (v > best[rr]) {
                         best[rr] = v;
@@ -443,6 +472,8 @@ __global__ __launch_bounds__(64 * NW, 1) void discrete_act_fused_kernel(FusedAct
                         bestp[rr] = pc[rr][e];
                     }
                     if (a.probs_out && live[rr]) a.probs_out[row * A + c] = pc[rr][e];
+                } else if (MASKED && c < A) {
+                    if (a.probs_out && live[rr]) a.probs_out[row * A + c] = 0.f;
                 }
             }
         }
@@ -459,6 +490,7 @@ __global__ __launch_bounds__(64 * NW, 1) void discrete_act_fused_kernel(FusedAct
     }
         FA_BFLY(FA_ARG_STEP)
 #undef FA_ARG_STEP
+#undef FA_IN
 #undef FA_SUM_STEP
 #undef FA_MAX_STEP
 #undef FA_BFLY
@@ -558,13 +590,22 @@ int launch_discrete_act_fused(hipStream_t st, const NetLayout &net, const float 
     a.done_words = io.done_words;
     a.done_value = io.done_value;
     a.noise_ctl = io.noise_ctl;
+    a.mask = io.mask;
+    a.mask_words = io.mask_words;
+    RLPPO_CHECK_ARG(!io.mask || (!io.noise_ctl && io.mask_words == (a.A + 31) / 32),
+                    "discrete act: action_mask needs mask_words=%d == ceil(n_actions=%d / 32) and no noise_ctl", io.mask_words, a.A);
     const int H = net.L[0].pout;
     dim3 grid((unsigned)cdiv(n, FA_ROWS));
-    static PerDeviceOnce attr_set[3];
+    static PerDeviceOnce attr_set[6];
 #define FA_LAUNCH(J, W, SLOT)                                                                                                    \
     do {                                                                                                                         \
         constexpr int LDS_BYTES = (2 * 16 * J * W * FA_ROWS + W * FA_STAGES * J * 256 + FA_MAX_LAYERS * 16 * J * W + FA_QFLOATS) * 4; \
         /* up to 110 KiB of dynamic LDS (H = 256): above the default 64 KiB limit */                                             \
+        if (a.mask) { /* [ABI 8] */                                                                                             \
+            if (int rc_ = set_dynamic_lds_once((const void *)discrete_act_fused_kernel<J, W, true>, LDS_BYTES, attr_set[3 + SLOT])) return rc_; \
+            hipLaunchKernelGGL((discrete_act_fused_kernel<J, W, true>), grid, dim3(64 * W), LDS_BYTES, st, a);                   \
+            break;                                                                                                               \
+        }                                                                                                                        \
         if (int rc_ = set_dynamic_lds_once((const void *)discrete_act_fused_kernel<J, W>, LDS_BYTES, attr_set[SLOT])) return rc_; \
         hipLaunchKernelGGL((discrete_act_fused_kernel<J, W>), grid, dim3(64 * W), LDS_BYTES, st, a);                              \
     } while (0)

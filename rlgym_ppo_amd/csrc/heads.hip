@@ -5,6 +5,13 @@
 // literal softmax -> clamp(1e-11, 1) -> log (discrete_policy.py:52-54,70-78), NOT log_softmax, including the
 // clamp's zero-gradient region and torch.min's tie rule.
 // Gaussian / multi-discrete heads have 16 / 21 outputs per row: one thread per row, everything in registers.
+//
+// [ABI 8] Invalid-action masking (discrete head): every discrete kernel has a MASKED instantiation (template parameter; the unmasked
+// instantiations are the code they were).  A row's mask is W = ceil(A / 32) words, bit c % 32 of word c / 32 = action c valid.  An
+// invalid action's logit is -inf, as the padded columns c >= A always were: p = 0 exactly, no candidate of the arg-max, no term of
+// the entropy, dL/dz = 0.  A row without a valid action counts as all-valid.  The loss kernels do NOT get the words through the
+// minibatch gather: they read row idx[r]'s words straight from the buffer's mask field through the logical -> physical ring map
+// (MaskRows below) -- the workspace plan and the gather launches of a pass are the same with and without a mask.
 #include "common.hpp"
 
 namespace rlppo {
@@ -22,15 +29,33 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// softmax + clamp of one row spread over a wave; element c = lane + 64 e.
+// [ABI 8] the valid actions of one row as the wave holds it: bit e of the result = element c = lane + 64 e is an action (c < A)
+// whose mask bit is set.  Element c sits in word c / 32 = (lane >> 5) + 2 e at bit lane & 31.  A row without a valid action is
+// all-valid (wave-uniform decision).
 template <int EPL>
+__device__ __forceinline__ unsigned row_valid_bits(const unsigned *__restrict__ words, int A, int lane) {
+    unsigned bits = 0, in_row = 0;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        const int c = lane + 64 * e;
+        if (c < A) {
+            in_row |= 1u << e;
+            bits |= ((words[(lane >> 5) + 2 * e] >> (lane & 31)) & 1u) << e;
+        }
+    }
+    return __ballot(bits != 0) ? bits : in_row;
+}
+
+// softmax + clamp of one row spread over a wave; element c = lane + 64 e.  MASKED: `valid` (row_valid_bits) takes the place of c < A.
+template <int EPL, bool MASKED = false>
 __device__ __forceinline__ void row_softmax(const float *__restrict__ z, int A, int lane, float (&p)[EPL],
-                                            float (&pc)[EPL]) {
+                                            float (&pc)[EPL], unsigned valid = 0) {
     float mx = -INFINITY;
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
-        p[e] = c < A ? z[c] : -INFINITY;
+        const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
+        p[e] = in ? z[c] : -INFINITY;
         mx = fmaxf(mx, p[e]);
     }
     mx = wave_max(mx);
@@ -38,7 +63,8 @@ __device__ __forceinline__ void row_softmax(const float *__restrict__ z, int A, 
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
-        p[e] = c < A ? expf(p[e] - mx) : 0.f;
+        const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
+        p[e] = in ? expf(p[e] - mx) : 0.f;
         s += p[e];
     }
     s = wave_sum(s);
@@ -51,18 +77,24 @@ __device__ __forceinline__ void row_softmax(const float *__restrict__ z, int A, 
 
 // ----------------------------------------------------------------------------------- discrete: sampling
 // action = argmax_c pc[c] / q[c] (first index wins ties), logp = log(pc[action]).  `from_probs`: the row already
-// holds clamped probabilities (rlppo_categorical_select).
-template <int EPL, bool FROM_PROBS>
+// holds clamped probabilities (rlppo_categorical_select).  MASKED [ABI 8]: mask[n][W] words; only valid actions are candidates (the
+// clamp's 1e-11 never makes an invalid one selectable), probs_out is 0 on invalid actions; the noise stays [n][A].
+template <int EPL, bool FROM_PROBS, bool MASKED = false>
 __global__ __launch_bounds__(256) void discrete_sample_kernel(const float *__restrict__ src, int64_t ld, int64_t n,
                                                                int A, const float *__restrict__ noise,
                                                                int64_t *__restrict__ actions, float *__restrict__ logp,
-                                                               float *__restrict__ probs_out) {
+                                                               float *__restrict__ probs_out,
+                                                               const unsigned *__restrict__ mask = nullptr, int W = 0) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
     float p[EPL], pc[EPL];
     const float *z = src + row * ld;
-    if (FROM_PROBS) {
+    unsigned valid = 0;
+    if (MASKED) valid = row_valid_bits<EPL>(mask + row * W, A, lane);
+    if (MASKED) {
+        row_softmax<EPL, true>(z, A, lane, p, pc, valid);
+    } else if (FROM_PROBS) {
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
             const int c = lane + 64 * e;
@@ -77,7 +109,17 @@ __global__ __launch_bounds__(256) void discrete_sample_kernel(const float *__res
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
-        if (c < A) {
+        if (MASKED) {
+            if ((valid >> e) & 1u) {
+                const float v = pc[e] / noise[row * A + c];
+                if (v > best) {
+                    best = v;
+                    besti = c;
+                    bestp = pc[e];
+                }
+            }
+            if (probs_out && c < A) probs_out[row * A + c] = ((valid >> e) & 1u) ? pc[e] : 0.f;
+        } else if (c < A) {
             const float v = pc[e] / noise[row * A + c];  // IEEE fp32 division, as at::div
             if (v > best) {
                 best = v;
@@ -106,9 +148,24 @@ __global__ __launch_bounds__(256) void discrete_sample_kernel(const float *__res
 
 template <bool FROM_PROBS>
 static int launch_discrete_sample(hipStream_t st, const float *src, int64_t ld, int64_t n, int A, const float *noise,
-                                  int64_t *actions, float *logp, float *probs_out) {
+                                  int64_t *actions, float *logp, float *probs_out, const unsigned *mask = nullptr, int W = 0) {
     if (n <= 0) return 0;
     dim3 grid((unsigned)cdiv(n, 4)), block(256);
+    if (!FROM_PROBS && mask) {  // [ABI 8] the masked instantiations
+        RLPPO_CHECK_ARG(W == (A + 31) / 32, "discrete head: mask_words=%d, n_actions=%d needs %d", W, A, (A + 31) / 32);
+        if (A <= 128)
+            hipLaunchKernelGGL((discrete_sample_kernel<2, false, true>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out, mask, W);
+        else if (A <= 512)
+            hipLaunchKernelGGL((discrete_sample_kernel<8, false, true>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out, mask, W);
+        else if (A <= 2048)
+            hipLaunchKernelGGL((discrete_sample_kernel<32, false, true>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out, mask, W);
+        else {
+            set_error("discrete head: n_actions=%d > 2048 unsupported", A);
+            return RLPPO_ERR_ARG;
+        }
+        RLPPO_LAUNCH_CHECK();
+        return 0;
+    }
     if (A <= 128)
         hipLaunchKernelGGL((discrete_sample_kernel<2, FROM_PROBS>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out);
     else if (A <= 512)
@@ -124,8 +181,8 @@ static int launch_discrete_sample(hipStream_t st, const float *src, int64_t ld, 
 }
 
 int launch_discrete_sample_logits(hipStream_t st, const float *logits, int64_t ld, int64_t n, int A, const float *noise,
-                                  int64_t *actions, float *logp, float *probs_out) {
-    return launch_discrete_sample<false>(st, logits, ld, n, A, noise, actions, logp, probs_out);
+                                  int64_t *actions, float *logp, float *probs_out, const unsigned *mask, int mask_words) {
+    return launch_discrete_sample<false>(st, logits, ld, n, A, noise, actions, logp, probs_out, mask, mask_words);
 }
 int launch_categorical_select(hipStream_t st, const float *probs, int64_t ld, int64_t n, int A, const float *noise,
                               int64_t *actions, float *logp) {
@@ -137,21 +194,36 @@ int launch_categorical_select(hipStream_t st, const float *probs, int64_t ld, in
 // numpy's argmax over the FLATTENED [n, A] array -- quirk Q11: one index for the whole batch, first occurrence of the maximum).
 // The flat arg-max is one 64-bit atomic max per row on key = (float bits of the row maximum << 32) | ~flat index: clamped
 // probabilities are positive, so their bit patterns order like the values, and of equal values the smaller flat index wins.
-template <int EPL>
+// MASKED [ABI 8]: invalid actions read 0 (with and without the clamp) and are no candidates of the arg-max.
+template <int EPL, bool MASKED = false>
 __global__ __launch_bounds__(256) void discrete_probs_kernel(const float *__restrict__ logits, int64_t ld, int64_t n, int A,
                                                               int clamp, float *__restrict__ probs, int64_t ld_p,
-                                                              unsigned long long *__restrict__ key) {
+                                                              unsigned long long *__restrict__ key,
+                                                              const unsigned *__restrict__ mask = nullptr, int W = 0) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
     float p[EPL], pc[EPL];
-    row_softmax<EPL>(logits + row * ld, A, lane, p, pc);
+    unsigned valid = 0;
+    if (MASKED) {
+        valid = row_valid_bits<EPL>(mask + row * W, A, lane);
+        row_softmax<EPL, true>(logits + row * ld, A, lane, p, pc, valid);
+    } else {
+        row_softmax<EPL>(logits + row * ld, A, lane, p, pc);
+    }
     float best = -1.f;
     int besti = 0x7fffffff;
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + 64 * e;
-        if (c < A) {
+        if (MASKED) {
+            const bool ok = ((valid >> e) & 1u) != 0;
+            if (probs && c < A) probs[row * ld_p + c] = ok ? (clamp ? pc[e] : p[e]) : 0.f;
+            if (ok && pc[e] > best) {
+                best = pc[e];
+                besti = c;
+            }
+        } else if (c < A) {
             if (probs) probs[row * ld_p + c] = clamp ? pc[e] : p[e];
             if (pc[e] > best) {
                 best = pc[e];
@@ -179,8 +251,9 @@ __global__ void decode_flat_argmax_kernel(unsigned long long *key) {
 }
 
 int launch_discrete_probs(hipStream_t st, const float *logits, int64_t ld, int64_t n, int A, int clamp, float *probs,
-                          int64_t ld_p, int64_t *flat_argmax) {
+                          int64_t ld_p, int64_t *flat_argmax, const unsigned *mask, int W) {
     if (n <= 0) return 0;
+    RLPPO_CHECK_ARG(!mask || W == (A + 31) / 32, "discrete head: mask_words=%d, n_actions=%d needs %d", W, A, (A + 31) / 32);
     if (flat_argmax && (unsigned long long)n * (unsigned long long)A > 0xffffffffull) {
         set_error("discrete_probs: n * n_actions exceeds the 32-bit flat index of the arg-max key");
         return RLPPO_ERR_ARG;
@@ -188,7 +261,13 @@ int launch_discrete_probs(hipStream_t st, const float *logits, int64_t ld, int64
     unsigned long long *key = (unsigned long long *)flat_argmax;
     if (key) RLPPO_HIP(hipMemsetAsync(key, 0, sizeof(*key), st));
     dim3 grid((unsigned)cdiv(n, 4)), block(256);
-    if (A <= 128)
+    if (mask && A <= 128)
+        hipLaunchKernelGGL((discrete_probs_kernel<2, true>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key, mask, W);
+    else if (mask && A <= 512)
+        hipLaunchKernelGGL((discrete_probs_kernel<8, true>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key, mask, W);
+    else if (mask && A <= 2048)
+        hipLaunchKernelGGL((discrete_probs_kernel<32, true>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key, mask, W);
+    else if (A <= 128)
         hipLaunchKernelGGL((discrete_probs_kernel<2>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key);
     else if (A <= 512)
         hipLaunchKernelGGL((discrete_probs_kernel<8>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key);
@@ -266,28 +345,38 @@ __device__ __forceinline__ float value_row(float *vout_row, float target, float 
 
 // ----------------------------------------------------------------------------------- discrete: loss + grad
 // One wave per row.  logits[row][0:A] is overwritten with dL/dlogits.
-template <int EPL>
+// MASKED [ABI 8]: the row's mask words come from the buffer's mask field at the physical row of idx[row] (MaskRows); invalid
+// actions have p = 0, no entropy term and dL/dz = 0.  A stored action its own mask marks invalid (a caller error) takes the literal
+// chain: pc_a = 1e-11 inside the clamp's zero-gradient region -- finite, no gradient.
+template <int EPL, bool MASKED = false>
 __global__ __launch_bounds__(256) void discrete_loss_kernel(float *__restrict__ logits, int64_t ld, int A,
                                                              const float *__restrict__ actions,
                                                              const float *__restrict__ old_logp,
                                                              const float *__restrict__ advantages, int64_t mb,
-                                                             LossCfg cfg, double *__restrict__ stats) {
+                                                             LossCfg cfg, double *__restrict__ stats, MaskRows mr = MaskRows{}) {
     const int lane = threadIdx.x & 63;
     float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     // grid-stride over rows: statistics stay in registers, so a launch issues 5 atomics per BLOCK, not per 4 rows
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < mb; row += (int64_t)gridDim.x * 4) {
         float *z = logits + row * ld;
         float p[EPL], pc[EPL], lp[EPL];
-        row_softmax<EPL>(z, A, lane, p, pc);
+        unsigned valid = 0;
+        if (MASKED) {
+            valid = row_valid_bits<EPL>(mr.mask + ring_row(mr.idx[row], mr.ring_base, mr.ring_cap) * mr.W, A, lane);
+            row_softmax<EPL, true>(z, A, lane, p, pc, valid);
+        } else {
+            row_softmax<EPL>(z, A, lane, p, pc);
+        }
         const int a = (int)actions[row];  // acts.long() of a float-encoded index (discrete_policy.py:71)
         float ent = 0.f, lpa = 0.f, pca = 0.f;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
             const int c = lane + 64 * e;
-            lp[e] = c < A ? logf(pc[e]) : 0.f;
-            if (c < A) ent -= lp[e] * pc[e];
+            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
+            lp[e] = in ? logf(pc[e]) : 0.f;
+            if (in) ent -= lp[e] * pc[e];
             if (c == a) {
-                lpa = lp[e];
+                lpa = MASKED && !in ? logf(pc[e]) : lp[e];
                 pca = pc[e];
             }
         }
@@ -306,8 +395,9 @@ __global__ __launch_bounds__(256) void discrete_loss_kernel(float *__restrict__ 
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
             const int c = lane + 64 * e;
+            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
             float g = 0.f;
-            if (c < A) {
+            if (in) {
                 g = g_ent * (lp[e] + 1.f);
                 if (c == a) g += g_logp / pca;
                 if (!(p[e] >= PROB_MIN)) g = 0.f;  // clamp passes gradient on [1e-11, 1] only
@@ -319,7 +409,8 @@ __global__ __launch_bounds__(256) void discrete_loss_kernel(float *__restrict__ 
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
             const int c = lane + 64 * e;
-            if (c < ld) z[c] = c < A ? p[e] * (gp[e] - dot) : 0.f;
+            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
+            if (c < ld) z[c] = in ? p[e] * (gp[e] - dot) : 0.f;
         }
         if (lane == 0) {
             st[RLPPO_STAT_ENTROPY] += ent * cfg.inv_mb;
@@ -355,11 +446,13 @@ __device__ __forceinline__ float row16_max(float v) {
     return v;
 }
 
+// MASKED [ABI 8]: a lane's 8 consecutive logits are exactly byte l16 of the row's mask words (little-endian bit order).
+template <bool MASKED = false>
 __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict__ logits, int64_t ld, int A,
                                                                const float *__restrict__ actions,
                                                                const float *__restrict__ old_logp,
                                                                const float *__restrict__ advantages, int64_t mb,
-                                                               LossCfg cfg, double *__restrict__ stats) {
+                                                               LossCfg cfg, double *__restrict__ stats, MaskRows mr = MaskRows{}) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int l16 = threadIdx.x & 15, grp = threadIdx.x >> 4;
     const int c0 = l16 * 8;
@@ -380,17 +473,26 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
         }
         const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
         const int a = (int)actions[row];  // acts.long() of a float-encoded index (discrete_policy.py:71)
+        unsigned valid = 0;  // (MASKED) bit e: action c0 + e exists and is valid
+        if (MASKED) {
+            const unsigned in_bits = c0 + 8 <= A ? 0xffu : (c0 < A ? (1u << (A - c0)) - 1u : 0u);
+            if (in_bits)  // (c0 < A: byte l16 lies inside the row's W = ceil(A / 32) words)
+                valid = reinterpret_cast<const unsigned char *>(mr.mask + ring_row(mr.idx[row], mr.ring_base, mr.ring_cap) * mr.W)[l16] & in_bits;
+            if (!(row16_max(valid ? 1.f : 0.f) > 0.f)) valid = in_bits;  // a row without a valid action: all-valid
+        }
         float mx = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            if (!(in_row && c0 + e < A)) p[e] = -INFINITY;
+            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : (in_row && c0 + e < A);
+            if (!in) p[e] = -INFINITY;
             mx = fmaxf(mx, p[e]);
         }
         mx = row16_max(mx);
         float s = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            p[e] = (c0 + e < A) ? expf(p[e] - mx) : 0.f;
+            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : (c0 + e < A);
+            p[e] = in ? expf(p[e] - mx) : 0.f;
             s += p[e];
         }
         s = row16_sum(s);
@@ -398,12 +500,13 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int c = c0 + e;
+            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
             p[e] = p[e] / s;
             pc[e] = fminf(fmaxf(p[e], PROB_MIN), 1.0f);
-            lp[e] = c < A ? logf(pc[e]) : 0.f;
-            if (c < A) ent -= lp[e] * pc[e];
+            lp[e] = in ? logf(pc[e]) : 0.f;
+            if (in) ent -= lp[e] * pc[e];
             if (c == a) {
-                lpa = lp[e];
+                lpa = MASKED && !in ? logf(pc[e]) : lp[e];
                 pca = pc[e];
             }
         }
@@ -421,8 +524,9 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int c = c0 + e;
+            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
             float g = 0.f;
-            if (c < A) {
+            if (in) {
                 g = g_ent * (lp[e] + 1.f);
                 if (c == a) g += g_logp / pca;
                 if (!(p[e] >= PROB_MIN)) g = 0.f;  // clamp passes gradient on [1e-11, 1] only
@@ -435,8 +539,10 @@ __global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict_
             f32x4 o0, o1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                o0[e] = (c0 + e < A) ? p[e] * (gp[e] - dot) : 0.f;
-                o1[e] = (c0 + 4 + e < A) ? p[4 + e] * (gp[4 + e] - dot) : 0.f;
+                const bool in0 = MASKED ? ((valid >> e) & 1u) != 0 : (c0 + e < A);
+                const bool in1 = MASKED ? ((valid >> (4 + e)) & 1u) != 0 : (c0 + 4 + e < A);
+                o0[e] = in0 ? p[e] * (gp[e] - dot) : 0.f;
+                o1[e] = in1 ? p[4 + e] * (gp[4 + e] - dot) : 0.f;
             }
             *reinterpret_cast<f32x4 *>(z) = o0;
             *reinterpret_cast<f32x4 *>(z + 4) = o1;
@@ -479,17 +585,29 @@ int64_t kl_slots_doubles(int64_t mb) {  // grids: discrete <= 2048 workgroups, g
 }
 
 int launch_discrete_loss(hipStream_t st, float *logits, int64_t ld, int A, const float *actions, const float *old_logp, const float *adv,
-                         int64_t mb, const LossCfg &cfg, double *stats) {
+                         int64_t mb, const LossCfg &cfg, double *stats, const MaskRows *mr) {
     if (mb <= 0) return 0;
     dim3 grid((unsigned)(cdiv(mb, 4) < 2048 ? cdiv(mb, 4) : 2048)), block(256);
     RLPPO_CHECK_ARG(ld <= DISCRETE_LOSS_MAX_LD, "discrete head: padded width %ld too large", (long)ld);
+    if (mr && mr->mask) {  // [ABI 8] the masked instantiations, same grids
+        RLPPO_CHECK_ARG(mr->W == (A + 31) / 32 && mr->idx, "discrete head: mask_words=%d, n_actions=%d needs %d", mr->W, A, (A + 31) / 32);
+        if (ld <= 128) {
+            dim3 grid16((unsigned)(cdiv(mb, 16) < 2048 ? cdiv(mb, 16) : 2048));
+            hipLaunchKernelGGL(discrete_loss16_kernel<true>, grid16, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, *mr);
+        } else if (ld <= 512)
+            hipLaunchKernelGGL((discrete_loss_kernel<8, true>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, *mr);
+        else
+            hipLaunchKernelGGL((discrete_loss_kernel<32, true>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, *mr);
+        RLPPO_LAUNCH_CHECK();
+        return 0;
+    }
     if (ld <= 128) {  // 16 lanes per row, DPP reductions
         dim3 grid16((unsigned)(cdiv(mb, 16) < 2048 ? cdiv(mb, 16) : 2048));
-        hipLaunchKernelGGL(discrete_loss16_kernel, grid16, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats);
+        hipLaunchKernelGGL(discrete_loss16_kernel<false>, grid16, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, MaskRows{});
     } else if (ld <= 512)  // one wave per row
-        hipLaunchKernelGGL((discrete_loss_kernel<8>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats);
+        hipLaunchKernelGGL((discrete_loss_kernel<8>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, MaskRows{});
     else
-        hipLaunchKernelGGL((discrete_loss_kernel<32>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats);
+        hipLaunchKernelGGL((discrete_loss_kernel<32>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, MaskRows{});
     RLPPO_LAUNCH_CHECK();
     return 0;
 }

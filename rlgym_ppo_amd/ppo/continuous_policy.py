@@ -10,6 +10,11 @@ from ..util import torch_functions
 from ._mlp import ArenaModule, build_body
 
 
+def _no_action_mask(action_mask):
+    if action_mask is not None:
+        raise ValueError("action_mask: invalid-action masking is an option of the discrete head (DiscreteFF), not of the Gaussian head")
+
+
 class ContinuousPolicy(ArenaModule):
     def __init__(self, input_shape, output_shape, layer_sizes, device, var_min=0.1, var_max=1.0):
         super().__init__()
@@ -19,13 +24,15 @@ class ContinuousPolicy(ArenaModule):
         self._finish(device)
 
     @torch.no_grad()
-    def get_output(self, obs):
+    def get_output(self, obs, action_mask=None):
+        _no_action_mask(action_mask)
         rows = self.arena.stage_obs(obs)
         y = self.arena.forward(rows, out_tanh=True)[:, :self.n_out]
         return self.affine_map(y)
 
     @torch.no_grad()
-    def get_action(self, obs, summed_probs=True, deterministic=False, noise=None, standardize=None):
+    def get_action(self, obs, summed_probs=True, deterministic=False, noise=None, standardize=None, action_mask=None):
+        _no_action_mask(action_mask)
         a = self.arena
         if deterministic or not summed_probs:
             mean, std = self.get_output(obs)
@@ -57,8 +64,9 @@ class ContinuousPolicy(ArenaModule):
                                            ptr(noise), float(self.affine_map.m), float(self.affine_map.b), ptr(actions),
                                            ptr(logp), ptr(ws), ws.numel(), opts))
 
-    def act_padded(self, rows, noise=None):
+    def act_padded(self, rows, noise=None, action_mask=None):
         """Padded device rows -> (actions fp32 [n, k], summed log_probs fp32 [n]) on the device (see DiscreteFF.act_padded)."""
+        _no_action_mask(action_mask)
         a = self.arena
         n, k = rows.shape[0], self.n_out // 2
         if noise is None and self.noise_mode == "device":
@@ -81,8 +89,9 @@ class ContinuousPolicy(ArenaModule):
         return (-torch.divide(msq, 2 * ssq) + torch.divide(mean * x, ssq) - torch.divide(xsq, 2 * ssq)
                 + torch.log(1 / torch.sqrt(2 * np.pi * ssq)))
 
-    def get_backprop_data(self, obs, acts, summed_probs=True):
+    def get_backprop_data(self, obs, acts, summed_probs=True, action_mask=None):
         """Compatibility accessor with an autograd graph (continuous_policy.py:100-121); unused by PPOLearner."""
+        _no_action_mask(action_mask)
         if not isinstance(obs, torch.Tensor):
             obs = torch.as_tensor(np.asarray(obs), dtype=torch.float32, device=self.arena.device)
         mean, std = self.affine_map(self.model(obs))

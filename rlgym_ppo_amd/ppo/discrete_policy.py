@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from .. import _native as N
 from ..engine import host_exponential, host_exponential_prefetch, ptr, stream_ptr
+from ..util import action_mask as AM
 from ._mlp import ArenaModule, build_body
 
 
@@ -25,55 +26,72 @@ class DiscreteFF(ArenaModule):
         self._host_out = None  # pinned (actions, log-probs) the fused step writes into (grown on demand)
         self._finish(device)
 
-    def _probs(self, rows, clamp, want_probs=True, want_argmax=False):
+    def _mask_opts(self, action_mask, n):
+        """(rlppo_act_opts carrying the packed mask, the packed words) of a call on n rows, or (None, None) without a mask.
+        action_mask: bool / 0-1 [n, n_actions], host or device, or util.action_mask.Packed (already the kernels' words)."""
+        if action_mask is None:
+            return None, None
+        words = AM.pack(action_mask, self.n_actions, self.arena.device)
+        if words.shape[0] != n:
+            raise ValueError(f"action mask has {words.shape[0]} rows, the call {n}")
+        opts = N.ActOpts()
+        opts.action_mask, opts.mask_words = words.data_ptr(), words.shape[1]
+        return opts, words
+
+    def _probs(self, rows, clamp, want_probs=True, want_argmax=False, action_mask=None):
         """rlppo_discrete_probs on padded device rows: softmax (or clamp(softmax)) [n, n_actions] and/or the flat arg-max."""
         a = self.arena
         n = rows.shape[0]
+        opts, _words = self._mask_opts(action_mask, n)
         a.ensure_packed()
         probs = torch.empty(n, self.n_actions, dtype=torch.float32, device=a.device) if want_probs else None
         best = torch.empty(1, dtype=torch.int64, device=a.device) if want_argmax else None
         ws = a.forward_ws(n)
         N.check(N.lib().rlppo_discrete_probs(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1], n, int(clamp),
                                              ptr(probs) if want_probs else None, self.n_actions, ptr(best) if want_argmax else None,
-                                             ptr(ws), ws.numel(), None))
+                                             ptr(ws), ws.numel(), ctypes.byref(opts) if opts is not None else None))
         return probs, best
 
     @torch.no_grad()
-    def get_output(self, obs):
-        """Softmax probabilities [n, n_actions] on the device (discrete_policy.py:34-42)."""
-        return self._probs(self.arena.stage_obs(obs), clamp=False)[0]
+    def get_output(self, obs, action_mask=None):
+        """Softmax probabilities [n, n_actions] on the device (discrete_policy.py:34-42).  action_mask (optional, [n, n_actions]
+        valid = 1): the softmax over the valid actions, 0 on the others."""
+        return self._probs(self.arena.stage_obs(obs), clamp=False, action_mask=action_mask)[0]
 
-    def get_action(self, obs, deterministic=False, noise=None, standardize=None):
+    def get_action(self, obs, deterministic=False, noise=None, standardize=None, action_mask=None):
         """-> (actions int64 CPU [n], log_probs fp32 CPU [n]) like discrete_policy.py:44-62.
         `noise`: optional [n, n_actions] Exp(1) draws (default: torch.empty(n, A).exponential_(1) from the CPU
-        generator, the reference's stream).  `standardize`: optional (mean0, std0) scalars fused into staging."""
-        if not deterministic:
+        generator, the reference's stream).  `standardize`: optional (mean0, std0) scalars fused into staging.
+        `action_mask`: optional [n, n_actions], valid = 1 (invalid-action masking: only valid actions are sampled; the noise draw
+        and the generator's state are those of the unmasked call).  A masked call takes the general path."""
+        if not deterministic and action_mask is None:
             # small host batches: one hipGraph replay (ppo/_mlp.py).  (Nothing in there touches autograd: the no_grad scope -- 2 us
             # of a 45 us call -- is entered below, where torch operators run.)
             out = self._graph_act(obs, noise, standardize)
             if out is not None:
                 return out
-        return self._get_action_general(obs, deterministic, noise, standardize)
+        return self._get_action_general(obs, deterministic, noise, standardize, action_mask)
 
     @torch.no_grad()
-    def _get_action_general(self, obs, deterministic, noise, standardize):
+    def _get_action_general(self, obs, deterministic, noise, standardize, action_mask=None):
         a = self.arena
         if not deterministic:
-            return self.step(obs, noise, standardize)       # [r3] the whole step in one launch (rlppo_discrete_step)
+            return self.step(obs, noise, standardize, action_mask=action_mask)       # [r3] the whole step in one launch (rlppo_discrete_step)
         rows = a.stage_obs(obs, standardize)
         n = rows.shape[0]
         if deterministic:  # quirk Q11: numpy's argmax over the flattened clamped [n, A] array -- one index for the whole batch
-            return np.int64(self._probs(rows, clamp=True, want_probs=False, want_argmax=True)[1].item()), 0
-        actions, logp = self.act_padded(rows, noise)
+            return np.int64(self._probs(rows, clamp=True, want_probs=False, want_argmax=True, action_mask=action_mask)[1].item()), 0
+        actions, logp = self.act_padded(rows, noise, action_mask)
         return actions.cpu(), logp.cpu()
 
-    def step(self, obs, noise=None, standardize=None, rows_out=None, actions_f32=None, logp_out=None, to_host=True):
+    def step(self, obs, noise=None, standardize=None, rows_out=None, actions_f32=None, logp_out=None, to_host=True, action_mask=None):
         """One rollout step through rlppo_discrete_step [r3]: raw observations (numpy / tensor, fp32 or fp64, host or device) ->
         standardise + pad -> MLP -> softmax -> clamp -> argmax(p / q) -> log p, one launch (csrc/fused_act.hip).
         to_host=True: the kernel stores actions (int64) and log-probabilities straight into pinned host buffers; after ONE stream
         synchronisation they are returned as CPU tensors (no device-to-host copies).  to_host=False: device tensors.
         rows_out / actions_f32 / logp_out: optional device destinations of a device-resident rollout (VectorAgentManager): the
-        padded policy-input rows [n, ld_in], the actions as floats [n] and the log-probabilities [n]."""
+        padded policy-input rows [n, ld_in], the actions as floats [n] and the log-probabilities [n].
+        action_mask: optional [n, n_actions] valid = 1 (or util.action_mask.Packed device words): read by the same launch."""
         a = self.arena
         if isinstance(obs, torch.Tensor):
             t = obs.detach()
@@ -108,6 +126,7 @@ class DiscreteFF(ArenaModule):
                 mode = 2
             else:
                 mode, mean0, std0 = 1, float(standardize[0]), float(standardize[1])
+        opts, _words = self._mask_opts(action_mask, n)
         a.ensure_packed()
         L = N.lib()
         if to_host:
@@ -126,7 +145,8 @@ class DiscreteFF(ArenaModule):
         ws = a.ws.get(L.rlppo_discrete_step_workspace_bytes(a.dims_c, a.n_layers, n))
         N.check(L.rlppo_discrete_step(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(t), int(t.dtype == torch.float64), d, n,
                                       mode, mean0, std0, ptr(mean_v), ptr(std_v), ptr(q), ptr(actions), ptr(actions_f32), ptr(logp),
-                                      ptr(rows_out), rows_out.stride(0) if rows_out is not None else 0, ptr(ws), ws.numel(), None))
+                                      ptr(rows_out), rows_out.stride(0) if rows_out is not None else 0, ptr(ws), ws.numel(),
+                                      ctypes.byref(opts) if opts is not None else None))
         if to_host:
             torch.cuda.current_stream(a.device).synchronize()
             return actions.clone(), (logp.clone() if to_host is True else logp)
@@ -166,11 +186,12 @@ class DiscreteFF(ArenaModule):
                                          ctypes.byref(opts) if opts is not None else None))
         N.check(L.rlppo_discrete_step(stream_ptr(), *args[1]))
 
-    def act_padded(self, rows, noise=None):
+    def act_padded(self, rows, noise=None, action_mask=None):
         """Padded device rows [n, ld_in] -> (actions int64 [n], log_probs fp32 [n]) ON THE DEVICE: the part of get_action
-        after staging, for callers that keep the rollout on the GPU (VectorAgentManager)."""
+        after staging, for callers that keep the rollout on the GPU (VectorAgentManager).  action_mask: as in step()."""
         a = self.arena
         n = rows.shape[0]
+        opts, _words = self._mask_opts(action_mask, n)
         if noise is None and self.noise_mode == "device":
             noise = torch.empty(n, self.n_actions, device=a.device).exponential_(1)  # fast mode: torch's HIP generator, not the reference's CPU stream
         elif noise is None:  # the reference's CPU stream, uploaded asynchronously (the pinned ring slot is event-protected)
@@ -181,15 +202,27 @@ class DiscreteFF(ArenaModule):
         logp = torch.empty(n, dtype=torch.float32, device=a.device)
         ws = a.forward_ws(n)
         N.check(N.lib().rlppo_discrete_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1], n,
-                                           ptr(q), ptr(actions), ptr(logp), None, ptr(ws), ws.numel(), None))
+                                           ptr(q), ptr(actions), ptr(logp), None, ptr(ws), ws.numel(),
+                                           ctypes.byref(opts) if opts is not None else None))
         return actions, logp
 
-    def get_backprop_data(self, obs, acts):
+    def get_backprop_data(self, obs, acts, action_mask=None):
         """Compatibility accessor with an autograd graph (discrete_policy.py:64-80), evaluated by stock PyTorch
-        on the same parameters.  PPOLearner.learn does NOT use it: the update runs in rlppo_ppo_minibatch."""
+        on the same parameters.  PPOLearner.learn does NOT use it: the update runs in rlppo_ppo_minibatch.
+        action_mask (optional, [n, n_actions] valid = 1): the masked semantics of the update -- invalid logits -inf, the entropy
+        summed over valid actions -- for cross-checks."""
         acts = acts.long()
         if not isinstance(obs, torch.Tensor):
             obs = torch.as_tensor(np.asarray(obs), dtype=torch.float32, device=self.arena.device)
-        probs = torch.clamp(self.model(obs).view(-1, self.n_actions), min=1e-11, max=1)
+        if action_mask is None:
+            probs = torch.clamp(self.model(obs).view(-1, self.n_actions), min=1e-11, max=1)
+            log_probs = torch.log(probs)
+            return log_probs.gather(-1, acts), -(log_probs * probs).sum(dim=-1).mean()
+        m = torch.as_tensor(np.asarray(action_mask) if not isinstance(action_mask, torch.Tensor) else action_mask).to(obs.device) != 0
+        m = m.view(-1, self.n_actions)
+        m = torch.where(m.any(dim=-1, keepdim=True), m, torch.ones_like(m))  # a row without a valid action: all-valid
+        logits = self.model[:-1](obs).view(-1, self.n_actions)               # (the body without its Softmax)
+        probs = torch.clamp(torch.softmax(logits.masked_fill(~m, float("-inf")), dim=-1), min=1e-11, max=1)
         log_probs = torch.log(probs)
-        return log_probs.gather(-1, acts), -(log_probs * probs).sum(dim=-1).mean()
+        ent = -torch.where(m, log_probs * probs, torch.zeros_like(probs)).sum(dim=-1).mean()
+        return log_probs.gather(-1, acts), ent

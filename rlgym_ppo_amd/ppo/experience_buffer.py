@@ -9,6 +9,9 @@ the buffer through index vectors (`epoch_indices`) instead of materialised gathe
 here new rows overwrite the oldest ones in place and a rotating base index maps logical row i (0 = oldest, the reference's
 order) to physical row (base + i) mod capacity -- the kernels apply that map to the permutation's entries
 (rlppo_minibatch_args.ring_base / ring_cap), the reference-shaped accessors materialise the logical order on demand.
+
+Beyond the reference: an optional tenth field, `action_masks` (invalid-action masking of the discrete head), stored packed
+(int32 words [capacity, ceil(A / 32)], util/action_mask.py) under the same FIFO / grow / wrap rules.  A buffer is masked or not.
 """
 import os
 
@@ -17,11 +20,15 @@ import torch
 
 from .. import _native as N
 from ..engine import DeviceIndexRing, LegacyPermutation, ptr, require_gpu, stream_ptr
+from ..util import action_mask as AM
 
 _FIELDS = ("states", "actions", "log_probs", "rewards", "next_states", "dones", "truncated", "values", "advantages")
 
 
 class ExperienceBuffer(object):
+    _fields = _FIELDS    # + "action_masks" once a masked submit has arrived (decided by the first submit after a clear())
+    _n_actions = None    # actions a mask row describes
+
     def __init__(self, max_size, seed, device):
         # the reference's Learner passes device="cpu" here (learner.py:124-126); the data still belongs in HBM
         self.device = device
@@ -43,14 +50,15 @@ class ExperienceBuffer(object):
         self._base = 0    # physical row of logical row 0 (the oldest sample)
         self._count = 0   # valid rows
         self._d = None    # logical observation width
+        self._fields, self._n_actions = _FIELDS, None
 
     # ------------------------------------------------------------------------------------------- FIFO
     def _grow(self, need, new):
         """(Re-)allocate the ring for at least `need` rows (at most max_size), keeping the current rows in logical order."""
         cap = min(self.max_size, max(need, 2 * self._cap))
         fresh = {}
-        for k in _FIELDS:
-            t = torch.empty((cap,) + tuple(new[k].shape[1:]), dtype=torch.float32, device=self._dev)
+        for k in self._fields:
+            t = torch.empty((cap,) + tuple(new[k].shape[1:]), dtype=new[k].dtype, device=self._dev)
             if self._count:
                 t[:self._count].copy_(self._logical(k))
             fresh[k] = t
@@ -68,11 +76,11 @@ class ExperienceBuffer(object):
         n_new = new["rewards"].shape[0]
         size = self.max_size
         if n_new >= size:                       # the new chunk alone fills the buffer: its last max_size rows
-            if self._cap < size or any(self._store[k].shape[1:] != new[k].shape[1:] for k in _FIELDS):
+            if self._cap < size or any(self._store[k].shape[1:] != new[k].shape[1:] for k in self._fields):
                 self._count = 0
                 self._cap = 0
                 self._grow(size, new)
-            for k in _FIELDS:
+            for k in self._fields:
                 self._store[k].copy_(new[k][n_new - size:])
             self._base, self._count = 0, size
             return
@@ -81,7 +89,7 @@ class ExperienceBuffer(object):
         cap = self._cap
         w0 = (self._base + self._count) % cap   # first physical row to write
         first = min(n_new, cap - w0)
-        for k in _FIELDS:
+        for k in self._fields:
             self._store[k][w0:w0 + first].copy_(new[k][:first])
             if first < n_new:
                 self._store[k][:n_new - first].copy_(new[k][first:])
@@ -110,15 +118,32 @@ class ExperienceBuffer(object):
         N.check(N.lib().rlppo_pad_rows(stream_ptr(), ptr(t), 0, n, d, d, ptr(out), ld, 0, 0.0, 1.0))
         return out
 
-    def submit_experience(self, states, actions, log_probs, rewards, next_states, dones, truncated, values, advantages):
+    def submit_experience(self, states, actions, log_probs, rewards, next_states, dones, truncated, values, advantages,
+                          action_masks=None):
+        """action_masks (optional, not in the reference): [n, A] bool / 0-1, host or device, valid = 1 -- the masks the actions
+        were sampled under (or util.action_mask.Packed).  Either every submit since the last clear() carries them or none does."""
+        masked = action_masks is not None
+        if (self._cap or self._count) and masked != (len(self._fields) > len(_FIELDS)):
+            raise ValueError("submit_experience: the buffer holds " + ("unmasked" if masked else "masked") + " experience and this submit is "
+                             + ("masked" if masked else "unmasked") + ": a buffer is masked or not (clear() resets that)")
         new = dict(states=self._pad_states(states), actions=self._to_dev(actions), log_probs=self._to_dev(log_probs),
                    rewards=self._to_dev(rewards), next_states=self._pad_states(next_states), dones=self._to_dev(dones),
                    truncated=self._to_dev(truncated), values=self._to_dev(values), advantages=self._to_dev(advantages))
+        if masked:
+            m = action_masks
+            if not hasattr(m, "shape"):
+                m = np.asarray(m)
+            n_act = int(m.shape[-1])
+            if self._n_actions is not None and n_act != self._n_actions and self._count:
+                raise ValueError(f"submit_experience: action mask of {n_act} actions, the buffer's rows have {self._n_actions}")
+            new["action_masks"] = AM.pack(m, n_act, self._dev)
+            self._n_actions = n_act
+            self._fields = _FIELDS + ("action_masks",)
         n = new["rewards"].shape[0]
-        for k in _FIELDS:
+        for k in self._fields:
             if new[k].shape[0] != n:
                 raise ValueError(f"submit_experience: field '{k}' has {new[k].shape[0]} rows, 'rewards' has {n}")
-        if self._cap and any(self._store[k].shape[1:] != new[k].shape[1:] for k in _FIELDS) and n < self.max_size:
+        if self._cap and any(self._store[k].shape[1:] != new[k].shape[1:] for k in self._fields) and n < self.max_size:
             raise ValueError("submit_experience: row shapes differ from the rows already in the buffer")
         if n:
             self._append(new)
@@ -145,6 +170,15 @@ class ExperienceBuffer(object):
     truncated = property(lambda s: s._get("truncated"))
     values = property(lambda s: s._get("values"))
     advantages = property(lambda s: s._get("advantages"))
+
+    @property
+    def action_masks(self):
+        """bool [n, A] in logical order (oldest first), or None for an unmasked buffer."""
+        if len(self._fields) == len(_FIELDS):
+            return None
+        if self._count == 0:
+            return torch.empty((0, self._n_actions), dtype=torch.bool, device=self._dev)
+        return AM.unpack(self._logical("action_masks"), self._n_actions)
 
     def __len__(self):
         return self._count

@@ -9,6 +9,11 @@ from ..util import torch_functions
 from ._mlp import ArenaModule, build_body
 
 
+def _no_action_mask(action_mask):
+    if action_mask is not None:
+        raise ValueError("action_mask: invalid-action masking is an option of the discrete head (DiscreteFF), not of the multi-discrete head")
+
+
 class MultiDiscreteFF(ArenaModule):
     def __init__(self, input_shape, layer_sizes, device):
         super().__init__()
@@ -19,12 +24,14 @@ class MultiDiscreteFF(ArenaModule):
         self._finish(device)
 
     @torch.no_grad()
-    def get_output(self, obs):
+    def get_output(self, obs, action_mask=None):
+        _no_action_mask(action_mask)
         rows = self.arena.stage_obs(obs)
         return self.arena.forward(rows)[:, :21]
 
     @torch.no_grad()
-    def get_action(self, obs, deterministic=False, noise=None, standardize=None):
+    def get_action(self, obs, deterministic=False, noise=None, standardize=None, action_mask=None):
+        _no_action_mask(action_mask)
         a = self.arena
         if deterministic:
             logits = self.get_output(obs)
@@ -55,8 +62,9 @@ class MultiDiscreteFF(ArenaModule):
         N.check(N.lib().rlppo_multidiscrete_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1],
                                                 n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(), opts))
 
-    def act_padded(self, rows, noise=None):
+    def act_padded(self, rows, noise=None, action_mask=None):
         """Padded device rows -> (actions int64 [n, 8], log_probs fp32 [n]) on the device (see DiscreteFF.act_padded)."""
+        _no_action_mask(action_mask)
         a = self.arena
         n = rows.shape[0]
         if noise is None and self.noise_mode == "device":
@@ -72,8 +80,9 @@ class MultiDiscreteFF(ArenaModule):
                                                 n, ptr(q), ptr(actions), ptr(logp), ptr(ws), ws.numel(), None))
         return actions, logp
 
-    def get_backprop_data(self, obs, acts):
+    def get_backprop_data(self, obs, acts, action_mask=None):
         """Compatibility accessor with an autograd graph (multi_discrete_policy.py:76-89); unused by PPOLearner."""
+        _no_action_mask(action_mask)
         if not isinstance(obs, torch.Tensor):
             obs = torch.as_tensor(np.asarray(obs), dtype=torch.float32, device=self.arena.device)
         dist = self.multi_discrete

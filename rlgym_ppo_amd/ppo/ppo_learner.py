@@ -241,6 +241,11 @@ class PPOLearner(object):
         a.old_logp = st["log_probs"].data_ptr()
         a.targets = st["values"].data_ptr()
         a.advantages = st["advantages"].data_ptr()
+        if "action_masks" in st:  # invalid-action masking (ExperienceBuffer.submit_experience(..., action_masks=...))
+            if self.policy_type != 0:
+                raise ValueError("the experience buffer holds action masks: invalid-action masking is an option of the discrete head, "
+                                 f"not of policy_type {self.policy_type}")
+            a.action_mask, a.mask_words = st["action_masks"].data_ptr(), st["action_masks"].shape[1]
         a.clip_range, a.ent_coef = float(self.clip_range), float(self.ent_coef)
         a.mb_ratio = float(self.mini_batch_size / self.batch_size)
         if self.policy_type == 2:

@@ -1,0 +1,84 @@
+"""Action masks at the library boundary (include/rlppo.h, rlppo_act_opts.action_mask / rlppo_minibatch_args.action_mask).
+
+A mask row marks each of the A actions valid (1 / True) or invalid (0 / False).  The kernels read it packed: W = ceil(A / 32)
+32-bit words per row, bit c % 32 of word c / 32 set = action c valid, bits at and beyond A clear.  `pack` builds that form on
+the device from a bool / 0-1 array or tensor [n, A] (host or device); `unpack` is its inverse for the accessors.
+"""
+import numpy as np
+import torch
+
+
+class Packed(object):
+    """Masks already in the kernels' form: int32 device words [n, W] + the action count they describe (what a device-resident
+    rollout hands from the collector to the buffer without unpacking)."""
+    __slots__ = ("words", "n_actions")
+
+    def __init__(self, words, n_actions):
+        self.words, self.n_actions = words, int(n_actions)
+
+    @property
+    def shape(self):
+        return (self.words.shape[0], self.n_actions)
+
+    def unpack(self):
+        return unpack(self.words, self.n_actions)
+
+
+def mask_words(n_actions):
+    """Words per row: ceil(A / 32)."""
+    return (int(n_actions) + 31) // 32
+
+
+def pack_host(mask, n_actions):
+    """numpy bool / 0-1 [n, A] -> int32 words [n, W]; a row without a valid action raises ValueError naming it."""
+    m = np.asarray(mask)
+    if m.ndim == 1:
+        m = m.reshape(1, -1)
+    if m.ndim != 2 or m.shape[1] != int(n_actions):
+        raise ValueError(f"action mask shape {tuple(m.shape)} != (n, {int(n_actions)})")
+    m = m != 0
+    empty = np.flatnonzero(~m.any(axis=1))
+    if empty.size:
+        raise ValueError(f"action mask: row {int(empty[0])} has no valid action")
+    w = mask_words(n_actions)
+    padded = np.zeros((m.shape[0], w * 32), dtype=bool)
+    padded[:, :m.shape[1]] = m
+    by = np.packbits(padded, axis=1, bitorder="little")           # byte k of a row = actions 8 k .. 8 k + 7, LSB first
+    return np.ascontiguousarray(by).view("<u4").astype(np.uint32, copy=False).view(np.int32).reshape(m.shape[0], w)
+
+
+def pack(mask, n_actions, device):
+    """bool / 0-1 array or tensor [n, A], host or device -> int32 words [n, W] on `device`.  Host input is checked for rows
+    without a valid action (ValueError naming the row); device input is not read back -- the kernels treat such a row as
+    all-valid."""
+    A = int(n_actions)
+    if isinstance(mask, Packed):
+        if mask.n_actions != A:
+            raise ValueError(f"packed action mask of {mask.n_actions} actions != {A}")
+        return mask.words.to(device).contiguous()
+    if isinstance(mask, torch.Tensor) and mask.is_cuda:
+        m = mask.detach()
+        if m.dim() == 1:
+            m = m.view(1, -1)
+        if m.dim() != 2 or m.shape[1] != A:
+            raise ValueError(f"action mask shape {tuple(m.shape)} != (n, {A})")
+        w = mask_words(A)
+        bits = torch.zeros((m.shape[0], w * 32), dtype=torch.int32, device=m.device)
+        bits[:, :A] = (m != 0).to(torch.int32)
+        shifts = torch.arange(32, dtype=torch.int32, device=m.device)
+        # distinct bits: the int32 sum is their OR (bit 31 wraps into the sign, the word's bit pattern)
+        words = (bits.view(m.shape[0], w, 32) << shifts).sum(-1, dtype=torch.int32)
+        return words.to(device).contiguous()
+    if isinstance(mask, torch.Tensor):
+        mask = mask.detach().numpy()
+    return torch.from_numpy(pack_host(mask, A)).to(device, non_blocking=False)
+
+
+def unpack(words, n_actions):
+    """int32 words [n, W] (tensor, any device) -> bool tensor [n, A] on the same device."""
+    A = int(n_actions)
+    w = mask_words(A)
+    t = words.reshape(-1, w).to(torch.int64)
+    shifts = torch.arange(32, device=t.device)
+    bits = ((t.unsqueeze(-1) >> shifts) & 1).reshape(t.shape[0], w * 32)
+    return bits[:, :A] != 0
