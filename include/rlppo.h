@@ -245,6 +245,23 @@ int rlppo_gae(void *stream, const float *rews, const float *dones, const float *
               int64_t n, double gamma, double lmbda, float return_std,
               float *value_targets, float *advantages, float *returns, void *workspace, size_t ws_bytes);
 
+/* rlppo_gae with truncated trajectories bootstrapped from V of their OWN next state (time-limit handling as Stable-Baselines3,
+ * CleanRL and Gymnasium do it).  Per step t, with nd = 1 - done[t], nt = 1 - truncated[t] (flags exactly 0.0 or 1.0):
+ *     vnext            = boot_values[t]   if truncated[t] != 0 and done[t] == 0      (done wins over truncated)
+ *                        values[t + 1]    otherwise
+ *     delta            = clip(r/sigma) + gamma * vnext * nd - values[t]
+ *     adv[t]           = delta + gamma * lambda * nd * nt * adv[t + 1]
+ *     value_targets[t] = values[t] + adv[t]
+ *     ret[t]           = r[t] + gamma * nd * nt * ret[t + 1]                           (as rlppo_gae: returns are not bootstrapped)
+ * boot_values: float[n], 16-byte aligned, USED only at steps that are truncated and not done -- every other entry may hold
+ * anything (NaN, uninitialised memory) and never reaches an output (the kernels read the array as a fifth input stream and select
+ * by the flags: measured faster than a sparse read behind the flags).  boot_values == NULL is exactly rlppo_gae, launch for launch.
+ * Same arithmetic, same workspace (rlppo_gae_workspace_bytes), same forms (one launch; two under stream capture), same bounded
+ * look-back wait and timeout word as rlppo_gae. */
+int rlppo_gae_boot(void *stream, const float *rews, const float *dones, const float *truncated, const float *values,
+                   const float *boot_values, int64_t n, double gamma, double lmbda, float return_std,
+                   float *value_targets, float *advantages, float *returns, void *workspace, size_t ws_bytes);
+
 /* -------------------------------------------------------------------------------------- PPO update */
 
 size_t rlppo_minibatch_workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims,

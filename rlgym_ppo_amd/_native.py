@@ -135,6 +135,8 @@ SIGNATURES = {
     "rlppo_gae_workspace_bytes": (c_size_t, [c_int64]),
     "rlppo_gae": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_float,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "rlppo_gae_boot": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_float,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "rlppo_minibatch_workspace_bytes": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64]),
     "rlppo_minibatch_workspace_bytes_for": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
     "rlppo_ppo_minibatch": (c_int32, [c_void_p, POINTER(MinibatchArgs)]),

@@ -21,8 +21,14 @@ truncated [n], info)` with auto-reset of finished agents; `observation_space.sha
 Optional (the sb3-contrib convention, discrete policy only): `action_masks() -> [n, n_actions]` booleans for the observation
 the agents act on next, called after `reset()` and after every `step()`; the policy then samples valid actions only and the
 masks leave the collect trajectory-major as `self.action_mask_rows` (next to `value_input_rows`).
+Optional, used with `bootstrap_truncated` (Learner(gae_bootstrap_truncated=True)) only: `info["final_observation"]`, float
+[n, d], whose rows are meaningful where `truncated` is set and `done` is not -- the observation the episode ended on, which
+the auto-reset has replaced in `obs`.  Those rows are standardised like that step's `obs`, kept out of the running
+statistics and put into the next-state rows of those steps; the collect then leaves `bootstrap_steps`, `bootstrap_index`
+and `bootstrap_rows` (the truncated-and-not-done steps and their next-state rows) for the GAE scan.
 """
 import time
+import warnings
 
 import numpy as np
 import torch
@@ -52,6 +58,13 @@ class VectorAgentManager(object):
         self._ep_rews = None
         self.action_mask_rows = None  # util.action_mask.Packed [N, W] of the last collect (trajectory-major), or None: env without masks
         self._pending_mask = None     # packed device words [n_agents, W] of the observation the agents act on next
+        # Learner(gae_bootstrap_truncated=True): every collect leaves what the bootstrap form of the GAE scan needs; off, a collect
+        # does exactly what it did without the option
+        self.bootstrap_truncated = False
+        self.bootstrap_steps = None   # int64 host indices (trajectory-major) of the steps with truncated and not done
+        self.bootstrap_index = None   # the same on the device; None when they are exactly the last step of every agent (the flush)
+        self.bootstrap_rows = None    # [m, ld] device rows: the next states of those steps, in the order of bootstrap_steps
+        self._warned_no_final_obs = False
 
     def _env_mask(self):
         """The environment's action_masks() for the observation the agents act on next, packed on the device; None without it."""
@@ -108,6 +121,36 @@ class VectorAgentManager(object):
         self._scalars_cache = (key, out)
         return out
 
+    def _final_obs_rows(self, info, dones, truncated, scalars):
+        """Environment-side truncations of one step (truncated and not done; `obs` is already the auto-reset observation there):
+        -> (agent indices, staged rows of info["final_observation"]) or None.  The rows take the standardisation scalars of that
+        step's returned observation and never enter the running statistics."""
+        sel = np.flatnonzero((np.asarray(truncated) != 0) & (np.asarray(dones) == 0))
+        if sel.size == 0:
+            return None
+        if not (isinstance(info, dict) and "final_observation" in info):
+            if not self._warned_no_final_obs:
+                self._warned_no_final_obs = True
+                warnings.warn("gae_bootstrap_truncated: the environment truncated an episode but its info has no 'final_observation': "
+                              "environment-side truncations bootstrap from the post-reset observation (the truncation at the end of "
+                              "every collect is not affected)", RuntimeWarning, stacklevel=3)
+            return None
+        fo = np.asarray(info["final_observation"], dtype=np.float32).reshape(self.n_agents, -1)[sel]
+        return sel, self.policy.arena.stage_obs(np.ascontiguousarray(fo), scalars)
+
+    def _bootstrap_out(self, dones_tm, trunc_tm, nxt_flat, last_rows, patched):
+        """Host flags [T, na] of a finished collect (flush rule applied) -> bootstrap_steps / bootstrap_index / bootstrap_rows.
+        With no terminal agent at the flush and no other truncation the rows are `last_rows` (the observations the agents act on
+        next) as they stand: no index upload and no gather."""
+        T, na = dones_tm.shape
+        hit = (trunc_tm != 0) & (dones_tm == 0)
+        self.bootstrap_steps = np.flatnonzero(hit.T)          # trajectory-major: a * T + t
+        if not patched and hit[T - 1].all() and not hit[:T - 1].any():
+            self.bootstrap_index, self.bootstrap_rows = None, last_rows
+            return
+        self.bootstrap_index = torch.from_numpy(self.bootstrap_steps).to(nxt_flat.device)
+        self.bootstrap_rows = nxt_flat.index_select(0, self.bootstrap_index)
+
     @torch.no_grad()
     def collect_timesteps(self, n):
         """-> ((states, actions, log_probs, rewards, next_states, dones, truncated), metrics, n_collected, seconds):
@@ -142,6 +185,7 @@ class VectorAgentManager(object):
         obs_dev, scalars = self._pending_obs
         stage = self._obs_staging(na, arena.d_in)
         mask, M = self._first_mask(), None
+        final_rows = []   # bootstrap_truncated: (t, agents, staged final observations) of environment-side truncations
         for t in range(T):
             if mask is not None:
                 if M is None:
@@ -168,6 +212,10 @@ class VectorAgentManager(object):
             if self.collect_metrics_fn is not None:
                 metrics.append(self.collect_metrics_fn(info["state"]))
             scalars = self._standardize_scalars()  # fetched BEFORE this step's increment (batched_agent_manager.py:230-235)
+            if self.bootstrap_truncated:
+                fin = self._final_obs_rows(info, row[1], row[2], scalars)
+                if fin is not None:
+                    final_rows.append((t,) + fin)
             if self.standardize_obs:  # same cadence as one worker response per step
                 if self.steps_since_obs_stats_update > self.steps_per_obs_stats_increment:
                     self._increment_obs_stats(obs_dev)
@@ -190,6 +238,10 @@ class VectorAgentManager(object):
         nxt_flat.view(na, T, ld).copy_(S[1:].transpose(0, 1))
         flat[N_].copy_(S[T][na - 1])                         # next_states[-1]: what add_new_experience appends (learner.py:347)
         rdt[2, T - 1] = np.where(rdt[1, T - 1] == 0, 1.0, 0.0)   # flush rule (quirk Q4)
+        if self.bootstrap_truncated:
+            for t, sel, rows in final_rows:
+                nxt_flat[torch.from_numpy(sel * T + t).to(dev)] = rows
+            self._bootstrap_out(rdt[1], rdt[2], nxt_flat, S[T], bool(final_rows))
         rdt_dev = torch.from_numpy(rdt).to(dev).transpose(1, 2).contiguous()   # [3, na, T]: trajectory-major, transposed on the device
         self.value_input_rows = flat
         self._next_rows = S[T]
@@ -225,6 +277,7 @@ class VectorAgentManager(object):
             self._next_rows = arena.stage_obs(self._initial_obs)
         rows = self._next_rows
         mask, M = self._first_mask(), None
+        patched = False   # bootstrap_truncated: a final observation went into the next-state rows
         for t in range(T):
             if mask is not None:
                 if M is None:
@@ -263,8 +316,15 @@ class VectorAgentManager(object):
             self._track_rewards(rews[:, t], (dones[:, t] + trunc[:, t]) > 0)
             rows = arena.stage_obs(obs_dev, scalars)
             n3[:, t].copy_(rows)
+            if self.bootstrap_truncated:
+                fin = self._final_obs_rows(info, dones[:, t], trunc[:, t], scalars)
+                if fin is not None:
+                    nxt_flat[torch.from_numpy(fin[0] * T + t).to(dev)] = fin[1]
+                    patched = True
         flat[N_].copy_(rows[na - 1])                      # next_states[-1]: what add_new_experience appends (learner.py:347)
         trunc[:, T - 1] = np.where(dones[:, T - 1] == 0, 1.0, 0.0)   # flush rule (quirk Q4)
+        if self.bootstrap_truncated:
+            self._bootstrap_out(dones.T, trunc.T, nxt_flat, rows, patched)
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x.reshape(-1))).to(dev)
         self.value_input_rows = flat
         self._next_rows = rows

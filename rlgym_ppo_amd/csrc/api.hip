@@ -623,7 +623,17 @@ int rlppo_gae(void *stream, const float *rews, const float *dones, const float *
     if (n == 0) return 0;
     RLPPO_CHECK_ARG(n > 0 && rews && dones && truncated && values && value_targets && advantages && returns && workspace,
                     "gae: bad argument");
-    return launch_gae((hipStream_t)stream, rews, dones, truncated, values, n, gamma, lmbda, return_std, value_targets,
+    return launch_gae((hipStream_t)stream, rews, dones, truncated, values, nullptr, n, gamma, lmbda, return_std, value_targets,
+                      advantages, returns, workspace, ws_bytes);
+}
+
+int rlppo_gae_boot(void *stream, const float *rews, const float *dones, const float *truncated, const float *values,
+                   const float *boot_values, int64_t n, double gamma, double lmbda, float return_std, float *value_targets,
+                   float *advantages, float *returns, void *workspace, size_t ws_bytes) {
+    if (n == 0) return 0;
+    RLPPO_CHECK_ARG(n > 0 && rews && dones && truncated && values && value_targets && advantages && returns && workspace,
+                    "gae_boot: bad argument");
+    return launch_gae((hipStream_t)stream, rews, dones, truncated, values, boot_values, n, gamma, lmbda, return_std, value_targets,
                       advantages, returns, workspace, ws_bytes);
 }
 

@@ -277,7 +277,8 @@ void set_gae_spin_limit(int v);
 void set_gae_oversubscribe(int v);
 void set_fused_spin_limit(int v);
 void set_fused_test_hold(int v);
-int launch_gae(hipStream_t, const float *, const float *, const float *, const float *, int64_t, double, double, float,
+// (rews, dones, truncated, values, boot_values or null, n, gamma, lambda, return_std, value_targets, advantages, returns, ws, bytes)
+int launch_gae(hipStream_t, const float *, const float *, const float *, const float *, const float *, int64_t, double, double, float,
                float *, float *, float *, void *, size_t);
 
 // optim.hip -------------------------------------------------------------------------------------------

@@ -16,6 +16,12 @@
 //                   in-block suffix scan with wave shuffles and writes the three outputs.
 // Arithmetic: float32 reward scaling, float64 recurrences, one rounding to float32 at the store -- the reference's
 // behaviour under its pinned NumPy < 2 (oracle/gae_oracle.c mode 0).
+//
+// BOOT form (rlppo_gae_boot): at a step that is truncated and not done, V_{t+1} in b_t is boot[t] -- V of the step's own next
+// state -- instead of values[t + 1], the first state of whichever trajectory follows.  boot[] is USED at those steps only (the
+// other entries may hold anything); it is read as a fifth input stream beside the other four and selected by the flags
+// (BOOT_DENSE below: why not a sparse load).  Every kernel has a BOOT instantiation and a call without boot values launches
+// the plain ones.
 #include <atomic>
 #include <chrono>
 
@@ -100,13 +106,41 @@ struct Steps {
 
 struct RawSteps {
     float r[GAE_EPT], d[GAE_EPT], tr[GAE_EPT], v[GAE_EPT + 1];
+    float bv[GAE_EPT];  // BOOT form with BOOT_DENSE only (never touched otherwise)
 };
+// How the BOOT form fetches boot[]: 1 (the product) = all of boot[] is requested together with the other four streams (32
+// algorithmic bytes per step instead of 28) and the flags select afterwards; 0 = an A/B build (`make variant NAME=gae_boot_sparse
+// SRC=gae DEFS=-DGAE_BOOT_DENSE_V=0`, tools/gae_bootstrap_cost.py --sparse-lib) with a sparse load behind the flags, at
+// truncated-and-not-done steps only (28 B per step + one sector per such step).  The sparse form moves fewer bytes and is SLOWER:
+// its load can only be issued once the flags have arrived, a second memory round trip on the critical path of workgroups that all
+// move in lockstep (one resident wave of workgroups covers the 8192 x 256 scan) -- about +10 % / +16 % over the plain scan at
+// one truncated step per 256 / per 16, against about +7 % / +7 % dense (profiles/gae_bootstrap_cost.json).
+// Either way an entry that is not to be used never reaches an output (a select, not arithmetic).
+#ifndef GAE_BOOT_DENSE_V
+#define GAE_BOOT_DENSE_V 1
+#endif
+constexpr bool BOOT_DENSE = GAE_BOOT_DENSE_V;
 
 // the loads only (so that a caller can put independent work between issuing them and consuming them)
+template <bool DENSE = false>
 __device__ __forceinline__ void load_raw(const float *__restrict__ rews, const float *__restrict__ dones,
                                          const float *__restrict__ trunc, const float *__restrict__ values, int64_t t0,
-                                         int64_t n, RawSteps &w) {
+                                         int64_t n, RawSteps &w, const float *__restrict__ boot = nullptr) {
     float *r = w.r, *d = w.d, *tr = w.tr, *v = w.v;
+    if constexpr (DENSE) {
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        if (t0 + GAE_EPT <= n) {
+#pragma unroll
+            for (int h = 0; h < GAE_EPT / 4; ++h) {
+                const f4 b4 = *reinterpret_cast<const f4 *>(boot + t0 + 4 * h);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w.bv[4 * h + e] = b4[e];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < GAE_EPT; ++e) w.bv[e] = t0 + e < n ? boot[t0 + e] : 0.f;
+        }
+    }
     if (t0 + GAE_EPT <= n) {
         typedef float f4 __attribute__((ext_vector_type(4)));
 #pragma unroll
@@ -140,7 +174,19 @@ __device__ __forceinline__ void load_raw(const float *__restrict__ rews, const f
     }
 }
 
-__device__ __forceinline__ void make_steps(const RawSteps &w, int64_t t0, int64_t n, const GaeParams &p, Steps &s) {
+// the V_{t+1} of one step: its own bootstrap value where the step is truncated and not done (BOOT), else the next entry of values
+template <bool BOOT>
+__device__ __forceinline__ float next_value(float d, float tr, float v1, const float *__restrict__ boot, int64_t t) {
+    if constexpr (BOOT) {
+        if (tr != 0.f && d == 0.f) v1 = boot[t];
+    }
+    return v1;
+}
+__device__ __forceinline__ float next_value_dense(float d, float tr, float v1, float b) { return tr != 0.f && d == 0.f ? b : v1; }
+
+template <bool BOOT>
+__device__ __forceinline__ void make_steps(const RawSteps &w, int64_t t0, int64_t n, const GaeParams &p, const float *__restrict__ boot,
+                                           Steps &s) {
     const float *r = w.r, *d = w.d, *tr = w.tr, *v = w.v;
     s.mbits = 0;
 #pragma unroll
@@ -149,7 +195,9 @@ __device__ __forceinline__ void make_steps(const RawSteps &w, int64_t t0, int64_
             const float ndf = 1.0f - d[e], ntf = 1.0f - tr[e];
             float rn = r[e];
             if (p.use_std) rn = fminf(fmaxf(r[e] / p.ret_std, -10.f), 10.f);
-            s.b_adv[e] = ((double)rn + p.gamma * (double)v[e + 1] * (double)ndf) - (double)v[e];
+            const float v1 = BOOT && BOOT_DENSE ? next_value_dense(d[e], tr[e], v[e + 1], w.bv[e])
+                                                : next_value<BOOT>(d[e], tr[e], v[e + 1], boot, t0 + e);
+            s.b_adv[e] = ((double)rn + p.gamma * (double)v1 * (double)ndf) - (double)v[e];
             s.mbits |= (ndf * ntf != 0.f ? 1u : 0u) << e;  // (0/1 flags: the float product is the exact 0/1 the reference's double one is)
             s.r[e] = r[e];
         } else {  // past the end: the zero map
@@ -160,12 +208,13 @@ __device__ __forceinline__ void make_steps(const RawSteps &w, int64_t t0, int64_
     }
 }
 
+template <bool BOOT>
 __device__ __forceinline__ void load_steps(const float *__restrict__ rews, const float *__restrict__ dones,
                                            const float *__restrict__ trunc, const float *__restrict__ values,
-                                           int64_t t0, int64_t n, const GaeParams &p, Steps &s) {
+                                           int64_t t0, int64_t n, const GaeParams &p, const float *__restrict__ boot, Steps &s) {
     RawSteps w;
-    load_raw(rews, dones, trunc, values, t0, n, w);
-    make_steps(w, t0, n, p, s);
+    load_raw<BOOT && BOOT_DENSE>(rews, dones, trunc, values, t0, n, w, boot);
+    make_steps<BOOT>(w, t0, n, p, boot, s);
 }
 
 __device__ __forceinline__ double coef_adv(const Steps &s, int e, const GaeParams &p) { return (s.mbits >> e) & 1u ? p.gl : 0.0; }
@@ -199,19 +248,22 @@ __device__ __forceinline__ Aff2 block_reduce(Aff2 v, Aff2 *lds4) {
     return compose(compose(lds4[0], lds4[1]), compose(lds4[2], lds4[3]));
 }
 
+template <bool BOOT>
 __global__ __launch_bounds__(GAE_THREADS) void gae_summary_kernel(const float *__restrict__ rews,
                                                                    const float *__restrict__ dones,
                                                                    const float *__restrict__ trunc,
                                                                    const float *__restrict__ values, int64_t n,
-                                                                   GaeParams p, Aff2 *__restrict__ summaries) {
+                                                                   GaeParams p, Aff2 *__restrict__ summaries,
+                                                                   const float *__restrict__ boot) {
     __shared__ Aff2 lds4[4];
     const int64_t t0 = ((int64_t)blockIdx.x * GAE_THREADS + threadIdx.x) * GAE_EPT;
     Steps s;
-    load_steps(rews, dones, trunc, values, t0, n, p, s);
+    load_steps<BOOT>(rews, dones, trunc, values, t0, n, p, boot, s);
     const Aff2 c = block_reduce(thread_composite(s, p), lds4);
     if (threadIdx.x == 0) summaries[blockIdx.x] = c;
 }
 
+template <bool BOOT>
 __global__ __launch_bounds__(GAE_THREADS) void gae_apply_kernel(const float *__restrict__ rews,
                                                                  const float *__restrict__ dones,
                                                                  const float *__restrict__ trunc,
@@ -219,7 +271,8 @@ __global__ __launch_bounds__(GAE_THREADS) void gae_apply_kernel(const float *__r
                                                                  GaeParams p, const Aff2 *__restrict__ summaries,
                                                                  int n_blocks, float *__restrict__ vt_out,
                                                                  float *__restrict__ adv_out,
-                                                                 float *__restrict__ ret_out) {
+                                                                 float *__restrict__ ret_out,
+                                                                 const float *__restrict__ boot) {
     __shared__ Aff2 lds4[4];
     __shared__ Aff2 wave_tot[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -227,7 +280,7 @@ __global__ __launch_bounds__(GAE_THREADS) void gae_apply_kernel(const float *__r
 
     // issue this block's loads first; the carry look-up below overlaps with them
     Steps s;
-    load_steps(rews, dones, trunc, values, t0, n, p, s);
+    load_steps<BOOT>(rews, dones, trunc, values, t0, n, p, boot, s);
 
     // ---- carry-in: x at the first step of block+1 = (composite of every block to the right)(0)
     Aff2 right = aff_identity();
@@ -413,7 +466,7 @@ __device__ __forceinline__ void resolve_carry(const int chunk, const int n_block
 #define GAE_STORE_T_V 1
 #endif
 constexpr bool STORE_T = GAE_STORE_T_V;  // lane-contiguous output stores through an in-wave LDS transpose ([r4]; 0 = rounds 1-3's shape, for A/B builds)
-template <bool LOOP>
+template <bool LOOP, bool BOOT>
 __global__ __launch_bounds__(GAE_THREADS, 4) void gae_lookback_kernel(const float *__restrict__ rews,
                                                                     const float *__restrict__ dones,
                                                                     const float *__restrict__ trunc,
@@ -423,7 +476,8 @@ __global__ __launch_bounds__(GAE_THREADS, 4) void gae_lookback_kernel(const floa
                                                                     unsigned *__restrict__ slow_word, int n_blocks,
                                                                     float *__restrict__ vt_out,
                                                                     float *__restrict__ adv_out,
-                                                                    float *__restrict__ ret_out) {
+                                                                    float *__restrict__ ret_out,
+                                                                    const float *__restrict__ boot) {
     __shared__ Aff2 wave_tot[4];
     __shared__ Aff2 wave_la[4];  // look-ahead window of the next chunk: per-wave composites (64 steps each)
     __shared__ double s_carry[2];
@@ -456,17 +510,24 @@ __global__ __launch_bounds__(GAE_THREADS, 4) void gae_lookback_kernel(const floa
         l_v = values[lt0];
         l_v1 = values[lt0 + 1];
     }
+    float l_b = 0.f;
+    if constexpr (BOOT && BOOT_DENSE) {
+        if (l_ok) l_b = boot[lt0];
+    }
     RawSteps raw;
-    load_raw(rews, dones, trunc, values, t0, n, raw);
+    load_raw<BOOT && BOOT_DENSE>(rews, dones, trunc, values, t0, n, raw, boot);
     {   // the window's composite while the chunk's own loads are still in flight (the window's were issued first)
         Aff2 l1 = aff_identity();  // steps past the end: identity (x = 0 there is handled by covers_all in resolve_carry)
-        if (l_ok) l1 = step_affine(l_r, l_d, l_t, l_v, l_v1, p);
+        // (BOOT: a truncated step of the window contributes its own bootstrap value, as it does in its own chunk's scan)
+        if (l_ok)
+            l1 = step_affine(l_r, l_d, l_t, l_v,
+                             BOOT && BOOT_DENSE ? next_value_dense(l_d, l_t, l_v1, l_b) : next_value<BOOT>(l_d, l_t, l_v1, boot, lt0), p);
         const Aff2 ls = wave_suffix_scan(l1, lane);
         if (lane == 0) wave_la[wave] = ls;
     }
     __builtin_amdgcn_sched_barrier(0);
     Steps s;
-    make_steps(raw, t0, n, p, s);
+    make_steps<BOOT>(raw, t0, n, p, boot, s);
     const Aff2 mine = thread_composite(s, p);
     // Who will ever read this chunk's records?  Only the chunk to the left, and only if its look-ahead over OUR first
     // LOOKAHEAD steps finds no trajectory end (a chunk whose own carry came from the fast path publishes its inclusive value
@@ -553,6 +614,7 @@ static int g_gae_oversubscribe = 0;  // rlppo_dbg_set(22, 0/1)
 void set_gae_oversubscribe(int v) { g_gae_oversubscribe = v; }
 static int g_gae_algo = 1;  // 1 = single-pass look-back (default), 0 = two launches (summary + apply)
 void set_gae_algo(int a) { g_gae_algo = a; }
+static std::atomic<unsigned> g_tag{0};  // per-launch record tags (launch_gae_form), one counter for both forms
 static unsigned g_gae_spin_limit = LB_SPIN_LIMIT;  // rlppo_dbg_set(21, v): tests set 0 to force the timeout path
 void set_gae_spin_limit(int v) { g_gae_spin_limit = v < 0 ? LB_SPIN_LIMIT : (unsigned)v; }
 
@@ -561,12 +623,15 @@ void set_gae_spin_limit(int v) { g_gae_spin_limit = v < 0 ? LB_SPIN_LIMIT : (uns
 // region for its per-chunk composites (32 B per chunk)
 size_t gae_workspace_bytes(int64_t n) { return 16 + (size_t)(cdiv(n > 0 ? n : 1, GAE_BLOCK)) * LB_STRIDE * sizeof(u64); }
 
-int launch_gae(hipStream_t st, const float *rews, const float *dones, const float *trunc, const float *values, int64_t n,
-               double gamma, double lmbda, float ret_std, float *vt, float *adv, float *ret, void *ws, size_t ws_bytes) {
+// BOOT = false: `boot` is ignored (null) and the launches are the plain instantiations
+template <bool BOOT>
+static int launch_gae_form(hipStream_t st, const float *rews, const float *dones, const float *trunc, const float *values,
+                           const float *boot, int64_t n, double gamma, double lmbda, float ret_std, float *vt, float *adv, float *ret,
+                           void *ws, size_t ws_bytes) {
     if (n == 0) return 0;
     RLPPO_CHECK_ARG(n > 0, "gae: n=%ld", (long)n);
     RLPPO_CHECK_ARG(((uintptr_t)rews | (uintptr_t)dones | (uintptr_t)trunc | (uintptr_t)values | (uintptr_t)vt |
-                     (uintptr_t)adv | (uintptr_t)ret | (uintptr_t)ws) % 16 == 0,
+                     (uintptr_t)adv | (uintptr_t)ret | (uintptr_t)ws | (uintptr_t)boot) % 16 == 0,
                     "gae: arrays and workspace must be 16-byte aligned");
     if (ws_bytes < gae_workspace_bytes(n)) {
         set_error("gae: workspace %zu < %zu bytes", ws_bytes, gae_workspace_bytes(n));
@@ -587,7 +652,7 @@ int launch_gae(hipStream_t st, const float *rews, const float *dones, const floa
         // The LOOP form (more chunks than the grid) makes a workgroup of round k wait on one of round k - 1, which is only safe
         // while the whole grid is resident -- and other streams' kernels may hold some of the slots the occupancy query counts:
         // the grid is therefore kept one workgroup per CU BELOW the theoretical occupancy.
-        static std::atomic<int> resident_by_dev[64], cus_by_dev[64];
+        static std::atomic<int> resident_by_dev[64], cus_by_dev[64];  // (function-local: one pair per form)
         int dev = 0;
         RLPPO_HIP(hipGetDevice(&dev));
         RLPPO_CHECK_ARG(dev >= 0 && dev < 64, "gae: device id %d", dev);
@@ -596,7 +661,7 @@ int launch_gae(hipStream_t st, const float *rews, const float *dones, const floa
             int per_cu = 0;
             hipDeviceProp_t prop;
             RLPPO_HIP(hipGetDeviceProperties(&prop, dev));
-            RLPPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gae_lookback_kernel<true>, GAE_THREADS, 0));
+            RLPPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gae_lookback_kernel<true, BOOT>, GAE_THREADS, 0));
             // the occupancy API over-reports by one block per CU only in the SGPR-limited 7-8 blocks/CU regime
             // (MI355X_MICROARCH.md "Residency and cooperative launch"); this kernel is VGPR-limited far below that
             per_cu = per_cu > 6 ? 6 : (per_cu < 1 ? 1 : per_cu);
@@ -615,7 +680,6 @@ int launch_gae(hipStream_t st, const float *rews, const float *dones, const floa
         int grid = (nb <= resident || g_gae_oversubscribe) ? nb : loop_grid;
         // per-launch tag: process-wide counter seeded from the clock (a recycled workspace may hold records of another
         // process's launches), never 0 (zero-filled memory)
-        static std::atomic<unsigned> g_tag{0};
         if (g_tag.load(std::memory_order_relaxed) == 0) {
             unsigned expect = 0;
             const unsigned seed = (unsigned)std::chrono::steady_clock::now().time_since_epoch().count() | 1u;
@@ -623,19 +687,26 @@ int launch_gae(hipStream_t st, const float *rews, const float *dones, const floa
         }
         unsigned tag = g_tag.fetch_add(1, std::memory_order_relaxed) + 1;
         if (tag == 0) tag = g_tag.fetch_add(1, std::memory_order_relaxed) + 1;
-        auto *kern = grid == nb ? gae_lookback_kernel<false> : gae_lookback_kernel<true>;
+        auto *kern = grid == nb ? gae_lookback_kernel<false, BOOT> : gae_lookback_kernel<true, BOOT>;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, state, tag, g_gae_spin_limit,
-                           hdr + 1, nb, vt, adv, ret);
+                           hdr + 1, nb, vt, adv, ret, boot);
         RLPPO_LAUNCH_CHECK();
         return 0;
     }
     Aff2 *summ = reinterpret_cast<Aff2 *>(reinterpret_cast<char *>(ws) + 16);
-    hipLaunchKernelGGL(gae_summary_kernel, dim3(nb), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, summ);
+    hipLaunchKernelGGL(gae_summary_kernel<BOOT>, dim3(nb), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, summ, boot);
     RLPPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gae_apply_kernel, dim3(nb), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, summ, nb,
-                       vt, adv, ret);
+    hipLaunchKernelGGL(gae_apply_kernel<BOOT>, dim3(nb), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, summ, nb,
+                       vt, adv, ret, boot);
     RLPPO_LAUNCH_CHECK();
     return 0;
+}
+
+// boot == nullptr: exactly the plain scan
+int launch_gae(hipStream_t st, const float *rews, const float *dones, const float *trunc, const float *values, const float *boot,
+               int64_t n, double gamma, double lmbda, float ret_std, float *vt, float *adv, float *ret, void *ws, size_t ws_bytes) {
+    if (boot) return launch_gae_form<true>(st, rews, dones, trunc, values, boot, n, gamma, lmbda, ret_std, vt, adv, ret, ws, ws_bytes);
+    return launch_gae_form<false>(st, rews, dones, trunc, values, nullptr, n, gamma, lmbda, ret_std, vt, adv, ret, ws, ws_bytes);
 }
 
 }  // namespace rlppo

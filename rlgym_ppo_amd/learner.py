@@ -40,7 +40,7 @@ class Learner(object):
             checkpoints_save_folder=None, add_unix_timestamp: bool = True, checkpoint_load_folder="latest",
             save_every_ts: int = 1_000_000, instance_launch_delay=None, random_seed: int = 123,
             n_checkpoints_to_keep: int = 5, shm_buffer_size: int = 8192, device: str = "auto",
-            vector_env: bool = False, per_feature_obs_standardization: bool = False,
+            vector_env: bool = False, gae_bootstrap_truncated: bool = False, per_feature_obs_standardization: bool = False,
             ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
         assert env_create_function is not None, "MUST PROVIDE A FUNCTION TO CREATE RLGYM FUNCTIONS TO INITIALIZE RLGYM-PPO"
         if checkpoints_save_folder is None:
@@ -91,6 +91,11 @@ class Learner(object):
         # not in the reference (which standardises every feature with the statistics of feature 0, quirk Q5): every feature
         # with its own running mean / std
         self.agent.per_feature_obs_standardization = bool(per_feature_obs_standardization)
+        # not in the reference (quirk Q3: a truncated step bootstraps from values[step + 1], the first state of whichever trajectory
+        # follows in concatenation order): bootstrap it from V of its own next state, as SB3 / CleanRL / Gymnasium's time limits do
+        self.gae_bootstrap_truncated = bool(gae_bootstrap_truncated)
+        if vector_env:
+            self.agent.bootstrap_truncated = self.gae_bootstrap_truncated
         obs_space_size, act_space_size, action_space_type = self.agent.init_processes(
             n_processes=n_proc, build_env_fn=env_create_function, collect_metrics_fn=collect_metrics_fn,
             spawn_delay=instance_launch_delay, render=render, render_delay=render_delay, shm_buffer_size=shm_buffer_size)
@@ -115,6 +120,7 @@ class Learner(object):
             "ppo_batch_size": ppo_batch_size, "ppo_minibatch_size": ppo_minibatch_size, "ppo_ent_coef": ppo_ent_coef,
             "ppo_clip_range": ppo_clip_range, "gae_lambda": gae_lambda, "gae_gamma": gae_gamma, "policy_lr": policy_lr,
             "critic_lr": critic_lr, "shm_buffer_size": shm_buffer_size,
+            "gae_bootstrap_truncated": self.gae_bootstrap_truncated,  # (a hyper-parameter, not checkpoint state)
         }
 
         self.wandb_run = wandb_run
@@ -198,28 +204,56 @@ class Learner(object):
     @torch.no_grad()
     def add_new_experience(self, experience):
         """Value pass on [N+1, d] (states + the last next_state, learner.py:347-349), GAE, return statistics, buffer
-        submit -- all on the device; only min(150, N) returns come back to the host (learner.py:368-372)."""
+        submit -- all on the device; only min(150, N) returns come back to the host (learner.py:368-372).
+
+        gae_bootstrap_truncated: the m steps that are truncated and not done (known from the HOST copies of the flags: no
+        read-back) get V of their own next state -- process mode: m more rows in the one value pass; vector mode: a value pass
+        on the manager's m next-state rows -- scattered into a length-N device buffer for the bootstrap form of the scan."""
         states, actions, log_probs, rewards, next_states, dones, truncated = experience
         value_net = self.ppo_learner.value_net
         n = states.shape[0]
         on_device = isinstance(states, torch.Tensor) and states.is_cuda   # VectorAgentManager: rollout already in HBM
+        boot_values = boot_idx = None
         if on_device:
             rows = self.agent.value_input_rows               # [N+1, ld]: states ++ the last next_state, padded
             assert rows.shape[0] == n + 1 and rows.data_ptr() == states.data_ptr()
             d_logical = int(self.ppo_learner.policy.arena.d_in)
+            val_preds = value_net.forward_padded(rows).contiguous()
+            if self.gae_bootstrap_truncated and self.agent.bootstrap_steps.size:
+                boot_idx = self.agent.bootstrap_index        # None: exactly the last step of every agent (the flush)
+                boot_values = value_net.forward_padded(self.agent.bootstrap_rows)
         else:
-            val_inp = np.concatenate([np.asarray(states).reshape(n, -1), np.asarray(next_states[-1]).reshape(1, -1)], axis=0)
-            rows = value_net.arena.stage_obs(val_inp)        # zero-padded fp32 device rows [N+1, ld]
-            d_logical = int(np.asarray(states).reshape(n, -1).shape[1])
-        val_preds = value_net.forward_padded(rows).contiguous()
+            flat_states = np.asarray(states).reshape(n, -1)
+            parts = [flat_states, np.asarray(next_states[-1]).reshape(1, -1)]
+            if self.gae_bootstrap_truncated:
+                steps = np.flatnonzero((np.asarray(truncated).reshape(n) != 0) & (np.asarray(dones).reshape(n) == 0))
+                if steps.size:
+                    parts.append(np.asarray(next_states).reshape(n, -1)[steps])
+                    boot_idx = steps
+            val_inp = np.concatenate(parts, axis=0)
+            rows = value_net.arena.stage_obs(val_inp)        # zero-padded fp32 device rows [N+1 (+m), ld]
+            d_logical = int(flat_states.shape[1])
+            val_preds = value_net.forward_padded(rows).contiguous()
+            if boot_idx is not None:
+                boot_values, val_preds = val_preds[n + 1:], val_preds[:n + 1]
+                boot_idx = torch.from_numpy(boot_idx).to(rows.device)
+                rows = rows[:n + 1]
 
         dev = rows.device
+        if boot_values is not None:   # scatter the m values to their steps; the other entries are never used (include/rlppo.h)
+            m, boot = boot_values.shape[0], torch.empty(n, dtype=torch.float32, device=dev)
+            if boot_idx is None:
+                boot.view(m, n // m)[:, -1] = boot_values
+            else:
+                boot[boot_idx] = boot_values
+            boot_values = boot
         up = lambda x: x.to(dev, torch.float32) if isinstance(x, torch.Tensor) else \
             torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32))).to(dev)
         rews_d, dones_d, trunc_d = up(rewards), up(dones), up(truncated)
         ret_std = self.return_stats.std[0] if self.standardize_returns else None
         value_targets, advantages, returns, gae_timeouts = torch_functions.gae_device_deferred(
-            rews_d, dones_d, trunc_d, val_preds, gamma=self.gae_gamma, lmbda=self.gae_lambda, return_std=ret_std)
+            rews_d, dones_d, trunc_d, val_preds, gamma=self.gae_gamma, lmbda=self.gae_lambda, return_std=ret_std,
+            **({} if boot_values is None else {"boot_values": boot_values}))
 
         # ONE device-to-host read per call: the scan's timeout counter travels with the min(150, N) returns the statistics need
         n_to_increment = min(self.max_returns_per_stats_increment, n) if self.standardize_returns else 0
