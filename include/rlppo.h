@@ -43,6 +43,7 @@ extern "C" {
 #define RLPPO_ERR_WORKSPACE 1002  /* workspace too small */
 #define RLPPO_ERR_COLLECT_TIMEOUT 1003  /* rlppo_collector_collect: no worker message for a minute */
 #define RLPPO_ERR_INTERRUPTED 1004     /* rlppo_collector_collect: a signal arrived; n_collected holds the progress, call again with resume = 1 */
+#define RLPPO_ERR_MASK_ROW 1005        /* rlppo_collector_ready_masks: a worker reported an action-mask row without a valid action */
 
 /* policy head codes == the reference's `policy_type` (ppo_learner.py:34-50) */
 #define RLPPO_HEAD_DISCRETE 0
@@ -130,8 +131,10 @@ typedef struct rlppo_act_opts {
      * pc_c / q_c (the clamp's floor never makes an invalid action selectable), logp = log(pc_action).  noise_q stays
      * [n][n_actions]: the entries of invalid actions are ignored.  probs_out / rlppo_discrete_probs (with and without clamp_probs)
      * hold 0 on invalid actions and flat_argmax runs over valid entries only.  A row without a valid action is treated as all-valid
-     * (hosts reject such rows before they get here).  An all-valid mask gives the unmasked results bit for bit.  Not together with
-     * noise_ctl (rlppo_discrete_step_one_launch answers 0 for that pair, rlppo_discrete_step RLPPO_ERR_ARG). */
+     * (hosts reject such rows before they get here).  An all-valid mask gives the unmasked results bit for bit.  Together with
+     * noise_ctl (rlppo_discrete_step's one-launch kernel) only the noise is late: the words are in place BEFORE the launch, in
+     * memory the kernel reads like its observations (a host window, or pinned memory), and rows at and beyond the live-row word
+     * -- whose mask words may be stale -- store nothing. */
     const uint32_t *action_mask;
     int32_t mask_words;
 } rlppo_act_opts;
@@ -490,7 +493,16 @@ int rlppo_learn_report(void *stream, const rlppo_report_args *args);
  *   finish: flushes every trajectory -> the sizes _emit needs; emit: states / next_states [n][obs_dim], actions [n][act_width],
  *     log_probs [n] float32, rewards / dones / truncated [n] float64 (the dtypes the reference's lists become), and every message's
  *     metrics record (values flat; 9 ints per record: rank, dimensions).
- *   average_reward: get (set == 0) / set the manager's running average (is_none: it has not seen an episode end yet). */
+ *   average_reward: get (set == 0) / set the manager's running average (is_none: it has not seen an episode end yet).
+ * Masked runs (the workers' environments have action_masks(): the opt-in mask trailer of comm_consts.py, n_agents x n_actions
+ * floats of 0 / 1 behind every observation).  Masks cross this boundary as BYTES, one per action, 0 = invalid (the host packs them
+ * to the kernels' words where it stages them for a launch: util/action_mask.py):
+ *   set_masked: once, before the first _collect: every slab carries the trailer for n_actions actions.
+ *   set_mask: the mask [rows][n_actions] of the observation last given to set_obs for that worker.
+ *   ready_masks: after _ready, the mask rows of exactly that batch, row for row with its observations; RLPPO_ERR_MASK_ROW (the
+ *     text names worker and agent) when a row has no valid action -- nothing has been sent for the batch at that point.
+ *   emit_masks: between _finish and _emit, the masks the actions were sampled under, [n_steps][n_actions], row for row with
+ *     _emit's states. */
 int rlppo_collector_create(int32_t n_workers, const int32_t *socket_fds, const int32_t *peer_ports, const float *shm_base,
                            int64_t shm_floats_per_worker, int32_t obs_dim, void **handle);
 int rlppo_collector_destroy(void *handle);
@@ -504,6 +516,10 @@ int rlppo_collector_finish(void *handle, int64_t *n_steps, int32_t *act_width, i
 int rlppo_collector_emit(void *handle, float *states, float *actions, float *log_probs, double *rewards, float *next_states, double *dones,
                          double *truncated, float *metrics_values, int32_t *metrics_shapes);
 int rlppo_collector_average_reward(void *handle, int32_t set, double *value, int32_t *is_none);
+int rlppo_collector_set_masked(void *handle, int32_t n_actions);
+int rlppo_collector_set_mask(void *handle, int32_t worker, const uint8_t *mask, int32_t rows);
+int rlppo_collector_ready_masks(void *handle, uint8_t *mask_out, int64_t cap_rows);
+int rlppo_collector_emit_masks(void *handle, uint8_t *masks);
 
 /* ------------------------------------------------------------------------------------- data-parallel exchange */
 

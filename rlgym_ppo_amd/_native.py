@@ -158,6 +158,10 @@ SIGNATURES = {
     "rlppo_collector_finish": (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int32), POINTER(c_int64), POINTER(c_int64)]),
     "rlppo_collector_emit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rlppo_collector_average_reward": (c_int32, [c_void_p, c_int32, POINTER(c_double), POINTER(c_int32)]),
+    "rlppo_collector_set_masked": (c_int32, [c_void_p, c_int32]),
+    "rlppo_collector_set_mask": (c_int32, [c_void_p, c_int32, c_void_p, c_int32]),
+    "rlppo_collector_ready_masks": (c_int32, [c_void_p, c_void_p, c_int64]),
+    "rlppo_collector_emit_masks": (c_int32, [c_void_p, c_void_p]),
     "rlppo_comm_set_library": (c_int32, [ctypes.c_char_p]),
     "rlppo_comm_unique_id": (c_int32, [c_void_p]),
     "rlppo_comm_init": (c_int32, [c_int32, c_int32, c_void_p]),

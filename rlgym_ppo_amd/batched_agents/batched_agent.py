@@ -5,7 +5,6 @@ side of the protocol can be swapped for the reference's."""
 import pickle
 import socket
 import time
-import warnings
 
 import numpy as np
 
@@ -33,14 +32,17 @@ class StepSlab:
         self.view = np.frombuffer(shm_buffer, dtype=np.float32, offset=shm_offset, count=shm_size)
         self.size = shm_size
 
-    def write_step(self, prev_n_agents, done, truncated, rewards, metrics, metrics_shape, obs):
+    def write_step(self, prev_n_agents, done, truncated, rewards, metrics, metrics_shape, obs, mask=None):
         """obs: float32 array as the environment returned it (rank 1 for a one-agent env, rank 2 otherwise); metrics_shape: []
-        when the worker has no metrics function, else the shape of what it returned (batched_agent.py:146-151)."""
+        when the worker has no metrics function, else the shape of what it returned (batched_agent.py:146-151).  mask (a worker
+        whose environment has action_masks() only): float32 [n_agents, n_actions] of 0 / 1, appended behind the observation."""
         metrics = np.asarray(metrics, dtype=np.float32)
         metrics_shape = [float(d) for d in metrics_shape]
         state_shape = [float(d) for d in obs.shape]
         head = [float(prev_n_agents), float(done), float(truncated), float(len(state_shape)), float(len(metrics_shape))]
         parts = [head, metrics_shape, state_shape, [float(r) for r in rewards], metrics.ravel(), obs.ravel()]
+        if mask is not None:
+            parts.append(mask.ravel())
         count = sum(len(p) for p in parts)
         assert count <= self.size, "ATTEMPTED TO CREATE AGENT MESSAGE BUFFER LARGER THAN MAXIMUM ALLOWED SIZE"
         o = 0
@@ -49,6 +51,28 @@ class StepSlab:
             self.view[o:o + n] = p
             o += n
         return count
+
+
+def env_action_masks(env, n_agents):
+    """env.action_masks() for the observation the worker is about to report, as the trailer's float32 [n_agents, n_actions] of
+    0 / 1 ([n_actions] from a one-agent environment becomes one row)."""
+    m = np.asarray(env.action_masks())
+    m = m.reshape(1, -1) if m.ndim == 1 else m
+    if m.ndim != 2 or m.shape[0] != n_agents:
+        raise ValueError(f"action_masks() returned shape {tuple(m.shape)} for {n_agents} agents")
+    return (m != 0).astype(np.float32)
+
+
+def reset_state_message(obs, mask=None):
+    """The ENV_RESET_STATE_HEADER datagram of an observation (+ the mask trailer of a masked worker)."""
+    shape = [float(d) for d in obs.shape]
+    msg = C.pack_message(C.ENV_RESET_STATE_HEADER + [float(len(shape))] + shape) + obs.tobytes()
+    if mask is not None:
+        msg += mask.tobytes()
+        # (the learner reads PACKET_MAX_SIZE bytes of a datagram and UDP drops the rest without a word)
+        assert len(msg) <= C.PACKET_MAX_SIZE, "ATTEMPTED TO SEND A MASKED RESET STATE LARGER THAN THE LARGEST DATAGRAM THE LEARNER READS " \
+            "(%d > %d BYTES)" % (len(msg), C.PACKET_MAX_SIZE)
+    return msg
 
 
 def batched_agent_process(proc_id, endpoint, shm_buffer, shm_offset, shm_size, seed, render, render_delay):
@@ -67,14 +91,10 @@ def batched_agent_process(proc_id, endpoint, shm_buffer, shm_offset, shm_size, s
                 env = build_env_fn()
         if hasattr(env.action_space, "seed"):
             env.action_space.seed(seed)
-        if proc_id == 0 and hasattr(env, "action_masks"):  # (said once: by the first worker)
-            warnings.warn("the environment offers action_masks(), but process-mode collection has no room for a mask in its wire "
-                          "format (the reference's, byte for byte): running UNMASKED.  Invalid-action masking needs "
-                          "Learner(..., vector_env=True).")
+        masked = hasattr(env, "action_masks")  # the opt-in mask trailer (comm_consts.py); without it: the reference's bytes exactly
         obs = np.asarray(env.reset(), dtype=np.float32)
-        shape = [float(d) for d in obs.shape]
-        n_agents = int(shape[0]) if len(shape) > 1 else 1
-        pipe.sendto(C.pack_message(C.ENV_RESET_STATE_HEADER + [float(len(shape))] + shape) + obs.tobytes(), endpoint)
+        n_agents = int(obs.shape[0]) if obs.ndim > 1 else 1
+        pipe.sendto(reset_state_message(obs, env_action_masks(env, n_agents) if masked else None), endpoint)
 
         slab = StepSlab(shm_buffer, shm_offset, shm_size)
         step_header = C.pack_message(C.ENV_STEP_DATA_HEADER)
@@ -113,7 +133,8 @@ def batched_agent_process(proc_id, endpoint, shm_buffer, shm_offset, shm_size, s
                     metrics_shape = metrics.shape
                 else:
                     metrics, metrics_shape = np.empty((0,), np.float32), ()
-                slab.write_step(prev_n_agents, 1.0 if done else 0.0, 1.0 if truncated else 0.0, rew, metrics, metrics_shape, obs)
+                slab.write_step(prev_n_agents, 1.0 if done else 0.0, 1.0 if truncated else 0.0, rew, metrics, metrics_shape, obs,
+                                env_action_masks(env, int(obs.shape[0]) if obs.ndim > 1 else 1) if masked else None)
                 pipe.sendto(step_header, endpoint)
                 if render:
                     env.render()
@@ -124,7 +145,8 @@ def batched_agent_process(proc_id, endpoint, shm_buffer, shm_offset, shm_size, s
                         last_render = time.time()
             elif kind == C.ENV_SHAPES_HEADER[0]:
                 n_acts, code = describe_action_space(env.action_space)
-                pipe.sendto(C.pack_message(C.ENV_SHAPES_HEADER + [float(np.prod(env.observation_space.shape)), n_acts, code]), endpoint)
+                pipe.sendto(C.pack_message(C.ENV_SHAPES_HEADER + [float(np.prod(env.observation_space.shape)), n_acts, code]
+                                           + ([1.0] if masked else [])), endpoint)
             elif kind == C.STOP_MESSAGE_HEADER[0]:
                 break
     except (EOFError, KeyboardInterrupt):

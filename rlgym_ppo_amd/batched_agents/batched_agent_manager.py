@@ -22,16 +22,17 @@ import torch
 from .. import _native as N
 from ..util import WelfordRunningStat
 from . import comm_consts as C
-from .batched_agent import _as_f32, batched_agent_process, describe_action_space
+from .batched_agent import _as_f32, batched_agent_process, describe_action_space, env_action_masks
 from .batched_trajectory import BatchedTrajectory
 
 # messages as the manager's logic sees them, whatever carried them
 RESET_STATE, STEP_DATA, ENV_SHAPES = "env_reset_state", "env_step_data", "env_shapes"
 
 
-def parse_step_slab(shm_view):
+def parse_step_slab(shm_view, n_actions=0):
     """One step out of a worker's slab (layout: comm_consts.py; reference batched_agent_manager.py:254-299) ->
-    (prev_n_agents, done, truncated, rewards list, metrics array, observation [n_agents, d] float32 copy)."""
+    (prev_n_agents, done, truncated, rewards list, metrics array, observation [n_agents, d] float32 copy); with n_actions > 0 (a
+    worker that sends the mask trailer) a seventh value, the observation's masks as bool [n_agents, n_actions]."""
     # (a handful of bulk .tolist() reads instead of ~20 scalar indexings and two np.prod calls: this runs once per worker and step)
     h = shm_view[:5].tolist()
     prev_n, done, truncated, state_rank, metrics_rank = int(h[0]), h[1], h[2], int(h[3]), int(h[4])
@@ -55,7 +56,28 @@ def parse_step_slab(shm_view):
     for d in state_shape:
         n_obs *= d
     obs = shm_view[o:o + n_obs].copy().reshape(state_shape)
+    if n_actions:
+        o += n_obs
+        return prev_n, done, truncated, rews, metrics, obs, shm_view[o:o + state_shape[0] * n_actions].reshape(state_shape[0], n_actions) != 0
     return prev_n, done, truncated, rews, metrics, obs
+
+
+def parse_reset_state(floats):
+    """The floats of an ENV_RESET_STATE_HEADER datagram -> (observation [n_agents, d], masks bool [n_agents, n_actions] or None:
+    whatever follows the observation is the mask trailer of a masked worker)."""
+    rank = int(floats[C.HEADER_LEN])
+    o = C.HEADER_LEN + 1 + rank
+    shape = [int(d) for d in floats[C.HEADER_LEN + 1:o]]
+    if rank == 1:
+        shape = [1, shape[0]]
+    n_obs = int(np.prod(shape))
+    obs = np.array(floats[o:o + n_obs], dtype=np.float32).reshape(shape)
+    rest = floats[o + n_obs:]
+    if rest.size == 0:
+        return obs, None
+    if rest.size % shape[0]:
+        raise ValueError(f"reset state: {rest.size} floats behind an observation of {shape[0]} agents are no mask trailer")
+    return obs, rest.reshape(shape[0], -1) != 0
 
 
 class _ProcessWorker:
@@ -70,6 +92,7 @@ class _ProcessWorker:
         self.proc.start()
         self.shm_view = np.frombuffer(shm_buffer, dtype=np.float32, offset=offset, count=shm_size)
         self.child = None
+        self.n_actions = 0   # > 0: the worker sends the mask trailer for that many actions (learnt from its shapes reply)
         self._actions_header = C.pack_message(C.POLICY_ACTIONS_HEADER)
 
     def handshake(self, build_env_fn, metrics_fn):
@@ -89,16 +112,13 @@ class _ProcessWorker:
         if header is None:
             return None
         if header[0] == C.ENV_STEP_DATA_HEADER[0]:
-            return (STEP_DATA,) + parse_step_slab(self.shm_view)
+            return (STEP_DATA,) + parse_step_slab(self.shm_view, self.n_actions)
         floats = np.frombuffer(data, dtype=np.float32)
         if header == C.ENV_RESET_STATE_HEADER:
-            rank = int(floats[C.HEADER_LEN])
-            shape = [int(d) for d in floats[C.HEADER_LEN + 1:C.HEADER_LEN + 1 + rank]]
-            if rank == 1:
-                shape = [1, shape[0]]
-            return (RESET_STATE, np.array(floats[C.HEADER_LEN + 1 + rank:], dtype=np.float32).reshape(shape))
-        if header == C.ENV_SHAPES_HEADER:
-            return (ENV_SHAPES,) + tuple(float(x) for x in floats[C.HEADER_LEN:C.HEADER_LEN + 3])
+            obs, mask = parse_reset_state(floats)
+            return (RESET_STATE, obs) if mask is None else (RESET_STATE, obs, mask)
+        if header == C.ENV_SHAPES_HEADER:   # three floats, or four from a worker that sends the mask trailer
+            return (ENV_SHAPES,) + tuple(float(x) for x in floats[C.HEADER_LEN:C.HEADER_LEN + 4])
         return None
 
     def fileno(self):
@@ -122,8 +142,13 @@ class _LocalWorker:
         self.metrics_fn = metrics_fn
         if hasattr(self.env.action_space, "seed"):
             self.env.action_space.seed(seed)
+        self.masked = hasattr(self.env, "action_masks")
         self.obs = _as_f32(self.env.reset())
-        self.inbox = [(RESET_STATE, self.obs)]
+        self.inbox = [(RESET_STATE, self.obs) + self._mask()]
+
+    def _mask(self):
+        """() without action_masks() on the environment, else (the masks of self.obs as bool [n_agents, n_actions],)."""
+        return (env_action_masks(self.env, self.obs.shape[0]) != 0,) if self.masked else ()
 
     def send_actions(self, actions):
         prev_n = self.obs.shape[0]
@@ -134,11 +159,11 @@ class _LocalWorker:
             nxt = self.env.reset()
         self.obs = _as_f32(nxt)
         metrics = self.metrics_fn(info["state"]) if self.metrics_fn is not None else np.empty((0,), np.float32)
-        self.inbox.append((STEP_DATA, prev_n, 1.0 if done else 0.0, 1.0 if truncated else 0.0, rew, metrics, self.obs))
+        self.inbox.append((STEP_DATA, prev_n, 1.0 if done else 0.0, 1.0 if truncated else 0.0, rew, metrics, self.obs) + self._mask())
 
     def request_shapes(self):
         n_acts, code = describe_action_space(self.env.action_space)
-        self.inbox.append((ENV_SHAPES, float(np.prod(self.env.observation_space.shape)), n_acts, code))
+        self.inbox.append((ENV_SHAPES, float(np.prod(self.env.observation_space.shape)), n_acts, code) + ((1.0,) if self.masked else ()))
 
     def recv(self):
         return self.inbox.pop(0)
@@ -157,6 +182,12 @@ class BatchedAgentManager(object):
         self.seed = seed
         self.processes = []
         self.next_obs, self.current_obs, self.current_pids = [], [], []
+        # invalid-action masking (workers whose environment has action_masks(): the mask trailer of comm_consts.py): the mask of
+        # every observation travels with it; action_mask_rows: the masks of the last collect's steps, bool [N, n_actions], row for
+        # row with its states (what Learner.add_new_experience hands to the buffer) -- None in an unmasked run
+        self.masked, self.n_actions = False, 0
+        self.next_mask, self.current_mask = [], []
+        self.action_mask_rows = None
         self._average_reward = None
         # [r6] the per-message half of the collection loop in C++ (csrc/collector.cpp, rlppo_collector_*): used for worker PROCESSES
         # whose observation statistics are float32 (always, unless they were restored from JSON); False keeps the Python loop below,
@@ -203,6 +234,8 @@ class BatchedAgentManager(object):
         self.trajectory_map = [BatchedTrajectory() for _ in range(n)]
         self.current_obs = [None] * n
         self.next_obs = [None] * n
+        self.current_mask, self.next_mask = [None] * n, [None] * n
+        self.masked, self.n_actions, self.action_mask_rows = False, 0, None
         self.selector = selectors.DefaultSelector()
         if n_processes <= 0:
             self.processes = [_LocalWorker(build_env_fn, collect_metrics_fn, self.seed)]
@@ -231,6 +264,7 @@ class BatchedAgentManager(object):
             while msg is None or msg[0] != RESET_STATE:
                 msg = w.recv()
             obs = msg[1]
+            self.current_mask[pid] = msg[2] if len(msg) > 2 else None
             if self.standardize_obs:
                 if self.obs_stats is None:
                     self.obs_stats = WelfordRunningStat(shape=obs.shape[-1])
@@ -244,7 +278,41 @@ class BatchedAgentManager(object):
         while True:
             msg = w.recv()
             if msg is not None and msg[0] == ENV_SHAPES:
-                return int(msg[1]), int(msg[2]), int(msg[3])
+                break
+        self._configure_masking(msg)
+        return int(msg[1]), int(msg[2]), int(msg[3])
+
+    def _configure_masking(self, msg):
+        """Decides from a worker's shapes reply (a fourth float, 1.0 = it sends the mask trailer) and from what the initial reset
+        states carried whether the run is masked; a masked run needs the discrete head and masks as wide as the action space.
+        (Every worker runs the same environment: the first one's reply speaks for all, the reset states of all are checked.)"""
+        n_acts, code = int(msg[2]), int(msg[3])
+        with_mask = [m is not None for m in self.current_mask]
+        self.masked = len(msg) > 4 and msg[4] == 1.0
+        if self.masked != all(with_mask) or self.masked != any(with_mask):
+            raise ValueError("the workers disagree about the action-mask trailer: the shapes reply says "
+                             + ("masked" if self.masked else "unmasked") + f", {sum(with_mask)} of {len(with_mask)} reset states carry a mask")
+        if self.masked:
+            from ..ppo._mlp import ArenaModule
+            from ..ppo.discrete_policy import DiscreteFF
+            other = "an action space of type %d" % code if code != 0 else \
+                type(self.policy).__name__ if isinstance(self.policy, ArenaModule) and not isinstance(self.policy, DiscreteFF) else None
+            if other is not None:   # (the policy is usually built from what this call returns: the action space decides)
+                raise ValueError("the environment offers action_masks(): invalid-action masking is an option of the discrete head "
+                                 f"(DiscreteFF), not of {other}")
+            if any(m.shape[1] != n_acts for m in self.current_mask):
+                raise ValueError(f"the reset states carry masks of {self.current_mask[0].shape[1]} actions, the action space has {n_acts}")
+            self.n_actions = n_acts
+            for w in self.processes:
+                w.n_actions = n_acts
+
+    def _checked_masks(self, ready):
+        """The stacked mask rows of the ready workers; a row without a valid action raises before anything is sent."""
+        for pid in ready:
+            empty = np.flatnonzero(~self.current_mask[pid].any(axis=1))
+            if empty.size:
+                raise ValueError(f"action mask: worker {pid}, agent {int(empty[0])} has no valid action")
+        return np.concatenate([self.current_mask[pid] for pid in ready], axis=0)
 
     # ------------------------------------------------------------------------------------------- rollout
     @torch.no_grad()
@@ -254,7 +322,11 @@ class BatchedAgentManager(object):
             return
         obs = [self.current_obs[pid] for pid in ready]
         inference_batch = np.concatenate(obs, axis=0)                  # [n_ready_agents, d]
-        actions, log_probs = self.policy.get_action(inference_batch)   # one fused launch sequence for the whole batch
+        if self.masked:   # (the keyword only in a masked run: any policy with the reference's get_action serves an unmasked one)
+            masks = self._checked_masks(ready)
+            actions, log_probs = self.policy.get_action(inference_batch, action_mask=masks)
+        else:
+            actions, log_probs = self.policy.get_action(inference_batch)   # one fused launch sequence for the whole batch
         actions = actions.numpy().astype(np.float32)
         # (numpy rows from here on: a torch slice per environment and a 0-d tensor per agent and step cost the collector a fifth of
         # its wall clock -- np.asarray over 50,000 0-d tensors alone 0.26 s of 1.1 s, tools/profile_process_collect.py)
@@ -264,6 +336,8 @@ class BatchedAgentManager(object):
             stop = step + o.shape[0]
             traj = self.trajectory_map[pid]
             traj.state, traj.action, traj.log_prob = inference_batch[step:stop], actions[step:stop], log_probs[step:stop]
+            if self.masked:
+                traj.action_mask = masks[step:stop]
             self.processes[pid].send_actions(actions[step:stop])
             step = stop
         self.current_pids = []
@@ -293,7 +367,9 @@ class BatchedAgentManager(object):
         msg = worker.recv()
         if msg is None or msg[0] != STEP_DATA:
             return 0
-        _, prev_n, done, truncated, rews, metrics, nxt = msg
+        _, prev_n, done, truncated, rews, metrics, nxt = msg[:7]
+        if self.masked:
+            self.next_mask[pid] = msg[7]
         collected_metrics.append(metrics)
         if self.standardize_obs:
             if self.steps_since_obs_stats_update > self.steps_per_obs_stats_increment:
@@ -351,6 +427,8 @@ class BatchedAgentManager(object):
                 if self.next_obs[pid] is not None:
                     self.current_obs[pid] = self.next_obs[pid]
                     self.next_obs[pid] = None
+                    if self.masked:
+                        self.current_mask[pid], self.next_mask[pid] = self.next_mask[pid], None
             self._sync_trajectories()
         for pid, traj in enumerate(self.trajectory_map):
             self.completed_trajectories.append(traj)
@@ -358,14 +436,20 @@ class BatchedAgentManager(object):
             if traj.state is not None and traj.reward is None:
                 # an action is in flight for this worker: keep its (state, action, log_prob) so that the response,
                 # which arrives during the next collect_timesteps call, is paired with the step that produced it
-                fresh.state, fresh.action, fresh.log_prob = traj.state, traj.action, traj.log_prob
+                fresh.state, fresh.action, fresh.log_prob, fresh.action_mask = traj.state, traj.action, traj.log_prob, traj.action_mask
             self.trajectory_map[pid] = fresh
+        mask_rows = []
         for traj in self.completed_trajectories:
+            if self.masked:
+                for seq in traj.get_all_masks():
+                    mask_rows += seq
             for seq in traj.get_all():
                 seq[6][-1] = 1 if seq[5][-1] == 0 else 0
                 for c, s in zip(cols, seq):
                     c += s
         self.completed_trajectories = []
+        if self.masked:
+            self.action_mask_rows = np.asarray(mask_rows, dtype=bool).reshape(len(mask_rows), self.n_actions)
         self.cumulative_timesteps += n_collected
         return tuple(np.asarray(c) for c in cols), metrics, n_collected, time.perf_counter() - t1
 
@@ -403,6 +487,8 @@ class BatchedAgentManager(object):
         N.check(N.lib().rlppo_collector_create(n, fds, ports, ctypes.c_void_p(ctypes.addressof(self.shm_buffer)), self.shm_size, self._nat_d,
                                                ctypes.byref(h)))
         self._native = h
+        if self.masked:
+            N.check(N.lib().rlppo_collector_set_masked(h, self.n_actions))
         for pid, o in enumerate(self.current_obs):
             if o is not None and pid not in self.current_pids:
                 a = np.ascontiguousarray(o, dtype=np.float32)
@@ -410,8 +496,14 @@ class BatchedAgentManager(object):
         for pid in self.current_pids:   # (in the order the Python loop would serve them)
             a = np.ascontiguousarray(self.current_obs[pid], dtype=np.float32)
             N.check(N.lib().rlppo_collector_set_obs(h, pid, a.ctypes.data, a.shape[0], 1))
+        if self.masked:
+            for pid, m in enumerate(self.current_mask):
+                if m is not None and self.current_obs[pid] is not None:
+                    m8 = np.ascontiguousarray(m, dtype=np.uint8)
+                    N.check(N.lib().rlppo_collector_set_mask(h, pid, m8.ctypes.data, m8.shape[0]))
         self.average_reward = self._average_reward
         self._nat_obs = np.zeros((max(64, 8 * n), self._nat_d), dtype=np.float32)
+        self._nat_mask = np.zeros((self._nat_obs.shape[0], self.n_actions), dtype=np.uint8) if self.masked else None
         self._nat_act_shape = None
         return True
 
@@ -432,10 +524,19 @@ class BatchedAgentManager(object):
             rc = L.rlppo_collector_ready(h, self._nat_obs.ctypes.data, self._nat_obs.shape[0], ctypes.byref(rows))
             if rc == 1002:  # more waiting agents than the staging matrix holds: grow it
                 self._nat_obs = np.zeros((2 * self._nat_obs.shape[0], self._nat_d), dtype=np.float32)
+                if self.masked:
+                    self._nat_mask = np.zeros((self._nat_obs.shape[0], self.n_actions), dtype=np.uint8)
                 continue
             N.check(rc)
-            if rows.value:
+            if rows.value and self.masked:
+                rc = L.rlppo_collector_ready_masks(h, self._nat_mask.ctypes.data, self._nat_mask.shape[0])
+                if rc == 1005:   # a row without a valid action: nothing has been sent for this batch
+                    raise ValueError(L.rlppo_last_error().decode())
+                N.check(rc)
+                actions, log_probs = self.policy.get_action(self._nat_obs[:rows.value], action_mask=self._nat_mask[:rows.value])
+            elif rows.value:
                 actions, log_probs = self.policy.get_action(self._nat_obs[:rows.value])
+            if rows.value:
                 a = np.ascontiguousarray(actions.numpy() if isinstance(actions, torch.Tensor) else actions, dtype=np.float32)
                 lp = np.ascontiguousarray(log_probs.numpy() if isinstance(log_probs, torch.Tensor) else log_probs, dtype=np.float32)
                 self._nat_act_shape = a.shape[1:]
@@ -476,6 +577,10 @@ class BatchedAgentManager(object):
         actions, logp = np.empty((k, w), np.float32), np.empty(k, np.float32)
         rewards, dones, trunc = np.empty(k, np.float64), np.empty(k, np.float64), np.empty(k, np.float64)
         mvals, mshapes = np.empty(int(met_floats.value), np.float32), np.zeros((int(n_met.value), 9), np.int32)
+        if self.masked:   # (before _emit, which releases the trajectories)
+            m8 = np.empty((k, self.n_actions), np.uint8)
+            N.check(L.rlppo_collector_emit_masks(h, m8.ctypes.data))
+            self.action_mask_rows = m8.view(bool)
         N.check(L.rlppo_collector_emit(h, states.ctypes.data, actions.ctypes.data, logp.ctypes.data, rewards.ctypes.data, nxt.ctypes.data,
                                        dones.ctypes.data, trunc.ctypes.data, mvals.ctypes.data, mshapes.ctypes.data))
         metrics, o = [], 0

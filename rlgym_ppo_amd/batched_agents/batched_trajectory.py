@@ -12,7 +12,9 @@ class BatchedTrajectory(object):
     def __init__(self):
         for f in _FIELDS:
             setattr(self, f, None)
+        self.action_mask = None   # masked runs: the mask [n_agents, n_actions] `action` was sampled under (set with `state`)
         self.complete_timesteps = []
+        self.complete_masks = []  # ... of every banked timestep (None in an unmasked run)
 
     def update(self):
         """Bank the pending timestep if all seven fields are present; True when that timestep ended the episode."""
@@ -23,13 +25,21 @@ class BatchedTrajectory(object):
         if not isinstance(self.reward, (list, tuple, np.ndarray)):
             self.reward = [self.reward]
         self.complete_timesteps.append((self.state, self.action, self.log_prob, self.reward, self.next_state, self.done, self.truncated))
+        self.complete_masks.append(self.action_mask)
         ended = bool(self.done)
         # `truncated` keeps its last value, like the reference
-        self.state = self.action = self.log_prob = self.reward = self.next_state = self.done = None
+        self.state = self.action = self.log_prob = self.reward = self.next_state = self.done = self.action_mask = None
         return ended
 
+    def get_all_masks(self):
+        """Masked runs, BEFORE get_all(): one list of mask rows per agent, row for row with get_all()'s states."""
+        steps, masks = self.complete_timesteps, self.complete_masks
+        if not steps:
+            return []
+        return [[m[i] for m in masks] for i in range(len(steps[0][3]))]
+
     def get_all(self):
-        steps, self.complete_timesteps = self.complete_timesteps, []
+        steps, self.complete_timesteps, self.complete_masks = self.complete_timesteps, [], []
         if not steps:
             return []
         n_agents = len(steps[0][3])

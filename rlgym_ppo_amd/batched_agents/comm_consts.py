@@ -16,6 +16,17 @@ process built for the reference and this manager (or the other way round) intero
   shared slab of worker i = float32[shm_size] at offset i * shm_size (RawArray('f'), batched_agent_manager.py:436-440):
     [prev_n_agents, done, truncated, rank(state), rank(metrics), *metrics_shape, *state_shape, *rewards[prev_n_agents],
      *metrics.ravel(), *obs.ravel()]                               (batched_agent.py:154-164)
+
+Opt-in mask trailer (not in the reference; invalid-action masking of the discrete head).  A worker whose environment has
+`action_masks()` -- and only such a worker: every other worker writes the bytes above exactly -- asks it after `reset()` and after
+every step (once a possible reset is done) for the masks of the observation it is about to report, [n_agents, n_actions] (or
+[n_actions] for a one-agent environment), and appends them as n_agents * n_actions float32 of 0.0 / 1.0 (1 = valid):
+    ENV_RESET_STATE_HEADER + [rank, *shape] + obs.tobytes() + mask.tobytes()
+    slab: [..., *obs.ravel(), *mask.ravel()]
+    ENV_SHAPES_HEADER + [obs_size, n_actions, action_space_type, 1.0]   a fourth float: "this worker sends the trailer"
+The reset datagram with its trailer must fit PACKET_MAX_SIZE bytes, the most the learner reads of a datagram (the worker asserts
+it; the slab has its own size assertion).  The manager learns from the fourth float -- and from the length of the initial reset datagrams -- that the run is masked; a reply
+of three floats (a worker built for the reference) means unmasked.
 """
 import struct
 
@@ -49,6 +60,7 @@ def header_of(message_bytes):
     return np.frombuffer(message_bytes, dtype=np.float32, count=HEADER_LEN).tolist()
 
 
-def step_slab_floats(prev_n_agents, n_agents, obs_dim, n_metrics=0, metrics_rank=0):
-    """Number of float32 values one step occupies in a worker's slab: what `shm_buffer_size // 4` has to cover."""
-    return 5 + metrics_rank + 2 + prev_n_agents + n_metrics + n_agents * obs_dim
+def step_slab_floats(prev_n_agents, n_agents, obs_dim, n_metrics=0, metrics_rank=0, n_actions=0):
+    """Number of float32 values one step occupies in a worker's slab: what `shm_buffer_size // 4` has to cover (n_actions: the
+    action count of a worker that sends the mask trailer, else 0)."""
+    return 5 + metrics_rank + 2 + prev_n_agents + n_metrics + n_agents * (obs_dim + n_actions)

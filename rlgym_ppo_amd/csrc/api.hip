@@ -467,7 +467,6 @@ int rlppo_discrete_step_one_launch(const int32_t *dims, int32_t n_layers, int64_
     if (make_layout(dims, n_layers, &net)) return -1;
     ActCtx cx;
     if (act_ctx(opts, &cx, true)) return -1;
-    if (cx.mask && cx.noise_ctl) return 0;  // [ABI 8] a masked call has no late-noise form: the general path
     return g_fused_act && !cx.bf16 && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
 }
 
@@ -489,7 +488,6 @@ int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, con
     RLPPO_CHECK_ARG(!rows_out || ld_rows_out >= pin, "discrete_step: ld_rows_out=%ld < padded width %d", (long)ld_rows_out, pin);
     rc = act_mask_check(cx, dims[n_layers]);
     if (rc) return rc;
-    RLPPO_CHECK_ARG(!(cx.mask && cx.noise_ctl), "discrete_step: action_mask and noise_ctl exclude each other (a masked call takes its noise before the launch)");
     hipStream_t st = (hipStream_t)stream;
     if (g_fused_act && !cx.bf16 && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
         FusedActIO io;

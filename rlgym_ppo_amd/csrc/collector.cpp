@@ -6,6 +6,8 @@
 // observable results, value for value (tests/test_wire_format.py, tests/test_native_collector.py).  The policy call stays in Python:
 // per inference the host makes three calls here (ready -> [get_action] -> send -> collect) instead of ~20 interpreter-level
 // operations per worker message.  50,000 timesteps of 8 two-agent workers: 27,000 messages, 0.32 s of the collection's 0.70 s.
+// Masked runs (rlppo_collector_set_masked: the workers append an action-mask trailer to every observation, comm_consts.py): the mask
+// of an observation travels with it -- current / next / pending timestep / banked step -- as one byte (0 / 1) per action.
 #ifndef _GNU_SOURCE
 #define _GNU_SOURCE 1
 #endif
@@ -39,6 +41,7 @@ constexpr int PACKET_MAX = 8192;                                        // comm_
 struct Step {  // one banked timestep of one environment (BatchedTrajectory.complete_timesteps entry)
     int n_state = 0, n_next = 0;
     std::vector<float> state, action, logp, next;
+    std::vector<uint8_t> mask;  // masked runs: [n_state][n_actions] bytes, the masks the actions were sampled under
     std::vector<double> rew;
     double done = 0, trunc = 0;
 };
@@ -48,6 +51,7 @@ struct Worker {
     const float *slab = nullptr;
     int cur_n = -1, next_n = -1;  // rows of current_obs / next_obs; -1 = None
     std::vector<float> cur_obs, next_obs;
+    std::vector<uint8_t> cur_mask, next_mask, p_mask;  // masked runs: the masks of cur_obs / next_obs / the pending timestep's state
     // the pending timestep's fields (BatchedTrajectory.state ... .truncated); has_* = "is not None"
     bool has_state = false, has_reward = false, has_next = false, has_done = false;
     int p_n = 0, p_next_n = 0;
@@ -63,6 +67,7 @@ struct Metrics {
 };
 struct Collector {
     int n = 0, d = 0, act_width = 0;
+    int n_actions = 0;  // > 0: a masked run, every observation in a slab is followed by rows x n_actions floats of 0 / 1
     int64_t slab_floats = 0;
     std::vector<Worker> w;
     std::vector<int> current_pids, ready_pids;
@@ -82,6 +87,7 @@ bool traj_update(Worker &w) {
     s.action.swap(w.p_action);
     s.logp.swap(w.p_logp);
     s.next.swap(w.p_next);
+    s.mask.swap(w.p_mask);
     s.rew.swap(w.p_rew);
     s.done = w.p_done;
     s.trunc = w.p_trunc;
@@ -189,6 +195,7 @@ int rlppo_collector_send(void *handle, const float *actions, int32_t act_width, 
         Worker &w = c->w[c->ready_pids[k]];
         const int n = w.cur_n;
         w.p_state = w.cur_obs;  // (the inference batch's rows ARE the current observations)
+        if (c->n_actions) w.p_mask = w.cur_mask;
         w.p_n = n;
         w.p_action.assign(actions + row * act_width, actions + (row + n) * act_width);
         w.p_logp.assign(log_probs + row, log_probs + row + n);
@@ -267,7 +274,7 @@ int rlppo_collector_collect(void *handle, int64_t min_obs, int32_t resume, int32
             o += metrics_rank;
             const int rows = state_rank == 1 ? 1 : (int)s[o], width = state_rank == 1 ? (int)s[o] : (int)s[o + 1];
             o += state_rank;
-            if (width != d || rows < 0 || n_metrics < 0 || o + prev_n + n_metrics + (int64_t)rows * d > c->slab_floats)
+            if (width != d || rows < 0 || n_metrics < 0 || o + prev_n + n_metrics + (int64_t)rows * (d + c->n_actions) > c->slab_floats)
                 COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_collect: worker %d's step does not fit (observation %d x %d against width %d, %ld metrics, %ld floats per slab)", pid, rows, width, d, (long)n_metrics, (long)c->slab_floats);
             std::vector<double> rews(s + o, s + o + prev_n);
             o += prev_n;
@@ -275,6 +282,11 @@ int rlppo_collector_collect(void *handle, int64_t min_obs, int32_t resume, int32
             o += n_metrics;
             c->metrics.push_back(std::move(m));
             std::vector<float> nxt(s + o, s + o + (size_t)rows * d);
+            if (c->n_actions) {  // the mask trailer: the masks of the observation just read
+                const float *mf = s + o + (size_t)rows * d;
+                w.next_mask.resize((size_t)rows * c->n_actions);
+                for (size_t i = 0; i < w.next_mask.size(); ++i) w.next_mask[i] = mf[i] != 0.f;
+            }
             if (standardize) {
                 if (*steps_since_increment > steps_per_increment) {
                     if (stats_f64) welford_rows<double>(nxt.data(), rows, d, static_cast<double *>(stats_mean), static_cast<double *>(stats_var), stats_count);
@@ -343,6 +355,7 @@ int rlppo_collector_collect(void *handle, int64_t min_obs, int32_t resume, int32
         Worker &w = c->w[pid];
         if (w.next_n >= 0) {
             w.cur_obs.swap(w.next_obs);
+            if (c->n_actions) w.cur_mask.swap(w.next_mask);
             w.cur_n = w.next_n;
             w.next_n = -1;
         }
@@ -426,6 +439,69 @@ int rlppo_collector_emit(void *handle, float *states, float *actions, float *log
         ++mi;
     }
     c->metrics.clear();
+    return 0;
+}
+
+// ---- masked runs.  set_masked: every worker sends the mask trailer for n_actions actions (before the first _collect).
+int rlppo_collector_set_masked(void *handle, int32_t n_actions) {
+    Collector *c = static_cast<Collector *>(handle);
+    if (!c || n_actions <= 0) COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_set_masked: bad argument (n_actions %d)", n_actions);
+    c->n_actions = n_actions;
+    return 0;
+}
+
+// the mask of current_obs[worker] (a reset state's, as the handshake received it): rows x n_actions bytes, 0 = invalid
+int rlppo_collector_set_mask(void *handle, int32_t worker, const uint8_t *mask, int32_t rows) {
+    Collector *c = static_cast<Collector *>(handle);
+    if (!c || !c->n_actions || worker < 0 || worker >= c->n || !mask || rows != c->w[worker].cur_n)
+        COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_set_mask: bad argument (worker %d, %d rows)", worker, rows);
+    Worker &w = c->w[worker];
+    w.cur_mask.resize((size_t)rows * c->n_actions);
+    for (size_t i = 0; i < w.cur_mask.size(); ++i) w.cur_mask[i] = mask[i] != 0;
+    return 0;
+}
+
+// the stacked mask rows of the batch the last _ready call handed out, row for row; a row without a valid action fails with
+// RLPPO_ERR_MASK_ROW naming worker and agent -- before _send has sent anything for this batch
+int rlppo_collector_ready_masks(void *handle, uint8_t *mask_out, int64_t cap_rows) {
+    Collector *c = static_cast<Collector *>(handle);
+    if (!c || !c->n_actions || !mask_out) COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_ready_masks: not a masked collector, or a null argument");
+    const int A = c->n_actions;
+    int64_t rows = 0;
+    for (int pid : c->ready_pids) {
+        const Worker &w = c->w[pid];
+        if ((int64_t)w.cur_mask.size() != (int64_t)w.cur_n * A)
+            COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_ready_masks: worker %d has %d observation rows and %ld mask bytes", pid, w.cur_n, (long)w.cur_mask.size());
+        if (rows + w.cur_n > cap_rows) COLLECTOR_FAIL(RLPPO_ERR_WORKSPACE, "collector_ready_masks: more than %ld waiting observations", (long)cap_rows);
+        for (int i = 0; i < w.cur_n; ++i) {
+            bool any = false;
+            for (int a = 0; a < A; ++a) any |= w.cur_mask[(size_t)i * A + a] != 0;
+            if (!any) COLLECTOR_FAIL(RLPPO_ERR_MASK_ROW, "action mask: worker %d, agent %d has no valid action", pid, i);
+        }
+        if (w.cur_n > 0) memcpy(mask_out + rows * A, w.cur_mask.data(), (size_t)w.cur_n * A);
+        rows += w.cur_n;
+    }
+    return 0;
+}
+
+// the masks of the steps _emit will lay out, row for row with its states: [n_steps][n_actions] bytes.  Between _finish and _emit
+// (which releases the trajectories).
+int rlppo_collector_emit_masks(void *handle, uint8_t *masks) {
+    Collector *c = static_cast<Collector *>(handle);
+    if (!c || !c->n_actions || !masks) COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_emit_masks: not a masked collector, or a null argument");
+    const int A = c->n_actions;
+    int64_t r = 0;
+    for (const auto &t : c->completed) {
+        if (t.empty()) continue;
+        const int agents = (int)t[0].rew.size();
+        for (int i = 0; i < agents; ++i)
+            for (const Step &s : t) {
+                if (i >= s.n_state || (int64_t)s.mask.size() != (int64_t)s.n_state * A)
+                    COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_emit_masks: a step of %d agents carries %ld mask bytes (agent %d, %d actions)", s.n_state, (long)s.mask.size(), i, A);
+                memcpy(masks + r * A, s.mask.data() + (size_t)i * A, (size_t)A);
+                ++r;
+            }
+    }
     return 0;
 }
 

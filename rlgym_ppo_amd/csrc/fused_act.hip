@@ -12,7 +12,9 @@
 //     in the K loop, one per layer for the activations;
 //   * the head's logits go to LDS and the waves sample 16 / NW rows each with the code of discrete_sample_kernel.
 // [ABI 8] MASKED instantiations: the sampling stage reads the (<= 4) mask words of its rows -- requested with the noise, before the
-// layers -- and treats invalid actions as the padded columns c >= A (heads.hip); no late-noise form (a.noise_ctl is NULL there).
+// layers -- and treats invalid actions as the padded columns c >= A (heads.hip).  With a.noise_ctl only the noise is late: the host
+// knows the mask before it launches and stages the words with the observations; both late-noise fetch sites are those of the
+// unmasked form, and rows at and beyond the live-row word (stale mask words of a replayed graph) store nothing.
 // Arithmetic is that of the chain, operation for operation (accumulators start from the bias, k in tiles of 16 through the same
 // v_mfma_f32_16x16x4_f32 sequence, relu as v_med3, the same softmax / division / arg-max order): logits, actions and
 // log-probabilities are BIT-identical to the layer-by-layer path (tests/test_gpu_kernels.py).
@@ -592,8 +594,8 @@ int launch_discrete_act_fused(hipStream_t st, const NetLayout &net, const float 
     a.noise_ctl = io.noise_ctl;
     a.mask = io.mask;
     a.mask_words = io.mask_words;
-    RLPPO_CHECK_ARG(!io.mask || (!io.noise_ctl && io.mask_words == (a.A + 31) / 32),
-                    "discrete act: action_mask needs mask_words=%d == ceil(n_actions=%d / 32) and no noise_ctl", io.mask_words, a.A);
+    RLPPO_CHECK_ARG(!io.mask || io.mask_words == (a.A + 31) / 32,
+                    "discrete act: action_mask needs mask_words=%d == ceil(n_actions=%d / 32)", io.mask_words, a.A);
     const int H = net.L[0].pout;
     dim3 grid((unsigned)cdiv(n, FA_ROWS));
     static PerDeviceOnce attr_set[6];

@@ -268,8 +268,9 @@ class Learner(object):
             self.return_stats.increment(head, n_to_increment)
 
         self.experience_buffer._d = d_logical  # logical width of the padded rows
-        # invalid-action masking (vector_env=True, an environment with action_masks()): the masks the actions were sampled under
-        masks = getattr(self.agent, "action_mask_rows", None) if on_device else None
+        # invalid-action masking (an environment with action_masks(), either collection mode): the masks the actions were sampled
+        # under -- packed device words from the vector manager, bool host rows [N, n_actions] from process-mode collection
+        masks = getattr(self.agent, "action_mask_rows", None)
         if masks is not None:
             self.experience_buffer.submit_experience(rows[:n], actions, log_probs, rews_d, next_states, dones_d, trunc_d,
                                                      value_targets, advantages, action_masks=masks)

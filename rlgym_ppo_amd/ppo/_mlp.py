@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from .. import _native as N
 from ..engine import NetArena, linears_of, ptr, require_gpu, selection_epoch, stream_ptr
+from ..util import action_mask as AM
 
 
 def build_body(input_shape, layer_sizes, n_out, final_activation=None):
@@ -47,12 +48,18 @@ class ActGraph:
     written straight into pinned host memory.  At the reference's rollout scale (8-80 observations per call,
     batched_agent_manager.py:202-204) a call is nothing but latency -- ~7 launches, three copies and two blocking read-backs,
     ~140-250 us; one replay + one synchronisation does the same work, with no copy node at all.  Same kernels, same
-    arguments: results are those of the eager path bit for bit.  Rows past the caller's n hold stale data and are ignored."""
+    arguments: results are those of the eager path bit for bit.  Rows past the caller's n hold stale data and are ignored.
+    masked (the discrete head's one-launch step only): the graph's call carries rlppo_act_opts.action_mask -- cap x mask_words
+    words in the window (or in pinned memory) that run() stages with the observations, before the flush and the launch; the noise
+    stays late."""
 
-    def __init__(self, pol, cap):
+    def __init__(self, pol, cap, masked=False):
         a = pol.arena
         dev, d = a.device, a.d_in
         self.cap = cap
+        self.masked = bool(masked)
+        self.mask_words = AM.mask_words(pol.n_actions) if masked else 0
+        self.mask_pin = None   # the words' home under RLPPO_ACT_PUSH=0 (or without a host window): made below, only then
         self.dev = dev
         self.obs_pin = torch.zeros(cap, d).pin_memory()
         self.q_pin = torch.ones(pol._noise_shape(cap)).pin_memory()
@@ -87,12 +94,14 @@ class ActGraph:
             # window is zeroed once and the host only ever writes the first d floats of a row: no pad launch)
             self.padded = raw is None
             obs_bytes, q_bytes = r256(cap * (a.ld_in if self.padded else d) * 4), r256(int(self.q_pin.numel()) * 4)
+            mask_bytes = r256(cap * self.mask_words * 4)   # (0 for an unmasked graph: its window is what it always was)
             win = ctypes.c_void_p()
             with torch.cuda.device(dev):   # (the window belongs to the device that is current when it is made)
-                rc_win = L.rlppo_host_window_alloc(256 + obs_bytes + q_bytes, ctypes.byref(win))
+                rc_win = L.rlppo_host_window_alloc(256 + obs_bytes + q_bytes + mask_bytes, ctypes.byref(win))
             if rc_win == 0:
                 self.window = win.value
                 self.ctl_arg, self.obs_arg, self.q_arg = win.value, win.value + 256, win.value + 256 + obs_bytes
+                self.mask_arg = win.value + 256 + obs_bytes + q_bytes
                 self._push, self._stage, self._stage_rows = L.rlppo_host_push, L.rlppo_host_stage_call, L.rlppo_host_stage_rows
                 # the device's host data path is flushed between the staged bytes and the launch (by the book: 0.9 us of the call;
                 # round 5's "flush behind the launch" ordered data by launch latency -- a timing argument, not a guarantee -- and is gone)
@@ -102,6 +111,19 @@ class ActGraph:
             else:
                 self.push = False   # (a device that does not expose its memory to the host)
         self.padded = self.push and raw is None
+        if masked:
+            if raw is None:
+                raise ValueError("ActGraph: a masked graph needs the one-launch step of the discrete head")
+            # what the warm-up launch, the capture and the rows beyond a call's n read: all-valid words -- in the window (whose
+            # allocation zero-fills it) written once here, in pinned memory from the start
+            valid = torch.full((cap, self.mask_words), -1, dtype=torch.int32)
+            if self.push:
+                N.check(self._push(self.mask_arg, valid.data_ptr(), 4 * valid.numel(), None, 0))
+                self._flush(self.window)
+            else:
+                self.mask_pin = valid.pin_memory()
+                self.mask_arg = self.mask_pin.data_ptr()
+            self.opts.action_mask, self.opts.mask_words = self.mask_arg, self.mask_words
         # [r5] late noise (rlppo_act_opts.noise_ctl): run() launches FIRST and draws the Exp(1) numbers afterwards -- the bit-exact
         # draw (5-11 us at 8-80 rows) then costs the call nothing, it hides behind the launch latency and the layers; the kernel
         # looks for control word 2 when its head layer starts.  Up to 256 rows: beyond that the draw outlasts the kernel.
@@ -135,6 +157,7 @@ class ActGraph:
         self.obs_np, self.q_np = self.obs_pin.numpy(), self.q_pin.view(-1).numpy()
         self.act_np, self.logp_np = self.act_pin.numpy(), self.logp_pin.numpy()
         self.done_np = self.done_pin.numpy()
+        self.mask_np = self.mask_pin.numpy() if self.mask_pin is not None else None
         self._done_ptr = ctypes.c_void_p(self.done_pin.data_ptr())
         self._wait = L.rlppo_host_wait_words
 
@@ -164,13 +187,27 @@ class ActGraph:
             N.check(N.lib().rlppo_pad_rows(stream_ptr(), ptr(self.obs_arg), 0, cap, a.d_in, a.d_in, ptr(self.rows), a.ld_in, 0, 0.0, 1.0))
         pol._act_launch(self.rows, cap, self.q_arg, self.act_pin, self.logp_pin, self.ws, self.opts)
 
-    def run(self, obs, q, n, draw=None, verify=None):
+    def run(self, obs, q, n, draw=None, verify=None, mask_words=None):
         """obs [n, d] float32 numpy; q: the call's noise (CPU tensor) or None with draw(): called for it -- AFTER the launch when
         the graph takes late noise.  verify (optional): () -> bool, asked after the launch whether what the launch read (the packed
-        weights) was current; on False redo() -- its second return value -- is run and the call made again."""
+        weights) was current; on False redo() -- its second return value -- is run and the call made again.  mask_words (a masked
+        graph: required): int32 numpy [n, mask_words], validated by the caller (util.action_mask.pack_host)."""
         # plain memcpy through numpy views made once: Tensor.copy_ fans out to an OpenMP team above 32k elements (10 ms on a
         # 256-thread host), and slicing tensors costs more than these copies at 8-80 rows
         m = n * self.q_per_row
+        if self.masked:
+            # the kernel reads the words at its start, with the observation requests: they are in place before the flush and the
+            # launch, like the observations (the host knows the mask before it launches; only the noise is late)
+            if mask_words is None or mask_words.shape != (n, self.mask_words) or mask_words.dtype != np.int32:
+                raise ValueError("action mask: expected int32 words [%d, %d]" % (n, self.mask_words))
+            if self.push:
+                if not mask_words.flags.c_contiguous:
+                    mask_words = np.ascontiguousarray(mask_words)
+                rc = self._push(self.mask_arg, mask_words.ctypes.data, mask_words.nbytes, None, 0)
+                if rc:
+                    N.check(rc)
+            else:
+                self.mask_np[:n] = mask_words
         if self.push:
             if not obs.flags.c_contiguous:
                 obs = np.ascontiguousarray(obs)
@@ -282,10 +319,14 @@ class ArenaModule(nn.Module):
         self._graphs = {}
         self._graph_epoch = -1
 
-    def _graph_act(self, obs, noise, standardize):
+    def _graph_act(self, obs, noise, standardize, action_mask=None):
         """get_action for a small HOST batch as one graph replay, or None when that form does not apply (device inputs, fused
-        standardisation, device-drawn noise, more than act_graph_max rows): the caller then takes the eager path."""
+        standardisation, device-drawn noise, more than act_graph_max rows): the caller then takes the eager path.
+        action_mask (the discrete head): a HOST mask [n, n_actions] is packed on the host -- no device work -- and staged with the
+        observations of a masked graph, cached beside the unmasked ones; a device mask or packed device words: the eager path."""
         if not self.act_graphs or standardize is not None or self.noise_mode != "host":
+            return None
+        if action_mask is not None and (isinstance(action_mask, AM.Packed) or (isinstance(action_mask, torch.Tensor) and action_mask.is_cuda)):
             return None
         if (isinstance(obs, torch.Tensor) and obs.is_cuda) or (isinstance(noise, torch.Tensor) and noise.is_cuda):
             return None
@@ -312,18 +353,25 @@ class ArenaModule(nn.Module):
         if epoch != self._graph_epoch:
             self._graphs.clear()
             self._graph_epoch = epoch
-        g = self._graphs.get(_bucket(n))
+        words = None
+        if action_mask is not None:
+            # (raises for a malformed mask or a row without a valid action -- here, before anything is staged or launched)
+            words = AM.pack_host(action_mask.numpy() if isinstance(action_mask, torch.Tensor) else action_mask, self.n_actions)
+            if words.shape[0] != n:
+                raise ValueError(f"action mask has {words.shape[0]} rows, the call {n}")
+        key = _bucket(n) if words is None else (_bucket(n), True)   # masked graphs beside the unmasked ones: (bucket, masked)
+        g = self._graphs.get(key)
         if g is None:
-            g = self._graphs[_bucket(n)] = ActGraph(self, _bucket(n))
+            g = self._graphs[key] = ActGraph(self, _bucket(n), masked=words is not None)
         if o.dtype != np.float32:
             o = o.astype(np.float32)
         if a._packed_key is not None:
             # launch on the packed copy as it is and check that it was current WHILE the GPU works (8 Parameters' versions and
             # addresses: 5 us of the call's critical path otherwise); a stale one -- rare: a stock optimiser stepped, the module
             # moved -- costs a second launch
-            return g.run(o, q, n, self._draw_bound(n), self._verify)
+            return g.run(o, q, n, self._draw_bound(n), self._verify, words)
         a.ensure_packed()
-        return g.run(o, q, n, self._draw_bound(n))
+        return g.run(o, q, n, self._draw_bound(n), None, words)
 
     def _draw_bound(self, n):
         return lambda: self._draw_noise(n)

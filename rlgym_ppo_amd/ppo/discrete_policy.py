@@ -63,11 +63,12 @@ class DiscreteFF(ArenaModule):
         `noise`: optional [n, n_actions] Exp(1) draws (default: torch.empty(n, A).exponential_(1) from the CPU
         generator, the reference's stream).  `standardize`: optional (mean0, std0) scalars fused into staging.
         `action_mask`: optional [n, n_actions], valid = 1 (invalid-action masking: only valid actions are sampled; the noise draw
-        and the generator's state are those of the unmasked call).  A masked call takes the general path."""
-        if not deterministic and action_mask is None:
+        and the generator's state are those of the unmasked call).  A host mask on a small host batch rides the same graph replay
+        as the unmasked call (its packed words are staged with the observations); a device mask takes the general path."""
+        if not deterministic:
             # small host batches: one hipGraph replay (ppo/_mlp.py).  (Nothing in there touches autograd: the no_grad scope -- 2 us
             # of a 45 us call -- is entered below, where torch operators run.)
-            out = self._graph_act(obs, noise, standardize)
+            out = self._graph_act(obs, noise, standardize, action_mask)
             if out is not None:
                 return out
         return self._get_action_general(obs, deterministic, noise, standardize, action_mask)
@@ -179,6 +180,7 @@ class DiscreteFF(ArenaModule):
         L = N.lib()
         if g is None:
             return int(L.rlppo_discrete_step_workspace_bytes(a.dims_c, a.n_layers, cap))
+        # (a masked graph's opts carry action_mask / mask_words: the words' region of its window, or of pinned memory)
         args = getattr(g, "_raw_args", None)
         if args is None or args[0] is not opts:  # every pointer of the call is fixed for the graph's lifetime: built once
             args = g._raw_args = (opts, (a.dims_c, a.n_layers, ptr(a.packed), g.obs_arg, 0, a.d_in, cap, 0, 0.0, 1.0, None, None, g.q_arg,
