@@ -37,6 +37,12 @@ extern "C" {
 
 #define RLPPO_ABI_VERSION 8
 #define RLPPO_MAX_LAYERS 16
+/* [nvec] limits of a multi-discrete action space MultiDiscrete(nvec) (rlppo_multidiscrete_act_nvec, rlppo_ppo_minibatch_nvec):
+ * 1 <= heads <= RLPPO_MD_MAX_HEADS, 1 <= nvec[h] <= RLPPO_MD_MAX_BINS, sum of nvec <= RLPPO_MD_MAX_LOGITS.  Anything beyond is
+ * RLPPO_ERR_ARG with a message naming the limit, before any launch. */
+#define RLPPO_MD_MAX_HEADS 64
+#define RLPPO_MD_MAX_BINS 64
+#define RLPPO_MD_MAX_LOGITS 512
 
 #define RLPPO_OK 0
 #define RLPPO_ERR_ARG 1001        /* bad argument / unsupported shape */
@@ -229,6 +235,19 @@ int rlppo_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, cons
 int rlppo_multidiscrete_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed,
                             const float *obs, int64_t ld_obs, int64_t n, const float *noise_q,
                             int64_t *actions, float *logp, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts);
+/* [nvec] The same step for MultiDiscrete(nvec) of any nvec -- MultiDiscreteRolv's construction (torch_functions.py:81-122) with the
+ * bins as a parameter.  nvec: HOST, n_heads = H entries b_0 .. b_(H-1), read during the call (limits: RLPPO_MD_MAX_*);
+ * dims[n_layers] == S = sum b_h.  Head h owns logits [s_h, s_h + b_h), s_h = b_0 + .. + b_(h-1); with B = max b_h the distribution
+ * is Categorical(logits = [n, H, B]), every head padded with -inf to B.  noise_q[n * H][B] as Categorical.sample draws it
+ * (torch.empty(n * H, B).exponential_(1)); the action of head h is the first arg-max over c < b_h of
+ * softmax(z_h)_c / noise_q[(row * H + h) * B + c] -- padded slots are no candidates, their noise is not read; actions int64[n][H];
+ * logp[n] = sum_h log_softmax(z_h)[a_h].  A head of one bin: action 0, log-probability 0.  opts as rlppo_multidiscrete_act (bf16
+ * inference and completion words work; an action mask is refused).  It always runs the general sampling kernel, also for the
+ * reference's nvec {3, 3, 3, 3, 3, 2, 2, 2}, where rlppo_multidiscrete_act keeps its fixed kernel. */
+int rlppo_multidiscrete_act_nvec(void *stream, const int32_t *dims, int32_t n_layers, const float *packed,
+                                 const float *obs, int64_t ld_obs, int64_t n, const float *noise_q,
+                                 int64_t *actions, float *logp, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts,
+                                 const int32_t *nvec, int32_t n_heads);
 
 /* ---------------------------------------------------------------------------------------------- GAE */
 
@@ -355,6 +374,17 @@ typedef struct rlppo_minibatch_args {
  * get_backprop_data, clipped surrogate + entropy + value losses, both backward passes; gradients are ADDED into
  * pol_grad / val_grad (the reference accumulates over the minibatches of a batch, ppo_learner.py:179-180). */
 int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *args);
+/* [nvec] The same pass with the multi-discrete head for MultiDiscrete(nvec) of any nvec (an added entry point: the struct and the ABI
+ * version stay as they are).  md_nvec: HOST, md_heads = H entries, read during the call (limits: RLPPO_MD_MAX_*).  md_nvec == NULL is
+ * exactly rlppo_ppo_minibatch (the reference's head: 21 outputs, act_dim 8, the fixed kernel; md_heads ignored).  Not NULL with
+ * RLPPO_HEAD_MULTIDISCRETE: the policy must have sum(md_nvec) outputs and args->act_dim == md_heads, and the loss runs the general
+ * kernel -- also when md_nvec holds the reference's bins.  Not NULL with another head: RLPPO_ERR_ARG.  `actions` holds H float-encoded
+ * indices per row; log p = sum_h log_softmax(z_h)[a_h], entropy = sum_h H(z_h) averaged over the rows (no division by H),
+ * dL/dz per head segment as the reference's head forms it, exactly 0 in the padded columns >= sum(md_nvec).  A head of one bin
+ * contributes log-probability 0, entropy 0 and a zero gradient.  A stored index outside [0, md_nvec[h]) is a caller error: it is
+ * clamped into the head's range before it indexes anything (the row trains on the nearest valid action; no address outside the row
+ * is formed).  The workspace of a pass does not depend on md_nvec. */
+int rlppo_ppo_minibatch_nvec(void *stream, const rlppo_minibatch_args *args, const int32_t *md_nvec, int32_t md_heads);
 
 /* Orders `stream` after every minibatch enqueued through non-zero slots since the last join (call it before the
  * gradient all-reduce / rlppo_clip_adam).  Independent minibatches of one batch only meet in the gradient arena
@@ -693,7 +723,8 @@ const int64_t *rlppo_selection_epoch_ptr(void);   /* the counter itself (a host 
 /* Which form calls took so far in this process (tests assert that the kernel they mean to pin is the one that ran): 0 = rollout steps
  * served by the one-launch kernel (rlppo_discrete_act / rlppo_discrete_step), 1 = by the layer chain, 2 = rlppo_ppo_minibatch passes,
  * 3 = of them with paired policy + critic launches, 4 = of them with the gather fused into the first layer, 5 = of them with the
- * grouped weight-gradient launch; -1 for an unknown key. */
+ * grouped weight-gradient launch, 6 = [nvec] launches of the multi-discrete head's general (any nvec) kernels, sampling and loss;
+ * -1 for an unknown key. */
 int64_t rlppo_dbg_counter(int32_t key);
 /* Single-kernel entry points used by tests/ and bench.py to check / time each GEMM flavour in isolation.
  * epilogue: 0 bias, 1 bias+relu, 2 bias+tanh, 3 relu-mask (mask_src > 0).  Shapes as in csrc/gemm.hip. */

@@ -12,6 +12,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_siz
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RLPPO_LIB") or os.path.join(HERE, "librlppo.so")  # RLPPO_LIB: an alternative build (A/B of compile-time variants)
 ABI_VERSION = 8
+MD_MAX_HEADS, MD_MAX_BINS, MD_MAX_LOGITS = 64, 64, 512  # RLPPO_MD_MAX_*
 COMM_ID_BYTES = 128  # RLPPO_COMM_ID_BYTES
 MAX_LAYERS = 16
 N_STATS = 8
@@ -122,6 +123,8 @@ SIGNATURES = {
                                      c_float, c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
     "rlppo_multidiscrete_act": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
+    "rlppo_multidiscrete_act_nvec": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_size_t, _PACT, _P32, c_int32]),
     "rlppo_act_done_words": (c_int64, [c_int64]),
     "rlppo_host_wait_words": (c_int32, [c_void_p, c_int64, c_uint32, c_int64]),
     "rlppo_discrete_step_one_launch": (c_int32, [_P32, c_int32, c_int64, _PACT]),
@@ -140,6 +143,7 @@ SIGNATURES = {
     "rlppo_minibatch_workspace_bytes": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64]),
     "rlppo_minibatch_workspace_bytes_for": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
     "rlppo_ppo_minibatch": (c_int32, [c_void_p, POINTER(MinibatchArgs)]),
+    "rlppo_ppo_minibatch_nvec": (c_int32, [c_void_p, POINTER(MinibatchArgs), _P32, c_int32]),
     "rlppo_ppo_join": (c_int32, [c_void_p]),
     "rlppo_kl_slots_doubles": (c_int64, [c_int64]),
     "rlppo_adv_stats": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),

@@ -274,7 +274,7 @@ using namespace rlppo;
 
 static int g_fused_act = 1;  // rlppo_dbg_set(27, 0/1): rlppo_discrete_act as one fused launch (fused_act.hip)
 // rlppo_dbg_counter: which form a call took (tests assert that the kernel they mean to pin is the one that ran)
-static std::atomic<long long> g_cnt_fused_act{0}, g_cnt_act_chain{0}, g_cnt_paired_pass{0}, g_cnt_gather_fused_pass{0}, g_cnt_pass{0}, g_cnt_group_dw{0};
+static std::atomic<long long> g_cnt_fused_act{0}, g_cnt_act_chain{0}, g_cnt_paired_pass{0}, g_cnt_gather_fused_pass{0}, g_cnt_pass{0}, g_cnt_group_dw{0}, g_cnt_md_nvec{0};
 // One workgroup per 16 rows and one workgroup per CU (102 KiB of LDS): a launch is rounds of 4096 rows at ~25 us each, whatever
 // the round's fill.  Measured (tools/act_kernel_time.py): 64 rows 26 us (chain 70), 4096 rows 29 us (chain 75), 16,384 rows 100 us
 // (chain 86): beyond two rounds the layer-by-layer GEMMs, which fill the chip, win.
@@ -609,6 +609,30 @@ int rlppo_multidiscrete_act(void *stream, const int32_t *dims, int32_t n_layers,
     rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
     if (rc) return rc;
     return launch_multidiscrete_sample((hipStream_t)stream, o, ldo, n, noise_q, actions, logp, cx.done, cx.done_value);
+}
+
+// [nvec] the same step for any nvec: the general sampling kernel, always (the fixed one stays behind rlppo_multidiscrete_act)
+int rlppo_multidiscrete_act_nvec(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
+                                 int64_t ld_obs, int64_t n, const float *noise_q, int64_t *actions, float *logp, void *workspace,
+                                 size_t ws_bytes, const rlppo_act_opts *opts, const int32_t *nvec, int32_t n_heads) {
+    NetLayout net;
+    int rc = make_layout(dims, n_layers, &net);
+    if (rc) return rc;
+    ActCtx cx;
+    rc = act_ctx(opts, &cx, false, "the multi-discrete head (rlppo_multidiscrete_act_nvec)");
+    if (rc) return rc;
+    MdSpec spec;
+    rc = md_spec_make(nvec, n_heads, "multidiscrete_act_nvec", &spec);
+    if (rc) return rc;
+    RLPPO_CHECK_ARG(dims[n_layers] == spec.S, "multidiscrete_act_nvec: output width %d, but nvec sums to %d", dims[n_layers], spec.S);
+    if (n == 0) return 0;
+    RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_q && actions && logp && workspace, "multidiscrete_act_nvec: bad argument");
+    const float *o;
+    int64_t ldo;
+    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
+    if (rc) return rc;
+    ++g_cnt_md_nvec;
+    return launch_multidiscrete_nvec_sample((hipStream_t)stream, o, ldo, n, noise_q, actions, logp, spec, cx.done, cx.done_value);
 }
 
 int64_t rlppo_act_done_words(int64_t n) { return n > 0 ? cdiv(n, 16) : 0; }
@@ -1061,6 +1085,8 @@ struct Pass {
     WsPlan w;
     RowSource rows;  // the first layers' operand
     LossCfg cfg;
+    MdSpec md;                   // [nvec] the multi-discrete head's bins when rlppo_ppo_minibatch_nvec gives them
+    bool md_general = false;
     const float *pol_w, *val_w;  // the packed weights the products read (bf16 precision: their rounded images)
     hipStream_t st, side;        // the policy's and the critic's chain (one stream: rlppo_dbg_set(4, 0))
     DwList *defer;               // [r5] the grouped weight gradients, or null
@@ -1100,6 +1126,10 @@ static int policy_loss(hipStream_t st, const Pass &p) {
     }
     if (a.head == RLPPO_HEAD_GAUSSIAN)
         return launch_gaussian_loss(st, w.pol.act[last], L.pout, L.out / 2, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
+    if (p.md_general) {  // [nvec] any nvec: the general kernel, also on the reference's bins
+        ++g_cnt_md_nvec;
+        return launch_multidiscrete_nvec_loss(st, w.pol.act[last], L.pout, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, p.md);
+    }
     return launch_multidiscrete_loss(st, w.pol.act[last], L.pout, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
 }
 
@@ -1290,7 +1320,8 @@ static int two_chain_pass(const Pass &p) {
     return backward(p.st, pol, p.pol_w, p.rows, mb, w.pol.act, w.pol.dx, a.pol_grad, w.pol.tn, w.pol.bits, phave, false, pol_x3, p.defer);
 }
 
-int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
+// one pass; md_nvec (host, or null = the reference's multi-discrete head) is rlppo_ppo_minibatch_nvec's
+static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads) {
     // ---- validation: every argument error is reported here, before the first HIP call
     RLPPO_CHECK_ARG(a != nullptr, "ppo_minibatch: null args");
     Pass p;
@@ -1334,7 +1365,16 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
     }
     if (a->head == RLPPO_HEAD_GAUSSIAN)
         RLPPO_CHECK_ARG(n_out % 2 == 0 && a->act_dim == n_out / 2, "gaussian head: act_dim=%d, outputs=%d", a->act_dim, n_out);
-    if (a->head == RLPPO_HEAD_MULTIDISCRETE)
+    // [nvec] md_nvec: the multi-discrete head alone; NULL = the reference's 21 outputs / 8 heads and the fixed kernel
+    RLPPO_CHECK_ARG(!md_nvec || a->head == RLPPO_HEAD_MULTIDISCRETE, "ppo_minibatch: md_nvec is an option of the multi-discrete head, not of the %s head",
+                    a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : "discrete");
+    if (a->head == RLPPO_HEAD_MULTIDISCRETE && md_nvec) {
+        rc = md_spec_make(md_nvec, md_heads, "multi-discrete head: md_nvec / md_heads", &p.md);
+        if (rc) return rc;
+        p.md_general = true;
+        RLPPO_CHECK_ARG(p.md.S == n_out, "multi-discrete head: md_nvec sums to %d, but the policy has %d outputs", p.md.S, n_out);
+        RLPPO_CHECK_ARG(a->act_dim == p.md.H, "multi-discrete head: act_dim=%d, but md_heads=%d", a->act_dim, p.md.H);
+    } else if (a->head == RLPPO_HEAD_MULTIDISCRETE)
         RLPPO_CHECK_ARG(n_out == 21 && a->act_dim == 8, "multi-discrete head: needs 21 outputs and act_dim 8");
     RLPPO_CHECK_ARG(p.prec != 1 || (a->pol_packed_r && a->val_packed_r && a->pol_wb16 && a->val_wb16),
                     "ppo_minibatch: the bf16 update precision needs the rlppo_net_pack_bf16 images of both networks (pol_packed_r / val_packed_r / pol_wb16 / val_wb16)");
@@ -1397,6 +1437,11 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) {
         rc = launch_gemm_tn_group(p.st, dws.p, dws.n, mb, p.w.pol.tn, p.w.tn_floats);
     }
     return rc;
+}
+
+int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) { return ppo_minibatch(stream, a, nullptr, 0); }
+int rlppo_ppo_minibatch_nvec(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads) {
+    return ppo_minibatch(stream, a, md_nvec, md_heads);
 }
 
 int rlppo_ppo_join(void *stream) {
@@ -1608,6 +1653,7 @@ int64_t rlppo_dbg_counter(int32_t key) {
         case 3: return g_cnt_paired_pass;
         case 4: return g_cnt_gather_fused_pass;
         case 5: return g_cnt_group_dw;
+        case 6: return g_cnt_md_nvec;
         default: return -1;
     }
 }

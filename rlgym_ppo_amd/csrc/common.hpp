@@ -241,6 +241,17 @@ int launch_discrete_loss(hipStream_t, float *, int64_t, int, const float *, cons
                          const MaskRows *mask_rows = nullptr);
 int launch_gaussian_loss(hipStream_t, float *, int64_t, int, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
 int launch_multidiscrete_loss(hipStream_t, float *, int64_t, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
+// [nvec] the multi-discrete head for any nvec: H heads of b[h] bins, S = sum b[h] logits, B = max b[h] (the noise's row width).
+// A kernel argument by value (76 bytes); md_spec_make validates a host nvec against the RLPPO_MD_MAX_* limits and fills it.
+struct MdSpec {
+    int H, B, S;
+    unsigned char b[RLPPO_MD_MAX_HEADS];
+};
+int md_spec_make(const int32_t *nvec, int n_heads, const char *who, MdSpec *spec);
+int launch_multidiscrete_nvec_sample(hipStream_t, const float *, int64_t, int64_t, const float *, int64_t *, float *, const MdSpec &,
+                                     unsigned *done_words = nullptr, unsigned done_value = 0);
+int launch_multidiscrete_nvec_loss(hipStream_t, float *, int64_t, const float *, const float *, const float *, int64_t, const LossCfg &, double *,
+                                   const MdSpec &);
 
 // fused_act.hip: the whole rollout step of the discrete policy in one launch ----------------
 struct FusedActIO {

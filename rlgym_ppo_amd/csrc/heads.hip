@@ -5,6 +5,8 @@
 // literal softmax -> clamp(1e-11, 1) -> log (discrete_policy.py:52-54,70-78), NOT log_softmax, including the
 // clamp's zero-gradient region and torch.min's tie rule.
 // Gaussian / multi-discrete heads have 16 / 21 outputs per row: one thread per row, everything in registers.
+// [nvec] The multi-discrete head for MultiDiscrete(nvec) of any nvec (up to 64 heads of up to 64 bins, 512 logits): a general
+// sampling and a general loss kernel next to the fixed two, one thread per row, no per-row array (at the end of this file).
 //
 // [ABI 8] Invalid-action masking (discrete head): every discrete kernel has a MASKED instantiation (template parameter; the unmasked
 // instantiations are the code they were).  A row's mask is W = ceil(A / 32) words, bit c % 32 of word c / 32 = action c valid.  An
@@ -858,6 +860,169 @@ int launch_multidiscrete_loss(hipStream_t st, float *logits, int64_t ld, const f
     if (mb <= 0) return 0;
     hipLaunchKernelGGL(multidiscrete_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, logits, ld, actions, old_logp,
                        adv, mb, cfg, stats);
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------ multi-discrete, any nvec [nvec]
+// MultiDiscreteRolv's construction with the bins as a parameter: head h owns logits [s_h, s_h + b_h), s_h = b_0 + .. + b_(h-1).  The
+// two kernels above stay as they are (their loops unroll completely, so their per-row arrays live in registers); with run-time bins
+// the same arrays would be run-time indexed and land in scratch, so these two keep NO per-row array: one thread per row walks the
+// heads, and whatever a later step needs again (a head's maximum, its sum, its entropy) is recomputed from the logits, which the
+// first walk has left in the cache.  The spec travels by value in the kernel arguments (a uniform index: scalar loads).
+int md_spec_make(const int32_t *nvec, int n_heads, const char *who, MdSpec *spec) {
+    RLPPO_CHECK_ARG(nvec != nullptr, "%s: nvec is NULL", who);
+    RLPPO_CHECK_ARG(n_heads >= 1 && n_heads <= RLPPO_MD_MAX_HEADS, "%s: %d heads, RLPPO_MD_MAX_HEADS allows 1 .. %d", who, n_heads,
+                    RLPPO_MD_MAX_HEADS);
+    MdSpec s = {};
+    s.H = n_heads;
+    for (int h = 0; h < n_heads; ++h) {
+        RLPPO_CHECK_ARG(nvec[h] >= 1 && nvec[h] <= RLPPO_MD_MAX_BINS, "%s: nvec[%d]=%d, RLPPO_MD_MAX_BINS allows 1 .. %d", who, h, nvec[h],
+                        RLPPO_MD_MAX_BINS);
+        s.b[h] = (unsigned char)nvec[h];
+        s.S += nvec[h];
+        s.B = nvec[h] > s.B ? nvec[h] : s.B;
+    }
+    RLPPO_CHECK_ARG(s.S <= RLPPO_MD_MAX_LOGITS, "%s: sum of nvec = %d logits, RLPPO_MD_MAX_LOGITS allows %d", who, s.S, RLPPO_MD_MAX_LOGITS);
+    *spec = s;
+    return 0;
+}
+
+// Categorical(logits=[n, H, B]).sample() == first arg-max over c < b_h of softmax(z_h)_c / q[(row H + h) B + c]: the padded slots
+// c >= b_h (p = 0 in the reference) are no candidates and their noise is never read.  The arithmetic of a head is that of
+// multidiscrete_sample_kernel (the exponentials are formed twice instead of being kept); the row's log-probability -- up to 64 float
+// terms -- is summed in double and rounded once, as the Gaussian head does above FLOAT_SUM_K terms (a serial float sum of 64 terms
+// near -44 alone drifts by ~1e-5).
+__global__ __launch_bounds__(256) void multidiscrete_nvec_sample_kernel(const float *__restrict__ logits, int64_t ld, int64_t n,
+                                                                         const float *__restrict__ noise, int64_t *__restrict__ actions,
+                                                                         float *__restrict__ logp, MdSpec spec, unsigned *done_words,
+                                                                         unsigned done_value) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // (one barrier site for the whole block, as in multidiscrete_sample_kernel: a wave whose lanes split at `row < n` must not
+    // arrive at the barrier of block_done_words twice)
+    if (row < n) {
+        const float *z = logits + row * ld;
+        const float *q = noise + row * spec.H * spec.B;
+        double lp = 0.0;
+        int s = 0;
+        for (int h = 0; h < spec.H; ++h) {
+            const int b = spec.b[h];
+            float mx = z[s];
+            for (int c = 1; c < b; ++c) mx = fmaxf(mx, z[s + c]);
+            float sum = 0.f;
+            for (int c = 0; c < b; ++c) sum += expf(z[s + c] - mx);
+            const float lse = mx + logf(sum);
+            float best = -INFINITY;
+            int bi = 0;
+            for (int c = 0; c < b; ++c) {
+                const float v = (expf(z[s + c] - mx) / sum) / q[c];
+                if (v > best) {
+                    best = v;
+                    bi = c;
+                }
+            }
+            actions[row * spec.H + h] = bi;
+            lp += (double)(z[s + bi] - lse);
+            s += b;
+            q += spec.B;
+        }
+        logp[row] = (float)lp;
+    }
+    block_done_words(done_words, done_value, n);
+}
+
+int launch_multidiscrete_nvec_sample(hipStream_t st, const float *logits, int64_t ld, int64_t n, const float *noise, int64_t *actions,
+                                     float *logp, const MdSpec &spec, unsigned *done_words, unsigned done_value) {
+    if (n <= 0) return 0;
+    RLPPO_CHECK_ARG(spec.S <= ld, "multi-discrete head: %d logits in rows of %ld", spec.S, (long)ld);
+    hipLaunchKernelGGL(multidiscrete_nvec_sample_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, logits, ld, n, noise, actions,
+                       logp, spec, done_words, done_value);
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
+// log-sum-exp of one head's logits (the chain of multidiscrete_loss_kernel: running maximum from z[0], sum in c order)
+__device__ __forceinline__ float md_head_lse(const float *z, int b) {
+    float mx = z[0];
+    for (int c = 1; c < b; ++c) mx = fmaxf(mx, z[c]);
+    float sum = 0.f;
+    for (int c = 0; c < b; ++c) sum += expf(z[c] - mx);
+    return mx + logf(sum);
+}
+// entropy of one head given its log-sum-exp
+__device__ __forceinline__ float md_head_entropy(const float *z, int b, float lse) {
+    float e = 0.f;
+    for (int c = 0; c < b; ++c) {
+        const float ls = z[c] - lse;
+        e -= expf(ls) * ls;
+    }
+    return e;
+}
+// the stored action of head h, float-encoded; clamped into [0, b) BEFORE it indexes anything (a value outside its head's range is a
+// caller error: the row then trains on the nearest valid action, and no address outside the row is ever formed)
+__device__ __forceinline__ int md_action(float a, int b) {
+    const int i = (int)a;
+    return i < 0 ? 0 : (i >= b ? b - 1 : i);
+}
+
+// The gradient multidiscrete_loss_kernel writes, per head segment; columns >= S of the padded row are zeroed.  First walk: log p
+// and the entropy of the row (float terms summed in double, rounded once: see the sampling kernel); second walk: each head's log-sum-exp and entropy again, then its gradient in place (a head's logits
+// are overwritten only after the head's own reads).
+__global__ __launch_bounds__(256) void multidiscrete_nvec_loss_kernel(float *__restrict__ logits, int64_t ld, const float *__restrict__ actions,
+                                                                       const float *__restrict__ old_logp,
+                                                                       const float *__restrict__ advantages, int64_t mb, LossCfg cfg,
+                                                                       double *__restrict__ stats, MdSpec spec) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = row < mb;
+    float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (active) {
+        float *z = logits + row * ld;
+        const float *ar = actions + row * spec.H;
+        double lpd = 0.0, entd = 0.0;
+        int s = 0;
+        for (int h = 0; h < spec.H; ++h) {
+            const int b = spec.b[h];
+            const float lse = md_head_lse(z + s, b);
+            entd += (double)md_head_entropy(z + s, b, lse);
+            lpd += (double)(z[s + md_action(ar[h], b)] - lse);
+            s += b;
+        }
+        const float lp = (float)lpd, ent = (float)entd;
+        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
+        const float lr = lp - old;
+        const float ratio = expf(lr);
+        float smin;
+        const float w = surrogate_weight(ratio, adv, cfg, smin);
+        const float g_logp = cfg.mb_ratio * (-(adv * w * ratio) * cfg.inv_mb);
+        const float g_ent = -cfg.mb_ratio * cfg.ent_coef * cfg.inv_mb;  // coefficient of d(entropy_row)/dz
+        s = 0;
+        for (int h = 0; h < spec.H; ++h) {
+            const int b = spec.b[h];
+            const float lse = md_head_lse(z + s, b);
+            const float eh = md_head_entropy(z + s, b, lse);
+            const int a = md_action(ar[h], b);
+            for (int c = 0; c < b; ++c) {
+                const float ls = z[s + c] - lse, ph = expf(ls);
+                const float onehot = (c == a) ? 1.f : 0.f;
+                z[s + c] = g_logp * (onehot - ph) + g_ent * (-ph * (ls + eh));
+            }
+            s += b;
+        }
+        for (int c = spec.S; c < ld; ++c) z[c] = 0.f;
+        st[RLPPO_STAT_ENTROPY] = ent * cfg.inv_mb;
+        st[RLPPO_STAT_KL] = ((ratio - 1.f) - lr) * cfg.inv_mb;
+        st[RLPPO_STAT_CLIPFRAC] = (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
+        st[RLPPO_STAT_PLOSS] = -smin * cfg.inv_mb;
+    }
+    block_stats_add(stats, st, active, cfg, cfg.kl_slots);
+}
+
+int launch_multidiscrete_nvec_loss(hipStream_t st, float *logits, int64_t ld, const float *actions, const float *old_logp, const float *adv,
+                                   int64_t mb, const LossCfg &cfg, double *stats, const MdSpec &spec) {
+    if (mb <= 0) return 0;
+    RLPPO_CHECK_ARG(spec.S <= ld, "multi-discrete head: %d logits in rows of %ld", spec.S, (long)ld);
+    hipLaunchKernelGGL(multidiscrete_nvec_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, logits, ld, actions, old_logp, adv,
+                       mb, cfg, stats, spec);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }

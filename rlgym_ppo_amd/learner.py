@@ -10,6 +10,7 @@ import os
 import random
 import shutil
 import time
+import warnings
 
 import numpy as np
 import torch
@@ -40,7 +41,8 @@ class Learner(object):
             checkpoints_save_folder=None, add_unix_timestamp: bool = True, checkpoint_load_folder="latest",
             save_every_ts: int = 1_000_000, instance_launch_delay=None, random_seed: int = 123,
             n_checkpoints_to_keep: int = 5, shm_buffer_size: int = 8192, device: str = "auto",
-            vector_env: bool = False, gae_bootstrap_truncated: bool = False, per_feature_obs_standardization: bool = False,
+            vector_env: bool = False, gae_bootstrap_truncated: bool = False, multi_discrete_bins=None,
+            per_feature_obs_standardization: bool = False,
             ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
         assert env_create_function is not None, "MUST PROVIDE A FUNCTION TO CREATE RLGYM FUNCTIONS TO INITIALIZE RLGYM-PPO"
         if checkpoints_save_folder is None:
@@ -103,6 +105,15 @@ class Learner(object):
         print("Initializing PPO...")
         if ppo_minibatch_size is None:
             ppo_minibatch_size = ppo_batch_size
+        if multi_discrete_bins is not None:   # the nvec of the environment's MultiDiscrete space (PPOLearner takes it as act_space_size)
+            from .ppo.multi_discrete_policy import check_bins
+            if action_space_type != 1:
+                raise ValueError(f"multi_discrete_bins is an option of the multi-discrete policy (action space type 1), not of type {action_space_type}")
+            multi_discrete_bins = check_bins(multi_discrete_bins)
+            if len(multi_discrete_bins) != int(act_space_size):
+                raise ValueError(f"multi_discrete_bins has {len(multi_discrete_bins)} entries, but the action space has "
+                                 f"{int(act_space_size)} components")
+            act_space_size = multi_discrete_bins
         self.ppo_learner = PPOLearner(
             obs_space_size, act_space_size, device=self.device, batch_size=ppo_batch_size,
             mini_batch_size=ppo_minibatch_size, n_epochs=ppo_epochs, continuous_var_range=continuous_var_range,
@@ -111,6 +122,15 @@ class Learner(object):
             normalize_advantages=ppo_normalize_advantages, value_clip_range=ppo_value_clip_range, target_kl=ppo_target_kl,
             max_grad_norm=ppo_max_grad_norm)
         self.agent.policy = self.ppo_learner.policy
+        # not in the reference (whose multi-discrete policy has eight fixed heads): multi_discrete_bins is the environment's nvec.
+        # It is never taken from the environment by itself -- the default stays the reference's policy -- but where the
+        # environment is in this process (vector mode) a disagreement is worth one warning.
+        nvec = getattr(getattr(getattr(self.agent, "env", None), "action_space", None), "nvec", None) if vector_env else None
+        if action_space_type == 1 and nvec is not None:
+            in_effect = [int(b) for b in self.ppo_learner.policy.splits]
+            if [int(b) for b in np.asarray(nvec).reshape(-1)] != in_effect:
+                warnings.warn(f"the environment's action space is MultiDiscrete({list(np.asarray(nvec).reshape(-1))}) but the policy samples "
+                              f"bins {in_effect}: pass multi_discrete_bins to Learner", RuntimeWarning, stacklevel=2)
 
         self.config = {
             "n_proc": n_proc, "min_inference_size": min_inference_size, "timestep_limit": timestep_limit,

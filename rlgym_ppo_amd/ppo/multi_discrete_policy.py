@@ -1,5 +1,12 @@
 """MultiDiscreteFF -- drop-in for rlgym_ppo/ppo/multi_discrete_policy.py:16-89 (+ MultiDiscreteRolv,
-util/torch_functions.py:81-122) on librlppo's fused forward + 8-way categorical sampling kernel."""
+util/torch_functions.py:81-122) on librlppo's fused forward + 8-way categorical sampling kernel.
+
+`bins` (not in the reference, whose bins are literals): the nvec of a MultiDiscrete(nvec) action space -- H = len(bins) heads,
+sum(bins) outputs, every head padded to B = max(bins) where the reference pads its 2-way heads to 3.  None or the reference's own
+list [3, 3, 3, 3, 3, 2, 2, 2] is the reference's policy on the fixed kernels, launch for launch; anything else runs the general
+kernels (rlppo_multidiscrete_act_nvec; limits: include/rlppo.h, RLPPO_MD_MAX_*)."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -14,20 +21,50 @@ def _no_action_mask(action_mask):
         raise ValueError("action_mask: invalid-action masking is an option of the discrete head (DiscreteFF), not of the multi-discrete head")
 
 
+REFERENCE_BINS = (3, 3, 3, 3, 3, 2, 2, 2)  # multi_discrete_policy.py:20
+
+
+def check_bins(bins):
+    """bins -> a list of ints within the library's limits (ValueError otherwise)."""
+    try:
+        out = [int(b) for b in bins]
+        exact = all(float(b) == float(i) for b, i in zip(bins, out))
+    except (TypeError, ValueError):
+        raise ValueError(f"multi-discrete bins must be a sequence of integers, got {bins!r}") from None
+    if not exact or not 1 <= len(out) <= N.MD_MAX_HEADS:
+        raise ValueError(f"multi-discrete bins: 1 .. {N.MD_MAX_HEADS} integer entries, got {bins!r}")
+    if min(out) < 1 or max(out) > N.MD_MAX_BINS:
+        raise ValueError(f"multi-discrete bins: every entry must be in 1 .. {N.MD_MAX_BINS}, got {bins!r}")
+    if sum(out) > N.MD_MAX_LOGITS:
+        raise ValueError(f"multi-discrete bins: at most {N.MD_MAX_LOGITS} logits in all, got {sum(out)}")
+    return out
+
+
 class MultiDiscreteFF(ArenaModule):
-    def __init__(self, input_shape, layer_sizes, device):
+    def __init__(self, input_shape, layer_sizes, device, bins=None):
         super().__init__()
-        bins = [3, 3, 3, 3, 3, 2, 2, 2]
+        bins = list(REFERENCE_BINS) if bins is None else check_bins(bins)
         self.model = build_body(input_shape, layer_sizes, sum(bins))
         self.splits = bins
+        self.n_heads, self.max_bins, self.n_logits = len(bins), max(bins), sum(bins)
+        # the general kernels' nvec (HOST memory the library reads during a call); None = the reference's bins on the fixed kernels.
+        # (`_force_general`: measurements run the general kernels on the reference's bins -- tools/multidiscrete_bins_cost.py)
+        self._force_general = False
+        self._nvec_c = (ctypes.c_int32 * len(bins))(*bins)
+        self._general = tuple(bins) != REFERENCE_BINS
         self.multi_discrete = torch_functions.MultiDiscreteRolv(bins)
         self._finish(device)
+
+    @property
+    def md_nvec(self):
+        """The ctypes nvec the library's general kernels take, or None where the fixed kernels (the reference's bins) run."""
+        return self._nvec_c if (self._general or self._force_general) else None
 
     @torch.no_grad()
     def get_output(self, obs, action_mask=None):
         _no_action_mask(action_mask)
         rows = self.arena.stage_obs(obs)
-        return self.arena.forward(rows)[:, :21]
+        return self.arena.forward(rows)[:, :self.n_logits]
 
     @torch.no_grad()
     def get_action(self, obs, deterministic=False, noise=None, standardize=None, action_mask=None):
@@ -49,35 +86,43 @@ class MultiDiscreteFF(ArenaModule):
 
     # ---- hooks of the graph-replayed rollout step (ppo/_mlp.py::ActGraph)
     def _noise_shape(self, n):
-        return (n * 8, 3)
+        return (n * self.n_heads, self.max_bins)
 
     def _draw_noise(self, n):
-        return host_exponential((n * 8, 3))  # Categorical.sample -> multinomial on [n*8, 3]: torch.empty(n*8, 3).exponential_(1)
+        # Categorical.sample -> multinomial on [n*H, B]: torch.empty(n*H, B).exponential_(1)
+        return host_exponential((n * self.n_heads, self.max_bins))
 
     def _action_buffer(self, cap):
-        return torch.zeros((cap, 8), dtype=torch.int64)
+        return torch.zeros((cap, self.n_heads), dtype=torch.int64)
 
     def _act_launch(self, rows, n, noise, actions, logp, ws, opts=None):
         a = self.arena
-        N.check(N.lib().rlppo_multidiscrete_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1],
-                                                n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(), opts))
+        nvec = self.md_nvec
+        if nvec is None:
+            N.check(N.lib().rlppo_multidiscrete_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1],
+                                                    n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(), opts))
+        else:
+            N.check(N.lib().rlppo_multidiscrete_act_nvec(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1],
+                                                         n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(), opts,
+                                                         nvec, self.n_heads))
 
     def act_padded(self, rows, noise=None, action_mask=None):
-        """Padded device rows -> (actions int64 [n, 8], log_probs fp32 [n]) on the device (see DiscreteFF.act_padded)."""
+        """Padded device rows -> (actions int64 [n, H], log_probs fp32 [n]) on the device (see DiscreteFF.act_padded)."""
         _no_action_mask(action_mask)
         a = self.arena
         n = rows.shape[0]
+        H, B = self.n_heads, self.max_bins
         if noise is None and self.noise_mode == "device":
-            noise = torch.empty(n * 8, 3, device=a.device).exponential_(1)  # fast mode: torch's HIP generator, not the reference's CPU stream
+            noise = torch.empty(n * H, B, device=a.device).exponential_(1)  # fast mode: torch's HIP generator, not the reference's CPU stream
         elif noise is None:
-            noise = host_exponential((n * 8, 3), device=a.device)  # Categorical.sample -> multinomial on [n*8, 3]
+            noise = host_exponential((n * H, B), device=a.device)  # Categorical.sample -> multinomial on [n*H, B]
         q = torch.as_tensor(noise, dtype=torch.float32).to(a.device, non_blocking=True).contiguous()
         a.ensure_packed()
-        actions = torch.empty((n, 8), dtype=torch.int64, device=a.device)
+        if q.numel() != n * H * B:
+            raise ValueError(f"noise: {tuple(q.shape)} given, {n} rows of bins {self.splits} need ({n * H}, {B})")
+        actions = torch.empty((n, H), dtype=torch.int64, device=a.device)
         logp = torch.empty(n, dtype=torch.float32, device=a.device)
-        ws = a.forward_ws(n)
-        N.check(N.lib().rlppo_multidiscrete_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1],
-                                                n, ptr(q), ptr(actions), ptr(logp), ptr(ws), ws.numel(), None))
+        self._act_launch(rows, n, q, actions, logp, a.forward_ws(n))
         return actions, logp
 
     def get_backprop_data(self, obs, acts, action_mask=None):

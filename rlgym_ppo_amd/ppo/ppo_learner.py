@@ -17,7 +17,10 @@ state_dict layouts).  What changed underneath:
 
 Four opt-in options go beyond the reference (trailing keyword arguments; DESIGN.md, "Options beyond the reference"): per-batch
 advantage normalisation, Stable-Baselines3's clipped value loss, a target-KL stop of the optimiser steps and the gradient-norm
-limit.  Their defaults are the reference's update, launch for launch.
+limit.  Their defaults are the reference's update, launch for launch.  With policy_type 1, `act_space_size` may be the nvec of a
+MultiDiscrete(nvec) action space (a sequence of bin counts) instead of its length: an integer keeps the reference's eight heads
+[3, 3, 3, 3, 3, 2, 2, 2] and its kernels.  (The constructor's parameter list is the reference's plus the four options and stays
+that: the bins have no keyword of their own here; `Learner` has `multi_discrete_bins`.)
 """
 import ctypes
 import os
@@ -31,7 +34,7 @@ from ..dp import all_reduce_sum, dist_info, fuse_runs, slices_for_rank
 from ..engine import Workspace, ptr, require_gpu, stream_ptr
 from .continuous_policy import ContinuousPolicy
 from .discrete_policy import DiscreteFF
-from .multi_discrete_policy import MultiDiscreteFF
+from .multi_discrete_policy import MultiDiscreteFF, check_bins
 from .value_estimator import ValueEstimator
 
 MAX_GRAD_NORM = 0.5  # ppo_learner.py:187-190
@@ -122,6 +125,15 @@ class PPOLearner(object):
     def __init__(self, obs_space_size, act_space_size, policy_type, policy_layer_sizes, critic_layer_sizes,
                  continuous_var_range, batch_size, n_epochs, policy_lr, critic_lr, clip_range, ent_coef, mini_batch_size,
                  device, normalize_advantages=False, value_clip_range=None, target_kl=None, max_grad_norm=MAX_GRAD_NORM):
+        # act_space_size as a sequence: the nvec of a MultiDiscrete action space (a hyper-parameter like the layer sizes: not
+        # checkpoint state); checked before anything needs the GPU
+        multi_discrete_bins = None
+        if not isinstance(act_space_size, (int, float, np.integer, np.floating)) and np.ndim(act_space_size) > 0:
+            if int(policy_type) != 1:
+                raise ValueError(f"act_space_size={act_space_size!r}: multi-discrete bins are an option of the multi-discrete policy "
+                                 f"(policy_type 1), not of policy_type {policy_type}")
+            multi_discrete_bins = check_bins(act_space_size)
+            act_space_size = len(multi_discrete_bins)
         self.device = device
         self._dev = require_gpu(device)
         N.lib()  # fail here, loudly, if the HIP library is missing
@@ -137,8 +149,8 @@ class PPOLearner(object):
                                            var_min=continuous_var_range[0], var_max=continuous_var_range[1]).to(device)
             self._act_dim = int(act_space_size)
         elif policy_type == 1:
-            self.policy = MultiDiscreteFF(obs_space_size, policy_layer_sizes, device).to(device)
-            self._act_dim = 8
+            self.policy = MultiDiscreteFF(obs_space_size, policy_layer_sizes, device, bins=multi_discrete_bins).to(device)
+            self._act_dim = self.policy.n_heads
         else:
             self.policy = DiscreteFF(obs_space_size, act_space_size, policy_layer_sizes, device).to(device)
             self._act_dim = 1
@@ -262,6 +274,14 @@ class PPOLearner(object):
         self._slot_ws = [ws.data_ptr() + i * nbytes for i in range(self.n_slots)]
         a.workspace, a.ws_bytes = self._slot_ws[0], nbytes
         return a
+
+    def _pass(self, st, args):
+        """One rlppo_ppo_minibatch pass; a multi-discrete policy with bins of its own goes through rlppo_ppo_minibatch_nvec (the
+        general loss kernel), every other policy through the plain entry point."""
+        nvec = self.policy.md_nvec if self.policy_type == 1 else None
+        if nvec is None:
+            return N.lib().rlppo_ppo_minibatch(st, ctypes.byref(args))
+        return N.lib().rlppo_ppo_minibatch_nvec(st, ctypes.byref(args), nvec, self.policy.n_heads)
 
     def _check_options(self):
         if self.value_clip_range is not None and not float(self.value_clip_range) > 0:
@@ -405,7 +425,7 @@ class PPOLearner(object):
                         args.idx = idx_dev.data_ptr() + 8 * off
                         args.mb = cnt * MB                      # cnt consecutive minibatches in one pass
                         args.mb_ratio = float(cnt * MB / B)
-                        N.check(L.rlppo_ppo_minibatch(st, ctypes.byref(args)))
+                        N.check(self._pass(st, args))
                         n_passes += 1
                     N.check(L.rlppo_ppo_join(st))
                     if not refilled:

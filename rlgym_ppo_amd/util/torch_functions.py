@@ -124,19 +124,20 @@ class MapContinuousToAction(nn.Module):
 
 
 class MultiDiscreteRolv(nn.Module):
-    """8 categoricals over 21 logits, 2-way heads padded with -inf (torch_functions.py:81-122).  Kept for API
-    compatibility (get_backprop_data); sampling and the update use the fused kernels."""
+    """One categorical per entry of `bins` over sum(bins) logits, every head padded with -inf to max(bins): the reference's
+    construction (torch_functions.py:81-122: 8 categoricals over 21 logits, its 2-way heads padded to 3) for any bins.  Kept for
+    API compatibility (get_backprop_data); sampling and the update use the fused kernels."""
 
     def __init__(self, bins):
         super().__init__()
         self.distribution = None
-        self.bins = bins
+        self.bins = [int(b) for b in bins]
 
     def make_distribution(self, logits):
-        parts = torch.split(logits, self.bins, dim=-1)
-        triplets = torch.stack(parts[:5], dim=-1)
-        duets = torch.nn.functional.pad(torch.stack(parts[5:], dim=-1), pad=(0, 0, 0, 1), value=float("-inf"))
-        self.distribution = torch.distributions.Categorical(logits=torch.cat((triplets, duets), dim=-1).swapdims(-1, -2))
+        width = max(self.bins)
+        parts = [torch.nn.functional.pad(part, pad=(0, width - part.shape[-1]), value=float("-inf"))
+                 for part in torch.split(logits, self.bins, dim=-1)]
+        self.distribution = torch.distributions.Categorical(logits=torch.stack(parts, dim=-2))   # [..., H, B]
 
     def log_prob(self, action):
         return self.distribution.log_prob(action).sum(dim=-1)
