@@ -1,19 +1,23 @@
 // heads.hip -- action-head kernels: sampling for rollout inference and the fused loss epilogue of the PPO update.
 //
-// Discrete head: one wave (64 lanes) per row, EPL logits per lane held in registers, wave-shuffle reductions
-// (max, sum-exp, entropy, the softmax-Jacobian dot product, arg-max of p/q).  The chain is the reference's
-// literal softmax -> clamp(1e-11, 1) -> log (discrete_policy.py:52-54,70-78), NOT log_softmax, including the
-// clamp's zero-gradient region and torch.min's tie rule.
+// Discrete head: a row's logits are held in registers, spread over lanes by a row layout (WaveRow: one wave per row, EPL strided
+// logits per lane, wave-shuffle reductions; Lanes16, the loss up to 128 padded columns: 16 lanes per row, DPP reductions), and each
+// kernel -- sampling, probabilities, loss -- is one body over a layout (max, sum-exp, entropy, the softmax-Jacobian dot product,
+// arg-max of p/q).  The chain is the reference's literal softmax -> clamp(1e-11, 1) -> log (discrete_policy.py:52-54,70-78), NOT
+// log_softmax, including the clamp's zero-gradient region and torch.min's tie rule.
 // Gaussian / multi-discrete heads have 16 / 21 outputs per row: one thread per row, everything in registers.
+// Every policy loss kernel ends in the same PPO surrogate (surrogate_row, surrogate_stats_add); dispatch_discrete picks a discrete
+// kernel's instantiation from the row width and the presence of a mask.
 // [nvec] The multi-discrete head for MultiDiscrete(nvec) of any nvec (up to 64 heads of up to 64 bins, 512 logits): a general
 // sampling and a general loss kernel next to the fixed two, one thread per row, no per-row array (at the end of this file).
 //
-// [ABI 8] Invalid-action masking (discrete head): every discrete kernel has a MASKED instantiation (template parameter; the unmasked
-// instantiations are the code they were).  A row's mask is W = ceil(A / 32) words, bit c % 32 of word c / 32 = action c valid.  An
-// invalid action's logit is -inf, as the padded columns c >= A always were: p = 0 exactly, no candidate of the arg-max, no term of
+// [ABI 8] Invalid-action masking (discrete head): every discrete kernel has a MASKED instantiation (template parameter).  A row's
+// mask is W = ceil(A / 32) words, bit c % 32 of word c / 32 = action c valid.  An invalid action's logit is -inf, as the padded columns c >= A always were: p = 0 exactly, no candidate of the arg-max, no term of
 // the entropy, dL/dz = 0.  A row without a valid action counts as all-valid.  The loss kernels do NOT get the words through the
 // minibatch gather: they read row idx[r]'s words straight from the buffer's mask field through the logical -> physical ring map
 // (MaskRows below) -- the workspace plan and the gather launches of a pass are the same with and without a mask.
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace rlppo {
@@ -31,105 +35,200 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// [ABI 8] the valid actions of one row as the wave holds it: bit e of the result = element c = lane + 64 e is an action (c < A)
-// whose mask bit is set.  Element c sits in word c / 32 = (lane >> 5) + 2 e at bit lane & 31.  A row without a valid action is
-// all-valid (wave-uniform decision).
-template <int EPL>
-__device__ __forceinline__ unsigned row_valid_bits(const unsigned *__restrict__ words, int A, int lane) {
-    unsigned bits = 0, in_row = 0;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (c < A) {
-            in_row |= 1u << e;
-            bits |= ((words[(lane >> 5) + 2 * e] >> (lane & 31)) & 1u) << e;
-        }
-    }
-    return __ballot(bits != 0) ? bits : in_row;
+// ---- 16 lanes per row: the reductions are 4 DPP steps inside a 16-lane row instead of 6 cross-lane shuffles of a whole wave
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+// all-reduce over a 16-lane DPP row: xor 1, xor 2 (quad_perm), then half-row mirror and row mirror (every lane of a quad /
+// half row already holds the same partial, so a mirror is as good as an xor)
+__device__ __forceinline__ float row16_sum(float v) {
+    v += dpp_mov<0xB1>(v);
+    v += dpp_mov<0x4E>(v);
+    v += dpp_mov<0x141>(v);
+    v += dpp_mov<0x140>(v);
+    return v;
+}
+__device__ __forceinline__ float row16_max(float v) {
+    v = fmaxf(v, dpp_mov<0xB1>(v));
+    v = fmaxf(v, dpp_mov<0x4E>(v));
+    v = fmaxf(v, dpp_mov<0x141>(v));
+    v = fmaxf(v, dpp_mov<0x140>(v));
+    return v;
 }
 
-// softmax + clamp of one row spread over a wave; element c = lane + 64 e.  MASKED: `valid` (row_valid_bits) takes the place of c < A.
-template <int EPL, bool MASKED = false>
-__device__ __forceinline__ void row_softmax(const float *__restrict__ z, int A, int lane, float (&p)[EPL],
-                                            float (&pc)[EPL], unsigned valid = 0) {
+// ------------------------------------------------------------------------------------------ row layouts
+// How a discrete row lies over lanes.  The sampling, probability and loss kernels are written once against a layout, which supplies:
+// EPL elements per lane and ROWS rows per block, the row a lane works on (`group`) and the lane that reports for it (`writer`), the
+// column of element e, the row-wide sum and max, the load and store of a lane's logits, the valid actions of a row as bit e per
+// element, and SHADOW: whether the idle groups of a block's last pass run along on the last row (storing nothing) or leave.
+// A kernel's `in(e)` is "element e takes part": col(e) < A, or [ABI 8] its bit of valid_bits.
+
+// One wave per row, 4 rows per block: lane l holds the EPL strided columns l + 64 e (any width up to 64 EPL).
+template <int EPL_>
+struct WaveRow {
+    static constexpr int EPL = EPL_, ROWS = 4;
+    static constexpr bool SHADOW = false;
+    const int lane = threadIdx.x & 63, group = threadIdx.x >> 6;
+    __device__ __forceinline__ bool writer() const { return lane == 0; }
+    __device__ __forceinline__ int col(int e) const { return lane + 64 * e; }
+    __device__ __forceinline__ static float sum(float v) { return wave_sum(v); }
+    __device__ __forceinline__ static float max(float v) { return wave_max(v); }
+    template <class In>
+    __device__ __forceinline__ void load(const float *__restrict__ z, int64_t, float (&p)[EPL], In in) const {
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) p[e] = in(e) ? z[col(e)] : -INFINITY;
+    }
+    __device__ __forceinline__ void store(float *__restrict__ z, int64_t ld, const float (&g)[EPL]) const {
+#pragma unroll
+        for (int e = 0; e < EPL; ++e)
+            if (col(e) < ld) z[col(e)] = g[e];
+    }
+    // [ABI 8] element c = lane + 64 e sits in word c / 32 = (lane >> 5) + 2 e at bit lane & 31.  A row without a valid action is
+    // all-valid (wave-uniform decision).
+    __device__ __forceinline__ unsigned valid_bits(const unsigned *__restrict__ words, int A) const {
+        unsigned bits = 0, in_row = 0;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+            if (col(e) < A) {
+                in_row |= 1u << e;
+                bits |= ((words[(lane >> 5) + 2 * e] >> (lane & 31)) & 1u) << e;
+            }
+        }
+        return __ballot(bits != 0) ? bits : in_row;
+    }
+};
+
+// 16 lanes per row, 16 rows per block (padded width <= 128): a wave works on 4 rows at once and lane l of a row holds the 8
+// CONSECUTIVE columns 8 l .. 8 l + 7, two 16-byte loads / stores.  The padded width is a multiple of 32, so a lane's 8 columns are
+// all inside the row or all outside.  Only the summation order inside a row differs from WaveRow.
+struct Lanes16 {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    static constexpr int EPL = 8, ROWS = 16;
+    static constexpr bool SHADOW = true;
+    const int l16 = threadIdx.x & 15, group = threadIdx.x >> 4;
+    __device__ __forceinline__ bool writer() const { return l16 == 0; }
+    __device__ __forceinline__ int col(int e) const { return l16 * 8 + e; }
+    __device__ __forceinline__ static float sum(float v) { return row16_sum(v); }
+    __device__ __forceinline__ static float max(float v) { return row16_max(v); }
+    template <class In>
+    __device__ __forceinline__ void load(const float *__restrict__ z, int64_t ld, float (&p)[8], In in) const {
+        if (col(0) < ld) {
+            const f32x4 z0 = *reinterpret_cast<const f32x4 *>(z + col(0)), z1 = *reinterpret_cast<const f32x4 *>(z + col(4));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                p[e] = z0[e];
+                p[4 + e] = z1[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (!in(e)) p[e] = -INFINITY;
+    }
+    __device__ __forceinline__ void store(float *__restrict__ z, int64_t ld, const float (&g)[8]) const {
+        if (col(0) < ld) {
+            *reinterpret_cast<f32x4 *>(z + col(0)) = f32x4{g[0], g[1], g[2], g[3]};
+            *reinterpret_cast<f32x4 *>(z + col(4)) = f32x4{g[4], g[5], g[6], g[7]};
+        }
+    }
+    // [ABI 8] a lane's 8 consecutive actions are exactly byte l16 of the row's mask words (little-endian bit order)
+    __device__ __forceinline__ unsigned valid_bits(const unsigned *__restrict__ words, int A) const {
+        const int c0 = col(0);
+        const unsigned in_bits = c0 + 8 <= A ? 0xffu : (c0 < A ? (1u << (A - c0)) - 1u : 0u);
+        unsigned valid = 0;
+        if (in_bits)  // (c0 < A: byte l16 lies inside the row's W = ceil(A / 32) words)
+            valid = reinterpret_cast<const unsigned char *>(words)[l16] & in_bits;
+        return row16_max(valid ? 1.f : 0.f) > 0.f ? valid : in_bits;  // a row without a valid action: all-valid
+    }
+};
+
+// softmax + clamp of one row: p holds the lane's logits (-inf where !in(e)) and leaves as the probabilities, pc as the clamped ones
+template <class L, class In>
+__device__ __forceinline__ void softmax_clamp(float (&p)[L::EPL], float (&pc)[L::EPL], In in) {
     float mx = -INFINITY;
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
-        p[e] = in ? z[c] : -INFINITY;
-        mx = fmaxf(mx, p[e]);
-    }
-    mx = wave_max(mx);
+    for (int e = 0; e < L::EPL; ++e) mx = fmaxf(mx, p[e]);
+    mx = L::max(mx);
     float s = 0.f;
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
-        p[e] = in ? expf(p[e] - mx) : 0.f;
+    for (int e = 0; e < L::EPL; ++e) {
+        p[e] = in(e) ? expf(p[e] - mx) : 0.f;
         s += p[e];
     }
-    s = wave_sum(s);
+    s = L::sum(s);
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) {
+    for (int e = 0; e < L::EPL; ++e) {
         p[e] = p[e] / s;
         pc[e] = fminf(fmaxf(p[e], PROB_MIN), 1.0f);
     }
+}
+
+// Width dispatch of the discrete kernels: widths up to 128 / 512 / 2048 take 2 / 8 / 32 elements per lane, and a mask selects the
+// MASKED instantiations.  f(epl, masked) gets both as compile-time constants (std::integral_constant, std::bool_constant).
+template <class F>
+static int dispatch_discrete(int width, bool masked, F f) {
+    const auto with_mask = [&](auto epl) {
+        if (masked)
+            f(epl, std::true_type{});
+        else
+            f(epl, std::false_type{});
+    };
+    if (width <= 128)
+        with_mask(std::integral_constant<int, 2>{});
+    else if (width <= 512)
+        with_mask(std::integral_constant<int, 8>{});
+    else if (width <= 2048)
+        with_mask(std::integral_constant<int, 32>{});
+    else {
+        set_error("discrete head: n_actions=%d > 2048 unsupported", width);
+        return RLPPO_ERR_ARG;
+    }
+    RLPPO_LAUNCH_CHECK();
+    return 0;
 }
 
 // ----------------------------------------------------------------------------------- discrete: sampling
 // action = argmax_c pc[c] / q[c] (first index wins ties), logp = log(pc[action]).  `from_probs`: the row already
 // holds clamped probabilities (rlppo_categorical_select).  MASKED [ABI 8]: mask[n][W] words; only valid actions are candidates (the
 // clamp's 1e-11 never makes an invalid one selectable), probs_out is 0 on invalid actions; the noise stays [n][A].
-template <int EPL, bool FROM_PROBS, bool MASKED = false>
+template <int EPL, bool FROM_PROBS, bool MASKED>
 __global__ __launch_bounds__(256) void discrete_sample_kernel(const float *__restrict__ src, int64_t ld, int64_t n,
                                                                int A, const float *__restrict__ noise,
                                                                int64_t *__restrict__ actions, float *__restrict__ logp,
                                                                float *__restrict__ probs_out,
-                                                               const unsigned *__restrict__ mask = nullptr, int W = 0) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+                                                               const unsigned *__restrict__ mask, int W) {
+    typedef WaveRow<EPL> L;
+    const L lay;
+    const int64_t row = (int64_t)blockIdx.x * L::ROWS + lay.group;
     if (row >= n) return;
     float p[EPL], pc[EPL];
     const float *z = src + row * ld;
     unsigned valid = 0;
-    if (MASKED) valid = row_valid_bits<EPL>(mask + row * W, A, lane);
-    if (MASKED) {
-        row_softmax<EPL, true>(z, A, lane, p, pc, valid);
-    } else if (FROM_PROBS) {
+    if (MASKED) valid = lay.valid_bits(mask + row * W, A);
+    const auto in = [&](int e) { return MASKED ? ((valid >> e) & 1u) != 0 : lay.col(e) < A; };
+    if (FROM_PROBS) {
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            const int c = lane + 64 * e;
-            pc[e] = c < A ? z[c] : 0.f;
-        }
+        for (int e = 0; e < EPL; ++e) pc[e] = in(e) ? z[lay.col(e)] : 0.f;
     } else {
-        row_softmax<EPL>(z, A, lane, p, pc);
+        lay.load(z, ld, p, in);
+        softmax_clamp<L>(p, pc, in);
     }
     float best = -INFINITY;
     int besti = 0x7fffffff;
     float bestp = 1.f;
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (MASKED) {
-            if ((valid >> e) & 1u) {
-                const float v = pc[e] / noise[row * A + c];
-                if (v > best) {
-                    best = v;
-                    besti = c;
-                    bestp = pc[e];
-                }
-            }
-            if (probs_out && c < A) probs_out[row * A + c] = ((valid >> e) & 1u) ? pc[e] : 0.f;
-        } else if (c < A) {
-            const float v = pc[e] / noise[row * A + c];  // IEEE fp32 division, as at::div
+        const int c = lay.col(e);
+        const int64_t i = row * A + c;  // element c of the row in noise and probs_out, both [n][A]
+        if (in(e)) {
+            const float v = pc[e] / noise[i];  // IEEE fp32 division, as at::div
             if (v > best) {
                 best = v;
                 besti = c;
                 bestp = pc[e];
             }
-            if (probs_out) probs_out[row * A + c] = pc[e];
         }
+        if (probs_out && c < A) probs_out[i] = in(e) ? pc[e] : 0.f;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -142,7 +241,7 @@ __global__ __launch_bounds__(256) void discrete_sample_kernel(const float *__res
             bestp = op;
         }
     }
-    if (lane == 0) {
+    if (lay.writer()) {
         actions[row] = besti;
         logp[row] = logf(bestp);
     }
@@ -152,34 +251,12 @@ template <bool FROM_PROBS>
 static int launch_discrete_sample(hipStream_t st, const float *src, int64_t ld, int64_t n, int A, const float *noise,
                                   int64_t *actions, float *logp, float *probs_out, const unsigned *mask = nullptr, int W = 0) {
     if (n <= 0) return 0;
-    dim3 grid((unsigned)cdiv(n, 4)), block(256);
-    if (!FROM_PROBS && mask) {  // [ABI 8] the masked instantiations
-        RLPPO_CHECK_ARG(W == (A + 31) / 32, "discrete head: mask_words=%d, n_actions=%d needs %d", W, A, (A + 31) / 32);
-        if (A <= 128)
-            hipLaunchKernelGGL((discrete_sample_kernel<2, false, true>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out, mask, W);
-        else if (A <= 512)
-            hipLaunchKernelGGL((discrete_sample_kernel<8, false, true>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out, mask, W);
-        else if (A <= 2048)
-            hipLaunchKernelGGL((discrete_sample_kernel<32, false, true>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out, mask, W);
-        else {
-            set_error("discrete head: n_actions=%d > 2048 unsupported", A);
-            return RLPPO_ERR_ARG;
-        }
-        RLPPO_LAUNCH_CHECK();
-        return 0;
-    }
-    if (A <= 128)
-        hipLaunchKernelGGL((discrete_sample_kernel<2, FROM_PROBS>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out);
-    else if (A <= 512)
-        hipLaunchKernelGGL((discrete_sample_kernel<8, FROM_PROBS>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out);
-    else if (A <= 2048)
-        hipLaunchKernelGGL((discrete_sample_kernel<32, FROM_PROBS>), grid, block, 0, st, src, ld, n, A, noise, actions, logp, probs_out);
-    else {
-        set_error("discrete head: n_actions=%d > 2048 unsupported", A);
-        return RLPPO_ERR_ARG;
-    }
-    RLPPO_LAUNCH_CHECK();
-    return 0;
+    if (FROM_PROBS) mask = nullptr;
+    RLPPO_CHECK_ARG(!mask || W == (A + 31) / 32, "discrete head: mask_words=%d, n_actions=%d needs %d", W, A, (A + 31) / 32);
+    return dispatch_discrete(A, mask != nullptr, [&](auto epl, auto masked) {
+        hipLaunchKernelGGL((discrete_sample_kernel<decltype(epl)::value, FROM_PROBS, !FROM_PROBS && decltype(masked)::value>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, src,
+                           ld, n, A, noise, actions, logp, probs_out, mask, W);
+    });
 }
 
 int launch_discrete_sample_logits(hipStream_t st, const float *logits, int64_t ld, int64_t n, int A, const float *noise,
@@ -197,40 +274,30 @@ int launch_categorical_select(hipStream_t st, const float *probs, int64_t ld, in
 // The flat arg-max is one 64-bit atomic max per row on key = (float bits of the row maximum << 32) | ~flat index: clamped
 // probabilities are positive, so their bit patterns order like the values, and of equal values the smaller flat index wins.
 // MASKED [ABI 8]: invalid actions read 0 (with and without the clamp) and are no candidates of the arg-max.
-template <int EPL, bool MASKED = false>
+template <int EPL, bool MASKED>
 __global__ __launch_bounds__(256) void discrete_probs_kernel(const float *__restrict__ logits, int64_t ld, int64_t n, int A,
                                                               int clamp, float *__restrict__ probs, int64_t ld_p,
                                                               unsigned long long *__restrict__ key,
-                                                              const unsigned *__restrict__ mask = nullptr, int W = 0) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+                                                              const unsigned *__restrict__ mask, int W) {
+    typedef WaveRow<EPL> L;
+    const L lay;
+    const int64_t row = (int64_t)blockIdx.x * L::ROWS + lay.group;
     if (row >= n) return;
     float p[EPL], pc[EPL];
     unsigned valid = 0;
-    if (MASKED) {
-        valid = row_valid_bits<EPL>(mask + row * W, A, lane);
-        row_softmax<EPL, true>(logits + row * ld, A, lane, p, pc, valid);
-    } else {
-        row_softmax<EPL>(logits + row * ld, A, lane, p, pc);
-    }
+    if (MASKED) valid = lay.valid_bits(mask + row * W, A);
+    const auto in = [&](int e) { return MASKED ? ((valid >> e) & 1u) != 0 : lay.col(e) < A; };
+    lay.load(logits + row * ld, ld, p, in);
+    softmax_clamp<L>(p, pc, in);
     float best = -1.f;
     int besti = 0x7fffffff;
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
-        const int c = lane + 64 * e;
-        if (MASKED) {
-            const bool ok = ((valid >> e) & 1u) != 0;
-            if (probs && c < A) probs[row * ld_p + c] = ok ? (clamp ? pc[e] : p[e]) : 0.f;
-            if (ok && pc[e] > best) {
-                best = pc[e];
-                besti = c;
-            }
-        } else if (c < A) {
-            if (probs) probs[row * ld_p + c] = clamp ? pc[e] : p[e];
-            if (pc[e] > best) {
-                best = pc[e];
-                besti = c;
-            }
+        const int c = lay.col(e);
+        if (probs && c < A) probs[row * ld_p + c] = in(e) ? (clamp ? pc[e] : p[e]) : 0.f;
+        if (in(e) && pc[e] > best) {
+            best = pc[e];
+            besti = c;
         }
     }
     if (!key) return;
@@ -243,7 +310,7 @@ __global__ __launch_bounds__(256) void discrete_probs_kernel(const float *__rest
             besti = oi;
         }
     }
-    if (lane == 0) {
+    if (lay.writer()) {
         const unsigned long long flat = (unsigned long long)(row * A + besti);
         atomicMax(key, ((unsigned long long)__float_as_uint(best) << 32) | (0xffffffffull - flat));
     }
@@ -262,24 +329,11 @@ int launch_discrete_probs(hipStream_t st, const float *logits, int64_t ld, int64
     }
     unsigned long long *key = (unsigned long long *)flat_argmax;
     if (key) RLPPO_HIP(hipMemsetAsync(key, 0, sizeof(*key), st));
-    dim3 grid((unsigned)cdiv(n, 4)), block(256);
-    if (mask && A <= 128)
-        hipLaunchKernelGGL((discrete_probs_kernel<2, true>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key, mask, W);
-    else if (mask && A <= 512)
-        hipLaunchKernelGGL((discrete_probs_kernel<8, true>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key, mask, W);
-    else if (mask && A <= 2048)
-        hipLaunchKernelGGL((discrete_probs_kernel<32, true>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key, mask, W);
-    else if (A <= 128)
-        hipLaunchKernelGGL((discrete_probs_kernel<2>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key);
-    else if (A <= 512)
-        hipLaunchKernelGGL((discrete_probs_kernel<8>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key);
-    else if (A <= 2048)
-        hipLaunchKernelGGL((discrete_probs_kernel<32>), grid, block, 0, st, logits, ld, n, A, clamp, probs, ld_p, key);
-    else {
-        set_error("discrete head: n_actions=%d > 2048 unsupported", A);
-        return RLPPO_ERR_ARG;
-    }
-    RLPPO_LAUNCH_CHECK();
+    const int rc = dispatch_discrete(A, mask != nullptr, [&](auto epl, auto masked) {
+        hipLaunchKernelGGL((discrete_probs_kernel<decltype(epl)::value, decltype(masked)::value>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, logits, ld, n, A, clamp, probs,
+                           ld_p, key, mask, W);
+    });
+    if (rc) return rc;
     if (key) {
         hipLaunchKernelGGL(decode_flat_argmax_kernel, dim3(1), dim3(1), 0, st, key);
         RLPPO_LAUNCH_CHECK();
@@ -296,6 +350,31 @@ __device__ __forceinline__ float surrogate_weight(float ratio, float adv, const 
     const float inr = (ratio >= c.clip_lo && ratio <= c.clip_hi) ? 1.f : 0.f;
     s_min = fminf(s1, s2);
     return s1 < s2 ? 1.f : (s1 > s2 ? inr : 0.5f + 0.5f * inr);
+}
+
+// [ABI 7] the advantage the surrogate sees: the stored one, or (A - mean) * scale of the batch (rlppo_adv_stats)
+__device__ __forceinline__ float surrogate_adv(float adv, const LossCfg &c) { return c.adv_norm ? (adv - c.adv_norm[0]) * c.adv_norm[1] : adv; }
+
+// The PPO surrogate of one row, the tail of every policy loss kernel: from the row's log-probability, the stored one and the stored
+// advantage to the log-ratio, the ratio, the surrogate min(s1, s2) and dL/d(log p)
+struct Surrogate {
+    float lr, ratio, smin, g_logp;
+};
+__device__ __forceinline__ Surrogate surrogate_row(float lp, float old_logp, float stored_adv, const LossCfg &c) {
+    const float adv = surrogate_adv(stored_adv, c);
+    Surrogate t;
+    t.lr = lp - old_logp;
+    t.ratio = expf(t.lr);
+    const float w = surrogate_weight(t.ratio, adv, c, t.smin);
+    t.g_logp = c.mb_ratio * (-(adv * w * t.ratio) * c.inv_mb);
+    return t;
+}
+// ... and the row's share of the four report statistics of the policy loss; `entropy` is the row's term of the mean entropy
+__device__ __forceinline__ void surrogate_stats_add(float (&st)[5], float entropy, const Surrogate &t, const LossCfg &c) {
+    st[RLPPO_STAT_ENTROPY] += entropy;
+    st[RLPPO_STAT_KL] += ((t.ratio - 1.f) - t.lr) * c.inv_mb;
+    st[RLPPO_STAT_CLIPFRAC] += (fabsf(t.ratio - 1.f) > c.clip ? 1.f : 0.f) * c.inv_mb;
+    st[RLPPO_STAT_PLOSS] += -t.smin * c.inv_mb;
 }
 
 // block-level accumulation of per-row statistics into the double accumulators.  [ABI 7] kl_slots (the policy loss launches of an
@@ -325,8 +404,17 @@ __device__ __forceinline__ void block_stats_add(double *stats, const float (&v)[
     }
 }
 
-// [ABI 7] the advantage the surrogate sees: the stored one, or (A - mean) * scale of the batch (rlppo_adv_stats)
-__device__ __forceinline__ float surrogate_adv(float adv, const LossCfg &c) { return c.adv_norm ? (adv - c.adv_norm[0]) * c.adv_norm[1] : adv; }
+// The grids of the policy loss launches: block b's KL sum lands in kl_slots[2 + b], so kl_slots_doubles sizes the slots from them.
+constexpr int64_t DISCRETE_LOSS_MAX_BLOCKS = 2048;  // the discrete loss strides its grid over the rows
+static unsigned discrete_loss_grid(int64_t mb, int rows_per_block) {
+    const int64_t g = cdiv(mb, rows_per_block);
+    return (unsigned)(g < DISCRETE_LOSS_MAX_BLOCKS ? g : DISCRETE_LOSS_MAX_BLOCKS);
+}
+static unsigned thread_per_row_grid(int64_t mb) { return (unsigned)cdiv(mb, 256); }  // gaussian / multi-discrete: one thread per row
+int64_t kl_slots_doubles(int64_t mb) {
+    const int64_t g = thread_per_row_grid(mb > 0 ? mb : 1);
+    return 2 + (g > DISCRETE_LOSS_MAX_BLOCKS ? g : DISCRETE_LOSS_MAX_BLOCKS);
+}
 
 // value loss for one row: writes dL/dv in place, returns (v - t)^2.  [ABI 7] vclip > 0: Stable-Baselines3's clipped prediction
 // v_pred = v_old + clamp(v - v_old, -c, c) around v_old = target - A (the buffer's target is V + A), loss (v_pred - t)^2, gradient
@@ -346,215 +434,64 @@ __device__ __forceinline__ float value_row(float *vout_row, float target, float 
 }
 
 // ----------------------------------------------------------------------------------- discrete: loss + grad
-// One wave per row.  logits[row][0:A] is overwritten with dL/dlogits.
+// logits[row][0:A] is overwritten with dL/dlogits.  One body for both layouts (L = Lanes16 up to a padded width of 128, WaveRow<8> and
+// WaveRow<32> above); the block strides over the rows and the statistics stay in registers, so a launch issues 5 atomics per BLOCK.
 // MASKED [ABI 8]: the row's mask words come from the buffer's mask field at the physical row of idx[row] (MaskRows); invalid
 // actions have p = 0, no entropy term and dL/dz = 0.  A stored action its own mask marks invalid (a caller error) takes the literal
 // chain: pc_a = 1e-11 inside the clamp's zero-gradient region -- finite, no gradient.
-template <int EPL, bool MASKED = false>
+template <class L, bool MASKED>
 __global__ __launch_bounds__(256) void discrete_loss_kernel(float *__restrict__ logits, int64_t ld, int A,
                                                              const float *__restrict__ actions,
                                                              const float *__restrict__ old_logp,
                                                              const float *__restrict__ advantages, int64_t mb,
-                                                             LossCfg cfg, double *__restrict__ stats, MaskRows mr = MaskRows{}) {
-    const int lane = threadIdx.x & 63;
+                                                             LossCfg cfg, double *__restrict__ stats, MaskRows mr) {
+    constexpr int EPL = L::EPL;
+    const L lay;
     float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    // grid-stride over rows: statistics stay in registers, so a launch issues 5 atomics per BLOCK, not per 4 rows
-    for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < mb; row += (int64_t)gridDim.x * 4) {
+    for (int64_t base = (int64_t)blockIdx.x * L::ROWS; base < mb; base += (int64_t)gridDim.x * L::ROWS) {
+        const bool live = base + lay.group < mb;
+        if (!L::SHADOW && !live) break;
+        const int64_t row = live ? base + lay.group : mb - 1;
         float *z = logits + row * ld;
-        float p[EPL], pc[EPL], lp[EPL];
         unsigned valid = 0;
-        if (MASKED) {
-            valid = row_valid_bits<EPL>(mr.mask + ring_row(mr.idx[row], mr.ring_base, mr.ring_cap) * mr.W, A, lane);
-            row_softmax<EPL, true>(z, A, lane, p, pc, valid);
-        } else {
-            row_softmax<EPL>(z, A, lane, p, pc);
-        }
+        if (MASKED) valid = lay.valid_bits(mr.mask + ring_row(mr.idx[row], mr.ring_base, mr.ring_cap) * mr.W, A);
+        const auto in = [&](int e) { return MASKED ? ((valid >> e) & 1u) != 0 : lay.col(e) < A; };
+        float p[EPL], pc[EPL], lp[EPL];
+        lay.load(z, ld, p, in);
+        softmax_clamp<L>(p, pc, in);
         const int a = (int)actions[row];  // acts.long() of a float-encoded index (discrete_policy.py:71)
         float ent = 0.f, lpa = 0.f, pca = 0.f;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
-            const int c = lane + 64 * e;
-            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
-            lp[e] = in ? logf(pc[e]) : 0.f;
-            if (in) ent -= lp[e] * pc[e];
-            if (c == a) {
-                lpa = MASKED && !in ? logf(pc[e]) : lp[e];
+            lp[e] = in(e) ? logf(pc[e]) : 0.f;
+            if (in(e)) ent -= lp[e] * pc[e];
+            if (lay.col(e) == a) {
+                lpa = MASKED && !in(e) ? logf(pc[e]) : lp[e];
                 pca = pc[e];
             }
         }
-        ent = wave_sum(ent);
-        lpa = wave_sum(lpa);  // exactly one lane holds a non-zero term
-        pca = wave_sum(pca);
-        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
-        const float lr = lpa - old;
-        const float ratio = expf(lr);
-        float smin;
-        const float w = surrogate_weight(ratio, adv, cfg, smin);
-        const float g_logp = cfg.mb_ratio * (-(adv * w * ratio) * cfg.inv_mb);
+        ent = L::sum(ent);
+        lpa = L::sum(lpa);  // exactly one lane holds a non-zero term
+        pca = L::sum(pca);
+        const Surrogate t = surrogate_row(lpa, old_logp[row], advantages[row], cfg);
         const float g_ent = cfg.mb_ratio * (cfg.ent_coef * cfg.inv_mb);
-        float gp[EPL];
+        float g[EPL];
         float dot = 0.f;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
-            const int c = lane + 64 * e;
-            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
-            float g = 0.f;
-            if (in) {
-                g = g_ent * (lp[e] + 1.f);
-                if (c == a) g += g_logp / pca;
-                if (!(p[e] >= PROB_MIN)) g = 0.f;  // clamp passes gradient on [1e-11, 1] only
+            g[e] = 0.f;
+            if (in(e)) {
+                g[e] = g_ent * (lp[e] + 1.f);
+                if (lay.col(e) == a) g[e] += t.g_logp / pca;
+                if (!(p[e] >= PROB_MIN)) g[e] = 0.f;  // clamp passes gradient on [1e-11, 1] only
             }
-            gp[e] = g;
-            dot += g * p[e];
+            dot += g[e] * p[e];
         }
-        dot = wave_sum(dot);
+        dot = L::sum(dot);
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            const int c = lane + 64 * e;
-            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
-            if (c < ld) z[c] = in ? p[e] * (gp[e] - dot) : 0.f;
-        }
-        if (lane == 0) {
-            st[RLPPO_STAT_ENTROPY] += ent * cfg.inv_mb;
-            st[RLPPO_STAT_KL] += ((ratio - 1.f) - lr) * cfg.inv_mb;
-            st[RLPPO_STAT_CLIPFRAC] += (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
-            st[RLPPO_STAT_PLOSS] += -smin * cfg.inv_mb;
-        }
-    }
-    block_stats_add(stats, st, true, cfg, cfg.kl_slots);
-}
-
-// ---- 16 lanes per row (padded width <= 128): a wave works on 4 rows at once, a lane holds 8 CONSECUTIVE logits (two
-// 16-byte loads/stores) and the six per-row reductions are 4 DPP steps inside a 16-lane row instead of 6 cross-lane
-// shuffles of a whole wave.  Same arithmetic chain as discrete_loss_kernel; only the summation order inside a row differs.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// all-reduce over a 16-lane DPP row: xor 1, xor 2 (quad_perm), then half-row mirror and row mirror (every lane of a quad /
-// half row already holds the same partial, so a mirror is as good as an xor)
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_mov<0xB1>(v);
-    v += dpp_mov<0x4E>(v);
-    v += dpp_mov<0x141>(v);
-    v += dpp_mov<0x140>(v);
-    return v;
-}
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, dpp_mov<0xB1>(v));
-    v = fmaxf(v, dpp_mov<0x4E>(v));
-    v = fmaxf(v, dpp_mov<0x141>(v));
-    v = fmaxf(v, dpp_mov<0x140>(v));
-    return v;
-}
-
-// MASKED [ABI 8]: a lane's 8 consecutive logits are exactly byte l16 of the row's mask words (little-endian bit order).
-template <bool MASKED = false>
-__global__ __launch_bounds__(256) void discrete_loss16_kernel(float *__restrict__ logits, int64_t ld, int A,
-                                                               const float *__restrict__ actions,
-                                                               const float *__restrict__ old_logp,
-                                                               const float *__restrict__ advantages, int64_t mb,
-                                                               LossCfg cfg, double *__restrict__ stats, MaskRows mr = MaskRows{}) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    const int l16 = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    const int c0 = l16 * 8;
-    const bool in_row = c0 < ld;  // ld is a multiple of 32, so a lane's 8 columns are all inside or all outside
-    float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int64_t base = (int64_t)blockIdx.x * 16; base < mb; base += (int64_t)gridDim.x * 16) {
-        const bool live = base + grp < mb;
-        const int64_t row = live ? base + grp : mb - 1;  // idle groups of the last pass shadow the last row (no stores)
-        float *z = logits + row * ld + c0;
-        float p[8], pc[8], lp[8];
-        if (in_row) {
-            const f32x4 z0 = *reinterpret_cast<const f32x4 *>(z), z1 = *reinterpret_cast<const f32x4 *>(z + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                p[e] = z0[e];
-                p[4 + e] = z1[e];
-            }
-        }
-        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
-        const int a = (int)actions[row];  // acts.long() of a float-encoded index (discrete_policy.py:71)
-        unsigned valid = 0;  // (MASKED) bit e: action c0 + e exists and is valid
-        if (MASKED) {
-            const unsigned in_bits = c0 + 8 <= A ? 0xffu : (c0 < A ? (1u << (A - c0)) - 1u : 0u);
-            if (in_bits)  // (c0 < A: byte l16 lies inside the row's W = ceil(A / 32) words)
-                valid = reinterpret_cast<const unsigned char *>(mr.mask + ring_row(mr.idx[row], mr.ring_base, mr.ring_cap) * mr.W)[l16] & in_bits;
-            if (!(row16_max(valid ? 1.f : 0.f) > 0.f)) valid = in_bits;  // a row without a valid action: all-valid
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : (in_row && c0 + e < A);
-            if (!in) p[e] = -INFINITY;
-            mx = fmaxf(mx, p[e]);
-        }
-        mx = row16_max(mx);
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : (c0 + e < A);
-            p[e] = in ? expf(p[e] - mx) : 0.f;
-            s += p[e];
-        }
-        s = row16_sum(s);
-        float ent = 0.f, lpa = 0.f, pca = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int c = c0 + e;
-            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
-            p[e] = p[e] / s;
-            pc[e] = fminf(fmaxf(p[e], PROB_MIN), 1.0f);
-            lp[e] = in ? logf(pc[e]) : 0.f;
-            if (in) ent -= lp[e] * pc[e];
-            if (c == a) {
-                lpa = MASKED && !in ? logf(pc[e]) : lp[e];
-                pca = pc[e];
-            }
-        }
-        ent = row16_sum(ent);
-        lpa = row16_sum(lpa);  // exactly one lane holds a non-zero term
-        pca = row16_sum(pca);
-        const float lr = lpa - old;
-        const float ratio = expf(lr);
-        float smin;
-        const float w = surrogate_weight(ratio, adv, cfg, smin);
-        const float g_logp = cfg.mb_ratio * (-(adv * w * ratio) * cfg.inv_mb);
-        const float g_ent = cfg.mb_ratio * (cfg.ent_coef * cfg.inv_mb);
-        float gp[8];
-        float dot = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int c = c0 + e;
-            const bool in = MASKED ? ((valid >> e) & 1u) != 0 : c < A;
-            float g = 0.f;
-            if (in) {
-                g = g_ent * (lp[e] + 1.f);
-                if (c == a) g += g_logp / pca;
-                if (!(p[e] >= PROB_MIN)) g = 0.f;  // clamp passes gradient on [1e-11, 1] only
-            }
-            gp[e] = g;
-            dot += g * p[e];
-        }
-        dot = row16_sum(dot);
-        if (live && in_row) {
-            f32x4 o0, o1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const bool in0 = MASKED ? ((valid >> e) & 1u) != 0 : (c0 + e < A);
-                const bool in1 = MASKED ? ((valid >> (4 + e)) & 1u) != 0 : (c0 + 4 + e < A);
-                o0[e] = in0 ? p[e] * (gp[e] - dot) : 0.f;
-                o1[e] = in1 ? p[4 + e] * (gp[4 + e] - dot) : 0.f;
-            }
-            *reinterpret_cast<f32x4 *>(z) = o0;
-            *reinterpret_cast<f32x4 *>(z + 4) = o1;
-        }
-        if (live && l16 == 0) {
-            st[RLPPO_STAT_ENTROPY] += ent * cfg.inv_mb;
-            st[RLPPO_STAT_KL] += ((ratio - 1.f) - lr) * cfg.inv_mb;
-            st[RLPPO_STAT_CLIPFRAC] += (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
-            st[RLPPO_STAT_PLOSS] += -smin * cfg.inv_mb;
-        }
+        for (int e = 0; e < EPL; ++e) g[e] = in(e) ? p[e] * (g[e] - dot) : 0.f;
+        if (live) lay.store(z, ld, g);
+        if (live && lay.writer()) surrogate_stats_add(st, ent * cfg.inv_mb, t, cfg);
     }
     block_stats_add(stats, st, true, cfg, cfg.kl_slots);
 }
@@ -581,37 +518,17 @@ int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const float *tar
     return 0;
 }
 
-int64_t kl_slots_doubles(int64_t mb) {  // grids: discrete <= 2048 workgroups, gaussian / multi-discrete cdiv(mb, 256)
-    const int64_t g = cdiv(mb > 0 ? mb : 1, 256);
-    return 2 + (g > 2048 ? g : 2048);
-}
-
 int launch_discrete_loss(hipStream_t st, float *logits, int64_t ld, int A, const float *actions, const float *old_logp, const float *adv,
                          int64_t mb, const LossCfg &cfg, double *stats, const MaskRows *mr) {
     if (mb <= 0) return 0;
-    dim3 grid((unsigned)(cdiv(mb, 4) < 2048 ? cdiv(mb, 4) : 2048)), block(256);
     RLPPO_CHECK_ARG(ld <= DISCRETE_LOSS_MAX_LD, "discrete head: padded width %ld too large", (long)ld);
-    if (mr && mr->mask) {  // [ABI 8] the masked instantiations, same grids
-        RLPPO_CHECK_ARG(mr->W == (A + 31) / 32 && mr->idx, "discrete head: mask_words=%d, n_actions=%d needs %d", mr->W, A, (A + 31) / 32);
-        if (ld <= 128) {
-            dim3 grid16((unsigned)(cdiv(mb, 16) < 2048 ? cdiv(mb, 16) : 2048));
-            hipLaunchKernelGGL(discrete_loss16_kernel<true>, grid16, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, *mr);
-        } else if (ld <= 512)
-            hipLaunchKernelGGL((discrete_loss_kernel<8, true>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, *mr);
-        else
-            hipLaunchKernelGGL((discrete_loss_kernel<32, true>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, *mr);
-        RLPPO_LAUNCH_CHECK();
-        return 0;
-    }
-    if (ld <= 128) {  // 16 lanes per row, DPP reductions
-        dim3 grid16((unsigned)(cdiv(mb, 16) < 2048 ? cdiv(mb, 16) : 2048));
-        hipLaunchKernelGGL(discrete_loss16_kernel<false>, grid16, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, MaskRows{});
-    } else if (ld <= 512)  // one wave per row
-        hipLaunchKernelGGL((discrete_loss_kernel<8>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, MaskRows{});
-    else
-        hipLaunchKernelGGL((discrete_loss_kernel<32>), grid, block, 0, st, logits, ld, A, actions, old_logp, adv, mb, cfg, stats, MaskRows{});
-    RLPPO_LAUNCH_CHECK();
-    return 0;
+    const bool masked = mr && mr->mask;
+    RLPPO_CHECK_ARG(!masked || (mr->W == (A + 31) / 32 && mr->idx), "discrete head: mask_words=%d, n_actions=%d needs %d", mr->W, A, (A + 31) / 32);
+    return dispatch_discrete((int)ld, masked, [&](auto epl, auto is_masked) {
+        typedef std::conditional_t<decltype(epl)::value == 2, Lanes16, WaveRow<decltype(epl)::value>> L;  // padded width <= 128: 16 lanes per row
+        hipLaunchKernelGGL((discrete_loss_kernel<L, decltype(is_masked)::value>), dim3(discrete_loss_grid(mb, L::ROWS)), dim3(256), 0, st, logits, ld, A, actions,
+                           old_logp, adv, mb, cfg, stats, masked ? *mr : MaskRows{});
+    });
 }
 
 // --------------------------------------------------------------------------------------------- gaussian
@@ -707,12 +624,7 @@ __global__ __launch_bounds__(256) void gaussian_loss_kernel(float *__restrict__ 
             lp = (float)lpd;
             ent = (float)entd;
         }
-        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
-        const float lr = lp - old;
-        const float ratio = expf(lr);
-        float smin;
-        const float w = surrogate_weight(ratio, adv, cfg, smin);
-        const float g_logp = cfg.mb_ratio * (-(adv * w * ratio) * cfg.inv_mb);
+        const Surrogate t = surrogate_row(lp, old_logp[row], advantages[row], cfg);
         const float g_ent = -cfg.mb_ratio * cfg.ent_coef * cfg.inv_mb / (float)k;  // d(-c_H * H)/d log sd
         // (no per-row arrays, so any k: the second pass re-reads mean / sd / x -- element j is overwritten only after its own reads)
 #pragma unroll 4
@@ -721,15 +633,12 @@ __global__ __launch_bounds__(256) void gaussian_loss_kernel(float *__restrict__ 
             const float sd = ys * cfg.var_m + cfg.var_b;
             const float d = xr[j] - ym;
             const float s2 = sd * sd;
-            const float d_mu = g_logp * d / s2;
-            const float d_sd = g_logp * (d * d / (s2 * sd) - 1.f / sd) + g_ent / sd;
+            const float d_mu = t.g_logp * d / s2;
+            const float d_sd = t.g_logp * (d * d / (s2 * sd) - 1.f / sd) + g_ent / sd;
             yr[j] = d_mu * (1.f - ym * ym);
             yr[k + j] = d_sd * cfg.var_m * (1.f - ys * ys);
         }
-        st[RLPPO_STAT_ENTROPY] = ent * cfg.inv_mb / (float)k;
-        st[RLPPO_STAT_KL] = ((ratio - 1.f) - lr) * cfg.inv_mb;
-        st[RLPPO_STAT_CLIPFRAC] = (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
-        st[RLPPO_STAT_PLOSS] = -smin * cfg.inv_mb;
+        surrogate_stats_add(st, ent * cfg.inv_mb / (float)k, t, cfg);
     }
     block_stats_add(stats, st, active, cfg, cfg.kl_slots);
 }
@@ -738,7 +647,7 @@ int launch_gaussian_loss(hipStream_t st, float *y, int64_t ld, int k, const floa
                          int64_t mb, const LossCfg &cfg, double *stats) {
     if (mb <= 0) return 0;
     RLPPO_CHECK_ARG(k >= 1, "gaussian head: action dim %d < 1", k);
-    hipLaunchKernelGGL(gaussian_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, y, ld, k, actions, old_logp, adv, mb,
+    hipLaunchKernelGGL(gaussian_loss_kernel, dim3(thread_per_row_grid(mb)), dim3(256), 0, st, y, ld, k, actions, old_logp, adv, mb,
                        cfg, stats);
     RLPPO_LAUNCH_CHECK();
     return 0;
@@ -831,26 +740,18 @@ __global__ __launch_bounds__(256) void multidiscrete_loss_kernel(float *__restri
             act[h] = (int)actions[row * 8 + h];
             lp += ls[s + act[h]];
         }
-        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
-        const float lr = lp - old;
-        const float ratio = expf(lr);
-        float smin;
-        const float w = surrogate_weight(ratio, adv, cfg, smin);
-        const float g_logp = cfg.mb_ratio * (-(adv * w * ratio) * cfg.inv_mb);
+        const Surrogate t = surrogate_row(lp, old_logp[row], advantages[row], cfg);
         const float g_ent = -cfg.mb_ratio * cfg.ent_coef * cfg.inv_mb;  // coefficient of d(entropy_row)/dz
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
             const int s = md_start(h), b = md_bins(h);
             for (int c = 0; c < b; ++c) {
                 const float onehot = (c == act[h]) ? 1.f : 0.f;
-                z[s + c] = g_logp * (onehot - ph[s + c]) + g_ent * (-ph[s + c] * (ls[s + c] + eh[h]));
+                z[s + c] = t.g_logp * (onehot - ph[s + c]) + g_ent * (-ph[s + c] * (ls[s + c] + eh[h]));
             }
         }
         for (int c = 21; c < ld; ++c) z[c] = 0.f;
-        st[RLPPO_STAT_ENTROPY] = ent * cfg.inv_mb;
-        st[RLPPO_STAT_KL] = ((ratio - 1.f) - lr) * cfg.inv_mb;
-        st[RLPPO_STAT_CLIPFRAC] = (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
-        st[RLPPO_STAT_PLOSS] = -smin * cfg.inv_mb;
+        surrogate_stats_add(st, ent * cfg.inv_mb, t, cfg);
     }
     block_stats_add(stats, st, active, cfg, cfg.kl_slots);
 }
@@ -858,7 +759,7 @@ __global__ __launch_bounds__(256) void multidiscrete_loss_kernel(float *__restri
 int launch_multidiscrete_loss(hipStream_t st, float *logits, int64_t ld, const float *actions, const float *old_logp, const float *adv,
                               int64_t mb, const LossCfg &cfg, double *stats) {
     if (mb <= 0) return 0;
-    hipLaunchKernelGGL(multidiscrete_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, logits, ld, actions, old_logp,
+    hipLaunchKernelGGL(multidiscrete_loss_kernel, dim3(thread_per_row_grid(mb)), dim3(256), 0, st, logits, ld, actions, old_logp,
                        adv, mb, cfg, stats);
     RLPPO_LAUNCH_CHECK();
     return 0;
@@ -988,12 +889,7 @@ __global__ __launch_bounds__(256) void multidiscrete_nvec_loss_kernel(float *__r
             s += b;
         }
         const float lp = (float)lpd, ent = (float)entd;
-        const float old = old_logp[row], adv = surrogate_adv(advantages[row], cfg);
-        const float lr = lp - old;
-        const float ratio = expf(lr);
-        float smin;
-        const float w = surrogate_weight(ratio, adv, cfg, smin);
-        const float g_logp = cfg.mb_ratio * (-(adv * w * ratio) * cfg.inv_mb);
+        const Surrogate t = surrogate_row(lp, old_logp[row], advantages[row], cfg);
         const float g_ent = -cfg.mb_ratio * cfg.ent_coef * cfg.inv_mb;  // coefficient of d(entropy_row)/dz
         s = 0;
         for (int h = 0; h < spec.H; ++h) {
@@ -1004,15 +900,12 @@ __global__ __launch_bounds__(256) void multidiscrete_nvec_loss_kernel(float *__r
             for (int c = 0; c < b; ++c) {
                 const float ls = z[s + c] - lse, ph = expf(ls);
                 const float onehot = (c == a) ? 1.f : 0.f;
-                z[s + c] = g_logp * (onehot - ph) + g_ent * (-ph * (ls + eh));
+                z[s + c] = t.g_logp * (onehot - ph) + g_ent * (-ph * (ls + eh));
             }
             s += b;
         }
         for (int c = spec.S; c < ld; ++c) z[c] = 0.f;
-        st[RLPPO_STAT_ENTROPY] = ent * cfg.inv_mb;
-        st[RLPPO_STAT_KL] = ((ratio - 1.f) - lr) * cfg.inv_mb;
-        st[RLPPO_STAT_CLIPFRAC] = (fabsf(ratio - 1.f) > cfg.clip ? 1.f : 0.f) * cfg.inv_mb;
-        st[RLPPO_STAT_PLOSS] = -smin * cfg.inv_mb;
+        surrogate_stats_add(st, ent * cfg.inv_mb, t, cfg);
     }
     block_stats_add(stats, st, active, cfg, cfg.kl_slots);
 }
@@ -1021,7 +914,7 @@ int launch_multidiscrete_nvec_loss(hipStream_t st, float *logits, int64_t ld, co
                                    int64_t mb, const LossCfg &cfg, double *stats, const MdSpec &spec) {
     if (mb <= 0) return 0;
     RLPPO_CHECK_ARG(spec.S <= ld, "multi-discrete head: %d logits in rows of %ld", spec.S, (long)ld);
-    hipLaunchKernelGGL(multidiscrete_nvec_loss_kernel, dim3((unsigned)cdiv(mb, 256)), dim3(256), 0, st, logits, ld, actions, old_logp, adv,
+    hipLaunchKernelGGL(multidiscrete_nvec_loss_kernel, dim3(thread_per_row_grid(mb)), dim3(256), 0, st, logits, ld, actions, old_logp, adv,
                        mb, cfg, stats, spec);
     RLPPO_LAUNCH_CHECK();
     return 0;

@@ -1,8 +1,11 @@
 """Every policy head on every update path: the Gaussian (ContinuousPolicy) and multi-discrete (MultiDiscreteFF) heads through the
 launch forms of rlppo_ppo_minibatch that the discrete head's tests pin (fused row-table gather, paired policy + critic launches,
 folded value head, stacked pairs, per-layer dW), across action widths and the edges of their loss kernels (csrc/heads.hip),
-with ring-resident experience, at the paired pass's default size, and through PPOLearner at an action width above 32.
+with ring-resident experience, at the paired pass's default size, and through PPOLearner at an action width above 32; and the
+discrete kernels' instantiations for more than 128 actions that the discrete head's own tests do not launch (section 7).
 Reference: float64 truth (tests/fp64_gate.py over oracle/ppo.py::minibatch_analytic)."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -358,3 +361,95 @@ def test_learn_continuous_40_actions_matches_float64(L):
         assert errs["hip"][0] <= max(1e-5, 1.5 * errs["ref"][0]), (s, errs)
         assert int((wp < 1e-4).sum() + (wv < 1e-4).sum()) <= 0.05 * (wp.size + wv.size)
         assert errs["hip"][1] <= 1.0 and errs["ref"][1] <= 1.0, (s, errs)
+
+
+# ------------------------------------------------------------------------------- 7. wide discrete rows, masked and from probabilities
+# The wave-per-row discrete kernels (csrc/heads.hip) hold 2 / 8 / 32 elements per lane for up to 128 / 512 / 2048 actions.  The widths
+# here are both ends of the 8 and of the 32 class, for the three forms no other test launches above 128 actions: sampling from given
+# probabilities, masked probabilities and the masked loss of the widest class.  5 rows = one block of 4 rows and a block with one.
+WIDE = [129, 512, 513, 2048]
+
+
+@pytest.mark.parametrize("A", WIDE)
+def test_categorical_select_wide_rows(L, A):
+    """tests/test_gpu_kernels.py::test_categorical_select_exact_at_scale above 128 categories: identical probabilities + identical
+    noise => identical indices, log-probability = log of the chosen one."""
+    torch.manual_seed(A)
+    n = 5
+    probs = torch.softmax(torch.randn(n, A) * 3, -1).clamp(1e-11, 1)
+    q = torch.empty(n, A).exponential_(1)
+    q[1, A - 1] = 1e-30   # the last column of a row wins: the row's last lane / element is a candidate
+    ref = torch.argmax(probs / q, -1)
+    act, lp = torch.empty(n, dtype=torch.int64, device="cuda"), torch.empty(n, device="cuda")
+    pd, qd = dev(probs), dev(q)
+    check(L, L.rlppo_categorical_select(stream(), P(pd), A, n, A, P(qd), P(act), P(lp)))
+    assert torch.equal(act.cpu(), ref) and int(act[1]) == A - 1
+    assert torch.equal(lp, torch.log(pd.gather(1, act.view(-1, 1))).view(-1))
+
+
+@pytest.mark.parametrize("A", WIDE)
+def test_masked_discrete_probs_wide_rows(L, A):
+    """rlppo_discrete_probs with an action mask above 128 actions, against the float64 masked softmax with the allowance of
+    tests/test_gpu_action_mask.py::check_sampling: invalid actions read exactly 0 with and without the clamp, a row without a valid
+    action is all-valid, and the flat arg-max is exact given the library's own probabilities (never an invalid action)."""
+    import test_gpu_action_mask as M
+    from rlgym_ppo_amd import _native as N
+    from rlgym_ppo_amd.util import action_mask as AM
+    rs = np.random.RandomState(A)
+    n, d = 5, 40
+    params = [(torch.as_tensor(rs.randn(A, d).astype(np.float32)), torch.as_tensor(rs.randn(A).astype(np.float32) * 3))]
+    net = Net(L, params)
+    obs = rs.randn(n, d).astype(np.float32)
+    m = M.rand_mask(rs, n, A)
+    z = M.logits64(params, obs)
+    m[np.arange(n), z.argmax(1)] = False   # every row's largest logit is masked out: the arg-max must not take it
+    m[2] = False                           # no valid action: all-valid
+    eff = m.copy()
+    eff[~m.any(1)] = True
+    rows, w = net.pad(obs), net.ws(n)
+    words = AM.pack(torch.from_numpy(m).cuda(), A, "cuda")
+    opts = N.ActOpts()
+    opts.action_mask, opts.mask_words = words.data_ptr(), words.shape[1]
+    soft, clamped = torch.full((n, A), float("nan"), device="cuda"), torch.full((n, A), float("nan"), device="cuda")
+    best = torch.empty(1, dtype=torch.int64, device="cuda")
+    check(L, L.rlppo_discrete_probs(stream(), net.dims_c, net.nl, P(net.packed), P(rows), net.ld_in, n, 0, P(soft), A, None, P(w), w.numel(),
+                                    ctypes.byref(opts)))
+    check(L, L.rlppo_discrete_probs(stream(), net.dims_c, net.nl, P(net.packed), P(rows), net.ld_in, n, 1, P(clamped), A, P(best), P(w),
+                                    w.numel(), ctypes.byref(opts)))
+    want = M.softmax64(z, eff)
+    got = soft.cpu().numpy()
+    assert np.isfinite(got).all() and (got[~eff] == 0.0).all() and (clamped.cpu().numpy()[~eff] == 0.0).all()
+    err = np.abs(got - want)[eff].max() / want.max()
+    print(f"[masked probs] A={A}: max|p - p64|/max p64 = {err:.2e}")
+    assert err <= 1e-5, err
+    valid = torch.from_numpy(eff).cuda()
+    assert torch.equal(clamped, torch.where(valid, soft.clamp(min=1e-11, max=1), torch.zeros_like(soft)))
+    assert int(best) == int(clamped.cpu().numpy().argmax()) and eff.reshape(-1)[int(best)]
+
+
+@pytest.mark.parametrize("A", [513, 2048])
+def test_masked_loss_widest_rows(L, A):
+    """The masked discrete loss above 512 padded columns (32 elements per lane), which tests/test_gpu_action_mask.py reaches at 90 and
+    200 actions only: 5 rows through rlppo_ppo_minibatch against that module's float64 gate.  Row 1 has no valid action (all-valid);
+    row 3's stored action is masked out (the literal chain: pc = 1e-11, no gradient through the clamp); ratios on both sides of the
+    clip interval and inside it."""
+    import test_gpu_action_mask as M
+    torch.manual_seed(A)
+    rs = np.random.RandomState(A)
+    n = 5
+    pol, val = nets.init_mlp(D, (64,), A), nets.init_mlp(D, (64,), 1)
+    obs = np.clip(rs.randn(n, D), -5, 5).astype(np.float32)
+    m = M.rand_mask(rs, n, A)
+    m[1] = False
+    eff = m.copy()
+    eff[1] = True
+    acts = np.array([rs.choice(np.flatnonzero(r)) for r in eff], np.float32)
+    m[3, int(acts[3])] = eff[3, int(acts[3])] = False
+    p = np.clip(M.softmax64(M.logits64(pol, obs), eff), 1e-11, 1.0)
+    logp = np.log(p[np.arange(n), acts.astype(int)])
+    assert p[3, int(acts[3])] == 1e-11
+    old = (logp - np.array([0.05, -0.3, 0.3, -0.05, 0.1])).astype(np.float32)
+    pr = dict(obs=obs, mask=m, acts=acts, old=old, adv=rs.randn(n).astype(np.float32), tgt=rs.randn(n).astype(np.float32), redrawn=0,
+              outside=0.4)
+    got = M.run_minibatch(L, pol, val, dict(pr, mask=torch.from_numpy(m).cuda()), np.array([4, 0, 3, 1, 2]))
+    M.masked_gate(L, pol, val, dict(pr, mask=eff), got, f"{D} -> (64,) -> {A}, 5 rows")

@@ -1,6 +1,6 @@
 """Generality of the kernel paths: odd layer widths (padding to 32 / 64 / 96 / 128 / k*128), one hidden layer, wide
-discrete heads (the 16-lane kernel up to its full 128 columns, EPL = 8 and 32 register variants of the wave-per-row kernels up to
-2048 columns, an argument error beyond), tiny and ragged batches, empty calls."""
+discrete heads (the 16-lane row layout of the loss kernel up to its full 128 columns, the wave-per-row layouts with 8 and 32 elements
+per lane up to 2048 columns, an argument error beyond), tiny and ragged batches, empty calls."""
 import ctypes
 
 import numpy as np
@@ -46,7 +46,7 @@ def test_discrete_odd_shapes(L, d, hidden, A, n, mb):
 
 
 def test_discrete_head_wider_than_the_loss_kernel_is_an_argument_error(L):
-    """2049 actions pad to 2176 outputs, beyond the 2048 columns of discrete_loss_kernel<32>: the minibatch call reports it (with the
+    """2049 actions pad to 2176 outputs, beyond the 2048 columns of discrete_loss_kernel<WaveRow<32>>: the minibatch call reports it (with the
     library's error text) before anything is enqueued: the call never reaches its pass."""
     torch.manual_seed(8)
     pol, val = nets.init_mlp(32, (64,), 2049), nets.init_mlp(32, (64,), 1)
