@@ -39,7 +39,32 @@ extern "C" {
 #define RLPPO_MAX_LAYERS 16
 /* [nvec] limits of a multi-discrete action space MultiDiscrete(nvec) (rlppo_multidiscrete_act_nvec, rlppo_ppo_minibatch_nvec):
  * 1 <= heads <= RLPPO_MD_MAX_HEADS, 1 <= nvec[h] <= RLPPO_MD_MAX_BINS, sum of nvec <= RLPPO_MD_MAX_LOGITS.  Anything beyond is
- * RLPPO_ERR_ARG with a message naming the limit, before any launch. */
+ * RLPPO_ERR_ARG with a message naming the limit, before any launch.
+ *
+ * [nvec, masked] Invalid-action masking of the multi-discrete head: rlppo_multidiscrete_act_nvec_masked (an added entry point, as
+ * the _nvec ones were) and rlppo_ppo_minibatch_nvec with md_nvec given; no new struct field, the ABI version stays 8.  A mask row has S = sum(nvec) bits, ONE PER LOGIT, in the encoding of rlppo_act_opts.action_mask: W = ceil(S / 32)
+ * words per row, bit c % 32 of word c / 32 set = logit c valid, bits at and beyond S ignored.  Head h owns bits [s_h, s_h + b_h);
+ * with V_h its valid set:
+ *   distribution  head h is Categorical(logits = z_h with -inf outside V_h): MultiDiscreteRolv's construction with more -inf than the
+ *                 padding alone;
+ *   sampling      the first arg-max over c in V_h of softmax_V(z_h)_c / noise_q[(row * H + h) * B + c]; the noise keeps its
+ *                 [n * H][B] shape and the noise of invalid bins is never read;
+ *   loss terms    log p = sum_h (z[a_h] - lse_V(z_h)), entropy = sum_h -sum_{c in V_h} p_c log p_c; the row sums are taken in double
+ *                 and rounded once, as without a mask;
+ *   gradient      dL/dz is exactly 0 on every invalid logit and on the padded columns >= S; on valid logits the unmasked
+ *                 expression with p, lse and the head's entropy taken over V_h;
+ *   one valid bin such a head contributes log-probability 0, entropy 0 and a zero gradient, as a head of one bin does;
+ *   no valid bin  a caller error: hosts reject such a row before launch; inside the kernels that head counts as all-valid;
+ *   a stored action its own mask marks invalid (a caller error): its term is the literal z[a] - lse_V, its one-hot falls on an
+ *                 invalid column and is dropped; everything stays finite;
+ *   no mask       the library as it is, launch for launch; an all-valid mask gives the unmasked general kernels' results bit for
+ *                 bit (the maximum and the sums run over the valid bins in c order);
+ *   fixed bins    rlppo_multidiscrete_act, and rlppo_ppo_minibatch / _nvec with md_nvec == NULL, refuse a mask (RLPPO_ERR_ARG): a
+ *                 masked call on the reference's bins gives md_nvec = {3, 3, 3, 3, 3, 2, 2, 2} and runs the general kernels;
+ *   act options   a mask in rlppo_act_opts stays refused by every multi-discrete rollout entry point, rlppo_multidiscrete_act_nvec
+ *                 included (the text callers know): the masked step takes its mask as an argument of its own entry point.
+ * A wrong mask_words is RLPPO_ERR_ARG naming the field and the needed count, before any HIP call.  A head has at most 64 bins, so
+ * the kernels assemble V_h as one 64-bit value from the two or three words it touches (no per-row array, no scratch). */
 #define RLPPO_MD_MAX_HEADS 64
 #define RLPPO_MD_MAX_BINS 64
 #define RLPPO_MD_MAX_LOGITS 512
@@ -130,7 +155,7 @@ typedef struct rlppo_act_opts {
     uint32_t *done_words;
     uint32_t *noise_ctl;
     /* [ABI 8] invalid-action masking (discrete head: rlppo_discrete_act / _step / _probs; any other entry point answers
-     * RLPPO_ERR_ARG).  action_mask: DEVICE [n][mask_words] words, mask_words == ceil(n_actions / 32), bit c % 32 of word c / 32 set =
+     * RLPPO_ERR_ARG -- the multi-discrete head's masked step is rlppo_multidiscrete_act_nvec_masked, "[nvec, masked]" above).  action_mask: DEVICE [n][mask_words] words, mask_words == ceil(n_actions / 32), bit c % 32 of word c / 32 set =
      * action c is valid in that row; bits at and beyond n_actions are ignored; NULL = no mask (the call is the unmasked one, launch
      * for launch).  Semantics: an invalid action's logit is -inf (what the padded columns c >= n_actions always were), so
      * p = softmax(z') is exactly 0 on it; pc = clamp(p, 1e-11, 1) on valid actions; action = first arg-max over VALID c of
@@ -248,6 +273,14 @@ int rlppo_multidiscrete_act_nvec(void *stream, const int32_t *dims, int32_t n_la
                                  const float *obs, int64_t ld_obs, int64_t n, const float *noise_q,
                                  int64_t *actions, float *logp, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts,
                                  const int32_t *nvec, int32_t n_heads);
+/* [nvec, masked] The same step under an action mask ("[nvec, masked]" above): action_mask DEVICE [n][mask_words] words, one bit per
+ * logit, mask_words == ceil(sum(nvec) / 32) (otherwise RLPPO_ERR_ARG naming mask_words and the needed count, before any HIP call);
+ * row `row` of the mask belongs to row `row` of obs.  action_mask == NULL is RLPPO_ERR_ARG.  Everything else, opts included, as
+ * rlppo_multidiscrete_act_nvec; an all-valid mask gives that entry point's results bit for bit. */
+int rlppo_multidiscrete_act_nvec_masked(void *stream, const int32_t *dims, int32_t n_layers, const float *packed,
+                                        const float *obs, int64_t ld_obs, int64_t n, const float *noise_q,
+                                        int64_t *actions, float *logp, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts,
+                                        const int32_t *nvec, int32_t n_heads, const uint32_t *action_mask, int32_t mask_words);
 
 /* ---------------------------------------------------------------------------------------------- GAE */
 
@@ -345,7 +378,9 @@ typedef struct rlppo_minibatch_args {
                                      launch, [1] <- mb_ratio, [2 + w] <- workgroup w's sum of the RLPPO_STAT_KL term (read by
                                      rlppo_kl_gate); NULL = not armed */
     const uint32_t *stop_word;    /* device; once non-zero, the pass adds nothing to `stats`; NULL = never */
-    /* [ABI 8] invalid-action masking, discrete head only (another head: RLPPO_ERR_ARG).  action_mask: [N][mask_words] words, a
+    /* [ABI 8] invalid-action masking: the discrete head, and the multi-discrete head through rlppo_ppo_minibatch_nvec with md_nvec
+     * given (one bit per logit, mask_words == ceil(sum(md_nvec) / 32), in every pass form and update precision: "[nvec, masked]"
+     * above); another head, or the multi-discrete head without md_nvec: RLPPO_ERR_ARG.  action_mask: [N][mask_words] words, a
      * buffer field like `actions` (row idx[r] through the ring map), mask_words == ceil(n_actions / 32), encoding as in
      * rlppo_act_opts; NULL = off (the parent's launches).  The loss kernel reads the words ITSELF through idx / ring_base / ring_cap --
      * they do not travel with the minibatch gather, so the workspace of a pass (rlppo_minibatch_workspace_bytes) and its gather
@@ -383,7 +418,8 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *args);
  * dL/dz per head segment as the reference's head forms it, exactly 0 in the padded columns >= sum(md_nvec).  A head of one bin
  * contributes log-probability 0, entropy 0 and a zero gradient.  A stored index outside [0, md_nvec[h]) is a caller error: it is
  * clamped into the head's range before it indexes anything (the row trains on the nearest valid action; no address outside the row
- * is formed).  The workspace of a pass does not depend on md_nvec. */
+ * is formed).  The workspace of a pass does not depend on md_nvec.  With md_nvec the pass takes args->action_mask / mask_words
+ * ("[nvec, masked]" above): the loss kernel reads row idx[r]'s words through the ring map itself, as the discrete head's does. */
 int rlppo_ppo_minibatch_nvec(void *stream, const rlppo_minibatch_args *args, const int32_t *md_nvec, int32_t md_heads);
 
 /* Orders `stream` after every minibatch enqueued through non-zero slots since the last join (call it before the

@@ -125,6 +125,8 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
     "rlppo_multidiscrete_act_nvec": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_size_t, _PACT, _P32, c_int32]),
+    "rlppo_multidiscrete_act_nvec_masked": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                                      c_void_p, c_void_p, c_void_p, c_size_t, _PACT, _P32, c_int32, c_void_p, c_int32]),
     "rlppo_act_done_words": (c_int64, [c_int64]),
     "rlppo_host_wait_words": (c_int32, [c_void_p, c_int64, c_uint32, c_int64]),
     "rlppo_discrete_step_one_launch": (c_int32, [_P32, c_int32, c_int64, _PACT]),

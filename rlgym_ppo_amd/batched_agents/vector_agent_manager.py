@@ -18,9 +18,10 @@ is its own trajectory stream (tests/test_gpu_vector_rollout.py compares with a n
 
 Environment interface: `reset() -> obs [n, d]`; `step(actions [n, k]) -> (obs [n, d], rewards [n], dones [n],
 truncated [n], info)` with auto-reset of finished agents; `observation_space.shape`, `action_space` as in the reference.
-Optional (the sb3-contrib convention, discrete policy only): `action_masks() -> [n, n_actions]` booleans for the observation
-the agents act on next, called after `reset()` and after every `step()`; the policy then samples valid actions only and the
-masks leave the collect trajectory-major as `self.action_mask_rows` (next to `value_input_rows`).
+Optional (the sb3-contrib convention; discrete and multi-discrete policies): `action_masks() -> [n, n_actions]` booleans for the
+observation the agents act on next ([n, sum(bins)] for a multi-discrete policy: one entry per bin of every component), called
+after `reset()` and after every `step()`; the policy then samples valid actions only and the masks leave the collect
+trajectory-major as `self.action_mask_rows` (next to `value_input_rows`).
 Optional, used with `bootstrap_truncated` (Learner(gae_bootstrap_truncated=True)) only: `info["final_observation"]`, float
 [n, d], whose rows are meaningful where `truncated` is set and `done` is not -- the observation the episode ended on, which
 the auto-reset has replaced in `obs`.  Those rows are standardised like that step's `obs`, kept out of the running
@@ -71,16 +72,38 @@ class VectorAgentManager(object):
         fn = getattr(self.env, "action_masks", None)
         if fn is None:
             return None
+        width, heads = self._mask_layout()
+        m = np.asarray(fn())
+        if m.ndim == 1:   # a one-agent environment may answer [n_actions]
+            m = m.reshape(1, -1)
+        if m.ndim != 2 or m.shape[1] != width:
+            raise ValueError(f"the environment's action_masks() has shape {tuple(m.shape)}: its width must be {width}, the policy's "
+                             + ("logit count sum(bins) (one entry per bin of every component)" if heads is not None else "action count"))
+        return AM.pack(m, width, self.policy.arena.device, heads=heads)
+
+    def _mask_layout(self):
+        """(entries of a mask row, the multi-discrete head's bins or None): n_actions of the discrete head; one entry per logit,
+        sum(bins), of the multi-discrete head.  Worked out once per policy object (every rollout step asks)."""
+        cached = getattr(self, "_mask_layout_cache", None)
+        if cached is not None and cached[0] is self.policy:
+            return cached[1]
+        self._mask_layout_cache = (self.policy, self._mask_layout_of_policy())
+        return self._mask_layout_cache[1]
+
+    def _mask_layout_of_policy(self):
         from ..ppo.discrete_policy import DiscreteFF
-        if not isinstance(self.policy, DiscreteFF):
-            raise ValueError("the environment offers action_masks(): invalid-action masking is an option of the discrete head "
-                             f"(DiscreteFF), not of {type(self.policy).__name__}")
-        return AM.pack(np.asarray(fn()), self.policy.n_actions, self.policy.arena.device)
+        from ..ppo.multi_discrete_policy import MultiDiscreteFF
+        if isinstance(self.policy, DiscreteFF):
+            return self.policy.n_actions, None
+        if isinstance(self.policy, MultiDiscreteFF):
+            return self.policy.n_logits, self.policy.splits
+        raise ValueError("the environment offers action_masks(): invalid-action masking is an option of the discrete head "
+                         f"(DiscreteFF) and of the multi-discrete head (MultiDiscreteFF), not of {type(self.policy).__name__}")
 
     def _masks_out(self, M, na, T):
         """Time-major words [T, na, W] -> self.action_mask_rows, trajectory-major (row a * T + t)."""
         self.action_mask_rows = None if M is None else AM.Packed(M.transpose(0, 1).reshape(na * T, M.shape[2]).contiguous(),
-                                                                 self.policy.n_actions)
+                                                                 self._mask_layout()[0])
 
     @property
     def action_masks(self):
@@ -283,7 +306,7 @@ class VectorAgentManager(object):
                 if M is None:
                     M = torch.empty((T, na, mask.shape[1]), dtype=torch.int32, device=dev)
                 M[t].copy_(mask)
-                a_dev, lp_dev = self.policy.act_padded(rows, action_mask=AM.Packed(M[t], self.policy.n_actions))
+                a_dev, lp_dev = self.policy.act_padded(rows, action_mask=AM.Packed(M[t], self._mask_layout()[0]))
             else:
                 a_dev, lp_dev = self.policy.act_padded(rows)
             if acts is None:

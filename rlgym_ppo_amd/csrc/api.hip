@@ -611,28 +611,51 @@ int rlppo_multidiscrete_act(void *stream, const int32_t *dims, int32_t n_layers,
     return launch_multidiscrete_sample((hipStream_t)stream, o, ldo, n, noise_q, actions, logp, cx.done, cx.done_value);
 }
 
-// [nvec] the same step for any nvec: the general sampling kernel, always (the fixed one stays behind rlppo_multidiscrete_act)
-int rlppo_multidiscrete_act_nvec(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
-                                 int64_t ld_obs, int64_t n, const float *noise_q, int64_t *actions, float *logp, void *workspace,
-                                 size_t ws_bytes, const rlppo_act_opts *opts, const int32_t *nvec, int32_t n_heads) {
+// [nvec] the same step for any nvec: the general sampling kernel, always (the fixed one stays behind rlppo_multidiscrete_act).
+// [nvec, masked] `mask` (one bit per logit, ceil(sum(nvec) / 32) words per row) is rlppo_multidiscrete_act_nvec_masked's argument:
+// a mask in rlppo_act_opts stays refused by both entry points, with the text it always had.
+static int multidiscrete_act_nvec(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
+                                  int64_t ld_obs, int64_t n, const float *noise_q, int64_t *actions, float *logp, void *workspace,
+                                  size_t ws_bytes, const rlppo_act_opts *opts, const int32_t *nvec, int32_t n_heads, const char *who,
+                                  const char *opts_for, const unsigned *mask, int mask_words) {
     NetLayout net;
     int rc = make_layout(dims, n_layers, &net);
     if (rc) return rc;
     ActCtx cx;
-    rc = act_ctx(opts, &cx, false, "the multi-discrete head (rlppo_multidiscrete_act_nvec)");
+    rc = act_ctx(opts, &cx, false, opts_for);
     if (rc) return rc;
     MdSpec spec;
-    rc = md_spec_make(nvec, n_heads, "multidiscrete_act_nvec", &spec);
+    rc = md_spec_make(nvec, n_heads, who, &spec);
     if (rc) return rc;
-    RLPPO_CHECK_ARG(dims[n_layers] == spec.S, "multidiscrete_act_nvec: output width %d, but nvec sums to %d", dims[n_layers], spec.S);
+    RLPPO_CHECK_ARG(dims[n_layers] == spec.S, "%s: output width %d, but nvec sums to %d", who, dims[n_layers], spec.S);
+    RLPPO_CHECK_ARG(!mask || mask_words == (spec.S + 31) / 32, "%s: mask_words=%d, but %d logits need %d words per row", who, mask_words, spec.S,
+                    (spec.S + 31) / 32);
     if (n == 0) return 0;
-    RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_q && actions && logp && workspace, "multidiscrete_act_nvec: bad argument");
+    RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_q && actions && logp && workspace, "%s: bad argument", who);
     const float *o;
     int64_t ldo;
     rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
     if (rc) return rc;
     ++g_cnt_md_nvec;
-    return launch_multidiscrete_nvec_sample((hipStream_t)stream, o, ldo, n, noise_q, actions, logp, spec, cx.done, cx.done_value);
+    return launch_multidiscrete_nvec_sample((hipStream_t)stream, o, ldo, n, noise_q, actions, logp, spec, cx.done, cx.done_value, mask, mask_words);
+}
+
+int rlppo_multidiscrete_act_nvec(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
+                                 int64_t ld_obs, int64_t n, const float *noise_q, int64_t *actions, float *logp, void *workspace,
+                                 size_t ws_bytes, const rlppo_act_opts *opts, const int32_t *nvec, int32_t n_heads) {
+    return multidiscrete_act_nvec(stream, dims, n_layers, packed, obs, ld_obs, n, noise_q, actions, logp, workspace, ws_bytes, opts, nvec, n_heads,
+                                  "multidiscrete_act_nvec", "the multi-discrete head (rlppo_multidiscrete_act_nvec)", nullptr, 0);
+}
+
+int rlppo_multidiscrete_act_nvec_masked(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
+                                        int64_t ld_obs, int64_t n, const float *noise_q, int64_t *actions, float *logp, void *workspace,
+                                        size_t ws_bytes, const rlppo_act_opts *opts, const int32_t *nvec, int32_t n_heads,
+                                        const uint32_t *action_mask, int32_t mask_words) {
+    RLPPO_CHECK_ARG(action_mask != nullptr, "multidiscrete_act_nvec_masked: action_mask is NULL (the unmasked step is rlppo_multidiscrete_act_nvec)");
+    return multidiscrete_act_nvec(stream, dims, n_layers, packed, obs, ld_obs, n, noise_q, actions, logp, workspace, ws_bytes, opts, nvec, n_heads,
+                                  "multidiscrete_act_nvec_masked",
+                                  "the multi-discrete head (rlppo_multidiscrete_act_nvec_masked takes its mask as an argument)", action_mask,
+                                  mask_words);
 }
 
 int64_t rlppo_act_done_words(int64_t n) { return n > 0 ? cdiv(n, 16) : 0; }
@@ -1115,20 +1138,21 @@ static int policy_loss(hipStream_t st, const Pass &p) {
     const int last = p.pol.n_layers - 1;
     const LayerLayout &L = p.pol.L[last];
     const WsPlan &w = p.w;
+    MaskRows mr;  // [ABI 8] the masked loss reads the buffer's mask rows through idx and the ring map itself
+    mr.mask = a.action_mask;
+    mr.W = a.mask_words;
+    mr.idx = a.idx;
+    mr.ring_base = p.ring_base;
+    mr.ring_cap = p.ring_cap;
     if (a.head == RLPPO_HEAD_DISCRETE) {
-        MaskRows mr;  // [ABI 8] the masked loss reads the buffer's mask rows through idx and the ring map itself
-        mr.mask = a.action_mask;
-        mr.W = a.mask_words;
-        mr.idx = a.idx;
-        mr.ring_base = p.ring_base;
-        mr.ring_cap = p.ring_cap;
         return launch_discrete_loss(st, w.pol.act[last], L.pout, L.out, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, a.action_mask ? &mr : nullptr);
     }
     if (a.head == RLPPO_HEAD_GAUSSIAN)
         return launch_gaussian_loss(st, w.pol.act[last], L.pout, L.out / 2, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
     if (p.md_general) {  // [nvec] any nvec: the general kernel, also on the reference's bins
         ++g_cnt_md_nvec;
-        return launch_multidiscrete_nvec_loss(st, w.pol.act[last], L.pout, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, p.md);
+        return launch_multidiscrete_nvec_loss(st, w.pol.act[last], L.pout, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, p.md,
+                                              a.action_mask ? &mr : nullptr);
     }
     return launch_multidiscrete_loss(st, w.pol.act[last], L.pout, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
 }
@@ -1353,9 +1377,11 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     const int n_out = pol.L[pol.n_layers - 1].out;
     RLPPO_CHECK_ARG(a->head == RLPPO_HEAD_DISCRETE || a->head == RLPPO_HEAD_GAUSSIAN || a->head == RLPPO_HEAD_MULTIDISCRETE,
                     "ppo_minibatch: unknown head %d", a->head);
-    // [ABI 8] action masks: the discrete head alone, ceil(A / 32) words per buffer row
-    RLPPO_CHECK_ARG(!a->action_mask || a->head == RLPPO_HEAD_DISCRETE, "ppo_minibatch: action_mask is an option of the discrete head, not of the %s head",
-                    a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : "multi-discrete");
+    // [ABI 8] action masks: the discrete head, and [nvec, masked] the multi-discrete head's general kernels (md_nvec given, also for
+    // the reference's bins): one bit per output, ceil(n_out / 32) words per buffer row
+    RLPPO_CHECK_ARG(!a->action_mask || a->head == RLPPO_HEAD_DISCRETE || (a->head == RLPPO_HEAD_MULTIDISCRETE && md_nvec),
+                    "ppo_minibatch: action_mask is an option of the discrete head, not of the %s head",
+                    a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : "multi-discrete (without md_nvec: the fixed-bin kernels take no mask)");
     RLPPO_CHECK_ARG(!a->action_mask || a->mask_words == (n_out + 31) / 32, "ppo_minibatch: mask_words=%d, but n_actions=%d needs %d words per row",
                     a->mask_words, n_out, (n_out + 31) / 32);
     if (a->head == RLPPO_HEAD_DISCRETE) {

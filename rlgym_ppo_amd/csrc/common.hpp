@@ -248,10 +248,13 @@ struct MdSpec {
     unsigned char b[RLPPO_MD_MAX_HEADS];
 };
 int md_spec_make(const int32_t *nvec, int n_heads, const char *who, MdSpec *spec);
+// [nvec, masked] mask (optional): one bit per LOGIT, W = ceil(S / 32) words per row -- the call's rows for the sampling kernel, the
+// buffer's rows through MaskRows for the loss kernel; the MASKED instantiations run only when one is given
 int launch_multidiscrete_nvec_sample(hipStream_t, const float *, int64_t, int64_t, const float *, int64_t *, float *, const MdSpec &,
-                                     unsigned *done_words = nullptr, unsigned done_value = 0);
+                                     unsigned *done_words = nullptr, unsigned done_value = 0, const unsigned *mask = nullptr,
+                                     int mask_words = 0);
 int launch_multidiscrete_nvec_loss(hipStream_t, float *, int64_t, const float *, const float *, const float *, int64_t, const LossCfg &, double *,
-                                   const MdSpec &);
+                                   const MdSpec &, const MaskRows *mask_rows = nullptr);
 
 // fused_act.hip: the whole rollout step of the discrete policy in one launch ----------------
 struct FusedActIO {

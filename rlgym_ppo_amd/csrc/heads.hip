@@ -789,33 +789,75 @@ int md_spec_make(const int32_t *nvec, int n_heads, const char *who, MdSpec *spec
     return 0;
 }
 
+// [nvec, masked] Invalid-action masking of the general kernels (template <bool MASKED>; the unmasked instantiations keep the
+// arithmetic and its order as they were -- the generated code of the sampling kernel differs by one instruction: DESIGN.md, 8b).  A mask row has W = ceil(S / 32) words, one bit per logit (bit c % 32 of word c / 32 set = logit c valid, bits at and
+// beyond S ignored); head h owns bits [s_h, s_h + b_h).  A head has at most 64 bins, so its valid set V_h is ONE 64-bit value
+// assembled from the two or three words it touches (md_head_valid) -- no per-row array.  Invalid bins are -inf: no candidate of the
+// maximum, the sums or the arg-max, gradient exactly 0, noise never read; the maximum and the sums run over the valid bins in c
+// order, so an all-valid mask gives the unmasked results bit for bit.  A head without a valid bin counts as all-valid.
+__device__ __forceinline__ unsigned long long md_head_valid(const unsigned *__restrict__ words, int s, int b) {
+    const int w0 = s >> 5, sh = s & 31, wl = (s + b - 1) >> 5;  // (wl <= (S - 1) / 32 < W: every word read lies inside the row)
+    unsigned long long lo = words[w0];
+    if (wl > w0) lo |= (unsigned long long)words[w0 + 1] << 32;
+    unsigned long long v = lo >> sh;
+    if (wl > w0 + 1) v |= (unsigned long long)words[w0 + 2] << (64 - sh);  // (three words: sh + b > 64 with b <= 64, so sh >= 1)
+    const unsigned long long all = b >= 64 ? ~0ull : (1ull << b) - 1ull;
+    v &= all;
+    return v ? v : all;
+}
+__device__ __forceinline__ bool md_in(unsigned long long valid, int c) { return ((valid >> c) & 1ull) != 0; }
+
+// maximum of one head's logits (running maximum from z[0]; MASKED: over the valid bins, in c order)
+template <bool MASKED>
+__device__ __forceinline__ float md_head_max(const float *z, int b, unsigned long long valid) {
+    if (!MASKED) {
+        float mx = z[0];
+        for (int c = 1; c < b; ++c) mx = fmaxf(mx, z[c]);
+        return mx;
+    }
+    float mx = -INFINITY;
+    for (int c = 0; c < b; ++c)
+        if (md_in(valid, c)) mx = fmaxf(mx, z[c]);
+    return mx;
+}
+// sum over the head's (valid) bins of exp(z - mx), in c order
+template <bool MASKED>
+__device__ __forceinline__ float md_head_sumexp(const float *z, int b, float mx, unsigned long long valid) {
+    float sum = 0.f;
+    for (int c = 0; c < b; ++c)
+        if (!MASKED || md_in(valid, c)) sum += expf(z[c] - mx);
+    return sum;
+}
+
 // Categorical(logits=[n, H, B]).sample() == first arg-max over c < b_h of softmax(z_h)_c / q[(row H + h) B + c]: the padded slots
 // c >= b_h (p = 0 in the reference) are no candidates and their noise is never read.  The arithmetic of a head is that of
 // multidiscrete_sample_kernel (the exponentials are formed twice instead of being kept); the row's log-probability -- up to 64 float
 // terms -- is summed in double and rounded once, as the Gaussian head does above FLOAT_SUM_K terms (a serial float sum of 64 terms
-// near -44 alone drifts by ~1e-5).
+// near -44 alone drifts by ~1e-5).  MASKED: mask[n][W], row `row` of the call's mask.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void multidiscrete_nvec_sample_kernel(const float *__restrict__ logits, int64_t ld, int64_t n,
                                                                          const float *__restrict__ noise, int64_t *__restrict__ actions,
                                                                          float *__restrict__ logp, MdSpec spec, unsigned *done_words,
-                                                                         unsigned done_value) {
+                                                                         unsigned done_value, const unsigned *__restrict__ mask, int W) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     // (one barrier site for the whole block, as in multidiscrete_sample_kernel: a wave whose lanes split at `row < n` must not
     // arrive at the barrier of block_done_words twice)
     if (row < n) {
         const float *z = logits + row * ld;
         const float *q = noise + row * spec.H * spec.B;
+        const unsigned *words = MASKED ? mask + row * W : nullptr;
         double lp = 0.0;
         int s = 0;
         for (int h = 0; h < spec.H; ++h) {
             const int b = spec.b[h];
-            float mx = z[s];
-            for (int c = 1; c < b; ++c) mx = fmaxf(mx, z[s + c]);
-            float sum = 0.f;
-            for (int c = 0; c < b; ++c) sum += expf(z[s + c] - mx);
+            const unsigned long long valid = MASKED ? md_head_valid(words, s, b) : 0ull;
+            const float mx = md_head_max<MASKED>(z + s, b, valid);
+            const float sum = md_head_sumexp<MASKED>(z + s, b, mx, valid);
             const float lse = mx + logf(sum);
             float best = -INFINITY;
-            int bi = 0;
+            int bi = MASKED ? __builtin_ctzll(valid) : 0;  // (never kept: a valid bin's score is > -inf unless it is NaN)
             for (int c = 0; c < b; ++c) {
+                if (MASKED && !md_in(valid, c)) continue;
                 const float v = (expf(z[s + c] - mx) / sum) / q[c];
                 if (v > best) {
                     best = v;
@@ -833,27 +875,33 @@ __global__ __launch_bounds__(256) void multidiscrete_nvec_sample_kernel(const fl
 }
 
 int launch_multidiscrete_nvec_sample(hipStream_t st, const float *logits, int64_t ld, int64_t n, const float *noise, int64_t *actions,
-                                     float *logp, const MdSpec &spec, unsigned *done_words, unsigned done_value) {
+                                     float *logp, const MdSpec &spec, unsigned *done_words, unsigned done_value, const unsigned *mask,
+                                     int W) {
     if (n <= 0) return 0;
     RLPPO_CHECK_ARG(spec.S <= ld, "multi-discrete head: %d logits in rows of %ld", spec.S, (long)ld);
-    hipLaunchKernelGGL(multidiscrete_nvec_sample_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, logits, ld, n, noise, actions,
-                       logp, spec, done_words, done_value);
+    RLPPO_CHECK_ARG(!mask || W == (spec.S + 31) / 32, "multi-discrete head: mask_words=%d, %d logits need %d", W, spec.S, (spec.S + 31) / 32);
+    if (mask)
+        hipLaunchKernelGGL(multidiscrete_nvec_sample_kernel<true>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, logits, ld, n, noise,
+                           actions, logp, spec, done_words, done_value, mask, W);
+    else
+        hipLaunchKernelGGL(multidiscrete_nvec_sample_kernel<false>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, logits, ld, n, noise,
+                           actions, logp, spec, done_words, done_value, nullptr, 0);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }
 
 // log-sum-exp of one head's logits (the chain of multidiscrete_loss_kernel: running maximum from z[0], sum in c order)
-__device__ __forceinline__ float md_head_lse(const float *z, int b) {
-    float mx = z[0];
-    for (int c = 1; c < b; ++c) mx = fmaxf(mx, z[c]);
-    float sum = 0.f;
-    for (int c = 0; c < b; ++c) sum += expf(z[c] - mx);
-    return mx + logf(sum);
+template <bool MASKED>
+__device__ __forceinline__ float md_head_lse(const float *z, int b, unsigned long long valid) {
+    const float mx = md_head_max<MASKED>(z, b, valid);
+    return mx + logf(md_head_sumexp<MASKED>(z, b, mx, valid));
 }
 // entropy of one head given its log-sum-exp
-__device__ __forceinline__ float md_head_entropy(const float *z, int b, float lse) {
+template <bool MASKED>
+__device__ __forceinline__ float md_head_entropy(const float *z, int b, float lse, unsigned long long valid) {
     float e = 0.f;
     for (int c = 0; c < b; ++c) {
+        if (MASKED && !md_in(valid, c)) continue;
         const float ls = z[c] - lse;
         e -= expf(ls) * ls;
     }
@@ -868,23 +916,28 @@ __device__ __forceinline__ int md_action(float a, int b) {
 
 // The gradient multidiscrete_loss_kernel writes, per head segment; columns >= S of the padded row are zeroed.  First walk: log p
 // and the entropy of the row (float terms summed in double, rounded once: see the sampling kernel); second walk: each head's log-sum-exp and entropy again, then its gradient in place (a head's logits
-// are overwritten only after the head's own reads).
+// are overwritten only after the head's own reads).  MASKED: the row's words are those of the buffer's physical row of idx[row]
+// (MaskRows); a stored action its own mask marks invalid (a caller error) takes the literal z[a] - lse_V, its one-hot falls on an
+// invalid column and is dropped.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void multidiscrete_nvec_loss_kernel(float *__restrict__ logits, int64_t ld, const float *__restrict__ actions,
                                                                        const float *__restrict__ old_logp,
                                                                        const float *__restrict__ advantages, int64_t mb, LossCfg cfg,
-                                                                       double *__restrict__ stats, MdSpec spec) {
+                                                                       double *__restrict__ stats, MdSpec spec, MaskRows mr) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = row < mb;
     float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     if (active) {
         float *z = logits + row * ld;
         const float *ar = actions + row * spec.H;
+        const unsigned *words = MASKED ? mr.mask + ring_row(mr.idx[row], mr.ring_base, mr.ring_cap) * mr.W : nullptr;
         double lpd = 0.0, entd = 0.0;
         int s = 0;
         for (int h = 0; h < spec.H; ++h) {
             const int b = spec.b[h];
-            const float lse = md_head_lse(z + s, b);
-            entd += (double)md_head_entropy(z + s, b, lse);
+            const unsigned long long valid = MASKED ? md_head_valid(words, s, b) : 0ull;
+            const float lse = md_head_lse<MASKED>(z + s, b, valid);
+            entd += (double)md_head_entropy<MASKED>(z + s, b, lse, valid);
             lpd += (double)(z[s + md_action(ar[h], b)] - lse);
             s += b;
         }
@@ -894,10 +947,15 @@ __global__ __launch_bounds__(256) void multidiscrete_nvec_loss_kernel(float *__r
         s = 0;
         for (int h = 0; h < spec.H; ++h) {
             const int b = spec.b[h];
-            const float lse = md_head_lse(z + s, b);
-            const float eh = md_head_entropy(z + s, b, lse);
+            const unsigned long long valid = MASKED ? md_head_valid(words, s, b) : 0ull;
+            const float lse = md_head_lse<MASKED>(z + s, b, valid);
+            const float eh = md_head_entropy<MASKED>(z + s, b, lse, valid);
             const int a = md_action(ar[h], b);
             for (int c = 0; c < b; ++c) {
+                if (MASKED && !md_in(valid, c)) {
+                    z[s + c] = 0.f;
+                    continue;
+                }
                 const float ls = z[s + c] - lse, ph = expf(ls);
                 const float onehot = (c == a) ? 1.f : 0.f;
                 z[s + c] = t.g_logp * (onehot - ph) + g_ent * (-ph * (ls + eh));
@@ -911,11 +969,18 @@ __global__ __launch_bounds__(256) void multidiscrete_nvec_loss_kernel(float *__r
 }
 
 int launch_multidiscrete_nvec_loss(hipStream_t st, float *logits, int64_t ld, const float *actions, const float *old_logp, const float *adv,
-                                   int64_t mb, const LossCfg &cfg, double *stats, const MdSpec &spec) {
+                                   int64_t mb, const LossCfg &cfg, double *stats, const MdSpec &spec, const MaskRows *mr) {
     if (mb <= 0) return 0;
     RLPPO_CHECK_ARG(spec.S <= ld, "multi-discrete head: %d logits in rows of %ld", spec.S, (long)ld);
-    hipLaunchKernelGGL(multidiscrete_nvec_loss_kernel, dim3(thread_per_row_grid(mb)), dim3(256), 0, st, logits, ld, actions, old_logp, adv,
-                       mb, cfg, stats, spec);
+    const bool masked = mr && mr->mask;
+    RLPPO_CHECK_ARG(!masked || (mr->W == (spec.S + 31) / 32 && mr->idx), "multi-discrete head: mask_words=%d, %d logits need %d", mr->W, spec.S,
+                    (spec.S + 31) / 32);
+    if (masked)
+        hipLaunchKernelGGL(multidiscrete_nvec_loss_kernel<true>, dim3(thread_per_row_grid(mb)), dim3(256), 0, st, logits, ld, actions, old_logp,
+                           adv, mb, cfg, stats, spec, *mr);
+    else
+        hipLaunchKernelGGL(multidiscrete_nvec_loss_kernel<false>, dim3(thread_per_row_grid(mb)), dim3(256), 0, st, logits, ld, actions, old_logp,
+                           adv, mb, cfg, stats, spec, MaskRows{});
     RLPPO_LAUNCH_CHECK();
     return 0;
 }

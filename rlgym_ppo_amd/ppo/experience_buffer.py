@@ -10,8 +10,9 @@ here new rows overwrite the oldest ones in place and a rotating base index maps 
 order) to physical row (base + i) mod capacity -- the kernels apply that map to the permutation's entries
 (rlppo_minibatch_args.ring_base / ring_cap), the reference-shaped accessors materialise the logical order on demand.
 
-Beyond the reference: an optional tenth field, `action_masks` (invalid-action masking of the discrete head), stored packed
-(int32 words [capacity, ceil(A / 32)], util/action_mask.py) under the same FIFO / grow / wrap rules.  A buffer is masked or not.
+Beyond the reference: an optional tenth field, `action_masks` (invalid-action masking: A entries per row, the discrete head's
+actions or the multi-discrete head's logits, one per bin of every component), stored packed (int32 words [capacity, ceil(A / 32)],
+util/action_mask.py) under the same FIFO / grow / wrap rules.  A buffer is masked or not.
 """
 import os
 
@@ -179,6 +180,11 @@ class ExperienceBuffer(object):
         if self._count == 0:
             return torch.empty((0, self._n_actions), dtype=torch.bool, device=self._dev)
         return AM.unpack(self._logical("action_masks"), self._n_actions)
+
+    @property
+    def mask_width(self):
+        """Entries of a mask row (the A of the packed words), or None for an unmasked buffer."""
+        return self._n_actions if len(self._fields) > len(_FIELDS) else None
 
     def __len__(self):
         return self._count

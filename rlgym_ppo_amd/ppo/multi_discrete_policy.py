@@ -4,7 +4,13 @@ util/torch_functions.py:81-122) on librlppo's fused forward + 8-way categorical 
 `bins` (not in the reference, whose bins are literals): the nvec of a MultiDiscrete(nvec) action space -- H = len(bins) heads,
 sum(bins) outputs, every head padded to B = max(bins) where the reference pads its 2-way heads to 3.  None or the reference's own
 list [3, 3, 3, 3, 3, 2, 2, 2] is the reference's policy on the fixed kernels, launch for launch; anything else runs the general
-kernels (rlppo_multidiscrete_act_nvec; limits: include/rlppo.h, RLPPO_MD_MAX_*)."""
+kernels (rlppo_multidiscrete_act_nvec; limits: include/rlppo.h, RLPPO_MD_MAX_*).
+
+`action_mask` (not in the reference): invalid-action masking per component, the sb3-contrib MaskablePPO convention -- one entry per
+LOGIT, [n, sum(bins)] bool / 0-1 (host or device, or util.action_mask.Packed), head h owning columns [s_h, s_h + b_h).  A head's
+distribution is the Categorical over its valid bins; every head of every row needs at least one (a host mask is checked, naming row
+and head).  A masked call always runs the general kernels, also on the reference's bins; get_output returns logits, which no mask
+changes, and keeps refusing one."""
 import ctypes
 
 import numpy as np
@@ -12,13 +18,15 @@ import torch
 
 from .. import _native as N
 from ..engine import host_exponential, ptr, stream_ptr
+from ..util import action_mask as AM
 from ..util import torch_functions
 from ._mlp import ArenaModule, build_body
 
 
 def _no_action_mask(action_mask):
     if action_mask is not None:
-        raise ValueError("action_mask: invalid-action masking is an option of the discrete head (DiscreteFF), not of the multi-discrete head")
+        raise ValueError("action_mask: get_output of the multi-discrete head returns logits, which no mask changes -- pass the mask to "
+                         "get_action / act_padded / get_backprop_data")
 
 
 REFERENCE_BINS = (3, 3, 3, 3, 3, 2, 2, 2)  # multi_discrete_policy.py:20
@@ -60,6 +68,29 @@ class MultiDiscreteFF(ArenaModule):
         """The ctypes nvec the library's general kernels take, or None where the fixed kernels (the reference's bins) run."""
         return self._nvec_c if (self._general or self._force_general) else None
 
+    def _mask_words(self, action_mask, n):
+        """The packed device words [n, W] of a call on n rows (one bit per logit), or None without a mask."""
+        if action_mask is None:
+            return None
+        words = AM.pack(action_mask, self.n_logits, self.arena.device, heads=self.splits)
+        if words.shape[0] != n:
+            raise ValueError(f"action mask has {words.shape[0]} rows, the call {n}")
+        return words
+
+    def _valid(self, action_mask, device):
+        """bool [n, S] on `device` of a mask in any accepted form; a head without a valid bin counts as all-valid (the kernels' rule
+        for masks that were not checked on the host)."""
+        if isinstance(action_mask, AM.Packed):
+            m = action_mask.unpack()
+        elif isinstance(action_mask, torch.Tensor):
+            m = action_mask.detach() != 0
+        else:
+            AM.check_heads(action_mask, self.splits)
+            m = torch.as_tensor(np.asarray(action_mask)) != 0
+        m = m.to(device).view(-1, self.n_logits)
+        parts = [torch.where(p.any(dim=-1, keepdim=True), p, torch.ones_like(p)) for p in torch.split(m, self.splits, dim=-1)]
+        return torch.cat(parts, dim=-1)
+
     @torch.no_grad()
     def get_output(self, obs, action_mask=None):
         _no_action_mask(action_mask)
@@ -68,20 +99,22 @@ class MultiDiscreteFF(ArenaModule):
 
     @torch.no_grad()
     def get_action(self, obs, deterministic=False, noise=None, standardize=None, action_mask=None):
-        _no_action_mask(action_mask)
         a = self.arena
         if deterministic:
             logits = self.get_output(obs)
+            if action_mask is not None:  # the arg-max over each head's valid bins
+                logits = logits.masked_fill(~self._valid(action_mask, logits.device), float("-inf"))
             action, start = [], 0
             for split in self.splits:
                 action.append(logits[..., start:start + split].argmax(dim=-1))
                 start += split
             return torch.stack(action).cpu().numpy(), 0
-        out = self._graph_act(obs, noise, standardize)  # small host batches: one hipGraph replay (ppo/_mlp.py)
+        # small host batches: one hipGraph replay (ppo/_mlp.py); a masked call takes the general path
+        out = self._graph_act(obs, noise, standardize) if action_mask is None else None
         if out is not None:
             return out
         rows = a.stage_obs(obs, standardize)
-        actions, logp = self.act_padded(rows, noise)
+        actions, logp = self.act_padded(rows, noise, action_mask)
         return actions.cpu(), logp.cpu()
 
     # ---- hooks of the graph-replayed rollout step (ppo/_mlp.py::ActGraph)
@@ -95,22 +128,27 @@ class MultiDiscreteFF(ArenaModule):
     def _action_buffer(self, cap):
         return torch.zeros((cap, self.n_heads), dtype=torch.int64)
 
-    def _act_launch(self, rows, n, noise, actions, logp, ws, opts=None):
+    def _act_launch(self, rows, n, noise, actions, logp, ws, opts=None, mask_words=None):
         a = self.arena
         nvec = self.md_nvec
-        if nvec is None:
+        if mask_words is not None:  # a masked call runs the general kernel, also on the reference's bins
+            N.check(N.lib().rlppo_multidiscrete_act_nvec_masked(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1],
+                                                                n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(), opts,
+                                                                self._nvec_c, self.n_heads, ptr(mask_words), mask_words.shape[1]))
+        elif nvec is None:
             N.check(N.lib().rlppo_multidiscrete_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1],
                                                     n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(), opts))
         else:
             N.check(N.lib().rlppo_multidiscrete_act_nvec(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1],
-                                                         n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(), opts,
-                                                         nvec, self.n_heads))
+                                                         n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(),
+                                                         opts, nvec, self.n_heads))
 
     def act_padded(self, rows, noise=None, action_mask=None):
-        """Padded device rows -> (actions int64 [n, H], log_probs fp32 [n]) on the device (see DiscreteFF.act_padded)."""
-        _no_action_mask(action_mask)
+        """Padded device rows -> (actions int64 [n, H], log_probs fp32 [n]) on the device (see DiscreteFF.act_padded).
+        action_mask: optional [n, sum(bins)] valid = 1 (or util.action_mask.Packed); the noise keeps its shape and its draw."""
         a = self.arena
         n = rows.shape[0]
+        words = self._mask_words(action_mask, n)
         H, B = self.n_heads, self.max_bins
         if noise is None and self.noise_mode == "device":
             noise = torch.empty(n * H, B, device=a.device).exponential_(1)  # fast mode: torch's HIP generator, not the reference's CPU stream
@@ -122,14 +160,17 @@ class MultiDiscreteFF(ArenaModule):
             raise ValueError(f"noise: {tuple(q.shape)} given, {n} rows of bins {self.splits} need ({n * H}, {B})")
         actions = torch.empty((n, H), dtype=torch.int64, device=a.device)
         logp = torch.empty(n, dtype=torch.float32, device=a.device)
-        self._act_launch(rows, n, q, actions, logp, a.forward_ws(n))
+        self._act_launch(rows, n, q, actions, logp, a.forward_ws(n), mask_words=words)
         return actions, logp
 
     def get_backprop_data(self, obs, acts, action_mask=None):
-        """Compatibility accessor with an autograd graph (multi_discrete_policy.py:76-89); unused by PPOLearner."""
-        _no_action_mask(action_mask)
+        """Compatibility accessor with an autograd graph (multi_discrete_policy.py:76-89); unused by PPOLearner.
+        action_mask (optional): the masked semantics of the update -- invalid logits -inf before make_distribution."""
         if not isinstance(obs, torch.Tensor):
             obs = torch.as_tensor(np.asarray(obs), dtype=torch.float32, device=self.arena.device)
         dist = self.multi_discrete
-        dist.make_distribution(self.model(obs))
+        logits = self.model(obs)
+        if action_mask is not None:
+            logits = logits.masked_fill(~self._valid(action_mask, logits.device).view(logits.shape), float("-inf"))
+        dist.make_distribution(logits)
         return dist.log_prob(acts), dist.entropy().mean()

@@ -254,9 +254,12 @@ class PPOLearner(object):
         a.targets = st["values"].data_ptr()
         a.advantages = st["advantages"].data_ptr()
         if "action_masks" in st:  # invalid-action masking (ExperienceBuffer.submit_experience(..., action_masks=...))
-            if self.policy_type != 0:
-                raise ValueError("the experience buffer holds action masks: invalid-action masking is an option of the discrete head, "
-                                 f"not of policy_type {self.policy_type}")
+            if self.policy_type not in (0, 1):
+                raise ValueError("the experience buffer holds action masks: invalid-action masking is an option of the discrete head "
+                                 f"and of the multi-discrete head, not of policy_type {self.policy_type}")
+            if self.policy_type == 1 and exp.mask_width != self.policy.n_logits:  # one mask entry per logit, [n, sum(bins)]
+                raise ValueError(f"the experience buffer's action masks have {exp.mask_width} entries per row, the multi-discrete policy has "
+                                 f"{self.policy.n_logits} logits (one entry per bin of every component)")
             a.action_mask, a.mask_words = st["action_masks"].data_ptr(), st["action_masks"].shape[1]
         a.clip_range, a.ent_coef = float(self.clip_range), float(self.ent_coef)
         a.mb_ratio = float(self.mini_batch_size / self.batch_size)
@@ -277,8 +280,10 @@ class PPOLearner(object):
 
     def _pass(self, st, args):
         """One rlppo_ppo_minibatch pass; a multi-discrete policy with bins of its own goes through rlppo_ppo_minibatch_nvec (the
-        general loss kernel), every other policy through the plain entry point."""
+        general loss kernel), and so does every masked multi-discrete pass; every other policy through the plain entry point."""
         nvec = self.policy.md_nvec if self.policy_type == 1 else None
+        if nvec is None and self.policy_type == 1 and args.action_mask:
+            nvec = self.policy._nvec_c  # a masked pass runs the general loss kernel, also on the reference's bins
         if nvec is None:
             return N.lib().rlppo_ppo_minibatch(st, ctypes.byref(args))
         return N.lib().rlppo_ppo_minibatch_nvec(st, ctypes.byref(args), nvec, self.policy.n_heads)

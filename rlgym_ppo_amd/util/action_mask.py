@@ -3,6 +3,10 @@
 A mask row marks each of the A actions valid (1 / True) or invalid (0 / False).  The kernels read it packed: W = ceil(A / 32)
 32-bit words per row, bit c % 32 of word c / 32 set = action c valid, bits at and beyond A clear.  `pack` builds that form on
 the device from a bool / 0-1 array or tensor [n, A] (host or device); `unpack` is its inverse for the accessors.
+
+The multi-discrete head (MultiDiscrete(nvec)) uses the same encoding with one bit per LOGIT: A = S = sum(nvec), head h owns bits
+[s_h, s_h + b_h).  `pack(..., heads=nvec)` / `check_heads` hold a host mask to the per-head rule: every head of every row keeps at
+least one valid bin.
 """
 import numpy as np
 import torch
@@ -29,14 +33,35 @@ def mask_words(n_actions):
     return (int(n_actions) + 31) // 32
 
 
-def pack_host(mask, n_actions):
-    """numpy bool / 0-1 [n, A] -> int32 words [n, W]; a row without a valid action raises ValueError naming it."""
+def check_heads(mask, heads):
+    """Host bool / 0-1 [n, sum(heads)]: a head without a valid bin raises ValueError naming the row and the head (a head with
+    exactly one valid bin is fine: it contributes log-probability 0 and entropy 0)."""
+    m = np.asarray(mask)
+    if m.ndim == 1:
+        m = m.reshape(1, -1)
+    heads = [int(b) for b in heads]
+    if m.ndim != 2 or m.shape[1] != sum(heads):
+        raise ValueError(f"action mask shape {tuple(m.shape)} != (n, {sum(heads)}) for bins {tuple(heads)}")
+    m = m != 0
+    s = 0
+    for h, b in enumerate(heads):
+        empty = np.flatnonzero(~m[:, s:s + b].any(axis=1))
+        if empty.size:
+            raise ValueError(f"action mask: row {int(empty[0])}, head {h} (bins {s} .. {s + b - 1}) has no valid bin")
+        s += b
+
+
+def pack_host(mask, n_actions, heads=None):
+    """numpy bool / 0-1 [n, A] -> int32 words [n, W]; a row without a valid action raises ValueError naming it (heads: the
+    multi-discrete head's nvec -- a head without a valid bin raises, naming row and head)."""
     m = np.asarray(mask)
     if m.ndim == 1:
         m = m.reshape(1, -1)
     if m.ndim != 2 or m.shape[1] != int(n_actions):
         raise ValueError(f"action mask shape {tuple(m.shape)} != (n, {int(n_actions)})")
     m = m != 0
+    if heads is not None:
+        check_heads(m, heads)
     empty = np.flatnonzero(~m.any(axis=1))
     if empty.size:
         raise ValueError(f"action mask: row {int(empty[0])} has no valid action")
@@ -47,10 +72,11 @@ def pack_host(mask, n_actions):
     return np.ascontiguousarray(by).view("<u4").astype(np.uint32, copy=False).view(np.int32).reshape(m.shape[0], w)
 
 
-def pack(mask, n_actions, device):
+def pack(mask, n_actions, device, heads=None):
     """bool / 0-1 array or tensor [n, A], host or device -> int32 words [n, W] on `device`.  Host input is checked for rows
-    without a valid action (ValueError naming the row); device input is not read back -- the kernels treat such a row as
-    all-valid."""
+    without a valid action (ValueError naming the row) and, with heads = the multi-discrete head's nvec (A = sum(heads)), for
+    heads without a valid bin (ValueError naming row and head); device input is not read back -- the kernels treat such a row
+    (such a head) as all-valid."""
     A = int(n_actions)
     if isinstance(mask, Packed):
         if mask.n_actions != A:
@@ -71,7 +97,7 @@ def pack(mask, n_actions, device):
         return words.to(device).contiguous()
     if isinstance(mask, torch.Tensor):
         mask = mask.detach().numpy()
-    return torch.from_numpy(pack_host(mask, A)).to(device, non_blocking=False)
+    return torch.from_numpy(pack_host(mask, A, heads)).to(device, non_blocking=False)
 
 
 def unpack(words, n_actions):
