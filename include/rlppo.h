@@ -63,6 +63,12 @@ extern "C" {
  *                 masked call on the reference's bins gives md_nvec = {3, 3, 3, 3, 3, 2, 2, 2} and runs the general kernels;
  *   act options   a mask in rlppo_act_opts stays refused by every multi-discrete rollout entry point, rlppo_multidiscrete_act_nvec
  *                 included (the text callers know): the masked step takes its mask as an argument of its own entry point.
+ *   captured     rlppo_multidiscrete_act_nvec_masked may be captured into a graph with completion words (rlppo_act_opts.done_words)
+ *                 and a mask in host-visible memory (a host window, or pinned memory) that the host rewrites before every
+ *                 replay: the kernel reads only words inside a row's W words and writes row r's results to row r, so rows
+ *                 whose words are stale are harmless and a stale head without a valid bin is all-valid (rule above);
+ *   collection    process-mode collection carries the S entries of a row behind its observation (the opt-in trailer of
+ *                 rlgym_ppo_amd/batched_agents/comm_consts.py) and rlppo_collector_set_mask_heads gives the C++ loop the layout.
  * A wrong mask_words is RLPPO_ERR_ARG naming the field and the needed count, before any HIP call.  A head has at most 64 bins, so
  * the kernels assemble V_h as one 64-bit value from the two or three words it touches (no per-row array, no scratch). */
 #define RLPPO_MD_MAX_HEADS 64
@@ -74,7 +80,7 @@ extern "C" {
 #define RLPPO_ERR_WORKSPACE 1002  /* workspace too small */
 #define RLPPO_ERR_COLLECT_TIMEOUT 1003  /* rlppo_collector_collect: no worker message for a minute */
 #define RLPPO_ERR_INTERRUPTED 1004     /* rlppo_collector_collect: a signal arrived; n_collected holds the progress, call again with resume = 1 */
-#define RLPPO_ERR_MASK_ROW 1005        /* rlppo_collector_ready_masks: a worker reported an action-mask row without a valid action */
+#define RLPPO_ERR_MASK_ROW 1005        /* rlppo_collector_ready_masks: a worker reported an action-mask row (a head of one) without a valid action */
 
 /* policy head codes == the reference's `policy_type` (ppo_learner.py:34-50) */
 #define RLPPO_HEAD_DISCRETE 0
@@ -564,9 +570,13 @@ int rlppo_learn_report(void *stream, const rlppo_report_args *args);
  * floats of 0 / 1 behind every observation).  Masks cross this boundary as BYTES, one per action, 0 = invalid (the host packs them
  * to the kernels' words where it stages them for a launch: util/action_mask.py):
  *   set_masked: once, before the first _collect: every slab carries the trailer for n_actions actions.
+ *   set_mask_heads: a multi-discrete run ("[nvec, masked]" above), after set_masked(S): the masks have one byte per LOGIT,
+ *     S = sum(nvec), head h owning bytes [s_h, s_h + nvec[h]); RLPPO_ERR_ARG unless nvec sums to the mask width.  Without the call
+ *     the S bytes of a row are one head (the discrete head).
  *   set_mask: the mask [rows][n_actions] of the observation last given to set_obs for that worker.
  *   ready_masks: after _ready, the mask rows of exactly that batch, row for row with its observations; RLPPO_ERR_MASK_ROW (the
- *     text names worker and agent) when a row has no valid action -- nothing has been sent for the batch at that point.
+ *     text names worker and agent) when a row has no valid action -- with set_mask_heads: when a HEAD of a row has no valid bin,
+ *     the text naming worker, agent and head -- nothing has been sent for the batch at that point.
  *   emit_masks: between _finish and _emit, the masks the actions were sampled under, [n_steps][n_actions], row for row with
  *     _emit's states. */
 int rlppo_collector_create(int32_t n_workers, const int32_t *socket_fds, const int32_t *peer_ports, const float *shm_base,
@@ -586,6 +596,7 @@ int rlppo_collector_set_masked(void *handle, int32_t n_actions);
 int rlppo_collector_set_mask(void *handle, int32_t worker, const uint8_t *mask, int32_t rows);
 int rlppo_collector_ready_masks(void *handle, uint8_t *mask_out, int64_t cap_rows);
 int rlppo_collector_emit_masks(void *handle, uint8_t *masks);
+int rlppo_collector_set_mask_heads(void *handle, const int32_t *nvec, int32_t n_heads);
 
 /* ------------------------------------------------------------------------------------- data-parallel exchange */
 
@@ -762,6 +773,12 @@ const int64_t *rlppo_selection_epoch_ptr(void);   /* the counter itself (a host 
  * grouped weight-gradient launch, 6 = [nvec] launches of the multi-discrete head's general (any nvec) kernels, sampling and loss;
  * -1 for an unknown key. */
 int64_t rlppo_dbg_counter(int32_t key);
+/* Debug helper, like rlppo_dbg_counter: adds delta to counter `key` (6 only; anything else RLPPO_ERR_ARG).  The launchers count when
+ * they are CALLED; a host that captures a call into a graph and replays it (rlgym_ppo_amd/ppo/_mlp.py::ActGraph, the masked
+ * multi-discrete call) takes the capture's launches off again and adds one run per replay, so that counter 6 keeps meaning "runs of
+ * the general kernels".  For such a graph counter 6 is HOST-MAINTAINED: it witnesses that the host replayed a graph whose body is
+ * the general kernel, not a launcher call. */
+int rlppo_dbg_count(int32_t key, int64_t delta);
 /* Single-kernel entry points used by tests/ and bench.py to check / time each GEMM flavour in isolation.
  * epilogue: 0 bias, 1 bias+relu, 2 bias+tanh, 3 relu-mask (mask_src > 0).  Shapes as in csrc/gemm.hip. */
 int rlppo_dbg_gemm_nt(void *stream, const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias,

@@ -168,6 +168,7 @@ SIGNATURES = {
     "rlppo_collector_set_mask": (c_int32, [c_void_p, c_int32, c_void_p, c_int32]),
     "rlppo_collector_ready_masks": (c_int32, [c_void_p, c_void_p, c_int64]),
     "rlppo_collector_emit_masks": (c_int32, [c_void_p, c_void_p]),
+    "rlppo_collector_set_mask_heads": (c_int32, [c_void_p, POINTER(c_int32), c_int32]),
     "rlppo_comm_set_library": (c_int32, [ctypes.c_char_p]),
     "rlppo_comm_unique_id": (c_int32, [c_void_p]),
     "rlppo_comm_init": (c_int32, [c_int32, c_int32, c_void_p]),
@@ -199,6 +200,7 @@ SIGNATURES = {
     "rlppo_dbg_set": (c_int32, [c_int32, c_int32]),
     "rlppo_selection_epoch": (c_int64, []),
     "rlppo_dbg_counter": (c_int64, [c_int32]),
+    "rlppo_dbg_count": (c_int32, [c_int32, c_int64]),
     "rlppo_dbg_gemm_nt": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                     c_int64, c_int32, c_int32, c_int32]),
     "rlppo_dbg_gemm_nt_bits_bytes": (c_size_t, [c_int64, c_int32]),

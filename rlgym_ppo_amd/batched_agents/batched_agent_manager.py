@@ -184,8 +184,11 @@ class BatchedAgentManager(object):
         self.next_obs, self.current_obs, self.current_pids = [], [], []
         # invalid-action masking (workers whose environment has action_masks(): the mask trailer of comm_consts.py): the mask of
         # every observation travels with it; action_mask_rows: the masks of the last collect's steps, bool [N, n_actions], row for
-        # row with its states (what Learner.add_new_experience hands to the buffer) -- None in an unmasked run
-        self.masked, self.n_actions = False, 0
+        # row with its states (what Learner.add_new_experience hands to the buffer) -- None in an unmasked run.  n_actions is the
+        # WIDTH of a mask row: the action count of a Discrete space, one entry per logit -- sum(nvec) -- of a MultiDiscrete one
+        # (action rows are then len(nvec) wide); mask_space_type: the action space type of the shapes reply (0 / 1)
+        self.masked, self.n_actions, self.mask_space_type = False, 0, 0
+        self._mask_layout_cache = None
         self.next_mask, self.current_mask = [], []
         self.action_mask_rows = None
         self._average_reward = None
@@ -236,6 +239,7 @@ class BatchedAgentManager(object):
         self.next_obs = [None] * n
         self.current_mask, self.next_mask = [None] * n, [None] * n
         self.masked, self.n_actions, self.action_mask_rows = False, 0, None
+        self.mask_space_type, self._mask_layout_cache = 0, None
         self.selector = selectors.DefaultSelector()
         if n_processes <= 0:
             self.processes = [_LocalWorker(build_env_fn, collect_metrics_fn, self.seed)]
@@ -284,7 +288,10 @@ class BatchedAgentManager(object):
 
     def _configure_masking(self, msg):
         """Decides from a worker's shapes reply (a fourth float, 1.0 = it sends the mask trailer) and from what the initial reset
-        states carried whether the run is masked; a masked run needs the discrete head and masks as wide as the action space.
+        states carried whether the run is masked; a masked run needs the discrete head and masks as wide as the action space, or
+        the multi-discrete head (type 1) and masks with one entry per logit.  The reply of a MultiDiscrete space carries len(nvec),
+        not sum(nvec), and the policy usually does not exist yet: the width the reset states carried is recorded here and held
+        against the policy's layout by _mask_layout, before the first action is sent.
         (Every worker runs the same environment: the first one's reply speaks for all, the reset states of all are checked.)"""
         n_acts, code = int(msg[2]), int(msg[3])
         with_mask = [m is not None for m in self.current_mask]
@@ -295,19 +302,63 @@ class BatchedAgentManager(object):
         if self.masked:
             from ..ppo._mlp import ArenaModule
             from ..ppo.discrete_policy import DiscreteFF
-            other = "an action space of type %d" % code if code != 0 else \
-                type(self.policy).__name__ if isinstance(self.policy, ArenaModule) and not isinstance(self.policy, DiscreteFF) else None
-            if other is not None:   # (the policy is usually built from what this call returns: the action space decides)
-                raise ValueError("the environment offers action_masks(): invalid-action masking is an option of the discrete head "
-                                 f"(DiscreteFF), not of {other}")
-            if any(m.shape[1] != n_acts for m in self.current_mask):
-                raise ValueError(f"the reset states carry masks of {self.current_mask[0].shape[1]} actions, the action space has {n_acts}")
-            self.n_actions = n_acts
+            from ..ppo.multi_discrete_policy import MultiDiscreteFF
+            head = {0: DiscreteFF, 1: MultiDiscreteFF}.get(code)
+            # (the policy is usually built from what this call returns: the action space decides)
+            refusal = "the environment offers action_masks(): invalid-action masking is an option of the discrete head (DiscreteFF) " \
+                      "and of the multi-discrete head (MultiDiscreteFF)"
+            if head is None:
+                raise ValueError(f"{refusal}, not of an action space of type {code}")
+            if isinstance(self.policy, ArenaModule) and not isinstance(self.policy, head):
+                if isinstance(self.policy, (DiscreteFF, MultiDiscreteFF)):   # a masking head, but not this action space's
+                    raise ValueError(f"{refusal}; an action space of type {code} is served by {head.__name__}, the policy is a "
+                                     f"{type(self.policy).__name__}")
+                raise ValueError(f"{refusal}, not of {type(self.policy).__name__}")
+            width = self.current_mask[0].shape[1]
+            if code == 0 and any(m.shape[1] != n_acts for m in self.current_mask):
+                raise ValueError(f"the reset states carry masks of {width} actions, the action space has {n_acts}")
+            if any(m.shape[1] != width for m in self.current_mask):
+                raise ValueError(f"the reset states carry masks of different widths: {sorted({m.shape[1] for m in self.current_mask})}")
+            if code == 1 and width < n_acts:
+                raise ValueError(f"the reset states carry masks of {width} entries, fewer than the {n_acts} components of the "
+                                 "MultiDiscrete action space (a mask has one entry per bin of every component)")
+            self.n_actions, self.mask_space_type, self._mask_layout_cache = width, code, None
             for w in self.processes:
-                w.n_actions = n_acts
+                w.n_actions = width
+
+    def _mask_layout(self):
+        """-> the bins of a masked multi-discrete run (None for the discrete head), after holding the width of the workers' masks
+        against the policy's layout (policy.n_logits, policy.splits: the pair VectorAgentManager._mask_layout reads).  Worked out
+        once per policy object; every collect asks before it sends an action."""
+        cached = self._mask_layout_cache
+        if cached is not None and cached[0] is self.policy:
+            return cached[1]
+        heads = None
+        if self.mask_space_type == 1:
+            n_logits, splits = getattr(self.policy, "n_logits", None), getattr(self.policy, "splits", None)
+            if n_logits is None or splits is None:
+                raise ValueError("the environment offers action_masks() on a MultiDiscrete action space: invalid-action masking needs the "
+                                 f"multi-discrete head's layout (policy.n_logits, policy.splits), which {type(self.policy).__name__} lacks")
+            heads = [int(b) for b in splits]
+            if int(n_logits) != self.n_actions or sum(heads) != self.n_actions:
+                raise ValueError(f"the workers' action masks have {self.n_actions} entries per agent, but the policy's bins {heads} have "
+                                 f"{sum(heads)} logits: action_masks() must answer one entry per bin of every component")
+        self._mask_layout_cache = (self.policy, heads)
+        return heads
 
     def _checked_masks(self, ready):
-        """The stacked mask rows of the ready workers; a row without a valid action raises before anything is sent."""
+        """The stacked mask rows of the ready workers; a row without a valid action -- in a multi-discrete run: a head of a row
+        without a valid bin -- raises before anything is sent."""
+        heads = self._mask_layout()
+        if heads is not None:
+            starts = np.cumsum([0] + heads[:-1])
+            for pid in ready:
+                ok = np.logical_or.reduceat(self.current_mask[pid], starts, axis=1)   # [n_agents, H]: head h keeps a valid bin
+                if not ok.all():
+                    agent, h = (int(x) for x in np.argwhere(~ok)[0])                  # (the first agent, its first such head)
+                    raise ValueError(f"action mask: worker {pid}, agent {agent}, head {h} (bins {int(starts[h])} .. "
+                                     f"{int(starts[h]) + heads[h] - 1}) has no valid bin")
+            return np.concatenate([self.current_mask[pid] for pid in ready], axis=0)
         for pid in ready:
             empty = np.flatnonzero(~self.current_mask[pid].any(axis=1))
             if empty.size:
@@ -411,6 +462,8 @@ class BatchedAgentManager(object):
     def collect_timesteps(self, n):
         """-> ((states, actions, log_probs, rewards, next_states, dones, truncated), metrics, n_collected, seconds),
         trajectory-concatenated, last step of every flushed trajectory force-marked truncated if not done (quirk Q4)."""
+        if self.masked:
+            self._mask_layout()   # (a multi-discrete run: the masks' width against the policy's bins, before any action is sent)
         if self._native_ok():
             return self._collect_timesteps_native(n)
         t1 = time.perf_counter()
@@ -489,6 +542,9 @@ class BatchedAgentManager(object):
         self._native = h
         if self.masked:
             N.check(N.lib().rlppo_collector_set_masked(h, self.n_actions))
+            heads = self._mask_layout()
+            if heads is not None:   # the multi-discrete head: _ready_masks holds every row to the per-head rule
+                N.check(N.lib().rlppo_collector_set_mask_heads(h, (ctypes.c_int32 * len(heads))(*heads), len(heads)))
         for pid, o in enumerate(self.current_obs):
             if o is not None and pid not in self.current_pids:
                 a = np.ascontiguousarray(o, dtype=np.float32)

@@ -17,7 +17,9 @@ process built for the reference and this manager (or the other way round) intero
     [prev_n_agents, done, truncated, rank(state), rank(metrics), *metrics_shape, *state_shape, *rewards[prev_n_agents],
      *metrics.ravel(), *obs.ravel()]                               (batched_agent.py:154-164)
 
-Opt-in mask trailer (not in the reference; invalid-action masking of the discrete head).  A worker whose environment has
+Opt-in mask trailer (not in the reference; invalid-action masking of the discrete and of the multi-discrete head; for a
+MultiDiscrete(nvec) space read "n_actions" below as sum(nvec), one entry per logit, head h owning entries [s_h, s_h + nvec[h]) --
+the shapes reply keeps len(nvec) in its second float, the learner takes the width from the trailer of the reset states).  A worker whose environment has
 `action_masks()` -- and only such a worker: every other worker writes the bytes above exactly -- asks it after `reset()` and after
 every step (once a possible reset is done) for the masks of the observation it is about to report, [n_agents, n_actions] (or
 [n_actions] for a one-agent environment), and appends them as n_agents * n_actions float32 of 0.0 / 1.0 (1 = valid):

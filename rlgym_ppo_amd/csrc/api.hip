@@ -1671,6 +1671,13 @@ int rlppo_dbg_set(int32_t key, int32_t value) {
 }
 int64_t rlppo_selection_epoch(void) { return g_selection_epoch; }
 const int64_t *rlppo_selection_epoch_ptr(void) { return &g_selection_epoch; }
+// a host that REPLAYS a captured call accounts for the runs itself (the launchers count when they are called, not when a graph
+// that holds their launches is replayed): ppo/_mlp.py::ActGraph, the masked multi-discrete call
+int rlppo_dbg_count(int32_t key, int64_t delta) {
+    RLPPO_CHECK_ARG(key == 6, "dbg_count: key %d (only counter 6 is kept by hosts that replay)", key);
+    g_cnt_md_nvec += delta;
+    return 0;
+}
 int64_t rlppo_dbg_counter(int32_t key) {
     switch (key) {
         case 0: return g_cnt_fused_act;

@@ -68,6 +68,7 @@ struct Metrics {
 struct Collector {
     int n = 0, d = 0, act_width = 0;
     int n_actions = 0;  // > 0: a masked run, every observation in a slab is followed by rows x n_actions floats of 0 / 1
+    std::vector<int> mask_heads;  // multi-discrete runs (rlppo_collector_set_mask_heads): nvec, summing to n_actions; empty: one head
     int64_t slab_floats = 0;
     std::vector<Worker> w;
     std::vector<int> current_pids, ready_pids;
@@ -450,6 +451,23 @@ int rlppo_collector_set_masked(void *handle, int32_t n_actions) {
     return 0;
 }
 
+// a multi-discrete run: the mask's n_actions entries are one per LOGIT, head h owning nvec[h] of them in order; from here on
+// _ready_masks holds every row to the per-head rule.  After set_masked; sum(nvec) must be the mask width.
+int rlppo_collector_set_mask_heads(void *handle, const int32_t *nvec, int32_t n_heads) {
+    Collector *c = static_cast<Collector *>(handle);
+    if (!c || !c->n_actions || !nvec || n_heads <= 0)
+        COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_set_mask_heads: not a masked collector (set_masked comes first), or a bad argument (%d heads)", n_heads);
+    int64_t sum = 0;
+    for (int h = 0; h < n_heads; ++h) {
+        if (nvec[h] <= 0) COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_set_mask_heads: nvec[%d] = %d", h, nvec[h]);
+        sum += nvec[h];
+    }
+    if (sum != c->n_actions)
+        COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_set_mask_heads: nvec sums to %ld, the collector's masks are %d wide", (long)sum, c->n_actions);
+    c->mask_heads.assign(nvec, nvec + n_heads);
+    return 0;
+}
+
 // the mask of current_obs[worker] (a reset state's, as the handshake received it): rows x n_actions bytes, 0 = invalid
 int rlppo_collector_set_mask(void *handle, int32_t worker, const uint8_t *mask, int32_t rows) {
     Collector *c = static_cast<Collector *>(handle);
@@ -474,9 +492,23 @@ int rlppo_collector_ready_masks(void *handle, uint8_t *mask_out, int64_t cap_row
             COLLECTOR_FAIL(RLPPO_ERR_ARG, "collector_ready_masks: worker %d has %d observation rows and %ld mask bytes", pid, w.cur_n, (long)w.cur_mask.size());
         if (rows + w.cur_n > cap_rows) COLLECTOR_FAIL(RLPPO_ERR_WORKSPACE, "collector_ready_masks: more than %ld waiting observations", (long)cap_rows);
         for (int i = 0; i < w.cur_n; ++i) {
-            bool any = false;
-            for (int a = 0; a < A; ++a) any |= w.cur_mask[(size_t)i * A + a] != 0;
-            if (!any) COLLECTOR_FAIL(RLPPO_ERR_MASK_ROW, "action mask: worker %d, agent %d has no valid action", pid, i);
+            const uint8_t *row = w.cur_mask.data() + (size_t)i * A;
+            if (c->mask_heads.empty()) {
+                bool any = false;
+                for (int a = 0; a < A; ++a) any |= row[a] != 0;
+                if (!any) COLLECTOR_FAIL(RLPPO_ERR_MASK_ROW, "action mask: worker %d, agent %d has no valid action", pid, i);
+                continue;
+            }
+            int s = 0;  // head h owns bytes [s, s + b)
+            for (size_t h = 0; h < c->mask_heads.size(); ++h) {
+                const int b = c->mask_heads[h];
+                bool any = false;
+                for (int a = s; a < s + b; ++a) any |= row[a] != 0;
+                if (!any)
+                    COLLECTOR_FAIL(RLPPO_ERR_MASK_ROW, "action mask: worker %d, agent %d, head %d (bins %d .. %d) has no valid bin", pid, i, (int)h, s,
+                                   s + b - 1);
+                s += b;
+            }
         }
         if (w.cur_n > 0) memcpy(mask_out + rows * A, w.cur_mask.data(), (size_t)w.cur_n * A);
         rows += w.cur_n;

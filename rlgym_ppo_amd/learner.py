@@ -122,6 +122,13 @@ class Learner(object):
             normalize_advantages=ppo_normalize_advantages, value_clip_range=ppo_value_clip_range, target_kl=ppo_target_kl,
             max_grad_norm=ppo_max_grad_norm)
         self.agent.policy = self.ppo_learner.policy
+        if not vector_env and self.agent.masked:
+            # a masked MultiDiscrete environment: its masks' width against the policy's bins, here rather than at the first collect
+            try:
+                self.agent._mask_layout()
+            except ValueError:
+                self.agent.cleanup()
+                raise
         # not in the reference (whose multi-discrete policy has eight fixed heads): multi_discrete_bins is the environment's nvec.
         # It is never taken from the environment by itself -- the default stays the reference's policy -- but where the
         # environment is in this process (vector mode) a disagreement is worth one warning.

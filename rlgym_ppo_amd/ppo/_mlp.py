@@ -49,16 +49,31 @@ class ActGraph:
     batched_agent_manager.py:202-204) a call is nothing but latency -- ~7 launches, three copies and two blocking read-backs,
     ~140-250 us; one replay + one synchronisation does the same work, with no copy node at all.  Same kernels, same
     arguments: results are those of the eager path bit for bit.  Rows past the caller's n hold stale data and are ignored.
-    masked (the discrete head's one-launch step only): the graph's call carries rlppo_act_opts.action_mask -- cap x mask_words
+    masked (the discrete head's one-launch step): the graph's call carries rlppo_act_opts.action_mask -- cap x mask_words
     words in the window (or in pinned memory) that run() stages with the observations, before the flush and the launch; the noise
-    stays late."""
+    stays late.
+    masked (the multi-discrete head, which has no one-launch step): the body is the layer chain as in the unmasked graph -- its
+    first layer reads the host window, no pad launch -- followed by rlppo_multidiscrete_act_nvec_masked with the completion
+    words; the mask is that entry point's ARGUMENT (rlppo_act_opts.action_mask stays NULL: both multi-discrete entry points refuse
+    one there) and points at cap x ceil(sum(bins) / 32) words behind the noise in the window (pinned memory under
+    RLPPO_ACT_PUSH=0 or without a window).  The words are all-valid once, run() stages a call's n rows with its observations,
+    the noise is in place before the launch (late noise is the discrete one-launch kernel's alone).  Rows at and beyond n keep
+    the words of an earlier call: the kernel reads words [s_h / 32, (s_h + b_h - 1) / 32] of a row only, all inside the row's
+    mask_words words (md_head_valid, csrc/heads.hip), writes row r's results to row r of buffers that hold cap rows, and treats a
+    head whose stale bits name no valid bin as all-valid -- a stale row can neither read nor write out of bounds nor divide by an
+    empty sum, and its results are ignored like those of its stale observation.
+    The Gaussian head has no mask: masked=True raises for it."""
 
     def __init__(self, pol, cap, masked=False):
         a = pol.arena
         dev, d = a.device, a.d_in
         self.cap = cap
         self.masked = bool(masked)
-        self.mask_words = AM.mask_words(pol.n_actions) if masked else 0
+        raw = getattr(pol, "_act_launch_raw", None)  # [r3] a head whose whole step is one launch on raw observations
+        if masked and raw is None and not getattr(pol, "_masked_chain", False):
+            raise ValueError("ActGraph: a masked graph needs the one-launch step of the discrete head or the masked general kernel of "
+                             "the multi-discrete head (%s has neither)" % type(pol).__name__)
+        self.mask_words = AM.mask_words(pol._mask_spec()[0]) if masked else 0
         self.mask_pin = None   # the words' home under RLPPO_ACT_PUSH=0 (or without a host window): made below, only then
         self.dev = dev
         self.obs_pin = torch.zeros(cap, d).pin_memory()
@@ -67,7 +82,6 @@ class ActGraph:
         self.act_pin = pol._action_buffer(cap).pin_memory()
         self.logp_pin = torch.zeros(cap, dtype=torch.float32).pin_memory()
         L = N.lib()
-        raw = getattr(pol, "_act_launch_raw", None)  # [r3] a head whose whole step is one launch on raw observations
         ws_bytes = max(int(L.rlppo_forward_workspace_bytes(a.dims_c, a.n_layers, cap)), raw(None, cap) if raw is not None else 0)
         self.ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
 
@@ -112,8 +126,6 @@ class ActGraph:
                 self.push = False   # (a device that does not expose its memory to the host)
         self.padded = self.push and raw is None
         if masked:
-            if raw is None:
-                raise ValueError("ActGraph: a masked graph needs the one-launch step of the discrete head")
             # what the warm-up launch, the capture and the rows beyond a call's n read: all-valid words -- in the window (whose
             # allocation zero-fills it) written once here, in pinned memory from the start
             valid = torch.full((cap, self.mask_words), -1, dtype=torch.int32)
@@ -123,7 +135,10 @@ class ActGraph:
             else:
                 self.mask_pin = valid.pin_memory()
                 self.mask_arg = self.mask_pin.data_ptr()
-            self.opts.action_mask, self.opts.mask_words = self.mask_arg, self.mask_words
+            if raw is not None:
+                self.opts.action_mask, self.opts.mask_words = self.mask_arg, self.mask_words
+            else:   # (the multi-discrete head: the mask is the entry point's argument, an address + a row width like the window's rows)
+                self.mask_rows = _WindowRows(self.mask_arg, cap, self.mask_words)
         # [r5] late noise (rlppo_act_opts.noise_ctl): run() launches FIRST and draws the Exp(1) numbers afterwards -- the bit-exact
         # draw (5-11 us at 8-80 rows) then costs the call nothing, it hides behind the launch latency and the layers; the kernel
         # looks for control word 2 when its head layer starts.  Up to 256 rows: beyond that the draw outlasts the kernel.
@@ -145,6 +160,7 @@ class ActGraph:
         # one-node graph then cost 2-3 us more than the launch.  [r5] With completion polled instead of synchronised the replay is
         # the cheaper of the two by 2-3 us -- one hipGraphLaunch against a 22-argument ctypes call + hipLaunchKernel --
         # tools/small_batch_latency.py, profiles/r05_small_batch_latency.txt.)
+        chain_masked = self.masked and raw is None
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -154,6 +170,14 @@ class ActGraph:
         # thread_local: the shuffle pipeline's helper threads may be issuing copies / events on their own stream right now
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             body()
+        # Counter 6 of rlppo_dbg_counter (runs of the multi-discrete head's general kernels) is kept by the launchers when they are
+        # CALLED, and a replay calls none.  The masked chain's body calls the general sampling launcher exactly once: the warm-up's and
+        # the capture's counts are taken off again here and run() adds one per call, so that a masked small call counts as one run,
+        # like the eager call it replaces (for this graph the counter is host-maintained: rlppo_dbg_count, include/rlppo.h).
+        self._count = None
+        if chain_masked:
+            N.check(L.rlppo_dbg_count(6, -2))
+            self._count = L.rlppo_dbg_count
         self.obs_np, self.q_np = self.obs_pin.numpy(), self.q_pin.view(-1).numpy()
         self.act_np, self.logp_np = self.act_pin.numpy(), self.logp_pin.numpy()
         self.done_np = self.done_pin.numpy()
@@ -185,7 +209,10 @@ class ActGraph:
             return
         if not self.padded:
             N.check(N.lib().rlppo_pad_rows(stream_ptr(), ptr(self.obs_arg), 0, cap, a.d_in, a.d_in, ptr(self.rows), a.ld_in, 0, 0.0, 1.0))
-        pol._act_launch(self.rows, cap, self.q_arg, self.act_pin, self.logp_pin, self.ws, self.opts)
+        if self.masked:
+            pol._act_launch(self.rows, cap, self.q_arg, self.act_pin, self.logp_pin, self.ws, self.opts, mask_words=self.mask_rows)
+        else:
+            pol._act_launch(self.rows, cap, self.q_arg, self.act_pin, self.logp_pin, self.ws, self.opts)
 
     def run(self, obs, q, n, draw=None, verify=None, mask_words=None):
         """obs [n, d] float32 numpy; q: the call's noise (CPU tensor) or None with draw(): called for it -- AFTER the launch when
@@ -236,6 +263,8 @@ class ActGraph:
         if self.push:
             self._flush(self.window)
         self.calls += 1
+        if self._count is not None:
+            self._count(6, 1)
         value, count = self._launch(n)
         if self.late:
             # the kernel is on its way: now the noise.  Whatever happens here control word 2 gets this call's sequence (a kernel left
@@ -322,8 +351,9 @@ class ArenaModule(nn.Module):
     def _graph_act(self, obs, noise, standardize, action_mask=None):
         """get_action for a small HOST batch as one graph replay, or None when that form does not apply (device inputs, fused
         standardisation, device-drawn noise, more than act_graph_max rows): the caller then takes the eager path.
-        action_mask (the discrete head): a HOST mask [n, n_actions] is packed on the host -- no device work -- and staged with the
-        observations of a masked graph, cached beside the unmasked ones; a device mask or packed device words: the eager path."""
+        action_mask (the discrete and the multi-discrete head): a HOST mask [n, n_actions] ([n, sum(bins)]: one entry per logit) is
+        packed on the host -- no device work -- and staged with the observations of a masked graph, cached beside the unmasked
+        ones; a device mask or packed device words: the eager path."""
         if not self.act_graphs or standardize is not None or self.noise_mode != "host":
             return None
         if action_mask is not None and (isinstance(action_mask, AM.Packed) or (isinstance(action_mask, torch.Tensor) and action_mask.is_cuda)):
@@ -356,7 +386,9 @@ class ArenaModule(nn.Module):
         words = None
         if action_mask is not None:
             # (raises for a malformed mask or a row without a valid action -- here, before anything is staged or launched)
-            words = AM.pack_host(action_mask.numpy() if isinstance(action_mask, torch.Tensor) else action_mask, self.n_actions)
+            # (the multi-discrete head: every head of every row needs a valid bin, the error names row and head)
+            width, heads = self._mask_spec()
+            words = AM.pack_host(action_mask.numpy() if isinstance(action_mask, torch.Tensor) else action_mask, width, heads=heads)
             if words.shape[0] != n:
                 raise ValueError(f"action mask has {words.shape[0]} rows, the call {n}")
         key = _bucket(n) if words is None else (_bucket(n), True)   # masked graphs beside the unmasked ones: (bucket, masked)
@@ -372,6 +404,10 @@ class ArenaModule(nn.Module):
             return g.run(o, q, n, self._draw_bound(n), self._verify, words)
         a.ensure_packed()
         return g.run(o, q, n, self._draw_bound(n), None, words)
+
+    def _mask_spec(self):
+        """(entries of a mask row, the multi-discrete head's bins or None): what util.action_mask.pack_host holds a host mask to."""
+        return self.n_actions, None
 
     def _draw_bound(self, n):
         return lambda: self._draw_noise(n)

@@ -10,7 +10,9 @@ kernels (rlppo_multidiscrete_act_nvec; limits: include/rlppo.h, RLPPO_MD_MAX_*).
 LOGIT, [n, sum(bins)] bool / 0-1 (host or device, or util.action_mask.Packed), head h owning columns [s_h, s_h + b_h).  A head's
 distribution is the Categorical over its valid bins; every head of every row needs at least one (a host mask is checked, naming row
 and head).  A masked call always runs the general kernels, also on the reference's bins; get_output returns logits, which no mask
-changes, and keeps refusing one."""
+changes, and keeps refusing one.  A host mask on a small host batch rides a masked hipGraph like the unmasked small call
+(ppo/_mlp.py::ActGraph, cached under (bucket, True)): the mask is packed and checked on the host and its words are staged with the
+observations; a device mask or a Packed one takes the eager path."""
 import ctypes
 
 import numpy as np
@@ -109,8 +111,8 @@ class MultiDiscreteFF(ArenaModule):
                 action.append(logits[..., start:start + split].argmax(dim=-1))
                 start += split
             return torch.stack(action).cpu().numpy(), 0
-        # small host batches: one hipGraph replay (ppo/_mlp.py); a masked call takes the general path
-        out = self._graph_act(obs, noise, standardize) if action_mask is None else None
+        # small host batches: one hipGraph replay (ppo/_mlp.py), with a host mask too (its words are staged with the observations)
+        out = self._graph_act(obs, noise, standardize, action_mask)
         if out is not None:
             return out
         rows = a.stage_obs(obs, standardize)
@@ -118,6 +120,11 @@ class MultiDiscreteFF(ArenaModule):
         return actions.cpu(), logp.cpu()
 
     # ---- hooks of the graph-replayed rollout step (ppo/_mlp.py::ActGraph)
+    _masked_chain = True  # a masked graph's body: the layer chain + rlppo_multidiscrete_act_nvec_masked (no one-launch step here)
+
+    def _mask_spec(self):
+        return self.n_logits, self.splits
+
     def _noise_shape(self, n):
         return (n * self.n_heads, self.max_bins)
 

@@ -33,6 +33,21 @@ def mask_words(n_actions):
     return (int(n_actions) + 31) // 32
 
 
+_STARTS = {}
+
+
+def _heads_ok(m, heads):
+    """bool [n, sum(heads)], heads a tuple of ints >= 1 -> True when every head of every row keeps a valid bin: one pass over the
+    rows for all heads (this runs per small get_action call of a masked multi-discrete rollout).  False = look closer (the callers'
+    loops word the error)."""
+    starts = _STARTS.get(heads)
+    if starts is None:
+        if not heads or min(heads) < 1 or len(_STARTS) > 64:
+            return False
+        starts = _STARTS[heads] = np.cumsum((0,) + heads[:-1])
+    return m.shape[0] > 0 and bool(np.logical_or.reduceat(m, starts, axis=1).all())
+
+
 def check_heads(mask, heads):
     """Host bool / 0-1 [n, sum(heads)]: a head without a valid bin raises ValueError naming the row and the head (a head with
     exactly one valid bin is fine: it contributes log-probability 0 and entropy 0)."""
@@ -43,6 +58,8 @@ def check_heads(mask, heads):
     if m.ndim != 2 or m.shape[1] != sum(heads):
         raise ValueError(f"action mask shape {tuple(m.shape)} != (n, {sum(heads)}) for bins {tuple(heads)}")
     m = m != 0
+    if _heads_ok(m, tuple(heads)):
+        return
     s = 0
     for h, b in enumerate(heads):
         empty = np.flatnonzero(~m[:, s:s + b].any(axis=1))
@@ -60,11 +77,12 @@ def pack_host(mask, n_actions, heads=None):
     if m.ndim != 2 or m.shape[1] != int(n_actions):
         raise ValueError(f"action mask shape {tuple(m.shape)} != (n, {int(n_actions)})")
     m = m != 0
-    if heads is not None:
-        check_heads(m, heads)
-    empty = np.flatnonzero(~m.any(axis=1))
-    if empty.size:
-        raise ValueError(f"action mask: row {int(empty[0])} has no valid action")
+    if heads is None or not _heads_ok(m, tuple(int(b) for b in heads)):   # (every head with a valid bin: every row with a valid action)
+        if heads is not None:
+            check_heads(m, heads)
+        empty = np.flatnonzero(~m.any(axis=1))
+        if empty.size:
+            raise ValueError(f"action mask: row {int(empty[0])} has no valid action")
     w = mask_words(n_actions)
     padded = np.zeros((m.shape[0], w * 32), dtype=bool)
     padded[:, :m.shape[1]] = m
