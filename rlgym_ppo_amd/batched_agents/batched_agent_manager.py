@@ -21,6 +21,7 @@ import torch
 
 from .. import _native as N
 from ..util import WelfordRunningStat
+from ..util import action_mask as AM
 from . import comm_consts as C
 from .batched_agent import _as_f32, batched_agent_process, describe_action_space, env_action_masks
 from .batched_trajectory import BatchedTrajectory
@@ -188,7 +189,7 @@ class BatchedAgentManager(object):
         # WIDTH of a mask row: the action count of a Discrete space, one entry per logit -- sum(nvec) -- of a MultiDiscrete one
         # (action rows are then len(nvec) wide); mask_space_type: the action space type of the shapes reply (0 / 1)
         self.masked, self.n_actions, self.mask_space_type = False, 0, 0
-        self._mask_layout_cache = None
+        self._wire_layout = None   # a masked discrete run: util.action_mask.Layout(n_actions), made when the width is learnt
         self.next_mask, self.current_mask = [], []
         self.action_mask_rows = None
         self._average_reward = None
@@ -238,8 +239,7 @@ class BatchedAgentManager(object):
         self.current_obs = [None] * n
         self.next_obs = [None] * n
         self.current_mask, self.next_mask = [None] * n, [None] * n
-        self.masked, self.n_actions, self.action_mask_rows = False, 0, None
-        self.mask_space_type, self._mask_layout_cache = 0, None
+        self.masked, self.n_actions, self.action_mask_rows, self.mask_space_type, self._wire_layout = False, 0, None, 0, None
         self.selector = selectors.DefaultSelector()
         if n_processes <= 0:
             self.processes = [_LocalWorker(build_env_fn, collect_metrics_fn, self.seed)]
@@ -305,8 +305,8 @@ class BatchedAgentManager(object):
             from ..ppo.multi_discrete_policy import MultiDiscreteFF
             head = {0: DiscreteFF, 1: MultiDiscreteFF}.get(code)
             # (the policy is usually built from what this call returns: the action space decides)
-            refusal = "the environment offers action_masks(): invalid-action masking is an option of the discrete head (DiscreteFF) " \
-                      "and of the multi-discrete head (MultiDiscreteFF)"
+            # (AM.REFUSAL: "invalid-action masking is an option of the discrete head (DiscreteFF) and of the multi-discrete head ...")
+            refusal = "the environment offers action_masks(): " + AM.REFUSAL
             if head is None:
                 raise ValueError(f"{refusal}, not of an action space of type {code}")
             if isinstance(self.policy, ArenaModule) and not isinstance(self.policy, head):
@@ -322,47 +322,34 @@ class BatchedAgentManager(object):
             if code == 1 and width < n_acts:
                 raise ValueError(f"the reset states carry masks of {width} entries, fewer than the {n_acts} components of the "
                                  "MultiDiscrete action space (a mask has one entry per bin of every component)")
-            self.n_actions, self.mask_space_type, self._mask_layout_cache = width, code, None
+            self.n_actions, self.mask_space_type = width, code
+            self._wire_layout = AM.Layout(width) if code == 0 else None
             for w in self.processes:
                 w.n_actions = width
 
     def _mask_layout(self):
-        """-> the bins of a masked multi-discrete run (None for the discrete head), after holding the width of the workers' masks
-        against the policy's layout (policy.n_logits, policy.splits: the pair VectorAgentManager._mask_layout reads).  Worked out
-        once per policy object; every collect asks before it sends an action."""
-        cached = self._mask_layout_cache
-        if cached is not None and cached[0] is self.policy:
-            return cached[1]
-        heads = None
-        if self.mask_space_type == 1:
-            n_logits, splits = getattr(self.policy, "n_logits", None), getattr(self.policy, "splits", None)
-            if n_logits is None or splits is None:
-                raise ValueError("the environment offers action_masks() on a MultiDiscrete action space: invalid-action masking needs the "
-                                 f"multi-discrete head's layout (policy.n_logits, policy.splits), which {type(self.policy).__name__} lacks")
-            heads = [int(b) for b in splits]
-            if int(n_logits) != self.n_actions or sum(heads) != self.n_actions:
-                raise ValueError(f"the workers' action masks have {self.n_actions} entries per agent, but the policy's bins {heads} have "
-                                 f"{sum(heads)} logits: action_masks() must answer one entry per bin of every component")
-        self._mask_layout_cache = (self.policy, heads)
-        return heads
+        """-> the util.action_mask.Layout of the run's masks.  A discrete run: the width the workers sent (any policy whose get_action
+        takes action_mask serves it).  A multi-discrete run: the policy's own layout, after holding the workers' width against it;
+        every collect asks before it sends an action."""
+        if self.mask_space_type != 1:
+            return self._wire_layout
+        lay = AM.Layout.of(self.policy)
+        if lay.heads is None:
+            raise ValueError(f"the workers' action masks are those of a MultiDiscrete action space, but {type(self.policy).__name__} "
+                             f"states a discrete layout of {lay.width} actions and no bins")
+        if lay.width != self.n_actions:
+            raise ValueError(f"the workers' action masks have {self.n_actions} entries per agent, but the policy's bins "
+                             f"{list(lay.heads)} have {lay.width} logits: action_masks() must answer one entry per bin of every component")
+        return lay
 
     def _checked_masks(self, ready):
         """The stacked mask rows of the ready workers; a row without a valid action -- in a multi-discrete run: a head of a row
         without a valid bin -- raises before anything is sent."""
-        heads = self._mask_layout()
-        if heads is not None:
-            starts = np.cumsum([0] + heads[:-1])
-            for pid in ready:
-                ok = np.logical_or.reduceat(self.current_mask[pid], starts, axis=1)   # [n_agents, H]: head h keeps a valid bin
-                if not ok.all():
-                    agent, h = (int(x) for x in np.argwhere(~ok)[0])                  # (the first agent, its first such head)
-                    raise ValueError(f"action mask: worker {pid}, agent {agent}, head {h} (bins {int(starts[h])} .. "
-                                     f"{int(starts[h]) + heads[h] - 1}) has no valid bin")
-            return np.concatenate([self.current_mask[pid] for pid in ready], axis=0)
+        lay = self._mask_layout()
         for pid in ready:
-            empty = np.flatnonzero(~self.current_mask[pid].any(axis=1))
-            if empty.size:
-                raise ValueError(f"action mask: worker {pid}, agent {int(empty[0])} has no valid action")
+            bad = lay.first_empty(self.current_mask[pid])
+            if bad is not None:
+                raise ValueError(f"action mask: worker {pid}, agent {bad[0]}{lay.what(bad[1])}")
         return np.concatenate([self.current_mask[pid] for pid in ready], axis=0)
 
     # ------------------------------------------------------------------------------------------- rollout
@@ -542,7 +529,7 @@ class BatchedAgentManager(object):
         self._native = h
         if self.masked:
             N.check(N.lib().rlppo_collector_set_masked(h, self.n_actions))
-            heads = self._mask_layout()
+            heads = self._mask_layout().heads
             if heads is not None:   # the multi-discrete head: _ready_masks holds every row to the per-head rule
                 N.check(N.lib().rlppo_collector_set_mask_heads(h, (ctypes.c_int32 * len(heads))(*heads), len(heads)))
         for pid, o in enumerate(self.current_obs):

@@ -72,38 +72,19 @@ class VectorAgentManager(object):
         fn = getattr(self.env, "action_masks", None)
         if fn is None:
             return None
-        width, heads = self._mask_layout()
+        lay = AM.Layout.of(self.policy)
         m = np.asarray(fn())
         if m.ndim == 1:   # a one-agent environment may answer [n_actions]
             m = m.reshape(1, -1)
-        if m.ndim != 2 or m.shape[1] != width:
-            raise ValueError(f"the environment's action_masks() has shape {tuple(m.shape)}: its width must be {width}, the policy's "
-                             + ("logit count sum(bins) (one entry per bin of every component)" if heads is not None else "action count"))
-        return AM.pack(m, width, self.policy.arena.device, heads=heads)
-
-    def _mask_layout(self):
-        """(entries of a mask row, the multi-discrete head's bins or None): n_actions of the discrete head; one entry per logit,
-        sum(bins), of the multi-discrete head.  Worked out once per policy object (every rollout step asks)."""
-        cached = getattr(self, "_mask_layout_cache", None)
-        if cached is not None and cached[0] is self.policy:
-            return cached[1]
-        self._mask_layout_cache = (self.policy, self._mask_layout_of_policy())
-        return self._mask_layout_cache[1]
-
-    def _mask_layout_of_policy(self):
-        from ..ppo.discrete_policy import DiscreteFF
-        from ..ppo.multi_discrete_policy import MultiDiscreteFF
-        if isinstance(self.policy, DiscreteFF):
-            return self.policy.n_actions, None
-        if isinstance(self.policy, MultiDiscreteFF):
-            return self.policy.n_logits, self.policy.splits
-        raise ValueError("the environment offers action_masks(): invalid-action masking is an option of the discrete head "
-                         f"(DiscreteFF) and of the multi-discrete head (MultiDiscreteFF), not of {type(self.policy).__name__}")
+        if m.ndim != 2 or m.shape[1] != lay.width:
+            raise ValueError(f"the environment's action_masks() has shape {tuple(m.shape)}: its width must be {lay.width}, the policy's "
+                             + ("logit count sum(bins) (one entry per bin of every component)" if lay.heads is not None else "action count"))
+        return lay.pack(m, self.policy.arena.device)
 
     def _masks_out(self, M, na, T):
         """Time-major words [T, na, W] -> self.action_mask_rows, trajectory-major (row a * T + t)."""
         self.action_mask_rows = None if M is None else AM.Packed(M.transpose(0, 1).reshape(na * T, M.shape[2]).contiguous(),
-                                                                 self._mask_layout()[0])
+                                                                 AM.Layout.of(self.policy).width)
 
     @property
     def action_masks(self):
@@ -208,17 +189,15 @@ class VectorAgentManager(object):
         obs_dev, scalars = self._pending_obs
         stage = self._obs_staging(na, arena.d_in)
         mask, M = self._first_mask(), None
+        width = None if mask is None else AM.Layout.of(self.policy).width
         final_rows = []   # bootstrap_truncated: (t, agents, staged final observations) of environment-side truncations
         for t in range(T):
             if mask is not None:
                 if M is None:
                     M = torch.empty((T, na, mask.shape[1]), dtype=torch.int32, device=dev)
                 M[t].copy_(mask)
-                a_host, _ = self.policy.step(obs_dev, standardize=scalars, rows_out=S[t], actions_f32=acts_tm[t], logp_out=logp_tm[t],
-                                             to_host="actions", action_mask=AM.Packed(M[t], self.policy.n_actions))
-            else:
-                a_host, _ = self.policy.step(obs_dev, standardize=scalars, rows_out=S[t], actions_f32=acts_tm[t], logp_out=logp_tm[t],
-                                             to_host="actions")
+            a_host, _ = self.policy.step(obs_dev, standardize=scalars, rows_out=S[t], actions_f32=acts_tm[t], logp_out=logp_tm[t],
+                                         to_host="actions", action_mask=None if mask is None else AM.Packed(M[t], width))
             step = self.env.step(a_host.numpy().astype(np.float32).reshape(na, -1))
             if len(step) == 4:
                 obs, r, d, info = step
@@ -300,15 +279,14 @@ class VectorAgentManager(object):
             self._next_rows = arena.stage_obs(self._initial_obs)
         rows = self._next_rows
         mask, M = self._first_mask(), None
+        width = None if mask is None else AM.Layout.of(self.policy).width
         patched = False   # bootstrap_truncated: a final observation went into the next-state rows
         for t in range(T):
             if mask is not None:
                 if M is None:
                     M = torch.empty((T, na, mask.shape[1]), dtype=torch.int32, device=dev)
                 M[t].copy_(mask)
-                a_dev, lp_dev = self.policy.act_padded(rows, action_mask=AM.Packed(M[t], self._mask_layout()[0]))
-            else:
-                a_dev, lp_dev = self.policy.act_padded(rows)
+            a_dev, lp_dev = self.policy.act_padded(rows, action_mask=None if mask is None else AM.Packed(M[t], width))
             if acts is None:
                 k = 1 if a_dev.dim() == 1 else a_dev.shape[1]
                 acts = torch.empty((na, T, k), dtype=torch.float32, device=dev)

@@ -309,12 +309,15 @@ static int act_ctx(const rlppo_act_opts *o, ActCtx *c, bool late_noise = false, 
                     "act options: noise_ctl needs done_words (a kernel that gives up on the noise reports it there) and done_value < 2^31");
     return 0;
 }
-// [ABI 8] a call's mask has the width its action count needs
-static int act_mask_check(const ActCtx &c, int n_actions) {
-    RLPPO_CHECK_ARG(!c.mask || c.mask_words == (n_actions + 31) / 32, "act options: mask_words=%d, but n_actions=%d needs %d words per row",
-                    c.mask_words, n_actions, (n_actions + 31) / 32);
+// [ABI 8] a mask has the words per row its entries need.  who: the caller's name; logits: it calls an entry a logit, not an action
+// (every caller's message reads as it always did)
+static int mask_words_check(const void *mask, int mask_words, int bits, const char *who, bool logits) {
+    RLPPO_CHECK_ARG(!mask || mask_words == (bits + 31) / 32,
+                    logits ? "%s: mask_words=%d, but %d logits need %d words per row" : "%s: mask_words=%d, but n_actions=%d needs %d words per row",
+                    who, mask_words, bits, (bits + 31) / 32);
     return 0;
 }
+static int act_mask_check(const ActCtx &c, int n_actions) { return mask_words_check(c.mask, c.mask_words, n_actions, "act options", false); }
 // the completion words of a call whose last launch does not write them itself: one more (tiny) launch behind it
 static int act_done(hipStream_t st, const ActCtx &c, int64_t n) {
     return c.done ? launch_signal_words(st, c.done, (int)rlppo_act_done_words(n), c.done_value) : 0;
@@ -628,8 +631,8 @@ static int multidiscrete_act_nvec(void *stream, const int32_t *dims, int32_t n_l
     rc = md_spec_make(nvec, n_heads, who, &spec);
     if (rc) return rc;
     RLPPO_CHECK_ARG(dims[n_layers] == spec.S, "%s: output width %d, but nvec sums to %d", who, dims[n_layers], spec.S);
-    RLPPO_CHECK_ARG(!mask || mask_words == (spec.S + 31) / 32, "%s: mask_words=%d, but %d logits need %d words per row", who, mask_words, spec.S,
-                    (spec.S + 31) / 32);
+    rc = mask_words_check(mask, mask_words, spec.S, who, true);
+    if (rc) return rc;
     if (n == 0) return 0;
     RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_q && actions && logp && workspace, "%s: bad argument", who);
     const float *o;
@@ -1382,8 +1385,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     RLPPO_CHECK_ARG(!a->action_mask || a->head == RLPPO_HEAD_DISCRETE || (a->head == RLPPO_HEAD_MULTIDISCRETE && md_nvec),
                     "ppo_minibatch: action_mask is an option of the discrete head, not of the %s head",
                     a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : "multi-discrete (without md_nvec: the fixed-bin kernels take no mask)");
-    RLPPO_CHECK_ARG(!a->action_mask || a->mask_words == (n_out + 31) / 32, "ppo_minibatch: mask_words=%d, but n_actions=%d needs %d words per row",
-                    a->mask_words, n_out, (n_out + 31) / 32);
+    if (int rc_mask = mask_words_check(a->action_mask, a->mask_words, n_out, "ppo_minibatch", false)) return rc_mask;
     if (a->head == RLPPO_HEAD_DISCRETE) {
         RLPPO_CHECK_ARG(a->act_dim == 1, "discrete head: act_dim must be 1");
         RLPPO_CHECK_ARG(pol.L[pol.n_layers - 1].pout <= DISCRETE_LOSS_MAX_LD, "discrete head: padded width %ld too large",

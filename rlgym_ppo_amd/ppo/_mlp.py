@@ -6,6 +6,7 @@ multi_discrete_policy.py:22-32, value_estimator.py:18-28): layers are built on t
 starts from the reference's weights bit for bit) and only then moved to the GPU arena.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -49,19 +50,16 @@ class ActGraph:
     batched_agent_manager.py:202-204) a call is nothing but latency -- ~7 launches, three copies and two blocking read-backs,
     ~140-250 us; one replay + one synchronisation does the same work, with no copy node at all.  Same kernels, same
     arguments: results are those of the eager path bit for bit.  Rows past the caller's n hold stale data and are ignored.
-    masked (the discrete head's one-launch step): the graph's call carries rlppo_act_opts.action_mask -- cap x mask_words
-    words in the window (or in pinned memory) that run() stages with the observations, before the flush and the launch; the noise
-    stays late.
-    masked (the multi-discrete head, which has no one-launch step): the body is the layer chain as in the unmasked graph -- its
-    first layer reads the host window, no pad launch -- followed by rlppo_multidiscrete_act_nvec_masked with the completion
-    words; the mask is that entry point's ARGUMENT (rlppo_act_opts.action_mask stays NULL: both multi-discrete entry points refuse
-    one there) and points at cap x ceil(sum(bins) / 32) words behind the noise in the window (pinned memory under
-    RLPPO_ACT_PUSH=0 or without a window).  The words are all-valid once, run() stages a call's n rows with its observations,
-    the noise is in place before the launch (late noise is the discrete one-launch kernel's alone).  Rows at and beyond n keep
-    the words of an earlier call: the kernel reads words [s_h / 32, (s_h + b_h - 1) / 32] of a row only, all inside the row's
-    mask_words words (md_head_valid, csrc/heads.hip), writes row r's results to row r of buffers that hold cap rows, and treats a
-    head whose stale bits name no valid bin as all-valid -- a stale row can neither read nor write out of bounds nor divide by an
-    empty sum, and its results are ignored like those of its stale observation.
+    masked: the call's packed mask words (util.action_mask.Layout: cap x Layout.of(pol).words int32) live behind the noise in the
+    window (in pinned memory under RLPPO_ACT_PUSH=0 or without a window).  They are all-valid once; run() stages a call's n rows
+    with its observations, before the flush and the launch.  The discrete head's one-launch step reads them through
+    rlppo_act_opts.action_mask and keeps its noise late.  The multi-discrete head has no one-launch step: its body is the
+    unmasked graph's layer chain followed by rlppo_multidiscrete_act_nvec_masked, which takes the words as an ARGUMENT
+    (rlppo_act_opts.action_mask stays NULL: both multi-discrete entry points refuse one there), with the noise in place before
+    the launch.  Rows at and beyond n keep the words of an earlier call: the kernel reads only words inside a row's own
+    (md_head_valid, csrc/heads.hip), writes row r's results to row r of buffers that hold cap rows, and treats a head whose stale
+    bits name no valid bin as all-valid -- a stale row can neither read nor write out of bounds nor divide by an empty sum, and
+    its results are ignored like those of its stale observation.
     The Gaussian head has no mask: masked=True raises for it."""
 
     def __init__(self, pol, cap, masked=False):
@@ -73,13 +71,14 @@ class ActGraph:
         if masked and raw is None and not getattr(pol, "_masked_chain", False):
             raise ValueError("ActGraph: a masked graph needs the one-launch step of the discrete head or the masked general kernel of "
                              "the multi-discrete head (%s has neither)" % type(pol).__name__)
-        self.mask_words = AM.mask_words(pol._mask_spec()[0]) if masked else 0
+        self.mask_words = AM.Layout.of(pol).words if masked else 0
         self.mask_pin = None   # the words' home under RLPPO_ACT_PUSH=0 (or without a host window): made below, only then
+        self.mask_rows = None  # the masked multi-discrete chain: the words as _act_launch's mask_words argument
         self.dev = dev
         self.obs_pin = torch.zeros(cap, d).pin_memory()
         self.q_pin = torch.ones(pol._noise_shape(cap)).pin_memory()
         self.rows = torch.zeros(cap, a.ld_in, device=dev)
-        self.act_pin = pol._action_buffer(cap).pin_memory()
+        self.act_pin = pol._action_buffer(cap).zero_().pin_memory()
         self.logp_pin = torch.zeros(cap, dtype=torch.float32).pin_memory()
         L = N.lib()
         ws_bytes = max(int(L.rlppo_forward_workspace_bytes(a.dims_c, a.n_layers, cap)), raw(None, cap) if raw is not None else 0)
@@ -209,10 +208,7 @@ class ActGraph:
             return
         if not self.padded:
             N.check(N.lib().rlppo_pad_rows(stream_ptr(), ptr(self.obs_arg), 0, cap, a.d_in, a.d_in, ptr(self.rows), a.ld_in, 0, 0.0, 1.0))
-        if self.masked:
-            pol._act_launch(self.rows, cap, self.q_arg, self.act_pin, self.logp_pin, self.ws, self.opts, mask_words=self.mask_rows)
-        else:
-            pol._act_launch(self.rows, cap, self.q_arg, self.act_pin, self.logp_pin, self.ws, self.opts)
+        pol._act_launch(self.rows, cap, self.q_arg, self.act_pin, self.logp_pin, self.ws, self.opts, self.mask_rows)
 
     def run(self, obs, q, n, draw=None, verify=None, mask_words=None):
         """obs [n, d] float32 numpy; q: the call's noise (CPU tensor) or None with draw(): called for it -- AFTER the launch when
@@ -337,6 +333,7 @@ class ArenaModule(nn.Module):
     #         seeded run picks the reference's actions (costs ~1 us per drawn number on the host);
     # "device": noise drawn on the GPU (what the reference does when it runs on cuda); no host work per step.
     noise_mode = "host"
+    mask_layout = None   # util.action_mask.Layout of a head that masks (DiscreteFF, MultiDiscreteFF): built once in __init__
 
     def _finish(self, device):
         self.device = device
@@ -387,8 +384,7 @@ class ArenaModule(nn.Module):
         if action_mask is not None:
             # (raises for a malformed mask or a row without a valid action -- here, before anything is staged or launched)
             # (the multi-discrete head: every head of every row needs a valid bin, the error names row and head)
-            width, heads = self._mask_spec()
-            words = AM.pack_host(action_mask.numpy() if isinstance(action_mask, torch.Tensor) else action_mask, width, heads=heads)
+            words = AM.Layout.of(self).pack_host(action_mask.numpy() if isinstance(action_mask, torch.Tensor) else action_mask)
             if words.shape[0] != n:
                 raise ValueError(f"action mask has {words.shape[0]} rows, the call {n}")
         key = _bucket(n) if words is None else (_bucket(n), True)   # masked graphs beside the unmasked ones: (bucket, masked)
@@ -405,9 +401,42 @@ class ArenaModule(nn.Module):
         a.ensure_packed()
         return g.run(o, q, n, self._draw_bound(n), None, words)
 
-    def _mask_spec(self):
-        """(entries of a mask row, the multi-discrete head's bins or None): what util.action_mask.pack_host holds a host mask to."""
-        return self.n_actions, None
+    def _mask_words(self, action_mask, n):
+        """The packed device words [n, W] of a call on n rows, or None without a mask.  action_mask: bool / 0-1 [n, width], host
+        (checked) or device, or util.action_mask.Packed; a head that cannot be masked refuses one."""
+        if action_mask is None:
+            return None
+        words = AM.Layout.of(self).pack(action_mask, self.arena.device)
+        if words.shape[0] != n:
+            raise ValueError(f"action mask has {words.shape[0]} rows, the call {n}")
+        return words
+
+    def _noise(self, n, noise):
+        """The noise of an eager call on n rows, contiguous float32 on the device: the caller's, or _draw_noise's -- the
+        reference's CPU stream, uploaded asynchronously, or (noise_mode == "device") torch's HIP generator."""
+        dev = self.arena.device
+        if noise is None:
+            noise = self._draw_noise(n, dev)
+        q = torch.as_tensor(noise, dtype=torch.float32).to(dev, non_blocking=True).contiguous()
+        shape = tuple(self._noise_shape(n))
+        if q.numel() != math.prod(shape):
+            raise ValueError(f"noise: {tuple(q.shape)} given, {n} rows need {shape}")
+        return q
+
+    def act_padded(self, rows, noise=None, action_mask=None):
+        """Padded device rows [n, ld_in] -> (actions [n] / [n, H] / [n, k], log_probs fp32 [n]) ON THE DEVICE: the part of
+        get_action after staging, for callers that keep the rollout on the GPU (VectorAgentManager).  The launch is the head's
+        _act_launch, the one ActGraph captures.  action_mask (the discrete and the multi-discrete head): see _mask_words; the
+        noise keeps its shape and its draw."""
+        a = self.arena
+        n = rows.shape[0]
+        words = self._mask_words(action_mask, n)
+        q = self._noise(n, noise)
+        a.ensure_packed()
+        actions = self._action_buffer(n, a.device)
+        logp = torch.empty(n, dtype=torch.float32, device=a.device)
+        self._act_launch(rows, n, q, actions, logp, a.forward_ws(n), None, words)
+        return actions, logp
 
     def _draw_bound(self, n):
         return lambda: self._draw_noise(n)

@@ -6,13 +6,14 @@ import torch.nn as nn
 
 from .. import _native as N
 from ..engine import ptr, stream_ptr
+from ..util import action_mask as AM
 from ..util import torch_functions
 from ._mlp import ArenaModule, build_body
 
 
 def _no_action_mask(action_mask):
     if action_mask is not None:
-        raise ValueError("action_mask: invalid-action masking is an option of the discrete head (DiscreteFF), not of the Gaussian head")
+        raise ValueError(f"action_mask: {AM.REFUSAL}, not of the Gaussian head")
 
 
 class ContinuousPolicy(ArenaModule):
@@ -52,36 +53,19 @@ class ContinuousPolicy(ArenaModule):
     def _noise_shape(self, n):
         return (n, self.n_out // 2)
 
-    def _draw_noise(self, n):
+    def _draw_noise(self, n, device=None):
+        if device is not None and self.noise_mode == "device":
+            return torch.empty(n, self.n_out // 2, device=device).normal_(0, 1)  # fast mode: torch's HIP generator, not the reference's CPU stream
         return torch.empty(n, self.n_out // 2).normal_(0, 1)  # what Normal.sample() draws on the reference's CPU path
 
-    def _action_buffer(self, cap):
-        return torch.zeros((cap, self.n_out // 2), dtype=torch.float32)
+    def _action_buffer(self, cap, device=None):
+        return torch.empty((cap, self.n_out // 2), dtype=torch.float32, device=device)
 
-    def _act_launch(self, rows, n, noise, actions, logp, ws, opts=None):
+    def _act_launch(self, rows, n, noise, actions, logp, ws, opts=None, mask_words=None):   # (mask_words: never given, act_padded refuses a mask)
         a = self.arena
         N.check(N.lib().rlppo_gaussian_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1], n,
                                            ptr(noise), float(self.affine_map.m), float(self.affine_map.b), ptr(actions),
                                            ptr(logp), ptr(ws), ws.numel(), opts))
-
-    def act_padded(self, rows, noise=None, action_mask=None):
-        """Padded device rows -> (actions fp32 [n, k], summed log_probs fp32 [n]) on the device (see DiscreteFF.act_padded)."""
-        _no_action_mask(action_mask)
-        a = self.arena
-        n, k = rows.shape[0], self.n_out // 2
-        if noise is None and self.noise_mode == "device":
-            noise = torch.empty(n, k, device=a.device).normal_(0, 1)  # fast mode: torch's HIP generator, not the reference's CPU stream
-        elif noise is None:
-            noise = torch.empty(n, k).normal_(0, 1)  # what Normal.sample() draws on the reference's CPU path
-        eps = torch.as_tensor(noise, dtype=torch.float32).to(a.device, non_blocking=True).contiguous()
-        a.ensure_packed()
-        actions = torch.empty((n, k), dtype=torch.float32, device=a.device)
-        logp = torch.empty(n, dtype=torch.float32, device=a.device)
-        ws = a.forward_ws(n)
-        N.check(N.lib().rlppo_gaussian_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1], n,
-                                           ptr(eps), float(self.affine_map.m), float(self.affine_map.b), ptr(actions),
-                                           ptr(logp), ptr(ws), ws.numel(), None))
-        return actions, logp
 
     @staticmethod
     def logpdf(x, mean, std):

@@ -23,20 +23,24 @@ class DiscreteFF(ArenaModule):
         super().__init__()
         self.model = build_body(input_shape, layer_sizes, n_actions, nn.Softmax(dim=-1))
         self.n_actions = int(n_actions)
+        self.mask_layout = AM.Layout(n_actions)
         self._host_out = None  # pinned (actions, log-probs) the fused step writes into (grown on demand)
         self._finish(device)
 
     def _mask_opts(self, action_mask, n):
         """(rlppo_act_opts carrying the packed mask, the packed words) of a call on n rows, or (None, None) without a mask.
         action_mask: bool / 0-1 [n, n_actions], host or device, or util.action_mask.Packed (already the kernels' words)."""
-        if action_mask is None:
-            return None, None
-        words = AM.pack(action_mask, self.n_actions, self.arena.device)
-        if words.shape[0] != n:
-            raise ValueError(f"action mask has {words.shape[0]} rows, the call {n}")
+        words = self._mask_words(action_mask, n)
+        return self._opts_of(words), words
+
+    @staticmethod
+    def _opts_of(words):
+        """The discrete kernels take the packed words in their options."""
+        if words is None:
+            return None
         opts = N.ActOpts()
         opts.action_mask, opts.mask_words = words.data_ptr(), words.shape[1]
-        return opts, words
+        return opts
 
     def _probs(self, rows, clamp, want_probs=True, want_argmax=False, action_mask=None):
         """rlppo_discrete_probs on padded device rows: softmax (or clamp(softmax)) [n, n_actions] and/or the flat arg-max."""
@@ -110,12 +114,7 @@ class DiscreteFF(ArenaModule):
         n, d = t.shape
         if d != a.d_in:
             raise ValueError(f"observation width {d} != network input {a.d_in}")
-        if noise is None and self.noise_mode == "device":
-            q = torch.empty(n, self.n_actions, device=a.device).exponential_(1)  # fast mode: not the reference's CPU stream
-        elif noise is None:
-            q = host_exponential((n, self.n_actions), device=a.device)
-        else:
-            q = torch.as_tensor(noise, dtype=torch.float32).to(a.device, non_blocking=True).contiguous()
+        q = self._noise(n, noise)
         if tuple(q.shape) != (n, self.n_actions):
             raise ValueError(f"noise shape {tuple(q.shape)} != {(n, self.n_actions)}")
         mode, mean0, std0, mean_v, std_v = 0, 0.0, 1.0, None, None
@@ -162,14 +161,22 @@ class DiscreteFF(ArenaModule):
     def _noise_shape(self, n):
         return (n, self.n_actions)
 
-    def _draw_noise(self, n):
-        return host_exponential((n, self.n_actions))  # == torch.empty(n, A).exponential_(1), drawn ahead (engine.py)
+    def _draw_noise(self, n, device=None):
+        if device is not None and self.noise_mode == "device":
+            return torch.empty(n, self.n_actions, device=device).exponential_(1)  # fast mode: torch's HIP generator, not the reference's CPU stream
+        # == torch.empty(n, A).exponential_(1), drawn ahead (engine.py); with a device: uploaded asynchronously (the pinned ring
+        # slot is event-protected)
+        return host_exponential((n, self.n_actions), device=device)
 
-    def _action_buffer(self, cap):
-        return torch.zeros(cap, dtype=torch.int64)
+    def _action_buffer(self, cap, device=None):
+        return torch.empty(cap, dtype=torch.int64, device=device)
 
-    def _act_launch(self, rows, n, noise, actions, logp, ws, opts=None):
+    def _act_launch(self, rows, n, noise, actions, logp, ws, opts=None, mask_words=None):
         a = self.arena
+        if mask_words is not None:   # (the words travel in the options: a caller with options of its own puts them there itself)
+            if opts is not None:
+                raise ValueError("DiscreteFF._act_launch: opts and mask_words are one argument here, give one of them")
+            opts = self._opts_of(mask_words)
         N.check(N.lib().rlppo_discrete_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1], n,
                                            ptr(noise), ptr(actions), ptr(logp), None, ptr(ws), ws.numel(), opts))
 
@@ -188,26 +195,6 @@ class DiscreteFF(ArenaModule):
                                          ctypes.byref(opts) if opts is not None else None))
         N.check(L.rlppo_discrete_step(stream_ptr(), *args[1]))
 
-    def act_padded(self, rows, noise=None, action_mask=None):
-        """Padded device rows [n, ld_in] -> (actions int64 [n], log_probs fp32 [n]) ON THE DEVICE: the part of get_action
-        after staging, for callers that keep the rollout on the GPU (VectorAgentManager).  action_mask: as in step()."""
-        a = self.arena
-        n = rows.shape[0]
-        opts, _words = self._mask_opts(action_mask, n)
-        if noise is None and self.noise_mode == "device":
-            noise = torch.empty(n, self.n_actions, device=a.device).exponential_(1)  # fast mode: torch's HIP generator, not the reference's CPU stream
-        elif noise is None:  # the reference's CPU stream, uploaded asynchronously (the pinned ring slot is event-protected)
-            noise = host_exponential((n, self.n_actions), device=a.device)
-        q = torch.as_tensor(noise, dtype=torch.float32).to(a.device, non_blocking=True).contiguous()
-        a.ensure_packed()
-        actions = torch.empty(n, dtype=torch.int64, device=a.device)
-        logp = torch.empty(n, dtype=torch.float32, device=a.device)
-        ws = a.forward_ws(n)
-        N.check(N.lib().rlppo_discrete_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1], n,
-                                           ptr(q), ptr(actions), ptr(logp), None, ptr(ws), ws.numel(),
-                                           ctypes.byref(opts) if opts is not None else None))
-        return actions, logp
-
     def get_backprop_data(self, obs, acts, action_mask=None):
         """Compatibility accessor with an autograd graph (discrete_policy.py:64-80), evaluated by stock PyTorch
         on the same parameters.  PPOLearner.learn does NOT use it: the update runs in rlppo_ppo_minibatch.
@@ -220,9 +207,9 @@ class DiscreteFF(ArenaModule):
             probs = torch.clamp(self.model(obs).view(-1, self.n_actions), min=1e-11, max=1)
             log_probs = torch.log(probs)
             return log_probs.gather(-1, acts), -(log_probs * probs).sum(dim=-1).mean()
-        m = torch.as_tensor(np.asarray(action_mask) if not isinstance(action_mask, torch.Tensor) else action_mask).to(obs.device) != 0
-        m = m.view(-1, self.n_actions)
-        m = torch.where(m.any(dim=-1, keepdim=True), m, torch.ones_like(m))  # a row without a valid action: all-valid
+        if not isinstance(action_mask, (torch.Tensor, AM.Packed)):           # (this accessor never checked a host array: as a tensor)
+            action_mask = torch.as_tensor(np.asarray(action_mask))
+        m = self.mask_layout.valid(action_mask, obs.device)                  # (a row without a valid action: all-valid)
         logits = self.model[:-1](obs).view(-1, self.n_actions)               # (the body without its Softmax)
         probs = torch.clamp(torch.softmax(logits.masked_fill(~m, float("-inf")), dim=-1), min=1e-11, max=1)
         log_probs = torch.log(probs)

@@ -57,6 +57,7 @@ class MultiDiscreteFF(ArenaModule):
         self.model = build_body(input_shape, layer_sizes, sum(bins))
         self.splits = bins
         self.n_heads, self.max_bins, self.n_logits = len(bins), max(bins), sum(bins)
+        self.mask_layout = AM.Layout(self.n_logits, bins)   # one mask entry per logit
         # the general kernels' nvec (HOST memory the library reads during a call); None = the reference's bins on the fixed kernels.
         # (`_force_general`: measurements run the general kernels on the reference's bins -- tools/multidiscrete_bins_cost.py)
         self._force_general = False
@@ -70,29 +71,6 @@ class MultiDiscreteFF(ArenaModule):
         """The ctypes nvec the library's general kernels take, or None where the fixed kernels (the reference's bins) run."""
         return self._nvec_c if (self._general or self._force_general) else None
 
-    def _mask_words(self, action_mask, n):
-        """The packed device words [n, W] of a call on n rows (one bit per logit), or None without a mask."""
-        if action_mask is None:
-            return None
-        words = AM.pack(action_mask, self.n_logits, self.arena.device, heads=self.splits)
-        if words.shape[0] != n:
-            raise ValueError(f"action mask has {words.shape[0]} rows, the call {n}")
-        return words
-
-    def _valid(self, action_mask, device):
-        """bool [n, S] on `device` of a mask in any accepted form; a head without a valid bin counts as all-valid (the kernels' rule
-        for masks that were not checked on the host)."""
-        if isinstance(action_mask, AM.Packed):
-            m = action_mask.unpack()
-        elif isinstance(action_mask, torch.Tensor):
-            m = action_mask.detach() != 0
-        else:
-            AM.check_heads(action_mask, self.splits)
-            m = torch.as_tensor(np.asarray(action_mask)) != 0
-        m = m.to(device).view(-1, self.n_logits)
-        parts = [torch.where(p.any(dim=-1, keepdim=True), p, torch.ones_like(p)) for p in torch.split(m, self.splits, dim=-1)]
-        return torch.cat(parts, dim=-1)
-
     @torch.no_grad()
     def get_output(self, obs, action_mask=None):
         _no_action_mask(action_mask)
@@ -105,7 +83,7 @@ class MultiDiscreteFF(ArenaModule):
         if deterministic:
             logits = self.get_output(obs)
             if action_mask is not None:  # the arg-max over each head's valid bins
-                logits = logits.masked_fill(~self._valid(action_mask, logits.device), float("-inf"))
+                logits = logits.masked_fill(~self.mask_layout.valid(action_mask, logits.device), float("-inf"))
             action, start = [], 0
             for split in self.splits:
                 action.append(logits[..., start:start + split].argmax(dim=-1))
@@ -122,18 +100,17 @@ class MultiDiscreteFF(ArenaModule):
     # ---- hooks of the graph-replayed rollout step (ppo/_mlp.py::ActGraph)
     _masked_chain = True  # a masked graph's body: the layer chain + rlppo_multidiscrete_act_nvec_masked (no one-launch step here)
 
-    def _mask_spec(self):
-        return self.n_logits, self.splits
-
     def _noise_shape(self, n):
         return (n * self.n_heads, self.max_bins)
 
-    def _draw_noise(self, n):
+    def _draw_noise(self, n, device=None):
+        if device is not None and self.noise_mode == "device":
+            return torch.empty(self._noise_shape(n), device=device).exponential_(1)  # fast mode: torch's HIP generator, not the reference's CPU stream
         # Categorical.sample -> multinomial on [n*H, B]: torch.empty(n*H, B).exponential_(1)
-        return host_exponential((n * self.n_heads, self.max_bins))
+        return host_exponential(self._noise_shape(n), device=device)
 
-    def _action_buffer(self, cap):
-        return torch.zeros((cap, self.n_heads), dtype=torch.int64)
+    def _action_buffer(self, cap, device=None):
+        return torch.empty((cap, self.n_heads), dtype=torch.int64, device=device)
 
     def _act_launch(self, rows, n, noise, actions, logp, ws, opts=None, mask_words=None):
         a = self.arena
@@ -150,26 +127,6 @@ class MultiDiscreteFF(ArenaModule):
                                                          n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(),
                                                          opts, nvec, self.n_heads))
 
-    def act_padded(self, rows, noise=None, action_mask=None):
-        """Padded device rows -> (actions int64 [n, H], log_probs fp32 [n]) on the device (see DiscreteFF.act_padded).
-        action_mask: optional [n, sum(bins)] valid = 1 (or util.action_mask.Packed); the noise keeps its shape and its draw."""
-        a = self.arena
-        n = rows.shape[0]
-        words = self._mask_words(action_mask, n)
-        H, B = self.n_heads, self.max_bins
-        if noise is None and self.noise_mode == "device":
-            noise = torch.empty(n * H, B, device=a.device).exponential_(1)  # fast mode: torch's HIP generator, not the reference's CPU stream
-        elif noise is None:
-            noise = host_exponential((n * H, B), device=a.device)  # Categorical.sample -> multinomial on [n*H, B]
-        q = torch.as_tensor(noise, dtype=torch.float32).to(a.device, non_blocking=True).contiguous()
-        a.ensure_packed()
-        if q.numel() != n * H * B:
-            raise ValueError(f"noise: {tuple(q.shape)} given, {n} rows of bins {self.splits} need ({n * H}, {B})")
-        actions = torch.empty((n, H), dtype=torch.int64, device=a.device)
-        logp = torch.empty(n, dtype=torch.float32, device=a.device)
-        self._act_launch(rows, n, q, actions, logp, a.forward_ws(n), mask_words=words)
-        return actions, logp
-
     def get_backprop_data(self, obs, acts, action_mask=None):
         """Compatibility accessor with an autograd graph (multi_discrete_policy.py:76-89); unused by PPOLearner.
         action_mask (optional): the masked semantics of the update -- invalid logits -inf before make_distribution."""
@@ -178,6 +135,6 @@ class MultiDiscreteFF(ArenaModule):
         dist = self.multi_discrete
         logits = self.model(obs)
         if action_mask is not None:
-            logits = logits.masked_fill(~self._valid(action_mask, logits.device).view(logits.shape), float("-inf"))
+            logits = logits.masked_fill(~self.mask_layout.valid(action_mask, logits.device).view(logits.shape), float("-inf"))
         dist.make_distribution(logits)
         return dist.log_prob(acts), dist.entropy().mean()

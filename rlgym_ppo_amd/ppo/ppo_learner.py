@@ -32,6 +32,7 @@ import torch
 from .. import _native as N
 from ..dp import all_reduce_sum, dist_info, fuse_runs, slices_for_rank
 from ..engine import Workspace, ptr, require_gpu, stream_ptr
+from ..util import action_mask as AM
 from .continuous_policy import ContinuousPolicy
 from .discrete_policy import DiscreteFF
 from .multi_discrete_policy import MultiDiscreteFF, check_bins
@@ -254,12 +255,13 @@ class PPOLearner(object):
         a.targets = st["values"].data_ptr()
         a.advantages = st["advantages"].data_ptr()
         if "action_masks" in st:  # invalid-action masking (ExperienceBuffer.submit_experience(..., action_masks=...))
-            if self.policy_type not in (0, 1):
-                raise ValueError("the experience buffer holds action masks: invalid-action masking is an option of the discrete head "
-                                 f"and of the multi-discrete head, not of policy_type {self.policy_type}")
-            if self.policy_type == 1 and exp.mask_width != self.policy.n_logits:  # one mask entry per logit, [n, sum(bins)]
-                raise ValueError(f"the experience buffer's action masks have {exp.mask_width} entries per row, the multi-discrete policy has "
-                                 f"{self.policy.n_logits} logits (one entry per bin of every component)")
+            lay = self.policy.mask_layout
+            if lay is None:
+                raise ValueError(f"the experience buffer holds action masks: {AM.REFUSAL}, not of policy_type {self.policy_type}")
+            if exp.mask_width != lay.width:  # (the C side sees the word count only: 33 and 40 entries are two words alike)
+                raise ValueError(f"the experience buffer's action masks have {exp.mask_width} entries per row, the "
+                                 + (f"multi-discrete policy has {lay.width} logits (one entry per bin of every component)"
+                                    if lay.heads is not None else f"discrete policy has {lay.width} actions"))
             a.action_mask, a.mask_words = st["action_masks"].data_ptr(), st["action_masks"].shape[1]
         a.clip_range, a.ent_coef = float(self.clip_range), float(self.ent_coef)
         a.mb_ratio = float(self.mini_batch_size / self.batch_size)

@@ -453,3 +453,55 @@ def test_masked_loss_widest_rows(L, A):
               outside=0.4)
     got = M.run_minibatch(L, pol, val, dict(pr, mask=torch.from_numpy(m).cuda()), np.array([4, 0, 3, 1, 2]))
     M.masked_gate(L, pol, val, dict(pr, mask=eff), got, f"{D} -> (64,) -> {A}, 5 rows")
+
+
+# ------------------------------------------------------------------ 5. one act_padded: the eager call, its launcher, the graph
+@pytest.mark.parametrize("head", ["discrete", "multidiscrete", "gaussian"])
+def test_act_padded_is_the_heads_act_launch_and_the_graph_replays_it(head):
+    """ArenaModule.act_padded is the head's _act_launch on buffers of its own: the same call made by hand on the same rows, noise and
+    mask words gives the same bits, and so does get_action on the same host batch through ActGraph.  17 rows (one ragged
+    bucket of the graph), a 2 x 64 body; the masking heads also under a mask with rows whose heads keep exactly one bin."""
+    from rlgym_ppo_amd.ppo.continuous_policy import ContinuousPolicy
+    from rlgym_ppo_amd.ppo.discrete_policy import DiscreteFF
+    from rlgym_ppo_amd.ppo.multi_discrete_policy import MultiDiscreteFF
+    torch.manual_seed(31)
+    rs = np.random.RandomState(31)
+    n, d, bins = 17, 23, (2, 7, 3, 11, 2)
+    pol = {"discrete": lambda: DiscreteFF(d, 33, (64, 64), "cuda:0"),
+           "multidiscrete": lambda: MultiDiscreteFF(d, (64, 64), "cuda:0", bins=bins),
+           "gaussian": lambda: ContinuousPolicy(d, 6, (64, 64), "cuda:0")}[head]()
+    obs = np.clip(rs.randn(n, d), -5, 5).astype(np.float32)
+    rows = pol.arena.stage_obs(obs)
+    q = pol._draw_noise(n).clone()
+    assert tuple(q.shape) == tuple(pol._noise_shape(n))
+    masks, lay = [None], pol.mask_layout
+    assert (lay is None) == (head == "gaussian")
+    single = [3, 11]
+    if lay is not None:
+        segs = [(0, lay.width)] if lay.heads is None else [(int(s), int(s) + b) for s, b in zip(lay.starts, lay.heads)]
+        m = rs.rand(n, lay.width) < 0.5
+        for lo, hi in segs:
+            m[np.arange(n), rs.randint(lo, hi, n)] = True
+        m[single] = False
+        only = [hi - 1 for _, hi in segs]
+        m[np.ix_(single, only)] = True        # exactly one valid bin (the last) in every head of these rows
+        masks.append(m)
+    bits = lambda t: t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
+    for m in masks:
+        a0, l0 = pol.act_padded(rows, noise=q, action_mask=m)
+        a1, l1 = pol._action_buffer(n, "cuda:0").fill_(-7), torch.full((n,), -7.0, device="cuda:0")
+        assert a1.dtype == a0.dtype and a1.shape == a0.shape
+        words = None if m is None else lay.pack(m, "cuda:0")
+        pol._act_launch(rows, n, q.cuda(), a1, l1, pol.arena.forward_ws(n), None, words)
+        assert torch.equal(bits(a0), bits(a1)) and torch.equal(bits(l0), bits(l1)), (head, m is not None)
+        calls = sum(g.calls for g in pol._graphs.values())
+        a2, l2 = pol.get_action(obs, noise=q, action_mask=m) if m is not None else pol.get_action(obs, noise=q)
+        key = 32 if m is None else (32, True)
+        assert key in pol._graphs and sum(g.calls for g in pol._graphs.values()) == calls + 1   # the graph served it
+        assert torch.equal(bits(a0.cpu()), bits(a2)) and torch.equal(bits(l0.cpu()), bits(l2)), (head, m is not None)
+        assert torch.isfinite(l0).all()
+        if m is not None:
+            a = a0.cpu().numpy().reshape(n, -1)
+            off = np.array([lo for lo, _ in segs])
+            assert m[np.arange(n)[:, None], a + off].all()                                       # valid actions only
+            assert np.array_equal((a + off)[single], np.tile(only, (2, 1))) and (l0.cpu().numpy()[single] == 0).all()

@@ -190,7 +190,7 @@ def _manager(policy_cls, mask, **attrs):
 
 def test_vector_manager_mask_shapes_for_both_heads():
     """A one-agent environment may answer a rank-1 [n_actions] mask (the discrete head's documented form, and the multi-discrete
-    head's [sum(bins)]); a wrong width names both numbers; the layout is worked out once per policy object."""
+    head's [sum(bins)]); a wrong width names both numbers; the layout is the policy's own (util.action_mask.Layout.of)."""
     from rlgym_ppo_amd.ppo.discrete_policy import DiscreteFF
     from rlgym_ppo_amd.ppo.multi_discrete_policy import MultiDiscreteFF
     from rlgym_ppo_amd.util import action_mask as AM
@@ -202,12 +202,17 @@ def test_vector_manager_mask_shapes_for_both_heads():
     with pytest.raises(ValueError, match=r"7\).*must be 9"):
         _manager(DiscreteFF, m1, n_actions=9)._env_mask()
     S = sum(BINS)
-    md = dict(n_logits=S, splits=list(BINS))
+    md = dict(n_logits=S, splits=list(BINS), mask_layout=AM.Layout(S, BINS))
     row = np.ones(S, bool)
     row[3:9] = False                                   # head 1 keeps its first bin only
     mgr = _manager(MultiDiscreteFF, row, **md)
     assert np.array_equal(AM.unpack(mgr._env_mask(), S).numpy(), row[None])
-    assert mgr._mask_layout() == (S, list(BINS)) and mgr._mask_layout_cache[0] is mgr.policy
+    lay = AM.Layout.of(mgr.policy)
+    assert lay is mgr.policy.mask_layout and lay.width == S and lay.heads == tuple(BINS) and lay.words == 1
+    duck = AM.Layout.of(_manager(MultiDiscreteFF, row, n_logits=S, splits=list(BINS)).policy)   # (no mask_layout: n_logits, splits)
+    assert duck.width == S and duck.heads == tuple(BINS)
+    flat = AM.Layout.of(_manager(DiscreteFF, m1, n_actions=7).policy)
+    assert flat.width == 7 and flat.heads is None
     with pytest.raises(ValueError, match=r"5.*must be 25"):
         _manager(MultiDiscreteFF, np.ones((12, len(BINS)), bool), **md)._env_mask()
     row[2] = False                                     # head 1 without a valid bin

@@ -153,12 +153,15 @@ def test_configure_masking_accepts_type_1_and_checks_the_width_against_the_polic
     ones = np.ones((2, S), bool)
     mgr = _configured([ones, ones], (23.0, float(H), 1.0, 1.0))
     assert mgr.masked and mgr.n_actions == S and mgr.mask_space_type == 1
-    # the policy is known later: the layout is worked out once per policy object
+    # the policy is known later: the layout is the policy's (util.action_mask.Layout.of), a duck-typed one's from (n_logits, splits)
+    from rlgym_ppo_amd.util.action_mask import Layout
     mgr.policy = _NvecPolicy()
-    assert mgr._mask_layout() == NVEC and mgr._mask_layout_cache[0] is mgr.policy and mgr._mask_layout() == NVEC
+    lay = mgr._mask_layout()
+    assert lay.width == S and lay.heads == tuple(NVEC) and lay.words == 1 and list(lay.starts) == W.starts(NVEC)
     pol = object.__new__(MultiDiscreteFF)                             # (no GPU: the attributes the check reads)
-    pol.__dict__.update(n_logits=S, splits=list(NVEC))
-    assert _configured([ones], (23.0, float(H), 1.0, 1.0), pol)._mask_layout() == NVEC
+    pol.__dict__.update(n_logits=S, splits=list(NVEC), mask_layout=Layout(S, NVEC))
+    mgr = _configured([ones], (23.0, float(H), 1.0, 1.0), pol)
+    assert mgr._mask_layout() is pol.mask_layout and Layout.of(mgr.policy) is mgr.policy.mask_layout
     # a width other than sum(splits): both numbers are named, whichever side is wrong
     mgr = _configured([np.ones((2, H), bool)], (23.0, float(H), 1.0, 1.0), _NvecPolicy())
     with pytest.raises(ValueError, match=rf"\b{H} entries.*\b{S} logits"):
@@ -187,7 +190,8 @@ def test_configure_masking_accepts_type_1_and_checks_the_width_against_the_polic
         _configured([np.ones((2, 7), bool)], (13.0, 7.0, 0.0, 1.0), pol)
     # the discrete head is what it was: masks as wide as the action space
     mgr = _configured([np.ones((2, 7), bool)], (13.0, 7.0, 0.0, 1.0))
-    assert mgr.masked and mgr.n_actions == 7 and mgr.mask_space_type == 0 and mgr._mask_layout() is None
+    assert mgr.masked and mgr.n_actions == 7 and mgr.mask_space_type == 0
+    assert mgr._mask_layout().width == 7 and mgr._mask_layout().heads is None and mgr._mask_layout().words == 1
     with pytest.raises(ValueError, match="masks of 6 actions, the action space has 7"):
         _configured([np.ones((2, 6), bool)], (13.0, 7.0, 0.0, 1.0))
 
