@@ -86,6 +86,33 @@ extern "C" {
 #define RLPPO_HEAD_DISCRETE 0
 #define RLPPO_HEAD_MULTIDISCRETE 1
 #define RLPPO_HEAD_GAUSSIAN 2
+/* [diag] The diagonal-Gaussian head with a learnable, state-independent log-std (Stable-Baselines3, CleanRL, rl_games; not in the
+ * reference): opt-in, a fourth head beside the reference's three (added entry points: rlppo_diag_gaussian_act,
+ * rlppo_ppo_minibatch_diag, rlppo_diag_scratch_bytes, rlppo_clip_adam_pack2_tail; no struct changes, the ABI version stays 8).  The
+ * policy network has dims {obs, hidden.., k}, its last layer is plain bias (NO tanh); log_std is k floats of DEVICE memory that are
+ * not a layer of the network: the first parameter that lives in a TAIL behind a network's rlppo_flat_floats.
+ *   sigma_j = exp(log_std_j), mu = net(obs), 1 <= k <= RLPPO_DIAG_MAX_K
+ *   sample         a_j = mu_j + sigma_j eps_j with the caller's eps[n][k] ~ N(0, 1); the sample is NOT clamped
+ *   deterministic  a = mu, row by row (rlppo_mlp_forward with out_tanh = 0; not the discrete head's one-index-per-batch quirk)
+ *   log p          sum_j [ -(a_j - mu_j)^2 / (2 sigma_j^2) - log_std_j - 1/2 log 2 pi ]: torch.distributions.Normal.log_prob's terms in
+ *                  its order, of the sample as drawn / as stored; up to 32 dimensions the float terms are summed in float in j order,
+ *                  above that in double and rounded once (the rule of RLPPO_HEAD_GAUSSIAN's kernels)
+ *   entropy        of one row: sum_j (1.4189385332046727 + log_std_j), summed over the dimensions with NO division by k; the report's
+ *                  entropy is its mean over the rows.  This deliberately DIFFERS from RLPPO_HEAD_GAUSSIAN, which averages over the
+ *                  action dimensions too (the reference's quirk Q8): here the entropy bonus is Normal.entropy().sum(-1), as in SB3
+ *   gradients      through the surrogate every head shares (clip range, torch.min's tie rule, adv_norm, stop_word, kl_slots as for
+ *                  the other heads): dL/dmu_j = g_logp (a_j - mu_j) / sigma_j^2, in place over the head output;
+ *                  dL/dlog_std_j = sum over the rows of [ g_logp ((a_j - mu_j)^2 / sigma_j^2 - 1) - mb_ratio ent_coef / mb ]
+ *   reduction      the log_std gradient is bit-reproducible: every workgroup of the loss launch (256 rows) writes its k partial sums
+ *                  (double, fixed tree) into its row of the caller's scratch (rlppo_diag_scratch_bytes(mb, k) bytes, no zeroing
+ *                  needed), a second small launch adds the rows in a fixed order (double) and adds the rounded sum ONCE per element
+ *                  and launch into log_std_grad -- the rule the weight gradients follow; no floating-point atomics inside the sum
+ *   masks          refused (RLPPO_ERR_ARG, the text the Gaussian head's refusal has)
+ *   optimiser      rlppo_clip_adam is n-based (n = rlppo_flat_floats + k); rlppo_clip_adam_pack2_tail is rlppo_clip_adam_pack2 with
+ *                  tail_floats more elements behind each network's layers: same norm, same Adam, zeroed gradient, skip_word, and
+ *                  never written into `packed`. */
+#define RLPPO_HEAD_DIAG_GAUSSIAN 3
+#define RLPPO_DIAG_MAX_K 256
 
 /* precision of a call (rlppo_act_opts.precision, rlppo_minibatch_args.precision): 0 = the process default set with
  * rlppo_set_inference_precision / rlppo_set_update_precision, else 1 + that setter's mode */
@@ -261,6 +288,15 @@ int rlppo_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, cons
                        const float *obs, int64_t ld_obs, int64_t n, const float *noise_eps, float var_m, float var_b,
                        float *actions, float *logp, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts);
 
+/* [diag] The rollout step of the diagonal-Gaussian head ("[diag]" above): the layer chain with out_tanh = 0, then the sampling kernel.
+ * dims[n_layers] == k; noise_eps[n][k] ~ N(0, 1) (the stream ContinuousPolicy draws); log_std: DEVICE, k floats, read when the
+ * kernel RUNS -- a changed parameter is seen by the next call, a replay of a captured call included.  actions: float[n][k], not
+ * clamped; logp: float[n].  opts as rlppo_gaussian_act: bf16 inference precision and completion words (they ride in the sampling
+ * kernel) work, an action mask is refused. */
+int rlppo_diag_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs, int64_t ld_obs,
+                            int64_t n, const float *noise_eps, const float *log_std, float *actions, float *logp, void *workspace,
+                            size_t ws_bytes, const rlppo_act_opts *opts);
+
 /* MultiDiscreteFF.get_action (multi_discrete_policy.py:46-74, torch_functions.py:93-122): 21 logits -> 8
  * categoricals (5x3 + 3x2); noise_q[n*8][3] as Categorical.sample draws it; actions int64[n][8]; logp[n]. */
 int rlppo_multidiscrete_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed,
@@ -428,6 +464,18 @@ int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *args);
  * ("[nvec, masked]" above): the loss kernel reads row idx[r]'s words through the ring map itself, as the discrete head's does. */
 int rlppo_ppo_minibatch_nvec(void *stream, const rlppo_minibatch_args *args, const int32_t *md_nvec, int32_t md_heads);
 
+/* [diag] The same pass with the diagonal-Gaussian head ("[diag]" above; an added entry point: the struct and the ABI version stay as
+ * they are).  args->head must be RLPPO_HEAD_DIAG_GAUSSIAN and args->act_dim == pol_dims[pol_layers] == k; var_m / var_b are ignored;
+ * an action mask is RLPPO_ERR_ARG.  log_std: DEVICE k floats; log_std_grad: DEVICE k floats, += (one add per element and launch);
+ * scratch: DEVICE, 8-byte aligned, rlppo_diag_scratch_bytes(args->mb, k) bytes owned by the caller for the duration of the pass (one
+ * region per slot in flight; it needs no initialisation and the pinned rlppo_minibatch_workspace_bytes_for values do not include
+ * it).  Every pass form (two streams, paired launches, fused minibatches, ring-mapped buffers, n_rows == 0) and every update
+ * precision works as for the other heads: the head math is fp32 on whatever the forward produced.  rlppo_ppo_minibatch and
+ * rlppo_ppo_minibatch_nvec answer head 3 with RLPPO_ERR_ARG; every argument check happens before the first HIP call. */
+size_t rlppo_diag_scratch_bytes(int64_t mb, int32_t k);
+int rlppo_ppo_minibatch_diag(void *stream, const rlppo_minibatch_args *args, const float *log_std, float *log_std_grad, void *scratch,
+                             size_t scratch_bytes);
+
 /* Orders `stream` after every minibatch enqueued through non-zero slots since the last join (call it before the
  * gradient all-reduce / rlppo_clip_adam).  Independent minibatches of one batch only meet in the gradient arena
  * (one add per element and launch), so they may overlap; each launch is short (50-100 us at 65,536 rows), and overlapping
@@ -508,6 +556,13 @@ typedef struct rlppo_opt_net {
                                    this network (both forms; rlppo_kl_gate's stop word); NULL = never skip */
 } rlppo_opt_net;
 int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws);
+/* [diag] The same call for networks that carry a parameter TAIL: params / grads / exp_avg / exp_avg_sq of network a hold
+ * rlppo_flat_floats(dims) + tail_a floats (b: tail_b), the tail behind the last bias (the diagonal-Gaussian head's log_std; any
+ * later parameter that is not a layer).  Tail elements are part of that network's squared norm (clipped under the SAME norm, as
+ * Stable-Baselines3 and CleanRL clip the whole policy together), updated by Adam, their gradients zeroed, they respect skip_word
+ * and the all-or-nothing give-up -- and are never written into `packed`.  Both forms (one launch with the grid barrier; three
+ * operations with sync_ws == NULL).  tail_a == tail_b == 0 is rlppo_clip_adam_pack2, launch for launch and bit for bit. */
+int rlppo_clip_adam_pack2_tail(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, int64_t tail_a, int64_t tail_b);
 
 /* [r6] The tail of PPOLearner.learn in ONE launch (ppo_learner.py:213-234: the update magnitudes ||theta_before - theta_after||_2 of
  * both networks, the report means' sums read out, one device -> host synchronisation): round 5 spent ten dependent eager launches
@@ -809,6 +864,13 @@ size_t rlppo_dbg_thin_head_workspace_bytes(int32_t out, int32_t kp, int64_t M);
 int rlppo_dbg_thin_head_b16(void *stream, const float *dY, int64_t ldy, int32_t out, const float *W, int64_t ldw, const void *bits,
                             const void *hb, int64_t ldh, void *dxb, float *dW, float *db, int32_t in, int32_t kp, int64_t M, void *ws,
                             size_t ws_bytes);
+/* [diag] The diagonal-Gaussian head's loss step on its own, on caller-supplied head outputs y[mb][ld] (the means; overwritten with
+ * dL/dmean), actions[mb][k], old_logp / advantages[mb] -- contiguous rows, as a pass has gathered them: part 0 = the loss launch and
+ * the fixed-order finish of the log_std reduction (what a pass runs), 1 = the loss launch alone (partial sums into scratch), 2 = the
+ * finish alone (on the partial sums an earlier call left).  tools/diag_gaussian_cost.py times them apart. */
+int rlppo_dbg_diag_loss(void *stream, float *y, int64_t ld, int32_t k, const float *actions, const float *old_logp, const float *advantages,
+                        int64_t mb, float clip_range, float ent_coef, float mb_ratio, const float *log_std, float *log_std_grad, void *scratch,
+                        size_t scratch_bytes, double *stats, int32_t part);
 /* dW[out][in] += dY^T . X, db[out] += colsum(dY) through partial tiles in `ws` (rlppo_dbg_gemm_tn_workspace_bytes) and a
  * fixed-order reduction: the form rlppo_ppo_minibatch uses. */
 size_t rlppo_dbg_gemm_tn_workspace_bytes(int32_t out, int32_t in, int64_t M);

@@ -26,6 +26,8 @@ MAX_SLOTS = 8
 STAT_ENTROPY, STAT_KL, STAT_VLOSS, STAT_CLIPFRAC, STAT_PLOSS = 0, 1, 2, 3, 4
 STAT_PASSES = 7  # host-side: passes of rlppo_ppo_minibatch behind the sums above (summed over ranks with them)
 HEAD_DISCRETE, HEAD_MULTIDISCRETE, HEAD_GAUSSIAN = 0, 1, 2
+HEAD_DIAG_GAUSSIAN = 3  # RLPPO_HEAD_DIAG_GAUSSIAN: learnable state-independent log_std, unbounded mean (include/rlppo.h, "[diag]")
+DIAG_MAX_K = 256  # RLPPO_DIAG_MAX_K
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16, PRECISION_X3 = 0, 1, 2, 3  # rlppo_minibatch_args.precision (1 + mode)
 
 
@@ -121,6 +123,8 @@ SIGNATURES = {
     "rlppo_categorical_select": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "rlppo_gaussian_act": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float,
                                      c_float, c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
+    "rlppo_diag_gaussian_act": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
     "rlppo_multidiscrete_act": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
     "rlppo_multidiscrete_act_nvec": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
@@ -146,6 +150,8 @@ SIGNATURES = {
     "rlppo_minibatch_workspace_bytes_for": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
     "rlppo_ppo_minibatch": (c_int32, [c_void_p, POINTER(MinibatchArgs)]),
     "rlppo_ppo_minibatch_nvec": (c_int32, [c_void_p, POINTER(MinibatchArgs), _P32, c_int32]),
+    "rlppo_diag_scratch_bytes": (c_size_t, [c_int64, c_int32]),
+    "rlppo_ppo_minibatch_diag": (c_int32, [c_void_p, POINTER(MinibatchArgs), c_void_p, c_void_p, c_void_p, c_size_t]),
     "rlppo_ppo_join": (c_int32, [c_void_p]),
     "rlppo_kl_slots_doubles": (c_int64, [c_int64]),
     "rlppo_adv_stats": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
@@ -153,6 +159,7 @@ SIGNATURES = {
     "rlppo_clip_adam": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double,
                                   c_double, c_double, c_double, c_int64, c_void_p]),
     "rlppo_clip_adam_pack2": (c_int32, [c_void_p, POINTER(OptNet), POINTER(OptNet), c_void_p]),
+    "rlppo_clip_adam_pack2_tail": (c_int32, [c_void_p, POINTER(OptNet), POINTER(OptNet), c_void_p, c_int64, c_int64]),
     "rlppo_learn_report": (c_int32, [c_void_p, POINTER(ReportArgs)]),
     "rlppo_collector_create": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, POINTER(c_void_p)]),
     "rlppo_collector_destroy": (c_int32, [c_void_p]),
@@ -213,6 +220,8 @@ SIGNATURES = {
     "rlppo_dbg_thin_head_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int64]),
     "rlppo_dbg_thin_head_b16": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                           c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_size_t]),
+    "rlppo_dbg_diag_loss": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_void_p,
+                                      c_void_p, c_void_p, c_size_t, c_void_p, c_int32]),
     "rlppo_dbg_gemm_tn_group_workspace_bytes": (c_size_t, [POINTER(TnProduct), c_int32, c_int64]),
     "rlppo_dbg_gemm_tn_group": (c_int32, [c_void_p, POINTER(TnProduct), c_int32, c_int64, c_void_p, c_size_t]),
     "rlppo_dbg_gemm_tn_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int64]),

@@ -595,6 +595,29 @@ int rlppo_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     return launch_gaussian_sample((hipStream_t)stream, o, ldo, n, dims[n_layers] / 2, noise_eps, var_m, var_b, actions, logp, cx.done, cx.done_value);
 }
 
+// [diag] the diagonal-Gaussian head: the layer chain WITHOUT tanh, then the sampling kernel, which reads log_std from device memory
+// when it runs (a captured call sees the parameter as it is at every replay)
+int rlppo_diag_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs, int64_t ld_obs,
+                            int64_t n, const float *noise_eps, const float *log_std, float *actions, float *logp, void *workspace,
+                            size_t ws_bytes, const rlppo_act_opts *opts) {
+    NetLayout net;
+    int rc = make_layout(dims, n_layers, &net);
+    if (rc) return rc;
+    ActCtx cx;
+    rc = act_ctx(opts, &cx, false, "the diagonal-Gaussian head (rlppo_diag_gaussian_act)");
+    if (rc) return rc;
+    RLPPO_CHECK_ARG(dims[n_layers] <= RLPPO_DIAG_MAX_K, "diag_gaussian_act: %d action dimensions, RLPPO_DIAG_MAX_K allows 1 .. %d", dims[n_layers],
+                    RLPPO_DIAG_MAX_K);
+    if (n == 0) return 0;
+    RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_eps && log_std && actions && logp && workspace, "diag_gaussian_act: bad argument");
+    const float *o;
+    int64_t ldo;
+    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
+    if (rc) return rc;
+    // (the completion words ride in the sampling kernel: a block of it holds 256 whole rows)
+    return launch_diag_gaussian_sample((hipStream_t)stream, o, ldo, n, dims[n_layers], noise_eps, log_std, actions, logp, cx.done, cx.done_value);
+}
+
 int rlppo_multidiscrete_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
                             int64_t ld_obs, int64_t n, const float *noise_q, int64_t *actions, float *logp,
                             void *workspace, size_t ws_bytes, const rlppo_act_opts *opts) {
@@ -1113,6 +1136,7 @@ struct Pass {
     LossCfg cfg;
     MdSpec md;                   // [nvec] the multi-discrete head's bins when rlppo_ppo_minibatch_nvec gives them
     bool md_general = false;
+    const DiagHead *diag = nullptr;  // [diag] the diagonal-Gaussian head's parameter, gradient and scratch (rlppo_ppo_minibatch_diag)
     const float *pol_w, *val_w;  // the packed weights the products read (bf16 precision: their rounded images)
     hipStream_t st, side;        // the policy's and the critic's chain (one stream: rlppo_dbg_set(4, 0))
     DwList *defer;               // [r5] the grouped weight gradients, or null
@@ -1152,6 +1176,8 @@ static int policy_loss(hipStream_t st, const Pass &p) {
     }
     if (a.head == RLPPO_HEAD_GAUSSIAN)
         return launch_gaussian_loss(st, w.pol.act[last], L.pout, L.out / 2, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
+    if (a.head == RLPPO_HEAD_DIAG_GAUSSIAN)  // [diag] + the fixed-order finish of the log_std gradient, behind it on the same stream
+        return launch_diag_gaussian_loss(st, w.pol.act[last], L.pout, L.out, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, *p.diag);
     if (p.md_general) {  // [nvec] any nvec: the general kernel, also on the reference's bins
         ++g_cnt_md_nvec;
         return launch_multidiscrete_nvec_loss(st, w.pol.act[last], L.pout, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, p.md,
@@ -1348,11 +1374,12 @@ static int two_chain_pass(const Pass &p) {
 }
 
 // one pass; md_nvec (host, or null = the reference's multi-discrete head) is rlppo_ppo_minibatch_nvec's
-static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads) {
+static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads, const DiagHead *diag = nullptr) {
     // ---- validation: every argument error is reported here, before the first HIP call
     RLPPO_CHECK_ARG(a != nullptr, "ppo_minibatch: null args");
     Pass p;
     p.a = a;
+    p.diag = diag;
     int rc = make_layout(a->pol_dims, a->pol_layers, &p.pol);
     if (rc) return rc;
     rc = make_layout(a->val_dims, a->val_layers, &p.val);
@@ -1378,13 +1405,20 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     }
     // every head pins act_dim to at most the policy's output width (the gathered actions' slots); the loss kernel's width too
     const int n_out = pol.L[pol.n_layers - 1].out;
-    RLPPO_CHECK_ARG(a->head == RLPPO_HEAD_DISCRETE || a->head == RLPPO_HEAD_GAUSSIAN || a->head == RLPPO_HEAD_MULTIDISCRETE,
-                    "ppo_minibatch: unknown head %d", a->head);
+    RLPPO_CHECK_ARG(a->head == RLPPO_HEAD_DISCRETE || a->head == RLPPO_HEAD_GAUSSIAN || a->head == RLPPO_HEAD_MULTIDISCRETE ||
+                        a->head == RLPPO_HEAD_DIAG_GAUSSIAN, "ppo_minibatch: unknown head %d", a->head);
+    // [diag] the diagonal-Gaussian head has a parameter of its own: only rlppo_ppo_minibatch_diag brings it (and nothing else does)
+    RLPPO_CHECK_ARG(a->head != RLPPO_HEAD_DIAG_GAUSSIAN || diag,
+                    "ppo_minibatch: head %d (RLPPO_HEAD_DIAG_GAUSSIAN) needs log_std, its gradient and scratch: rlppo_ppo_minibatch_diag", a->head);
+    RLPPO_CHECK_ARG(!diag || a->head == RLPPO_HEAD_DIAG_GAUSSIAN, "ppo_minibatch_diag: head %d, but the entry point runs RLPPO_HEAD_DIAG_GAUSSIAN (%d) only",
+                    a->head, RLPPO_HEAD_DIAG_GAUSSIAN);
     // [ABI 8] action masks: the discrete head, and [nvec, masked] the multi-discrete head's general kernels (md_nvec given, also for
     // the reference's bins): one bit per output, ceil(n_out / 32) words per buffer row
     RLPPO_CHECK_ARG(!a->action_mask || a->head == RLPPO_HEAD_DISCRETE || (a->head == RLPPO_HEAD_MULTIDISCRETE && md_nvec),
                     "ppo_minibatch: action_mask is an option of the discrete head, not of the %s head",
-                    a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : "multi-discrete (without md_nvec: the fixed-bin kernels take no mask)");
+                    a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian"
+                    : a->head == RLPPO_HEAD_DIAG_GAUSSIAN ? "diagonal-Gaussian"
+                                                          : "multi-discrete (without md_nvec: the fixed-bin kernels take no mask)");
     if (int rc_mask = mask_words_check(a->action_mask, a->mask_words, n_out, "ppo_minibatch", false)) return rc_mask;
     if (a->head == RLPPO_HEAD_DISCRETE) {
         RLPPO_CHECK_ARG(a->act_dim == 1, "discrete head: act_dim must be 1");
@@ -1393,9 +1427,17 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     }
     if (a->head == RLPPO_HEAD_GAUSSIAN)
         RLPPO_CHECK_ARG(n_out % 2 == 0 && a->act_dim == n_out / 2, "gaussian head: act_dim=%d, outputs=%d", a->act_dim, n_out);
+    if (a->head == RLPPO_HEAD_DIAG_GAUSSIAN) {
+        RLPPO_CHECK_ARG(a->act_dim == n_out, "diagonal-Gaussian head: act_dim=%d, but the policy has %d outputs (pol_dims[pol_layers])", a->act_dim, n_out);
+        RLPPO_CHECK_ARG(n_out <= RLPPO_DIAG_MAX_K, "diagonal-Gaussian head: %d action dimensions, RLPPO_DIAG_MAX_K allows 1 .. %d", n_out, RLPPO_DIAG_MAX_K);
+        RLPPO_CHECK_ARG(diag->log_std && diag->log_std_grad, "ppo_minibatch_diag: log_std / log_std_grad is NULL");
+        RLPPO_CHECK_ARG(diag->scratch && diag->scratch_bytes >= diag_scratch_bytes(mb, n_out),
+                        "ppo_minibatch_diag: scratch of %zu bytes, rlppo_diag_scratch_bytes(%ld, %d) = %zu needed", diag->scratch_bytes, (long)mb, n_out,
+                        diag_scratch_bytes(mb, n_out));
+    }
     // [nvec] md_nvec: the multi-discrete head alone; NULL = the reference's 21 outputs / 8 heads and the fixed kernel
     RLPPO_CHECK_ARG(!md_nvec || a->head == RLPPO_HEAD_MULTIDISCRETE, "ppo_minibatch: md_nvec is an option of the multi-discrete head, not of the %s head",
-                    a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : "discrete");
+                    a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : a->head == RLPPO_HEAD_DIAG_GAUSSIAN ? "diagonal-Gaussian" : "discrete");
     if (a->head == RLPPO_HEAD_MULTIDISCRETE && md_nvec) {
         rc = md_spec_make(md_nvec, md_heads, "multi-discrete head: md_nvec / md_heads", &p.md);
         if (rc) return rc;
@@ -1472,6 +1514,18 @@ int rlppo_ppo_minibatch_nvec(void *stream, const rlppo_minibatch_args *a, const 
     return ppo_minibatch(stream, a, md_nvec, md_heads);
 }
 
+size_t rlppo_diag_scratch_bytes(int64_t mb, int32_t k) { return diag_scratch_bytes(mb, k); }
+int rlppo_ppo_minibatch_diag(void *stream, const rlppo_minibatch_args *a, const float *log_std, float *log_std_grad, void *scratch,
+                             size_t scratch_bytes) {
+    DiagHead d;
+    d.log_std = log_std;
+    d.log_std_grad = log_std_grad;
+    d.scratch = reinterpret_cast<double *>(scratch);
+    d.scratch_bytes = scratch_bytes;
+    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "ppo_minibatch_diag: scratch must be 8-byte aligned");
+    return ppo_minibatch(stream, a, nullptr, 0, &d);
+}
+
 int rlppo_ppo_join(void *stream) {
     SlotBank *bank = nullptr;
     int rc = slot_bank(&bank);
@@ -1499,8 +1553,10 @@ int rlppo_clip_adam(void *stream, float *params, float *grads, float *exp_avg, f
                             (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, gnorm2);
 }
 
-int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws) {
+// tail[k]: parameters of network k behind its layers' rlppo_flat_floats (rlppo_clip_adam_pack2_tail); 0 = the plain call
+static int clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, const int64_t *tail) {
     RLPPO_CHECK_ARG(a && b, "clip_adam_pack2: null descriptor");
+    RLPPO_CHECK_ARG(tail[0] >= 0 && tail[1] >= 0, "clip_adam_pack2_tail: tail_floats %ld / %ld < 0", (long)tail[0], (long)tail[1]);
     const rlppo_opt_net *d[2] = {a, b};
     NetLayout nets[2];
     float *p[2], *g[2], *m[2], *v[2], *packed[2];
@@ -1520,13 +1576,21 @@ int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_
         p[k] = d[k]->params; g[k] = d[k]->grads; m[k] = d[k]->exp_avg; v[k] = d[k]->exp_avg_sq; packed[k] = d[k]->packed;
         gn[k] = d[k]->gnorm2;
         const LayerLayout &last = nets[k].L[nets[k].n_layers - 1];
-        n[k] = last.off_flat_b + last.out;  // = rlppo_flat_floats
+        n[k] = last.off_flat_b + last.out + tail[k];  // = rlppo_flat_floats (+ the parameter tail)
         max_norm[k] = (float)d[k]->max_norm; step_size[k] = (float)(d[k]->lr / bc1); bc2_sqrt[k] = (float)sqrt(bc2);
         omb1[k] = (float)(1.0 - d[k]->beta1); beta2[k] = (float)d[k]->beta2; omb2[k] = (float)(1.0 - d[k]->beta2);
         eps[k] = (float)d[k]->eps;
     }
     return launch_clip_adam_pack2((hipStream_t)stream, nets, p, g, m, v, packed, gn, n, max_norm, step_size, bc2_sqrt, omb1, beta2,
-                                  omb2, eps, sync_ws, skip);
+                                  omb2, eps, sync_ws, skip, tail);
+}
+int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws) {
+    const int64_t tail[2] = {0, 0};
+    return clip_adam_pack2(stream, a, b, sync_ws, tail);
+}
+int rlppo_clip_adam_pack2_tail(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, int64_t tail_a, int64_t tail_b) {
+    const int64_t tail[2] = {tail_a, tail_b};
+    return clip_adam_pack2(stream, a, b, sync_ws, tail);
 }
 
 int64_t rlppo_kl_slots_doubles(int64_t mb) { return kl_slots_doubles(mb); }
@@ -1577,6 +1641,23 @@ int rlppo_welford_merge(void *stream, int32_t d, void *mean, void *m2, int64_t c
     RLPPO_CHECK_ARG(d > 0 && count >= 0 && other_count > 0 && mean && m2 && other_mean && other_m2, "welford_merge: bad argument");
     return launch_welford_merge((hipStream_t)stream, d, mean, m2, (long long)count, other_mean, other_m2, (long long)other_count,
                                 state_is_f64 != 0);
+}
+// [diag] the diagonal-Gaussian head's loss launch and the finish of its log_std reduction on their own (tools/diag_gaussian_cost.py)
+int rlppo_dbg_diag_loss(void *stream, float *y, int64_t ld, int32_t k, const float *actions, const float *old_logp, const float *advantages,
+                        int64_t mb, float clip_range, float ent_coef, float mb_ratio, const float *log_std, float *log_std_grad, void *scratch,
+                        size_t scratch_bytes, double *stats, int32_t part) {
+    RLPPO_CHECK_ARG(mb > 0 && y && actions && old_logp && advantages && stats && part >= 0 && part <= 2, "dbg_diag_loss: bad argument");
+    rlppo_minibatch_args a = {};
+    a.clip_range = clip_range;
+    a.ent_coef = ent_coef;
+    a.mb_ratio = mb_ratio;
+    a.mb = mb;
+    DiagHead d;
+    d.log_std = log_std;
+    d.log_std_grad = log_std_grad;
+    d.scratch = reinterpret_cast<double *>(scratch);
+    d.scratch_bytes = scratch_bytes;
+    return launch_diag_gaussian_loss((hipStream_t)stream, y, ld, k, actions, old_logp, advantages, mb, loss_cfg(a), stats, d, part);
 }
 int64_t rlppo_wb16_elems(const int32_t *dims, int32_t n_layers) {
     NetLayout net;

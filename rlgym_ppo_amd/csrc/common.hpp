@@ -241,6 +241,20 @@ int launch_discrete_loss(hipStream_t, float *, int64_t, int, const float *, cons
                          const MaskRows *mask_rows = nullptr);
 int launch_gaussian_loss(hipStream_t, float *, int64_t, int, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
 int launch_multidiscrete_loss(hipStream_t, float *, int64_t, const float *, const float *, const float *, int64_t, const LossCfg &, double *);
+// [diag] the diagonal-Gaussian head: k outputs = the means, log_std a k-float device parameter read at run time.  DiagHead: what
+// rlppo_ppo_minibatch_diag adds to a pass -- the parameter, its gradient (+=) and the per-workgroup partial sums of that gradient
+// (diag_scratch_bytes(mb, k) bytes, written whole by every pass: no zeroing)
+struct DiagHead {
+    const float *log_std = nullptr;
+    float *log_std_grad = nullptr;
+    double *scratch = nullptr;
+    size_t scratch_bytes = 0;
+};
+size_t diag_scratch_bytes(int64_t mb, int k);
+int launch_diag_gaussian_sample(hipStream_t, const float *y, int64_t ld, int64_t n, int k, const float *eps, const float *log_std,
+                                float *actions, float *logp, unsigned *done_words = nullptr, unsigned done_value = 0);
+int launch_diag_gaussian_loss(hipStream_t, float *y, int64_t ld, int k, const float *actions, const float *old_logp, const float *adv,
+                              int64_t mb, const LossCfg &, double *stats, const DiagHead &, int part = 0);
 // [nvec] the multi-discrete head for any nvec: H heads of b[h] bins, S = sum b[h] logits, B = max b[h] (the noise's row width).
 // A kernel argument by value (76 bytes); md_spec_make validates a host nvec against the RLPPO_MD_MAX_* limits and fills it.
 struct MdSpec {
@@ -307,7 +321,8 @@ int launch_clip_adam(hipStream_t, float *p, float *g, float *m, float *v, int64_
 int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *p, float *const *g, float *const *m, float *const *v,
                            float *const *packed, double *const *gnorm2, const int64_t *n, const float *max_norm,
                            const float *step_size, const float *bc2_sqrt, const float *omb1, const float *beta2, const float *omb2,
-                           const float *eps, void *sync_ws = nullptr, const unsigned *const *skip = nullptr);
+                           const float *eps, void *sync_ws = nullptr, const unsigned *const *skip = nullptr,
+                           const int64_t *tail = nullptr);  // tail[k]: of the n[k] elements, the last tail[k] are not part of `packed`
 int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float *adv, int64_t ring_base, int64_t ring_cap, float *out,
                      void *ws);                             // [ABI 7] rlppo_adv_stats
 int launch_kl_gate(hipStream_t st, const rlppo_kl_gate_args &a);  // [ABI 7] rlppo_kl_gate

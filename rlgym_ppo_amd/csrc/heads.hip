@@ -653,6 +653,160 @@ int launch_gaussian_loss(hipStream_t st, float *y, int64_t ld, int k, const floa
     return 0;
 }
 
+// ------------------------------------------------------------------------------- diagonal Gaussian [diag]
+// RLPPO_HEAD_DIAG_GAUSSIAN (include/rlppo.h, "[diag]"): the head of Stable-Baselines3 / CleanRL / rl_games.  y[row][0:k] is the
+// network's output as it is (no tanh) = the mean; sigma_j = exp(log_std_j) with log_std a k-float PARAMETER read from device memory
+// at run time (a block keeps log_std and sigma in LDS).  Nothing is clamped; log p is Normal.log_prob's three terms in its order;
+// the float terms are summed as the Gaussian head above sums its (FLOAT_SUM_K).  One thread per row, no per-row array.
+constexpr float DIAG_HALF_LOG_2PI = 0.9189385332046727f;  // log(sqrt(2 pi))
+__device__ __forceinline__ float diag_logp_term(float d, float sd, float ls) { return -(d * d) / (2.f * (sd * sd)) - ls - DIAG_HALF_LOG_2PI; }
+// (every thread of the block, before anything diverges: the fill ends in a barrier)
+__device__ __forceinline__ void diag_fill_lds(const float *__restrict__ log_std, int k, float *s_ls, float *s_sd) {
+    for (int j = threadIdx.x; j < k; j += blockDim.x) {
+        const float ls = log_std[j];
+        s_ls[j] = ls;
+        s_sd[j] = expf(ls);
+    }
+    __syncthreads();
+}
+
+// action = mean + sigma * eps (NOT clamped), logp = sum_j log N(action_j; mean_j, sigma_j)
+__global__ __launch_bounds__(256) void diag_gaussian_sample_kernel(const float *__restrict__ y, int64_t ld, int64_t n, int k,
+                                                                    const float *__restrict__ eps, const float *__restrict__ log_std,
+                                                                    float *__restrict__ actions, float *__restrict__ logp,
+                                                                    unsigned *done_words, unsigned done_value) {
+    __shared__ float s_ls[RLPPO_DIAG_MAX_K], s_sd[RLPPO_DIAG_MAX_K];
+    diag_fill_lds(log_std, k, s_ls, s_sd);
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row < n) {  // (one barrier site behind it for the whole block: see multidiscrete_sample_kernel)
+        const float *yr = y + row * ld;
+        float lp = 0.f;
+        double lpd = 0.0;  // (k > FLOAT_SUM_K)
+        for (int j = 0; j < k; ++j) {
+            const float mean = yr[j], sd = s_sd[j];
+            const float a = eps[row * k + j] * sd + mean;  // at::normal: output.mul_(std).add_(mean)
+            actions[row * k + j] = a;
+            const float t = diag_logp_term(a - mean, sd, s_ls[j]);  // of the sample as stored: what the update will recompute
+            if (k <= FLOAT_SUM_K)
+                lp += t;
+            else
+                lpd += (double)t;
+        }
+        logp[row] = k <= FLOAT_SUM_K ? lp : (float)lpd;
+    }
+    block_done_words(done_words, done_value, n);
+}
+
+int launch_diag_gaussian_sample(hipStream_t st, const float *y, int64_t ld, int64_t n, int k, const float *eps, const float *log_std,
+                                float *actions, float *logp, unsigned *done_words, unsigned done_value) {
+    if (n <= 0) return 0;
+    RLPPO_CHECK_ARG(k >= 1 && k <= RLPPO_DIAG_MAX_K && k <= ld, "diagonal-Gaussian head: k=%d not in [1, RLPPO_DIAG_MAX_K=%d] (rows of %ld)", k,
+                    RLPPO_DIAG_MAX_K, (long)ld);
+    hipLaunchKernelGGL(diag_gaussian_sample_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, y, ld, n, k, eps, log_std, actions,
+                       logp, done_words, done_value);
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
+// y[row][0:k] (the means) is overwritten with dL/dmean = g_logp (a - mean) / sigma^2.  A row's entropy is sum_j (1/2 + 1/2 log 2 pi +
+// log_std_j): summed over the dimensions, NOT divided by k (unlike the Gaussian head above, quirk Q8), the same for every row.
+// dL/dlog_std_j is a sum over ALL rows of the pass of g_logp ((a - mean)^2 / sigma^2 - 1) - mb_ratio ent_coef inv_mb: every thread's
+// float term is widened to double, summed over the wave (shuffles, a fixed tree), the four waves' sums added in a fixed order, and
+// the workgroup's k sums land in ITS row of `partials` [grid][k] -- no atomics; diag_logstd_finish_kernel adds the rows.
+__global__ __launch_bounds__(256) void diag_gaussian_loss_kernel(float *__restrict__ y, int64_t ld, int k, const float *__restrict__ actions,
+                                                                  const float *__restrict__ old_logp, const float *__restrict__ advantages,
+                                                                  int64_t mb, LossCfg cfg, double *__restrict__ stats,
+                                                                  const float *__restrict__ log_std, double *__restrict__ partials) {
+    __shared__ float s_ls[RLPPO_DIAG_MAX_K], s_sd[RLPPO_DIAG_MAX_K];
+    __shared__ double s_red[4][RLPPO_DIAG_MAX_K];
+    diag_fill_lds(log_std, k, s_ls, s_sd);
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = row < mb;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float *yr = y + (active ? row : 0) * ld;
+    const float *xr = actions + (active ? row : 0) * k;
+    Surrogate t = {};
+    if (active) {
+        float lp = 0.f, ent = 0.f;
+        if (k <= FLOAT_SUM_K) {
+#pragma unroll 4
+            for (int j = 0; j < k; ++j) {
+                lp += diag_logp_term(xr[j] - yr[j], s_sd[j], s_ls[j]);
+                ent += 1.4189385332046727f + s_ls[j];  // Normal.entropy(): 0.5 + 0.5*log(2*pi) + log(sd)
+            }
+        } else {  // the same terms, summed in double (FLOAT_SUM_K)
+            double lpd = 0.0, entd = 0.0;
+#pragma unroll 4
+            for (int j = 0; j < k; ++j) {
+                lpd += (double)diag_logp_term(xr[j] - yr[j], s_sd[j], s_ls[j]);
+                entd += (double)(1.4189385332046727f + s_ls[j]);
+            }
+            lp = (float)lpd;
+            ent = (float)entd;
+        }
+        t = surrogate_row(lp, old_logp[row], advantages[row], cfg);
+        surrogate_stats_add(st, ent * cfg.inv_mb, t, cfg);
+    }
+    const float g_ent = -cfg.mb_ratio * cfg.ent_coef * cfg.inv_mb;  // d(-c_H * H_row)/d log_std_j of one row
+    // (the loop is uniform over the block: every lane takes part in the wave sums, rows beyond mb with a zero term)
+    for (int j = 0; j < k; ++j) {
+        float term = 0.f;
+        if (active) {
+            const float d = xr[j] - yr[j], sd = s_sd[j];
+            const float s2 = sd * sd;
+            yr[j] = t.g_logp * d / s2;
+            term = t.g_logp * (d * d / s2 - 1.f) + g_ent;
+        }
+        double s = (double)term;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0) s_red[wave][j] = s;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < k; j += blockDim.x)
+        partials[(int64_t)blockIdx.x * k + j] = (s_red[0][j] + s_red[1][j]) + (s_red[2][j] + s_red[3][j]);
+    block_stats_add(stats, st, active, cfg, cfg.kl_slots);
+}
+
+// log_std_grad[j] += the sum over the workgroups' partial sums of dimension j, in a fixed order: one workgroup per dimension, thread t
+// adds rows t, t + 256, ... of `partials`, then the fixed tree over the workgroup.  The one add per element and launch into the
+// gradient arena is an atomic, as the weight gradients' is (passes of different slots meet there).
+__global__ __launch_bounds__(256) void diag_logstd_finish_kernel(const double *__restrict__ partials, int nblocks, int k,
+                                                                  float *__restrict__ grad) {
+    const int j = blockIdx.x;
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 256) a += partials[(int64_t)b * k + j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(grad + j, (float)((red[0] + red[1]) + (red[2] + red[3])));
+}
+
+size_t diag_scratch_bytes(int64_t mb, int k) { return (size_t)thread_per_row_grid(mb > 0 ? mb : 1) * (size_t)(k > 0 ? k : 1) * sizeof(double); }
+
+int launch_diag_gaussian_loss(hipStream_t st, float *y, int64_t ld, int k, const float *actions, const float *old_logp, const float *adv,
+                              int64_t mb, const LossCfg &cfg, double *stats, const DiagHead &dg, int part) {
+    if (mb <= 0) return 0;
+    RLPPO_CHECK_ARG(k >= 1 && k <= RLPPO_DIAG_MAX_K && k <= ld, "diagonal-Gaussian head: k=%d not in [1, RLPPO_DIAG_MAX_K=%d] (rows of %ld)", k,
+                    RLPPO_DIAG_MAX_K, (long)ld);
+    RLPPO_CHECK_ARG(dg.log_std && dg.log_std_grad && dg.scratch && dg.scratch_bytes >= diag_scratch_bytes(mb, k),
+                    "diagonal-Gaussian head: log_std / log_std_grad / scratch (%zu bytes, %zu needed)", dg.scratch_bytes, diag_scratch_bytes(mb, k));
+    const unsigned grid = thread_per_row_grid(mb);
+    if (part != 2) {  // (part: rlppo_dbg_diag_loss times the two launches apart; a pass runs both)
+        hipLaunchKernelGGL(diag_gaussian_loss_kernel, dim3(grid), dim3(256), 0, st, y, ld, k, actions, old_logp, adv, mb, cfg, stats, dg.log_std,
+                           dg.scratch);
+        RLPPO_LAUNCH_CHECK();
+    }
+    if (part != 1) {
+        hipLaunchKernelGGL(diag_logstd_finish_kernel, dim3((unsigned)k), dim3(256), 0, st, dg.scratch, (int)grid, k, dg.log_std_grad);
+        RLPPO_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------- multi-discrete
 // 21 logits = 5 heads of 3 + 3 heads of 2 (multi_discrete_policy.py:20, torch_functions.py:101-113).
 __device__ __forceinline__ int md_start(int h) { return h < 5 ? 3 * h : 15 + 2 * (h - 5); }

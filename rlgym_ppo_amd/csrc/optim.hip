@@ -486,6 +486,7 @@ struct OptNet {
     float *p, *g, *m, *v, *packed;
     double *gnorm2;
     int64_t n;
+    int64_t n_net;  // elements [n_net, n) are a parameter tail behind the network's layers: clipped, updated and zeroed like the rest, never packed
     float max_norm, step_size, bc2_sqrt, omb1, beta2, omb2, eps;
     PackJobs jobs;
     const unsigned *skip;  // [ABI 7] rlppo_opt_net.skip_word: non-zero = leave this network as it is (NULL: never)
@@ -530,6 +531,7 @@ __global__ __launch_bounds__(256) void adam_pack2_kernel(OptPair o) {
         N.m[i] = mi;
         N.v[i] = vi;
         N.g[i] = 0.f;  // zero_grad of the next batch (the clipped gradient is not observable inside learn())
+        if (i >= N.n_net) continue;  // a tail parameter has no slot in `packed`
         int l = 0;     // flat order: W0[out][in], b0, W1, b1, ...
         while (l + 1 < N.jobs.n && i >= N.jobs.j[l + 1].off_flat_w) ++l;
         const PackJob &J = N.jobs.j[l];
@@ -586,6 +588,7 @@ __device__ __forceinline__ void adam_one(const OptNet &N, int64_t i, float gi, f
     N.m[i] = mi;
     N.v[i] = vi;
     N.g[i] = 0.f;  // zero_grad of the next batch (the clipped gradient is not observable inside learn())
+    if (i >= N.n_net) return;  // a tail parameter has no slot in `packed`
     int l = 0;     // flat order: W0[out][in], b0, W1, b1, ...
     while (l + 1 < N.jobs.n && i >= N.jobs.j[l + 1].off_flat_w) ++l;
     const PackJob &J = N.jobs.j[l];
@@ -739,7 +742,7 @@ static void fill_jobs(const NetLayout &net, PackJobs *jobs) {
 int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *p, float *const *g, float *const *m, float *const *v,
                            float *const *packed, double *const *gnorm2, const int64_t *n, const float *max_norm,
                            const float *step_size, const float *bc2_sqrt, const float *omb1, const float *beta2, const float *omb2,
-                           const float *eps, void *sync_ws, const unsigned *const *skip) {
+                           const float *eps, void *sync_ws, const unsigned *const *skip, const int64_t *tail) {
     OptPair o;
     int64_t nmax = 0;
     for (int k = 0; k < 2; ++k) {
@@ -748,6 +751,7 @@ int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *
         N.max_norm = max_norm[k]; N.step_size = step_size[k]; N.bc2_sqrt = bc2_sqrt[k]; N.omb1 = omb1[k]; N.beta2 = beta2[k];
         N.omb2 = omb2[k]; N.eps = eps[k];
         N.skip = skip ? skip[k] : nullptr;
+        N.n_net = n[k] - (tail ? tail[k] : 0);
         fill_jobs(nets[k], &N.jobs);
         nmax = n[k] > nmax ? n[k] : nmax;
     }

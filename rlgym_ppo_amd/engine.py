@@ -62,16 +62,23 @@ class Workspace:
 class NetArena:
     """Device state of one MLP: flat parameter arena (parameters_to_vector order), flat gradient arena, and the
     tile-padded packed copy the kernels read.  The nn.Module's Parameters are re-pointed at views of `flat`, so
-    state_dict()/load_state_dict() stay stock (keys model.{0,2,..}.{weight,bias})."""
+    state_dict()/load_state_dict() stay stock (keys model.{0,2,..}.{weight,bias}).
 
-    def __init__(self, linears, device):
+    tail (optional): Parameters that are not a layer of the MLP (the diagonal-Gaussian head's log_std).  They live BEHIND the network's
+    n_net = rlppo_flat_floats elements in `flat` / `grad` (n_flat = n_net + n_tail), so the optimiser, the gradient exchange and the
+    report cover them with the arena; params() yields them last; packing reads the first n_net elements only."""
+
+    def __init__(self, linears, device, tail=()):
         self.device = device
         self.linears = list(linears)
+        self.tail = list(tail)
         self.dims = [self.linears[0].in_features] + [l.out_features for l in self.linears]
         self.n_layers = len(self.linears)
         self.dims_c = N.dims_array(self.dims)
         L = N.lib()
-        self.n_flat = int(L.rlppo_flat_floats(self.dims_c, self.n_layers))
+        self.n_net = int(L.rlppo_flat_floats(self.dims_c, self.n_layers))
+        self.n_tail = sum(int(p.numel()) for p in self.tail)
+        self.n_flat = self.n_net + self.n_tail
         self.n_packed = int(L.rlppo_packed_floats(self.dims_c, self.n_layers))
         self.d_in = self.dims[0]
         self.d_out = self.dims[-1]
@@ -94,6 +101,7 @@ class NetArena:
         for lin in self.linears:
             yield lin.weight
             yield lin.bias
+        yield from self.tail
 
     def bind(self):
         """(Re-)point every Parameter (and its .grad) at its slice of the arenas, keeping current values."""
@@ -113,7 +121,7 @@ class NetArena:
         # (on the per-call path of get_action: Parameter.data_ptr() against cached byte offsets -- `p.data` would build an alias
         # tensor per parameter, 6-8 us per call for 8 parameters)
         plan = self._plan
-        if plan is None or len(plan) != 2 * len(self.linears):
+        if plan is None or len(plan) != 2 * len(self.linears) + len(self.tail):
             o, plan = 0, []
             for p in self.params():
                 plan.append(4 * o)
@@ -125,6 +133,10 @@ class NetArena:
             if lin.weight.data_ptr() != base + plan[i] or lin.bias.data_ptr() != base + plan[i + 1]:
                 return False
             i += 2
+        for p in self.tail:
+            if p.data_ptr() != base + plan[i]:
+                return False
+            i += 1
         return True
 
     def packed_is_current(self):

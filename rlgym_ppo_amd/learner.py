@@ -42,9 +42,32 @@ class Learner(object):
             save_every_ts: int = 1_000_000, instance_launch_delay=None, random_seed: int = 123,
             n_checkpoints_to_keep: int = 5, shm_buffer_size: int = 8192, device: str = "auto",
             vector_env: bool = False, gae_bootstrap_truncated: bool = False, multi_discrete_bins=None,
+            continuous_head: str = "reference", continuous_log_std_init: float = 0.0, continuous_action_clip="default",
             per_feature_obs_standardization: bool = False,
             ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
         assert env_create_function is not None, "MUST PROVIDE A FUNCTION TO CREATE RLGYM FUNCTIONS TO INITIALIZE RLGYM-PPO"
+        # not in the reference: continuous_head="diag" is the diagonal-Gaussian head with a learnable log_std (ppo/diag_gaussian_policy.py)
+        # for a continuous action space; "reference" (default) keeps ContinuousPolicy.  The head samples unbounded actions and the buffer
+        # stores them unclipped; continuous_action_clip = (lo, hi) is what the ENVIRONMENT receives ("default": (-1, 1) with "diag", the
+        # range the reference's head clamps to; None: no clipping).  The option values are checked here, before anything needs the GPU
+        # or spawns a process; that the action space IS continuous can only be checked once the environment has reported it (below,
+        # before the PPOLearner is built -- like multi_discrete_bins).
+        if continuous_head not in ("reference", "diag"):
+            raise ValueError(f"continuous_head must be 'reference' or 'diag', got {continuous_head!r}")
+        from .ppo.diag_gaussian_policy import check_log_std_init
+        from .util.action_clip import ClippedEnvFactory, check_clip
+        continuous_log_std_init = check_log_std_init(continuous_log_std_init)
+        default_clip = isinstance(continuous_action_clip, str) and continuous_action_clip == "default"   # (a pair may be an array)
+        if continuous_head == "reference":
+            if not default_clip:
+                raise ValueError("continuous_action_clip is an option of continuous_head='diag': the reference's head clamps its own "
+                                 f"samples to [-1, 1] (got {continuous_action_clip!r})")
+            continuous_action_clip = None
+        else:
+            continuous_action_clip = check_clip((-1.0, 1.0) if default_clip else continuous_action_clip)
+            if continuous_action_clip is not None:   # one mechanism for both collection modes: the environment is built wrapped
+                env_create_function = ClippedEnvFactory(env_create_function, *continuous_action_clip)
+        self.continuous_head, self.continuous_action_clip = continuous_head, continuous_action_clip
         if checkpoints_save_folder is None:
             checkpoints_save_folder = os.path.join("data", "checkpoints", "rlgym-ppo-run")
         self.add_unix_timestamp = add_unix_timestamp
@@ -114,6 +137,11 @@ class Learner(object):
                 raise ValueError(f"multi_discrete_bins has {len(multi_discrete_bins)} entries, but the action space has "
                                  f"{int(act_space_size)} components")
             act_space_size = multi_discrete_bins
+        if continuous_head == "diag":
+            if action_space_type != 2:
+                self.agent.cleanup()
+                raise ValueError(f"continuous_head='diag' is an option of a continuous action space (type 2), not of action space type {action_space_type}")
+            action_space_type = 3   # PPOLearner's policy_type of the diagonal-Gaussian head
         self.ppo_learner = PPOLearner(
             obs_space_size, act_space_size, device=self.device, batch_size=ppo_batch_size,
             mini_batch_size=ppo_minibatch_size, n_epochs=ppo_epochs, continuous_var_range=continuous_var_range,
@@ -121,6 +149,8 @@ class Learner(object):
             policy_lr=policy_lr, critic_lr=critic_lr, clip_range=ppo_clip_range, ent_coef=ppo_ent_coef,
             normalize_advantages=ppo_normalize_advantages, value_clip_range=ppo_value_clip_range, target_kl=ppo_target_kl,
             max_grad_norm=ppo_max_grad_norm)
+        if continuous_head == "diag":   # (a constant fill before the first step and before a checkpoint is loaded: no generator use)
+            self.ppo_learner.policy.fill_log_std(continuous_log_std_init)
         self.agent.policy = self.ppo_learner.policy
         if not vector_env and self.agent.masked:
             # a masked MultiDiscrete environment: its masks' width against the policy's bins, here rather than at the first collect

@@ -1,4 +1,5 @@
 from .continuous_policy import ContinuousPolicy
+from .diag_gaussian_policy import DiagGaussianPolicy
 from .multi_discrete_policy import MultiDiscreteFF
 from .discrete_policy import DiscreteFF
 from .value_estimator import ValueEstimator

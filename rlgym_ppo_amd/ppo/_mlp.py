@@ -339,7 +339,8 @@ class ArenaModule(nn.Module):
         self.device = device
         dev = require_gpu(device)
         self.model = self.model.to(dev)
-        self.arena = NetArena(linears_of(self.model), dev)
+        # (a head's parameters that are not a layer -- DiagGaussianPolicy.log_std -- ride in the arena's tail)
+        self.arena = NetArena(linears_of(self.model), dev, tail=getattr(self, "_arena_tail", ()))
         self.act_graphs = True  # get_action through a hipGraph per batch-size bucket (False: every call takes the general path)
         self.act_graph_max = 1024  # beyond that the explicit copies of the eager path are the better transport for the noise
         self._graphs = {}

@@ -21,6 +21,11 @@ limit.  Their defaults are the reference's update, launch for launch.  With poli
 MultiDiscrete(nvec) action space (a sequence of bin counts) instead of its length: an integer keeps the reference's eight heads
 [3, 3, 3, 3, 3, 2, 2, 2] and its kernels.  (The constructor's parameter list is the reference's plus the four options and stays
 that: the bins have no keyword of their own here; `Learner` has `multi_discrete_bins`.)
+
+policy_type 3 (not in the reference) is the diagonal-Gaussian head with a learnable log_std (ppo/diag_gaussian_policy.py):
+`act_space_size` = k action dimensions, `continuous_var_range` is ignored; log_std starts at 0 (SB3's default;
+DiagGaussianPolicy.fill_log_std sets another start, as `Learner(continuous_log_std_init=...)` does).  Its passes go through
+rlppo_ppo_minibatch_diag and its optimiser step through rlppo_clip_adam_pack2_tail (log_std is the tail of the policy's arena).
 """
 import ctypes
 import os
@@ -34,6 +39,7 @@ from ..dp import all_reduce_sum, dist_info, fuse_runs, slices_for_rank
 from ..engine import Workspace, ptr, require_gpu, stream_ptr
 from ..util import action_mask as AM
 from .continuous_policy import ContinuousPolicy
+from .diag_gaussian_policy import DiagGaussianPolicy
 from .discrete_policy import DiscreteFF
 from .multi_discrete_policy import MultiDiscreteFF, check_bins
 from .value_estimator import ValueEstimator
@@ -145,7 +151,10 @@ class PPOLearner(object):
         self.policy_type = int(policy_type)
         # construction order (policy, then critic) fixes the CPU-generator consumption and therefore the initial
         # weights (ppo_learner.py:34-53)
-        if policy_type == 2:
+        if policy_type == 3:   # the diagonal-Gaussian head: k means from the network + a learnable log_std (continuous_var_range unused)
+            self.policy = DiagGaussianPolicy(obs_space_size, act_space_size, policy_layer_sizes, device).to(device)
+            self._act_dim = int(act_space_size)
+        elif policy_type == 2:
             self.policy = ContinuousPolicy(obs_space_size, act_space_size * 2, policy_layer_sizes, device,
                                            var_min=continuous_var_range[0], var_max=continuous_var_range[1]).to(device)
             self._act_dim = int(act_space_size)
@@ -204,6 +213,7 @@ class PPOLearner(object):
         self._report_out_np, self._report_seq = self._report_out.numpy(), 0
         self._ws = Workspace(self._dev)
         self.n_slots = int(os.environ.get("RLPPO_SLOTS", 1))  # minibatches of a batch kept in flight concurrently
+        self._diag_scratch = None  # policy_type 3: one region of rlppo_diag_scratch_bytes per slot (partial sums of the log_std gradient)
         # Minibatch fusion.  The reference sums the gradients of a batch's minibatches, each the MB/B-scaled mean over its
         # rows, before ONE clip + Adam (ppo_learner.py:134-193): the minibatches are independent given the parameters and
         # their sum is the 1/B-scaled sum over all their rows.  They only exist to bound activation memory; with 288 GB of
@@ -278,11 +288,20 @@ class PPOLearner(object):
         ws = self._ws.get(nbytes * self.n_slots)
         self._slot_ws = [ws.data_ptr() + i * nbytes for i in range(self.n_slots)]
         a.workspace, a.ws_bytes = self._slot_ws[0], nbytes
+        if self.policy_type == 3:   # allocated once per slot (grown only when a larger pass comes)
+            sb = (int(N.lib().rlppo_diag_scratch_bytes(self._fused_rows, self._act_dim)) + 255) // 256 * 256
+            if self._diag_scratch is None or self._diag_scratch.numel() < sb * self.n_slots:
+                self._diag_scratch = torch.empty(sb * self.n_slots, dtype=torch.uint8, device=self._dev)
+            self._diag_scratch_bytes = sb
         return a
 
     def _pass(self, st, args):
         """One rlppo_ppo_minibatch pass; a multi-discrete policy with bins of its own goes through rlppo_ppo_minibatch_nvec (the
         general loss kernel), and so does every masked multi-discrete pass; every other policy through the plain entry point."""
+        if self.policy_type == 3:   # log_std and its gradient: the tail of the policy's arena, behind the layers
+            pa, sb = self.policy.arena, self._diag_scratch_bytes
+            return N.lib().rlppo_ppo_minibatch_diag(st, ctypes.byref(args), pa.flat.data_ptr() + 4 * pa.n_net, pa.grad.data_ptr() + 4 * pa.n_net,
+                                                    self._diag_scratch.data_ptr() + args.slot * sb, sb)
         nvec = self.policy.md_nvec if self.policy_type == 1 else None
         if nvec is None and self.policy_type == 1 and args.action_mask:
             nvec = self.policy._nvec_c  # a masked pass runs the general loss kernel, also on the reference's bins
@@ -465,8 +484,11 @@ class PPOLearner(object):
                         dp_ = self.policy_optimizer.fused_descriptor(max_norm)
                         if kl_on:   # (a step after the stop touches nothing: the gate's stop word)
                             dv.skip_word = dp_.skip_word = gate.stop_word
-                        N.check(L.rlppo_clip_adam_pack2(st, ctypes.byref(dv), ctypes.byref(dp_),
-                                                        ptr(self._opt_sync) if self.one_launch_optimizer else None))
+                        sync = ptr(self._opt_sync) if self.one_launch_optimizer else None
+                        if va.n_tail or pa.n_tail:   # parameters behind a network's layers (log_std): same norm, same step, never packed
+                            N.check(L.rlppo_clip_adam_pack2_tail(st, ctypes.byref(dv), ctypes.byref(dp_), sync, va.n_tail, pa.n_tail))
+                        else:
+                            N.check(L.rlppo_clip_adam_pack2(st, ctypes.byref(dv), ctypes.byref(dp_), sync))
                         va.mark_repacked()
                         pa.mark_repacked()
                         grads_zero = True
