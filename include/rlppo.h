@@ -564,6 +564,47 @@ int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_
  * operations with sync_ws == NULL).  tail_a == tail_b == 0 is rlppo_clip_adam_pack2, launch for launch and bit for bit. */
 int rlppo_clip_adam_pack2_tail(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, int64_t tail_a, int64_t tail_b);
 
+/* [lr] A learning rate that lives on the device: the KL-adaptive schedule of rsl_rl / rl_games ("adaptive"), decided by the gate and
+ * read by the optimiser step without the host in between (added entry points: rlppo_kl_gate_lr, rlppo_clip_adam_pack2_lr; no struct
+ * of an existing entry point changes, the ABI version stays 8).
+ *
+ * rlppo_kl_gate_lr is rlppo_kl_gate -- the same three phases, the same fixed-order sum KL_b -- plus the rate rule.  Phase 1 writes
+ * the exchange words and nothing else.  Phases 0 and 2, in this order:
+ *   1. the stop decision of rlppo_kl_gate, when args->stop_word is not NULL (threshold, batch as there);
+ *   2. *kl_out <- KL_b (when kl_out is not NULL);
+ *   3. when no stop word is given or it is 0 AFTER step 1 (a gate that stops the run moves no rate), for each of the n_lr adjacent
+ *      doubles lr[i], in double:
+ *          KL_b > 2 desired_kl         lr[i] <- max(lr_min, lr[i] / factor)
+ *          0 < KL_b < desired_kl / 2   lr[i] <- min(lr_max, lr[i] * factor)
+ *          otherwise                   unchanged
+ *      Both inequalities are strict; KL_b == 0, KL_b exactly on a threshold and a NaN KL_b change nothing.  Every rate is compared,
+ *      moved and clamped on its own.  KL_b is the SAMPLE estimate mean((ratio - 1) - log ratio) every head's loss launch writes, not
+ *      rsl_rl's analytic Gaussian KL;
+ *   4. the host words of rlppo_kl_gate, when args->host_words is not NULL.
+ * args->stop_word and args->host_words may both be NULL (the schedule without target_kl): the call then writes device memory only.
+ * 1 <= n_lr <= RLPPO_LR_MAX_RATES, desired_kl > 0, factor > 1, 0 < lr_min <= lr_max, all finite.
+ *
+ * rlppo_clip_adam_pack2_lr is rlppo_clip_adam_pack2_tail whose networks may take their rate from a device double: a non-NULL lr_a
+ * replaces a->lr (lr_b: b->lr).  The kernel forms step_size = (float)(*lr / bc1) with bc1 = 1 - beta1^step passed in as the host's
+ * double: the value the host forms for the same rate, bit for bit (IEEE double division, one rounding to float).  The rate is read
+ * after the grid barrier (one-launch form: once per workgroup; three-operation form: once per thread of the update launch), so the
+ * writer is any launch earlier on the stream -- the gate of the same batch.  The call never writes a rate: a step that is skipped
+ * (skip_word) or gives up leaves the rates as the gate set them.  Barrier protocol, give-up rule, skip_word, tails and both forms
+ * (sync_ws == NULL: three operations) are those of rlppo_clip_adam_pack2_tail; lr_a == lr_b == NULL is that call, launch for
+ * launch and bit for bit. */
+#define RLPPO_LR_MAX_RATES 8
+typedef struct rlppo_lr_adapt_args {
+    double *lr;          /* device: n_lr adjacent rates */
+    int32_t n_lr;
+    double desired_kl;
+    double factor;       /* 1.5 in rsl_rl */
+    double lr_min, lr_max;
+    double *kl_out;      /* device, optional: receives KL_b (phases 0 and 2) */
+} rlppo_lr_adapt_args;
+int rlppo_kl_gate_lr(void *stream, const rlppo_kl_gate_args *args, const rlppo_lr_adapt_args *lr);
+int rlppo_clip_adam_pack2_lr(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, int64_t tail_a, int64_t tail_b,
+                             const double *lr_a, const double *lr_b);
+
 /* [r6] The tail of PPOLearner.learn in ONE launch (ppo_learner.py:213-234: the update magnitudes ||theta_before - theta_after||_2 of
  * both networks, the report means' sums read out, one device -> host synchronisation): round 5 spent ten dependent eager launches
  * and a blocking copy here, 0.1 ms of a 3 ms learn() at the reference's own batch size.  The kernel

@@ -94,6 +94,14 @@ class KlGateArgs(ctypes.Structure):
     ]
 
 
+class LrAdaptArgs(ctypes.Structure):
+    """struct rlppo_lr_adapt_args (include/rlppo.h, "[lr]")."""
+    _fields_ = [
+        ("lr", c_void_p), ("n_lr", c_int32), ("desired_kl", c_double), ("factor", c_double), ("lr_min", c_double), ("lr_max", c_double),
+        ("kl_out", c_void_p),
+    ]
+
+
 _P32 = POINTER(c_int32)
 _PACT = POINTER(ActOpts)
 # name -> (restype, argtypes); kept in one table so tests can check it against the header's declarations
@@ -156,10 +164,12 @@ SIGNATURES = {
     "rlppo_kl_slots_doubles": (c_int64, [c_int64]),
     "rlppo_adv_stats": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "rlppo_kl_gate": (c_int32, [c_void_p, POINTER(KlGateArgs)]),
+    "rlppo_kl_gate_lr": (c_int32, [c_void_p, POINTER(KlGateArgs), POINTER(LrAdaptArgs)]),
     "rlppo_clip_adam": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double,
                                   c_double, c_double, c_double, c_int64, c_void_p]),
     "rlppo_clip_adam_pack2": (c_int32, [c_void_p, POINTER(OptNet), POINTER(OptNet), c_void_p]),
     "rlppo_clip_adam_pack2_tail": (c_int32, [c_void_p, POINTER(OptNet), POINTER(OptNet), c_void_p, c_int64, c_int64]),
+    "rlppo_clip_adam_pack2_lr": (c_int32, [c_void_p, POINTER(OptNet), POINTER(OptNet), c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "rlppo_learn_report": (c_int32, [c_void_p, POINTER(ReportArgs)]),
     "rlppo_collector_create": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, POINTER(c_void_p)]),
     "rlppo_collector_destroy": (c_int32, [c_void_p]),

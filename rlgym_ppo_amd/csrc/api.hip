@@ -1554,7 +1554,8 @@ int rlppo_clip_adam(void *stream, float *params, float *grads, float *exp_avg, f
 }
 
 // tail[k]: parameters of network k behind its layers' rlppo_flat_floats (rlppo_clip_adam_pack2_tail); 0 = the plain call
-static int clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, const int64_t *tail) {
+static int clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, const int64_t *tail,
+                           const double *const *lr = nullptr) {
     RLPPO_CHECK_ARG(a && b, "clip_adam_pack2: null descriptor");
     RLPPO_CHECK_ARG(tail[0] >= 0 && tail[1] >= 0, "clip_adam_pack2_tail: tail_floats %ld / %ld < 0", (long)tail[0], (long)tail[1]);
     const rlppo_opt_net *d[2] = {a, b};
@@ -1564,6 +1565,7 @@ static int clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt
     int64_t n[2];
     float max_norm[2], step_size[2], bc2_sqrt[2], omb1[2], beta2[2], omb2[2], eps[2];
     const unsigned *skip[2];
+    double bc1s[2];
     for (int k = 0; k < 2; ++k) {
         skip[k] = d[k]->skip_word;
         int rc = make_layout(d[k]->dims, d[k]->n_layers, &nets[k]);
@@ -1575,6 +1577,7 @@ static int clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt
         const double bc2 = 1.0 - pow(d[k]->beta2, (double)d[k]->step);
         p[k] = d[k]->params; g[k] = d[k]->grads; m[k] = d[k]->exp_avg; v[k] = d[k]->exp_avg_sq; packed[k] = d[k]->packed;
         gn[k] = d[k]->gnorm2;
+        bc1s[k] = bc1;  // [lr] a rate in device memory is divided by the same double on the device
         const LayerLayout &last = nets[k].L[nets[k].n_layers - 1];
         n[k] = last.off_flat_b + last.out + tail[k];  // = rlppo_flat_floats (+ the parameter tail)
         max_norm[k] = (float)d[k]->max_norm; step_size[k] = (float)(d[k]->lr / bc1); bc2_sqrt[k] = (float)sqrt(bc2);
@@ -1582,7 +1585,7 @@ static int clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt
         eps[k] = (float)d[k]->eps;
     }
     return launch_clip_adam_pack2((hipStream_t)stream, nets, p, g, m, v, packed, gn, n, max_norm, step_size, bc2_sqrt, omb1, beta2,
-                                  omb2, eps, sync_ws, skip, tail);
+                                  omb2, eps, sync_ws, skip, tail, lr, bc1s);
 }
 int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws) {
     const int64_t tail[2] = {0, 0};
@@ -1591,6 +1594,14 @@ int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_
 int rlppo_clip_adam_pack2_tail(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, int64_t tail_a, int64_t tail_b) {
     const int64_t tail[2] = {tail_a, tail_b};
     return clip_adam_pack2(stream, a, b, sync_ws, tail);
+}
+
+int rlppo_clip_adam_pack2_lr(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, int64_t tail_a, int64_t tail_b,
+                             const double *lr_a, const double *lr_b) {
+    const int64_t tail[2] = {tail_a, tail_b};
+    const double *lr[2] = {lr_a, lr_b};
+    RLPPO_CHECK_ARG((((uintptr_t)lr_a | (uintptr_t)lr_b) & 7) == 0, "clip_adam_pack2_lr: a rate must be 8-byte aligned");
+    return clip_adam_pack2(stream, a, b, sync_ws, tail, lr);
 }
 
 int64_t rlppo_kl_slots_doubles(int64_t mb) { return kl_slots_doubles(mb); }
@@ -1609,6 +1620,17 @@ int rlppo_kl_gate(void *stream, const rlppo_kl_gate_args *a) {
     RLPPO_CHECK_ARG(a->phase == 0 || a->exchange, "kl_gate: phases 1 and 2 need the exchange words");
     RLPPO_CHECK_ARG(a->phase == 1 || a->host_words, "kl_gate: host_words missing");
     return launch_kl_gate((hipStream_t)stream, *a);
+}
+
+int rlppo_kl_gate_lr(void *stream, const rlppo_kl_gate_args *a, const rlppo_lr_adapt_args *l) {
+    RLPPO_CHECK_ARG(a && a->kl_slots && a->n_passes >= 0 && a->slot_stride >= 3 && a->phase >= 0 && a->phase <= 2, "kl_gate_lr: bad argument");
+    RLPPO_CHECK_ARG(a->phase == 0 || a->exchange, "kl_gate_lr: phases 1 and 2 need the exchange words");
+    RLPPO_CHECK_ARG(l && l->lr && ((uintptr_t)l->lr & 7) == 0 && l->n_lr >= 1 && l->n_lr <= RLPPO_LR_MAX_RATES, "kl_gate_lr: 1 to %d adjacent rates",
+                    RLPPO_LR_MAX_RATES);
+    RLPPO_CHECK_ARG(std::isfinite(l->desired_kl) && l->desired_kl > 0 && std::isfinite(l->factor) && l->factor > 1 && std::isfinite(l->lr_min) &&
+                        std::isfinite(l->lr_max) && l->lr_min > 0 && l->lr_min <= l->lr_max,
+                    "kl_gate_lr: desired_kl=%g factor=%g bounds=[%g, %g]", l->desired_kl, l->factor, l->lr_min, l->lr_max);
+    return launch_kl_gate_lr((hipStream_t)stream, *a, *l);
 }
 
 int rlppo_learn_report(void *stream, const rlppo_report_args *a) {

@@ -322,10 +322,12 @@ int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *
                            float *const *packed, double *const *gnorm2, const int64_t *n, const float *max_norm,
                            const float *step_size, const float *bc2_sqrt, const float *omb1, const float *beta2, const float *omb2,
                            const float *eps, void *sync_ws = nullptr, const unsigned *const *skip = nullptr,
-                           const int64_t *tail = nullptr);  // tail[k]: of the n[k] elements, the last tail[k] are not part of `packed`
+                           const int64_t *tail = nullptr,   // tail[k]: of the n[k] elements, the last tail[k] are not part of `packed`
+                           const double *const *lr = nullptr, const double *bc1 = nullptr);  // [lr] lr[k]: device rate of network k (NULL: step_size[k]), bc1[k] its divisor
 int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float *adv, int64_t ring_base, int64_t ring_cap, float *out,
                      void *ws);                             // [ABI 7] rlppo_adv_stats
 int launch_kl_gate(hipStream_t st, const rlppo_kl_gate_args &a);  // [ABI 7] rlppo_kl_gate
+int launch_kl_gate_lr(hipStream_t st, const rlppo_kl_gate_args &a, const rlppo_lr_adapt_args &l);  // [lr] rlppo_kl_gate_lr
 int launch_welford(hipStream_t st, const float *x, int64_t ld, int64_t n, int d, void *mean, void *m2, long long count0, int state_f64);
 int launch_welford_merge(hipStream_t st, int d, void *mean, void *m2, long long count, const float *omean, const float *om2,
                          long long ocount, int state_f64);

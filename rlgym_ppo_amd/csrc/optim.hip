@@ -490,8 +490,13 @@ struct OptNet {
     float max_norm, step_size, bc2_sqrt, omb1, beta2, omb2, eps;
     PackJobs jobs;
     const unsigned *skip;  // [ABI 7] rlppo_opt_net.skip_word: non-zero = leave this network as it is (NULL: never)
+    const double *lr;      // [lr] rlppo_clip_adam_pack2_lr: the rate in device memory (NULL: step_size above, formed on the host)
+    double bc1;            //      1 - beta1^step, the host's double
 };
 __device__ __forceinline__ bool opt_skipped(const OptNet &N) { return N.skip && *N.skip; }
+// [lr] the host's step_size = (float)(lr / bc1) for the rate an earlier launch of the stream left in *N.lr: IEEE double division and
+// one rounding to float, so a rate in memory and the same rate in the descriptor give the same bits
+__device__ __forceinline__ float opt_step_size(const OptNet &N) { return N.lr ? (float)(*N.lr / N.bc1) : N.step_size; }
 struct OptPair {
     OptNet net[2];
 };
@@ -520,13 +525,14 @@ __global__ __launch_bounds__(256) void adam_pack2_kernel(OptPair o) {
     const float total = (float)sqrt(*N.gnorm2);
     float coef = N.max_norm / (total + 1e-6f);
     coef = coef > 1.f ? 1.f : coef;
+    const float step_size = opt_step_size(N);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N.n; i += (int64_t)gridDim.x * blockDim.x) {
         const float gi = N.g[i] * coef;
         float mi = N.m[i], vi = N.v[i];
         mi = mi + N.omb1 * (gi - mi);
         vi = vi * N.beta2 + (N.omb2 * gi) * gi;
         const float denom = sqrtf(vi) / N.bc2_sqrt + N.eps;
-        const float pi = N.p[i] + (-N.step_size * mi) / denom;
+        const float pi = N.p[i] + (-step_size * mi) / denom;
         N.p[i] = pi;
         N.m[i] = mi;
         N.v[i] = vi;
@@ -578,12 +584,12 @@ void set_fused_spin_limit(int v) { g_fused_spin_limit = v < 0 ? FUSED_SPIN_LIMIT
 static int g_fused_test_hold = 0;  // rlppo_dbg_set(35, 1): test hook -- workgroup (0, 0) never arrives (a grid that is not co-resident)
 void set_fused_test_hold(int v) { g_fused_test_hold = v; }
 
-__device__ __forceinline__ void adam_one(const OptNet &N, int64_t i, float gi, float mi, float vi, float p0, float coef) {
+__device__ __forceinline__ void adam_one(const OptNet &N, int64_t i, float gi, float mi, float vi, float p0, float coef, float step_size) {
     gi *= coef;
     mi = mi + N.omb1 * (gi - mi);
     vi = vi * N.beta2 + (N.omb2 * gi) * gi;
     const float denom = sqrtf(vi) / N.bc2_sqrt + N.eps;
-    const float pi = p0 + (-N.step_size * mi) / denom;
+    const float pi = p0 + (-step_size * mi) / denom;
     N.p[i] = pi;
     N.m[i] = mi;
     N.v[i] = vi;
@@ -639,7 +645,7 @@ __global__ __launch_bounds__(256) void adam_fused_kernel(OptPair o, FusedSync *_
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s);
     __shared__ double red[4];
-    __shared__ float s_total;
+    __shared__ float s_total, s_step;
     __shared__ int s_last, s_ok;
     __shared__ unsigned s_g0;
     if ((tid & 63) == 0) red[tid >> 6] = acc;
@@ -711,21 +717,22 @@ __global__ __launch_bounds__(256) void adam_fused_kernel(OptPair o, FusedSync *_
     if (tid == 0) {
         const double t = __hip_atomic_load(N.gnorm2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_total = (float)sqrt(t);
+        s_step = opt_step_size(N);  // [lr] behind the barrier: one read of the rate per workgroup
     }
     __syncthreads();
     if (!s_ok) return;  // given up: parameters, moments and gradients stay as they were (the timeout word says so)
     // [ABI 7] a skipped network still took part in the barrier (every workgroup arrives, whatever the other network does)
     if (opt_skipped(N)) return;
     // ---- phase 2: adam_pack2_kernel, element for element
-    const float total = s_total;
+    const float total = s_total, step_size = s_step;
     float coef = N.max_norm / (total + 1e-6f);
     coef = coef > 1.f ? 1.f : coef;
 #pragma unroll
     for (int e = 0; e < FUSED_EPT; ++e) {
         const int64_t i = i0 + e * stride;
-        if (i < N.n) adam_one(N, i, g[e], m[e], v[e], p[e], coef);
+        if (i < N.n) adam_one(N, i, g[e], m[e], v[e], p[e], coef, step_size);
     }
-    for (int64_t i = i0 + FUSED_EPT * stride; i < N.n; i += stride) adam_one(N, i, N.g[i], N.m[i], N.v[i], N.p[i], coef);
+    for (int64_t i = i0 + FUSED_EPT * stride; i < N.n; i += stride) adam_one(N, i, N.g[i], N.m[i], N.v[i], N.p[i], coef, step_size);
 }
 
 static void fill_jobs(const NetLayout &net, PackJobs *jobs) {
@@ -742,7 +749,8 @@ static void fill_jobs(const NetLayout &net, PackJobs *jobs) {
 int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *p, float *const *g, float *const *m, float *const *v,
                            float *const *packed, double *const *gnorm2, const int64_t *n, const float *max_norm,
                            const float *step_size, const float *bc2_sqrt, const float *omb1, const float *beta2, const float *omb2,
-                           const float *eps, void *sync_ws, const unsigned *const *skip, const int64_t *tail) {
+                           const float *eps, void *sync_ws, const unsigned *const *skip, const int64_t *tail, const double *const *lr,
+                           const double *bc1) {
     OptPair o;
     int64_t nmax = 0;
     for (int k = 0; k < 2; ++k) {
@@ -752,6 +760,8 @@ int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *
         N.omb2 = omb2[k]; N.eps = eps[k];
         N.skip = skip ? skip[k] : nullptr;
         N.n_net = n[k] - (tail ? tail[k] : 0);
+        N.lr = lr ? lr[k] : nullptr;
+        N.bc1 = bc1 ? bc1[k] : 1.0;
         fill_jobs(nets[k], &N.jobs);
         nmax = n[k] > nmax ? n[k] : nmax;
     }
@@ -954,7 +964,7 @@ int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float 
 
 // The target-KL gate (rlppo_kl_gate): one workgroup.  Thread t adds slots t, t + 256, ... of every pass region in order, a fixed
 // shuffle tree and a fixed sum over the four waves follow, the pass totals are weighted by their mb_ratio in pass order.
-__global__ __launch_bounds__(256) void kl_gate_kernel(rlppo_kl_gate_args g) {
+__device__ __forceinline__ double kl_gate_sum(const rlppo_kl_gate_args &g) {
     __shared__ double red[4];
     double kl = 0.0;
     for (int p = 0; p < g.n_passes; ++p) {
@@ -969,6 +979,11 @@ __global__ __launch_bounds__(256) void kl_gate_kernel(rlppo_kl_gate_args g) {
         kl += r[1] * ((red[0] + red[1]) + (red[2] + red[3]));
         __syncthreads();
     }
+    return kl;
+}
+
+__global__ __launch_bounds__(256) void kl_gate_kernel(rlppo_kl_gate_args g) {
+    double kl = kl_gate_sum(g);
     if (threadIdx.x != 0) return;
     if (g.phase == 1) {  // this rank's share travels in the tail of the exchanged gradient tensor
         const float hi = (float)kl;
@@ -985,6 +1000,54 @@ __global__ __launch_bounds__(256) void kl_gate_kernel(rlppo_kl_gate_args g) {
     __hip_atomic_store(g.host_words, stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
     __hip_atomic_store(g.host_words + 1, g.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// [lr] The same gate with the KL-adaptive rate rule (rlppo_kl_gate_lr; include/rlppo.h, "[lr]"): the stop decision first -- a gate
+// that stops the run moves no rate --, then every rate on its own, in double.  The stop word and the host words are optional: without
+// them the launch writes device memory only.  Plain vector stores of thread 0; the optimiser launch behind it on the stream reads them.
+__global__ __launch_bounds__(256) void kl_gate_lr_kernel(rlppo_kl_gate_args g, rlppo_lr_adapt_args l) {
+    double kl = kl_gate_sum(g);
+    if (threadIdx.x != 0) return;
+    if (g.phase == 1) {
+        const float hi = (float)kl;
+        g.exchange[0] = hi;
+        g.exchange[1] = (float)(kl - (double)hi);
+        return;
+    }
+    if (g.phase == 2) kl = (double)g.exchange[0] + (double)g.exchange[1];
+    unsigned stop = 0;
+    if (g.stop_word) {
+        stop = *g.stop_word;
+        if (stop == 0 && kl > g.threshold) {
+            stop = g.batch + 1;
+            *g.stop_word = stop;
+        }
+    }
+    if (l.kl_out) *l.kl_out = kl;
+    if (stop == 0) {
+        const double hi_kl = 2.0 * l.desired_kl, lo_kl = l.desired_kl / 2.0;
+        for (int i = 0; i < l.n_lr; ++i) {
+            const double lr = l.lr[i];
+            if (kl > hi_kl) {
+                const double v = lr / l.factor;
+                l.lr[i] = v < l.lr_min ? l.lr_min : v;
+            } else if (kl > 0.0 && kl < lo_kl) {
+                const double v = lr * l.factor;
+                l.lr[i] = v > l.lr_max ? l.lr_max : v;
+            }
+        }
+    }
+    if (g.host_words) {
+        __hip_atomic_store(g.host_words, stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+        __hip_atomic_store(g.host_words + 1, g.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+int launch_kl_gate_lr(hipStream_t st, const rlppo_kl_gate_args &a, const rlppo_lr_adapt_args &l) {
+    hipLaunchKernelGGL(kl_gate_lr_kernel, dim3(1), dim3(256), 0, st, a, l);
+    RLPPO_LAUNCH_CHECK();
+    return 0;
 }
 
 int launch_kl_gate(hipStream_t st, const rlppo_kl_gate_args &a) {

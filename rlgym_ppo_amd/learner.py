@@ -43,6 +43,7 @@ class Learner(object):
             n_checkpoints_to_keep: int = 5, shm_buffer_size: int = 8192, device: str = "auto",
             vector_env: bool = False, gae_bootstrap_truncated: bool = False, multi_discrete_bins=None,
             continuous_head: str = "reference", continuous_log_std_init: float = 0.0, continuous_action_clip="default",
+            ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
             per_feature_obs_standardization: bool = False,
             ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
         assert env_create_function is not None, "MUST PROVIDE A FUNCTION TO CREATE RLGYM FUNCTIONS TO INITIALIZE RLGYM-PPO"
@@ -52,6 +53,17 @@ class Learner(object):
         # range the reference's head clamps to; None: no clipping).  The option values are checked here, before anything needs the GPU
         # or spawns a process; that the action space IS continuous can only be checked once the environment has reported it (below,
         # before the PPOLearner is built -- like multi_discrete_bins).
+        # not in the reference: the learning-rate schedule (ppo/lr_schedule.py) -- "adaptive" is PPOLearner's (decided on the device, per
+        # optimiser step); "linear" is this loop's: before every learn() both rates are lr0 * max(0, 1 - T / timestep_limit), T the
+        # cumulative timesteps before the iteration's collect (stateless: a loaded checkpoint derives them from its book-keeping)
+        from .ppo import lr_schedule as LRS
+        ppo_lr_schedule, ppo_desired_kl, ppo_lr_bounds = LRS.check_schedule(ppo_lr_schedule, ppo_desired_kl, ppo_lr_bounds,
+                                                                            policy_lr=policy_lr, critic_lr=critic_lr)
+        if ppo_lr_schedule == "linear" and not (timestep_limit is not None and timestep_limit > 0):
+            raise ValueError(f"ppo_lr_schedule='linear' needs timestep_limit > 0, got {timestep_limit!r}")
+        if ppo_lr_schedule == "adaptive" and os.environ.get("RLPPO_FUSED_OPT", "1") == "0":   # (here: nothing is spawned yet)
+            raise ValueError(PPOLearner._ADAPTIVE_NEEDS_FUSED)
+        self.lr_schedule, self._lr0 = ppo_lr_schedule, [policy_lr, critic_lr]
         if continuous_head not in ("reference", "diag"):
             raise ValueError(f"continuous_head must be 'reference' or 'diag', got {continuous_head!r}")
         from .ppo.diag_gaussian_policy import check_log_std_init
@@ -149,6 +161,9 @@ class Learner(object):
             policy_lr=policy_lr, critic_lr=critic_lr, clip_range=ppo_clip_range, ent_coef=ppo_ent_coef,
             normalize_advantages=ppo_normalize_advantages, value_clip_range=ppo_value_clip_range, target_kl=ppo_target_kl,
             max_grad_norm=ppo_max_grad_norm)
+        if ppo_lr_schedule == "adaptive":   # ("linear" is this loop's: the update runs the constant schedule's launches)
+            self.ppo_learner.set_lr_schedule("adaptive", ppo_desired_kl, ppo_lr_bounds)
+        self.ppo_learner.report_learning_rates = ppo_lr_schedule != "constant"
         if continuous_head == "diag":   # (a constant fill before the first step and before a checkpoint is loaded: no generator use)
             self.ppo_learner.policy.fill_log_std(continuous_log_std_init)
         self.agent.policy = self.ppo_learner.policy
@@ -181,7 +196,10 @@ class Learner(object):
         }
 
         self.wandb_run = wandb_run
-        wandb_loaded = checkpoint_load_folder is not None and self.load(checkpoint_load_folder, load_wandb, policy_lr, critic_lr)
+        # "adaptive": the rates are run state -- a checkpoint's optimisers carry them (param_groups), the constructor's start a fresh run
+        # only; "linear": recomputed before every learn() anyway
+        lrs = (None, None) if ppo_lr_schedule != "constant" else (policy_lr, critic_lr)
+        wandb_loaded = checkpoint_load_folder is not None and self.load(checkpoint_load_folder, load_wandb, *lrs)
         if log_to_wandb and self.wandb_run is None and not wandb_loaded:
             if wandb is None:
                 raise RuntimeError("log_to_wandb=True but the wandb package is not installed")
@@ -191,13 +209,14 @@ class Learner(object):
         print("Learner successfully initialized!")
 
     def update_learning_rate(self, new_policy_lr=None, new_critic_lr=None):
+        # ("adaptive": the schedule goes on from the new rate at the next learn(); "linear": the new rate is the one annealed from)
         if new_policy_lr is not None:
-            self.policy_lr = new_policy_lr
+            self.policy_lr = self._lr0[0] = new_policy_lr
             for group in self.ppo_learner.policy_optimizer.param_groups:
                 group["lr"] = new_policy_lr
             print(f"New policy learning rate: {new_policy_lr}")
         if new_critic_lr is not None:
-            self.critic_lr = new_critic_lr
+            self.critic_lr = self._lr0[1] = new_critic_lr
             for group in self.ppo_learner.value_optimizer.param_groups:
                 group["lr"] = new_critic_lr
             print(f"New critic learning rate: {new_critic_lr}")
@@ -222,6 +241,10 @@ class Learner(object):
         print("Press (p) to pause (c) to checkpoint, (q) to checkpoint and quit (after next iteration)\n")
         while self.agent.cumulative_timesteps < self.timestep_limit:
             epoch_start = time.perf_counter()
+            if self.lr_schedule == "linear":
+                from .ppo.lr_schedule import linear_lr
+                for opt, lr0 in zip((self.ppo_learner.policy_optimizer, self.ppo_learner.value_optimizer), self._lr0):
+                    opt.param_groups[0]["lr"] = linear_lr(lr0, self.agent.cumulative_timesteps, self.timestep_limit)
             experience, collected_metrics, steps_collected, collection_time = self.agent.collect_timesteps(self.ts_per_epoch)
             if self.metrics_logger is not None:
                 self.metrics_logger.report_metrics(collected_metrics, self.wandb_run, self.agent.cumulative_timesteps)

@@ -19,13 +19,19 @@ Four opt-in options go beyond the reference (trailing keyword arguments; DESIGN.
 advantage normalisation, Stable-Baselines3's clipped value loss, a target-KL stop of the optimiser steps and the gradient-norm
 limit.  Their defaults are the reference's update, launch for launch.  With policy_type 1, `act_space_size` may be the nvec of a
 MultiDiscrete(nvec) action space (a sequence of bin counts) instead of its length: an integer keeps the reference's eight heads
-[3, 3, 3, 3, 3, 2, 2, 2] and its kernels.  (The constructor's parameter list is the reference's plus the four options and stays
-that: the bins have no keyword of their own here; `Learner` has `multi_discrete_bins`.)
+[3, 3, 3, 3, 3, 2, 2, 2] and its kernels.  (The constructor's parameter list is the reference's plus the four options: the bins
+have no keyword of their own here, `Learner` has `multi_discrete_bins`; the learning-rate schedule below is chosen with
+`set_lr_schedule`, after construction.)
 
 policy_type 3 (not in the reference) is the diagonal-Gaussian head with a learnable log_std (ppo/diag_gaussian_policy.py):
 `act_space_size` = k action dimensions, `continuous_var_range` is ignored; log_std starts at 0 (SB3's default;
 DiagGaussianPolicy.fill_log_std sets another start, as `Learner(continuous_log_std_init=...)` does).  Its passes go through
 rlppo_ppo_minibatch_diag and its optimiser step through rlppo_clip_adam_pack2_tail (log_std is the tail of the policy's arena).
+
+`set_lr_schedule("adaptive", desired_kl=0.01, lr_bounds=(1e-5, 1e-2))` (ppo/lr_schedule.py) is rsl_rl's
+KL-adaptive learning rate, once per optimiser step: both rates are doubles in device memory, moved by the batch's gate (rlppo_kl_gate_lr) and read by its
+optimiser step (rlppo_clip_adam_pack2_lr) -- no host decision, no wait that the constant schedule does not make.  "constant"
+(default) is the update above, launch for launch; "linear" needs a horizon and is `Learner`'s.
 """
 import ctypes
 import os
@@ -38,6 +44,7 @@ from .. import _native as N
 from ..dp import all_reduce_sum, dist_info, fuse_runs, slices_for_rank
 from ..engine import Workspace, ptr, require_gpu, stream_ptr
 from ..util import action_mask as AM
+from . import lr_schedule as LRS
 from .continuous_policy import ContinuousPolicy
 from .diag_gaussian_policy import DiagGaussianPolicy
 from .discrete_policy import DiscreteFF
@@ -60,6 +67,9 @@ class FusedAdam(torch.optim.Adam):
         self.exp_avg_sq = torch.zeros(a.n_flat, dtype=torch.float32, device=a.device)
         self.gnorm2 = torch.zeros(1, dtype=torch.float64, device=a.device)
         self.step_count = 0
+        # lr_schedule="adaptive": this optimiser's rate as ONE device double (PPOLearner lays both side by side, as it does gnorm2);
+        # param_groups[0]["lr"] is its host copy -- written to the device at the start of a learn(), read back at its end
+        self.lr_word = None
 
     def _expose_state(self):
         o = 0
@@ -195,7 +205,7 @@ class PPOLearner(object):
 
         # one contiguous gradient buffer [policy | critic] so that data-parallel needs a single all-reduce
         pa, va = self.policy.arena, self.value_net.arena
-        # (+ 2 floats: with target_kl set, the exchanged tensor carries this rank's KL partial of the batch in its tail)
+        # (+ 2 floats: with target_kl set or the adaptive schedule, the exchanged tensor carries this rank's KL partial of the batch in its tail)
         self._grad_ex = torch.zeros(pa.n_flat + va.n_flat + 2, dtype=torch.float32, device=self._dev)
         self._grad_all = self._grad_ex[:pa.n_flat + va.n_flat]
         pa.grad = self._grad_all[:pa.n_flat]
@@ -234,6 +244,13 @@ class PPOLearner(object):
         self.max_grad_norm = max_grad_norm
         self._opt = None      # their device state, allocated on first use
         self._kl_seq = 0
+        # learning-rate schedule (plain attributes like the options above, read by every learn(); set_lr_schedule checks and sets
+        # them at once).  "adaptive": [policy rate, critic rate, KL_b of the last gate (written only while lr_probe is set)] in
+        # device doubles + the pinned pair the rates come back in with the report
+        self.lr_schedule, self.desired_kl, self.lr_bounds = "constant", 0.01, (1e-5, 1e-2)
+        self.report_learning_rates = False   # (Learner sets it for its "linear" schedule)
+        self.lr_probe = None  # callable(rates [2] device doubles {policy, critic}, KL_b [1] device double) after every gate (tests)
+        self._lr_dev = self._lr_host = None
 
     # --------------------------------------------------------------------------------------------- learn
     def _minibatch_args(self, exp, rank=0, world=1):
@@ -309,7 +326,27 @@ class PPOLearner(object):
             return N.lib().rlppo_ppo_minibatch(st, ctypes.byref(args))
         return N.lib().rlppo_ppo_minibatch_nvec(st, ctypes.byref(args), nvec, self.policy.n_heads)
 
+    _ADAPTIVE_NEEDS_FUSED = ("lr_schedule='adaptive' needs the library's optimiser step (RLPPO_FUSED_OPT=1): the FusedAdam.step form takes "
+                             "its rate from the host and cannot read one the gate wrote on the device")
+
+    def set_lr_schedule(self, lr_schedule="constant", desired_kl=0.01, lr_bounds=(1e-5, 1e-2)):
+        """Choose the learning-rate schedule of every later learn(): "constant" (the default: the update as it was, launch for
+        launch) or "adaptive" (module docstring).  Checked here, on the host alone -- a ValueError leaves the learner as it was;
+        the rates "adaptive" starts from are the optimisers' current ones (param_groups[0]["lr"])."""
+        lr_schedule, desired_kl, lr_bounds = LRS.check_schedule(
+            lr_schedule, desired_kl, lr_bounds, policy_lr=self.policy_optimizer.param_groups[0]["lr"],
+            critic_lr=self.value_optimizer.param_groups[0]["lr"], allow_linear=False)
+        if lr_schedule == "adaptive" and not self.fused_optimizer_step:
+            raise ValueError(self._ADAPTIVE_NEEDS_FUSED)
+        self.lr_schedule, self.desired_kl, self.lr_bounds = lr_schedule, desired_kl, lr_bounds
+        self.report_learning_rates = lr_schedule != "constant"
+
     def _check_options(self):
+        self.lr_schedule, self.desired_kl, self.lr_bounds = LRS.check_schedule(
+            self.lr_schedule, self.desired_kl, self.lr_bounds, policy_lr=self.policy_optimizer.param_groups[0]["lr"],
+            critic_lr=self.value_optimizer.param_groups[0]["lr"], allow_linear=False)
+        if self.lr_schedule == "adaptive" and not self.fused_optimizer_step:
+            raise ValueError(self._ADAPTIVE_NEEDS_FUSED)
         if self.value_clip_range is not None and not float(self.value_clip_range) > 0:
             raise ValueError(f"value_clip_range must be > 0 or None, got {self.value_clip_range!r}")
         if self.target_kl is not None and not float(self.target_kl) > 0:
@@ -334,6 +371,17 @@ class PPOLearner(object):
         if o["kl"].numel() < kl_slot_doubles:
             o["kl"] = torch.zeros(kl_slot_doubles, dtype=torch.float64, device=self._dev)
         return o
+
+    def _lr_state(self):
+        """Device doubles of the adaptive schedule, refreshed from the optimisers' host copies (a rate written to
+        param_groups[0]["lr"] between two learn() calls is honoured): two fills, scalars as launch arguments -- no copy, no wait."""
+        if self._lr_dev is None:
+            self._lr_dev = torch.zeros(3, dtype=torch.float64, device=self._dev)
+            self._lr_host = torch.zeros(2, dtype=torch.float64).pin_memory()
+            self.policy_optimizer.lr_word, self.value_optimizer.lr_word = self._lr_dev[0:1], self._lr_dev[1:2]
+        for opt in (self.policy_optimizer, self.value_optimizer):
+            opt.lr_word.fill_(float(opt.param_groups[0]["lr"]))
+        return self._lr_dev
 
     def _kl_decision(self, g, done_value):
         """The stop word after batch g's gate (0 = running, else trigger + 1): waits for the gate's pinned words."""
@@ -369,7 +417,9 @@ class PPOLearner(object):
         B, MB = self.batch_size, self.mini_batch_size
         n_slices = B // MB
         max_norm = float(self.max_grad_norm)
-        kl_on = self.target_kl is not None
+        stop_on = self.target_kl is not None        # the host's decision wait and the stop word: target_kl alone
+        adaptive = self.lr_schedule == "adaptive"
+        kl_on = stop_on or adaptive                 # KL armed: the slots, the exchange tail, the gate
         stopped_at = None   # target_kl: the batch whose KL stopped this learn() (its step and every later one not applied)
         gate_values = {}    # batch -> done value of its gate
 
@@ -402,13 +452,22 @@ class PPOLearner(object):
                 if self.normalize_advantages:
                     args.adv_norm = o["adv"].data_ptr()
                 if kl_on:
-                    o["stop"].zero_()
-                    args.stop_word = o["stop"].data_ptr()
                     gate = N.KlGateArgs()
                     gate.kl_slots, gate.slot_stride, gate.n_passes = o["kl"].data_ptr(), stride, len(runs)
-                    gate.threshold = 1.5 * float(self.target_kl)
                     gate.exchange = self._grad_ex.data_ptr() + 4 * self._grad_all.numel()
+                if stop_on:
+                    o["stop"].zero_()
+                    args.stop_word = o["stop"].data_ptr()
+                    gate.threshold = 1.5 * float(self.target_kl)
                     gate.stop_word = o["stop"].data_ptr()
+                if adaptive:   # the gate moves the two rates, the optimiser step reads them: the host takes no part until the report
+                    lr_dev = self._lr_state()
+                    adapt = N.LrAdaptArgs()
+                    adapt.lr, adapt.n_lr, adapt.desired_kl, adapt.factor = lr_dev.data_ptr(), 2, self.desired_kl, LRS.ADAPT_FACTOR
+                    adapt.lr_min, adapt.lr_max = self.lr_bounds
+                    run_gate = lambda: L.rlppo_kl_gate_lr(st, ctypes.byref(gate), ctypes.byref(adapt))
+                elif kl_on:
+                    run_gate = lambda: L.rlppo_kl_gate(st, ctypes.byref(gate))
             # The legacy-MT19937 permutation is inherently serial host work.  The buffer's shuffle pipeline draws it on
             # helper threads several epochs ahead (also across learn() calls) and uploads every index vector on its own
             # stream (engine.LegacyPermutation / DeviceIndexRing): here an epoch only orders the stream after that copy.
@@ -422,7 +481,7 @@ class PPOLearner(object):
                 refilled = False
                 for b in range(n_batches):
                     g = epoch * n_batches + b
-                    if kl_on and g >= 2:
+                    if stop_on and g >= 2:
                         # at most one undecided batch beyond the executing one: batch g waits for the decision of batch g - 2
                         v = self._kl_decision(g - 2, gate_values[g - 2])
                         if v:
@@ -462,19 +521,23 @@ class PPOLearner(object):
                         self._before[1].copy_(va.flat)
                         have_before = True
                     n_minibatch_iterations += n_slices
-                    if kl_on:
+                    if stop_on:
                         self._kl_seq = self._kl_seq % 0x7FFFFFFF + 1
                         gate_values[g] = self._kl_seq
                         gate.batch, gate.done_value = g, self._kl_seq
                         gate.host_words = self._opt["host"].data_ptr() + 8 * (g % 4)
-                        if world > 1:  # this rank's KL share rides in the tail of the ONE exchange of the step
-                            gate.phase = 1
-                            N.check(L.rlppo_kl_gate(st, ctypes.byref(gate)))
+                    if kl_on and world > 1:  # this rank's KL share rides in the tail of the ONE exchange of the step
+                        gate.phase = 1
+                        N.check(run_gate())
                     if world > 1:
                         yield self._grad_ex if kl_on else self._grad_all  # summed over the ranks (RCCL over xGMI) before clipping
                     if kl_on:
                         gate.phase = 2 if world > 1 else 0
-                        N.check(L.rlppo_kl_gate(st, ctypes.byref(gate)))
+                        if adaptive:
+                            adapt.kl_out = lr_dev.data_ptr() + 16 if self.lr_probe is not None else None
+                        N.check(run_gate())
+                        if adaptive and self.lr_probe is not None:  # test hook: the rates this batch's step will use, the KL that set them
+                            self.lr_probe(lr_dev[:2], lr_dev[2:3])
                     if self.grad_probe is not None:  # test hook: the batch gradient clip_grad_norm_ / Adam are about to see
                         self.grad_probe(self._grad_all)
                     if self.fused_optimizer_step:
@@ -482,10 +545,13 @@ class PPOLearner(object):
                         # operations instead of 9 (csrc/optim.hip)
                         dv = self.value_optimizer.fused_descriptor(max_norm)
                         dp_ = self.policy_optimizer.fused_descriptor(max_norm)
-                        if kl_on:   # (a step after the stop touches nothing: the gate's stop word)
+                        if stop_on:   # (a step after the stop touches nothing: the gate's stop word)
                             dv.skip_word = dp_.skip_word = gate.stop_word
                         sync = ptr(self._opt_sync) if self.one_launch_optimizer else None
-                        if va.n_tail or pa.n_tail:   # parameters behind a network's layers (log_std): same norm, same step, never packed
+                        if adaptive:   # both rates from the device doubles the gate has just left (descriptor order: critic, policy)
+                            N.check(L.rlppo_clip_adam_pack2_lr(st, ctypes.byref(dv), ctypes.byref(dp_), sync, va.n_tail, pa.n_tail,
+                                                               self.value_optimizer.lr_word.data_ptr(), self.policy_optimizer.lr_word.data_ptr()))
+                        elif va.n_tail or pa.n_tail:   # parameters behind a network's layers (log_std): same norm, same step, never packed
                             N.check(L.rlppo_clip_adam_pack2_tail(st, ctypes.byref(dv), ctypes.byref(dp_), sync, va.n_tail, pa.n_tail))
                         else:
                             N.check(L.rlppo_clip_adam_pack2(st, ctypes.byref(dv), ctypes.byref(dp_), sync))
@@ -498,7 +564,7 @@ class PPOLearner(object):
                     n_iterations += 1
                 if not refilled:
                     exp.refill_shuffle()
-            if kl_on:
+            if stop_on:
                 if stopped_at is None and n_iterations > 0:   # a trigger among the last two batches
                     v = self._kl_decision(n_iterations - 1, gate_values[n_iterations - 1])
                     stopped_at = v - 1 if v else None
@@ -538,6 +604,9 @@ class PPOLearner(object):
             rep.extra = to_all.data_ptr()
         # [r6] update magnitudes (ppo_learner.py:214-222), the statistics and the give-up words in ONE launch that writes pinned memory
         # and releases a completion word (rlppo_learn_report): one device->host hand-over per learn(), no eager tail
+        lr_back = adaptive and self._lr_dev is not None and n_batches > 0 and total > 0
+        if lr_back:   # the two rates ride to pinned memory in front of the report launch: its completion word covers them too
+            self._lr_host.copy_(self._lr_dev[:2], non_blocking=True)
         self._report_seq = self._report_seq % 0x7FFFFFFF + 1
         rep.out, rep.done_word, rep.done_value, rep.ws = (self._report_out.data_ptr(), self._report_done.data_ptr(), self._report_seq,
                                                           self._report_ws.data_ptr())
@@ -548,6 +617,8 @@ class PPOLearner(object):
                 raise RuntimeError("rlppo_learn_report: the completion word did not arrive")
         self._stats_clean = True
         stats = self._report_out_np.copy()
+        if lr_back:   # gate state, not step state: they stand whatever became of the steps (stopped, skipped, given up)
+            self.policy_optimizer.param_groups[0]["lr"], self.value_optimizer.param_groups[0]["lr"] = (float(x) for x in self._lr_host.numpy())
         if stats[N.N_STATS + 3] != 0:
             # A grid-barrier wait of the one-launch optimiser step gave up on some rank (GPU shared with a kernel that never yields,
             # a partitioned device, or a defect).  Giving up is all or nothing (include/rlppo.h): on the rank it happened, that step
@@ -598,7 +669,7 @@ class PPOLearner(object):
         n_iter_r = max(n_iterations, 1)
         n_mb_r = max(float(stats[N.STAT_PASSES]), 1.0)
         policy_update_magnitude, critic_update_magnitude = float(stats[N.N_STATS]), float(stats[N.N_STATS + 1])
-        self.cumulative_model_updates += n_iterations if kl_on else n_iter_r   # (with target_kl: applied steps only)
+        self.cumulative_model_updates += n_iterations if stop_on else n_iter_r   # (with target_kl: applied steps only)
 
         report = {
             "PPO Batch Consumption Time": elapsed / n_iter_r,
@@ -610,9 +681,12 @@ class PPOLearner(object):
             "Policy Update Magnitude": policy_update_magnitude,
             "Value Function Update Magnitude": critic_update_magnitude,
         }
-        if kl_on:
+        if stop_on:
             report["PPO Optimizer Steps"] = n_iterations
             report["KL Early Stopped"] = 1.0 if stopped_at is not None else 0.0
+        if self.report_learning_rates:   # the optimisers' rates after this learn() ("adaptive": as its last gate left them; "linear": this iteration's)
+            report["Policy Learning Rate"] = float(self.policy_optimizer.param_groups[0]["lr"])
+            report["Critic Learning Rate"] = float(self.value_optimizer.param_groups[0]["lr"])
         if not grads_zero:  # the fused optimiser step leaves the arena zeroed
             self._grad_all.zero_()
         return report

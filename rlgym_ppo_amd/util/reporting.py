@@ -12,10 +12,12 @@ GROUPS = (
     ("Timesteps Collected",),
 )
 # keys of the options beyond the reference: printed (as one more group) only when the report has them -- PPOLearner adds them
-# when target_kl is set
+# when target_kl is set, and the two rates under a learning-rate schedule other than "constant"
 OPTIONAL_GROUPS = (
     ("PPO Optimizer Steps", "KL Early Stopped"),
+    ("Policy Learning Rate", "Critic Learning Rate"),
 )
+SCIENTIFIC = {"Policy Learning Rate", "Critic Learning Rate"}   # five decimals would print most learning rates as 0.00000
 
 
 def _form_printable_groups(report):
@@ -40,7 +42,7 @@ def _fmt(val):
 
 
 def dump_dict_to_debug_string(dictionary):
-    return "".join(f"{k}: {_fmt(v)}\n" for k, v in dictionary.items())
+    return "".join(f"{k}: {format(float(v), '.4e') if k in SCIENTIFIC else _fmt(v)}\n" for k, v in dictionary.items())
 
 
 def report_metrics(loggable_metrics, debug_metrics, wandb_run=None):
