@@ -779,6 +779,48 @@ int rlppo_welford_increment(void *stream, const float *samples, int64_t ld, int6
 int rlppo_welford_merge(void *stream, int32_t d, void *mean, void *m2, int64_t count, const float *other_mean,
                         const float *other_m2, int64_t other_count, int32_t state_is_f64);
 
+/* ------------------------------------------------------------------- device-resident vector environments (csrc/rollout.hip)
+ * The bookkeeping between two steps of an environment that lives on the GPU (batched_agents/vector_agent_manager.py,
+ * _collect_device).  The three entry points below make LAUNCHES ONLY: none of them contains a stream synchronisation, a blocking
+ * copy or an allocation, so a host that enqueues a whole collect through them never waits for the device. */
+#define RLPPO_DT_F32 0
+#define RLPPO_DT_F64 1
+#define RLPPO_DT_U8 2   /* one byte per entry: bool / uint8 */
+/* One environment step's rewards / dones / truncated (device arrays of n_agents entries; a dtype code each; rewards float32 or
+ * float64; the flags are zero / non-zero; truncated may be NULL = all zero) enter
+ *   rdt[3][T][n_agents] (float32, time-major planes rewards / dones / truncated) at step t: r rounded ONCE to float32, the flags as
+ *     exact 0.0 / 1.0; at t == T - 1 the truncated plane takes the flush rule instead (1 where done == 0, else 0: quirk Q4,
+ *     batched_agent_manager.py:154-172) -- the bookkeeping below has used the environment's own flags by then;
+ *   ep_sums[n_agents] (double): += (double)(float)r;
+ *   state (int64[3]: the bits of the double average, a has-value word, the ended-episode counter): every agent with done or
+ *     truncated set BY THE ENVIRONMENT'S FLAGS is folded into the average IN AGENT ORDER with the reference's operations
+ *     (batched_agent_manager.py:377-399): the first episode ever sets avg = x, after that avg = avg * 0.9 + x * 0.1 -- two double
+ *     multiplications and one addition, never contracted -- where x is the agent's episode sum including this step; its sum is
+ *     then zeroed and the counter advanced;
+ *   patch (optional, float32[n_agents], this step's row of a patch plane): 1.0 where the environment truncated and did not
+ *     terminate the episode (the steps whose next-state row is the final observation), else 0.0.
+ * One workgroup; the ended agents of a 1024-agent chunk are compacted in agent order and folded by one thread: the cost of a
+ * step on which every agent ends is n_agents dependent double multiply-adds (DESIGN.md section 8b has the measurement). */
+int rlppo_rollout_record(void *stream, const void *rewards, int32_t rewards_dt, const void *dones, int32_t dones_dt, const void *truncated,
+                         int32_t truncated_dt, int64_t n_agents, int64_t t, int64_t T, float *rdt, double *ep_sums, void *state,
+                         float *patch);
+/* WelfordRunningStat.mean / .std (running_stats.py:100-117) of a device-resident state (mean[d], m2[d] in the state's dtype, as
+ * rlppo_welford_increment keeps them) for the HOST-KNOWN sample count, as the float32 vectors mean_v[d] / std_v[d] that mode 2 of
+ * rlppo_discrete_step and rlppo_pad_rows_per_feature read: count < 2 gives 0 / 1; else var = m2 / (count - 1) in the state's dtype,
+ * 1 where var == 0, the IEEE square root, one rounding to float32.  per_feature == 0: every entry holds feature 0's pair (the
+ * reference's scalar standardisation, quirk Q5); else each its own. */
+int rlppo_obs_scalars(void *stream, const void *mean, const void *m2, int32_t state_is_f64, int64_t count, int32_t d, int32_t per_feature,
+                      float *mean_v, float *std_v);
+/* Time-major rollout storage -> the reference's trajectory-major arrays (row a * T + t of agent a, batched_trajectory.py:58-105), one
+ * launch that reads the storage once.  In: S[T + 1][n_agents][ld] policy-input rows (ld a multiple of 4, rows 16-byte aligned),
+ * acts[T][n_agents][k], logp[T][n_agents], rdt[3][T][n_agents].  Out (N = n_agents * T): flat[N + 1][ld] -- S[t][a] at a * T + t,
+ * flat[N] = S[T][n_agents - 1] --, nxt[N][ld] -- S[t][a] at a * T + t - 1 for t >= 1 --, actions[N][k], log_probs / rewards / dones /
+ * truncated[N].  patch[T][n_agents] with final_rows[T][n_agents][ld] (both or neither): where patch[t][a] != 0 the next-state row
+ * of step t of agent a is final_rows[t][a] instead. */
+int rlppo_rollout_to_trajectory_major(void *stream, const float *S, const float *acts, const float *logp, const float *rdt, int64_t n_agents,
+                                      int64_t T, int32_t ld, int32_t k, const float *patch, const float *final_rows, float *flat, float *nxt,
+                                      float *actions, float *log_probs, float *rewards, float *dones, float *truncated);
+
 /* Precision of the ROLLOUT forward passes (rlppo_mlp_forward, rlppo_*_act): 0 = fp32 (default; the parity mode),
  * 1 = activations and master weights rounded to bf16 as MFMA operands, fp32 accumulation / bias / activation
  * (BASELINE configs[4] "bf16 fwd / fp32 master weights").  The update has its own switch (rlppo_set_update_precision).  The reference
@@ -866,8 +908,8 @@ const int64_t *rlppo_selection_epoch_ptr(void);   /* the counter itself (a host 
 /* Which form calls took so far in this process (tests assert that the kernel they mean to pin is the one that ran): 0 = rollout steps
  * served by the one-launch kernel (rlppo_discrete_act / rlppo_discrete_step), 1 = by the layer chain, 2 = rlppo_ppo_minibatch passes,
  * 3 = of them with paired policy + critic launches, 4 = of them with the gather fused into the first layer, 5 = of them with the
- * grouped weight-gradient launch, 6 = [nvec] launches of the multi-discrete head's general (any nvec) kernels, sampling and loss;
- * -1 for an unknown key. */
+ * grouped weight-gradient launch, 6 = [nvec] launches of the multi-discrete head's general (any nvec) kernels, sampling and loss,
+ * 7 = rlppo_rollout_record launches (the device-resident collect form of the vector manager ran); -1 for an unknown key. */
 int64_t rlppo_dbg_counter(int32_t key);
 /* Debug helper, like rlppo_dbg_counter: adds delta to counter `key` (6 only; anything else RLPPO_ERR_ARG).  The launchers count when
  * they are CALLED; a host that captures a call into a graph and replays it (rlgym_ppo_amd/ppo/_mlp.py::ActGraph, the masked

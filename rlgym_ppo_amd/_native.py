@@ -204,6 +204,11 @@ SIGNATURES = {
     "rlppo_gather_rows": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64]),
     "rlppo_welford_increment": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32]),
     "rlppo_welford_merge": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32]),
+    "rlppo_rollout_record": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "rlppo_obs_scalars": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "rlppo_rollout_to_trajectory_major": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rlppo_set_inference_precision": (c_int32, [c_int32]),
     "rlppo_set_update_precision": (c_int32, [c_int32]),
     "rlppo_get_update_precision": (c_int32, []),

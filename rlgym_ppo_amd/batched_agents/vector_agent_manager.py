@@ -27,6 +27,24 @@ Optional, used with `bootstrap_truncated` (Learner(gae_bootstrap_truncated=True)
 the auto-reset has replaced in `obs`.  Those rows are standardised like that step's `obs`, kept out of the running
 statistics and put into the next-state rows of those steps; the collect then leaves `bootstrap_steps`, `bootstrap_index`
 and `bootstrap_rows` (the truncated-and-not-done steps and their next-state rows) for the GAE scan.
+
+Device interface (an environment that itself lives on the GPU; chosen when `reset()` answers a torch.Tensor on a GPU, collected by
+`_collect_device`; a numpy environment takes the two host forms exactly as they are):
+  * `reset() -> Tensor[n, d]`, float32 or float64;
+  * `step(actions) -> (obs[n, d], rewards[n], dones[n], truncated[n], info)`, or the 4-tuple without `truncated`: `actions` is a
+    fresh float32 device tensor [n, k] in the host interface's float encoding, never a view of the rollout storage; `rewards`
+    float32 or float64, the flags bool, uint8 or float (zero / non-zero);
+  * the environment works on torch's current stream and may reuse its output tensors at the next `step`: the manager has consumed
+    them by then in stream order;
+  * optional `action_masks() -> bool Tensor[n, width]` on the device, packed by `Layout.pack`'s device branch (nothing is read back;
+    an empty row counts as all-valid, as documented there);
+  * optional `info["final_observation"]`, Tensor[n, d], with `bootstrap_truncated`: staged with that step's standardisation vectors
+    and put into the next-state rows where the environment truncated and did not terminate.  The host does not know which steps
+    those are: the collect leaves the DENSE form, `bootstrap_dense = True` and `bootstrap_rows` = all N next-state rows (the scan
+    selects by the flags);
+  * `info["state"]` and `collect_metrics_fn` as above; a metrics function that reads the device is the user's own wait.
+Within a collect the host enqueues work and never waits for the device; it reads back once, at the end (the observation statistics,
+the reward average and the ended-episode count in one copy).  An environment on another GPU than the policy's is a ValueError.
 """
 import time
 import warnings
@@ -37,6 +55,89 @@ import torch
 from ..util import action_mask as AM
 from ..util.running_stats import WelfordRunningStat
 from .batched_agent import describe_action_space
+
+
+def device_env_of(first_obs):
+    """Which interface an environment speaks, judged by what its reset() answered: the torch.device of a tensor on a GPU (the device
+    interface, _collect_device), or None (numpy arrays, lists, CPU tensors: the host interface)."""
+    if isinstance(first_obs, torch.Tensor) and first_obs.is_cuda:
+        return first_obs.device
+    return None
+
+
+def check_same_device(env_device, policy_device):
+    """A device environment must live on the policy's GPU: the collect enqueues both on one stream."""
+    env_device, policy_device = torch.device(env_device), torch.device(policy_device)
+    same = env_device.type == policy_device.type and (env_device.index is None or policy_device.index is None
+                                                      or env_device.index == policy_device.index)
+    if not same:
+        raise ValueError(f"the vector environment lives on {env_device} but the policy on {policy_device}: a device-resident "
+                         "environment must be on the policy's device")
+
+
+_DT_CODES = {torch.float32: 0, torch.float64: 1, torch.bool: 2, torch.uint8: 2}   # RLPPO_DT_*
+
+
+def _dt_code(x, what, device, n):
+    """Device array of one step (rewards / flags) -> (tensor the record kernel reads, dtype code)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError(f"a device-resident vector environment answers device tensors: step() returned {what} as "
+                         f"{type(x).__name__}" + (f" on {x.device}" if isinstance(x, torch.Tensor) else ""))
+    check_same_device(x.device, device)
+    x = x.detach().reshape(-1)
+    if x.numel() != n:
+        raise ValueError(f"step() returned {x.numel()} {what} for {n} agents")
+    if x.dtype not in _DT_CODES:
+        x = x.to(torch.float32)
+    return x.contiguous(), _DT_CODES[x.dtype]
+
+
+class _HostInterfaceGuard(object):
+    """An environment whose reset() answered a CPU tensor speaks the host interface; a step() that then answers device tensors is
+    refused by name (numpy would fail on them with a conversion error)."""
+
+    def __init__(self, env):
+        self._env = env
+
+    def step(self, actions):
+        out = self._env.step(actions)
+        if isinstance(out[0], torch.Tensor) and out[0].is_cuda:
+            raise ValueError(f"the vector environment's reset() returned a CPU tensor but its step() returns observations on "
+                             f"{out[0].device}: a device-resident environment answers device tensors from reset() on")
+        return out
+
+    def __getattr__(self, name):
+        if name.startswith("__") or name == "_env":
+            raise AttributeError(name)
+        return getattr(self._env, name)
+
+
+class _DeviceBook(object):
+    """What _collect_device keeps on the device between environment steps, one allocation read back in ONE copy per collect:
+    blob = [ state: int64[3] = bits of the double episode-reward average, has-value word, ended-episode counter |
+             mean[d] | m2[d] : the running observation statistics in the host state's dtype (float32; float64 after a checkpoint load) ],
+    ep_sums double[n]; two pairs of standardisation vectors (mean_v, std_v): a step's increment writes the pair that the
+    observations still waiting for the previous pair do not read."""
+
+    def __init__(self, device, n_agents):
+        self.device, self.d, self.f64 = device, -1, False
+        self.ep_sums = torch.zeros(n_agents, dtype=torch.float64, device=device)
+        self.blob = self.pin = self.state = self.mean = self.m2 = None
+        self.vec, self.cur = None, 0
+
+    def layout(self, d, f64):
+        if self.blob is not None and (d, f64) == (self.d, self.f64):
+            return
+        self.d, self.f64 = d, f64
+        es, dt = (8, torch.float64) if f64 else (4, torch.float32)
+        size = 24 + 2 * d * es
+        self.blob = torch.zeros(size, dtype=torch.uint8, device=self.device)
+        self.pin = torch.zeros(size, dtype=torch.uint8, pin_memory=True)
+        self.state = self.blob[:24].view(torch.int64)
+        self.mean = self.blob[24:24 + d * es].view(dt)
+        self.m2 = self.blob[24 + d * es:].view(dt)
+        if d and self.vec is None:
+            self.vec = [tuple(torch.empty(d, dtype=torch.float32, device=self.device) for _ in range(2)) for _ in range(2)]
 
 
 class VectorAgentManager(object):
@@ -65,7 +166,12 @@ class VectorAgentManager(object):
         self.bootstrap_steps = None   # int64 host indices (trajectory-major) of the steps with truncated and not done
         self.bootstrap_index = None   # the same on the device; None when they are exactly the last step of every agent (the flush)
         self.bootstrap_rows = None    # [m, ld] device rows: the next states of those steps, in the order of bootstrap_steps
+        self.bootstrap_dense = False  # True (device environment): bootstrap_rows are ALL N next-state rows, the scan selects by the flags
         self._warned_no_final_obs = False
+        self._env_device = None       # torch.device of a device-resident environment (its reset() answered a GPU tensor), else None
+        self._book = None             # _DeviceBook: the device environment's persistent bookkeeping
+        self.last_enqueue_seconds = None   # device environment: host seconds the last collect spent enqueuing, before its one read
+        self.episodes_ended = 0       # device environment: episodes ended so far (read back with the average at the end of a collect)
 
     def _env_mask(self):
         """The environment's action_masks() for the observation the agents act on next, packed on the device; None without it."""
@@ -98,7 +204,13 @@ class VectorAgentManager(object):
         self.collect_metrics_fn = collect_metrics_fn
         if hasattr(self.env.action_space, "seed"):
             self.env.action_space.seed(self.seed)
-        obs = np.asarray(self.env.reset(), dtype=np.float32)
+        first = self.env.reset()
+        self._env_device = device_env_of(first)
+        if self._env_device is not None:   # a device-resident environment: _collect_device
+            return self._init_device_env(first)
+        if isinstance(first, torch.Tensor):   # a CPU tensor: the host interface, held to it (a device step() is refused by name)
+            self.env = _HostInterfaceGuard(self.env)
+        obs = np.asarray(first, dtype=np.float32)
         self.n_agents, d = obs.shape
         self._ep_rews = np.zeros(self.n_agents, np.float64)
         self.obs_stats = None
@@ -159,6 +271,8 @@ class VectorAgentManager(object):
     def collect_timesteps(self, n):
         """-> ((states, actions, log_probs, rewards, next_states, dones, truncated), metrics, n_collected, seconds):
         device tensors in trajectory-major order; `self.value_input_rows` holds states ++ last next_state contiguously."""
+        if self._env_device is not None:
+            return self._collect_device(n)
         if getattr(self.policy, "fused_step", False):
             return self._collect_fused(n)
         return self._collect_chain(n)
@@ -333,6 +447,207 @@ class VectorAgentManager(object):
         self._masks_out(M, na, T)
         self.cumulative_timesteps += N_
         experience = (flat[:N_], acts.view(N_, -1), logp.view(N_), up(rews), nxt_flat, up(dones), up(trunc))
+        return experience, metrics, N_, time.perf_counter() - t1
+
+    # ------------------------------------------------------------------------------------------ device-resident environment
+    def _init_device_env(self, first):
+        """init_processes for an environment whose reset() answered a GPU tensor.  The reset observations enter the statistics
+        through device_stats.increment (one wait, at start-up) and are acted on RAW, as in the host forms."""
+        from ..util import device_stats
+        obs = first.detach()
+        if obs.dim() != 2:
+            raise ValueError(f"a device-resident vector environment's reset() returns [n_agents, d], got {tuple(obs.shape)}")
+        obs = obs.to(torch.float32).contiguous().clone()   # (the environment may reuse its tensor at its first step)
+        self.n_agents, d = obs.shape
+        self.obs_stats = None
+        if self.standardize_obs:
+            self.obs_stats = WelfordRunningStat(shape=d)
+            device_stats.increment(self.obs_stats, obs)
+        self._initial_obs = obs
+        self._initial_mask_pending = hasattr(self.env, "action_masks")
+        n_acts, code = describe_action_space(self.env.action_space)
+        return int(np.prod(self.env.observation_space.shape)), int(n_acts), int(code)
+
+    def _env_mask_device(self, dev):
+        """action_masks() of a device environment -> packed device words (Layout.pack's device branch: nothing is read back, a row
+        without a valid action counts as all-valid); None without the method."""
+        fn = getattr(self.env, "action_masks", None)
+        if fn is None:
+            return None
+        lay = AM.Layout.of(self.policy)
+        m = fn()
+        if not (isinstance(m, torch.Tensor) and m.is_cuda):
+            raise ValueError("a device-resident vector environment's action_masks() returns a device tensor [n_agents, width]")
+        if m.dim() == 1:
+            m = m.view(1, -1)
+        if m.dim() != 2 or m.shape[1] != lay.width:
+            raise ValueError(f"the environment's action_masks() has shape {tuple(m.shape)}: its width must be {lay.width}, the policy's "
+                             + ("logit count sum(bins) (one entry per bin of every component)" if lay.heads is not None else "action count"))
+        return lay.pack(m, dev)
+
+    def _book_in(self, dev):
+        """Collect start: the host's average and statistics (the host objects own them: checkpoints, Learner.load) go to the device
+        through a page-locked buffer, without a wait; the standardisation vectors of the statistics as they stand are computed
+        into the pair that the pending observations do not read.  -> the book."""
+        from ..engine import ptr, stream_ptr
+        from .. import _native as N
+        if self._book is None or self._book.device != dev:
+            self._book = _DeviceBook(dev, self.n_agents)
+        b, st = self._book, self.obs_stats if self.standardize_obs else None
+        d = 0 if st is None else int(np.prod(np.shape(st.running_mean)))
+        f64 = st is not None and np.asarray(st.running_mean).dtype == np.float64
+        b.layout(d, f64)
+        host = b.pin.numpy()
+        host[:8].view(np.float64)[0] = 0.0 if self.average_reward is None else float(self.average_reward)
+        host[8:24].view(np.int64)[:] = (0 if self.average_reward is None else 1, 0)
+        if st is not None:
+            dt, es = (np.float64, 8) if f64 else (np.float32, 4)
+            host[24:24 + d * es].view(dt)[:] = np.asarray(st.running_mean, dt).reshape(-1)
+            host[24 + d * es:].view(dt)[:] = np.asarray(st.running_variance, dt).reshape(-1)
+        b.blob.copy_(b.pin, non_blocking=True)
+        if st is not None:
+            pending = self._pending_obs[1] if self._pending_obs is not None else None
+            b.cur = 1 if pending is not None and pending[0] is b.vec[0][0] else 0
+            N.check(N.lib().rlppo_obs_scalars(stream_ptr(), ptr(b.mean), ptr(b.m2), int(f64), int(st.count), d,
+                                              int(bool(self.per_feature_obs_standardization)), ptr(b.vec[b.cur][0]), ptr(b.vec[b.cur][1])))
+        return b
+
+    def _book_out(self, b):
+        """Collect end: ONE device-to-host copy brings back the statistics, the average and the ended-episode count."""
+        host = b.blob.cpu().numpy()
+        st_words = host[8:24].view(np.int64)
+        self.average_reward = float(host[:8].view(np.float64)[0]) if st_words[0] else None
+        self.episodes_ended += int(st_words[1])
+        if self.standardize_obs:
+            st, (dt, es) = self.obs_stats, ((np.float64, 8) if b.f64 else (np.float32, 4))
+            shape, keep = np.shape(st.running_mean), np.asarray(st.running_mean).dtype
+            st.running_mean = host[24:24 + b.d * es].view(dt).reshape(shape).astype(keep, copy=True)
+            st.running_variance = host[24 + b.d * es:].view(dt).reshape(shape).astype(keep, copy=True)
+
+    def _collect_device(self, n):
+        """The collect of a DEVICE-RESIDENT environment (reset() / step() answer GPU tensors on torch's current stream): the numbers of
+        _collect_fused / _collect_chain, bit for bit, with nothing between two steps on the host -- per step the policy's launch (the
+        one-launch step with device standardisation vectors; other heads: stage_obs + act_padded), a copy of the action row for the
+        environment, the environment's own work and ONE rlppo_rollout_record (rewards / flags into the time-major planes, episode
+        sums and the 0.9 / 0.1 average in agent order); on the steps where the statistics move, rlppo_welford_increment on the
+        device state and rlppo_obs_scalars.  The host enqueues and never waits; it reads back once, at the end (_book_out)."""
+        from ..engine import _resolve_device, ptr, stream_ptr
+        from .. import _native as N
+        t1 = time.perf_counter()
+        arena = self.policy.arena
+        dev, ld, na = _resolve_device(arena.device), arena.ld_in, self.n_agents
+        check_same_device(self._env_device, dev)
+        L = N.lib()
+        fused = bool(getattr(self.policy, "fused_step", False))
+        T = max(1, -(-int(n) // na))
+        N_ = na * T
+        S = torch.empty((T + 1, na, ld), dtype=torch.float32, device=dev)     # time-major, as in _collect_fused
+        logp_tm = torch.empty((T, na), dtype=torch.float32, device=dev)
+        acts_tm = torch.empty((T, na, 1), dtype=torch.float32, device=dev) if fused else None
+        rdt = torch.empty((3, T, na), dtype=torch.float32, device=dev)
+        metrics = []
+        b = self._book_in(dev)
+        if self._pending_obs is None:   # first collect: the reset observations are acted on RAW
+            self._pending_obs = (self._initial_obs, None)
+        obs_dev, scalars = self._pending_obs
+        if not fused:
+            arena.stage_obs(obs_dev, scalars, out=S[0])
+        if self._initial_mask_pending:
+            self._initial_mask_pending = False
+            self._pending_mask = self._env_mask_device(dev)
+        mask, M = self._pending_mask, None
+        width = None if mask is None else AM.Layout.of(self.policy).width
+        F = P = None   # bootstrap_truncated: staged final observations [T, na, ld] and the patch plane [T, na], allocated on first use
+        for t in range(T):
+            am = None
+            if mask is not None:
+                if M is None:
+                    M = torch.empty((T, na, mask.shape[1]), dtype=torch.int32, device=dev)
+                M[t].copy_(mask)
+                am = AM.Packed(M[t], width)
+            if fused:
+                self.policy.step(obs_dev, standardize=scalars, rows_out=S[t], actions_f32=acts_tm[t].view(na), logp_out=logp_tm[t],
+                                 to_host=False, action_mask=am)
+                a_env = acts_tm[t].clone()
+            else:
+                a_dev, lp_dev = self.policy.act_padded(S[t], action_mask=am)
+                a_dev = a_dev.view(na, -1)
+                if acts_tm is None:
+                    acts_tm = torch.empty((T, na, a_dev.shape[1]), dtype=torch.float32, device=dev)
+                acts_tm[t].copy_(a_dev)
+                logp_tm[t].copy_(lp_dev)
+                a_env = a_dev.to(torch.float32)   # (act_padded's own output or a conversion of it: never the storage)
+            step = self.env.step(a_env)
+            if len(step) == 4:
+                obs, r, d, info = step
+                tr = None
+            else:
+                obs, r, d, tr, info = step
+            if not (isinstance(obs, torch.Tensor) and obs.is_cuda):
+                raise ValueError("a device-resident vector environment answers device tensors: step() returned observations as "
+                                 f"{type(obs).__name__}" + (f" on {obs.device}" if isinstance(obs, torch.Tensor) else ""))
+            check_same_device(obs.device, dev)
+            obs_dev = obs.detach().to(torch.float32).reshape(na, -1).contiguous()
+            if mask is not None:
+                mask = self._env_mask_device(dev)   # describes `obs`, the observation of step t + 1
+            if self.collect_metrics_fn is not None:
+                metrics.append(self.collect_metrics_fn(info["state"]))
+            scalars = b.vec[b.cur] if self.standardize_obs else None   # the pair BEFORE this step's increment
+            patch_t = None
+            if self.bootstrap_truncated:
+                if isinstance(info, dict) and "final_observation" in info:
+                    if F is None:
+                        F = torch.empty((T, na, ld), dtype=torch.float32, device=dev)
+                        P = torch.zeros((T, na), dtype=torch.float32, device=dev)
+                    arena.stage_obs(info["final_observation"].reshape(na, -1), scalars, out=F[t])
+                    patch_t = P[t]
+                elif not self._warned_no_final_obs:   # (decided by the key alone: nothing on the device is read)
+                    self._warned_no_final_obs = True
+                    warnings.warn("gae_bootstrap_truncated: the environment's info has no 'final_observation': environment-side "
+                                  "truncations bootstrap from the post-reset observation (the truncation at the end of every collect "
+                                  "is not affected)", RuntimeWarning, stacklevel=3)
+            if self.standardize_obs:   # the host forms' cadence; the sample count is the host's
+                if self.steps_since_obs_stats_update > self.steps_per_obs_stats_increment:
+                    st = self.obs_stats
+                    N.check(L.rlppo_welford_increment(stream_ptr(), ptr(obs_dev), obs_dev.stride(0), na, b.d, ptr(b.mean), ptr(b.m2),
+                                                      int(st.count), int(b.f64)))
+                    st.count += na
+                    b.cur = 1 - b.cur
+                    N.check(L.rlppo_obs_scalars(stream_ptr(), ptr(b.mean), ptr(b.m2), int(b.f64), int(st.count), b.d,
+                                                int(bool(self.per_feature_obs_standardization)), ptr(b.vec[b.cur][0]), ptr(b.vec[b.cur][1])))
+                    self.steps_since_obs_stats_update = 0
+                else:
+                    self.steps_since_obs_stats_update += 1
+            r, r_dt = _dt_code(r, "rewards", dev, na)
+            if r_dt == 2:
+                r, r_dt = r.to(torch.float32), 0
+            d, d_dt = _dt_code(d, "dones", dev, na)
+            tr, tr_dt = (None, 0) if tr is None else _dt_code(tr, "truncated", dev, na)
+            N.check(L.rlppo_rollout_record(stream_ptr(), ptr(r), r_dt, ptr(d), d_dt, ptr(tr), tr_dt, na, t, T, ptr(rdt), ptr(b.ep_sums),
+                                           ptr(b.state), ptr(patch_t)))
+            if not fused or t == T - 1:
+                arena.stage_obs(obs_dev, scalars, out=S[t + 1])   # the rows the agents act on next
+        self._pending_obs = (obs_dev, scalars)
+        self._pending_mask = mask
+        self._masks_out(M, na, T)
+        if getattr(self.policy, "noise_mode", None) == "host" and hasattr(self.policy, "prefetch_noise"):
+            self.policy.prefetch_noise(na, T)   # as _collect_fused: the next collect's draws, produced while the update runs
+        k = acts_tm.shape[2]
+        flat = torch.empty((N_ + 1, ld), dtype=torch.float32, device=dev)
+        nxt_flat = torch.empty((N_, ld), dtype=torch.float32, device=dev)
+        actions = torch.empty((N_, k), dtype=torch.float32, device=dev)
+        small = torch.empty((4, N_), dtype=torch.float32, device=dev)   # log_probs, rewards, dones, truncated
+        N.check(L.rlppo_rollout_to_trajectory_major(stream_ptr(), ptr(S), ptr(acts_tm), ptr(logp_tm), ptr(rdt), na, T, ld, k, ptr(P), ptr(F),
+                                                    ptr(flat), ptr(nxt_flat), ptr(actions), ptr(small[0]), ptr(small[1]), ptr(small[2]),
+                                                    ptr(small[3])))
+        if self.bootstrap_truncated:   # the host does not know which steps are truncated: all N next-state rows, the scan selects
+            self.bootstrap_dense, self.bootstrap_steps, self.bootstrap_index, self.bootstrap_rows = True, None, None, nxt_flat
+        self.value_input_rows = flat
+        self._next_rows = S[T]
+        self.cumulative_timesteps += N_
+        self.last_enqueue_seconds = time.perf_counter() - t1   # host time of the whole collect before its one wait
+        self._book_out(b)
+        experience = (flat[:N_], actions, small[0], small[1], nxt_flat, small[2], small[3])
         return experience, metrics, N_, time.perf_counter() - t1
 
     def _first_mask(self):

@@ -1664,6 +1664,40 @@ int rlppo_welford_merge(void *stream, int32_t d, void *mean, void *m2, int64_t c
     return launch_welford_merge((hipStream_t)stream, d, mean, m2, (long long)count, other_mean, other_m2, (long long)other_count,
                                 state_is_f64 != 0);
 }
+// the device-resident vector environment's bookkeeping (csrc/rollout.hip): launches only
+static bool dt_ok(int32_t dt) { return dt == RLPPO_DT_F32 || dt == RLPPO_DT_F64 || dt == RLPPO_DT_U8; }
+int rlppo_rollout_record(void *stream, const void *rewards, int32_t rewards_dt, const void *dones, int32_t dones_dt, const void *truncated,
+                         int32_t truncated_dt, int64_t n_agents, int64_t t, int64_t T, float *rdt, double *ep_sums, void *state,
+                         float *patch) {
+    RLPPO_CHECK_ARG(rewards && dones && rdt && ep_sums && state, "rollout_record: null pointer (rewards / dones / rdt / ep_sums / state)");
+    RLPPO_CHECK_ARG(n_agents > 0 && T > 0 && t >= 0 && t < T, "rollout_record: n_agents=%ld, step %ld of %ld", (long)n_agents, (long)t, (long)T);
+    RLPPO_CHECK_ARG(dt_ok(rewards_dt) && rewards_dt != RLPPO_DT_U8 && dt_ok(dones_dt) && (!truncated || dt_ok(truncated_dt)),
+                    "rollout_record: dtype codes %d / %d / %d (rewards float32 or float64; flags float32, float64 or one byte)", rewards_dt,
+                    dones_dt, truncated_dt);
+    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(state) & 7) == 0 && (reinterpret_cast<uintptr_t>(ep_sums) & 7) == 0,
+                    "rollout_record: state and ep_sums must be 8-byte aligned");
+    return launch_rollout_record((hipStream_t)stream, rewards, rewards_dt, dones, dones_dt, truncated, truncated_dt, n_agents, t, T, rdt, ep_sums,
+                                 state, patch);
+}
+int rlppo_obs_scalars(void *stream, const void *mean, const void *m2, int32_t state_is_f64, int64_t count, int32_t d, int32_t per_feature,
+                      float *mean_v, float *std_v) {
+    RLPPO_CHECK_ARG(mean && m2 && mean_v && std_v && d > 0 && count >= 0, "obs_scalars: bad argument");
+    return launch_obs_scalars((hipStream_t)stream, mean, m2, state_is_f64 != 0, (long long)count, d, per_feature != 0, mean_v, std_v);
+}
+int rlppo_rollout_to_trajectory_major(void *stream, const float *S, const float *acts, const float *logp, const float *rdt, int64_t n_agents,
+                                      int64_t T, int32_t ld, int32_t k, const float *patch, const float *final_rows, float *flat, float *nxt,
+                                      float *actions, float *log_probs, float *rewards, float *dones, float *truncated) {
+    RLPPO_CHECK_ARG(S && acts && logp && rdt && flat && nxt && actions && log_probs && rewards && dones && truncated,
+                    "rollout_to_trajectory_major: null pointer");
+    RLPPO_CHECK_ARG(n_agents > 0 && T > 0 && ld > 0 && ld % 4 == 0 && k > 0, "rollout_to_trajectory_major: n_agents=%ld T=%ld ld=%d k=%d",
+                    (long)n_agents, (long)T, ld, k);
+    RLPPO_CHECK_ARG((patch == nullptr) == (final_rows == nullptr), "rollout_to_trajectory_major: patch and final_rows come together");
+    RLPPO_CHECK_ARG(((reinterpret_cast<uintptr_t>(S) | reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(nxt) |
+                      reinterpret_cast<uintptr_t>(final_rows)) & 15) == 0, "rollout_to_trajectory_major: rows must be 16-byte aligned");
+    RLPPO_CHECK_ARG((T + 1) * n_agents * (int64_t)(ld / 4) < (int64_t)256 * 0x7fffffff, "rollout_to_trajectory_major: too many rows for one launch");
+    return launch_to_trajectory_major((hipStream_t)stream, S, acts, logp, rdt, n_agents, T, ld, k, patch, final_rows, flat, nxt, actions, log_probs,
+                                      rewards, dones, truncated);
+}
 // [diag] the diagonal-Gaussian head's loss launch and the finish of its log_std reduction on their own (tools/diag_gaussian_cost.py)
 int rlppo_dbg_diag_loss(void *stream, float *y, int64_t ld, int32_t k, const float *actions, const float *old_logp, const float *advantages,
                         int64_t mb, float clip_range, float ent_coef, float mb_ratio, const float *log_std, float *log_std_grad, void *scratch,
@@ -1792,6 +1826,7 @@ int64_t rlppo_dbg_counter(int32_t key) {
         case 4: return g_cnt_gather_fused_pass;
         case 5: return g_cnt_group_dw;
         case 6: return g_cnt_md_nvec;
+        case 7: return rollout_record_count();
         default: return -1;
     }
 }

@@ -346,5 +346,14 @@ int launch_learn_report(hipStream_t st, const rlppo_report_args &r);  // [r6] th
 int launch_signal_words(hipStream_t st, unsigned *words, int count, unsigned value);  // words[0..count) <- value, released at system scope
 int launch_pad_rows(hipStream_t, const void *, int, int64_t, int64_t, int64_t, float *, int64_t, int, float, float);
 int launch_pad_rows_vec(hipStream_t, const void *, int, int64_t, int64_t, int64_t, float *, int64_t, const float *, const float *);
+// rollout.hip: the device-resident vector environment's bookkeeping (rlppo_rollout_record / rlppo_obs_scalars / rlppo_rollout_to_trajectory_major)
+int launch_rollout_record(hipStream_t st, const void *rewards, int r_dt, const void *dones, int d_dt, const void *truncated, int t_dt,
+                          int64_t n, int64_t t, int64_t T, float *rdt, double *ep_sums, void *state, float *patch);
+long long rollout_record_count();   // rlppo_dbg_counter(7)
+int launch_obs_scalars(hipStream_t st, const void *mean, const void *m2, int state_f64, long long count, int d, int per_feature,
+                       float *mean_v, float *std_v);
+int launch_to_trajectory_major(hipStream_t st, const float *S, const float *acts, const float *logp, const float *rdt, int64_t n, int64_t T,
+                               int ld, int k, const float *patch, const float *final_rows, float *flat, float *nxt, float *actions,
+                               float *log_probs, float *rewards, float *dones, float *truncated);
 
 }  // namespace rlppo

@@ -288,18 +288,24 @@ class Learner(object):
 
         gae_bootstrap_truncated: the m steps that are truncated and not done (known from the HOST copies of the flags: no
         read-back) get V of their own next state -- process mode: m more rows in the one value pass; vector mode: a value pass
-        on the manager's m next-state rows -- scattered into a length-N device buffer for the bootstrap form of the scan."""
+        on the manager's m next-state rows -- scattered into a length-N device buffer for the bootstrap form of the scan.  A
+        device-resident vector environment (the manager's bootstrap_dense): the flags exist on the device only, so one value pass over
+        all N next-state rows gives the dense boot_values as they are."""
         states, actions, log_probs, rewards, next_states, dones, truncated = experience
         value_net = self.ppo_learner.value_net
         n = states.shape[0]
         on_device = isinstance(states, torch.Tensor) and states.is_cuda   # VectorAgentManager: rollout already in HBM
-        boot_values = boot_idx = None
+        boot_values = boot_idx = dense_boot = None
         if on_device:
             rows = self.agent.value_input_rows               # [N+1, ld]: states ++ the last next_state, padded
             assert rows.shape[0] == n + 1 and rows.data_ptr() == states.data_ptr()
             d_logical = int(self.ppo_learner.policy.arena.d_in)
             val_preds = value_net.forward_padded(rows).contiguous()
-            if self.gae_bootstrap_truncated and self.agent.bootstrap_steps.size:
+            if self.gae_bootstrap_truncated and getattr(self.agent, "bootstrap_dense", False):
+                # a device-resident environment: which steps are truncated is known on the device only -- one value pass over ALL N
+                # next-state rows; the scan selects by the flags and never uses the other entries (include/rlppo.h, rlppo_gae_boot)
+                dense_boot = value_net.forward_padded(self.agent.bootstrap_rows).contiguous()
+            elif self.gae_bootstrap_truncated and self.agent.bootstrap_steps.size:
                 boot_idx = self.agent.bootstrap_index        # None: exactly the last step of every agent (the flush)
                 boot_values = value_net.forward_padded(self.agent.bootstrap_rows)
         else:
@@ -327,6 +333,8 @@ class Learner(object):
             else:
                 boot[boot_idx] = boot_values
             boot_values = boot
+        elif dense_boot is not None:
+            boot_values = dense_boot
         up = lambda x: x.to(dev, torch.float32) if isinstance(x, torch.Tensor) else \
             torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32))).to(dev)
         rews_d, dones_d, trunc_d = up(rewards), up(dones), up(truncated)

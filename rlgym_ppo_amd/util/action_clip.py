@@ -7,6 +7,7 @@ path) as long as the wrapped factory does."""
 import math
 
 import numpy as np
+import torch
 
 
 def check_clip(clip):
@@ -29,6 +30,8 @@ class ActionClipEnv:
         self._env, self._lo, self._hi = env, np.float32(lo), np.float32(hi)
 
     def step(self, actions):
+        if isinstance(actions, torch.Tensor):   # a device-resident vector environment: out of place, dtype and device kept
+            return self._env.step(torch.clamp(actions, float(self._lo), float(self._hi)))
         return self._env.step(np.clip(np.asarray(actions, dtype=np.float32), self._lo, self._hi))
 
     def __getattr__(self, name):   # (only reached for what the wrapper does not define itself)
