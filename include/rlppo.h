@@ -201,7 +201,22 @@ typedef struct rlppo_act_opts {
      * -- whose mask words may be stale -- store nothing. */
     const uint32_t *action_mask;
     int32_t mask_words;
+    /* [act] the activation of every hidden layer: RLPPO_ACT_RELU (0: today's call, launch for launch), RLPPO_ACT_TANH, RLPPO_ACT_ELU
+     * (alpha = 1).  The member occupies what were the struct's 4 bytes of tail padding (size and every other offset unchanged: ABI 8
+     * stays), so a zeroed struct and a NULL pointer are the ReLU call.  Every rollout entry point honours it through its layer
+     * chain; with tanh / ELU rlppo_discrete_act / _step skip the one-launch kernel (rlppo_discrete_step_one_launch answers 0, so
+     * noise_ctl is refused), and the bf16 inference precision is RLPPO_ERR_ARG (its kernels are ReLU only).  Any other value:
+     * RLPPO_ERR_ARG before the first HIP call. */
+    int32_t hidden_act;
 } rlppo_act_opts;
+#define RLPPO_ACT_RELU 0
+#define RLPPO_ACT_TANH 1
+#define RLPPO_ACT_ELU 2
+#ifdef __cplusplus
+static_assert(sizeof(rlppo_act_opts) == 40 && offsetof(rlppo_act_opts, hidden_act) == 36, "rlppo_act_opts: hidden_act lives in the former tail padding");
+#else
+_Static_assert(sizeof(rlppo_act_opts) == 40 && offsetof(rlppo_act_opts, hidden_act) == 36, "rlppo_act_opts: hidden_act lives in the former tail padding");
+#endif
 int64_t rlppo_act_done_words(int64_t n);
 /* HOST: spins until words[0..count) all hold `value` (acquire loads) or timeout_us has passed; 0 = all there, 1 = timed out,
  * 2 = a word holds value | 0x80000000 (the kernel gave up: noise_ctl above). */
@@ -475,6 +490,26 @@ int rlppo_ppo_minibatch_nvec(void *stream, const rlppo_minibatch_args *args, con
 size_t rlppo_diag_scratch_bytes(int64_t mb, int32_t k);
 int rlppo_ppo_minibatch_diag(void *stream, const rlppo_minibatch_args *args, const float *log_std, float *log_std_grad, void *scratch,
                              size_t scratch_bytes);
+
+/* [act] The same pass for every head, with the hidden activation of each network (an added entry point: rlppo_minibatch_args and the
+ * ABI version stay as they are).  ext == NULL or all-zero is exactly rlppo_ppo_minibatch.  md_nvec / md_heads: as
+ * rlppo_ppo_minibatch_nvec's; log_std / log_std_grad / scratch / scratch_bytes: as rlppo_ppo_minibatch_diag's (any of them set = that
+ * entry point's checks).  pol_hidden_act / val_hidden_act: RLPPO_ACT_* of every hidden layer of the policy / the critic.  When either
+ * is tanh or ELU the pass takes the PLAIN form -- one launch chain per network on rows gathered into the workspace, dX multiplied by
+ * f'(h) of the SAVED OUTPUT h (tanh: 1 - h^2; ELU: h > 0 ? 1 : h + 1 -- no pre-activation is stored) -- without ReLU bitmasks, paired
+ * launches, the folded value head or the gather-fused first layer; the grouped weight-gradient launch is used as it is.  The
+ * workspace is rlppo_minibatch_workspace_bytes_for, unchanged.  tanh / ELU with update precision bf16 or x3 is RLPPO_ERR_ARG (those
+ * kernels carry the ReLU bitmask by construction), as is any other activation code; every check comes before the first HIP call. */
+typedef struct rlppo_minibatch_ext {
+    int32_t pol_hidden_act, val_hidden_act;
+    const int32_t *md_nvec;
+    int32_t md_heads;
+    const float *log_std;
+    float *log_std_grad;
+    void *scratch;
+    size_t scratch_bytes;
+} rlppo_minibatch_ext;
+int rlppo_ppo_minibatch_ex(void *stream, const rlppo_minibatch_args *args, const rlppo_minibatch_ext *ext);
 
 /* Orders `stream` after every minibatch enqueued through non-zero slots since the last join (call it before the
  * gradient all-reduce / rlppo_clip_adam).  Independent minibatches of one batch only meet in the gradient arena
@@ -875,6 +910,8 @@ int rlppo_dbg_gemm_nt_x3(void *stream, const float *A, int64_t lda, const void *
 /* A/B switches for measurements and tests (also RLPPO_TUNE="key=value,..." in the Python host).  Defaults in brackets.
  *   1 GAE algorithm [1 single-pass look-back | 0 two launches]
  *   4 policy / critic chains of rlppo_ppo_minibatch on two streams [1]
+ *  19 [act] fp32 update passes [1 = the ReLU bitmask forms where they apply (default) | 0 = every pass takes the plain form of a
+ *     tanh / ELU pass: two chains on gathered rows, dX by the saved activation (measurements: what the form costs a ReLU pass)]
  *  21 GAE look-back spin limit [-1 = default 2^20 | 0 = every wait times out at once (tests)]
  *  22 GAE grid [0 = at most the resident capacity, workgroups loop over chunks beyond it | 1 = one workgroup per chunk always]
  *  23 bf16 update precision, form of the hidden-layer forward / dX / dW products [2 = 256 x 256 tiles walked by persistent workgroups
@@ -918,7 +955,9 @@ int64_t rlppo_dbg_counter(int32_t key);
  * the general kernel, not a launcher call. */
 int rlppo_dbg_count(int32_t key, int64_t delta);
 /* Single-kernel entry points used by tests/ and bench.py to check / time each GEMM flavour in isolation.
- * epilogue: 0 bias, 1 bias+relu, 2 bias+tanh, 3 relu-mask (mask_src > 0).  Shapes as in csrc/gemm.hip. */
+ * epilogue: 0 bias, 1 bias+relu, 2 bias+tanh, 3 relu-mask (mask_src > 0).  Shapes as in csrc/gemm.hip.
+ * [act] 4 bias+ELU (alpha = 1: x > 0 ? x : expm1(x)); the dX epilogues of a tanh / ELU hidden layer, which read the saved activation
+ * h from mask_src exactly as epilogue 3 does: 5 times tanh' (C = (A.B^T) (1 - h^2)), 6 times ELU' (C = (A.B^T) (h > 0 ? 1 : h + 1)). */
 int rlppo_dbg_gemm_nt(void *stream, const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias,
                       const float *mask_src, int64_t ld_mask, float *C, int64_t ldc, int64_t M, int32_t N, int32_t K,
                       int32_t epilogue);

@@ -29,6 +29,8 @@ HEAD_DISCRETE, HEAD_MULTIDISCRETE, HEAD_GAUSSIAN = 0, 1, 2
 HEAD_DIAG_GAUSSIAN = 3  # RLPPO_HEAD_DIAG_GAUSSIAN: learnable state-independent log_std, unbounded mean (include/rlppo.h, "[diag]")
 DIAG_MAX_K = 256  # RLPPO_DIAG_MAX_K
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16, PRECISION_X3 = 0, 1, 2, 3  # rlppo_minibatch_args.precision (1 + mode)
+ACT_RELU, ACT_TANH, ACT_ELU = 0, 1, 2  # RLPPO_ACT_*: rlppo_act_opts.hidden_act, rlppo_minibatch_ext.{pol,val}_hidden_act
+HIDDEN_ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "elu": ACT_ELU}
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -46,10 +48,36 @@ class OptNet(ctypes.Structure):
     ]
 
 
+class _TailInt32:
+    """An int32 member that lives in the tail padding of a ctypes.Structure (offset / size like a ctypes field descriptor)."""
+
+    def __init__(self, offset):
+        self.offset, self.size = offset, 4
+
+    def __get__(self, obj, owner=None):
+        return self if obj is None else c_int32.from_address(ctypes.addressof(obj) + self.offset).value
+
+    def __set__(self, obj, value):
+        c_int32.from_address(ctypes.addressof(obj) + self.offset).value = int(value)
+
+
 class ActOpts(ctypes.Structure):
     """struct rlppo_act_opts (include/rlppo.h)."""
     _fields_ = [("precision", c_int32), ("done_value", c_uint32), ("done_words", c_void_p), ("noise_ctl", c_void_p),
                 ("action_mask", c_void_p), ("mask_words", c_int32)]
+    # [act] rlppo_act_opts.hidden_act: the int32 in what were the struct's 4 bytes of tail padding.  _fields_ stays the list it was
+    # (its tail is pinned: the mask fields close it), so the member is a descriptor over those bytes; a fresh ActOpts is zero-filled,
+    # i.e. ReLU
+    hidden_act = _TailInt32(36)
+
+
+assert ActOpts.mask_words.offset + 4 == ActOpts.hidden_act.offset and ActOpts.hidden_act.offset + 4 == ctypes.sizeof(ActOpts)
+
+
+class MinibatchExt(ctypes.Structure):
+    """struct rlppo_minibatch_ext (include/rlppo.h, "[act]")."""
+    _fields_ = [("pol_hidden_act", c_int32), ("val_hidden_act", c_int32), ("md_nvec", POINTER(c_int32)), ("md_heads", c_int32),
+                ("log_std", c_void_p), ("log_std_grad", c_void_p), ("scratch", c_void_p), ("scratch_bytes", c_size_t)]
 
 
 class ReportArgs(ctypes.Structure):
@@ -160,6 +188,7 @@ SIGNATURES = {
     "rlppo_ppo_minibatch_nvec": (c_int32, [c_void_p, POINTER(MinibatchArgs), _P32, c_int32]),
     "rlppo_diag_scratch_bytes": (c_size_t, [c_int64, c_int32]),
     "rlppo_ppo_minibatch_diag": (c_int32, [c_void_p, POINTER(MinibatchArgs), c_void_p, c_void_p, c_void_p, c_size_t]),
+    "rlppo_ppo_minibatch_ex": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt)]),
     "rlppo_ppo_join": (c_int32, [c_void_p]),
     "rlppo_kl_slots_doubles": (c_int64, [c_int64]),
     "rlppo_adv_stats": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),

@@ -111,9 +111,16 @@ struct RowSource {
 // Training only: bits[l] (may be null) receives the ReLU bitmask of hidden layer l and have_bits[l] says whether it was
 // written (csrc/gemm.hip, launch_gemm_nt_bits); backward() then masks dX with it instead of re-reading acts[l].
 // in.rowtab != nullptr: the first layer fetches its rows through the table (nt_gather_ok must hold for it).
+// [act] hidden_act (HiddenAct): the activation of every hidden layer.  tanh / ELU have the plain form only -- the callers give them no
+// bitmasks, no folded head, no row table, no bf16 operands and no split planes (all of those carry ReLU by construction).
 static int forward(hipStream_t st, const NetLayout &net, const float *packed, const RowSource &in, int64_t n, int out_tanh,
                    float *const *acts, int bf16_operands = 0, unsigned long long *const *bits = nullptr, bool *have_bits = nullptr,
-                   bool *head_folded = nullptr, const unsigned short *x3 = nullptr, bool head_prezeroed = false) {
+                   bool *head_folded = nullptr, const unsigned short *x3 = nullptr, bool head_prezeroed = false,
+                   int hidden_act = ACT_RELU) {
+    if (hidden_act != ACT_RELU && (bf16_operands || bits || head_folded || x3 || in.rowtab)) {
+        set_error("forward: hidden activation %s runs the plain fp32 layer chain only", hidden_act_name(hidden_act));
+        return RLPPO_ERR_ARG;
+    }
     X3Layout xl;
     if (x3) x3_layout(net, &xl);
     if (have_bits)
@@ -130,7 +137,7 @@ static int forward(hipStream_t st, const NetLayout &net, const float *packed, co
     for (int l = 0; l < net.n_layers; ++l) {
         const LayerLayout &L = net.L[l];
         const bool last = l == net.n_layers - 1;
-        const int epi = last ? (out_tanh ? EPI_BIAS_TANH : EPI_BIAS) : EPI_BIAS_RELU;
+        const int epi = last ? (out_tanh ? EPI_BIAS_TANH : EPI_BIAS) : hidden_act_fwd_epi(hidden_act);
         int rc;
         if (last && head_folded && *head_folded) break;
         if (last && !out_tanh && gemv_head_ok(L.out, L.pin))  // one-output head: matrix-vector kernel (gemv.hip)
@@ -249,7 +256,7 @@ static size_t forward_ws_floats(const NetLayout &net, int64_t n) { return (size_
 // runs the net with ping-pong buffers from the workspace and returns the pointer/ld of the last layer's output
 static int forward_pingpong(hipStream_t st, const NetLayout &net, const float *packed, const float *obs, int64_t ld_obs,
                             int64_t n, int out_tanh, void *ws, size_t ws_bytes, float *final_out, const float **out,
-                            int64_t *ld_out, int bf16_operands) {
+                            int64_t *ld_out, int bf16_operands, int hidden_act) {
     if (ws_bytes < forward_ws_floats(net, n) * sizeof(float)) {
         set_error("forward: workspace %zu < %zu bytes", ws_bytes, forward_ws_floats(net, n) * sizeof(float));
         return RLPPO_ERR_WORKSPACE;
@@ -261,7 +268,8 @@ static int forward_pingpong(hipStream_t st, const NetLayout &net, const float *p
     float *acts[RLPPO_MAX_LAYERS];
     for (int l = 0; l < net.n_layers; ++l) acts[l] = (l & 1) ? b1 : b0;
     if (final_out) acts[net.n_layers - 1] = final_out;
-    int rc = forward(st, net, packed, RowSource{obs, ld_obs}, n, out_tanh, acts, bf16_operands);  // inference only
+    int rc = forward(st, net, packed, RowSource{obs, ld_obs}, n, out_tanh, acts, bf16_operands, nullptr, nullptr, nullptr, nullptr, false,
+                     hidden_act);  // inference only
     if (rc) return rc;
     *out = acts[net.n_layers - 1];
     *ld_out = net.L[net.n_layers - 1].pout;
@@ -289,6 +297,7 @@ struct ActCtx {
     unsigned *noise_ctl = nullptr;
     const unsigned *mask = nullptr;  // [ABI 8] rlppo_act_opts.action_mask / mask_words
     int mask_words = 0;
+    int hidden_act = ACT_RELU;       // [act] rlppo_act_opts.hidden_act
 };
 // late_noise: the entry point can take its noise while it runs (rlppo_act_opts.noise_ctl; rlppo_discrete_step alone)
 // mask_for: nullptr = the entry point samples the discrete head and takes an action mask; else the name of what it runs instead
@@ -298,6 +307,11 @@ static int act_ctx(const rlppo_act_opts *o, ActCtx *c, bool late_noise = false, 
     RLPPO_CHECK_ARG(o->precision == RLPPO_PRECISION_DEFAULT || o->precision == RLPPO_PRECISION_FP32 || o->precision == RLPPO_PRECISION_BF16,
                     "act options: inference precision %d (0 = process default, 1 = fp32, 2 = bf16 operands)", o->precision);
     if (o->precision != RLPPO_PRECISION_DEFAULT) c->bf16 = o->precision == RLPPO_PRECISION_BF16;
+    RLPPO_CHECK_ARG(hidden_act_ok(o->hidden_act), "act options: hidden_act %d (0 = ReLU, 1 = tanh, 2 = ELU)", o->hidden_act);
+    c->hidden_act = o->hidden_act;
+    RLPPO_CHECK_ARG(!(c->bf16 && c->hidden_act != ACT_RELU),
+                    "act options: hidden activation %s with the bf16 inference precision: the bf16-operand kernels are ReLU only",
+                    hidden_act_name(c->hidden_act));
     c->done = o->done_words;
     c->done_value = o->done_value;
     c->noise_ctl = o->noise_ctl;
@@ -388,7 +402,7 @@ int rlppo_mlp_forward(void *stream, const int32_t *dims, int32_t n_layers, const
                     (long)ld_out, net.L[n_layers - 1].pout);
     const float *o;
     int64_t ldo;
-    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, out_tanh, workspace, ws_bytes, out, &o, &ldo, cx.bf16);
+    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, out_tanh, workspace, ws_bytes, out, &o, &ldo, cx.bf16, cx.hidden_act);
     return rc ? rc : act_done((hipStream_t)stream, cx, n);
 }
 
@@ -407,7 +421,7 @@ int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     if (rc) return rc;
     // [r3] one launch for the whole step when the network has the form fused_act.hip covers (fp32 inference precision); the
     // layer-by-layer chain below otherwise -- bit-identical results either way
-    if (g_fused_act && !cx.bf16 && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS && ld_obs >= net.L[0].pin && ld_obs % 4 == 0 &&
+    if (g_fused_act && !cx.bf16 && !cx.hidden_act && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS && ld_obs >= net.L[0].pin && ld_obs % 4 == 0 &&
         (reinterpret_cast<uintptr_t>(obs) & 15) == 0) {  // (the kernel stages the padded rows with 16-byte loads)
         FusedActIO io;
         io.rows = obs;
@@ -426,7 +440,7 @@ int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     ++g_cnt_act_chain;
     const float *o;
     int64_t ldo;
-    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
+    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16, cx.hidden_act);
     if (rc) return rc;
     rc = launch_discrete_sample_logits((hipStream_t)stream, o, ldo, n, dims[n_layers], noise_q, actions, logp, probs_out, cx.mask, cx.mask_words);
     return rc ? rc : act_done((hipStream_t)stream, cx, n);
@@ -470,7 +484,7 @@ int rlppo_discrete_step_one_launch(const int32_t *dims, int32_t n_layers, int64_
     if (make_layout(dims, n_layers, &net)) return -1;
     ActCtx cx;
     if (act_ctx(opts, &cx, true)) return -1;
-    return g_fused_act && !cx.bf16 && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
+    return g_fused_act && !cx.bf16 && !cx.hidden_act && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
 }
 
 int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const void *obs, int32_t obs_is_f64,
@@ -492,7 +506,7 @@ int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, con
     rc = act_mask_check(cx, dims[n_layers]);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (g_fused_act && !cx.bf16 && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
+    if (g_fused_act && !cx.bf16 && !cx.hidden_act && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
         FusedActIO io;
         io.raw = obs;
         io.raw_is_f64 = obs_is_f64;
@@ -537,7 +551,7 @@ int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, con
     if (rc) return rc;
     const float *o;
     int64_t ldo;
-    rc = forward_pingpong(st, net, packed, rows, ld_rows, n, 0, ws, ws_bytes, nullptr, &o, &ldo, cx.bf16);
+    rc = forward_pingpong(st, net, packed, rows, ld_rows, n, 0, ws, ws_bytes, nullptr, &o, &ldo, cx.bf16, cx.hidden_act);
     if (rc) return rc;
     rc = launch_discrete_sample_logits(st, o, ldo, n, dims[n_layers], noise_q, actions, logp, nullptr, cx.mask, cx.mask_words);
     if (rc == 0 && actions_f32) rc = launch_i64_to_f32(st, actions, actions_f32, n);
@@ -561,7 +575,7 @@ int rlppo_discrete_probs(void *stream, const int32_t *dims, int32_t n_layers, co
     if (rc) return rc;
     const float *o;
     int64_t ldo;
-    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
+    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16, cx.hidden_act);
     if (rc) return rc;
     rc = launch_discrete_probs((hipStream_t)stream, o, ldo, n, dims[n_layers], clamp_probs != 0, probs_out, ld_probs, flat_argmax, cx.mask,
                                cx.mask_words);
@@ -589,7 +603,7 @@ int rlppo_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     RLPPO_CHECK_ARG(dims[n_layers] % 2 == 0, "gaussian_act: output width %d must be 2k", dims[n_layers]);
     const float *o;
     int64_t ldo;
-    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 1, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
+    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 1, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16, cx.hidden_act);
     if (rc) return rc;
     // (the completion words ride in the sampling kernel: a block of it holds 256 whole rows)
     return launch_gaussian_sample((hipStream_t)stream, o, ldo, n, dims[n_layers] / 2, noise_eps, var_m, var_b, actions, logp, cx.done, cx.done_value);
@@ -612,7 +626,7 @@ int rlppo_diag_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers,
     RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_eps && log_std && actions && logp && workspace, "diag_gaussian_act: bad argument");
     const float *o;
     int64_t ldo;
-    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
+    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16, cx.hidden_act);
     if (rc) return rc;
     // (the completion words ride in the sampling kernel: a block of it holds 256 whole rows)
     return launch_diag_gaussian_sample((hipStream_t)stream, o, ldo, n, dims[n_layers], noise_eps, log_std, actions, logp, cx.done, cx.done_value);
@@ -632,7 +646,7 @@ int rlppo_multidiscrete_act(void *stream, const int32_t *dims, int32_t n_layers,
     RLPPO_CHECK_ARG(dims[n_layers] == 21, "multidiscrete_act: output width %d must be 21", dims[n_layers]);
     const float *o;
     int64_t ldo;
-    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
+    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16, cx.hidden_act);
     if (rc) return rc;
     return launch_multidiscrete_sample((hipStream_t)stream, o, ldo, n, noise_q, actions, logp, cx.done, cx.done_value);
 }
@@ -660,7 +674,7 @@ static int multidiscrete_act_nvec(void *stream, const int32_t *dims, int32_t n_l
     RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_q && actions && logp && workspace, "%s: bad argument", who);
     const float *o;
     int64_t ldo;
-    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16);
+    rc = forward_pingpong((hipStream_t)stream, net, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr, &o, &ldo, cx.bf16, cx.hidden_act);
     if (rc) return rc;
     ++g_cnt_md_nvec;
     return launch_multidiscrete_nvec_sample((hipStream_t)stream, o, ldo, n, noise_q, actions, logp, spec, cx.done, cx.done_value, mask, mask_words);
@@ -898,7 +912,7 @@ size_t rlppo_minibatch_workspace_bytes(const int32_t *pol_dims, int32_t pol_laye
 // dL/d(acts[l-1]) = dY of layer l-1 (one buffer per layer: the dW launches read them later)
 static int backward(hipStream_t st, const NetLayout &net, const float *packed, const RowSource &in, int64_t mb, float *const *acts,
                     float *const *dx, float *grad, float *tn_ws, unsigned long long *const *bits, const bool *have_bits,
-                    bool head_folded = false, const unsigned short *x3 = nullptr, DwList *defer = nullptr) {
+                    bool head_folded = false, const unsigned short *x3 = nullptr, DwList *defer = nullptr, int hidden_act = ACT_RELU) {
     const int last = net.n_layers - 1;
     int rc = 0;
     X3Layout xl;
@@ -921,10 +935,12 @@ static int backward(hipStream_t st, const NetLayout &net, const float *packed, c
         if (l == 0) break;
         // dX[mb][pin] = (dY[mb][pout] . W[pout][pin]) masked by relu'(acts[l-1]); B operand = W^T [pin][pout].  The mask is the
         // bitmask the forward left when there is one (no re-read of the activation), else the saved activation itself.
+        // [act] tanh / ELU: times f'(acts[l-1]), a function of the saved OUTPUT alone (1 - h^2; h > 0 ? 1 : h + 1) -- the same
+        // "by the saved activation" launches with the derivative epilogue; there are no bitmasks (have_bits is all false)
         rc = -1;
         if (gemv) {
             if (have_bits[l - 1]) rc = launch_gemv_dx_bits(st, dY, ld_hy, packed + L.off_w, bits[l - 1], dx[l - 1], L.pin, L.pin, mb);
-            if (rc == -1) rc = launch_gemv_dx(st, dY, ld_hy, packed + L.off_w, acts[l - 1], L.pin, dx[l - 1], L.pin, L.pin, mb);
+            if (rc == -1) rc = launch_gemv_dx(st, dY, ld_hy, packed + L.off_w, acts[l - 1], L.pin, dx[l - 1], L.pin, L.pin, mb, hidden_act);
         } else {
             if (have_bits[l - 1] && x3 && xl.dx[l] >= 0)  // [r4] split-bf16 dX
                 rc = launch_gemm_nt_split(st, dY, L.pout, x3 + xl.dx[l], nullptr, dx[l - 1], L.pin, mb, L.pin, L.pout, 1, bits[l - 1]);
@@ -933,7 +949,7 @@ static int backward(hipStream_t st, const NetLayout &net, const float *packed, c
                                          EPI_MASK, bits[l - 1]);
             if (rc == -1)
                 rc = launch_gemm_nt(st, dY, L.pout, packed + L.off_wt, L.pout, nullptr, acts[l - 1], L.pin, dx[l - 1], L.pin, mb,
-                                    L.pin, L.pout, EPI_MASK);
+                                    L.pin, L.pout, hidden_act_dx_epi(hidden_act));
         }
         if (rc) return rc;
     }
@@ -1112,7 +1128,9 @@ static int head_backward(hipStream_t st, const NetLayout &net, const float *pack
 // launches (11.59 against 11.71 ms per 10-epoch learn() at the 8-rank share, tools/ab_update.py, profiles/r05_ab_update_final.txt);
 // at 524,288 rows per pass the two are equal and the fused form saves the 268 MB copy.  rlppo_dbg_set(26, 2): at every size (tests).
 constexpr int64_t FUSED_GATHER_MIN_ROWS = 262144;
-static RowSource first_layer_rows(const rlppo_minibatch_args &a, const NetLayout &pol, const NetLayout &val, int prec, const WsPlan &w) {
+static RowSource first_layer_rows(const rlppo_minibatch_args &a, const NetLayout &pol, const NetLayout &val, int prec, const WsPlan &w,
+                                  bool plain = false) {
+    if (plain) return RowSource{w.states, pol.L[0].pin};  // [act] the gathered first layer is a ReLU-bitmask launch: the gather pass
     const int64_t src_rows = a.ring_cap > 0 ? a.ring_cap : a.n_rows;
     auto gather_form = [&](const NetLayout &n) {
         return n.n_layers > 1 && nt_gather_ok(a.ld_states, src_rows, n.L[0].pout, n.L[0].pin) && tn_gather_ok(a.ld_states, src_rows) &&
@@ -1140,6 +1158,11 @@ struct Pass {
     const float *pol_w, *val_w;  // the packed weights the products read (bf16 precision: their rounded images)
     hipStream_t st, side;        // the policy's and the critic's chain (one stream: rlppo_dbg_set(4, 0))
     DwList *defer;               // [r5] the grouped weight gradients, or null
+    // [act] the hidden activation of each network (HiddenAct), and whether the pass is the PLAIN form: two chains on gathered rows,
+    // dX by the saved activation -- no bitmasks, no folded value head, no paired launches, no gather-fused first layer.  A pass with
+    // a tanh / ELU network is plain (that machinery is ReLU by construction); rlppo_dbg_set(19, 0) makes a ReLU pass plain too.
+    int pol_act = ACT_RELU, val_act = ACT_RELU;
+    bool plain = false;
 };
 
 static LossCfg loss_cfg(const rlppo_minibatch_args &a) {
@@ -1347,6 +1370,11 @@ static int two_chain_pass(const Pass &p) {
         if (rc) return rc;
         rc = forward_b16(p.st, pol, p.pol_w, pol_wb16, p.rows.x, w.states_b, p.rows.ld, mb, a.head == RLPPO_HEAD_GAUSSIAN, w.pol.act,
                          w.pol.actb, w.pol.bits, phave, pf32);
+    } else if (p.plain) {  // [act] (fp32 precision only: validated)
+        rc = forward(p.side, val, p.val_w, p.rows, mb, 0, w.val.act, 0, nullptr, vhave, nullptr, nullptr, false, p.val_act);
+        if (rc) return rc;
+        rc = forward(p.st, pol, p.pol_w, p.rows, mb, a.head == RLPPO_HEAD_GAUSSIAN, w.pol.act, 0, nullptr, phave, nullptr, nullptr, false,
+                     p.pol_act);
     } else {
         rc = forward(p.side, val, p.val_w, p.rows, mb, 0, w.val.act, 0, w.val.bits, vhave, &v_folded, val_x3, true);
         if (rc) return rc;
@@ -1368,13 +1396,17 @@ static int two_chain_pass(const Pass &p) {
         return backward_b16(p.st, pol, p.pol_w, pol_wb16, p.rows.x, w.states_b, p.rows.ld, mb, w.pol.act, w.pol.actb, w.pol.dx, w.pol.dxb,
                             a.pol_grad, w.pol.tn, tn_ws_floats(pol, mb, p.prec), w.pol.bits, phave, pf32);
     }
-    rc = backward(p.side, val, p.val_w, p.rows, mb, w.val.act, w.val.dx, a.val_grad, w.val.tn, w.val.bits, vhave, v_folded, val_x3, p.defer);
+    rc = backward(p.side, val, p.val_w, p.rows, mb, w.val.act, w.val.dx, a.val_grad, w.val.tn, w.val.bits, vhave, v_folded, val_x3, p.defer,
+                  p.val_act);
     if (rc) return rc;
-    return backward(p.st, pol, p.pol_w, p.rows, mb, w.pol.act, w.pol.dx, a.pol_grad, w.pol.tn, w.pol.bits, phave, false, pol_x3, p.defer);
+    return backward(p.st, pol, p.pol_w, p.rows, mb, w.pol.act, w.pol.dx, a.pol_grad, w.pol.tn, w.pol.bits, phave, false, pol_x3, p.defer,
+                    p.pol_act);
 }
 
 // one pass; md_nvec (host, or null = the reference's multi-discrete head) is rlppo_ppo_minibatch_nvec's
-static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads, const DiagHead *diag = nullptr) {
+static int g_relu_bits = 1;  // rlppo_dbg_set(19, 0/1): 0 = every fp32 pass takes the plain form (measurements: what the form costs a ReLU pass)
+static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads, const DiagHead *diag = nullptr,
+                         int pol_act = ACT_RELU, int val_act = ACT_RELU) {
     // ---- validation: every argument error is reported here, before the first HIP call
     RLPPO_CHECK_ARG(a != nullptr, "ppo_minibatch: null args");
     Pass p;
@@ -1390,6 +1422,15 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     // [r5] the precision is an argument of the call (two learners of one process may differ); the process-wide switch is its default
     rc = resolve_precision(a->precision, &p.prec);
     if (rc) return rc;
+    // [act] the hidden activations: tanh / ELU passes are fp32 (the bf16 and split-bf16 kernels carry the ReLU bitmask by construction)
+    RLPPO_CHECK_ARG(hidden_act_ok(pol_act) && hidden_act_ok(val_act), "ppo_minibatch: pol_hidden_act=%d val_hidden_act=%d (0 = ReLU, 1 = tanh, 2 = ELU)",
+                    pol_act, val_act);
+    p.pol_act = pol_act;
+    p.val_act = val_act;
+    const bool non_relu = pol_act != ACT_RELU || val_act != ACT_RELU;
+    RLPPO_CHECK_ARG(!(non_relu && p.prec != 0), "ppo_minibatch: hidden activation %s with update precision %s: the %s kernels are ReLU only (use fp32)",
+                    hidden_act_name(pol_act != ACT_RELU ? pol_act : val_act), p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
+    p.plain = non_relu || (p.prec == 0 && !g_relu_bits);
     RLPPO_CHECK_ARG(mb > 0 && a->pol_packed && a->val_packed && a->pol_grad && a->val_grad && a->states && a->actions &&
                         a->old_logp && a->targets && a->advantages && a->idx && a->stats && a->workspace,
                     "ppo_minibatch: null pointer");
@@ -1459,8 +1500,8 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     RLPPO_CHECK_ARG(slot >= 0 && slot < RLPPO_MAX_SLOTS, "ppo_minibatch: slot %d not in [0, %d)", slot, RLPPO_MAX_SLOTS);
 
     // ---- plan: the first layers' rows, the form, the loss settings
-    p.rows = first_layer_rows(*a, pol, val, p.prec, p.w);
-    const bool twin = p.prec == 0 && (g_paired == 2 || (g_paired == 1 && mb >= PAIRED_MIN_ROWS)) && twin_ok(pol, val, mb);
+    p.rows = first_layer_rows(*a, pol, val, p.prec, p.w, p.plain);
+    const bool twin = p.prec == 0 && !p.plain && (g_paired == 2 || (g_paired == 1 && mb >= PAIRED_MIN_ROWS)) && twin_ok(pol, val, mb);
     p.cfg = loss_cfg(*a);
     p.pol_w = p.prec == 1 ? a->pol_packed_r : a->pol_packed;
     p.val_w = p.prec == 1 ? a->val_packed_r : a->val_packed;
@@ -1512,6 +1553,19 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
 int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) { return ppo_minibatch(stream, a, nullptr, 0); }
 int rlppo_ppo_minibatch_nvec(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads) {
     return ppo_minibatch(stream, a, md_nvec, md_heads);
+}
+
+// [act] every head through one call: the hidden activations + what the _nvec / _diag entry points bring.  NULL / zeroed ext: rlppo_ppo_minibatch
+int rlppo_ppo_minibatch_ex(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext) {
+    if (!ext) return ppo_minibatch(stream, a, nullptr, 0);
+    const bool diag = ext->log_std || ext->log_std_grad || ext->scratch || ext->scratch_bytes;
+    DiagHead d;
+    d.log_std = ext->log_std;
+    d.log_std_grad = ext->log_std_grad;
+    d.scratch = reinterpret_cast<double *>(ext->scratch);
+    d.scratch_bytes = ext->scratch_bytes;
+    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(ext->scratch) & 7) == 0, "ppo_minibatch_ex: scratch must be 8-byte aligned");
+    return ppo_minibatch(stream, a, ext->md_nvec, ext->md_heads, diag ? &d : nullptr, ext->pol_hidden_act, ext->val_hidden_act);
 }
 
 size_t rlppo_diag_scratch_bytes(int64_t mb, int32_t k) { return diag_scratch_bytes(mb, k); }
@@ -1786,6 +1840,7 @@ int rlppo_dbg_set(int32_t key, int32_t value) {
     switch (key) {
         case 1: set_gae_algo(value); return 0;
         case 4: g_two_streams = value; return 0;
+        case 19: g_relu_bits = value; return 0;
         case 21: set_gae_spin_limit(value); return 0;
         case 22: set_gae_oversubscribe(value); return 0;
         case 34: set_fused_spin_limit(value); return 0;

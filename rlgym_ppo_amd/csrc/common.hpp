@@ -95,7 +95,20 @@ struct NetLayout {
 int make_layout(const int32_t *dims, int32_t n_layers, NetLayout *out);
 
 // ---- kernel launchers shared between translation units ------------------------------------------
-enum Epilogue { EPI_BIAS = 0, EPI_BIAS_RELU = 1, EPI_BIAS_TANH = 2, EPI_MASK = 3 };
+enum Epilogue {
+    EPI_BIAS = 0, EPI_BIAS_RELU = 1, EPI_BIAS_TANH = 2, EPI_MASK = 3,
+    // [act] hidden activations beyond ReLU: the ELU (alpha = 1) forward, and the two dX epilogues whose factor is a function of the
+    // saved OUTPUT h alone (read from mask_src exactly as EPI_MASK reads it): acc *= 1 - h^2 / acc *= (h > 0 ? 1 : h + 1)
+    EPI_BIAS_ELU = 4, EPI_DTANH = 5, EPI_DELU = 6
+};
+// the epilogues that multiply by a function of the saved activation: no bias, mask_src required
+constexpr bool epi_reads_act(int e) { return e == EPI_MASK || e == EPI_DTANH || e == EPI_DELU; }
+// [act] rlppo_act_opts.hidden_act / rlppo_minibatch_ext.*_hidden_act: 0 = ReLU, 1 = tanh, 2 = ELU (alpha = 1)
+enum HiddenAct { ACT_RELU = 0, ACT_TANH = 1, ACT_ELU = 2 };
+inline bool hidden_act_ok(int a) { return a >= ACT_RELU && a <= ACT_ELU; }
+inline const char *hidden_act_name(int a) { return a == ACT_TANH ? "tanh" : a == ACT_ELU ? "elu" : "relu"; }
+inline int hidden_act_fwd_epi(int a) { return a == ACT_TANH ? EPI_BIAS_TANH : a == ACT_ELU ? EPI_BIAS_ELU : EPI_BIAS_RELU; }
+inline int hidden_act_dx_epi(int a) { return a == ACT_TANH ? EPI_DTANH : a == ACT_ELU ? EPI_DELU : EPI_MASK; }
 
 // gemm.hip ------------------------------------------------------------------------------------------
 // C[m][0:N] = epi(A[m][0:K] . B[n][0:K]^T)   (K % 32 == 0, N = padded out in {32,64,96,128,k*128})
@@ -193,7 +206,9 @@ int launch_thin_dx_b16(hipStream_t st, const float *dy, int64_t ldy, int out, co
                        const unsigned long long *bits, unsigned short *dxb, int64_t ldc, int kp, int64_t n);
 int launch_thin_dw_b16(hipStream_t st, const float *dy, int64_t ldy, const unsigned short *xb, int64_t ldx, float *dw, float *db,
                        int out, int in, int kp, int64_t n, float *ws, size_t ws_floats);
-int launch_gemv_dx(hipStream_t st, const float *dy, int64_t ldy, const float *w, const float *mask, int64_t ldm, float *dx, int64_t ldc, int kp, int64_t n);
+// act (HiddenAct): the derivative the saved activation `mask` stands for -- h > 0 ? d w : 0, d w (1 - h^2) or d w (h > 0 ? 1 : h + 1)
+int launch_gemv_dx(hipStream_t st, const float *dy, int64_t ldy, const float *w, const float *mask, int64_t ldm, float *dx, int64_t ldc, int kp, int64_t n,
+                   int act = 0);
 int launch_gemv_dx_bits(hipStream_t st, const float *dy, int64_t ldy, const float *w, const unsigned long long *bits, float *dx,
                         int64_t ldc, int kp, int64_t n);
 int launch_gemv_dw(hipStream_t st, const float *dy, int64_t ldy, const float *x, int64_t ldx, float *dw, float *db, int in, int kp, int64_t n,

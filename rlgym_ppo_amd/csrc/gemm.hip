@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256, BKT == 16 ? 4 : 2) void gemm_nt_dma_kernel(con
     }
 
     f32x4 acc[2][NB];
-    if (EPI == EPI_MASK) {
+    if (epi_reads_act(EPI)) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -328,13 +328,13 @@ static int launch_nt_1(hipStream_t st, dim3 grid, int epi, const float *A, unsig
     // input is padded to 16], where it runs BK = 16 with its one ragged pass
     constexpr int BKT = (NB * 16) % 32 == 0 && NB * 16 >= 64 ? 16 : 32;
     if (BKT == 32 && K % 32 != 0) {
-        if (epi == EPI_BIAS_RELU || epi == EPI_BIAS || epi == EPI_BIAS_TANH || epi == EPI_MASK) {
+        if (epi >= EPI_BIAS && epi <= EPI_DELU) {
 #define NT16(E)                                                                                                         \
     case E:                                                                                                            \
         hipLaunchKernelGGL((gemm_nt_dma_kernel<NB, E, 16>), grid, dim3(256), 0, st, A, lda_b, B, ldb_b, bias, mask_src,  \
                            ldm_b, C, ldc_b, M, K);                                                                     \
         break;
-            switch (epi) { NT16(EPI_BIAS) NT16(EPI_BIAS_RELU) NT16(EPI_BIAS_TANH) NT16(EPI_MASK) }
+            switch (epi) { NT16(EPI_BIAS) NT16(EPI_BIAS_RELU) NT16(EPI_BIAS_TANH) NT16(EPI_MASK) NT16(EPI_BIAS_ELU) NT16(EPI_DTANH) NT16(EPI_DELU) }
 #undef NT16
             RLPPO_LAUNCH_CHECK();
             return 0;
@@ -346,7 +346,7 @@ static int launch_nt_1(hipStream_t st, dim3 grid, int epi, const float *A, unsig
                            ldm_b, C, ldc_b, M, K);                                                                     \
         break;
     switch (epi) {
-        NT(EPI_BIAS) NT(EPI_BIAS_RELU) NT(EPI_BIAS_TANH) NT(EPI_MASK)
+        NT(EPI_BIAS) NT(EPI_BIAS_RELU) NT(EPI_BIAS_TANH) NT(EPI_MASK) NT(EPI_BIAS_ELU) NT(EPI_DTANH) NT(EPI_DELU)
         default:
             set_error("gemm_nt: bad epilogue %d", epi);
             return RLPPO_ERR_ARG;
@@ -417,6 +417,7 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_kernel(const float *__rest
     for (int e = 0; e < 4; ++e) {
         if (EPI == EPI_BIAS_RELU) acc[e] = relu1(acc[e]);
         if (EPI == EPI_BIAS_TANH) acc[e] = tanhf(acc[e]);
+        if constexpr (EPI == EPI_BIAS_ELU) acc[e] = elu1(acc[e]);
     }
     // lane (r16, q) holds C[row m0 + r16][columns n0 + 4 q .. + 3]
     if (m0 + r16 < M) *reinterpret_cast<f32x4 *>(C + (m0 + r16) * ldc + n0 + q * 4) = acc;
@@ -430,7 +431,7 @@ static int launch_gemm_nt_skinny(hipStream_t st, const float *A, int64_t lda, co
         hipLaunchKernelGGL((gemm_nt_skinny_kernel<E>), grid, dim3(256), 0, st, A, lda, B, ldb, bias, C, ldc, M, N, K);      \
         break;
     switch (epi) {
-        SK(EPI_BIAS) SK(EPI_BIAS_RELU) SK(EPI_BIAS_TANH)
+        SK(EPI_BIAS) SK(EPI_BIAS_RELU) SK(EPI_BIAS_TANH) SK(EPI_BIAS_ELU)
         default:
             set_error("gemm_nt (few rows): bad epilogue %d", epi);
             return RLPPO_ERR_ARG;
@@ -532,8 +533,9 @@ int launch_gemm_nt(hipStream_t st, const float *A, int64_t lda, const float *B, 
     RLPPO_CHECK_ARG(lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && lda >= K && ldb >= K && ldc >= N,
                     "gemm_nt: leading dimensions lda=%ld ldb=%ld ldc=%ld incompatible with K=%d N=%d", (long)lda,
                     (long)ldb, (long)ldc, K, N);
-    RLPPO_CHECK_ARG(epi != EPI_MASK || (mask_src && ld_mask >= N && ld_mask % 4 == 0), "gemm_nt: mask operand missing");
-    RLPPO_CHECK_ARG(epi == EPI_MASK || bias, "gemm_nt: bias operand missing");
+    const bool by_act = epi_reads_act(epi);  // the dX epilogues: relu mask, [act] times tanh' / times ELU' of the saved activation
+    RLPPO_CHECK_ARG(!by_act || (mask_src && ld_mask >= N && ld_mask % 4 == 0), "gemm_nt: mask operand missing");
+    RLPPO_CHECK_ARG(by_act || bias, "gemm_nt: bias operand missing");
     int nb;
     if (N % 128 == 0) nb = 8;
     else if (N == 96) nb = 6;
@@ -549,8 +551,8 @@ int launch_gemm_nt(hipStream_t st, const float *A, int64_t lda, const float *B, 
                     "gemm_nt: a leading dimension is too wide for 32-bit tile offsets");
     // (the bf16-operand inference kernel steps K by 32: a layer whose K is only a multiple of 16 -- a first layer padded to 16 --
     // keeps the fp32 kernel, i.e. is computed MORE precisely than the mode asks)
-    if (bf16_operands && epi != EPI_MASK && K % 32 == 0) return launch_gemm_nt_bf16(st, A, lda, B, ldb, bias, C, ldc, M, N, nb, K, epi);
-    if (g_nt_skinny && M <= SK_MAX_ROWS && epi != EPI_MASK && !bf16_operands) return launch_gemm_nt_skinny(st, A, lda, B, ldb, bias, C, ldc, M, N, K, epi);
+    if (bf16_operands && !by_act && K % 32 == 0) return launch_gemm_nt_bf16(st, A, lda, B, ldb, bias, C, ldc, M, N, nb, K, epi);
+    if (g_nt_skinny && M <= SK_MAX_ROWS && !by_act && !bf16_operands) return launch_gemm_nt_skinny(st, A, lda, B, ldb, bias, C, ldc, M, N, K, epi);
     dim3 grid((unsigned)cdiv(M, SBM), (unsigned)(N / (nb * 16)));
     const unsigned la = (unsigned)(lda * 4), lb = (unsigned)(ldb * 4), lc = (unsigned)(ldc * 4), lm = (unsigned)(ld_mask * 4);
     switch (nb) {

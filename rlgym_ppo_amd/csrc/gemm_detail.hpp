@@ -30,6 +30,8 @@ __device__ __forceinline__ void stb(__amdgpu_buffer_rsrc_t r, unsigned voff, uns
 // canonicalisation; an inline-asm v_max is invisible to the MFMA -> VALU hazard recogniser and read accumulators early:
 // rare wrong activations under load, found by the 2-rank test.)  NaN -> 0 like the select form.
 __device__ __forceinline__ float relu1(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, __builtin_inff()); }
+// [act] ELU, alpha = 1: expm1f keeps the relative accuracy of e^x - 1 near 0, where exp(x) - 1 cancels
+__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
 }  // namespace
 
 // The 128-column tile of a wave (32 rows) leaves through LDS, 16 rows at a time: a lane holds 4 consecutive columns of one row (a
@@ -88,6 +90,24 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[2][NB], const float *ma
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[i][j][e] = h[e] > 0.f ? acc[i][j][e] : 0.f;
             }
+    } else if constexpr (EPI == EPI_DTANH || EPI == EPI_DELU) {
+        // [act] dX of a tanh / ELU hidden layer: the derivative is a function of the saved output h alone (1 - h^2; h > 0 ? 1 : h + 1),
+        // read as EPI_MASK reads it -- same descriptor, same lane map; rows past M load h = 0 (factor 1) and their stores are dropped
+        const __amdgpu_buffer_rsrc_t m_rs = make_rsrc(reinterpret_cast<const char *>(mask_src) + m0 * ldm_b + (int64_t)n0 * 4,
+                                                      (unsigned)(rows_here - 1) * ldm_b + BN * 4);
+        const unsigned m_off = (unsigned)row_l * ldm_b + q * 16;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const f32x4 h = ldb(m_rs, m_off, 16 * i * ldm_b + j * 64);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float x = acc[i][j][e];
+                    if constexpr (EPI == EPI_DTANH) acc[i][j][e] = x * (1.f - h[e] * h[e]);
+                    else acc[i][j][e] = x * (h[e] > 0.f ? 1.f : h[e] + 1.f);
+                }
+            }
     } else if (EPI != EPI_BIAS && EPI != EPI_NONE) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -97,6 +117,7 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[2][NB], const float *ma
                 for (int e = 0; e < 4; ++e) {
                     if (EPI == EPI_BIAS_RELU) acc[i][j][e] = relu1(acc[i][j][e]);
                     if (EPI == EPI_BIAS_TANH) acc[i][j][e] = tanhf(acc[i][j][e]);
+                    if constexpr (EPI == EPI_BIAS_ELU) acc[i][j][e] = elu1(acc[i][j][e]);
                 }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -112,7 +133,9 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[2][NB], const float *ma
         for (int j = 0; j < NB; ++j) stb(c_rs, c_off, 16 * i * ldc_b + j * 64, acc[i][j]);
 }
 
-// ReLU bitmask (rlppo_dbg_set(19)).  dX = (dY . W) masked by [h > 0] needs one BIT of the forward activation per element,
+// ReLU bitmask.  (rlppo_dbg_set(19, 0) turns it off together with everything built on it -- the folded value head, paired launches,
+// the gather-fused first layer: every fp32 pass then takes the plain form of a tanh / ELU pass, include/rlppo.h.)
+// dX = (dY . W) masked by [h > 0] needs one BIT of the forward activation per element,
 // but re-reading h costs a 64 KB tile per workgroup whose latency nothing hides (the accumulators occupy the registers the
 // tile would have to be prefetched into): the masked epilogue is 11 % of a dX launch (scratch/epi_cost.py).  Instead the
 // forward epilogue of a hidden layer also emits, per lane, the 64 bits [acc > 0] of the 64 outputs the lane owns --

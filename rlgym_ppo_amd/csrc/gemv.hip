@@ -69,7 +69,9 @@ __global__ __launch_bounds__(256) void gemv_fwd_kernel(const XT *__restrict__ x,
     }
 }
 
-// 16 bytes per thread
+// 16 bytes per thread.  ACT (HiddenAct): what the saved activation h says about the hidden layer's derivative -- ReLU [h > 0], [act]
+// tanh 1 - h^2, ELU (alpha = 1) h > 0 ? 1 : h + 1
+template <int ACT>
 __global__ __launch_bounds__(256) void gemv_dx_kernel(const float *__restrict__ dy, int64_t ldy, const float *__restrict__ w,
                                                       const float *__restrict__ mask, int64_t ldm, float *__restrict__ dx,
                                                       int64_t ldc, int cpr, int64_t n) {
@@ -82,7 +84,11 @@ __global__ __launch_bounds__(256) void gemv_dx_kernel(const float *__restrict__ 
     const f32x4 wv = *reinterpret_cast<const f32x4 *>(w + c);
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = h[e] > 0.f ? d * wv[e] : 0.f;
+    for (int e = 0; e < 4; ++e) {
+        if constexpr (ACT == ACT_TANH) o[e] = (d * wv[e]) * (1.f - h[e] * h[e]);
+        else if constexpr (ACT == ACT_ELU) o[e] = (d * wv[e]) * (h[e] > 0.f ? 1.f : h[e] + 1.f);
+        else o[e] = h[e] > 0.f ? d * wv[e] : 0.f;
+    }
     *reinterpret_cast<f32x4 *>(dx + row * ldc + c) = o;
 }
 
@@ -384,10 +390,13 @@ int launch_gemv_fwd_b16(hipStream_t st, const unsigned short *x, int64_t ldx, co
 }
 
 int launch_gemv_dx(hipStream_t st, const float *dy, int64_t ldy, const float *w, const float *mask, int64_t ldm, float *dx,
-                   int64_t ldc, int kp, int64_t n) {
+                   int64_t ldc, int kp, int64_t n, int act) {
     if (n <= 0) return 0;
     const int cpr = kp / 4;
-    hipLaunchKernelGGL(gemv_dx_kernel, dim3((unsigned)cdiv(n * cpr, 256)), dim3(256), 0, st, dy, ldy, w, mask, ldm, dx, ldc, cpr, n);
+    const dim3 grid((unsigned)cdiv(n * cpr, 256));
+    if (act == ACT_TANH) hipLaunchKernelGGL(gemv_dx_kernel<ACT_TANH>, grid, dim3(256), 0, st, dy, ldy, w, mask, ldm, dx, ldc, cpr, n);
+    else if (act == ACT_ELU) hipLaunchKernelGGL(gemv_dx_kernel<ACT_ELU>, grid, dim3(256), 0, st, dy, ldy, w, mask, ldm, dx, ldc, cpr, n);
+    else hipLaunchKernelGGL(gemv_dx_kernel<ACT_RELU>, grid, dim3(256), 0, st, dy, ldy, w, mask, ldm, dx, ldc, cpr, n);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }

@@ -66,10 +66,15 @@ class NetArena:
 
     tail (optional): Parameters that are not a layer of the MLP (the diagonal-Gaussian head's log_std).  They live BEHIND the network's
     n_net = rlppo_flat_floats elements in `flat` / `grad` (n_flat = n_net + n_tail), so the optimiser, the gradient exchange and the
-    report cover them with the arena; params() yields them last; packing reads the first n_net elements only."""
+    report cover them with the arena; params() yields them last; packing reads the first n_net elements only.
 
-    def __init__(self, linears, device, tail=()):
+    hidden_act: the RLPPO_ACT_* code of the network's hidden activation (0 = ReLU).  The kernels learn it per call: act_opts() puts
+    it into the rlppo_act_opts of every rollout call on this arena, PPOLearner into rlppo_minibatch_ext."""
+
+    def __init__(self, linears, device, tail=(), hidden_act=0):
         self.device = device
+        self.hidden_act = int(hidden_act)
+        self._act_opts = None
         self.linears = list(linears)
         self.tail = list(tail)
         self.dims = [self.linears[0].in_features] + [l.out_features for l in self.linears]
@@ -241,6 +246,19 @@ class NetArena:
                                        flag, mean0, std0))
         return out
 
+    def act_opts(self, opts=None):
+        """The rlppo_act_opts a rollout call on this arena passes: `opts` (the caller's, or None) carrying the hidden activation.
+        A ReLU arena passes exactly what it was given -- None where the caller has none."""
+        if self.hidden_act == 0:
+            return opts
+        if opts is None:
+            if self._act_opts is None:
+                self._act_opts = N.ActOpts()
+                self._act_opts.hidden_act = self.hidden_act
+            return self._act_opts
+        opts.hidden_act = self.hidden_act
+        return opts
+
     def forward_ws(self, n):
         return self.ws.get(N.lib().rlppo_forward_workspace_bytes(self.dims_c, self.n_layers, n))
 
@@ -251,7 +269,7 @@ class NetArena:
         out = torch.empty((n, self.ld_out), dtype=torch.float32, device=self.device)
         ws = self.forward_ws(n)
         N.check(N.lib().rlppo_mlp_forward(stream_ptr(), self.dims_c, self.n_layers, ptr(self.packed), ptr(obs_padded),
-                                          obs_padded.shape[1], n, int(out_tanh), ptr(out), self.ld_out, ptr(ws), ws.numel(), None))
+                                          obs_padded.shape[1], n, int(out_tanh), ptr(out), self.ld_out, ptr(ws), ws.numel(), self.act_opts()))
         return out
 
 

@@ -43,6 +43,7 @@ class Learner(object):
             n_checkpoints_to_keep: int = 5, shm_buffer_size: int = 8192, device: str = "auto",
             vector_env: bool = False, gae_bootstrap_truncated: bool = False, multi_discrete_bins=None,
             continuous_head: str = "reference", continuous_log_std_init: float = 0.0, continuous_action_clip="default",
+            hidden_activation: str = "relu",
             ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
             per_feature_obs_standardization: bool = False,
             ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
@@ -56,6 +57,26 @@ class Learner(object):
         # not in the reference: the learning-rate schedule (ppo/lr_schedule.py) -- "adaptive" is PPOLearner's (decided on the device, per
         # optimiser step); "linear" is this loop's: before every learn() both rates are lr0 * max(0, 1 - T / timestep_limit), T the
         # cumulative timesteps before the iteration's collect (stateless: a loaded checkpoint derives them from its book-keeping)
+        # not in the reference (whose networks are ReLU): hidden_activation = "relu" | "tanh" | "elu" (alpha = 1) for every hidden layer of
+        # the policy AND the critic.  It travels to the networks inside the layer sizes (ppo.LayerSizes); sizes that already are a
+        # LayerSizes keep their activation while hidden_activation is left at its default and must agree with it otherwise.  Checked
+        # here, before anything is built or spawned.  (The default IS "relu", so an explicit hidden_activation="relu" cannot be told
+        # from an omitted one: LayerSizes(..., "tanh") beside it builds a tanh network and raises nothing -- the one disagreement that
+        # is not refused.  self.hidden_activations says what was built.)
+        from .ppo._mlp import LayerSizes, check_activation
+        hidden_activation = check_activation(hidden_activation)
+
+        def with_activation(name, sizes):
+            own = getattr(sizes, "activation", None)
+            if own is not None and own != hidden_activation and hidden_activation != "relu":
+                raise ValueError(f"{name} is LayerSizes(..., {own!r}) but hidden_activation={hidden_activation!r}: give one of them")
+            return LayerSizes(sizes, own if own is not None else hidden_activation)
+        sizes_given = (policy_layer_sizes, critic_layer_sizes)   # (what the config dict logs, as it always did)
+        policy_layer_sizes = with_activation("policy_layer_sizes", policy_layer_sizes)
+        critic_layer_sizes = with_activation("critic_layer_sizes", critic_layer_sizes)
+        # what was built, per network; and as one name where both agree (the keyword's own type), None where they differ
+        self.hidden_activations = {"policy": policy_layer_sizes.activation, "critic": critic_layer_sizes.activation}
+        self.hidden_activation = policy_layer_sizes.activation if policy_layer_sizes.activation == critic_layer_sizes.activation else None
         from .ppo import lr_schedule as LRS
         ppo_lr_schedule, ppo_desired_kl, ppo_lr_bounds = LRS.check_schedule(ppo_lr_schedule, ppo_desired_kl, ppo_lr_bounds,
                                                                             policy_lr=policy_lr, critic_lr=critic_lr)
@@ -188,7 +209,9 @@ class Learner(object):
             "n_proc": n_proc, "min_inference_size": min_inference_size, "timestep_limit": timestep_limit,
             "exp_buffer_size": exp_buffer_size, "ts_per_iteration": ts_per_iteration,
             "standardize_returns": standardize_returns, "standardize_obs": standardize_obs,
-            "policy_layer_sizes": policy_layer_sizes, "critic_layer_sizes": critic_layer_sizes, "ppo_epochs": ppo_epochs,
+            "policy_layer_sizes": sizes_given[0], "critic_layer_sizes": sizes_given[1], "ppo_epochs": ppo_epochs,
+            # (a hyper-parameter like the layer sizes, not checkpoint state)
+            "hidden_activation": self.hidden_activation if self.hidden_activation is not None else dict(self.hidden_activations),
             "ppo_batch_size": ppo_batch_size, "ppo_minibatch_size": ppo_minibatch_size, "ppo_ent_coef": ppo_ent_coef,
             "ppo_clip_range": ppo_clip_range, "gae_lambda": gae_lambda, "gae_gamma": gae_gamma, "policy_lr": policy_lr,
             "critic_lr": critic_lr, "shm_buffer_size": shm_buffer_size,

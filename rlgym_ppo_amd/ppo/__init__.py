@@ -1,3 +1,4 @@
+from ._mlp import LayerSizes
 from .continuous_policy import ContinuousPolicy
 from .diag_gaussian_policy import DiagGaussianPolicy
 from .multi_discrete_policy import MultiDiscreteFF

@@ -18,13 +18,51 @@ from ..engine import NetArena, linears_of, ptr, require_gpu, selection_epoch, st
 from ..util import action_mask as AM
 
 
+HIDDEN_MODULES = {"relu": nn.ReLU, "tanh": nn.Tanh, "elu": nn.ELU}   # (nn.ELU's default alpha = 1: the only one the kernels have)
+
+
+def check_activation(name):
+    """The name of a hidden activation the library runs ("relu", "tanh", "elu"); ValueError otherwise."""
+    if not isinstance(name, str) or name not in HIDDEN_MODULES:
+        raise ValueError(f"hidden activation must be one of {sorted(HIDDEN_MODULES)}, got {name!r}")
+    return name
+
+
+class LayerSizes(tuple):
+    """Hidden layer sizes that carry the hidden activation ("relu", "tanh" or "elu", alpha = 1) of the network built from them -- the
+    activation travels in an argument every constructor already has, the way multi-discrete bins travel in act_space_size.  A tuple
+    in every other respect (tuple(x) gives the plain sizes back); a plain tuple means "relu"."""
+
+    def __new__(cls, sizes, activation="relu"):
+        self = super().__new__(cls, tuple(sizes))
+        self.activation = check_activation(activation)
+        return self
+
+    def __reduce__(self):
+        return (LayerSizes, (tuple(self), self.activation))
+
+    def __repr__(self):
+        return f"LayerSizes({tuple(self)!r}, {self.activation!r})"
+
+
+def activation_of(module):
+    """The hidden activation's name of a body build_body made (index 1 of the Sequential is the first hidden activation)."""
+    for name, cls in HIDDEN_MODULES.items():
+        if type(module[1]) is cls:
+            return name
+    raise ValueError(f"hidden activation {type(module[1]).__name__} has no kernels (build_body makes {sorted(HIDDEN_MODULES)})")
+
+
 def build_body(input_shape, layer_sizes, n_out, final_activation=None):
     assert len(layer_sizes) != 0, "AT LEAST ONE LAYER MUST BE SPECIFIED TO BUILD THE NEURAL NETWORK!"
-    layers = [nn.Linear(int(input_shape), int(layer_sizes[0])), nn.ReLU()]
+    # the activation modules have no parameters and draw nothing: whichever is chosen, the Sequential's indices, its state_dict keys
+    # and the CPU generator's consumption are the same, so a seeded run starts from the same weights
+    act = HIDDEN_MODULES[check_activation(getattr(layer_sizes, "activation", "relu"))]
+    layers = [nn.Linear(int(input_shape), int(layer_sizes[0])), act()]
     prev = int(layer_sizes[0])
     for size in layer_sizes[1:]:
         layers.append(nn.Linear(prev, int(size)))
-        layers.append(nn.ReLU())
+        layers.append(act())
         prev = int(size)
     layers.append(nn.Linear(prev, int(n_out)))
     if final_activation is not None:
@@ -92,7 +130,9 @@ class ActGraph:
         # switches (RLPPO_ACT_POLL / _EAGER / _LATE_NOISE / _HDP_FLUSH / _GRAPH) were configurations nobody ran and are gone.
         self.n_done = int(L.rlppo_act_done_words(cap))
         self.done_pin = torch.zeros(max(self.n_done, 1), dtype=torch.int32).pin_memory()
-        self.opts = N.ActOpts(N.PRECISION_DEFAULT, 1, self.done_pin.data_ptr())
+        # (a tanh / ELU arena: the options carry its activation -- the discrete head's step is then the layer chain, `late` below is
+        # false because rlppo_discrete_step_one_launch answers 0, and the noise is staged before the launch)
+        self.opts = a.act_opts(N.ActOpts(N.PRECISION_DEFAULT, 1, self.done_pin.data_ptr()))
         self.calls = self.polled = self.poll_timeouts = self.late_retries = self.stale_relaunches = 0
         self.graph_value = 1   # (the warm-up launch and the capture below store 1)
         # [r5] host window (rlppo_host_window_alloc): the one-launch step reads its observations, noise and control words from DEVICE
@@ -340,7 +380,9 @@ class ArenaModule(nn.Module):
         dev = require_gpu(device)
         self.model = self.model.to(dev)
         # (a head's parameters that are not a layer -- DiagGaussianPolicy.log_std -- ride in the arena's tail)
-        self.arena = NetArena(linears_of(self.model), dev, tail=getattr(self, "_arena_tail", ()))
+        self.hidden_activation = activation_of(self.model)
+        self.arena = NetArena(linears_of(self.model), dev, tail=getattr(self, "_arena_tail", ()),
+                              hidden_act=N.HIDDEN_ACTIVATIONS[self.hidden_activation])
         self.act_graphs = True  # get_action through a hipGraph per batch-size bucket (False: every call takes the general path)
         self.act_graph_max = 1024  # beyond that the explicit copies of the eager path are the better transport for the noise
         self._graphs = {}

@@ -65,7 +65,7 @@ class ContinuousPolicy(ArenaModule):
         a = self.arena
         N.check(N.lib().rlppo_gaussian_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1], n,
                                            ptr(noise), float(self.affine_map.m), float(self.affine_map.b), ptr(actions),
-                                           ptr(logp), ptr(ws), ws.numel(), opts))
+                                           ptr(logp), ptr(ws), ws.numel(), a.act_opts(opts)))
 
     @staticmethod
     def logpdf(x, mean, std):

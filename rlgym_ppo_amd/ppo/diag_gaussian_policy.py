@@ -91,7 +91,7 @@ class DiagGaussianPolicy(ArenaModule):
         # (log_std's ADDRESS is an argument: the kernel reads the values when it runs, so a captured call follows the parameter)
         N.check(N.lib().rlppo_diag_gaussian_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1], n,
                                                 ptr(noise), ptr(self._log_std_dev()), ptr(actions), ptr(logp), ptr(ws), ws.numel(),
-                                                opts))
+                                                a.act_opts(opts)))
 
     def act_padded(self, rows, noise=None, action_mask=None):
         _no_action_mask(action_mask)

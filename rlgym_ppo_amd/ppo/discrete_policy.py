@@ -31,7 +31,7 @@ class DiscreteFF(ArenaModule):
         """(rlppo_act_opts carrying the packed mask, the packed words) of a call on n rows, or (None, None) without a mask.
         action_mask: bool / 0-1 [n, n_actions], host or device, or util.action_mask.Packed (already the kernels' words)."""
         words = self._mask_words(action_mask, n)
-        return self._opts_of(words), words
+        return self.arena.act_opts(self._opts_of(words)), words
 
     @staticmethod
     def _opts_of(words):
@@ -178,7 +178,7 @@ class DiscreteFF(ArenaModule):
                 raise ValueError("DiscreteFF._act_launch: opts and mask_words are one argument here, give one of them")
             opts = self._opts_of(mask_words)
         N.check(N.lib().rlppo_discrete_act(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1], n,
-                                           ptr(noise), ptr(actions), ptr(logp), None, ptr(ws), ws.numel(), opts))
+                                           ptr(noise), ptr(actions), ptr(logp), None, ptr(ws), ws.numel(), a.act_opts(opts)))
 
     def _act_launch_raw(self, g, cap, opts=None):
         """ActGraph's body as one node: rlppo_discrete_step on the graph's pinned observations / noise / outputs (g=None: the

@@ -115,6 +115,7 @@ class MultiDiscreteFF(ArenaModule):
     def _act_launch(self, rows, n, noise, actions, logp, ws, opts=None, mask_words=None):
         a = self.arena
         nvec = self.md_nvec
+        opts = a.act_opts(opts)
         if mask_words is not None:  # a masked call runs the general kernel, also on the reference's bins
             N.check(N.lib().rlppo_multidiscrete_act_nvec_masked(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(rows), rows.shape[1],
                                                                 n, ptr(noise), ptr(actions), ptr(logp), ptr(ws), ws.numel(), opts,

@@ -314,7 +314,19 @@ class PPOLearner(object):
 
     def _pass(self, st, args):
         """One rlppo_ppo_minibatch pass; a multi-discrete policy with bins of its own goes through rlppo_ppo_minibatch_nvec (the
-        general loss kernel), and so does every masked multi-discrete pass; every other policy through the plain entry point."""
+        general loss kernel), and so does every masked multi-discrete pass; every other policy through the plain entry point.
+        A tanh / ELU network (LayerSizes): every head through rlppo_ppo_minibatch_ex, which carries both activations."""
+        pa, va = self.policy.arena, self.value_net.arena
+        if pa.hidden_act or va.hidden_act:
+            ext = N.MinibatchExt()
+            ext.pol_hidden_act, ext.val_hidden_act = pa.hidden_act, va.hidden_act
+            if self.policy_type == 3:
+                sb = self._diag_scratch_bytes
+                ext.log_std, ext.log_std_grad = pa.flat.data_ptr() + 4 * pa.n_net, pa.grad.data_ptr() + 4 * pa.n_net
+                ext.scratch, ext.scratch_bytes = self._diag_scratch.data_ptr() + args.slot * sb, sb
+            elif self.policy_type == 1 and (self.policy.md_nvec is not None or args.action_mask):
+                ext.md_nvec, ext.md_heads = ctypes.cast(self.policy._nvec_c, ctypes.POINTER(ctypes.c_int32)), self.policy.n_heads
+            return N.lib().rlppo_ppo_minibatch_ex(st, ctypes.byref(args), ctypes.byref(ext))
         if self.policy_type == 3:   # log_std and its gradient: the tail of the policy's arena, behind the layers
             pa, sb = self.policy.arena, self._diag_scratch_bytes
             return N.lib().rlppo_ppo_minibatch_diag(st, ctypes.byref(args), pa.flat.data_ptr() + 4 * pa.n_net, pa.grad.data_ptr() + 4 * pa.n_net,
@@ -342,6 +354,13 @@ class PPOLearner(object):
         self.report_learning_rates = lr_schedule != "constant"
 
     def _check_options(self):
+        # a tanh / ELU network updates in fp32: the bf16 and split-bf16 kernels carry the ReLU bitmask by construction
+        acts = {m.hidden_activation for m in (self.policy, self.value_net)} - {"relu"}
+        if acts:
+            prec = self.update_precision or {0: "fp32", 1: "bf16", 2: "x3"}[int(N.lib().rlppo_get_update_precision())]
+            if prec != "fp32":
+                raise ValueError(f"hidden activation {sorted(acts)[0]!r} with update precision {prec!r}: the {prec} update kernels are ReLU "
+                                 "only -- use update_precision='fp32'")
         self.lr_schedule, self.desired_kl, self.lr_bounds = LRS.check_schedule(
             self.lr_schedule, self.desired_kl, self.lr_bounds, policy_lr=self.policy_optimizer.param_groups[0]["lr"],
             critic_lr=self.value_optimizer.param_groups[0]["lr"], allow_linear=False)
