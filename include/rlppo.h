@@ -140,7 +140,11 @@ int64_t rlppo_packed_floats(const int32_t *dims, int32_t n_layers);
 int64_t rlppo_flat_floats(const int32_t *dims, int32_t n_layers);
 
 /* Build the packed copy (padded W, W^T, b per layer) from the flat arena.  Called after every optimiser step.
- * Replaces nothing in the reference (it is the price of tile-aligned kernels). */
+ * Replaces nothing in the reference (it is the price of tile-aligned kernels).  The image, layer after layer with
+ * Pin_0 = rlppo_padded_width(dims[0]), Pin_l = Pout_(l-1), Pout_l = rlppo_padded_out(dims[l+1]):
+ *     W[Pout][Pin] | W^T[Pin][Pout] | b[Pout],   zero wherever no parameter lands.
+ * The call writes EVERY one of the rlppo_packed_floats entries, the zero padding included: `packed` needs no
+ * initialisation (rlppo_clip_adam_pack2, which rewrites the parameters' slots only, relies on an image built here). */
 int rlppo_net_pack(void *stream, const int32_t *dims, int32_t n_layers, const float *flat, float *packed);
 
 /* Copy/convert observation rows into the padded device layout: dst[r][0:d] = (float)src[r][0:d], zero fill to
@@ -433,7 +437,11 @@ typedef struct rlppo_minibatch_args {
                                      V + A and A), v_pred = v_old + clamp(v - v_old, -c, c), loss (v_pred - target)^2; 0 = off */
     double *kl_slots;             /* this pass's region of rlppo_kl_slots_doubles(mb) doubles: [0] <- workgroups of the policy loss
                                      launch, [1] <- mb_ratio, [2 + w] <- workgroup w's sum of the RLPPO_STAT_KL term (read by
-                                     rlppo_kl_gate); NULL = not armed */
+                                     rlppo_kl_gate); NULL = not armed.  Slot 2 + w holds THE double workgroup w adds to
+                                     stats[RLPPO_STAT_KL] (its rows' ((ratio - 1) - log ratio) / mb, NOT weighted by mb_ratio), so
+                                     the pass's increment of stats[RLPPO_STAT_KL] equals the sum of slots [2, 2 + [0]) up to the order
+                                     of the double additions; nothing behind slot 2 + [0] is written; a set stop_word keeps the
+                                     pass out of `stats` but not out of the slots */
     const uint32_t *stop_word;    /* device; once non-zero, the pass adds nothing to `stats`; NULL = never */
     /* [ABI 8] invalid-action masking: the discrete head, and the multi-discrete head through rlppo_ppo_minibatch_nvec with md_nvec
      * given (one bit per logit, mask_words == ceil(sum(md_nvec) / 32), in every pass form and update precision: "[nvec, masked]"
