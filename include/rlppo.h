@@ -954,7 +954,10 @@ const int64_t *rlppo_selection_epoch_ptr(void);   /* the counter itself (a host 
  * served by the one-launch kernel (rlppo_discrete_act / rlppo_discrete_step), 1 = by the layer chain, 2 = rlppo_ppo_minibatch passes,
  * 3 = of them with paired policy + critic launches, 4 = of them with the gather fused into the first layer, 5 = of them with the
  * grouped weight-gradient launch, 6 = [nvec] launches of the multi-discrete head's general (any nvec) kernels, sampling and loss,
- * 7 = rlppo_rollout_record launches (the device-resident collect form of the vector manager ran); -1 for an unknown key. */
+ * 7 = rlppo_rollout_record launches (the device-resident collect form of the vector manager ran); launches by the kernel form the
+ * launcher selected: 8 = rlppo_dbg_gemm_nt / layer-chain fp32 NT products by the few-row kernel, 9 = by the 128-row-tile kernel, 10 = bf16 hidden / dX product on
+ * 256 x 256 tiles with one workgroup per tile, 11 = with persistent workgroups, 12 = split-bf16 product with persistent workgroups,
+ * 13 = the one-output head's dW through fixed-order partials (not atomics); -1 for an unknown key. */
 int64_t rlppo_dbg_counter(int32_t key);
 /* Debug helper, like rlppo_dbg_counter: adds delta to counter `key` (6 only; anything else RLPPO_ERR_ARG).  The launchers count when
  * they are CALLED; a host that captures a call into a graph and replays it (rlgym_ppo_amd/ppo/_mlp.py::ActGraph, the masked
@@ -983,17 +986,38 @@ int rlppo_dbg_gemm_nt_b16(void *stream, const void *A, int64_t lda, const void *
 /* hidden == 2 is the backward product of that precision: Cb[M][N] (bf16) = round_bf16(A . W^T) masked by the ReLU bitmask `bits`
  * the hidden forward of the same M x N geometry wrote (epilogue 3, bias and C NULL; N % 128 == 0, K % 64 == 0).
  * rlppo_dbg_gemm_tn_b16: the weight-gradient product of that precision, dW[out][in] += dY^T . X, db[out] += colsum(dY), both
- * operands bf16 [M][ld] with pout / pin (multiples of 128) columns of which out / in are meaningful; workspace as rlppo_dbg_gemm_tn. */
+ * operands bf16 [M][ld] with pout / pin (multiples of 128) columns of which out / in are meaningful (the others are read and may hold any
+ * finite values, as the padded columns of rlppo_dbg_gemm_tn; nothing beyond pout / pin is read); workspace as rlppo_dbg_gemm_tn. */
 int rlppo_dbg_gemm_tn_b16(void *stream, const void *dY, int64_t ldy, const void *X, int64_t ldx, float *dW, float *db, int32_t pout,
                           int32_t pin, int32_t out, int32_t in, int64_t M, void *ws, size_t ws_bytes);
 /* The output layer's two backward products in the bf16 update precision for a head of out <= 32 outputs (gemv.hip): dY[M][ldy]
  * fp32 (the loss gradient), W[out][ldw] fp32 (bf16-rounded values), hb[M][ldh] the last hidden activation as bf16, bits its ReLU
  * bitmask (rlppo_dbg_gemm_nt_bits_bytes(M, kp)): dxb[M][kp] (bf16) = round_bf16(dY . W) masked; dW[out][in] += dY^T . hb,
- * db[out] += colsum(dY) with a fixed summation order.  kp: padded hidden width, a power of two and a multiple of 128. */
+ * db[out] += colsum(dY) with a fixed summation order.  kp: padded hidden width, a power of two and a multiple of 128.  dY is read over
+ * its first max(4, po) columns, po = out rounded up to 1, 8, 16, 24 or 32 (ldy >= that, a multiple of 4): the columns from `out` on may
+ * hold any finite values (a pass leaves zeros), they reach no output; W is read over its first `out` rows and all kp columns, hb over kp
+ * columns; nothing outside dxb[M][kp], dW[out][in], db[out] and the stated workspace is written. */
 size_t rlppo_dbg_thin_head_workspace_bytes(int32_t out, int32_t kp, int64_t M);
 int rlppo_dbg_thin_head_b16(void *stream, const float *dY, int64_t ldy, int32_t out, const float *W, int64_t ldw, const void *bits,
                             const void *hb, int64_t ldh, void *dxb, float *dW, float *db, int32_t in, int32_t kp, int64_t M, void *ws,
                             size_t ws_bytes);
+/* The fp32 one-output (critic) head's matrix-vector kernels (csrc/gemv.hip), one at a time (tests): kp, the padded hidden width, a
+ * power of two in 32 .. 1024; every row stride but ldy of the backward calls a multiple of 4 floats; x, w, mask, y and dx 16-byte aligned.
+ * rlppo_dbg_gemv_fwd: y[m][0] = b[0] + sum_k x[m][k] w[k] over ALL kp columns, y[m][1 .. pout - 1] = 0 (the layout's padded outputs;
+ * pout a multiple of 4, at most 64; nothing beyond column pout - 1 is written).
+ * rlppo_dbg_gemv_dx: dx[m][k] = dy[m][0] w[k] where the hidden unit was on, 0 where it was off, for all kp columns -- by the ReLU
+ * bitmask `bits` of the M x kp geometry (rlppo_dbg_gemm_nt_bits_bytes; kp % 128 == 0) when bits != NULL, else by mask[m][k] > 0 (the
+ * saved activation, row stride ldm).
+ * rlppo_dbg_gemv_dw: dw[k] += sum_m dy[m][0] x[m][k] for k < in, db[0] += sum_m dy[m][0] (db may be NULL); x is read over all kp
+ * columns.  With ws_bytes >= rlppo_dbg_gemv_dw_workspace_bytes the blocks' partial sums meet in a fixed order (what a pass runs:
+ * bit-reproducible), with less (or ws == NULL) they are added atomically. */
+int rlppo_dbg_gemv_fwd(void *stream, const float *x, int64_t ldx, const float *w, const float *b, float *y, int64_t ldy, int64_t M,
+                       int32_t kp, int32_t pout);
+int rlppo_dbg_gemv_dx(void *stream, const float *dy, int64_t ldy, const float *w, const float *mask, int64_t ldm, const void *bits,
+                      float *dx, int64_t ldc, int32_t kp, int64_t M);
+size_t rlppo_dbg_gemv_dw_workspace_bytes(int32_t kp, int64_t M);
+int rlppo_dbg_gemv_dw(void *stream, const float *dy, int64_t ldy, const float *x, int64_t ldx, float *dw, float *db, int32_t in,
+                      int32_t kp, int64_t M, void *ws, size_t ws_bytes);
 /* [diag] The diagonal-Gaussian head's loss step on its own, on caller-supplied head outputs y[mb][ld] (the means; overwritten with
  * dL/dmean), actions[mb][k], old_logp / advantages[mb] -- contiguous rows, as a pass has gathered them: part 0 = the loss launch and
  * the fixed-order finish of the log_std reduction (what a pass runs), 1 = the loss launch alone (partial sums into scratch), 2 = the
@@ -1002,7 +1026,13 @@ int rlppo_dbg_diag_loss(void *stream, float *y, int64_t ld, int32_t k, const flo
                         int64_t mb, float clip_range, float ent_coef, float mb_ratio, const float *log_std, float *log_std_grad, void *scratch,
                         size_t scratch_bytes, double *stats, int32_t part);
 /* dW[out][in] += dY^T . X, db[out] += colsum(dY) through partial tiles in `ws` (rlppo_dbg_gemm_tn_workspace_bytes) and a
- * fixed-order reduction: the form rlppo_ppo_minibatch uses. */
+ * fixed-order reduction: the form rlppo_ppo_minibatch uses.  dY[M][ldy] is read over its first ny_valid columns and X[M][ldx] over its
+ * first kx_valid (multiples of 4, out <= ny_valid <= ldy, in <= kx_valid <= ldx); nothing beyond them is read.  The padded columns
+ * out .. ny_valid - 1 of dY and in .. kx_valid - 1 of X may hold ANY FINITE values (a pass leaves zeros there): they are multiplied,
+ * but their products land in partial-tile elements the reduction drops and reach no element of dW or db.  dW is the contiguous
+ * out x in block of the flat gradient arena (4-byte aligned); nothing outside dW, db and the first
+ * rlppo_dbg_gemm_tn_workspace_bytes of ws is written.  The same holds per product of rlppo_dbg_gemm_tn_group, for the rows a row
+ * table names. */
 size_t rlppo_dbg_gemm_tn_workspace_bytes(int32_t out, int32_t in, int64_t M);
 int rlppo_dbg_gemm_tn(void *stream, const float *dY, int64_t ldy, int32_t ny_valid, const float *X, int64_t ldx,
                       int32_t kx_valid, float *dW, float *db, int32_t out, int32_t in, int64_t M, void *ws, size_t ws_bytes);

@@ -264,6 +264,11 @@ SIGNATURES = {
     "rlppo_dbg_thin_head_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int64]),
     "rlppo_dbg_thin_head_b16": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                           c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_size_t]),
+    "rlppo_dbg_gemv_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32]),
+    "rlppo_dbg_gemv_dx": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int64]),
+    "rlppo_dbg_gemv_dw_workspace_bytes": (c_size_t, [c_int32, c_int64]),
+    "rlppo_dbg_gemv_dw": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p,
+                                    c_size_t]),
     "rlppo_dbg_diag_loss": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_void_p,
                                       c_void_p, c_void_p, c_size_t, c_void_p, c_int32]),
     "rlppo_dbg_gemm_tn_group_workspace_bytes": (c_size_t, [POINTER(TnProduct), c_int32, c_int64]),

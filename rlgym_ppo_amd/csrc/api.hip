@@ -1882,6 +1882,7 @@ int64_t rlppo_dbg_counter(int32_t key) {
         case 5: return g_cnt_group_dw;
         case 6: return g_cnt_md_nvec;
         case 7: return rollout_record_count();
+        case 8: case 9: case 10: case 11: case 12: case 13: return g_form_launches[key - 8];
         default: return -1;
     }
 }
@@ -1924,6 +1925,30 @@ int rlppo_dbg_thin_head_b16(void *stream, const float *dY, int64_t ldy, int32_t 
     rc = launch_thin_dw_b16((hipStream_t)stream, dY, ldy, reinterpret_cast<const unsigned short *>(hb), ldh, dW, db, out, in, kp, M,
                             (float *)ws, ws_bytes / sizeof(float));
     return rc == -1 ? RLPPO_ERR_ARG : rc;
+}
+// the fp32 one-output head's matrix-vector kernels, one at a time (tests)
+static bool gemv_dbg_ok(int32_t kp, int64_t M) { return gemv_head_ok(1, kp) && M >= 0; }
+int rlppo_dbg_gemv_fwd(void *stream, const float *x, int64_t ldx, const float *w, const float *b, float *y, int64_t ldy, int64_t M,
+                       int32_t kp, int32_t pout) {
+    RLPPO_CHECK_ARG(gemv_dbg_ok(kp, M) && x && w && b && y && ldx >= kp && ldx % 4 == 0 && pout >= 4 && pout <= 64 && pout % 4 == 0 &&
+                        ldy >= pout && ldy % 4 == 0,
+                    "dbg_gemv_fwd: kp=%d pout=%d ldx=%ld ldy=%ld", kp, pout, (long)ldx, (long)ldy);
+    return launch_gemv_fwd((hipStream_t)stream, x, ldx, w, b, y, ldy, M, kp, pout);
+}
+int rlppo_dbg_gemv_dx(void *stream, const float *dy, int64_t ldy, const float *w, const float *mask, int64_t ldm, const void *bits,
+                      float *dx, int64_t ldc, int32_t kp, int64_t M) {
+    RLPPO_CHECK_ARG(gemv_dbg_ok(kp, M) && dy && w && dx && ldy >= 1 && ldc >= kp && ldc % 4 == 0 &&
+                        (bits ? kp % 128 == 0 : (mask && ldm >= kp && ldm % 4 == 0)),
+                    "dbg_gemv_dx: kp=%d ldy=%ld ldm=%ld ldc=%ld", kp, (long)ldy, (long)ldm, (long)ldc);
+    if (bits) return launch_gemv_dx_bits((hipStream_t)stream, dy, ldy, w, reinterpret_cast<const unsigned long long *>(bits), dx, ldc, kp, M);
+    return launch_gemv_dx((hipStream_t)stream, dy, ldy, w, mask, ldm, dx, ldc, kp, M, ACT_RELU);
+}
+size_t rlppo_dbg_gemv_dw_workspace_bytes(int32_t kp, int64_t M) { return gemv_dw_ws_floats(kp, M) * sizeof(float); }
+int rlppo_dbg_gemv_dw(void *stream, const float *dy, int64_t ldy, const float *x, int64_t ldx, float *dw, float *db, int32_t in,
+                      int32_t kp, int64_t M, void *ws, size_t ws_bytes) {
+    RLPPO_CHECK_ARG(gemv_dbg_ok(kp, M) && dy && x && dw && ldy >= 1 && ldx >= kp && ldx % 4 == 0 && in >= 1 && in <= kp,
+                    "dbg_gemv_dw: kp=%d in=%d ldy=%ld ldx=%ld", kp, in, (long)ldy, (long)ldx);
+    return launch_gemv_dw((hipStream_t)stream, dy, ldy, x, ldx, dw, db, in, kp, M, (float *)ws, ws_bytes / sizeof(float));
 }
 static int tn_products(const rlppo_tn_product *p, int32_t n, TnProduct *q) {
     RLPPO_CHECK_ARG(p && n > 0 && n <= 2 * RLPPO_MAX_LAYERS, "gemm_tn_group: %d products (1..%d)", n, 2 * RLPPO_MAX_LAYERS);

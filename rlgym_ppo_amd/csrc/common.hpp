@@ -202,6 +202,7 @@ int launch_gemv_fwd_b16(hipStream_t st, const unsigned short *x, int64_t ldx, co
 // narrow heads (<= 32 outputs) of the bf16 update precision: bf16 activation in, bf16 gradient out (gemv.hip)
 bool thin_head_ok(int out, int kp);
 size_t thin_dw_ws_floats(int out, int kp, int64_t n);
+size_t gemv_dw_ws_floats(int kp, int64_t n);  // the block partials of launch_gemv_dw's fixed-order form
 int launch_thin_dx_b16(hipStream_t st, const float *dy, int64_t ldy, int out, const float *w, int64_t ldw,
                        const unsigned long long *bits, unsigned short *dxb, int64_t ldc, int kp, int64_t n);
 int launch_thin_dw_b16(hipStream_t st, const float *dy, int64_t ldy, const unsigned short *xb, int64_t ldx, float *dw, float *db,
@@ -365,6 +366,10 @@ int launch_pad_rows_vec(hipStream_t, const void *, int, int64_t, int64_t, int64_
 int launch_rollout_record(hipStream_t st, const void *rewards, int r_dt, const void *dones, int d_dt, const void *truncated, int t_dt,
                           int64_t n, int64_t t, int64_t T, float *rdt, double *ep_sums, void *state, float *patch);
 long long rollout_record_count();   // rlppo_dbg_counter(7)
+// launches by kernel form, counted where the launcher selects it (rlppo_dbg_counter(8 + form)): tests that mean to pin one form
+// assert that it is the one that ran
+enum LaunchForm { FORM_NT_FEW_ROWS = 0, FORM_NT_TILED, FORM_B16_WIDE, FORM_B16_PERSISTENT, FORM_X3_PERSISTENT, FORM_GEMV_DW_ORDERED, FORM_COUNT };
+extern long long g_form_launches[FORM_COUNT];
 int launch_obs_scalars(hipStream_t st, const void *mean, const void *m2, int state_f64, long long count, int d, int per_feature,
                        float *mean_v, float *std_v);
 int launch_to_trajectory_major(hipStream_t st, const float *S, const float *acts, const float *logp, const float *rdt, int64_t n, int64_t T,

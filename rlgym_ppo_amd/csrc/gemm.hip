@@ -369,6 +369,7 @@ constexpr int SK_AHEAD = 8;          // K-tiles of 16 in flight per operand
 constexpr int64_t SK_MAX_ROWS = 1024;  // beyond that the 128-row tiles fill the chip as well, at half the operand traffic
 int g_nt_skinny = 1;                 // rlppo_dbg_set(40, 0/1)
 }  // namespace
+long long g_form_launches[FORM_COUNT] = {};  // rlppo_dbg_counter(8 ..)
 void set_nt_skinny(int on) { g_nt_skinny = on; }
 
 template <int EPI>
@@ -552,7 +553,11 @@ int launch_gemm_nt(hipStream_t st, const float *A, int64_t lda, const float *B, 
     // (the bf16-operand inference kernel steps K by 32: a layer whose K is only a multiple of 16 -- a first layer padded to 16 --
     // keeps the fp32 kernel, i.e. is computed MORE precisely than the mode asks)
     if (bf16_operands && !by_act && K % 32 == 0) return launch_gemm_nt_bf16(st, A, lda, B, ldb, bias, C, ldc, M, N, nb, K, epi);
-    if (g_nt_skinny && M <= SK_MAX_ROWS && !by_act && !bf16_operands) return launch_gemm_nt_skinny(st, A, lda, B, ldb, bias, C, ldc, M, N, K, epi);
+    if (g_nt_skinny && M <= SK_MAX_ROWS && !by_act && !bf16_operands) {
+        ++g_form_launches[FORM_NT_FEW_ROWS];
+        return launch_gemm_nt_skinny(st, A, lda, B, ldb, bias, C, ldc, M, N, K, epi);
+    }
+    ++g_form_launches[FORM_NT_TILED];
     dim3 grid((unsigned)cdiv(M, SBM), (unsigned)(N / (nb * 16)));
     const unsigned la = (unsigned)(lda * 4), lb = (unsigned)(ldb * 4), lc = (unsigned)(ldc * 4), lm = (unsigned)(ld_mask * 4);
     switch (nb) {

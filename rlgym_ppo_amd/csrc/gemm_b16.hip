@@ -697,6 +697,7 @@ int launch_gemm_nt_b16(hipStream_t st, const unsigned short *A, int64_t lda, con
             else B16P(B16_HIDDEN);
 #undef B16P
             RLPPO_LAUNCH_CHECK();
+            ++g_form_launches[FORM_B16_PERSISTENT];
             return 0;
         }
 #define B16W(MODE_)                                                                                                          \
@@ -710,6 +711,7 @@ int launch_gemm_nt_b16(hipStream_t st, const unsigned short *A, int64_t lda, con
         else B16W(B16_HIDDEN);
 #undef B16W
         RLPPO_LAUNCH_CHECK();
+        ++g_form_launches[FORM_B16_WIDE];
         return 0;
     }
     const int nb = N % 128 == 0 ? 8 : N / 16;

@@ -562,6 +562,7 @@ int launch_gemm_nt_split(hipStream_t st, const float *A, int64_t lda, const unsi
     if (int rc_ = device_cu_count(&cus)) return rc_;
     if (g_split_persistent && (K / 32) % 2 == 0 && row_tiles >= 2 * (cus / (8 * col_tiles) > 0 ? cus / (8 * col_tiles) : 1) * 8 && col_tiles <= 8) {
         // persistent workgroups: whole groups of 8 row tiles x all column tiles, never more workgroups than CUs (or than the work)
+        ++g_form_launches[FORM_X3_PERSISTENT];
         const int group = 8 * col_tiles;
         int grid = cus / group * group;
         const int need = (int)cdiv(row_tiles, 8) * group;

@@ -412,13 +412,16 @@ int launch_gemv_dx_bits(hipStream_t st, const float *dy, int64_t ldy, const floa
     return 0;
 }
 
+// 1024 blocks at M = 65,536: enough loads in flight to stream h at HBM rate; larger M keeps about 2048 blocks
+static int gemv_dw_rows_per_block(int64_t n) { return n > 131072 ? (int)round_up(cdiv(n, 2048), 64) : 64; }
+size_t gemv_dw_ws_floats(int kp, int64_t n) { return n > 0 && kp > 0 ? (size_t)cdiv(n, gemv_dw_rows_per_block(n)) * (size_t)(kp + 4) : 0; }
 int launch_gemv_dw(hipStream_t st, const float *dy, int64_t ldy, const float *x, int64_t ldx, float *dw, float *db, int in,
                    int kp, int64_t n, float *ws, size_t ws_floats) {
     if (n <= 0) return 0;
-    // 1024 blocks at M = 65,536: enough loads in flight to stream h at HBM rate; larger M keeps about 2048 blocks
-    const int rows_per_block = n > 131072 ? (int)round_up(cdiv(n, 2048), 64) : 64;
+    const int rows_per_block = gemv_dw_rows_per_block(n);
     const int blocks = (int)cdiv(n, rows_per_block);
-    float *part = (ws && ws_floats >= (size_t)blocks * (kp + 4)) ? ws : nullptr;
+    float *part = (ws && ws_floats >= gemv_dw_ws_floats(kp, n)) ? ws : nullptr;
+    if (part) ++g_form_launches[FORM_GEMV_DW_ORDERED];
     hipLaunchKernelGGL(gemv_dw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dy, ldy, x, ldx, dw, db, in, kp / 4, n,
                        rows_per_block, part);
     RLPPO_LAUNCH_CHECK();

@@ -28,6 +28,15 @@ def test_every_declared_symbol_is_exported_and_bound():
         assert name in N.SIGNATURES, f"{name} has no ctypes signature in rlgym_ppo_amd/_native.py"
     assert sorted(N.SIGNATURES) == names, "ctypes table and header disagree"
     assert L.rlppo_abi_version() == N.ABI_VERSION
+    # the one-output head's single-kernel entry points (tests/test_gpu_products.py): an addition to ABI 8, pinned argument by argument
+    c, V, I64, I32 = ctypes, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    assert N.SIGNATURES["rlppo_dbg_gemv_fwd"] == (I32, [V, V, I64, V, V, V, I64, I64, I32, I32])
+    assert N.SIGNATURES["rlppo_dbg_gemv_dx"] == (I32, [V, V, I64, V, V, I64, V, V, I64, I32, I64])
+    assert N.SIGNATURES["rlppo_dbg_gemv_dw_workspace_bytes"] == (c.c_size_t, [I32, I64])
+    assert N.SIGNATURES["rlppo_dbg_gemv_dw"] == (I32, [V, V, I64, V, I64, V, V, I32, I32, I64, V, c.c_size_t])
+    assert L.rlppo_dbg_gemv_dw_workspace_bytes(256, 257) == 5 * 260 * 4 and L.rlppo_dbg_gemv_dw_workspace_bytes(64, 0) == 0
+    # the launch-form counters 8 .. 13 (which kernel a launcher selected): nothing has launched here, and 14 is no key
+    assert [L.rlppo_dbg_counter(k) for k in range(8, 15)] == [0] * 6 + [-1]
 
 
 def test_layout_queries_host_only():
