@@ -230,7 +230,15 @@ __host__ __device__ __forceinline__ int64_t ring_row(int64_t i, int64_t base, in
     const int64_t r = i + base;
     return r >= cap ? r - cap : r;
 }
+// ring-resident experience: ring_cap == 0 means "not a ring" (logical row == physical row)
+inline int ring_window(const char *who, int64_t ring_base, int64_t ring_cap, int64_t *base, int64_t *cap) {
+    *cap = ring_cap > 0 ? ring_cap : INT64_MAX;
+    *base = ring_cap > 0 ? ring_base : 0;
+    RLPPO_CHECK_ARG(*base >= 0 && *base < *cap, "%s: ring_base=%ld not in [0, ring_cap=%ld)", who, (long)ring_base, (long)ring_cap);
+    return 0;
+}
 // [ABI 8] action masks: mask (optional) = [n][mask_words] words, bit c % 32 of word c / 32 set = action c valid
+int mask_words_check(const void *mask, int mask_words, int bits, const char *who, bool logits);  // api.hip
 int launch_discrete_sample_logits(hipStream_t, const float *, int64_t, int64_t, int, const float *, int64_t *, float *, float *,
                                   const unsigned *mask = nullptr, int mask_words = 0);
 int launch_discrete_probs(hipStream_t st, const float *logits, int64_t ld, int64_t n, int A, int clamp, float *probs,
@@ -370,6 +378,13 @@ long long rollout_record_count();   // rlppo_dbg_counter(7)
 // assert that it is the one that ran
 enum LaunchForm { FORM_NT_FEW_ROWS = 0, FORM_NT_TILED, FORM_B16_WIDE, FORM_B16_PERSISTENT, FORM_X3_PERSISTENT, FORM_GEMV_DW_ORDERED, FORM_COUNT };
 extern long long g_form_launches[FORM_COUNT];
+// rlppo_dbg_counter(0 .. 6): which form a call took, counted where the call selects it (api.hip, update.hip)
+enum CallCount { CNT_FUSED_ACT = 0, CNT_ACT_CHAIN, CNT_PASS, CNT_PAIRED_PASS, CNT_GATHER_FUSED_PASS, CNT_GROUP_DW, CNT_MD_NVEC, CNT_COUNT };
+extern std::atomic<long long> g_call_counts[CNT_COUNT];
+// update.hip: the switches of the PPO pass (rlppo_dbg_set 4 / 19 / 26 / 29 / 31 / 37, rlppo_set_update_precision)
+void set_two_streams(int v), set_relu_bits(int v), set_fused_gather(int v), set_paired(int v), set_head_order(int v), set_group_dw(int v);
+void set_update_precision(int v);
+int get_update_precision();
 int launch_obs_scalars(hipStream_t st, const void *mean, const void *m2, int state_f64, long long count, int d, int per_feature,
                        float *mean_v, float *std_v);
 int launch_to_trajectory_major(hipStream_t st, const float *S, const float *acts, const float *logp, const float *rdt, int64_t n, int64_t T,

@@ -136,7 +136,7 @@ def g5big_inputs(cfg):
 
 def g5big_learn(R):
     """G5big [r4]: PPOLearner.learn (ppo_learner.py:92-238) at the size where the product's paired / gather-fused launches engage
-    (csrc/api.hip: from 262,144 rows per pass): 256x3 nets, n = B = 262,144, MB = 65,536, 2 epochs = 2 optimiser steps of 4
+    (csrc/update.hip: from 262,144 rows per pass): 256x3 nets, n = B = 262,144, MB = 65,536, 2 epochs = 2 optimiser steps of 4
     minibatches.  The inputs come from seeds (g5big_inputs: a test rebuilds them); stored: an exact bit hash + the first 64 values
     of the initial parameters, every 8th entry + norms of the first step's batch gradient (before clipping), the first 64 values +
     plain sums of the parameters after step 0, the FULL parameter vectors after the last step, the report.  ~2 minutes on one thread."""

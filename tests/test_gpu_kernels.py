@@ -1252,7 +1252,7 @@ def test_minibatch_gather_and_accumulate_cfg2_shape(L):
 def test_fused_gather_and_paired_launches_are_bitwise_neutral(L):
     """[r3] The first layer's four launches fetch their rows straight from the experience arrays through the row table (the
     minibatch gather fused into the GEMMs' load stage), and policy and critic layers of equal widths run as ONE launch
-    (csrc/api.hip, paired pass).  Neither changes a product or the order of a sum: gradients must be BIT-identical to the separate
+    (csrc/update.hip, paired pass).  Neither changes a product or the order of a sum: gradients must be BIT-identical to the separate
     gather pass (rlppo_dbg_set(26, 0)) and to one launch chain per network (rlppo_dbg_set(29, 0)), on a ragged minibatch (1500
     rows: a partial row tile, a partial dW stage) drawn at random, with repeats, from a 5000-row buffer."""
     rs = np.random.RandomState(21)

@@ -116,7 +116,7 @@ def test_learn_at_the_paired_launch_size_matches_the_reference_fixture(golden, p
     """(precision "x3": the same fixture and the same gates with rlppo_set_update_precision(2) -- the hidden forward / dX products
     on the bf16 MFMA pipe from three-piece operands, policy and critic as two chains)
     [r4] G5big: the reference's PPOLearner.learn at 256x3, n = B = 262,144, MB = 65,536, 2 epochs -- the size from which the update
-    runs its PAIRED policy + critic launches with the minibatch gather FUSED into the first layer (csrc/api.hip), which until
+    runs its PAIRED policy + critic launches with the minibatch gather FUSED into the first layer (csrc/update.hip), which until
     round 4 no reference-held vector ever reached.  The experience is rebuilt from seeds by the generator's own function (its bit
     hashes are in the fixture), the seeded construction must give the reference's initial parameters bit for bit (hash + first 64
     values), a library counter says which launch form ran, and the parameters after both optimiser steps go through the same
