@@ -519,6 +519,27 @@ typedef struct rlppo_minibatch_ext {
 } rlppo_minibatch_ext;
 int rlppo_ppo_minibatch_ex(void *stream, const rlppo_minibatch_args *args, const rlppo_minibatch_ext *ext);
 
+/* [critic rows] The same pass with a critic that reads a row matrix of its own (asymmetric actor-critic: "privileged observations";
+ * an added entry point: the structs and the ABI version stay as they are).  critic->states: DEVICE, 16-byte aligned, [N][ld_states]
+ * padded rows -- a buffer field like args->states over the SAME physical rows: row idx[r] through the same ring map, with args->n_rows,
+ * ring_base and ring_cap.  critic == NULL or critic->states == NULL is exactly rlppo_ppo_minibatch_ex(stream, args, ext).  Otherwise
+ * val_dims[0] is the width of the critic's matrix and may differ from pol_dims[0]; critic->ld_states >= rlppo_padded_width(val_dims[0]),
+ * a multiple of 4; columns val_dims[0] .. padded width of every row must be zero, as for args->states.  The workspace is
+ * rlppo_minibatch_workspace_bytes_critic (the plan of rlppo_minibatch_workspace_bytes_for + the critic's gathered rows,
+ * [mb][padded width of val_dims[0]]); one sized by the other functions is RLPPO_ERR_WORKSPACE.  Every head, mask, hidden activation,
+ * slot, ring and n_rows == 0 works as in rlppo_ppo_minibatch_ex, and so do update precisions fp32 and x3; bf16 is RLPPO_ERR_ARG (its
+ * gather writes one bf16 image, of the policy's rows).  The pass starts with ONE gather launch for both matrices, or -- gather-fused
+ * form, decided as before on both networks' first layers, the critic's on its own ld -- both first layers read through the one row
+ * table, each from its own matrix.  It never takes paired launches (a paired layer 0 shares one A operand).  Every argument error
+ * is reported before the first HIP call.  rlppo_dbg_counter(15) counts these passes. */
+typedef struct rlppo_critic_rows {
+    const float *states;
+    int64_t ld_states;
+} rlppo_critic_rows;
+size_t rlppo_minibatch_workspace_bytes_critic(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
+                                              int64_t mb, int32_t precision);
+int rlppo_ppo_minibatch_critic(void *stream, const rlppo_minibatch_args *args, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic);
+
 /* Orders `stream` after every minibatch enqueued through non-zero slots since the last join (call it before the
  * gradient all-reduce / rlppo_clip_adam).  Independent minibatches of one batch only meet in the gradient arena
  * (one add per element and launch), so they may overlap; each launch is short (50-100 us at 65,536 rows), and overlapping
@@ -808,6 +829,29 @@ int rlppo_torch_cpu_exponential_burst(const void *state, void *link_in0, int64_t
  * step-major -> trajectory-major flatten of a device-resident rollout (batched_agent_manager.py:154-172 builds the same
  * order with Python lists). */
 int rlppo_gather_rows(void *stream, const float *src, int64_t ld_src, const int64_t *idx, float *dst, int32_t width, int64_t n);
+/* [critic rows] The gather launch of a pass with separate critic rows, on its own: for r < n, with s = the physical row of idx[r]
+ * (ring_cap == 0: s = idx[r]; else (idx[r] + ring_base) mod ring_cap), dst[r][0..width) = src[s][0..width) and
+ * critic_dst[r][0..critic_width) = critic_src[s][0..critic_width) in ONE launch (16 bytes per thread; widths and lds multiples of
+ * 4, the four matrices 16-byte aligned, dst rows `width` / `critic_width` floats apart).  The per-row scalars ride along when given
+ * (all of them or none): g_old[r] = old_logp[s], g_adv[r] = advantages[s], g_tgt[r] = targets[s], g_act[r][0..act_dim) =
+ * actions[s][0..act_dim), and zero_n[r] = 0 when zero_n is given. */
+typedef struct rlppo_gather2_args {
+    const float *src;
+    int64_t ld_src;
+    float *dst;
+    int32_t width;
+    const float *critic_src;
+    int64_t critic_ld_src;
+    float *critic_dst;
+    int32_t critic_width;
+    const int64_t *idx;
+    int64_t n;
+    int64_t ring_base, ring_cap;
+    const float *actions, *old_logp, *advantages, *targets;
+    int32_t act_dim;
+    float *g_act, *g_old, *g_adv, *g_tgt, *zero_n;
+} rlppo_gather2_args;
+int rlppo_gather_rows2(void *stream, const rlppo_gather2_args *args);
 
 /* WelfordRunningStat.increment(samples, n) (running_stats.py:28-46) on the device, bit-exact with the reference's sample-by-
  * sample update: mean[d], m2[d] (= running_mean, running_variance) are updated in place with the n rows of `samples` (fp32,
@@ -957,7 +1001,8 @@ const int64_t *rlppo_selection_epoch_ptr(void);   /* the counter itself (a host 
  * 7 = rlppo_rollout_record launches (the device-resident collect form of the vector manager ran); launches by the kernel form the
  * launcher selected: 8 = rlppo_dbg_gemm_nt / layer-chain fp32 NT products by the few-row kernel, 9 = by the 128-row-tile kernel, 10 = bf16 hidden / dX product on
  * 256 x 256 tiles with one workgroup per tile, 11 = with persistent workgroups, 12 = split-bf16 product with persistent workgroups,
- * 13 = the one-output head's dW through fixed-order partials (not atomics); -1 for an unknown key. */
+ * 13 = the one-output head's dW through fixed-order partials (not atomics); 15 = [critic rows] rlppo_ppo_minibatch passes with separate
+ * critic rows (rlppo_ppo_minibatch_critic with a matrix); -1 for an unknown key (14 is none). */
 int64_t rlppo_dbg_counter(int32_t key);
 /* Debug helper, like rlppo_dbg_counter: adds delta to counter `key` (6 only; anything else RLPPO_ERR_ARG).  The launchers count when
  * they are CALLED; a host that captures a call into a graph and replays it (rlgym_ppo_amd/ppo/_mlp.py::ActGraph, the masked

@@ -30,6 +30,7 @@ HEAD_DIAG_GAUSSIAN = 3  # RLPPO_HEAD_DIAG_GAUSSIAN: learnable state-independent 
 DIAG_MAX_K = 256  # RLPPO_DIAG_MAX_K
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16, PRECISION_X3 = 0, 1, 2, 3  # rlppo_minibatch_args.precision (1 + mode)
 ACT_RELU, ACT_TANH, ACT_ELU = 0, 1, 2  # RLPPO_ACT_*: rlppo_act_opts.hidden_act, rlppo_minibatch_ext.{pol,val}_hidden_act
+COUNTER_CRITIC_ROWS_PASS = 15  # rlppo_dbg_counter key: passes with separate critic rows
 HIDDEN_ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "elu": ACT_ELU}
 
 
@@ -78,6 +79,20 @@ class MinibatchExt(ctypes.Structure):
     """struct rlppo_minibatch_ext (include/rlppo.h, "[act]")."""
     _fields_ = [("pol_hidden_act", c_int32), ("val_hidden_act", c_int32), ("md_nvec", POINTER(c_int32)), ("md_heads", c_int32),
                 ("log_std", c_void_p), ("log_std_grad", c_void_p), ("scratch", c_void_p), ("scratch_bytes", c_size_t)]
+
+
+class CriticRows(ctypes.Structure):
+    """struct rlppo_critic_rows (include/rlppo.h, "[critic rows]")."""
+    _fields_ = [("states", c_void_p), ("ld_states", c_int64)]
+
+
+class Gather2Args(ctypes.Structure):
+    """struct rlppo_gather2_args (include/rlppo.h, "[critic rows]")."""
+    _fields_ = [("src", c_void_p), ("ld_src", c_int64), ("dst", c_void_p), ("width", c_int32),
+                ("critic_src", c_void_p), ("critic_ld_src", c_int64), ("critic_dst", c_void_p), ("critic_width", c_int32),
+                ("idx", c_void_p), ("n", c_int64), ("ring_base", c_int64), ("ring_cap", c_int64),
+                ("actions", c_void_p), ("old_logp", c_void_p), ("advantages", c_void_p), ("targets", c_void_p), ("act_dim", c_int32),
+                ("g_act", c_void_p), ("g_old", c_void_p), ("g_adv", c_void_p), ("g_tgt", c_void_p), ("zero_n", c_void_p)]
 
 
 class ReportArgs(ctypes.Structure):
@@ -189,6 +204,8 @@ SIGNATURES = {
     "rlppo_diag_scratch_bytes": (c_size_t, [c_int64, c_int32]),
     "rlppo_ppo_minibatch_diag": (c_int32, [c_void_p, POINTER(MinibatchArgs), c_void_p, c_void_p, c_void_p, c_size_t]),
     "rlppo_ppo_minibatch_ex": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt)]),
+    "rlppo_minibatch_workspace_bytes_critic": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
+    "rlppo_ppo_minibatch_critic": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows)]),
     "rlppo_ppo_join": (c_int32, [c_void_p]),
     "rlppo_kl_slots_doubles": (c_int64, [c_int64]),
     "rlppo_adv_stats": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
@@ -231,6 +248,7 @@ SIGNATURES = {
     "rlppo_torch_cpu_exponential_burst": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p, c_int64,
                                                     c_int32, c_int32, c_int32, c_void_p]),
     "rlppo_gather_rows": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64]),
+    "rlppo_gather_rows2": (c_int32, [c_void_p, POINTER(Gather2Args)]),
     "rlppo_welford_increment": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32]),
     "rlppo_welford_merge": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32]),
     "rlppo_rollout_record": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p,

@@ -22,6 +22,12 @@ Optional (the sb3-contrib convention; discrete and multi-discrete policies): `ac
 observation the agents act on next ([n, sum(bins)] for a multi-discrete policy: one entry per bin of every component), called
 after `reset()` and after every `step()`; the policy then samples valid actions only and the masks leave the collect
 trajectory-major as `self.action_mask_rows` (next to `value_input_rows`).
+Optional, asked for with `critic_observations` (Learner(critic_observations=True)) only: `critic_observations() -> [n, d_c]`, the
+critic's own ("privileged") observation of the state the agents act on next, called after `reset()` and after every `step()` like
+`action_masks()` (a device environment answers a device tensor).  The rows are standardised by a second running statistic,
+`critic_obs_stats` (same cadence, same per-feature flag, first collect raw), staged with the critic's arena and leave the collect
+trajectory-major as `self.critic_value_input_rows`, [N + 1, ld_c] next to `value_input_rows`: what the value pass and the buffer's
+`critic_states` read.  The 7-tuple of `collect_timesteps` is what it was.
 Optional, used with `bootstrap_truncated` (Learner(gae_bootstrap_truncated=True)) only: `info["final_observation"]`, float
 [n, d], whose rows are meaningful where `truncated` is set and `done` is not -- the observation the episode ended on, which
 the auto-reset has replaced in `obs`.  Those rows are standardised like that step's `obs`, kept out of the running
@@ -172,6 +178,15 @@ class VectorAgentManager(object):
         self._book = None             # _DeviceBook: the device environment's persistent bookkeeping
         self.last_enqueue_seconds = None   # device environment: host seconds the last collect spent enqueuing, before its one read
         self.episodes_ended = 0       # device environment: episodes ended so far (read back with the average at the end of a collect)
+        # Learner(critic_observations=True): the critic's own observation rows (module docstring); off, a collect does what it did
+        self.critic_observations = False
+        self.value_net = None                  # the critic (its arena stages the rows); set by Learner once it exists
+        self.critic_obs_size = None            # d_c, from the environment's first answer
+        self.critic_obs_stats = None           # WelfordRunningStat(d_c), moved when obs_stats moves
+        self.critic_value_input_rows = None    # [N + 1, ld_c] device rows of the last collect, mirroring value_input_rows
+        self._critic_initial = None            # the answer after reset(): acted on RAW by the first collect
+        self._critic_next_rows = None          # [n_agents, ld_c] staged rows of the observation the agents act on next
+        self._cbook = None                     # _DeviceBook of critic_obs_stats (device environment)
 
     def _env_mask(self):
         """The environment's action_masks() for the observation the agents act on next, packed on the device; None without it."""
@@ -197,6 +212,73 @@ class VectorAgentManager(object):
         """bool [N, n_actions] of the last collect, trajectory-major; None when the environment has no action_masks()."""
         return None if self.action_mask_rows is None else self.action_mask_rows.unpack()
 
+    # --------------------------------------------------------------------------------------- critic observations
+    def _critic_answer(self, dev=None):
+        """The environment's critic_observations() for the observation the agents act on next: host interface -> float32 numpy
+        [n_agents, d_c]; device interface (dev given) -> float32 device tensor."""
+        x = self.env.critic_observations()
+        if dev is not None or self._env_device is not None:
+            if not (isinstance(x, torch.Tensor) and x.is_cuda):
+                raise ValueError("a device-resident vector environment answers device tensors: critic_observations() returned "
+                                 f"{type(x).__name__}" + (f" on {x.device}" if isinstance(x, torch.Tensor) else ""))
+            check_same_device(x.device, self._env_device if dev is None else dev)
+            x = x.detach().to(torch.float32)
+            x = x.reshape(1, -1) if x.dim() == 1 else x
+        else:
+            if isinstance(x, torch.Tensor) and x.is_cuda:
+                raise ValueError(f"the vector environment speaks the host interface but its critic_observations() returned a tensor on {x.device}")
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+            x = x.reshape(1, -1) if x.ndim == 1 else x
+        if len(x.shape) != 2 or x.shape[0] != self.n_agents or (self.critic_obs_size is not None and x.shape[1] != self.critic_obs_size):
+            raise ValueError(f"the environment's critic_observations() has shape {tuple(x.shape)}: expected [{self.n_agents}, "
+                             f"{self.critic_obs_size if self.critic_obs_size is not None else 'd_c'}]")
+        return x.contiguous() if isinstance(x, torch.Tensor) else x
+
+    def _critic_init(self):
+        """init_processes: the answer after reset() gives d_c, enters critic_obs_stats and is acted on RAW (as the observations)."""
+        if not self.critic_observations:
+            return
+        if not hasattr(self.env, "critic_observations"):
+            raise ValueError("critic_observations=True needs a vector environment with a critic_observations() method")
+        x = self._critic_answer()
+        self.critic_obs_size = int(x.shape[1])
+        self.critic_obs_stats = None
+        if isinstance(x, torch.Tensor):
+            x = x.clone()   # (the environment may reuse its tensor at its first step)
+        if self.standardize_obs:
+            self.critic_obs_stats = WelfordRunningStat(shape=self.critic_obs_size)
+            if isinstance(x, torch.Tensor):
+                from ..util import device_stats
+                device_stats.increment(self.critic_obs_stats, x)
+            else:
+                self.critic_obs_stats.increment(x, x.shape[0])
+        self._critic_initial = x
+
+    def _critic_begin(self, T, dev):
+        """Collect start -> CS [T + 1, n_agents, ld_c], time-major like S, CS[0] = the rows the agents act on now; None when off."""
+        if not self.critic_observations:
+            return None
+        if self.value_net is None:
+            raise ValueError("critic_observations: the manager needs the critic (value_net) whose arena stages the rows")
+        arena = self.value_net.arena
+        CS = torch.empty((T + 1, self.n_agents, arena.ld_in), dtype=torch.float32, device=dev)
+        if self._critic_next_rows is None:   # first collect: the reset answer, RAW
+            arena.stage_obs(self._critic_initial, None, out=CS[0])
+        else:
+            CS[0].copy_(self._critic_next_rows)
+        return CS
+
+    def _critic_out(self, CS):
+        """Collect end: time-major -> trajectory-major once (row a * T + t), + the last next-state row, as value_input_rows."""
+        if CS is None:
+            return
+        T, na, ld = CS.shape[0] - 1, CS.shape[1], CS.shape[2]
+        rows = torch.empty((na * T + 1, ld), dtype=torch.float32, device=CS.device)
+        rows[:na * T].view(na, T, ld).copy_(CS[:T].transpose(0, 1))
+        rows[na * T].copy_(CS[T][na - 1])
+        self.critic_value_input_rows = rows
+        self._critic_next_rows = CS[T]
+
     # same signature as BatchedAgentManager.init_processes (learner.py:140-150); n_processes is ignored
     def init_processes(self, n_processes, build_env_fn, collect_metrics_fn=None, spawn_delay=None, render=False,
                        render_delay=None, shm_buffer_size=8192):
@@ -219,22 +301,25 @@ class VectorAgentManager(object):
             self.obs_stats.increment(obs, obs.shape[0])
         self._initial_obs = obs
         self._initial_mask_pending = hasattr(self.env, "action_masks")  # read once the policy exists (first collect)
+        self._critic_init()
         n_acts, code = describe_action_space(self.env.action_space)
         return int(np.prod(self.env.observation_space.shape)), int(n_acts), int(code)
 
-    def _standardize_scalars(self):
+    def _standardize_scalars(self, critic=False):
+        """critic: of critic_obs_stats (its own cache), for the critic's observation rows."""
         if not self.standardize_obs:
             return None
-        key = (id(self.obs_stats), self.obs_stats.count, id(self.obs_stats.running_mean), self.per_feature_obs_standardization)
-        cached = getattr(self, "_scalars_cache", None)
+        stats, slot = (self.critic_obs_stats, "_critic_scalars_cache") if critic else (self.obs_stats, "_scalars_cache")
+        key = (id(stats), stats.count, id(stats.running_mean), self.per_feature_obs_standardization)
+        cached = getattr(self, slot, None)
         if cached is not None and cached[0] == key:   # the statistics have not moved since (they move every 6th step)
             return cached[1]
         if self.per_feature_obs_standardization:  # device vectors -> rlppo_pad_rows_per_feature
-            out = (torch.from_numpy(np.asarray(self.obs_stats.mean, np.float32).reshape(-1).copy()),
-                   torch.from_numpy(np.asarray(self.obs_stats.std, np.float32).reshape(-1).copy()))
+            out = (torch.from_numpy(np.asarray(stats.mean, np.float32).reshape(-1).copy()),
+                   torch.from_numpy(np.asarray(stats.std, np.float32).reshape(-1).copy()))
         else:
-            out = (float(self.obs_stats.mean[0]), float(self.obs_stats.std[0]))
-        self._scalars_cache = (key, out)
+            out = (float(stats.mean[0]), float(stats.std[0]))
+        setattr(self, slot, (key, out))
         return out
 
     def _final_obs_rows(self, info, dones, truncated, scalars):
@@ -305,6 +390,7 @@ class VectorAgentManager(object):
         mask, M = self._first_mask(), None
         width = None if mask is None else AM.Layout.of(self.policy).width
         final_rows = []   # bootstrap_truncated: (t, agents, staged final observations) of environment-side truncations
+        CS = self._critic_begin(T, dev)
         for t in range(T):
             if mask is not None:
                 if M is None:
@@ -332,17 +418,25 @@ class VectorAgentManager(object):
                 fin = self._final_obs_rows(info, row[1], row[2], scalars)
                 if fin is not None:
                     final_rows.append((t,) + fin)
+            if CS is not None:   # the critic's observation of step t + 1, with ITS scalars before this step's increment
+                cobs_dev = torch.from_numpy(self._critic_answer()).to(dev)
+                cscalars = self._standardize_scalars(critic=True)
             if self.standardize_obs:  # same cadence as one worker response per step
                 if self.steps_since_obs_stats_update > self.steps_per_obs_stats_increment:
                     self._increment_obs_stats(obs_dev)
+                    if CS is not None:
+                        self._increment_obs_stats(cobs_dev, critic=True)
                     self.steps_since_obs_stats_update = 0
                 else:
                     self.steps_since_obs_stats_update += 1
+            if CS is not None:
+                self.value_net.arena.stage_obs(cobs_dev, cscalars, out=CS[t + 1])
             self._track_rewards(row[0], (row[1] + row[2]) > 0)
         arena.stage_obs(obs_dev, scalars, out=S[T])          # the rows the agents act on next = next_states of the last step
         self._pending_obs = (obs_dev, scalars)
         self._pending_mask = mask
         self._masks_out(M, na, T)
+        self._critic_out(CS)
         if getattr(self.policy, "noise_mode", None) == "host" and hasattr(self.policy, "prefetch_noise"):
             # the NEXT collect's T draws of the reference's CPU noise stream, produced on the helper threads while the value pass,
             # the GAE scan and PPOLearner.learn run (none of them touches torch's CPU generator; if anything does, the chain is
@@ -395,6 +489,7 @@ class VectorAgentManager(object):
         mask, M = self._first_mask(), None
         width = None if mask is None else AM.Layout.of(self.policy).width
         patched = False   # bootstrap_truncated: a final observation went into the next-state rows
+        CS = self._critic_begin(T, dev)
         for t in range(T):
             if mask is not None:
                 if M is None:
@@ -422,12 +517,19 @@ class VectorAgentManager(object):
             if self.collect_metrics_fn is not None:
                 metrics.append(self.collect_metrics_fn(info["state"]))
             scalars = self._standardize_scalars()  # fetched BEFORE this step's increment (batched_agent_manager.py:230-235)
+            if CS is not None:   # the critic's observation of step t + 1, with ITS scalars before this step's increment
+                cobs_dev = torch.from_numpy(self._critic_answer()).to(dev)
+                cscalars = self._standardize_scalars(critic=True)
             if self.standardize_obs:  # same cadence as one worker response per step
                 if self.steps_since_obs_stats_update > self.steps_per_obs_stats_increment:
                     self._increment_obs_stats(obs_dev)
+                    if CS is not None:
+                        self._increment_obs_stats(cobs_dev, critic=True)
                     self.steps_since_obs_stats_update = 0
                 else:
                     self.steps_since_obs_stats_update += 1
+            if CS is not None:
+                self.value_net.arena.stage_obs(cobs_dev, cscalars, out=CS[t + 1])
             self._track_rewards(rews[:, t], (dones[:, t] + trunc[:, t]) > 0)
             rows = arena.stage_obs(obs_dev, scalars)
             n3[:, t].copy_(rows)
@@ -445,6 +547,7 @@ class VectorAgentManager(object):
         self._next_rows = rows
         self._pending_mask = mask
         self._masks_out(M, na, T)
+        self._critic_out(CS)
         self.cumulative_timesteps += N_
         experience = (flat[:N_], acts.view(N_, -1), logp.view(N_), up(rews), nxt_flat, up(dones), up(trunc))
         return experience, metrics, N_, time.perf_counter() - t1
@@ -465,6 +568,7 @@ class VectorAgentManager(object):
             device_stats.increment(self.obs_stats, obs)
         self._initial_obs = obs
         self._initial_mask_pending = hasattr(self.env, "action_masks")
+        self._critic_init()
         n_acts, code = describe_action_space(self.env.action_space)
         return int(np.prod(self.env.observation_space.shape)), int(n_acts), int(code)
 
@@ -512,17 +616,49 @@ class VectorAgentManager(object):
                                               int(bool(self.per_feature_obs_standardization)), ptr(b.vec[b.cur][0]), ptr(b.vec[b.cur][1])))
         return b
 
-    def _book_out(self, b):
-        """Collect end: ONE device-to-host copy brings back the statistics, the average and the ended-episode count."""
-        host = b.blob.cpu().numpy()
+    def _book_out(self, b, cb=None):
+        """Collect end: ONE device-to-host copy brings back the statistics, the average and the ended-episode count (cb: and the
+        critic's statistics, in the same copy)."""
+        if cb is not None and cb.blob is not None:
+            both = torch.cat((b.blob, cb.blob)).cpu().numpy()
+            host, chost = both[:b.blob.numel()], both[b.blob.numel():]
+        else:
+            host, chost = b.blob.cpu().numpy(), None
         st_words = host[8:24].view(np.int64)
         self.average_reward = float(host[:8].view(np.float64)[0]) if st_words[0] else None
         self.episodes_ended += int(st_words[1])
-        if self.standardize_obs:
-            st, (dt, es) = self.obs_stats, ((np.float64, 8) if b.f64 else (np.float32, 4))
+        for book, st, h in ((b, self.obs_stats, host), (cb, self.critic_obs_stats, chost)):
+            if not self.standardize_obs or h is None:
+                continue
+            dt, es = (np.float64, 8) if book.f64 else (np.float32, 4)
             shape, keep = np.shape(st.running_mean), np.asarray(st.running_mean).dtype
-            st.running_mean = host[24:24 + b.d * es].view(dt).reshape(shape).astype(keep, copy=True)
-            st.running_variance = host[24 + b.d * es:].view(dt).reshape(shape).astype(keep, copy=True)
+            st.running_mean = h[24:24 + book.d * es].view(dt).reshape(shape).astype(keep, copy=True)
+            st.running_variance = h[24 + book.d * es:].view(dt).reshape(shape).astype(keep, copy=True)
+
+    def _critic_book_in(self, dev):
+        """_book_in for critic_obs_stats: its state to a _DeviceBook of its own (the 24 state bytes unused) and the standardisation
+        vectors of the statistics as they stand; None when the critic's rows are not standardised."""
+        from ..engine import ptr, stream_ptr
+        from .. import _native as N
+        st = self.critic_obs_stats if self.standardize_obs else None
+        if st is None:
+            return None
+        if self._cbook is None or self._cbook.device != dev:
+            self._cbook = _DeviceBook(dev, 0)
+        cb = self._cbook
+        d = int(np.prod(np.shape(st.running_mean)))
+        f64 = np.asarray(st.running_mean).dtype == np.float64
+        cb.layout(d, f64)
+        host = cb.pin.numpy()
+        host[:24] = 0
+        dt, es = (np.float64, 8) if f64 else (np.float32, 4)
+        host[24:24 + d * es].view(dt)[:] = np.asarray(st.running_mean, dt).reshape(-1)
+        host[24 + d * es:].view(dt)[:] = np.asarray(st.running_variance, dt).reshape(-1)
+        cb.blob.copy_(cb.pin, non_blocking=True)
+        cb.cur = 0   # (the critic's rows are staged in the step that fetched their pair: nothing pending reads the other one)
+        N.check(N.lib().rlppo_obs_scalars(stream_ptr(), ptr(cb.mean), ptr(cb.m2), int(f64), int(st.count), d,
+                                          int(bool(self.per_feature_obs_standardization)), ptr(cb.vec[0][0]), ptr(cb.vec[0][1])))
+        return cb
 
     def _collect_device(self, n):
         """The collect of a DEVICE-RESIDENT environment (reset() / step() answer GPU tensors on torch's current stream): the numbers of
@@ -547,6 +683,8 @@ class VectorAgentManager(object):
         rdt = torch.empty((3, T, na), dtype=torch.float32, device=dev)
         metrics = []
         b = self._book_in(dev)
+        CS = self._critic_begin(T, dev)
+        cb = self._critic_book_in(dev) if CS is not None else None
         if self._pending_obs is None:   # first collect: the reset observations are acted on RAW
             self._pending_obs = (self._initial_obs, None)
         obs_dev, scalars = self._pending_obs
@@ -606,6 +744,9 @@ class VectorAgentManager(object):
                     warnings.warn("gae_bootstrap_truncated: the environment's info has no 'final_observation': environment-side "
                                   "truncations bootstrap from the post-reset observation (the truncation at the end of every collect "
                                   "is not affected)", RuntimeWarning, stacklevel=3)
+            if CS is not None:   # the critic's observation of step t + 1, staged with ITS pair before this step's increment
+                cobs_dev = self._critic_answer(dev)
+                self.value_net.arena.stage_obs(cobs_dev, None if cb is None else cb.vec[cb.cur], out=CS[t + 1])
             if self.standardize_obs:   # the host forms' cadence; the sample count is the host's
                 if self.steps_since_obs_stats_update > self.steps_per_obs_stats_increment:
                     st = self.obs_stats
@@ -615,6 +756,14 @@ class VectorAgentManager(object):
                     b.cur = 1 - b.cur
                     N.check(L.rlppo_obs_scalars(stream_ptr(), ptr(b.mean), ptr(b.m2), int(b.f64), int(st.count), b.d,
                                                 int(bool(self.per_feature_obs_standardization)), ptr(b.vec[b.cur][0]), ptr(b.vec[b.cur][1])))
+                    if cb is not None:   # critic_obs_stats moves with obs_stats, on its own device state
+                        cst = self.critic_obs_stats
+                        N.check(L.rlppo_welford_increment(stream_ptr(), ptr(cobs_dev), cobs_dev.stride(0), na, cb.d, ptr(cb.mean), ptr(cb.m2),
+                                                          int(cst.count), int(cb.f64)))
+                        cst.count += na
+                        cb.cur = 1 - cb.cur
+                        N.check(L.rlppo_obs_scalars(stream_ptr(), ptr(cb.mean), ptr(cb.m2), int(cb.f64), int(cst.count), cb.d,
+                                                    int(bool(self.per_feature_obs_standardization)), ptr(cb.vec[cb.cur][0]), ptr(cb.vec[cb.cur][1])))
                     self.steps_since_obs_stats_update = 0
                 else:
                     self.steps_since_obs_stats_update += 1
@@ -630,6 +779,7 @@ class VectorAgentManager(object):
         self._pending_obs = (obs_dev, scalars)
         self._pending_mask = mask
         self._masks_out(M, na, T)
+        self._critic_out(CS)
         if getattr(self.policy, "noise_mode", None) == "host" and hasattr(self.policy, "prefetch_noise"):
             self.policy.prefetch_noise(na, T)   # as _collect_fused: the next collect's draws, produced while the update runs
         k = acts_tm.shape[2]
@@ -646,7 +796,7 @@ class VectorAgentManager(object):
         self._next_rows = S[T]
         self.cumulative_timesteps += N_
         self.last_enqueue_seconds = time.perf_counter() - t1   # host time of the whole collect before its one wait
-        self._book_out(b)
+        self._book_out(b, cb)
         experience = (flat[:N_], actions, small[0], small[1], nxt_flat, small[2], small[3])
         return experience, metrics, N_, time.perf_counter() - t1
 
@@ -658,12 +808,12 @@ class VectorAgentManager(object):
             self._pending_mask = self._env_mask()
         return self._pending_mask
 
-    def _increment_obs_stats(self, obs_dev):
+    def _increment_obs_stats(self, obs_dev, critic=False):
         """WelfordRunningStat.increment(obs, n) on the device (bit-exact with the host class's sample-by-sample update in the
         state's dtype -- float32, or float64 after a checkpoint load -- which costs ~10 ms of Python per 4096 samples); the host
         object stays the owner of the state (checkpoints)."""
         from ..util import device_stats
-        device_stats.increment(self.obs_stats, obs_dev)
+        device_stats.increment(self.critic_obs_stats if critic else self.obs_stats, obs_dev)
 
     def _track_rewards(self, r, ended):
         """Episode-reward average as batched_agent_manager.py:377-399 keeps it, one agent = one stream: the ended agents' episode

@@ -622,6 +622,25 @@ int rlppo_gather_rows(void *stream, const float *src, int64_t ld_src, const int6
     RLPPO_CHECK_ARG(n > 0 && src && idx && dst, "gather_rows: null pointer");
     return launch_gather_rows((hipStream_t)stream, src, ld_src, idx, dst, width, n);
 }
+int rlppo_gather_rows2(void *stream, const rlppo_gather2_args *a) {
+    RLPPO_CHECK_ARG(a != nullptr, "gather_rows2: null args");
+    if (a->n == 0) return 0;
+    RLPPO_CHECK_ARG(a->n > 0 && a->src && a->critic_src && a->idx && a->dst && a->critic_dst, "gather_rows2: null pointer");
+    RLPPO_CHECK_ARG((a->old_logp && a->advantages && a->targets && a->actions && a->g_old && a->g_adv && a->g_tgt && a->g_act && a->act_dim > 0) ||
+                        !(a->old_logp || a->advantages || a->targets || a->actions || a->g_old || a->g_adv || a->g_tgt || a->g_act || a->zero_n),
+                    "gather_rows2: the per-row scalars come together (actions / old_logp / advantages / targets and their four destinations, act_dim > 0) or not at all");
+    RLPPO_CHECK_ARG(((reinterpret_cast<uintptr_t>(a->src) | reinterpret_cast<uintptr_t>(a->critic_src) | reinterpret_cast<uintptr_t>(a->dst) |
+                      reinterpret_cast<uintptr_t>(a->critic_dst)) & 15) == 0, "gather_rows2: the four matrices must be 16-byte aligned");
+    int64_t base, cap;
+    if (int rc = ring_window("gather_rows2", a->ring_base, a->ring_cap, &base, &cap)) return rc;
+    GatherMeta gm;
+    gm.actions = a->actions; gm.old_logp = a->old_logp; gm.adv = a->advantages; gm.targets = a->targets;
+    gm.g_old = a->g_old; gm.g_adv = a->g_adv; gm.g_tgt = a->g_tgt; gm.g_act = a->g_act;
+    gm.zero_n = a->zero_n;
+    gm.act_dim = a->act_dim;
+    return launch_gather_rows2((hipStream_t)stream, a->src, a->ld_src, a->dst, a->width, a->critic_src, a->critic_ld_src, a->critic_dst, a->critic_width,
+                               a->idx, a->n, base, cap, a->g_old ? &gm : nullptr);
+}
 int rlppo_welford_increment(void *stream, const float *samples, int64_t ld, int64_t n, int32_t d, void *mean, void *m2,
                             int64_t count, int32_t state_is_f64) {
     if (n == 0) return 0;
@@ -768,6 +787,7 @@ int64_t rlppo_dbg_counter(int32_t key) {
         case 0: case 1: case 2: case 3: case 4: case 5: case 6: return g_call_counts[key];
         case 7: return rollout_record_count();
         case 8: case 9: case 10: case 11: case 12: case 13: return g_form_launches[key - 8];
+        case 15: return g_call_counts[CNT_CRITIC_ROWS_PASS];
         default: return -1;
     }
 }

@@ -365,6 +365,16 @@ int launch_gather_rows(hipStream_t st, const float *src, int64_t ld_src, const i
 int launch_gather_meta(hipStream_t st, const int64_t *idx, const float *actions, int act_dim, const float *old_logp,
                        const float *adv, const float *targets, float *g_act, float *g_old, float *g_adv, float *g_tgt, int64_t n,
                        int64_t ring_base, int64_t ring_cap, unsigned *rowtab = nullptr, float *zero_n = nullptr);
+struct GatherSide {  // [critic rows] one matrix of gather_rows2_kernel: dst[r][0 .. 4 cpr) = src[row of r][0 .. 4 cpr)
+    const float *src;
+    int64_t ld;
+    float *dst;
+    int cpr;  // 16-byte chunks per row
+};
+// [critic rows] the policy's and the critic's rows (two matrices over the same physical rows) in one launch, + meta as above
+int launch_gather_rows2(hipStream_t st, const float *src_p, int64_t ld_p, float *dst_p, int width_p, const float *src_c, int64_t ld_c,
+                        float *dst_c, int width_c, const int64_t *idx, int64_t n, int64_t ring_base = 0, int64_t ring_cap = INT64_MAX,
+                        const GatherMeta *meta = nullptr);
 int launch_i64_to_f32(hipStream_t st, const int64_t *src, float *dst, int64_t n);
 int launch_learn_report(hipStream_t st, const rlppo_report_args &r);  // [r6] the tail of a learn(): norms of the update, statistics out, one completion word
 int launch_signal_words(hipStream_t st, unsigned *words, int count, unsigned value);  // words[0..count) <- value, released at system scope
@@ -378,8 +388,9 @@ long long rollout_record_count();   // rlppo_dbg_counter(7)
 // assert that it is the one that ran
 enum LaunchForm { FORM_NT_FEW_ROWS = 0, FORM_NT_TILED, FORM_B16_WIDE, FORM_B16_PERSISTENT, FORM_X3_PERSISTENT, FORM_GEMV_DW_ORDERED, FORM_COUNT };
 extern long long g_form_launches[FORM_COUNT];
-// rlppo_dbg_counter(0 .. 6): which form a call took, counted where the call selects it (api.hip, update.hip)
-enum CallCount { CNT_FUSED_ACT = 0, CNT_ACT_CHAIN, CNT_PASS, CNT_PAIRED_PASS, CNT_GATHER_FUSED_PASS, CNT_GROUP_DW, CNT_MD_NVEC, CNT_COUNT };
+// rlppo_dbg_counter(0 .. 6): which form a call took, counted where the call selects it (api.hip, update.hip); CNT_CRITIC_ROWS_PASS
+// (a pass with separate critic rows, rlppo_ppo_minibatch_critic) is rlppo_dbg_counter(15): keys 7 .. 13 were taken and 14 is pinned as no key
+enum CallCount { CNT_FUSED_ACT = 0, CNT_ACT_CHAIN, CNT_PASS, CNT_PAIRED_PASS, CNT_GATHER_FUSED_PASS, CNT_GROUP_DW, CNT_MD_NVEC, CNT_CRITIC_ROWS_PASS, CNT_COUNT };
 extern std::atomic<long long> g_call_counts[CNT_COUNT];
 // update.hip: the switches of the PPO pass (rlppo_dbg_set 4 / 19 / 26 / 29 / 31 / 37, rlppo_set_update_precision)
 void set_two_streams(int v), set_relu_bits(int v), set_fused_gather(int v), set_paired(int v), set_head_order(int v), set_group_dw(int v);

@@ -225,6 +225,48 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restric
     }
 }
 
+// [critic rows] The gather of a pass whose critic reads a matrix of its own (privileged observations): row idx[r] of BOTH matrices in
+// one launch.  Thread t is 16-byte chunk t % (p.cpr + c.cpr) of row t / (p.cpr + c.cpr): the first p.cpr chunks of a row are the
+// policy's, the others the critic's -- so a wave's lanes still read and write runs of consecutive 16-byte chunks (one run per
+// matrix and row), and the pass still starts with one launch.  `meta` rides on chunk 0 of the policy part, as above.
+__global__ __launch_bounds__(256) void gather_rows2_kernel(GatherSide p, GatherSide c, const int64_t *__restrict__ idx, int64_t n,
+                                                           int64_t ring_base, int64_t ring_cap, GatherMeta meta) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const int cpr = p.cpr + c.cpr;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = t / cpr;
+    const int k = (int)(t - row * cpr);
+    if (row >= n) return;
+    const int64_t srow = ring_row(idx[row], ring_base, ring_cap);
+    const bool critic = k >= p.cpr;
+    const float *src = critic ? c.src : p.src;
+    float *dst = critic ? c.dst : p.dst;
+    const int64_t ld = critic ? c.ld : p.ld, scpr = critic ? c.cpr : p.cpr;
+    const int ck = critic ? k - p.cpr : k;
+    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(src + srow * ld) + ck);
+    reinterpret_cast<f32x4 *>(dst)[row * scpr + ck] = v;
+    if (k == 0 && meta.g_old) {
+        meta.g_old[row] = meta.old_logp[srow];
+        meta.g_adv[row] = meta.adv[srow];
+        meta.g_tgt[row] = meta.targets[srow];
+        for (int a = 0; a < meta.act_dim; ++a) meta.g_act[row * meta.act_dim + a] = meta.actions[srow * meta.act_dim + a];
+        if (meta.zero_n) meta.zero_n[row] = 0.f;
+    }
+}
+
+int launch_gather_rows2(hipStream_t st, const float *src_p, int64_t ld_p, float *dst_p, int width_p, const float *src_c, int64_t ld_c,
+                        float *dst_c, int width_c, const int64_t *idx, int64_t n, int64_t ring_base, int64_t ring_cap, const GatherMeta *meta) {
+    if (n <= 0) return 0;
+    RLPPO_CHECK_ARG(width_p > 0 && width_p % 4 == 0 && ld_p >= width_p && ld_p % 4 == 0 && width_c > 0 && width_c % 4 == 0 && ld_c >= width_c &&
+                        ld_c % 4 == 0, "gather_rows2: width=%d ld=%ld, critic width=%d ld=%ld", width_p, (long)ld_p, width_c, (long)ld_c);
+    const GatherSide p{src_p, ld_p, dst_p, width_p / 4}, c{src_c, ld_c, dst_c, width_c / 4};
+    const int64_t blocks = cdiv(n * (p.cpr + c.cpr), 256);
+    RLPPO_CHECK_ARG(blocks <= 0x7fffffff, "gather_rows2: %ld rows of %d + %d floats are too many for one launch", (long)n, width_p, width_c);
+    hipLaunchKernelGGL(gather_rows2_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, c, idx, n, ring_base, ring_cap, meta ? *meta : GatherMeta{});
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
 // The same gather for the bf16 update precision: the gathered observation rows are rounded to bf16 on the way -- written as
 // fp32 (X operand of the first layer's fp32 weight gradient) and as bf16 (A operand of the first layer's bf16 forward).
 __global__ __launch_bounds__(256) void gather_rows_round_kernel(const float *__restrict__ src, int64_t ld_src,

@@ -81,6 +81,7 @@ struct WsPlan {
     NetWs pol, val;
     size_t tn_floats = 0;  // the region from pol.tn on: both chains' partial buffers, one region for the grouped dW launch
     float *states = nullptr;  // the gathered minibatch rows, [mb][policy pin]
+    float *cstates = nullptr;  // [critic rows] the critic's gathered rows, [mb][critic pin], when it reads a matrix of its own
     float *g_old = nullptr, *g_adv = nullptr, *g_tgt = nullptr, *g_act = nullptr;  // the gathered per-row scalars (act_dim per row)
     unsigned *rowtab = nullptr;  // the physical buffer row of every row of the pass (gather_meta_kernel)
     unsigned short *states_b = nullptr;  // bf16 update precision: the gathered rows as bf16
@@ -89,8 +90,9 @@ struct WsPlan {
 // them from the address (the base is 256-byte aligned by contract); the size reserves the largest pad.
 constexpr size_t BITS_PAD_RESERVE = 2, B16_PAD_RESERVE = 4;
 // Lays out the workspace of a pass from `base` into *w and returns its size in floats: the size the host is told and the layout
-// the pass uses come from this one walk.
-static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec, void *base, WsPlan *w) {
+// the pass uses come from this one walk.  critic_rows: the plan of a pass with separate critic rows (rlppo_ppo_minibatch_critic) -- the
+// critic's gathered rows follow the policy's, so they start on the boundary those do and every other plan is what it was.
+static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec, void *base, WsPlan *w, bool critic_rows = false) {
     const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
     const size_t rows = (size_t)mb;
     size_t off = 0, slack = 0;  // floats from the base; the unused part of the pad reserves
@@ -120,6 +122,7 @@ static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t
             ws[i]->bits[l] = f ? reinterpret_cast<unsigned long long *>(take(f)) : nullptr;
         }
     w->states = take(rows * pol.L[0].pin);
+    w->cstates = critic_rows ? take(rows * val.L[0].pin) : nullptr;
     w->g_old = take(rows);
     w->g_adv = take(rows);
     w->g_tgt = take(rows);
@@ -181,18 +184,25 @@ static bool twin_ok(const NetLayout &p, const NetLayout &v, int64_t mb) {
 // launches (11.59 against 11.71 ms per 10-epoch learn() at the 8-rank share, tools/ab_update.py, profiles/r05_ab_update_final.txt);
 // at 524,288 rows per pass the two are equal and the fused form saves the 268 MB copy.  rlppo_dbg_set(26, 2): at every size (tests).
 constexpr int64_t FUSED_GATHER_MIN_ROWS = 262144;
-static RowSource first_layer_rows(const rlppo_minibatch_args &a, const NetLayout &pol, const NetLayout &val, int prec, const WsPlan &w,
-                                  bool plain) {
-    if (plain) return RowSource{w.states, pol.L[0].pin};  // [act] the gathered first layer is a ReLU-bitmask launch: the gather pass
+// [critic rows] One RowSource per network (rows[0] the policy's, rows[1] the critic's): the same decision for both, as before -- both
+// first layers through the one row table, each from its own matrix, or both on gathered rows.  `critic` null: one matrix for both.
+static void first_layer_rows(const rlppo_minibatch_args &a, const rlppo_critic_rows *critic, const NetLayout &pol, const NetLayout &val, int prec,
+                             const WsPlan &w, bool plain, RowSource rows[2]) {
+    const float *vx = critic ? critic->states : a.states;
+    const int64_t vld = critic ? critic->ld_states : a.ld_states;
+    rows[0] = RowSource{w.states, pol.L[0].pin};
+    rows[1] = critic ? RowSource{w.cstates, val.L[0].pin} : rows[0];
+    if (plain) return;  // [act] the gathered first layer is a ReLU-bitmask launch: the gather pass
     const int64_t src_rows = a.ring_cap > 0 ? a.ring_cap : a.n_rows;
-    auto gather_form = [&](const NetLayout &n) {
-        return n.n_layers > 1 && nt_gather_ok(a.ld_states, src_rows, n.L[0].pout, n.L[0].pin) && tn_gather_ok(a.ld_states, src_rows) &&
+    auto gather_form = [&](const NetLayout &n, int64_t ld) {
+        return n.n_layers > 1 && nt_gather_ok(ld, src_rows, n.L[0].pout, n.L[0].pin) && tn_gather_ok(ld, src_rows) &&
                !(n.L[0].out > 64 && n.L[0].out <= 96 && !(n.L[0].in > 96 && n.L[0].in <= 112));
     };
     if (prec != 1 && (g_fused_gather == 2 || (g_fused_gather == 1 && a.mb >= FUSED_GATHER_MIN_ROWS)) && src_rows > 0 &&
-        gather_form(pol) && gather_form(val))
-        return RowSource{a.states, a.ld_states, w.rowtab, src_rows};
-    return RowSource{w.states, pol.L[0].pin};
+        gather_form(pol, a.ld_states) && gather_form(val, vld)) {
+        rows[0] = RowSource{a.states, a.ld_states, w.rowtab, src_rows};
+        rows[1] = RowSource{vx, vld, w.rowtab, src_rows};
+    }
 }
 
 // One validated call of rlppo_ppo_minibatch, as its forms see it
@@ -203,7 +213,8 @@ struct Pass {
     int prec;  // update precision: 0 fp32, 1 bf16, 2 split-bf16
     int64_t ring_base, ring_cap;
     WsPlan w;
-    RowSource rows;  // the first layers' operand
+    const rlppo_critic_rows *critic = nullptr;  // [critic rows] the critic's own row matrix (rlppo_ppo_minibatch_critic), or null
+    RowSource rows[2];  // the first layers' operand: [0] the policy's, [1] the critic's (the same unless `critic`)
     LossCfg cfg;
     MdSpec md;                   // [nvec] the multi-discrete head's bins when rlppo_ppo_minibatch_nvec gives them
     bool md_general = false;
@@ -227,7 +238,7 @@ static Chain pass_chain(const Pass &p, bool critic) {
     c.st = critic ? p.side : p.st;
     c.net = critic ? &p.val : &p.pol;
     c.w = critic ? p.val_w : p.pol_w;
-    c.in = p.rows;
+    c.in = p.rows[critic ? 1 : 0];
     c.in_b = p.w.states_b;
     c.n = p.mb;
     c.out_tanh = !critic && a.head == RLPPO_HEAD_GAUSSIAN;
@@ -297,19 +308,22 @@ static int gather(const Pass &p) {
         const int rc = launch_gather_rows_round(p.st, a.states, a.ld_states, a.idx, lean0(p.pol) && lean0(p.val) ? nullptr : w.states,
                                                 w.states_b, width, p.mb, p.ring_base, p.ring_cap);
         if (rc) return rc;
-    } else if (!p.rows.rowtab) {  // (the per-row scalars ride in the same launch)
+    } else if (!p.rows[0].rowtab) {  // (the per-row scalars ride in the same launch)
         GatherMeta gm;
         gm.actions = a.actions; gm.old_logp = a.old_logp; gm.adv = a.advantages; gm.targets = a.targets;
         gm.g_old = w.g_old; gm.g_adv = w.g_adv; gm.g_tgt = w.g_tgt; gm.g_act = w.g_act;
         gm.zero_n = vout;
         gm.act_dim = a.act_dim;
+        if (p.critic)  // [critic rows] both matrices' rows, still one launch
+            return launch_gather_rows2(p.st, a.states, a.ld_states, w.states, width, p.critic->states, p.critic->ld_states, w.cstates,
+                                       p.val.L[0].pin, a.idx, p.mb, p.ring_base, p.ring_cap, &gm);
         return launch_gather_rows(p.st, a.states, a.ld_states, a.idx, w.states, width, p.mb, p.ring_base, p.ring_cap, &gm);
     }
     // ... and writes the row table the fused first layers read.  ([r5] It also zeroes the first mb floats of the critic's output
     // buffer: a folded value head accumulates into them; when the rows were gathered by a pass of their own, that launch has done
     // all of this already.)
     return launch_gather_meta(p.st, a.idx, a.actions, a.act_dim, a.old_logp, a.advantages, a.targets, w.g_act, w.g_old, w.g_adv, w.g_tgt,
-                              p.mb, p.ring_base, p.ring_cap, p.rows.rowtab ? w.rowtab : nullptr, vout);
+                              p.mb, p.ring_base, p.ring_cap, p.rows[0].rowtab ? w.rowtab : nullptr, vout);
 }
 
 // The paired pass ([r3] paired launches, above).  It joins the critic's stream itself, before the hidden layers' backward.
@@ -329,8 +343,9 @@ static int paired_pass(const Pass &p, SlotBank &bk, int slot) {
     const bool fold_v = cv.head_folded = get_fold_vhead() && gemv_head_ok(Lvh.out, Lvh.pin) && val.L[H - 1].pout / 128 <= 2;
     float *vout = w.val.act[H];
     const int64_t ldv = fold_v ? 1 : Lvh.pout;
-    const float *xp = p.rows.x, *xv = xp;
-    int64_t ldx = p.rows.ld;
+    const RowSource &rows = p.rows[0];  // (a paired layer 0 shares one A operand: never a pass with separate critic rows)
+    const float *xp = rows.x, *xv = xp;
+    int64_t ldx = rows.ld;
     for (int l = 0; l < H; ++l) {
         const LayerLayout &Lp = pol.L[l], &Lv = val.L[l];
         NtAlt alt;
@@ -347,7 +362,7 @@ static int paired_pass(const Pass &p, SlotBank &bk, int slot) {
             dots[1].b = p.val_w + Lvh.off_b;
         }
         rc = launch_gemm_nt_bits(st, xp, ldx, p.pol_w + Lp.off_w, Lp.pin, p.pol_w + Lp.off_b, w.pol.act[l], Lp.pout, mb, Lp.pout, Lp.pin,
-                                 EPI_BIAS_RELU, w.pol.bits[l], l == 0 ? p.rows.rowtab : nullptr, p.rows.src_rows, &alt,
+                                 EPI_BIAS_RELU, w.pol.bits[l], l == 0 ? rows.rowtab : nullptr, rows.src_rows, &alt,
                                  fold_here ? dots : nullptr);
         if (rc) {
             if (rc == -1) set_error("paired pass: a hidden layer does not have the bitmask form");
@@ -396,8 +411,8 @@ static int paired_pass(const Pass &p, SlotBank &bk, int slot) {
     // hidden layers, backward: dW (+ reduction) of both networks, then dX of both
     for (int l = H - 1; l >= 0; --l) {
         const LayerLayout &Lp = pol.L[l], &Lv = val.L[l];
-        const RowSource Xp = l > 0 ? RowSource{w.pol.act[l - 1], pol.L[l - 1].pout} : p.rows;
-        const RowSource Xv = l > 0 ? RowSource{w.val.act[l - 1], val.L[l - 1].pout} : p.rows;
+        const RowSource Xp = l > 0 ? RowSource{w.pol.act[l - 1], pol.L[l - 1].pout} : rows;
+        const RowSource Xv = l > 0 ? RowSource{w.val.act[l - 1], val.L[l - 1].pout} : rows;
         if (p.defer) {
             p.defer->add(Lp, w.pol.dx[l], Xp, a.pol_grad);
             p.defer->add(Lv, w.val.dx[l], Xv, a.val_grad);
@@ -447,12 +462,13 @@ static int two_chain_pass(const Pass &p) {
 
 // one pass; md_nvec (host, or null = the reference's multi-discrete head) is rlppo_ppo_minibatch_nvec's
 static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads, const DiagHead *diag,
-                         int pol_act, int val_act) {
+                         int pol_act, int val_act, const rlppo_critic_rows *critic = nullptr) {
     // ---- validation: every argument error is reported here, before the first HIP call
     RLPPO_CHECK_ARG(a != nullptr, "ppo_minibatch: null args");
     Pass p;
     p.a = a;
     p.diag = diag;
+    p.critic = critic;
     int rc = make_layout(a->pol_dims, a->pol_layers, &p.pol);
     if (rc) return rc;
     rc = make_layout(a->val_dims, a->val_layers, &p.val);
@@ -477,12 +493,21 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
                     "ppo_minibatch: null pointer");
     RLPPO_CHECK_ARG(val.L[val.n_layers - 1].out == 1, "ppo_minibatch: critic must have one output");
     RLPPO_CHECK_ARG(a->value_clip >= 0.f && a->value_clip < INFINITY, "ppo_minibatch: value_clip=%g", (double)a->value_clip);
-    RLPPO_CHECK_ARG(pol.L[0].in == val.L[0].in, "ppo_minibatch: policy and critic observe different sizes");
+    RLPPO_CHECK_ARG(critic || pol.L[0].in == val.L[0].in, "ppo_minibatch: policy and critic observe different sizes");
+    if (critic) {  // [critic rows] val_dims[0] is the width of the critic's own matrix
+        RLPPO_CHECK_ARG(critic->ld_states >= val.L[0].pin && critic->ld_states % 4 == 0,
+                        "ppo_minibatch_critic: critic ld_states=%ld < %d (the padded width of val_dims[0]=%d), or not a multiple of 4",
+                        (long)critic->ld_states, val.L[0].pin, val.L[0].in);
+        RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(critic->states) & 15) == 0, "ppo_minibatch_critic: critic states must be 16-byte aligned");
+        RLPPO_CHECK_ARG(p.prec != 1, "ppo_minibatch_critic: update precision bf16 with separate critic rows: its gather writes one bf16 image, "
+                                     "of the policy's rows (use fp32 or x3)");
+    }
     RLPPO_CHECK_ARG(a->ld_states >= pol.L[0].pin && a->ld_states % 4 == 0, "ppo_minibatch: ld_states=%ld < %d",
                     (long)a->ld_states, pol.L[0].pin);
-    const size_t ws_bytes = plan_workspace(pol, val, mb, p.prec, a->workspace, &p.w) * sizeof(float);
+    const size_t ws_bytes = plan_workspace(pol, val, mb, p.prec, a->workspace, &p.w, critic != nullptr) * sizeof(float);
     if (a->ws_bytes < ws_bytes) {
-        set_error("ppo_minibatch: workspace %zu < %zu bytes", a->ws_bytes, ws_bytes);
+        set_error("ppo_minibatch: workspace %zu < %zu bytes%s", a->ws_bytes, ws_bytes,
+                  critic ? " (separate critic rows: rlppo_minibatch_workspace_bytes_critic)" : "");
         return RLPPO_ERR_WORKSPACE;
     }
     // every head pins act_dim to at most the policy's output width (the gathered actions' slots); the loss kernel's width too
@@ -538,8 +563,8 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     RLPPO_CHECK_ARG(slot >= 0 && slot < RLPPO_MAX_SLOTS, "ppo_minibatch: slot %d not in [0, %d)", slot, RLPPO_MAX_SLOTS);
 
     // ---- plan: the first layers' rows, the form, the loss settings
-    p.rows = first_layer_rows(*a, pol, val, p.prec, p.w, p.plain);
-    const bool twin = p.prec == 0 && !p.plain && (g_paired == 2 || (g_paired == 1 && mb >= PAIRED_MIN_ROWS)) && twin_ok(pol, val, mb);
+    first_layer_rows(*a, critic, pol, val, p.prec, p.w, p.plain, p.rows);
+    const bool twin = p.prec == 0 && !p.plain && !critic && (g_paired == 2 || (g_paired == 1 && mb >= PAIRED_MIN_ROWS)) && twin_ok(pol, val, mb);
     p.cfg = loss_cfg(*a);
     p.pol_w = p.prec == 1 ? a->pol_packed_r : a->pol_packed;
     p.val_w = p.prec == 1 ? a->val_packed_r : a->val_packed;
@@ -574,7 +599,8 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     }
     ++g_call_counts[CNT_PASS];
     if (twin) ++g_call_counts[CNT_PAIRED_PASS];
-    if (p.rows.rowtab) ++g_call_counts[CNT_GATHER_FUSED_PASS];
+    if (p.rows[0].rowtab) ++g_call_counts[CNT_GATHER_FUSED_PASS];
+    if (critic) ++g_call_counts[CNT_CRITIC_ROWS_PASS];
     rc = twin ? paired_pass(p, bk, slot) : two_chain_pass(p);
     if (rc) return rc;
     if (!twin && p.side != p.st) {  // (the paired pass has joined already)
@@ -602,6 +628,14 @@ size_t rlppo_minibatch_workspace_bytes_for(const int32_t *pol_dims, int32_t pol_
     WsPlan unused;
     return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused) * sizeof(float) + 256;
 }
+size_t rlppo_minibatch_workspace_bytes_critic(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
+                                              int64_t mb, int32_t precision) {
+    NetLayout pol, val;
+    int prec = 0;
+    if (make_layout(pol_dims, pol_layers, &pol) || make_layout(val_dims, val_layers, &val) || resolve_precision(precision, &prec)) return 0;
+    WsPlan unused;
+    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused, true) * sizeof(float) + 256;
+}
 size_t rlppo_minibatch_workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims,
                                        int32_t val_layers, int64_t mb) {
     return rlppo_minibatch_workspace_bytes_for(pol_dims, pol_layers, val_dims, val_layers, mb, RLPPO_PRECISION_DEFAULT);
@@ -619,6 +653,17 @@ int rlppo_ppo_minibatch_ex(void *stream, const rlppo_minibatch_args *a, const rl
     const DiagHead d = diag_head(ext->log_std, ext->log_std_grad, ext->scratch, ext->scratch_bytes);
     RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(ext->scratch) & 7) == 0, "ppo_minibatch_ex: scratch must be 8-byte aligned");
     return ppo_minibatch(stream, a, ext->md_nvec, ext->md_heads, diag ? &d : nullptr, ext->pol_hidden_act, ext->val_hidden_act);
+}
+
+// [critic rows] the same call with the critic's own row matrix; no matrix: rlppo_ppo_minibatch_ex
+int rlppo_ppo_minibatch_critic(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic) {
+    if (!critic || !critic->states) return rlppo_ppo_minibatch_ex(stream, a, ext);
+    const rlppo_minibatch_ext none = {};
+    if (!ext) ext = &none;
+    const bool diag = ext->log_std || ext->log_std_grad || ext->scratch || ext->scratch_bytes;
+    const DiagHead d = diag_head(ext->log_std, ext->log_std_grad, ext->scratch, ext->scratch_bytes);
+    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(ext->scratch) & 7) == 0, "ppo_minibatch_critic: scratch must be 8-byte aligned");
+    return ppo_minibatch(stream, a, ext->md_nvec, ext->md_heads, diag ? &d : nullptr, ext->pol_hidden_act, ext->val_hidden_act, critic);
 }
 
 size_t rlppo_diag_scratch_bytes(int64_t mb, int32_t k) { return diag_scratch_bytes(mb, k); }

@@ -45,6 +45,7 @@ class Learner(object):
             continuous_head: str = "reference", continuous_log_std_init: float = 0.0, continuous_action_clip="default",
             hidden_activation: str = "relu",
             ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
+            critic_observations: bool = False,
             per_feature_obs_standardization: bool = False,
             ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
         assert env_create_function is not None, "MUST PROVIDE A FUNCTION TO CREATE RLGYM FUNCTIONS TO INITIALIZE RLGYM-PPO"
@@ -63,6 +64,21 @@ class Learner(object):
         # here, before anything is built or spawned.  (The default IS "relu", so an explicit hidden_activation="relu" cannot be told
         # from an omitted one: LayerSizes(..., "tanh") beside it builds a tanh network and raises nothing -- the one disagreement that
         # is not refused.  self.hidden_activations says what was built.)
+        # not in the reference: critic_observations=True is the asymmetric actor-critic of rsl_rl / Isaac Lab ("privileged observations") --
+        # the vector environment's critic_observations() -> [n_agents, d_c] describes, for the critic alone, the state the agents act on
+        # next; the critic is built on d_c inputs (taken from the first answer), the value pass and the update read those rows
+        # (VectorAgentManager.critic_value_input_rows, ExperienceBuffer.critic_states).  Vector mode only: the process-mode wire format
+        # has no slot for the rows; and not together with gae_bootstrap_truncated, which would need FINAL critic observations.  Checked
+        # here, before anything is built or spawned; False is the library as it was, launch for launch.
+        self.critic_observations = bool(critic_observations)
+        if self.critic_observations:
+            if not vector_env:
+                raise ValueError("critic_observations=True needs vector_env=True: process-mode collection is not supported (its wire format "
+                                 "has no slot for the critic's observation rows)")
+            if gae_bootstrap_truncated:
+                raise ValueError("critic_observations=True together with gae_bootstrap_truncated=True is not supported: bootstrapping a "
+                                 "truncated step needs the critic's FINAL observation of the episode, which the environment interface "
+                                 "does not carry yet")
         from .ppo._mlp import LayerSizes, check_activation
         hidden_activation = check_activation(hidden_activation)
 
@@ -154,6 +170,7 @@ class Learner(object):
         self.gae_bootstrap_truncated = bool(gae_bootstrap_truncated)
         if vector_env:
             self.agent.bootstrap_truncated = self.gae_bootstrap_truncated
+            self.agent.critic_observations = self.critic_observations   # (init_processes refuses an environment without the method)
         obs_space_size, act_space_size, action_space_type = self.agent.init_processes(
             n_processes=n_proc, build_env_fn=env_create_function, collect_metrics_fn=collect_metrics_fn,
             spawn_delay=instance_launch_delay, render=render, render_delay=render_delay, shm_buffer_size=shm_buffer_size)
@@ -175,6 +192,9 @@ class Learner(object):
                 self.agent.cleanup()
                 raise ValueError(f"continuous_head='diag' is an option of a continuous action space (type 2), not of action space type {action_space_type}")
             action_space_type = 3   # PPOLearner's policy_type of the diagonal-Gaussian head
+        if self.critic_observations:   # the critic's input size is the environment's first answer (ppo.ObsSizes carries both sizes)
+            from .ppo import ObsSizes
+            obs_space_size = ObsSizes(int(obs_space_size), self.agent.critic_obs_size)
         self.ppo_learner = PPOLearner(
             obs_space_size, act_space_size, device=self.device, batch_size=ppo_batch_size,
             mini_batch_size=ppo_minibatch_size, n_epochs=ppo_epochs, continuous_var_range=continuous_var_range,
@@ -182,6 +202,8 @@ class Learner(object):
             policy_lr=policy_lr, critic_lr=critic_lr, clip_range=ppo_clip_range, ent_coef=ppo_ent_coef,
             normalize_advantages=ppo_normalize_advantages, value_clip_range=ppo_value_clip_range, target_kl=ppo_target_kl,
             max_grad_norm=ppo_max_grad_norm)
+        if self.critic_observations:
+            self.agent.value_net = self.ppo_learner.value_net   # its arena stages the critic's observation rows
         if ppo_lr_schedule == "adaptive":   # ("linear" is this loop's: the update runs the constant schedule's launches)
             self.ppo_learner.set_lr_schedule("adaptive", ppo_desired_kl, ppo_lr_bounds)
         self.ppo_learner.report_learning_rates = ppo_lr_schedule != "constant"
@@ -216,6 +238,7 @@ class Learner(object):
             "ppo_clip_range": ppo_clip_range, "gae_lambda": gae_lambda, "gae_gamma": gae_gamma, "policy_lr": policy_lr,
             "critic_lr": critic_lr, "shm_buffer_size": shm_buffer_size,
             "gae_bootstrap_truncated": self.gae_bootstrap_truncated,  # (a hyper-parameter, not checkpoint state)
+            "critic_observations": self.critic_observations,
         }
 
         self.wandb_run = wandb_run
@@ -323,7 +346,10 @@ class Learner(object):
             rows = self.agent.value_input_rows               # [N+1, ld]: states ++ the last next_state, padded
             assert rows.shape[0] == n + 1 and rows.data_ptr() == states.data_ptr()
             d_logical = int(self.ppo_learner.policy.arena.d_in)
-            val_preds = value_net.forward_padded(rows).contiguous()
+            critic_rows = self.agent.critic_value_input_rows if self.critic_observations else None   # [N+1, ld_c]: the critic's own rows
+            if critic_rows is not None:
+                assert critic_rows.shape[0] == n + 1
+            val_preds = value_net.forward_padded(rows if critic_rows is None else critic_rows).contiguous()
             if self.gae_bootstrap_truncated and getattr(self.agent, "bootstrap_dense", False):
                 # a device-resident environment: which steps are truncated is known on the device only -- one value pass over ALL N
                 # next-state rows; the scan selects by the flags and never uses the other entries (include/rlppo.h, rlppo_gae_boot)
@@ -379,15 +405,19 @@ class Learner(object):
             self.return_stats.increment(head, n_to_increment)
 
         self.experience_buffer._d = d_logical  # logical width of the padded rows
+        extra = {}
+        if on_device and self.critic_observations:
+            self.experience_buffer._dc = int(value_net.arena.d_in)
+            extra["critic_states"] = critic_rows[:n]
         # invalid-action masking (an environment with action_masks(), either collection mode): the masks the actions were sampled
         # under -- packed device words from the vector manager, bool host rows [N, n_actions] from process-mode collection
         masks = getattr(self.agent, "action_mask_rows", None)
         if masks is not None:
             self.experience_buffer.submit_experience(rows[:n], actions, log_probs, rews_d, next_states, dones_d, trunc_d,
-                                                     value_targets, advantages, action_masks=masks)
+                                                     value_targets, advantages, action_masks=masks, **extra)
             return
         self.experience_buffer.submit_experience(rows[:n], actions, log_probs, rews_d, next_states, dones_d, trunc_d,
-                                                 value_targets, advantages)
+                                                 value_targets, advantages, **extra)
 
     # ------------------------------------------------------------------------------------------ checkpoints
     def save(self, cumulative_timesteps):
@@ -413,6 +443,8 @@ class Learner(object):
         }
         if self.agent.standardize_obs and self.agent.obs_stats is not None:
             book["obs_running_stats"] = self.agent.obs_stats.to_json()
+        if self.critic_observations and self.agent.standardize_obs and getattr(self.agent, "critic_obs_stats", None) is not None:
+            book["critic_obs_running_stats"] = self.agent.critic_obs_stats.to_json()
         if self.wandb_run is not None:
             book.update(wandb_run_id=self.wandb_run.id, wandb_project=self.wandb_run.project,
                         wandb_entity=self.wandb_run.entity, wandb_group=self.wandb_run.group,
@@ -463,6 +495,13 @@ class Learner(object):
         if self.agent.standardize_obs and "obs_running_stats" in book:
             self.agent.obs_stats = WelfordRunningStat(1)
             self.agent.obs_stats.from_json(book["obs_running_stats"])
+        if self.critic_observations and self.agent.standardize_obs:
+            if "critic_obs_running_stats" in book:
+                self.agent.critic_obs_stats = WelfordRunningStat(1)
+                self.agent.critic_obs_stats.from_json(book["critic_obs_running_stats"])
+            else:
+                warnings.warn("the checkpoint has no 'critic_obs_running_stats' (it was written without critic_observations): the critic's "
+                              "observation statistics start fresh", RuntimeWarning, stacklevel=2)
         self.epoch = book["epoch"]
         if new_policy_lr is not None or new_critic_lr is not None:
             self.update_learning_rate(new_policy_lr, new_critic_lr)

@@ -12,7 +12,9 @@ order) to physical row (base + i) mod capacity -- the kernels apply that map to 
 
 Beyond the reference: an optional tenth field, `action_masks` (invalid-action masking: A entries per row, the discrete head's
 actions or the multi-discrete head's logits, one per bin of every component), stored packed (int32 words [capacity, ceil(A / 32)],
-util/action_mask.py) under the same FIFO / grow / wrap rules.  A buffer is masked or not.
+util/action_mask.py) under the same FIFO / grow / wrap rules.  A buffer is masked or not.  And an optional field `critic_states`
+(asymmetric actor-critic: the critic's own, "privileged" observation of every row), a second padded device matrix over the same
+physical rows as `states`; a buffer holds it for every row or for none.
 """
 import os
 
@@ -29,6 +31,7 @@ _FIELDS = ("states", "actions", "log_probs", "rewards", "next_states", "dones", 
 class ExperienceBuffer(object):
     _fields = _FIELDS    # + "action_masks" once a masked submit has arrived (decided by the first submit after a clear())
     _n_actions = None    # actions a mask row describes
+    _dc = None           # logical width of a critic_states row
 
     def __init__(self, max_size, seed, device):
         # the reference's Learner passes device="cpu" here (learner.py:124-126); the data still belongs in HBM
@@ -51,7 +54,7 @@ class ExperienceBuffer(object):
         self._base = 0    # physical row of logical row 0 (the oldest sample)
         self._count = 0   # valid rows
         self._d = None    # logical observation width
-        self._fields, self._n_actions = _FIELDS, None
+        self._fields, self._n_actions, self._dc = _FIELDS, None, None
 
     # ------------------------------------------------------------------------------------------- FIFO
     def _grow(self, need, new):
@@ -104,29 +107,38 @@ class ExperienceBuffer(object):
             return x.detach().to(self._dev, dtype=torch.float32)
         return torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32))).to(self._dev)
 
-    def _pad_states(self, x):
-        if isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 2 and self._d is not None \
-                and x.shape[1] == N.lib().rlppo_padded_width(self._d):
+    def _pad_states(self, x, width="_d"):
+        """width: the attribute that holds the rows' logical width ("_d": states / next_states, "_dc": critic_states)."""
+        known = getattr(self, width)
+        if isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 2 and known is not None \
+                and x.shape[1] == N.lib().rlppo_padded_width(known):
             return x  # already padded device rows (Learner.add_new_experience hands them over as such)
         t = self._to_dev(x)
         if t.dim() == 1:
             t = t.view(-1, 1)
         t = t.reshape(t.shape[0], -1).contiguous()
         n, d = t.shape
-        self._d = d
+        setattr(self, width, d)
         ld = int(N.lib().rlppo_padded_width(d))
         out = torch.empty((n, ld), dtype=torch.float32, device=self._dev)
         N.check(N.lib().rlppo_pad_rows(stream_ptr(), ptr(t), 0, n, d, d, ptr(out), ld, 0, 0.0, 1.0))
         return out
 
     def submit_experience(self, states, actions, log_probs, rewards, next_states, dones, truncated, values, advantages,
-                          action_masks=None):
+                          action_masks=None, critic_states=None):
         """action_masks (optional, not in the reference): [n, A] bool / 0-1, host or device, valid = 1 -- the masks the actions
-        were sampled under (or util.action_mask.Packed).  Either every submit since the last clear() carries them or none does."""
+        were sampled under (or util.action_mask.Packed).  Either every submit since the last clear() carries them or none does.
+        critic_states (optional, not in the reference): [n, d_c], host or device (or already padded device rows, as `states`) -- the
+        critic's own observation of every row; likewise in every submit since the last clear() or in none."""
         masked = action_masks is not None
-        if (self._cap or self._count) and masked != (len(self._fields) > len(_FIELDS)):
+        if (self._cap or self._count) and masked != ("action_masks" in self._fields):
             raise ValueError("submit_experience: the buffer holds " + ("unmasked" if masked else "masked") + " experience and this submit is "
                              + ("masked" if masked else "unmasked") + ": a buffer is masked or not (clear() resets that)")
+        privileged = critic_states is not None
+        if (self._cap or self._count) and privileged != ("critic_states" in self._fields):
+            raise ValueError("submit_experience: the buffer holds experience " + ("without" if privileged else "with") + " critic_states and this "
+                             "submit comes " + ("with" if privileged else "without") + " them: a buffer holds them for every row or for none "
+                             "(clear() resets that)")
         new = dict(states=self._pad_states(states), actions=self._to_dev(actions), log_probs=self._to_dev(log_probs),
                    rewards=self._to_dev(rewards), next_states=self._pad_states(next_states), dones=self._to_dev(dones),
                    truncated=self._to_dev(truncated), values=self._to_dev(values), advantages=self._to_dev(advantages))
@@ -139,7 +151,9 @@ class ExperienceBuffer(object):
                 raise ValueError(f"submit_experience: action mask of {n_act} actions, the buffer's rows have {self._n_actions}")
             new["action_masks"] = AM.pack(m, n_act, self._dev)
             self._n_actions = n_act
-            self._fields = _FIELDS + ("action_masks",)
+        if privileged:
+            new["critic_states"] = self._pad_states(critic_states, "_dc")
+        self._fields = _FIELDS + (("action_masks",) if masked else ()) + (("critic_states",) if privileged else ())
         n = new["rewards"].shape[0]
         for k in self._fields:
             if new[k].shape[0] != n:
@@ -173,9 +187,23 @@ class ExperienceBuffer(object):
     advantages = property(lambda s: s._get("advantages"))
 
     @property
+    def critic_states(self):
+        """[n, d_c] in logical order (oldest first), or None for a buffer without critic states."""
+        if "critic_states" not in self._fields:
+            return None
+        if self._count == 0:
+            return torch.empty((0, self._dc), dtype=torch.float32, device=self._dev)
+        return self._logical("critic_states")[:, :self._dc]
+
+    @property
+    def critic_width(self):
+        """Logical width d_c of a critic_states row, or None for a buffer without them."""
+        return self._dc if "critic_states" in self._fields else None
+
+    @property
     def action_masks(self):
         """bool [n, A] in logical order (oldest first), or None for an unmasked buffer."""
-        if len(self._fields) == len(_FIELDS):
+        if "action_masks" not in self._fields:
             return None
         if self._count == 0:
             return torch.empty((0, self._n_actions), dtype=torch.bool, device=self._dev)
@@ -184,7 +212,7 @@ class ExperienceBuffer(object):
     @property
     def mask_width(self):
         """Entries of a mask row (the A of the packed words), or None for an unmasked buffer."""
-        return self._n_actions if len(self._fields) > len(_FIELDS) else None
+        return self._n_actions if "action_masks" in self._fields else None
 
     def __len__(self):
         return self._count

@@ -32,6 +32,15 @@ rlppo_ppo_minibatch_diag and its optimiser step through rlppo_clip_adam_pack2_ta
 KL-adaptive learning rate, once per optimiser step: both rates are doubles in device memory, moved by the batch's gate (rlppo_kl_gate_lr) and read by its
 optimiser step (rlppo_clip_adam_pack2_lr) -- no host decision, no wait that the constant schedule does not make.  "constant"
 (default) is the update above, launch for launch; "linear" needs a horizon and is `Learner`'s.
+
+`obs_space_size=ObsSizes(d, d_c)` (not in the reference, whose critic sees what the policy sees) is the asymmetric actor-critic of
+rsl_rl / Isaac Lab ("privileged observations"); like the bins it travels in a reference parameter, because the constructor's
+parameter list is pinned.  `self.critic_obs_space_size` says what was built (None: one size).  The critic is built on d_c inputs --
+construction order and generator use unchanged, so a seeded policy has the weights it has without it -- and every pass reads the buffer's `critic_states` matrix
+(ExperienceBuffer.submit_experience(..., critic_states=...)) through rlppo_ppo_minibatch_critic -- one gather launch for both
+matrices, no paired launches.  Whenever the buffer holds `critic_states` the passes take that entry point (also with d_c equal to
+the policy's width); a buffer without them and a critic of another width, or the reverse mismatch, is a ValueError before the first
+pass; update precision "bf16" is refused.  Without critic states learn() makes the calls it always made.
 """
 import ctypes
 import os
@@ -50,6 +59,19 @@ from .diag_gaussian_policy import DiagGaussianPolicy
 from .discrete_policy import DiscreteFF
 from .multi_discrete_policy import MultiDiscreteFF, check_bins
 from .value_estimator import ValueEstimator
+
+
+class ObsSizes(object):
+    """PPOLearner(obs_space_size=ObsSizes(policy, critic)): the policy's observation size and the critic's own."""
+
+    def __init__(self, policy, critic):
+        for name, v in (("policy", policy), ("critic", critic)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError(f"ObsSizes: {name} observation size must be a positive integer, got {v!r}")
+        self.policy, self.critic = int(policy), int(critic)
+
+    def __repr__(self):
+        return f"ObsSizes(policy={self.policy}, critic={self.critic})"
 
 MAX_GRAD_NORM = 0.5  # ppo_learner.py:187-190
 
@@ -151,6 +173,12 @@ class PPOLearner(object):
                                  f"(policy_type 1), not of policy_type {policy_type}")
             multi_discrete_bins = check_bins(act_space_size)
             act_space_size = len(multi_discrete_bins)
+        # obs_space_size as ObsSizes(policy, critic): a critic with observations of its own (checked at its construction, before
+        # anything needs the GPU); an integer is one size for both, as in the reference
+        critic_obs_space_size = None
+        if isinstance(obs_space_size, ObsSizes):
+            obs_space_size, critic_obs_space_size = obs_space_size.policy, obs_space_size.critic
+        self.critic_obs_space_size = critic_obs_space_size
         self.device = device
         self._dev = require_gpu(device)
         N.lib()  # fail here, loudly, if the HIP library is missing
@@ -174,7 +202,8 @@ class PPOLearner(object):
         else:
             self.policy = DiscreteFF(obs_space_size, act_space_size, policy_layer_sizes, device).to(device)
             self._act_dim = 1
-        self.value_net = ValueEstimator(obs_space_size, critic_layer_sizes, device).to(device)
+        self.value_net = ValueEstimator(obs_space_size if critic_obs_space_size is None else critic_obs_space_size, critic_layer_sizes,
+                                        device).to(device)
         self.mini_batch_size = mini_batch_size
 
         self.policy_optimizer = FusedAdam(self.policy, lr=policy_lr)
@@ -290,6 +319,19 @@ class PPOLearner(object):
                                  + (f"multi-discrete policy has {lay.width} logits (one entry per bin of every component)"
                                     if lay.heads is not None else f"discrete policy has {lay.width} actions"))
             a.action_mask, a.mask_words = st["action_masks"].data_ptr(), st["action_masks"].shape[1]
+        # the critic's own rows (ExperienceBuffer.submit_experience(..., critic_states=...)): rlppo_ppo_minibatch_critic
+        self._critic_rows = None
+        d_c = getattr(exp, "critic_width", None)
+        if d_c is None and va.d_in != pa.d_in:
+            raise ValueError(f"the critic observes {va.d_in} features and the policy {pa.d_in} (ObsSizes), but the experience "
+                             "buffer holds no critic_states: submit_experience(..., critic_states=...)")
+        if d_c is not None:
+            if d_c != va.d_in:
+                raise ValueError(f"the experience buffer's critic_states have {d_c} features, the critic observes {va.d_in}"
+                                 + ("" if self.critic_obs_space_size is not None else " (PPOLearner was built without ObsSizes)"))
+            cr = N.CriticRows()
+            cr.states, cr.ld_states = st["critic_states"].data_ptr(), st["critic_states"].shape[1]
+            self._critic_rows = cr
         a.clip_range, a.ent_coef = float(self.clip_range), float(self.ent_coef)
         a.mb_ratio = float(self.mini_batch_size / self.batch_size)
         if self.policy_type == 2:
@@ -300,7 +342,8 @@ class PPOLearner(object):
         n_slices = self.batch_size // self.mini_batch_size
         runs = fuse_runs(slices_for_rank(max(1, n_slices), rank, world), self.max_fused_minibatches)
         self._fused_rows = self.mini_batch_size * max([cnt for _, cnt in runs] or [1])
-        nbytes = int(N.lib().rlppo_minibatch_workspace_bytes_for(pa.dims_c, pa.n_layers, va.dims_c, va.n_layers, self._fused_rows, a.precision))
+        size_fn = N.lib().rlppo_minibatch_workspace_bytes_for if self._critic_rows is None else N.lib().rlppo_minibatch_workspace_bytes_critic
+        nbytes = int(size_fn(pa.dims_c, pa.n_layers, va.dims_c, va.n_layers, self._fused_rows, a.precision))
         nbytes = (nbytes + 255) // 256 * 256
         ws = self._ws.get(nbytes * self.n_slots)
         self._slot_ws = [ws.data_ptr() + i * nbytes for i in range(self.n_slots)]
@@ -317,7 +360,8 @@ class PPOLearner(object):
         general loss kernel), and so does every masked multi-discrete pass; every other policy through the plain entry point.
         A tanh / ELU network (LayerSizes): every head through rlppo_ppo_minibatch_ex, which carries both activations."""
         pa, va = self.policy.arena, self.value_net.arena
-        if pa.hidden_act or va.hidden_act:
+        crit = getattr(self, "_critic_rows", None)
+        if pa.hidden_act or va.hidden_act or crit is not None:
             ext = N.MinibatchExt()
             ext.pol_hidden_act, ext.val_hidden_act = pa.hidden_act, va.hidden_act
             if self.policy_type == 3:
@@ -326,6 +370,8 @@ class PPOLearner(object):
                 ext.scratch, ext.scratch_bytes = self._diag_scratch.data_ptr() + args.slot * sb, sb
             elif self.policy_type == 1 and (self.policy.md_nvec is not None or args.action_mask):
                 ext.md_nvec, ext.md_heads = ctypes.cast(self.policy._nvec_c, ctypes.POINTER(ctypes.c_int32)), self.policy.n_heads
+            if crit is not None:   # the buffer holds critic_states: the critic reads its own matrix
+                return N.lib().rlppo_ppo_minibatch_critic(st, ctypes.byref(args), ctypes.byref(ext), ctypes.byref(crit))
             return N.lib().rlppo_ppo_minibatch_ex(st, ctypes.byref(args), ctypes.byref(ext))
         if self.policy_type == 3:   # log_std and its gradient: the tail of the policy's arena, behind the layers
             pa, sb = self.policy.arena, self._diag_scratch_bytes
@@ -353,7 +399,13 @@ class PPOLearner(object):
         self.lr_schedule, self.desired_kl, self.lr_bounds = lr_schedule, desired_kl, lr_bounds
         self.report_learning_rates = lr_schedule != "constant"
 
-    def _check_options(self):
+    def _check_options(self, exp=None):
+        # separate critic rows update in fp32 or x3: the bf16 gather writes one bf16 image, of the policy's rows
+        if getattr(self, "critic_obs_space_size", None) is not None or (exp is not None and getattr(exp, "critic_width", None) is not None):
+            prec = self.update_precision or {0: "fp32", 1: "bf16", 2: "x3"}[int(N.lib().rlppo_get_update_precision())]
+            if prec == "bf16":
+                raise ValueError("update_precision='bf16' with separate critic observations (ObsSizes / critic_states): the "
+                                 "bf16 gather writes one bf16 image, of the policy's rows -- use 'fp32' or 'x3'")
         # a tanh / ELU network updates in fp32: the bf16 and split-bf16 kernels carry the ReLU bitmask by construction
         acts = {m.hidden_activation for m in (self.policy, self.value_net)} - {"relu"}
         if acts:
@@ -431,7 +483,7 @@ class PPOLearner(object):
         drives it with torch.distributed's all-reduce; dp.run_virtual_ranks drives the generators of N replicas in ONE process
         (the 8-way partition of BASELINE configs[3] on a one-GPU box).  With world == 1 it never yields."""
         L = N.lib()
-        self._check_options()
+        self._check_options(exp)
         pa, va = self.policy.arena, self.value_net.arena
         B, MB = self.batch_size, self.mini_batch_size
         n_slices = B // MB
