@@ -378,6 +378,34 @@ int rlppo_gae_boot(void *stream, const float *rews, const float *dones, const fl
                    const float *boot_values, int64_t n, double gamma, double lmbda, float return_std,
                    float *value_targets, float *advantages, float *returns, void *workspace, size_t ws_bytes);
 
+/* [vnorm] rlppo_gae_boot on NORMALISED values (value normalisation: the critic is trained on standardised value targets, so what it
+ * puts out is v^ = (V - mu) / sigma).  value_scale: DEVICE float[4] = {mu, 1/sigma, sigma, 0}, 16-byte aligned, as
+ * rlppo_value_norm_update publishes it.  Every value the scan reads -- values[t], values[t + 1] and boot_values[t] -- is first taken
+ * to real units as V = fmaf(v^, value_scale[2], value_scale[0]): ONE float32 fused multiply-add, spelled out (it does not depend on
+ * the build's contraction setting), with the two floats read once per workgroup.  Everything behind it is rlppo_gae_boot: the
+ * outputs (value_targets, advantages, returns) are in REAL units.  boot_values may be NULL (the plain scan on normalised values).
+ * value_scale == NULL is exactly rlppo_gae_boot, launch for launch, with the kernels it always ran; value_scale = {0, 1, 1, 0} runs
+ * the normalised kernels and gives the same bits.  Same workspace, alignment rules, forms (one launch; two under stream capture --
+ * a replay reads value_scale as it stands then), bounded look-back wait and timeout word.  A value_scale that is not 16-byte
+ * aligned is RLPPO_ERR_ARG before any HIP call. */
+int rlppo_gae_norm(void *stream, const float *rews, const float *dones, const float *truncated, const float *values,
+                   const float *boot_values, const float *value_scale, int64_t n, double gamma, double lmbda, float return_std,
+                   float *value_targets, float *advantages, float *returns, void *workspace, size_t ws_bytes);
+
+/* [vnorm] The running statistic of the value targets, advanced by one batch on the device (rl_games' normalize_value / RunningMeanStd;
+ * PopArt without its weight-preserving step).  targets: DEVICE float[n].  state: DEVICE double[4] = {count, mean, M2, rejected},
+ * 8-byte aligned, zero for a fresh statistic.  scale: DEVICE float[4], 16-byte aligned, what rlppo_gae_norm and
+ * rlppo_ppo_minibatch_vnorm read: {mu, 1/sigma, sigma, 0} with sigma = sqrt(M2 / count + 1e-5) (population variance), each entry
+ * computed in double and rounded once; the owner of a fresh statistic fills it with {0, 1, 1, 0}.  ONE launch: every workgroup sums
+ * (x - x_0) and its square in double, the workgroup that arrives last (an atomic ticket; nobody waits) adds the slots in slot order,
+ * forms n_b = n, mean_b, M2_b and merges with Chan's formula
+ *     delta = mean_b - mean;  tot = count + n_b;  mean += delta * n_b / tot;  M2 += M2_b + delta^2 * count * n_b / tot
+ * and writes scale.  Bit-reproducible, no floating-point atomics.  A batch whose sums are not finite (a NaN or infinite target)
+ * leaves state[0..2] and scale as they are and adds 1 to state[3].  ws: RLPPO_VALUE_NORM_WS_BYTES of device memory zeroed once by
+ * its owner (every call leaves it armed).  n <= 0, a NULL pointer or a misaligned one is RLPPO_ERR_ARG before any HIP call. */
+#define RLPPO_VALUE_NORM_WS_BYTES 4096
+int rlppo_value_norm_update(void *stream, const float *targets, int64_t n, double *state, float *scale, void *ws);
+
 /* -------------------------------------------------------------------------------------- PPO update */
 
 size_t rlppo_minibatch_workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims,
@@ -539,6 +567,20 @@ typedef struct rlppo_critic_rows {
 size_t rlppo_minibatch_workspace_bytes_critic(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
                                               int64_t mb, int32_t precision);
 int rlppo_ppo_minibatch_critic(void *stream, const rlppo_minibatch_args *args, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic);
+
+/* [vnorm] The same pass with the critic trained on normalised value targets (an added entry point: the structs and the ABI version stay
+ * as they are).  vnorm->scale: DEVICE float[4] = {mu, 1/sigma, sigma, 0}, 16-byte aligned (rlppo_value_norm_update).  vnorm == NULL or
+ * vnorm->scale == NULL is exactly rlppo_ppo_minibatch_critic(stream, args, ext, critic).  Otherwise the critic's output v^ is a
+ * normalised value and the value loss reads the buffer's real-unit target as t^ = (target - mu) * (1/sigma) -- a float32 subtraction,
+ * then a float32 multiplication -- and is (v^ - t^)^2; with args->value_clip > 0 the clipping happens in normalised units around
+ * v^_old = (fl32(target - A) - mu) * (1/sigma), the rest as in rlppo_ppo_minibatch.  RLPPO_STAT_VLOSS is then in normalised units.
+ * Nothing else of the pass changes: the same workspace, the same launches, every head, mask, hidden activation, precision (the value
+ * loss is fp32 on whatever the forward produced), critic rows, slot and ring as before. */
+typedef struct rlppo_value_norm {
+    const float *scale;
+} rlppo_value_norm;
+int rlppo_ppo_minibatch_vnorm(void *stream, const rlppo_minibatch_args *args, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
+                              const rlppo_value_norm *vnorm);
 
 /* Orders `stream` after every minibatch enqueued through non-zero slots since the last join (call it before the
  * gradient all-reduce / rlppo_clip_adam).  Independent minibatches of one batch only meet in the gradient arena

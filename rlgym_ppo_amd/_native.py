@@ -20,6 +20,7 @@ OPT_SYNC_BYTES = 16384  # RLPPO_OPT_SYNC_BYTES
 OPT_SYNC_TIMEOUT_WORD = 2  # uint32 index of the barrier-timeout counter in the sync block
 REPORT_WS_BYTES = 4096  # RLPPO_REPORT_WS_BYTES
 ADV_STATS_WS_BYTES = 4096  # RLPPO_ADV_STATS_WS_BYTES
+VALUE_NORM_WS_BYTES = 4096  # RLPPO_VALUE_NORM_WS_BYTES
 REPORT_OUT_DOUBLES = N_STATS + 4  # RLPPO_REPORT_OUT_DOUBLES
 EXP_LINK_HEADER = 64  # RLPPO_EXP_LINK_HEADER
 MAX_SLOTS = 8
@@ -84,6 +85,11 @@ class MinibatchExt(ctypes.Structure):
 class CriticRows(ctypes.Structure):
     """struct rlppo_critic_rows (include/rlppo.h, "[critic rows]")."""
     _fields_ = [("states", c_void_p), ("ld_states", c_int64)]
+
+
+class ValueNormArg(ctypes.Structure):
+    """struct rlppo_value_norm (include/rlppo.h, "[vnorm]")."""
+    _fields_ = [("scale", c_void_p)]
 
 
 class Gather2Args(ctypes.Structure):
@@ -197,6 +203,9 @@ SIGNATURES = {
                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "rlppo_gae_boot": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_float,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "rlppo_gae_norm": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_float,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "rlppo_value_norm_update": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "rlppo_minibatch_workspace_bytes": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64]),
     "rlppo_minibatch_workspace_bytes_for": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
     "rlppo_ppo_minibatch": (c_int32, [c_void_p, POINTER(MinibatchArgs)]),
@@ -206,6 +215,7 @@ SIGNATURES = {
     "rlppo_ppo_minibatch_ex": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt)]),
     "rlppo_minibatch_workspace_bytes_critic": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
     "rlppo_ppo_minibatch_critic": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows)]),
+    "rlppo_ppo_minibatch_vnorm": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows), POINTER(ValueNormArg)]),
     "rlppo_ppo_join": (c_int32, [c_void_p]),
     "rlppo_kl_slots_doubles": (c_int64, [c_int64]),
     "rlppo_adv_stats": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),

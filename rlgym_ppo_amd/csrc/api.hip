@@ -513,6 +513,32 @@ int rlppo_gae_boot(void *stream, const float *rews, const float *dones, const fl
                       advantages, returns, workspace, ws_bytes);
 }
 
+// [vnorm] the scan on normalised values; no scale: rlppo_gae_boot (no boot values either: rlppo_gae)
+int rlppo_gae_norm(void *stream, const float *rews, const float *dones, const float *truncated, const float *values,
+                   const float *boot_values, const float *value_scale, int64_t n, double gamma, double lmbda, float return_std,
+                   float *value_targets, float *advantages, float *returns, void *workspace, size_t ws_bytes) {
+    if (!value_scale)
+        return rlppo_gae_boot(stream, rews, dones, truncated, values, boot_values, n, gamma, lmbda, return_std, value_targets, advantages,
+                              returns, workspace, ws_bytes);
+    if (n == 0) return 0;
+    RLPPO_CHECK_ARG(n > 0 && rews && dones && truncated && values && value_targets && advantages && returns && workspace,
+                    "gae_norm: bad argument");
+    return launch_gae((hipStream_t)stream, rews, dones, truncated, values, boot_values, n, gamma, lmbda, return_std, value_targets,
+                      advantages, returns, workspace, ws_bytes, value_scale);
+}
+
+int rlppo_value_norm_update(void *stream, const float *targets, int64_t n, double *state, float *scale, void *ws) {
+    RLPPO_CHECK_ARG(n >= 1, "value_norm_update: n=%ld < 1", (long)n);
+    RLPPO_CHECK_ARG(targets != nullptr, "value_norm_update: targets is NULL");
+    RLPPO_CHECK_ARG(state != nullptr, "value_norm_update: state is NULL");
+    RLPPO_CHECK_ARG(scale != nullptr, "value_norm_update: scale is NULL");
+    RLPPO_CHECK_ARG(ws != nullptr, "value_norm_update: ws is NULL");
+    RLPPO_CHECK_ARG((uintptr_t)targets % 4 == 0, "value_norm_update: targets must be 4-byte aligned");
+    RLPPO_CHECK_ARG((uintptr_t)state % 8 == 0, "value_norm_update: state must be 8-byte aligned");
+    RLPPO_CHECK_ARG((uintptr_t)scale % 16 == 0, "value_norm_update: scale must be 16-byte aligned");
+    RLPPO_CHECK_ARG((uintptr_t)ws % 8 == 0, "value_norm_update: ws must be 8-byte aligned");
+    return launch_value_norm_update((hipStream_t)stream, targets, n, state, scale, ws);
+}
 
 int rlppo_clip_adam(void *stream, float *params, float *grads, float *exp_avg, float *exp_avg_sq, int64_t n,
                     double max_norm, double lr, double beta1, double beta2, double eps, int64_t step, double *gnorm2) {

@@ -224,6 +224,9 @@ struct LossCfg {
     float vclip = 0.f;                    // > 0: clipped value prediction around v_old = target - A
     double *kl_slots = nullptr;           // per-workgroup sums of the KL term of the policy loss launch (rlppo_kl_gate)
     const unsigned *stop_word = nullptr;  // non-zero: the launch adds nothing to the report statistics
+    // [vnorm] value normalisation (rlppo_ppo_minibatch_vnorm): {mu, 1/sigma, sigma, 0} in device memory; the critic's output is a
+    // normalised value and the value loss reads the target (and v_old under clipping) as (x - mu) * (1/sigma)
+    const float *vnorm = nullptr;
 };
 // logical -> physical row of the ring-resident experience (i < cap, base < cap: one conditional subtraction)
 __host__ __device__ __forceinline__ int64_t ring_row(int64_t i, int64_t base, int64_t cap) {
@@ -329,9 +332,10 @@ void set_gae_spin_limit(int v);
 void set_gae_oversubscribe(int v);
 void set_fused_spin_limit(int v);
 void set_fused_test_hold(int v);
-// (rews, dones, truncated, values, boot_values or null, n, gamma, lambda, return_std, value_targets, advantages, returns, ws, bytes)
+// (rews, dones, truncated, values, boot_values or null, n, gamma, lambda, return_std, value_targets, advantages, returns, ws, bytes,
+//  value_scale or null: [vnorm] the values are normalised ones, V = fmaf(v, value_scale[2], value_scale[0]))
 int launch_gae(hipStream_t, const float *, const float *, const float *, const float *, const float *, int64_t, double, double, float,
-               float *, float *, float *, void *, size_t);
+               float *, float *, float *, void *, size_t, const float *value_scale = nullptr);
 
 // optim.hip -------------------------------------------------------------------------------------------
 int launch_pack(hipStream_t, const NetLayout &, const float *, float *);
@@ -350,6 +354,7 @@ int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *
                            const double *const *lr = nullptr, const double *bc1 = nullptr);  // [lr] lr[k]: device rate of network k (NULL: step_size[k]), bc1[k] its divisor
 int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float *adv, int64_t ring_base, int64_t ring_cap, float *out,
                      void *ws);                             // [ABI 7] rlppo_adv_stats
+int launch_value_norm_update(hipStream_t st, const float *targets, int64_t n, double *state, float *scale, void *ws);  // [vnorm] rlppo_value_norm_update
 int launch_kl_gate(hipStream_t st, const rlppo_kl_gate_args &a);  // [ABI 7] rlppo_kl_gate
 int launch_kl_gate_lr(hipStream_t st, const rlppo_kl_gate_args &a, const rlppo_lr_adapt_args &l);  // [lr] rlppo_kl_gate_lr
 int launch_welford(hipStream_t st, const float *x, int64_t ld, int64_t n, int d, void *mean, void *m2, long long count0, int state_f64);

@@ -22,6 +22,12 @@
 // other entries may hold anything); it is read as a fifth input stream beside the other four and selected by the flags
 // (BOOT_DENSE below: why not a sparse load).  Every kernel has a BOOT instantiation and a call without boot values launches
 // the plain ones.
+//
+// NORM form (rlppo_gae_norm with a value_scale): the critic's outputs are NORMALISED values v^ and every value the scan reads --
+// values[t], values[t + 1] (the look-ahead window's loads included) and boot[t] -- is first taken to real units as
+// V = fmaf(v^, sigma, mu), one explicit float32 fma, with {mu, sigma} = value_scale[0], value_scale[2] read once per workgroup
+// (uniform: two scalar loads).  Everything behind that point is the code above, so the outputs are in real units as always.  NORM
+// is a template flag beside BOOT; a call without a scale launches the instantiations it always did.
 #include <atomic>
 #include <chrono>
 
@@ -174,19 +180,48 @@ __device__ __forceinline__ void load_raw(const float *__restrict__ rews, const f
     }
 }
 
+// NORM: {mu, sigma} of a workgroup (uniform loads); real-unit value of a normalised one.  The fma is spelled out: no dependence on
+// the contraction setting of the build.
+struct VScale {
+    float mu, sd;
+};
+template <bool NORM>
+__device__ __forceinline__ VScale load_vscale(const float *__restrict__ vscale) {
+    if constexpr (NORM) return VScale{vscale[0], vscale[2]};
+    return VScale{0.f, 1.f};
+}
+template <bool NORM>
+__device__ __forceinline__ float denorm(float v, const VScale &k) {
+    if constexpr (NORM) return fmaf(v, k.sd, k.mu);
+    return v;
+}
 // the V_{t+1} of one step: its own bootstrap value where the step is truncated and not done (BOOT), else the next entry of values
-template <bool BOOT>
-__device__ __forceinline__ float next_value(float d, float tr, float v1, const float *__restrict__ boot, int64_t t) {
+template <bool BOOT, bool NORM = false>
+__device__ __forceinline__ float next_value(float d, float tr, float v1, const float *__restrict__ boot, int64_t t, const VScale &k = VScale{0.f, 1.f}) {
     if constexpr (BOOT) {
-        if (tr != 0.f && d == 0.f) v1 = boot[t];
+        if (tr != 0.f && d == 0.f) v1 = denorm<NORM>(boot[t], k);
     }
     return v1;
 }
 __device__ __forceinline__ float next_value_dense(float d, float tr, float v1, float b) { return tr != 0.f && d == 0.f ? b : v1; }
 
-template <bool BOOT>
+// every loaded value (and dense bootstrap value) of a thread's steps to real units; entries past the end are never used
+template <bool NORM, bool DENSE>
+__device__ __forceinline__ void denorm_raw(RawSteps &w, const VScale &k) {
+    if constexpr (NORM) {
+#pragma unroll
+        for (int e = 0; e <= GAE_EPT; ++e) w.v[e] = denorm<true>(w.v[e], k);
+        if constexpr (DENSE) {
+#pragma unroll
+            for (int e = 0; e < GAE_EPT; ++e) w.bv[e] = denorm<true>(w.bv[e], k);
+        }
+    }
+}
+
+// (NORM: w holds real-unit values already -- denorm_raw; vs only serves the sparse bootstrap load)
+template <bool BOOT, bool NORM = false>
 __device__ __forceinline__ void make_steps(const RawSteps &w, int64_t t0, int64_t n, const GaeParams &p, const float *__restrict__ boot,
-                                           Steps &s) {
+                                           Steps &s, const VScale &vs = VScale{0.f, 1.f}) {
     const float *r = w.r, *d = w.d, *tr = w.tr, *v = w.v;
     s.mbits = 0;
 #pragma unroll
@@ -196,7 +231,7 @@ __device__ __forceinline__ void make_steps(const RawSteps &w, int64_t t0, int64_
             float rn = r[e];
             if (p.use_std) rn = fminf(fmaxf(r[e] / p.ret_std, -10.f), 10.f);
             const float v1 = BOOT && BOOT_DENSE ? next_value_dense(d[e], tr[e], v[e + 1], w.bv[e])
-                                                : next_value<BOOT>(d[e], tr[e], v[e + 1], boot, t0 + e);
+                                                : next_value<BOOT, NORM>(d[e], tr[e], v[e + 1], boot, t0 + e, vs);
             s.b_adv[e] = ((double)rn + p.gamma * (double)v1 * (double)ndf) - (double)v[e];
             s.mbits |= (ndf * ntf != 0.f ? 1u : 0u) << e;  // (0/1 flags: the float product is the exact 0/1 the reference's double one is)
             s.r[e] = r[e];
@@ -208,13 +243,15 @@ __device__ __forceinline__ void make_steps(const RawSteps &w, int64_t t0, int64_
     }
 }
 
-template <bool BOOT>
+template <bool BOOT, bool NORM = false>
 __device__ __forceinline__ void load_steps(const float *__restrict__ rews, const float *__restrict__ dones,
                                            const float *__restrict__ trunc, const float *__restrict__ values,
-                                           int64_t t0, int64_t n, const GaeParams &p, const float *__restrict__ boot, Steps &s) {
+                                           int64_t t0, int64_t n, const GaeParams &p, const float *__restrict__ boot, Steps &s,
+                                           const VScale &vs = VScale{0.f, 1.f}) {
     RawSteps w;
     load_raw<BOOT && BOOT_DENSE>(rews, dones, trunc, values, t0, n, w, boot);
-    make_steps<BOOT>(w, t0, n, p, boot, s);
+    denorm_raw<NORM, BOOT && BOOT_DENSE>(w, vs);
+    make_steps<BOOT, NORM>(w, t0, n, p, boot, s, vs);
 }
 
 __device__ __forceinline__ double coef_adv(const Steps &s, int e, const GaeParams &p) { return (s.mbits >> e) & 1u ? p.gl : 0.0; }
@@ -248,22 +285,24 @@ __device__ __forceinline__ Aff2 block_reduce(Aff2 v, Aff2 *lds4) {
     return compose(compose(lds4[0], lds4[1]), compose(lds4[2], lds4[3]));
 }
 
-template <bool BOOT>
+template <bool BOOT, bool NORM>
 __global__ __launch_bounds__(GAE_THREADS) void gae_summary_kernel(const float *__restrict__ rews,
                                                                    const float *__restrict__ dones,
                                                                    const float *__restrict__ trunc,
                                                                    const float *__restrict__ values, int64_t n,
                                                                    GaeParams p, Aff2 *__restrict__ summaries,
-                                                                   const float *__restrict__ boot) {
+                                                                   const float *__restrict__ boot,
+                                                                   const float *__restrict__ vscale) {
     __shared__ Aff2 lds4[4];
     const int64_t t0 = ((int64_t)blockIdx.x * GAE_THREADS + threadIdx.x) * GAE_EPT;
+    const VScale vs = load_vscale<NORM>(vscale);
     Steps s;
-    load_steps<BOOT>(rews, dones, trunc, values, t0, n, p, boot, s);
+    load_steps<BOOT, NORM>(rews, dones, trunc, values, t0, n, p, boot, s, vs);
     const Aff2 c = block_reduce(thread_composite(s, p), lds4);
     if (threadIdx.x == 0) summaries[blockIdx.x] = c;
 }
 
-template <bool BOOT>
+template <bool BOOT, bool NORM>
 __global__ __launch_bounds__(GAE_THREADS) void gae_apply_kernel(const float *__restrict__ rews,
                                                                  const float *__restrict__ dones,
                                                                  const float *__restrict__ trunc,
@@ -272,15 +311,17 @@ __global__ __launch_bounds__(GAE_THREADS) void gae_apply_kernel(const float *__r
                                                                  int n_blocks, float *__restrict__ vt_out,
                                                                  float *__restrict__ adv_out,
                                                                  float *__restrict__ ret_out,
-                                                                 const float *__restrict__ boot) {
+                                                                 const float *__restrict__ boot,
+                                                                 const float *__restrict__ vscale) {
     __shared__ Aff2 lds4[4];
     __shared__ Aff2 wave_tot[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t t0 = ((int64_t)blockIdx.x * GAE_THREADS + threadIdx.x) * GAE_EPT;
+    const VScale vs = load_vscale<NORM>(vscale);
 
     // issue this block's loads first; the carry look-up below overlaps with them
     Steps s;
-    load_steps<BOOT>(rews, dones, trunc, values, t0, n, p, boot, s);
+    load_steps<BOOT, NORM>(rews, dones, trunc, values, t0, n, p, boot, s, vs);
 
     // ---- carry-in: x at the first step of block+1 = (composite of every block to the right)(0)
     Aff2 right = aff_identity();
@@ -466,7 +507,7 @@ __device__ __forceinline__ void resolve_carry(const int chunk, const int n_block
 #define GAE_STORE_T_V 1
 #endif
 constexpr bool STORE_T = GAE_STORE_T_V;  // lane-contiguous output stores through an in-wave LDS transpose ([r4]; 0 = rounds 1-3's shape, for A/B builds)
-template <bool LOOP, bool BOOT>
+template <bool LOOP, bool BOOT, bool NORM>
 __global__ __launch_bounds__(GAE_THREADS, 4) void gae_lookback_kernel(const float *__restrict__ rews,
                                                                     const float *__restrict__ dones,
                                                                     const float *__restrict__ trunc,
@@ -477,7 +518,8 @@ __global__ __launch_bounds__(GAE_THREADS, 4) void gae_lookback_kernel(const floa
                                                                     float *__restrict__ vt_out,
                                                                     float *__restrict__ adv_out,
                                                                     float *__restrict__ ret_out,
-                                                                    const float *__restrict__ boot) {
+                                                                    const float *__restrict__ boot,
+                                                                    const float *__restrict__ vscale) {
     __shared__ Aff2 wave_tot[4];
     __shared__ Aff2 wave_la[4];  // look-ahead window of the next chunk: per-wave composites (64 steps each)
     __shared__ double s_carry[2];
@@ -491,6 +533,7 @@ __global__ __launch_bounds__(GAE_THREADS, 4) void gae_lookback_kernel(const floa
     // possible when chunk 0's fast path needs nobody -- would have read the NEXT launch's tag and never matched its
     // neighbours.)  A captured launch would replay a frozen tag, so launch_gae takes the two-launch form under capture.
     const unsigned TAG_AGG = tag, TAG_INC = tag;
+    const VScale vs = load_vscale<NORM>(vscale);  // (once per workgroup, also in the LOOP form)
     // Chunks are taken right-to-left, grid-strided.  A chunk waits only on chunks to its right, i.e. on work of this
     // same round owned by lower block ids or on earlier rounds; the launcher sizes the grid to the number of
     // co-resident workgroups, so every awaited chunk belongs to a running workgroup whatever the dispatch order.
@@ -519,15 +562,19 @@ __global__ __launch_bounds__(GAE_THREADS, 4) void gae_lookback_kernel(const floa
     {   // the window's composite while the chunk's own loads are still in flight (the window's were issued first)
         Aff2 l1 = aff_identity();  // steps past the end: identity (x = 0 there is handled by covers_all in resolve_carry)
         // (BOOT: a truncated step of the window contributes its own bootstrap value, as it does in its own chunk's scan)
+        // (NORM: the window's three values to real units, as in the chunk that owns them)
         if (l_ok)
-            l1 = step_affine(l_r, l_d, l_t, l_v,
-                             BOOT && BOOT_DENSE ? next_value_dense(l_d, l_t, l_v1, l_b) : next_value<BOOT>(l_d, l_t, l_v1, boot, lt0), p);
+            l1 = step_affine(l_r, l_d, l_t, denorm<NORM>(l_v, vs),
+                             BOOT && BOOT_DENSE ? next_value_dense(l_d, l_t, denorm<NORM>(l_v1, vs), denorm<NORM>(l_b, vs))
+                                                : next_value<BOOT, NORM>(l_d, l_t, denorm<NORM>(l_v1, vs), boot, lt0, vs),
+                             p);
         const Aff2 ls = wave_suffix_scan(l1, lane);
         if (lane == 0) wave_la[wave] = ls;
     }
     __builtin_amdgcn_sched_barrier(0);
     Steps s;
-    make_steps<BOOT>(raw, t0, n, p, boot, s);
+    denorm_raw<NORM, BOOT && BOOT_DENSE>(raw, vs);
+    make_steps<BOOT, NORM>(raw, t0, n, p, boot, s, vs);
     const Aff2 mine = thread_composite(s, p);
     // Who will ever read this chunk's records?  Only the chunk to the left, and only if its look-ahead over OUR first
     // LOOKAHEAD steps finds no trajectory end (a chunk whose own carry came from the fast path publishes its inclusive value
@@ -623,16 +670,17 @@ void set_gae_spin_limit(int v) { g_gae_spin_limit = v < 0 ? LB_SPIN_LIMIT : (uns
 // region for its per-chunk composites (32 B per chunk)
 size_t gae_workspace_bytes(int64_t n) { return 16 + (size_t)(cdiv(n > 0 ? n : 1, GAE_BLOCK)) * LB_STRIDE * sizeof(u64); }
 
-// BOOT = false: `boot` is ignored (null) and the launches are the plain instantiations
-template <bool BOOT>
+// BOOT = false: `boot` is ignored (null) and the launches are the plain instantiations; NORM = false: the same for `vscale`
+template <bool BOOT, bool NORM>
 static int launch_gae_form(hipStream_t st, const float *rews, const float *dones, const float *trunc, const float *values,
-                           const float *boot, int64_t n, double gamma, double lmbda, float ret_std, float *vt, float *adv, float *ret,
-                           void *ws, size_t ws_bytes) {
+                           const float *boot, const float *vscale, int64_t n, double gamma, double lmbda, float ret_std, float *vt,
+                           float *adv, float *ret, void *ws, size_t ws_bytes) {
     if (n == 0) return 0;
     RLPPO_CHECK_ARG(n > 0, "gae: n=%ld", (long)n);
     RLPPO_CHECK_ARG(((uintptr_t)rews | (uintptr_t)dones | (uintptr_t)trunc | (uintptr_t)values | (uintptr_t)vt |
                      (uintptr_t)adv | (uintptr_t)ret | (uintptr_t)ws | (uintptr_t)boot) % 16 == 0,
                     "gae: arrays and workspace must be 16-byte aligned");
+    RLPPO_CHECK_ARG((uintptr_t)vscale % 16 == 0, "gae: value_scale must be 16-byte aligned");
     if (ws_bytes < gae_workspace_bytes(n)) {
         set_error("gae: workspace %zu < %zu bytes", ws_bytes, gae_workspace_bytes(n));
         return RLPPO_ERR_WORKSPACE;
@@ -661,7 +709,7 @@ static int launch_gae_form(hipStream_t st, const float *rews, const float *dones
             int per_cu = 0;
             hipDeviceProp_t prop;
             RLPPO_HIP(hipGetDeviceProperties(&prop, dev));
-            RLPPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gae_lookback_kernel<true, BOOT>, GAE_THREADS, 0));
+            RLPPO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gae_lookback_kernel<true, BOOT, NORM>, GAE_THREADS, 0));
             // the occupancy API over-reports by one block per CU only in the SGPR-limited 7-8 blocks/CU regime
             // (MI355X_MICROARCH.md "Residency and cooperative launch"); this kernel is VGPR-limited far below that
             per_cu = per_cu > 6 ? 6 : (per_cu < 1 ? 1 : per_cu);
@@ -687,26 +735,30 @@ static int launch_gae_form(hipStream_t st, const float *rews, const float *dones
         }
         unsigned tag = g_tag.fetch_add(1, std::memory_order_relaxed) + 1;
         if (tag == 0) tag = g_tag.fetch_add(1, std::memory_order_relaxed) + 1;
-        auto *kern = grid == nb ? gae_lookback_kernel<false, BOOT> : gae_lookback_kernel<true, BOOT>;
+        auto *kern = grid == nb ? gae_lookback_kernel<false, BOOT, NORM> : gae_lookback_kernel<true, BOOT, NORM>;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, state, tag, g_gae_spin_limit,
-                           hdr + 1, nb, vt, adv, ret, boot);
+                           hdr + 1, nb, vt, adv, ret, boot, vscale);
         RLPPO_LAUNCH_CHECK();
         return 0;
     }
     Aff2 *summ = reinterpret_cast<Aff2 *>(reinterpret_cast<char *>(ws) + 16);
-    hipLaunchKernelGGL(gae_summary_kernel<BOOT>, dim3(nb), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, summ, boot);
+    hipLaunchKernelGGL((gae_summary_kernel<BOOT, NORM>), dim3(nb), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, summ, boot,
+                       vscale);
     RLPPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gae_apply_kernel<BOOT>, dim3(nb), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, summ, nb,
-                       vt, adv, ret, boot);
+    hipLaunchKernelGGL((gae_apply_kernel<BOOT, NORM>), dim3(nb), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, summ, nb,
+                       vt, adv, ret, boot, vscale);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }
 
-// boot == nullptr: exactly the plain scan
+// boot == nullptr: exactly the plain scan; vscale == nullptr: the values are real-unit values, as they always were
 int launch_gae(hipStream_t st, const float *rews, const float *dones, const float *trunc, const float *values, const float *boot,
-               int64_t n, double gamma, double lmbda, float ret_std, float *vt, float *adv, float *ret, void *ws, size_t ws_bytes) {
-    if (boot) return launch_gae_form<true>(st, rews, dones, trunc, values, boot, n, gamma, lmbda, ret_std, vt, adv, ret, ws, ws_bytes);
-    return launch_gae_form<false>(st, rews, dones, trunc, values, nullptr, n, gamma, lmbda, ret_std, vt, adv, ret, ws, ws_bytes);
+               int64_t n, double gamma, double lmbda, float ret_std, float *vt, float *adv, float *ret, void *ws, size_t ws_bytes,
+               const float *vscale) {
+#define RLPPO_GAE_FORM(B, V) launch_gae_form<B, V>(st, rews, dones, trunc, values, boot, vscale, n, gamma, lmbda, ret_std, vt, adv, ret, ws, ws_bytes)
+    if (vscale) return boot ? RLPPO_GAE_FORM(true, true) : RLPPO_GAE_FORM(false, true);
+    return boot ? RLPPO_GAE_FORM(true, false) : RLPPO_GAE_FORM(false, false);
+#undef RLPPO_GAE_FORM
 }
 
 }  // namespace rlppo

@@ -419,10 +419,19 @@ int64_t kl_slots_doubles(int64_t mb) {
 // value loss for one row: writes dL/dv in place, returns (v - t)^2.  [ABI 7] vclip > 0: Stable-Baselines3's clipped prediction
 // v_pred = v_old + clamp(v - v_old, -c, c) around v_old = target - A (the buffer's target is V + A), loss (v_pred - t)^2, gradient
 // where |v - v_old| <= c (torch.clamp passes it at its bounds)
+// [vnorm] c.vnorm = {mu, 1/sigma, ...}: v is a NORMALISED value; the target becomes (target - mu) * (1/sigma) -- a float32 subtraction,
+// then a float32 multiplication -- and under clipping so does v_old = target - A (rl_games: clipping in normalised units).  The rest
+// of the row is the code it always was, on the normalised numbers.
 __device__ __forceinline__ float value_row(float *vout_row, float target, float adv, const LossCfg &c) {
     const float v = vout_row[0];
+    float v_old_n = 0.f;
+    if (c.vnorm) {
+        const float mu = c.vnorm[0], inv_sd = c.vnorm[1];
+        if (c.vclip > 0.f) v_old_n = __fmul_rn(__fsub_rn(__fsub_rn(target, adv), mu), inv_sd);
+        target = __fmul_rn(__fsub_rn(target, mu), inv_sd);
+    }
     if (c.vclip > 0.f) {
-        const float v_old = target - adv;
+        const float v_old = c.vnorm ? v_old_n : target - adv;
         const float dv = v - v_old;
         const float d = (v_old + fminf(fmaxf(dv, -c.vclip), c.vclip)) - target;
         vout_row[0] = fabsf(dv) <= c.vclip ? c.mb_ratio * (2.f * d * c.inv_mb) : 0.f;

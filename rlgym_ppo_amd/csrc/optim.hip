@@ -1004,6 +1004,93 @@ int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float 
     return 0;
 }
 
+// ----------------------------------------------------------------------------------- [vnorm] value normalisation
+// The running statistic of the value targets (rlppo_value_norm_update): adv_stats_kernel's pattern on a contiguous array.  Every
+// workgroup sums (x - x_0) and (x - x_0)^2 in double over its grid-stride share (shifted sums: a constant batch gives exactly zero),
+// parks the pair in its slot and takes a ticket; the last arriver adds the slots in slot order, forms the batch's n_b, mean_b, M2_b
+// and merges them into state = {count, mean, M2, rejected} with Chan's formula, then publishes scale = {mu, 1/sigma, sigma, 0} with
+// sigma = sqrt(M2 / count + 1e-5) (population variance and epsilon of rl_games' RunningMeanStd), computed in double, rounded once.
+// A batch whose sums are not finite (a NaN or infinite target) changes nothing but state[3], the count of rejected batches.  No
+// floating-point atomics, no spin-wait: the same state and batch give the same bits every run.
+namespace {
+constexpr int VNORM_BLOCKS = 128;
+struct VnormWs {
+    unsigned tickets;
+    unsigned pad[3];
+    double partial[VNORM_BLOCKS][2];
+};
+static_assert(sizeof(VnormWs) <= RLPPO_VALUE_NORM_WS_BYTES, "value norm workspace");
+}  // namespace
+
+__global__ __launch_bounds__(256) void value_norm_update_kernel(const float *__restrict__ x, int64_t n, double *__restrict__ state,
+                                                                float *__restrict__ scale, VnormWs *__restrict__ ws) {
+    const double k0 = (double)x[0];
+    double s[2] = {0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double d = (double)x[i] - k0;
+        s[0] += d;
+        s[1] += d * d;
+    }
+    __shared__ double red[4][2];
+    __shared__ int last;
+    for (int k = 0; k < 2; ++k) {
+        double v = s[k];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ws->partial[blockIdx.x][0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+        ws->partial[blockIdx.x][1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+        __threadfence();
+        last = atomicAdd(&ws->tickets, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __shared__ double slots[VNORM_BLOCKS][2];
+    __threadfence();
+    if (threadIdx.x < 2 * gridDim.x)
+        slots[threadIdx.x >> 1][threadIdx.x & 1] = __hip_atomic_load(&ws->partial[threadIdx.x >> 1][threadIdx.x & 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double t0 = 0.0, t1 = 0.0;
+    for (unsigned b = 0; b < gridDim.x; ++b) {
+        t0 += slots[b][0];
+        t1 += slots[b][1];
+    }
+    // (a NaN / infinite target makes k0 or a sum non-finite: x - x = NaN covers an infinite pivot)
+    if (!(fabs(t0) < INFINITY && fabs(t1) < INFINITY && fabs(k0) < INFINITY)) {
+        state[3] += 1.0;
+    } else {
+        const double nb = (double)n;
+        const double m = t0 / nb;
+        const double mean_b = k0 + m;
+        double m2_b = t1 - t0 * m;
+        m2_b = m2_b > 0.0 ? m2_b : 0.0;
+        const double count = state[0], mean = state[1], m2 = state[2];
+        const double delta = mean_b - mean, tot = count + nb;
+        const double mean_new = mean + delta * nb / tot;
+        const double m2_new = m2 + (m2_b + delta * delta * count * nb / tot);
+        state[0] = tot;
+        state[1] = mean_new;
+        state[2] = m2_new;
+        const double sd = sqrt(m2_new / tot + 1e-5);
+        scale[0] = (float)mean_new;
+        scale[1] = (float)(1.0 / sd);
+        scale[2] = (float)sd;
+        scale[3] = 0.f;
+    }
+    __hip_atomic_store(&ws->tickets, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+int launch_value_norm_update(hipStream_t st, const float *targets, int64_t n, double *state, float *scale, void *ws) {
+    const int64_t blocks = cdiv(n, 256 * 2) < VNORM_BLOCKS ? cdiv(n, 256 * 2) : VNORM_BLOCKS;  // adv_stats' grid: beyond 65,536 targets the workgroups stride
+    hipLaunchKernelGGL(value_norm_update_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, st, targets, n, state, scale,
+                       reinterpret_cast<VnormWs *>(ws));
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
 // The target-KL gate (rlppo_kl_gate): one workgroup.  Thread t adds slots t, t + 256, ... of every pass region in order, a fixed
 // shuffle tree and a fixed sum over the four waves follow, the pass totals are weighted by their mb_ratio in pass order.
 __device__ __forceinline__ double kl_gate_sum(const rlppo_kl_gate_args &g) {

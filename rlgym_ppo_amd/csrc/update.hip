@@ -462,7 +462,7 @@ static int two_chain_pass(const Pass &p) {
 
 // one pass; md_nvec (host, or null = the reference's multi-discrete head) is rlppo_ppo_minibatch_nvec's
 static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads, const DiagHead *diag,
-                         int pol_act, int val_act, const rlppo_critic_rows *critic = nullptr) {
+                         int pol_act, int val_act, const rlppo_critic_rows *critic = nullptr, const float *vnorm = nullptr) {
     // ---- validation: every argument error is reported here, before the first HIP call
     RLPPO_CHECK_ARG(a != nullptr, "ppo_minibatch: null args");
     Pass p;
@@ -493,6 +493,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
                     "ppo_minibatch: null pointer");
     RLPPO_CHECK_ARG(val.L[val.n_layers - 1].out == 1, "ppo_minibatch: critic must have one output");
     RLPPO_CHECK_ARG(a->value_clip >= 0.f && a->value_clip < INFINITY, "ppo_minibatch: value_clip=%g", (double)a->value_clip);
+    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(vnorm) & 15) == 0, "ppo_minibatch_vnorm: vnorm scale must be 16-byte aligned");
     RLPPO_CHECK_ARG(critic || pol.L[0].in == val.L[0].in, "ppo_minibatch: policy and critic observe different sizes");
     if (critic) {  // [critic rows] val_dims[0] is the width of the critic's own matrix
         RLPPO_CHECK_ARG(critic->ld_states >= val.L[0].pin && critic->ld_states % 4 == 0,
@@ -566,6 +567,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     first_layer_rows(*a, critic, pol, val, p.prec, p.w, p.plain, p.rows);
     const bool twin = p.prec == 0 && !p.plain && !critic && (g_paired == 2 || (g_paired == 1 && mb >= PAIRED_MIN_ROWS)) && twin_ok(pol, val, mb);
     p.cfg = loss_cfg(*a);
+    p.cfg.vnorm = vnorm;  // [vnorm] the value loss alone reads it: same plan, same launches
     p.pol_w = p.prec == 1 ? a->pol_packed_r : a->pol_packed;
     p.val_w = p.prec == 1 ? a->val_packed_r : a->val_packed;
     DwList dws;
@@ -664,6 +666,19 @@ int rlppo_ppo_minibatch_critic(void *stream, const rlppo_minibatch_args *a, cons
     const DiagHead d = diag_head(ext->log_std, ext->log_std_grad, ext->scratch, ext->scratch_bytes);
     RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(ext->scratch) & 7) == 0, "ppo_minibatch_critic: scratch must be 8-byte aligned");
     return ppo_minibatch(stream, a, ext->md_nvec, ext->md_heads, diag ? &d : nullptr, ext->pol_hidden_act, ext->val_hidden_act, critic);
+}
+
+// [vnorm] the same call with the critic trained on normalised value targets; no scale: rlppo_ppo_minibatch_critic
+int rlppo_ppo_minibatch_vnorm(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
+                              const rlppo_value_norm *vnorm) {
+    if (!vnorm || !vnorm->scale) return rlppo_ppo_minibatch_critic(stream, a, ext, critic);
+    const rlppo_minibatch_ext none = {};
+    if (!ext) ext = &none;
+    const bool diag = ext->log_std || ext->log_std_grad || ext->scratch || ext->scratch_bytes;
+    const DiagHead d = diag_head(ext->log_std, ext->log_std_grad, ext->scratch, ext->scratch_bytes);
+    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(ext->scratch) & 7) == 0, "ppo_minibatch_vnorm: scratch must be 8-byte aligned");
+    return ppo_minibatch(stream, a, ext->md_nvec, ext->md_heads, diag ? &d : nullptr, ext->pol_hidden_act, ext->val_hidden_act,
+                         critic && critic->states ? critic : nullptr, vnorm->scale);
 }
 
 size_t rlppo_diag_scratch_bytes(int64_t mb, int32_t k) { return diag_scratch_bytes(mb, k); }

@@ -46,6 +46,7 @@ class Learner(object):
             hidden_activation: str = "relu",
             ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
             critic_observations: bool = False,
+            ppo_normalize_value: bool = False,
             per_feature_obs_standardization: bool = False,
             ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
         assert env_create_function is not None, "MUST PROVIDE A FUNCTION TO CREATE RLGYM FUNCTIONS TO INITIALIZE RLGYM-PPO"
@@ -204,6 +205,12 @@ class Learner(object):
             max_grad_norm=ppo_max_grad_norm)
         if self.critic_observations:
             self.agent.value_net = self.ppo_learner.value_net   # its arena stages the critic's observation rows
+        # not in the reference: ppo_normalize_value trains the critic on standardised value targets (rl_games' normalize_value;
+        # PPOLearner.set_value_normalization).  The statistic is checkpoint state (value_norm_running_stats in the book).
+        self.normalize_value = bool(ppo_normalize_value)
+        self._value_norm_host = None   # (mu, sigma, rejected batches) as of the last add_new_experience: its one read-back
+        if self.normalize_value:
+            self.ppo_learner.set_value_normalization(True)
         if ppo_lr_schedule == "adaptive":   # ("linear" is this loop's: the update runs the constant schedule's launches)
             self.ppo_learner.set_lr_schedule("adaptive", ppo_desired_kl, ppo_lr_bounds)
         self.ppo_learner.report_learning_rates = ppo_lr_schedule != "constant"
@@ -239,6 +246,7 @@ class Learner(object):
             "critic_lr": critic_lr, "shm_buffer_size": shm_buffer_size,
             "gae_bootstrap_truncated": self.gae_bootstrap_truncated,  # (a hyper-parameter, not checkpoint state)
             "critic_observations": self.critic_observations,
+            "ppo_normalize_value": self.normalize_value,
         }
 
         self.wandb_run = wandb_run
@@ -307,6 +315,8 @@ class Learner(object):
             report["Collected Steps per Second"] = steps_collected / collection_time
             report["Overall Steps per Second"] = steps_collected / epoch_time
             report["Policy Reward"] = self.agent.average_reward if self.agent.average_reward is not None else np.nan
+            if self.normalize_value and self._value_norm_host is not None:   # ("Value Function Loss" is in normalised units then)
+                report["Value Norm Mean"], report["Value Norm Std"] = self._value_norm_host[0], self._value_norm_host[1]
             self.ts_since_last_save += steps_collected
             reporting.report_metrics(loggable_metrics=report, debug_metrics=None, wandb_run=self.wandb_run)
 
@@ -336,7 +346,12 @@ class Learner(object):
         read-back) get V of their own next state -- process mode: m more rows in the one value pass; vector mode: a value pass
         on the manager's m next-state rows -- scattered into a length-N device buffer for the bootstrap form of the scan.  A
         device-resident vector environment (the manager's bootstrap_dense): the flags exist on the device only, so one value pass over
-        all N next-state rows gives the dense boot_values as they are."""
+        all N next-state rows gives the dense boot_values as they are.
+
+        ppo_normalize_value: the value pass yields NORMALISED values; the scan takes every one of them (bootstrap values included) to
+        real units under the statistic as it stands -- the one the critic was trained under -- so targets, advantages and returns are
+        in real units as always; then the statistic advances with this call's N value targets (one launch) and learn() runs under
+        the new, fixed scale.  mu, sigma and the count of rejected batches ride in the call's one device-to-host read."""
         states, actions, log_probs, rewards, next_states, dones, truncated = experience
         value_net = self.ppo_learner.value_net
         n = states.shape[0]
@@ -388,16 +403,30 @@ class Learner(object):
             torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32))).to(dev)
         rews_d, dones_d, trunc_d = up(rewards), up(dones), up(truncated)
         ret_std = self.return_stats.std[0] if self.standardize_returns else None
+        value_norm = self.ppo_learner.value_norm if self.normalize_value else None
+        gae_kw = {} if boot_values is None else {"boot_values": boot_values}
+        if value_norm is not None:
+            gae_kw["value_scale"] = value_norm.scale
         value_targets, advantages, returns, gae_timeouts = torch_functions.gae_device_deferred(
-            rews_d, dones_d, trunc_d, val_preds, gamma=self.gae_gamma, lmbda=self.gae_lambda, return_std=ret_std,
-            **({} if boot_values is None else {"boot_values": boot_values}))
+            rews_d, dones_d, trunc_d, val_preds, gamma=self.gae_gamma, lmbda=self.gae_lambda, return_std=ret_std, **gae_kw)
+        if value_norm is not None:
+            value_norm.update(value_targets)
 
         # ONE device-to-host read per call: the scan's timeout counter travels with the min(150, N) returns the statistics need
         n_to_increment = min(self.max_returns_per_stats_increment, n) if self.standardize_returns else 0
         parts = [returns[:n_to_increment]] + ([gae_timeouts.float()] if gae_timeouts is not None else [])
+        n_head = n_to_increment + (1 if gae_timeouts is not None else 0)
+        if value_norm is not None:   # mu, sigma, rejected batches (a count: exact in float32 far beyond any run)
+            parts += [value_norm.scale[0:1], value_norm.scale[2:3], value_norm.state[3:4].float()]
         host = torch.cat(parts).cpu().numpy()
         if gae_timeouts is not None:
-            torch_functions.raise_if_timed_out(host[-1])   # GAETimeout: NaN advantages must never reach the buffer
+            torch_functions.raise_if_timed_out(host[n_head - 1])   # GAETimeout: NaN advantages must never reach the buffer
+        if value_norm is not None:
+            before = self._value_norm_host[2] if self._value_norm_host is not None else 0.0
+            self._value_norm_host = tuple(float(x) for x in host[n_head:n_head + 3])
+            if self._value_norm_host[2] > before:
+                warnings.warn("value normalisation: this iteration's value targets are not all finite -- the batch was left out of the "
+                              "running statistic", RuntimeWarning, stacklevel=2)
         if self.standardize_returns:
             head = host[:n_to_increment]
             if np.isnan(head).any():
@@ -445,6 +474,8 @@ class Learner(object):
             book["obs_running_stats"] = self.agent.obs_stats.to_json()
         if self.critic_observations and self.agent.standardize_obs and getattr(self.agent, "critic_obs_stats", None) is not None:
             book["critic_obs_running_stats"] = self.agent.critic_obs_stats.to_json()
+        if getattr(self, "normalize_value", False):   # count / mean / var (+ what makes the round trip exact to the bit)
+            book["value_norm_running_stats"] = self.ppo_learner.value_norm_state()
         if self.wandb_run is not None:
             book.update(wandb_run_id=self.wandb_run.id, wandb_project=self.wandb_run.project,
                         wandb_entity=self.wandb_run.entity, wandb_group=self.wandb_run.group,
@@ -502,6 +533,16 @@ class Learner(object):
             else:
                 warnings.warn("the checkpoint has no 'critic_obs_running_stats' (it was written without critic_observations): the critic's "
                               "observation statistics start fresh", RuntimeWarning, stacklevel=2)
+        normalize_value = getattr(self, "normalize_value", False)
+        if "value_norm_running_stats" in book:
+            if not normalize_value:
+                raise ValueError("the checkpoint was written with ppo_normalize_value=True (its critic puts out normalised values): "
+                                 "load it into a Learner with ppo_normalize_value=True")
+            self.ppo_learner.load_value_norm_state(book["value_norm_running_stats"])
+            self._value_norm_host = None
+        elif normalize_value:
+            warnings.warn("the checkpoint has no 'value_norm_running_stats' (it was written without ppo_normalize_value): the value "
+                          "statistic starts fresh, and the loaded critic's outputs are read as normalised values", RuntimeWarning, stacklevel=2)
         self.epoch = book["epoch"]
         if new_policy_lr is not None or new_critic_lr is not None:
             self.update_learning_rate(new_policy_lr, new_critic_lr)

@@ -4,5 +4,5 @@ from .diag_gaussian_policy import DiagGaussianPolicy
 from .multi_discrete_policy import MultiDiscreteFF
 from .discrete_policy import DiscreteFF
 from .value_estimator import ValueEstimator
-from .ppo_learner import ObsSizes, PPOLearner
+from .ppo_learner import ObsSizes, PPOLearner, ValueNorm
 from .experience_buffer import ExperienceBuffer

@@ -139,6 +139,7 @@ class ActGraph:
         # memory that run() writes directly through the PCIe aperture (posted writes: 1.5-2.5 us for 8-80 observations) instead of
         # reading pinned host memory itself (GPU-initiated PCIe reads: 11-20 us of the kernel).  RLPPO_ACT_PUSH=0: pinned memory.
         self.window = None
+        self._owner_pid = os.getpid()   # (__del__ frees the window in the process that made it only)
         self.obs_arg, self.q_arg = self.obs_pin.data_ptr(), self.q_pin.data_ptr()   # what _act_launch_raw hands to the kernel
         self.push = os.environ.get("RLPPO_ACT_PUSH", "1") != "0"   # (the layer chains of the other heads read the window too)
         if self.push:
@@ -226,7 +227,7 @@ class ActGraph:
 
     def __del__(self):
         win, self.window = getattr(self, "window", None), None
-        if win:
+        if win and getattr(self, "_owner_pid", None) == os.getpid():   # (a forked child holds a copy of the object, not the window)
             try:
                 torch.cuda.synchronize(self.dev)   # (its graph may still be running)
                 with torch.cuda.device(self.dev):

@@ -41,6 +41,15 @@ construction order and generator use unchanged, so a seeded policy has the weigh
 matrices, no paired launches.  Whenever the buffer holds `critic_states` the passes take that entry point (also with d_c equal to
 the policy's width); a buffer without them and a critic of another width, or the reverse mismatch, is a ValueError before the first
 pass; update precision "bf16" is refused.  Without critic states learn() makes the calls it always made.
+
+`set_value_normalization(True)` (not in the reference; off by default = the update above, launch for launch) is
+rl_games' `normalize_value`: the critic regresses standardised value targets.  `self.value_norm` (a ValueNorm) owns the running
+statistic {count, mean, M2} in device doubles and the four floats {mu, 1/sigma, sigma, 0} every pass reads
+(rlppo_ppo_minibatch_vnorm): the buffer keeps REAL-unit targets and the value loss normalises them on the fly, under the statistic as
+it stands -- learn() itself never moves it (`Learner.add_new_experience` does, once per iteration; a caller of a bare PPOLearner
+calls `value_norm.update(targets)`).  The critic then puts out normalised values: `value_norm.denormalize(v)` gives real units.
+No collective is added for data-parallel use: replicas must see the same targets or be given one state (`value_norm_state()` /
+`load_value_norm_state()`).
 """
 import ctypes
 import os
@@ -74,6 +83,57 @@ class ObsSizes(object):
         return f"ObsSizes(policy={self.policy}, critic={self.critic})"
 
 MAX_GRAD_NORM = 0.5  # ppo_learner.py:187-190
+
+
+class ValueNorm(object):
+    """The running statistic of the value targets and what the kernels read of it (include/rlppo.h, "[vnorm]").
+    state: device double[4] = {count, mean, M2, rejected batches}; scale: device float[4] = {mu, 1/sigma, sigma, 0} with
+    sigma = sqrt(M2 / count + 1e-5), {0, 1, 1, 0} while count == 0 (the first iteration runs raw)."""
+
+    def __init__(self, device):
+        self.state = torch.zeros(4, dtype=torch.float64, device=device)
+        self.scale = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float32, device=device)
+        self._ws = torch.zeros(N.VALUE_NORM_WS_BYTES, dtype=torch.uint8, device=device)   # zeroed once: every call leaves it armed
+        self.arg = N.ValueNormArg()
+        self.arg.scale = self.scale.data_ptr()
+
+    def update(self, targets):
+        """Advance the statistic with a batch of real-unit value targets (fp32 device tensor) and publish the new scale: one launch,
+        no host wait.  A batch with a non-finite entry changes nothing but state[3]."""
+        t = targets.reshape(-1)
+        assert t.dtype == torch.float32 and t.device == self.state.device
+        if t.numel() == 0:
+            return
+        t = t.contiguous()
+        N.check(N.lib().rlppo_value_norm_update(stream_ptr(), ptr(t), t.numel(), ptr(self.state), ptr(self.scale), ptr(self._ws)))
+
+    def denormalize(self, v):
+        """Real-unit values of the critic's normalised outputs (a torch op, for users; the scan does it itself)."""
+        return v * self.scale[2] + self.scale[0]
+
+    def state_dict(self):
+        """{count, mean, var (population), m2, rejected, scale}: one device-to-host read.  count / mean / var are the portable triple;
+        m2 and scale make a round trip exact to the bit."""
+        count, mean, m2, rejected = (float(x) for x in self.state.cpu().numpy())
+        return {"count": count, "mean": mean, "var": m2 / count if count > 0 else 0.0, "m2": m2, "rejected": rejected,
+                "scale": [float(x) for x in self.scale.cpu().numpy()]}
+
+    def load_state_dict(self, d):
+        count, mean = float(d["count"]), float(d["mean"])
+        if not (count >= 0 and np.isfinite(count) and np.isfinite(mean)):
+            raise ValueError(f"value normalisation state: count={count!r}, mean={mean!r}")
+        m2 = float(d["m2"]) if "m2" in d else float(d["var"]) * count
+        if not (m2 >= 0 and np.isfinite(m2)):
+            raise ValueError(f"value normalisation state: M2={m2!r}")
+        if "scale" in d:
+            scale = [float(x) for x in d["scale"]]
+        elif count > 0:   # the kernel's arithmetic: double, rounded once
+            sd = float(np.sqrt(np.float64(m2) / np.float64(count) + np.float64(1e-5)))
+            scale = [mean, 1.0 / sd, sd, 0.0]
+        else:
+            scale = [0.0, 1.0, 1.0, 0.0]
+        self.state.copy_(torch.tensor([count, mean, m2, float(d.get("rejected", 0.0))], dtype=torch.float64))
+        self.scale.copy_(torch.tensor(scale, dtype=torch.float64).to(torch.float32))
 
 
 class FusedAdam(torch.optim.Adam):
@@ -280,6 +340,24 @@ class PPOLearner(object):
         self.report_learning_rates = False   # (Learner sets it for its "linear" schedule)
         self.lr_probe = None  # callable(rates [2] device doubles {policy, critic}, KL_b [1] device double) after every gate (tests)
         self._lr_dev = self._lr_host = None
+        self.value_norm = None   # set_value_normalization(True): a ValueNorm; None = the critic regresses raw value targets
+
+    def set_value_normalization(self, on=True):
+        """Train the critic on standardised value targets from now on (module docstring), or stop doing so.  Switching it on keeps a
+        statistic that exists; a fresh one publishes {0, 1, 1, 0}: raw until its first update."""
+        if not on:
+            self.value_norm = None
+        elif self.value_norm is None:
+            self.value_norm = ValueNorm(self._dev)
+
+    def value_norm_state(self):
+        """The statistic as a dictionary (ValueNorm.state_dict), None with the option off: what a replica or a checkpoint needs."""
+        return None if self.value_norm is None else self.value_norm.state_dict()
+
+    def load_value_norm_state(self, state):
+        if self.value_norm is None:
+            raise ValueError("load_value_norm_state: value normalisation is off (set_value_normalization(True) first)")
+        self.value_norm.load_state_dict(state)
 
     # --------------------------------------------------------------------------------------------- learn
     def _minibatch_args(self, exp, rank=0, world=1):
@@ -361,7 +439,8 @@ class PPOLearner(object):
         A tanh / ELU network (LayerSizes): every head through rlppo_ppo_minibatch_ex, which carries both activations."""
         pa, va = self.policy.arena, self.value_net.arena
         crit = getattr(self, "_critic_rows", None)
-        if pa.hidden_act or va.hidden_act or crit is not None:
+        vn = self.value_norm
+        if pa.hidden_act or va.hidden_act or crit is not None or vn is not None:
             ext = N.MinibatchExt()
             ext.pol_hidden_act, ext.val_hidden_act = pa.hidden_act, va.hidden_act
             if self.policy_type == 3:
@@ -370,6 +449,9 @@ class PPOLearner(object):
                 ext.scratch, ext.scratch_bytes = self._diag_scratch.data_ptr() + args.slot * sb, sb
             elif self.policy_type == 1 and (self.policy.md_nvec is not None or args.action_mask):
                 ext.md_nvec, ext.md_heads = ctypes.cast(self.policy._nvec_c, ctypes.POINTER(ctypes.c_int32)), self.policy.n_heads
+            if vn is not None:     # value normalisation: the value loss reads the targets through the statistic's scale
+                return N.lib().rlppo_ppo_minibatch_vnorm(st, ctypes.byref(args), ctypes.byref(ext), None if crit is None else ctypes.byref(crit),
+                                                         ctypes.byref(vn.arg))
             if crit is not None:   # the buffer holds critic_states: the critic reads its own matrix
                 return N.lib().rlppo_ppo_minibatch_critic(st, ctypes.byref(args), ctypes.byref(ext), ctypes.byref(crit))
             return N.lib().rlppo_ppo_minibatch_ex(st, ctypes.byref(args), ctypes.byref(ext))

@@ -12,10 +12,12 @@ GROUPS = (
     ("Timesteps Collected",),
 )
 # keys of the options beyond the reference: printed (as one more group) only when the report has them -- PPOLearner adds them
-# when target_kl is set, and the two rates under a learning-rate schedule other than "constant"
+# when target_kl is set, and the two rates under a learning-rate schedule other than "constant"; Learner adds the value statistic's
+# mean and deviation with ppo_normalize_value ("Value Function Loss" is then in normalised units)
 OPTIONAL_GROUPS = (
     ("PPO Optimizer Steps", "KL Early Stopped"),
     ("Policy Learning Rate", "Critic Learning Rate"),
+    ("Value Norm Mean", "Value Norm Std"),
 )
 SCIENTIFIC = {"Policy Learning Rate", "Critic Learning Rate"}   # five decimals would print most learning rates as 0.00000
 

@@ -36,7 +36,7 @@ def raise_if_timed_out(timeouts):
                          f"and must not be trained on (GPU shared with a long-running kernel, or a defect)")
 
 
-def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, boot_values=None):
+def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, boot_values=None, value_scale=None):
     """gae_device without its synchronisation: returns (value_targets, advantages, returns, timeouts) where `timeouts` is a
     one-element int32 DEVICE tensor -- this call's own snapshot of the workspace header's counter, taken on the stream right
     behind the scan -- that the caller MUST hand to raise_if_timed_out() once it has the value on the host (e.g. folded into a
@@ -45,13 +45,20 @@ def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, 
 
     `boot_values` (default None: the plain scan, launch for launch): fp32 device tensor [n]; a step that is truncated and not
     done bootstraps from boot_values[t] -- V of its own next state -- instead of values[t + 1] (rlppo_gae_boot, include/rlppo.h).
-    Only those entries are used; the others may hold anything."""
+    Only those entries are used; the others may hold anything.
+
+    `value_scale` (default None: the calls above, launch for launch): fp32 device tensor of 4 floats {mu, 1/sigma, sigma, 0}
+    (ppo.ValueNorm.scale).  `values` and `boot_values` are then NORMALISED values; the scan reads each as fmaf(v, sigma, mu) and its
+    three outputs are in real units as always (rlppo_gae_norm, include/rlppo.h).  The scan reads the tensor when it runs: a captured
+    call replays with the tensor's contents of that moment."""
     n = rews.shape[0]
     dev = rews.device
     assert values.shape[0] == n + 1 and dones.shape[0] == n and truncated.shape[0] == n
     if boot_values is not None:
         assert boot_values.shape[0] == n and boot_values.dtype == torch.float32 and boot_values.device == dev
         boot_values = boot_values.contiguous()
+    if value_scale is not None:
+        assert value_scale.dtype == torch.float32 and value_scale.device == dev and value_scale.numel() == 4 and value_scale.is_contiguous()
     vt = torch.empty(n, dtype=torch.float32, device=dev)
     adv = torch.empty(n, dtype=torch.float32, device=dev)
     ret = torch.empty(n, dtype=torch.float32, device=dev)
@@ -63,7 +70,11 @@ def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, 
     hdr = ws[:16].view(torch.int32)
     if not capturing:
         hdr.zero_()  # word 1 = look-back waits that timed out (a grown / recycled workspace holds anything)
-    if boot_values is None:
+    if value_scale is not None:
+        N.check(N.lib().rlppo_gae_norm(stream_ptr(), ptr(rews), ptr(dones), ptr(truncated), ptr(values),
+                                       None if boot_values is None else ptr(boot_values), ptr(value_scale), n, float(gamma), float(lmbda),
+                                       std, ptr(vt), ptr(adv), ptr(ret), ptr(ws), ws.numel()))
+    elif boot_values is None:
         N.check(N.lib().rlppo_gae(stream_ptr(), ptr(rews), ptr(dones), ptr(truncated), ptr(values), n, float(gamma),
                                   float(lmbda), std, ptr(vt), ptr(adv), ptr(ret), ptr(ws), ws.numel()))
     else:
@@ -72,7 +83,7 @@ def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, 
     return vt, adv, ret, (None if capturing else hdr[1:2].clone())
 
 
-def gae_device(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, check=True, boot_values=None):
+def gae_device(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, check=True, boot_values=None, value_scale=None):
     """All inputs fp32 device tensors (values has N+1 entries).  Returns (value_targets, advantages, returns) as
     fp32 device tensors.  return_std=None disables reward scaling (torch_functions.py:62-65).
 
@@ -84,20 +95,24 @@ def gae_device(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_st
     caller looks at.  check=False leaves the call asynchronous (timing loops); a caller with a device-to-host read of its own
     uses gae_device_deferred and folds the counter into it (Learner.add_new_experience).
 
-    `boot_values`: see gae_device_deferred."""
-    vt, adv, ret, timeouts = gae_device_deferred(rews, dones, truncated, values, gamma, lmbda, return_std, boot_values=boot_values)
+    `boot_values`, `value_scale`: see gae_device_deferred."""
+    vt, adv, ret, timeouts = gae_device_deferred(rews, dones, truncated, values, gamma, lmbda, return_std, boot_values=boot_values,
+                                                 value_scale=value_scale)
     if check and timeouts is not None:
         raise_if_timed_out(timeouts.item())
     return vt, adv, ret
 
 
-def compute_gae(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, device=None, next_values=None):
+def compute_gae(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, device=None, next_values=None, value_scale=None):
     """Reference signature: sequences in, (value_targets fp32 tensor, advantages fp32 tensor, returns sequence) out.
     The tensors come back on the CPU like the reference's; `returns` is a float32 numpy array (the reference
     returns a list; callers slice and iterate it, learner.py:370-372).
 
     `next_values` (not in the reference; default None = the reference's behaviour): a length-n sequence; a step that is truncated
-    and not done bootstraps from next_values[t], V of its own next state, instead of values[t + 1].  Only those entries are used."""
+    and not done bootstraps from next_values[t], V of its own next state, instead of values[t + 1].  Only those entries are used.
+
+    `value_scale` (not in the reference; default None): a device tensor of 4 floats; `values` and `next_values` are normalised values
+    (gae_device_deferred)."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
 
@@ -105,7 +120,7 @@ def compute_gae(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_s
         return torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32))).to(device)
 
     boot = None if next_values is None else up(next_values)
-    vt, adv, ret = gae_device(up(rews), up(dones), up(truncated), up(values), gamma, lmbda, return_std, boot_values=boot)
+    vt, adv, ret = gae_device(up(rews), up(dones), up(truncated), up(values), gamma, lmbda, return_std, boot_values=boot, value_scale=value_scale)
     return vt.cpu(), adv.cpu(), ret.cpu().numpy()
 
 
