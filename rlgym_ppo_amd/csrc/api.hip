@@ -493,38 +493,34 @@ int64_t rlppo_act_done_words(int64_t n) { return n > 0 ? cdiv(n, 16) : 0; }
 
 size_t rlppo_gae_workspace_bytes(int64_t n) { return gae_workspace_bytes(n) + 256; }
 
+// the three forms of the scan: one check, one launch.  who: the form's name in the error text
+static int gae(const char *who, void *stream, const float *rews, const float *dones, const float *truncated, const float *values,
+               const float *boot_values, const float *value_scale, int64_t n, double gamma, double lmbda, float return_std,
+               float *value_targets, float *advantages, float *returns, void *workspace, size_t ws_bytes) {
+    if (n == 0) return 0;
+    RLPPO_CHECK_ARG(n > 0 && rews && dones && truncated && values && value_targets && advantages && returns && workspace,
+                    "%s: bad argument", who);
+    return launch_gae((hipStream_t)stream, rews, dones, truncated, values, boot_values, n, gamma, lmbda, return_std, value_targets,
+                      advantages, returns, workspace, ws_bytes, value_scale);
+}
 int rlppo_gae(void *stream, const float *rews, const float *dones, const float *truncated, const float *values, int64_t n,
               double gamma, double lmbda, float return_std, float *value_targets, float *advantages, float *returns,
               void *workspace, size_t ws_bytes) {
-    if (n == 0) return 0;
-    RLPPO_CHECK_ARG(n > 0 && rews && dones && truncated && values && value_targets && advantages && returns && workspace,
-                    "gae: bad argument");
-    return launch_gae((hipStream_t)stream, rews, dones, truncated, values, nullptr, n, gamma, lmbda, return_std, value_targets,
-                      advantages, returns, workspace, ws_bytes);
+    return gae("gae", stream, rews, dones, truncated, values, nullptr, nullptr, n, gamma, lmbda, return_std, value_targets, advantages,
+               returns, workspace, ws_bytes);
 }
-
 int rlppo_gae_boot(void *stream, const float *rews, const float *dones, const float *truncated, const float *values,
                    const float *boot_values, int64_t n, double gamma, double lmbda, float return_std, float *value_targets,
                    float *advantages, float *returns, void *workspace, size_t ws_bytes) {
-    if (n == 0) return 0;
-    RLPPO_CHECK_ARG(n > 0 && rews && dones && truncated && values && value_targets && advantages && returns && workspace,
-                    "gae_boot: bad argument");
-    return launch_gae((hipStream_t)stream, rews, dones, truncated, values, boot_values, n, gamma, lmbda, return_std, value_targets,
-                      advantages, returns, workspace, ws_bytes);
+    return gae("gae_boot", stream, rews, dones, truncated, values, boot_values, nullptr, n, gamma, lmbda, return_std, value_targets,
+               advantages, returns, workspace, ws_bytes);
 }
-
 // [vnorm] the scan on normalised values; no scale: rlppo_gae_boot (no boot values either: rlppo_gae)
 int rlppo_gae_norm(void *stream, const float *rews, const float *dones, const float *truncated, const float *values,
                    const float *boot_values, const float *value_scale, int64_t n, double gamma, double lmbda, float return_std,
                    float *value_targets, float *advantages, float *returns, void *workspace, size_t ws_bytes) {
-    if (!value_scale)
-        return rlppo_gae_boot(stream, rews, dones, truncated, values, boot_values, n, gamma, lmbda, return_std, value_targets, advantages,
-                              returns, workspace, ws_bytes);
-    if (n == 0) return 0;
-    RLPPO_CHECK_ARG(n > 0 && rews && dones && truncated && values && value_targets && advantages && returns && workspace,
-                    "gae_norm: bad argument");
-    return launch_gae((hipStream_t)stream, rews, dones, truncated, values, boot_values, n, gamma, lmbda, return_std, value_targets,
-                      advantages, returns, workspace, ws_bytes, value_scale);
+    return gae(value_scale ? "gae_norm" : "gae_boot", stream, rews, dones, truncated, values, boot_values, value_scale, n, gamma, lmbda,
+               return_std, value_targets, advantages, returns, workspace, ws_bytes);
 }
 
 int rlppo_value_norm_update(void *stream, const float *targets, int64_t n, double *state, float *scale, void *ws) {
@@ -553,9 +549,10 @@ int rlppo_clip_adam(void *stream, float *params, float *grads, float *exp_avg, f
                             (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, gnorm2);
 }
 
-// tail[k]: parameters of network k behind its layers' rlppo_flat_floats (rlppo_clip_adam_pack2_tail); 0 = the plain call
+// tail[k]: parameters of network k behind its layers' rlppo_flat_floats (rlppo_clip_adam_pack2_tail), 0 = the plain call; lr: the two
+// rates in device memory (rlppo_clip_adam_pack2_lr), null = the descriptors' own
 static int clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, const int64_t *tail,
-                           const double *const *lr = nullptr) {
+                           const double *const *lr) {
     RLPPO_CHECK_ARG(a && b, "clip_adam_pack2: null descriptor");
     RLPPO_CHECK_ARG(tail[0] >= 0 && tail[1] >= 0, "clip_adam_pack2_tail: tail_floats %ld / %ld < 0", (long)tail[0], (long)tail[1]);
     const rlppo_opt_net *d[2] = {a, b};
@@ -589,11 +586,11 @@ static int clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt
 }
 int rlppo_clip_adam_pack2(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws) {
     const int64_t tail[2] = {0, 0};
-    return clip_adam_pack2(stream, a, b, sync_ws, tail);
+    return clip_adam_pack2(stream, a, b, sync_ws, tail, nullptr);
 }
 int rlppo_clip_adam_pack2_tail(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, int64_t tail_a, int64_t tail_b) {
     const int64_t tail[2] = {tail_a, tail_b};
-    return clip_adam_pack2(stream, a, b, sync_ws, tail);
+    return clip_adam_pack2(stream, a, b, sync_ws, tail, nullptr);
 }
 
 int rlppo_clip_adam_pack2_lr(void *stream, const rlppo_opt_net *a, const rlppo_opt_net *b, void *sync_ws, int64_t tail_a, int64_t tail_b,
@@ -614,17 +611,21 @@ int rlppo_adv_stats(void *stream, const int64_t *idx, int64_t n, const float *ad
     return launch_adv_stats((hipStream_t)stream, idx, n, advantages, base, cap, out, ws);
 }
 
+// what both gates check first.  who: the entry point's name in the texts; need_stop: it writes the stop word
+static int kl_gate_check(const rlppo_kl_gate_args *a, const char *who, bool need_stop) {
+    RLPPO_CHECK_ARG(a && a->kl_slots && a->n_passes >= 0 && a->slot_stride >= 3 && a->phase >= 0 && a->phase <= 2 && (!need_stop || a->stop_word),
+                    "%s: bad argument", who);
+    RLPPO_CHECK_ARG(a->phase == 0 || a->exchange, "%s: phases 1 and 2 need the exchange words", who);
+    return 0;
+}
 int rlppo_kl_gate(void *stream, const rlppo_kl_gate_args *a) {
-    RLPPO_CHECK_ARG(a && a->kl_slots && a->n_passes >= 0 && a->slot_stride >= 3 && a->phase >= 0 && a->phase <= 2 && a->stop_word,
-                    "kl_gate: bad argument");
-    RLPPO_CHECK_ARG(a->phase == 0 || a->exchange, "kl_gate: phases 1 and 2 need the exchange words");
+    if (int rc = kl_gate_check(a, "kl_gate", true)) return rc;
     RLPPO_CHECK_ARG(a->phase == 1 || a->host_words, "kl_gate: host_words missing");
     return launch_kl_gate((hipStream_t)stream, *a);
 }
 
 int rlppo_kl_gate_lr(void *stream, const rlppo_kl_gate_args *a, const rlppo_lr_adapt_args *l) {
-    RLPPO_CHECK_ARG(a && a->kl_slots && a->n_passes >= 0 && a->slot_stride >= 3 && a->phase >= 0 && a->phase <= 2, "kl_gate_lr: bad argument");
-    RLPPO_CHECK_ARG(a->phase == 0 || a->exchange, "kl_gate_lr: phases 1 and 2 need the exchange words");
+    if (int rc = kl_gate_check(a, "kl_gate_lr", false)) return rc;
     RLPPO_CHECK_ARG(l && l->lr && ((uintptr_t)l->lr & 7) == 0 && l->n_lr >= 1 && l->n_lr <= RLPPO_LR_MAX_RATES, "kl_gate_lr: 1 to %d adjacent rates",
                     RLPPO_LR_MAX_RATES);
     RLPPO_CHECK_ARG(std::isfinite(l->desired_kl) && l->desired_kl > 0 && std::isfinite(l->factor) && l->factor > 1 && std::isfinite(l->lr_min) &&

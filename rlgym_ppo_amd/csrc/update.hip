@@ -92,7 +92,7 @@ constexpr size_t BITS_PAD_RESERVE = 2, B16_PAD_RESERVE = 4;
 // Lays out the workspace of a pass from `base` into *w and returns its size in floats: the size the host is told and the layout
 // the pass uses come from this one walk.  critic_rows: the plan of a pass with separate critic rows (rlppo_ppo_minibatch_critic) -- the
 // critic's gathered rows follow the policy's, so they start on the boundary those do and every other plan is what it was.
-static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec, void *base, WsPlan *w, bool critic_rows = false) {
+static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec, void *base, WsPlan *w, bool critic_rows) {
     const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
     const size_t rows = (size_t)mb;
     size_t off = 0, slack = 0;  // floats from the base; the unused part of the pad reserves
@@ -460,15 +460,24 @@ static int two_chain_pass(const Pass &p) {
     return 0;
 }
 
-// one pass; md_nvec (host, or null = the reference's multi-discrete head) is rlppo_ppo_minibatch_nvec's
-static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads, const DiagHead *diag,
-                         int pol_act, int val_act, const rlppo_critic_rows *critic = nullptr, const float *vnorm = nullptr) {
+// What a pass may bring beyond rlppo_minibatch_args: every optional part once, whichever exported form brought it
+struct PassOpts {
+    const int32_t *md_nvec = nullptr;  // [nvec] the multi-discrete head's md_heads bins (host); null = the reference's head, the fixed kernel
+    int32_t md_heads = 0;
+    DiagHead diag;  // [diag] the diagonal-Gaussian head's parameter, gradient and scratch, when has_diag
+    bool has_diag = false;
+    int pol_act = ACT_RELU, val_act = ACT_RELU;  // [act] the hidden activations
+    const rlppo_critic_rows *critic = nullptr;   // [critic rows] the critic's own row matrix: non-null only with critic->states set
+    const float *vnorm = nullptr;                // [vnorm] the value statistic's scale
+};
+
+static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const PassOpts &o) {
     // ---- validation: every argument error is reported here, before the first HIP call
     RLPPO_CHECK_ARG(a != nullptr, "ppo_minibatch: null args");
     Pass p;
     p.a = a;
-    p.diag = diag;
-    p.critic = critic;
+    const DiagHead *const diag = p.diag = o.has_diag ? &o.diag : nullptr;
+    const rlppo_critic_rows *const critic = p.critic = o.critic;
     int rc = make_layout(a->pol_dims, a->pol_layers, &p.pol);
     if (rc) return rc;
     rc = make_layout(a->val_dims, a->val_layers, &p.val);
@@ -480,20 +489,20 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     rc = resolve_precision(a->precision, &p.prec);
     if (rc) return rc;
     // [act] the hidden activations: tanh / ELU passes are fp32 (the bf16 and split-bf16 kernels carry the ReLU bitmask by construction)
-    RLPPO_CHECK_ARG(hidden_act_ok(pol_act) && hidden_act_ok(val_act), "ppo_minibatch: pol_hidden_act=%d val_hidden_act=%d (0 = ReLU, 1 = tanh, 2 = ELU)",
-                    pol_act, val_act);
-    p.pol_act = pol_act;
-    p.val_act = val_act;
-    const bool non_relu = pol_act != ACT_RELU || val_act != ACT_RELU;
+    RLPPO_CHECK_ARG(hidden_act_ok(o.pol_act) && hidden_act_ok(o.val_act), "ppo_minibatch: pol_hidden_act=%d val_hidden_act=%d (0 = ReLU, 1 = tanh, 2 = ELU)",
+                    o.pol_act, o.val_act);
+    p.pol_act = o.pol_act;
+    p.val_act = o.val_act;
+    const bool non_relu = o.pol_act != ACT_RELU || o.val_act != ACT_RELU;
     RLPPO_CHECK_ARG(!(non_relu && p.prec != 0), "ppo_minibatch: hidden activation %s with update precision %s: the %s kernels are ReLU only (use fp32)",
-                    hidden_act_name(pol_act != ACT_RELU ? pol_act : val_act), p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
+                    hidden_act_name(o.pol_act != ACT_RELU ? o.pol_act : o.val_act), p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
     p.plain = non_relu || (p.prec == 0 && !g_relu_bits);
     RLPPO_CHECK_ARG(mb > 0 && a->pol_packed && a->val_packed && a->pol_grad && a->val_grad && a->states && a->actions &&
                         a->old_logp && a->targets && a->advantages && a->idx && a->stats && a->workspace,
                     "ppo_minibatch: null pointer");
     RLPPO_CHECK_ARG(val.L[val.n_layers - 1].out == 1, "ppo_minibatch: critic must have one output");
     RLPPO_CHECK_ARG(a->value_clip >= 0.f && a->value_clip < INFINITY, "ppo_minibatch: value_clip=%g", (double)a->value_clip);
-    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(vnorm) & 15) == 0, "ppo_minibatch_vnorm: vnorm scale must be 16-byte aligned");
+    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(o.vnorm) & 15) == 0, "ppo_minibatch_vnorm: vnorm scale must be 16-byte aligned");
     RLPPO_CHECK_ARG(critic || pol.L[0].in == val.L[0].in, "ppo_minibatch: policy and critic observe different sizes");
     if (critic) {  // [critic rows] val_dims[0] is the width of the critic's own matrix
         RLPPO_CHECK_ARG(critic->ld_states >= val.L[0].pin && critic->ld_states % 4 == 0,
@@ -522,7 +531,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
                     a->head, RLPPO_HEAD_DIAG_GAUSSIAN);
     // [ABI 8] action masks: the discrete head, and [nvec, masked] the multi-discrete head's general kernels (md_nvec given, also for
     // the reference's bins): one bit per output, ceil(n_out / 32) words per buffer row
-    RLPPO_CHECK_ARG(!a->action_mask || a->head == RLPPO_HEAD_DISCRETE || (a->head == RLPPO_HEAD_MULTIDISCRETE && md_nvec),
+    RLPPO_CHECK_ARG(!a->action_mask || a->head == RLPPO_HEAD_DISCRETE || (a->head == RLPPO_HEAD_MULTIDISCRETE && o.md_nvec),
                     "ppo_minibatch: action_mask is an option of the discrete head, not of the %s head",
                     a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian"
                     : a->head == RLPPO_HEAD_DIAG_GAUSSIAN ? "diagonal-Gaussian"
@@ -544,10 +553,10 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
                         diag_scratch_bytes(mb, n_out));
     }
     // [nvec] md_nvec: the multi-discrete head alone; NULL = the reference's 21 outputs / 8 heads and the fixed kernel
-    RLPPO_CHECK_ARG(!md_nvec || a->head == RLPPO_HEAD_MULTIDISCRETE, "ppo_minibatch: md_nvec is an option of the multi-discrete head, not of the %s head",
+    RLPPO_CHECK_ARG(!o.md_nvec || a->head == RLPPO_HEAD_MULTIDISCRETE, "ppo_minibatch: md_nvec is an option of the multi-discrete head, not of the %s head",
                     a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : a->head == RLPPO_HEAD_DIAG_GAUSSIAN ? "diagonal-Gaussian" : "discrete");
-    if (a->head == RLPPO_HEAD_MULTIDISCRETE && md_nvec) {
-        rc = md_spec_make(md_nvec, md_heads, "multi-discrete head: md_nvec / md_heads", &p.md);
+    if (a->head == RLPPO_HEAD_MULTIDISCRETE && o.md_nvec) {
+        rc = md_spec_make(o.md_nvec, o.md_heads, "multi-discrete head: md_nvec / md_heads", &p.md);
         if (rc) return rc;
         p.md_general = true;
         RLPPO_CHECK_ARG(p.md.S == n_out, "multi-discrete head: md_nvec sums to %d, but the policy has %d outputs", p.md.S, n_out);
@@ -567,7 +576,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
     first_layer_rows(*a, critic, pol, val, p.prec, p.w, p.plain, p.rows);
     const bool twin = p.prec == 0 && !p.plain && !critic && (g_paired == 2 || (g_paired == 1 && mb >= PAIRED_MIN_ROWS)) && twin_ok(pol, val, mb);
     p.cfg = loss_cfg(*a);
-    p.cfg.vnorm = vnorm;  // [vnorm] the value loss alone reads it: same plan, same launches
+    p.cfg.vnorm = o.vnorm;  // [vnorm] the value loss alone reads it: same plan, same launches
     p.pol_w = p.prec == 1 ? a->pol_packed_r : a->pol_packed;
     p.val_w = p.prec == 1 ? a->val_packed_r : a->val_packed;
     DwList dws;
@@ -619,75 +628,70 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const int3
 static DiagHead diag_head(const float *log_std, float *log_std_grad, void *scratch, size_t scratch_bytes) {
     return DiagHead{log_std, log_std_grad, reinterpret_cast<double *>(scratch), scratch_bytes};
 }
+static bool scratch_aligned(const void *scratch) { return (reinterpret_cast<uintptr_t>(scratch) & 7) == 0; }
+// The optional parts of rlppo_ppo_minibatch_ex / _critic / _vnorm, decoded once: a NULL ext is the zeroed one, a critic struct without states
+// and a value norm without a scale are absent.  The call is named after the last part it brings, whichever of the three forms it came through.
+static int ppo_minibatch_opts(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
+                              const rlppo_value_norm *vnorm) {
+    const rlppo_minibatch_ext none = {};
+    if (!ext) ext = &none;
+    const bool has_diag = ext->log_std || ext->log_std_grad || ext->scratch || ext->scratch_bytes;
+    const PassOpts o{ext->md_nvec, ext->md_heads, diag_head(ext->log_std, ext->log_std_grad, ext->scratch, ext->scratch_bytes), has_diag,
+                     ext->pol_hidden_act, ext->val_hidden_act, critic && critic->states ? critic : nullptr, vnorm ? vnorm->scale : nullptr};
+    RLPPO_CHECK_ARG(scratch_aligned(ext->scratch), "%s: scratch must be 8-byte aligned",
+                    o.vnorm ? "ppo_minibatch_vnorm" : o.critic ? "ppo_minibatch_critic" : "ppo_minibatch_ex");
+    return ppo_minibatch(stream, a, o);
+}
+
+static size_t workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers, int64_t mb,
+                              int32_t precision, bool critic_rows) {
+    NetLayout pol, val;
+    int prec = 0;
+    if (make_layout(pol_dims, pol_layers, &pol) || make_layout(val_dims, val_layers, &val) || resolve_precision(precision, &prec)) return 0;
+    WsPlan unused;
+    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused, critic_rows) * sizeof(float) + 256;
+}
 
 extern "C" {
 
 size_t rlppo_minibatch_workspace_bytes_for(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
                                            int64_t mb, int32_t precision) {
-    NetLayout pol, val;
-    int prec = 0;
-    if (make_layout(pol_dims, pol_layers, &pol) || make_layout(val_dims, val_layers, &val) || resolve_precision(precision, &prec)) return 0;
-    WsPlan unused;
-    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused) * sizeof(float) + 256;
+    return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, false);
 }
 size_t rlppo_minibatch_workspace_bytes_critic(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
                                               int64_t mb, int32_t precision) {
-    NetLayout pol, val;
-    int prec = 0;
-    if (make_layout(pol_dims, pol_layers, &pol) || make_layout(val_dims, val_layers, &val) || resolve_precision(precision, &prec)) return 0;
-    WsPlan unused;
-    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused, true) * sizeof(float) + 256;
+    return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, true);
 }
 size_t rlppo_minibatch_workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims,
                                        int32_t val_layers, int64_t mb) {
-    return rlppo_minibatch_workspace_bytes_for(pol_dims, pol_layers, val_dims, val_layers, mb, RLPPO_PRECISION_DEFAULT);
+    return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, RLPPO_PRECISION_DEFAULT, false);
 }
 
-int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) { return ppo_minibatch(stream, a, nullptr, 0, nullptr, ACT_RELU, ACT_RELU); }
+// one call with optional parts: each form fills a PassOpts with what it brings
+int rlppo_ppo_minibatch(void *stream, const rlppo_minibatch_args *a) { return ppo_minibatch(stream, a, PassOpts{}); }
 int rlppo_ppo_minibatch_nvec(void *stream, const rlppo_minibatch_args *a, const int32_t *md_nvec, int32_t md_heads) {
-    return ppo_minibatch(stream, a, md_nvec, md_heads, nullptr, ACT_RELU, ACT_RELU);
+    return ppo_minibatch(stream, a, PassOpts{md_nvec, md_heads});
 }
-
+int rlppo_ppo_minibatch_diag(void *stream, const rlppo_minibatch_args *a, const float *log_std, float *log_std_grad, void *scratch,
+                             size_t scratch_bytes) {
+    RLPPO_CHECK_ARG(scratch_aligned(scratch), "ppo_minibatch_diag: scratch must be 8-byte aligned");
+    return ppo_minibatch(stream, a, PassOpts{nullptr, 0, diag_head(log_std, log_std_grad, scratch, scratch_bytes), true});
+}
 // [act] every head through one call: the hidden activations + what the _nvec / _diag entry points bring.  NULL / zeroed ext: rlppo_ppo_minibatch
 int rlppo_ppo_minibatch_ex(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext) {
-    if (!ext) return rlppo_ppo_minibatch(stream, a);
-    const bool diag = ext->log_std || ext->log_std_grad || ext->scratch || ext->scratch_bytes;
-    const DiagHead d = diag_head(ext->log_std, ext->log_std_grad, ext->scratch, ext->scratch_bytes);
-    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(ext->scratch) & 7) == 0, "ppo_minibatch_ex: scratch must be 8-byte aligned");
-    return ppo_minibatch(stream, a, ext->md_nvec, ext->md_heads, diag ? &d : nullptr, ext->pol_hidden_act, ext->val_hidden_act);
+    return ppo_minibatch_opts(stream, a, ext, nullptr, nullptr);
 }
-
 // [critic rows] the same call with the critic's own row matrix; no matrix: rlppo_ppo_minibatch_ex
 int rlppo_ppo_minibatch_critic(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic) {
-    if (!critic || !critic->states) return rlppo_ppo_minibatch_ex(stream, a, ext);
-    const rlppo_minibatch_ext none = {};
-    if (!ext) ext = &none;
-    const bool diag = ext->log_std || ext->log_std_grad || ext->scratch || ext->scratch_bytes;
-    const DiagHead d = diag_head(ext->log_std, ext->log_std_grad, ext->scratch, ext->scratch_bytes);
-    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(ext->scratch) & 7) == 0, "ppo_minibatch_critic: scratch must be 8-byte aligned");
-    return ppo_minibatch(stream, a, ext->md_nvec, ext->md_heads, diag ? &d : nullptr, ext->pol_hidden_act, ext->val_hidden_act, critic);
+    return ppo_minibatch_opts(stream, a, ext, critic, nullptr);
 }
-
 // [vnorm] the same call with the critic trained on normalised value targets; no scale: rlppo_ppo_minibatch_critic
 int rlppo_ppo_minibatch_vnorm(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
                               const rlppo_value_norm *vnorm) {
-    if (!vnorm || !vnorm->scale) return rlppo_ppo_minibatch_critic(stream, a, ext, critic);
-    const rlppo_minibatch_ext none = {};
-    if (!ext) ext = &none;
-    const bool diag = ext->log_std || ext->log_std_grad || ext->scratch || ext->scratch_bytes;
-    const DiagHead d = diag_head(ext->log_std, ext->log_std_grad, ext->scratch, ext->scratch_bytes);
-    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(ext->scratch) & 7) == 0, "ppo_minibatch_vnorm: scratch must be 8-byte aligned");
-    return ppo_minibatch(stream, a, ext->md_nvec, ext->md_heads, diag ? &d : nullptr, ext->pol_hidden_act, ext->val_hidden_act,
-                         critic && critic->states ? critic : nullptr, vnorm->scale);
+    return ppo_minibatch_opts(stream, a, ext, critic, vnorm);
 }
 
 size_t rlppo_diag_scratch_bytes(int64_t mb, int32_t k) { return diag_scratch_bytes(mb, k); }
-int rlppo_ppo_minibatch_diag(void *stream, const rlppo_minibatch_args *a, const float *log_std, float *log_std_grad, void *scratch,
-                             size_t scratch_bytes) {
-    const DiagHead d = diag_head(log_std, log_std_grad, scratch, scratch_bytes);
-    RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "ppo_minibatch_diag: scratch must be 8-byte aligned");
-    return ppo_minibatch(stream, a, nullptr, 0, &d, ACT_RELU, ACT_RELU);
-}
 // [diag] the diagonal-Gaussian head's loss launch and the finish of its log_std reduction on their own (tools/diag_gaussian_cost.py)
 int rlppo_dbg_diag_loss(void *stream, float *y, int64_t ld, int32_t k, const float *actions, const float *old_logp, const float *advantages,
                         int64_t mb, float clip_range, float ent_coef, float mb_ratio, const float *log_std, float *log_std_grad, void *scratch,

@@ -1,55 +1,44 @@
 """PPOLearner -- drop-in for rlgym_ppo/ppo/ppo_learner.py:10-271 with the update running in librlppo.so.
 
-Same constructor, attributes (`policy`, `value_net`, `policy_optimizer`, `value_optimizer`,
-`cumulative_model_updates`), `learn(exp) -> 8-key report`, `save_to` / `load_from` (same four .pt files with stock
-state_dict layouts).  What changed underneath:
+Same constructor, attributes (`policy`, `value_net`, `policy_optimizer`, `value_optimizer`, `cumulative_model_updates`),
+`learn(exp) -> 8-key report`, `save_to` / `load_from` (same four .pt files with stock state_dict layouts).  What changed underneath:
 
-  * one call to rlppo_ppo_minibatch per minibatch replaces ~60 eager ATen launches, 5 H2D copies and 5 .item()
-    syncs (ppo_learner.py:139-185); the report statistics accumulate in device doubles and are read back once;
-  * the epoch permutation is drawn on the host (bit-identical numpy legacy stream) while the GPU is still busy
-    with the previous epoch, and only the index vector crosses PCIe;
+  * one call to rlppo_ppo_minibatch per minibatch replaces ~60 eager ATen launches, 5 H2D copies and 5 .item() syncs
+    (ppo_learner.py:139-185); the report statistics accumulate in device doubles and are read back once;
+  * the epoch permutation is drawn on the host (bit-identical numpy legacy stream) while the GPU is still busy with the previous
+    epoch, and only the index vector crosses PCIe;
   * clip_grad_norm_ + Adam.step() are one fused pass over a flat parameter arena (rlppo_clip_adam);
   * the tail of learn() (ppo_learner.py:213-236: update magnitudes, report means) is ONE launch that writes pinned memory and
     releases a completion word (rlppo_learn_report); nothing is enqueued in front of the first pass that the pass does not need;
-  * data-parallel: the minibatch slices of a batch are dealt round-robin to the ranks of the default
-    torch.distributed group and ONE RCCL all-reduce of the flat gradient arena precedes clipping -- algebraically
-    the reference's own gradient accumulation (ppo_learner.py:134-193) with slice j living on rank j % world.
+  * data-parallel: the minibatch slices of a batch are dealt round-robin to the ranks of the default torch.distributed group and
+    ONE RCCL all-reduce of the flat gradient arena precedes clipping -- algebraically the reference's own gradient accumulation
+    (ppo_learner.py:134-193) with slice j living on rank j % world.
 
-Four opt-in options go beyond the reference (trailing keyword arguments; DESIGN.md, "Options beyond the reference"): per-batch
+Everything beyond the reference is opt-in, and with every option off learn() is the reference's update, launch for launch: it makes
+the calls it always made.  Four options are trailing keyword arguments ("Options beyond the reference"): per-batch
 advantage normalisation, Stable-Baselines3's clipped value loss, a target-KL stop of the optimiser steps and the gradient-norm
-limit.  Their defaults are the reference's update, launch for launch.  With policy_type 1, `act_space_size` may be the nvec of a
-MultiDiscrete(nvec) action space (a sequence of bin counts) instead of its length: an integer keeps the reference's eight heads
-[3, 3, 3, 3, 3, 2, 2, 2] and its kernels.  (The constructor's parameter list is the reference's plus the four options: the bins
-have no keyword of their own here, `Learner` has `multi_discrete_bins`; the learning-rate schedule below is chosen with
-`set_lr_schedule`, after construction.)
+limit.  The constructor's parameter list is pinned (the reference's plus those four), so every other choice travels in a
+reference parameter or is set after construction:
 
-policy_type 3 (not in the reference) is the diagonal-Gaussian head with a learnable log_std (ppo/diag_gaussian_policy.py):
-`act_space_size` = k action dimensions, `continuous_var_range` is ignored; log_std starts at 0 (SB3's default;
-DiagGaussianPolicy.fill_log_std sets another start, as `Learner(continuous_log_std_init=...)` does).  Its passes go through
-rlppo_ppo_minibatch_diag and its optimiser step through rlppo_clip_adam_pack2_tail (log_std is the tail of the policy's arena).
-
-`set_lr_schedule("adaptive", desired_kl=0.01, lr_bounds=(1e-5, 1e-2))` (ppo/lr_schedule.py) is rsl_rl's
-KL-adaptive learning rate, once per optimiser step: both rates are doubles in device memory, moved by the batch's gate (rlppo_kl_gate_lr) and read by its
-optimiser step (rlppo_clip_adam_pack2_lr) -- no host decision, no wait that the constant schedule does not make.  "constant"
-(default) is the update above, launch for launch; "linear" needs a horizon and is `Learner`'s.
-
-`obs_space_size=ObsSizes(d, d_c)` (not in the reference, whose critic sees what the policy sees) is the asymmetric actor-critic of
-rsl_rl / Isaac Lab ("privileged observations"); like the bins it travels in a reference parameter, because the constructor's
-parameter list is pinned.  `self.critic_obs_space_size` says what was built (None: one size).  The critic is built on d_c inputs --
-construction order and generator use unchanged, so a seeded policy has the weights it has without it -- and every pass reads the buffer's `critic_states` matrix
-(ExperienceBuffer.submit_experience(..., critic_states=...)) through rlppo_ppo_minibatch_critic -- one gather launch for both
-matrices, no paired launches.  Whenever the buffer holds `critic_states` the passes take that entry point (also with d_c equal to
-the policy's width); a buffer without them and a critic of another width, or the reverse mismatch, is a ValueError before the first
-pass; update precision "bf16" is refused.  Without critic states learn() makes the calls it always made.
-
-`set_value_normalization(True)` (not in the reference; off by default = the update above, launch for launch) is
-rl_games' `normalize_value`: the critic regresses standardised value targets.  `self.value_norm` (a ValueNorm) owns the running
-statistic {count, mean, M2} in device doubles and the four floats {mu, 1/sigma, sigma, 0} every pass reads
-(rlppo_ppo_minibatch_vnorm): the buffer keeps REAL-unit targets and the value loss normalises them on the fly, under the statistic as
-it stands -- learn() itself never moves it (`Learner.add_new_experience` does, once per iteration; a caller of a bare PPOLearner
-calls `value_norm.update(targets)`).  The critic then puts out normalised values: `value_norm.denormalize(v)` gives real units.
-No collective is added for data-parallel use: replicas must see the same targets or be given one state (`value_norm_state()` /
-`load_value_norm_state()`).
+  * policy_type 1: `act_space_size` may be the nvec of a MultiDiscrete(nvec) action space (a sequence of bin counts; `Learner` has
+    `multi_discrete_bins`) instead of its length: an integer keeps the reference's eight heads [3, 3, 3, 3, 3, 2, 2, 2] and its kernels.
+  * policy_type 3 is the diagonal-Gaussian head with a learnable log_std (ppo/diag_gaussian_policy.py): `act_space_size` = k action
+    dimensions, `continuous_var_range` is ignored, log_std starts at 0 (SB3's default).  Its passes go through
+    rlppo_ppo_minibatch_diag, its optimiser step through rlppo_clip_adam_pack2_tail (log_std is the tail of the policy's arena).
+  * `set_lr_schedule("adaptive", desired_kl=0.01, lr_bounds=(1e-5, 1e-2))` (ppo/lr_schedule.py) is rsl_rl's
+    KL-adaptive learning rate, once per optimiser step: both rates are doubles in device memory, moved by the batch's gate
+    (rlppo_kl_gate_lr) and read by its optimiser step (rlppo_clip_adam_pack2_lr) -- no host decision, no added wait.
+  * `obs_space_size=ObsSizes(d, d_c)` is the asymmetric actor-critic of rsl_rl / Isaac Lab ("privileged observations");
+    `self.critic_obs_space_size` says what was built (None: one size).  The critic is built on d_c inputs (construction order and
+    generator use unchanged: a seeded policy has the weights it has without it) and every pass reads the buffer's `critic_states`
+    matrix through rlppo_ppo_minibatch_critic: one gather launch for both matrices, no paired launches.  Whenever the buffer holds
+    `critic_states` the passes take that entry point; a buffer without them and a critic of another width, or the reverse mismatch,
+    is a ValueError before the first pass; update precision "bf16" is refused.
+  * `set_value_normalization(True)` is rl_games' `normalize_value`: the critic regresses standardised value
+    targets and puts out normalised values.  `self.value_norm` (a ValueNorm) owns the running statistic and the scale every pass
+    reads (rlppo_ppo_minibatch_vnorm); the buffer keeps REAL-unit targets.  learn() never moves the statistic (`Learner` does, once per
+    iteration; a caller of a bare PPOLearner calls `value_norm.update(targets)`) and no collective is added for data-parallel use:
+    replicas see the same targets or are given one state (`value_norm_state()` / `load_value_norm_state()`).
 """
 import ctypes
 import os
@@ -216,6 +205,19 @@ class FusedAdam(torch.optim.Adam):
             self._expose_state()
 
 
+class _LearnCall(object):
+    """What the steps of one learn() share (PPOLearner.learn_steps): the options in force, what _arm_options made of them, the counts."""
+    args = st = runs = gate = adapt = run_gate = lr_dev = None   # the passes' arguments, the stream, this rank's fused runs of a batch; the armed gate
+    stride = n_iterations = n_minibatch_iterations = n_passes = 0   # n_passes: this rank's passes (each adds one mean to every report statistic)
+    stopped_at, grads_zero = None, False   # target_kl: the batch whose KL stopped this learn() (its step and every later one not applied)
+
+    def __init__(self, learner, rank, world):
+        self.rank, self.world, self.gate_values = rank, world, {}   # gate_values: batch -> done value of its gate
+        self.stop_on = learner.target_kl is not None        # the host's decision wait and the stop word: target_kl alone
+        self.adaptive = learner.lr_schedule == "adaptive"
+        self.kl_on = self.stop_on or self.adaptive          # KL armed: the slots, the exchange tail, the gate
+
+
 class OptimizerBarrierTimeout(RuntimeError):
     """The one-launch optimiser tail's grid barrier gave up; see PPOLearner.learn (the learner has already recovered)."""
 
@@ -369,11 +371,8 @@ class PPOLearner(object):
         a.pol_dims = ctypes.cast(pa.dims_c, ctypes.POINTER(ctypes.c_int32))
         a.val_dims = ctypes.cast(va.dims_c, ctypes.POINTER(ctypes.c_int32))
         a.pol_packed, a.val_packed = pa.packed.data_ptr(), va.packed.data_ptr()
-        if self.update_precision is None:
-            prec, a.precision = int(N.lib().rlppo_get_update_precision()), N.PRECISION_DEFAULT
-        else:
-            prec = {"fp32": 0, "bf16": 1, "x3": 2}[self.update_precision]
-            a.precision = 1 + prec
+        prec = {"fp32": 0, "bf16": 1, "x3": 2}[self._precision()]
+        a.precision = N.PRECISION_DEFAULT if self.update_precision is None else 1 + prec
         self._bf16 = prec == 1  # bf16-operand forward: the rounded weight images travel too
         self._x3 = prec == 2    # [r4] fp32 update with split-bf16 hidden forward / dX products: the three-plane images travel
         if self._x3:
@@ -384,10 +383,8 @@ class PPOLearner(object):
         a.pol_grad, a.val_grad = pa.grad.data_ptr(), va.grad.data_ptr()
         st, a.ring_base, a.ring_cap = exp.ring()  # physical rows; the kernels map the permutation's logical rows onto them
         a.states, a.ld_states, a.n_rows = st["states"].data_ptr(), st["states"].shape[1], st["states"].shape[0]
-        a.actions = st["actions"].data_ptr()
-        a.old_logp = st["log_probs"].data_ptr()
-        a.targets = st["values"].data_ptr()
-        a.advantages = st["advantages"].data_ptr()
+        a.actions, a.old_logp = st["actions"].data_ptr(), st["log_probs"].data_ptr()
+        a.targets, a.advantages = st["values"].data_ptr(), st["advantages"].data_ptr()
         if "action_masks" in st:  # invalid-action masking (ExperienceBuffer.submit_experience(..., action_masks=...))
             lay = self.policy.mask_layout
             if lay is None:
@@ -398,7 +395,7 @@ class PPOLearner(object):
                                     if lay.heads is not None else f"discrete policy has {lay.width} actions"))
             a.action_mask, a.mask_words = st["action_masks"].data_ptr(), st["action_masks"].shape[1]
         # the critic's own rows (ExperienceBuffer.submit_experience(..., critic_states=...)): rlppo_ppo_minibatch_critic
-        self._critic_rows = None
+        cr = None
         d_c = getattr(exp, "critic_width", None)
         if d_c is None and va.d_in != pa.d_in:
             raise ValueError(f"the critic observes {va.d_in} features and the policy {pa.d_in} (ObsSizes), but the experience "
@@ -409,7 +406,6 @@ class PPOLearner(object):
                                  + ("" if self.critic_obs_space_size is not None else " (PPOLearner was built without ObsSizes)"))
             cr = N.CriticRows()
             cr.states, cr.ld_states = st["critic_states"].data_ptr(), st["critic_states"].shape[1]
-            self._critic_rows = cr
         a.clip_range, a.ent_coef = float(self.clip_range), float(self.ent_coef)
         a.mb_ratio = float(self.mini_batch_size / self.batch_size)
         if self.policy_type == 2:
@@ -420,7 +416,7 @@ class PPOLearner(object):
         n_slices = self.batch_size // self.mini_batch_size
         runs = fuse_runs(slices_for_rank(max(1, n_slices), rank, world), self.max_fused_minibatches)
         self._fused_rows = self.mini_batch_size * max([cnt for _, cnt in runs] or [1])
-        size_fn = N.lib().rlppo_minibatch_workspace_bytes_for if self._critic_rows is None else N.lib().rlppo_minibatch_workspace_bytes_critic
+        size_fn = N.lib().rlppo_minibatch_workspace_bytes_for if cr is None else N.lib().rlppo_minibatch_workspace_bytes_critic
         nbytes = int(size_fn(pa.dims_c, pa.n_layers, va.dims_c, va.n_layers, self._fused_rows, a.precision))
         nbytes = (nbytes + 255) // 256 * 256
         ws = self._ws.get(nbytes * self.n_slots)
@@ -431,40 +427,42 @@ class PPOLearner(object):
             if self._diag_scratch is None or self._diag_scratch.numel() < sb * self.n_slots:
                 self._diag_scratch = torch.empty(sb * self.n_slots, dtype=torch.uint8, device=self._dev)
             self._diag_scratch_bytes = sb
+        a.call = self._pass_call(a, cr)   # (a Python attribute of the ctypes struct: the choice travels with the arguments it was made for)
         return a
 
+    def _pass_call(self, args, crit=None):
+        """How a learn()'s passes are called, decided once -> (entry point, its arguments behind (stream, args), ext, scratch base, crit).
+        The entry point: value normalisation, else critic rows, else _ex for a tanh / ELU network (LayerSizes), else the head's own form (_diag;
+        _nvec for bins of its own and for every masked pass, which runs the general loss kernel also on the reference's bins; else the plain
+        one).  The head's parts are written once, into the ext every form takes them from."""
+        L, pa, va, vn = N.lib(), self.policy.arena, self.value_net.arena, self.value_norm
+        e, scratch = N.MinibatchExt(), 0
+        e.pol_hidden_act, e.val_hidden_act = pa.hidden_act, va.hidden_act
+        if self.policy_type == 3:   # log_std and its gradient: the tail of the policy's arena, behind the layers; one scratch region per slot
+            e.log_std, e.log_std_grad = pa.flat.data_ptr() + 4 * pa.n_net, pa.grad.data_ptr() + 4 * pa.n_net
+            scratch, e.scratch_bytes = self._diag_scratch.data_ptr(), self._diag_scratch_bytes
+        elif self.policy_type == 1 and (self.policy.md_nvec is not None or args.action_mask):
+            e.md_nvec, e.md_heads = ctypes.cast(self.policy._nvec_c, ctypes.POINTER(ctypes.c_int32)), self.policy.n_heads
+        if vn is not None:      # the value loss reads the targets through the statistic's scale
+            fn, tail = L.rlppo_ppo_minibatch_vnorm, (ctypes.byref(e), None if crit is None else ctypes.byref(crit), ctypes.byref(vn.arg))
+        elif crit is not None:  # the buffer holds critic_states: the critic reads its own matrix
+            fn, tail = L.rlppo_ppo_minibatch_critic, (ctypes.byref(e), ctypes.byref(crit))
+        elif pa.hidden_act or va.hidden_act:
+            fn, tail = L.rlppo_ppo_minibatch_ex, (ctypes.byref(e),)
+        elif self.policy_type == 3:
+            fn, tail = L.rlppo_ppo_minibatch_diag, None   # (the ext's four diag fields, read per pass: the scratch moves with the slot)
+        elif e.md_nvec:
+            fn, tail = L.rlppo_ppo_minibatch_nvec, (e.md_nvec, e.md_heads)
+        else:
+            fn, tail = L.rlppo_ppo_minibatch, ()
+        return fn, tail, e, scratch, crit
+
     def _pass(self, st, args):
-        """One rlppo_ppo_minibatch pass; a multi-discrete policy with bins of its own goes through rlppo_ppo_minibatch_nvec (the
-        general loss kernel), and so does every masked multi-discrete pass; every other policy through the plain entry point.
-        A tanh / ELU network (LayerSizes): every head through rlppo_ppo_minibatch_ex, which carries both activations."""
-        pa, va = self.policy.arena, self.value_net.arena
-        crit = getattr(self, "_critic_rows", None)
-        vn = self.value_norm
-        if pa.hidden_act or va.hidden_act or crit is not None or vn is not None:
-            ext = N.MinibatchExt()
-            ext.pol_hidden_act, ext.val_hidden_act = pa.hidden_act, va.hidden_act
-            if self.policy_type == 3:
-                sb = self._diag_scratch_bytes
-                ext.log_std, ext.log_std_grad = pa.flat.data_ptr() + 4 * pa.n_net, pa.grad.data_ptr() + 4 * pa.n_net
-                ext.scratch, ext.scratch_bytes = self._diag_scratch.data_ptr() + args.slot * sb, sb
-            elif self.policy_type == 1 and (self.policy.md_nvec is not None or args.action_mask):
-                ext.md_nvec, ext.md_heads = ctypes.cast(self.policy._nvec_c, ctypes.POINTER(ctypes.c_int32)), self.policy.n_heads
-            if vn is not None:     # value normalisation: the value loss reads the targets through the statistic's scale
-                return N.lib().rlppo_ppo_minibatch_vnorm(st, ctypes.byref(args), ctypes.byref(ext), None if crit is None else ctypes.byref(crit),
-                                                         ctypes.byref(vn.arg))
-            if crit is not None:   # the buffer holds critic_states: the critic reads its own matrix
-                return N.lib().rlppo_ppo_minibatch_critic(st, ctypes.byref(args), ctypes.byref(ext), ctypes.byref(crit))
-            return N.lib().rlppo_ppo_minibatch_ex(st, ctypes.byref(args), ctypes.byref(ext))
-        if self.policy_type == 3:   # log_std and its gradient: the tail of the policy's arena, behind the layers
-            pa, sb = self.policy.arena, self._diag_scratch_bytes
-            return N.lib().rlppo_ppo_minibatch_diag(st, ctypes.byref(args), pa.flat.data_ptr() + 4 * pa.n_net, pa.grad.data_ptr() + 4 * pa.n_net,
-                                                    self._diag_scratch.data_ptr() + args.slot * sb, sb)
-        nvec = self.policy.md_nvec if self.policy_type == 1 else None
-        if nvec is None and self.policy_type == 1 and args.action_mask:
-            nvec = self.policy._nvec_c  # a masked pass runs the general loss kernel, also on the reference's bins
-        if nvec is None:
-            return N.lib().rlppo_ppo_minibatch(st, ctypes.byref(args))
-        return N.lib().rlppo_ppo_minibatch_nvec(st, ctypes.byref(args), nvec, self.policy.n_heads)
+        """One pass of the update through the entry point _minibatch_args chose for these arguments."""
+        fn, tail, e, scratch, _ = getattr(args, "call", None) or self._pass_call(args)
+        if scratch:
+            e.scratch = scratch + args.slot * e.scratch_bytes
+        return fn(st, ctypes.byref(args), *((e.log_std, e.log_std_grad, e.scratch, e.scratch_bytes) if tail is None else tail))
 
     _ADAPTIVE_NEEDS_FUSED = ("lr_schedule='adaptive' needs the library's optimiser step (RLPPO_FUSED_OPT=1): the FusedAdam.step form takes "
                              "its rate from the host and cannot read one the gate wrote on the device")
@@ -473,33 +471,33 @@ class PPOLearner(object):
         """Choose the learning-rate schedule of every later learn(): "constant" (the default: the update as it was, launch for
         launch) or "adaptive" (module docstring).  Checked here, on the host alone -- a ValueError leaves the learner as it was;
         the rates "adaptive" starts from are the optimisers' current ones (param_groups[0]["lr"])."""
-        lr_schedule, desired_kl, lr_bounds = LRS.check_schedule(
-            lr_schedule, desired_kl, lr_bounds, policy_lr=self.policy_optimizer.param_groups[0]["lr"],
-            critic_lr=self.value_optimizer.param_groups[0]["lr"], allow_linear=False)
-        if lr_schedule == "adaptive" and not self.fused_optimizer_step:
+        self.lr_schedule, self.desired_kl, self.lr_bounds = self._checked_schedule(lr_schedule, desired_kl, lr_bounds)
+        self.report_learning_rates = self.lr_schedule != "constant"
+
+    def _checked_schedule(self, lr_schedule, desired_kl, lr_bounds):
+        checked = LRS.check_schedule(lr_schedule, desired_kl, lr_bounds, policy_lr=self.policy_optimizer.param_groups[0]["lr"],
+                                     critic_lr=self.value_optimizer.param_groups[0]["lr"], allow_linear=False)
+        if checked[0] == "adaptive" and not self.fused_optimizer_step:
             raise ValueError(self._ADAPTIVE_NEEDS_FUSED)
-        self.lr_schedule, self.desired_kl, self.lr_bounds = lr_schedule, desired_kl, lr_bounds
-        self.report_learning_rates = lr_schedule != "constant"
+        return checked
+
+    def _precision(self):
+        """The update precision of this learner's passes by name: its own, else the process default."""
+        return self.update_precision or ("fp32", "bf16", "x3")[int(N.lib().rlppo_get_update_precision())]
 
     def _check_options(self, exp=None):
         # separate critic rows update in fp32 or x3: the bf16 gather writes one bf16 image, of the policy's rows
-        if getattr(self, "critic_obs_space_size", None) is not None or (exp is not None and getattr(exp, "critic_width", None) is not None):
-            prec = self.update_precision or {0: "fp32", 1: "bf16", 2: "x3"}[int(N.lib().rlppo_get_update_precision())]
-            if prec == "bf16":
-                raise ValueError("update_precision='bf16' with separate critic observations (ObsSizes / critic_states): the "
-                                 "bf16 gather writes one bf16 image, of the policy's rows -- use 'fp32' or 'x3'")
+        critic_rows = getattr(self, "critic_obs_space_size", None) is not None or (exp is not None and getattr(exp, "critic_width", None) is not None)
+        if critic_rows and self._precision() == "bf16":
+            raise ValueError("update_precision='bf16' with separate critic observations (ObsSizes / critic_states): the "
+                             "bf16 gather writes one bf16 image, of the policy's rows -- use 'fp32' or 'x3'")
         # a tanh / ELU network updates in fp32: the bf16 and split-bf16 kernels carry the ReLU bitmask by construction
         acts = {m.hidden_activation for m in (self.policy, self.value_net)} - {"relu"}
-        if acts:
-            prec = self.update_precision or {0: "fp32", 1: "bf16", 2: "x3"}[int(N.lib().rlppo_get_update_precision())]
-            if prec != "fp32":
-                raise ValueError(f"hidden activation {sorted(acts)[0]!r} with update precision {prec!r}: the {prec} update kernels are ReLU "
-                                 "only -- use update_precision='fp32'")
-        self.lr_schedule, self.desired_kl, self.lr_bounds = LRS.check_schedule(
-            self.lr_schedule, self.desired_kl, self.lr_bounds, policy_lr=self.policy_optimizer.param_groups[0]["lr"],
-            critic_lr=self.value_optimizer.param_groups[0]["lr"], allow_linear=False)
-        if self.lr_schedule == "adaptive" and not self.fused_optimizer_step:
-            raise ValueError(self._ADAPTIVE_NEEDS_FUSED)
+        prec = self._precision() if acts else "fp32"
+        if prec != "fp32":
+            raise ValueError(f"hidden activation {sorted(acts)[0]!r} with update precision {prec!r}: the {prec} update kernels are ReLU "
+                             "only -- use update_precision='fp32'")
+        self.lr_schedule, self.desired_kl, self.lr_bounds = self._checked_schedule(self.lr_schedule, self.desired_kl, self.lr_bounds)
         if self.value_clip_range is not None and not float(self.value_clip_range) > 0:
             raise ValueError(f"value_clip_range must be > 0 or None, got {self.value_clip_range!r}")
         if self.target_kl is not None and not float(self.target_kl) > 0:
@@ -536,14 +534,21 @@ class PPOLearner(object):
             opt.lr_word.fill_(float(opt.param_groups[0]["lr"]))
         return self._lr_dev
 
-    def _kl_decision(self, g, done_value):
-        """The stop word after batch g's gate (0 = running, else trigger + 1): waits for the gate's pinned words."""
-        L, words = N.lib(), self._opt["host"].data_ptr() + 8 * (g % 4)
-        if L.rlppo_host_wait_words(words + 4, 1, done_value, 5000) != 0:
+    def _wait_word(self, address, value, what):
+        """Wait for `value` in the pinned word at `address`: a short spin, then once more behind the stream (a long learn(): sleep
+        instead of spinning); RuntimeError(what) if it still has not arrived."""
+        L = N.lib()
+        if L.rlppo_host_wait_words(address, 1, value, 5000) != 0:
             torch.cuda.current_stream(self._dev).synchronize()
-            if L.rlppo_host_wait_words(words + 4, 1, done_value, 1000000) != 0:
-                raise RuntimeError("rlppo_kl_gate: the decision word did not arrive")
-        return int(self._opt["host_np"][2 * (g % 4)])
+            if L.rlppo_host_wait_words(address, 1, value, 1000000) != 0:
+                raise RuntimeError(what)
+
+    def _kl_decision(self, c, g):
+        """Waits for the pinned words of batch g's gate; a stop word (0 = running, else trigger + 1) sets c.stopped_at.  -> stopped"""
+        self._wait_word(self._opt["host"].data_ptr() + 8 * (g % 4) + 4, c.gate_values[g], "rlppo_kl_gate: the decision word did not arrive")
+        v = int(self._opt["host_np"][2 * (g % 4)])
+        c.stopped_at = v - 1 if v else None
+        return v != 0
 
     def learn(self, exp):
         """Compute PPO updates with an experience buffer; returns the reference's report dictionary
@@ -563,86 +568,46 @@ class PPOLearner(object):
         ranks it needs (the [grad_policy | grad_value] arena after a batch's last backward pass, the report statistics at the end)
         and continues once the caller has put that sum into it; the report dictionary is the generator's return value.  learn()
         drives it with torch.distributed's all-reduce; dp.run_virtual_ranks drives the generators of N replicas in ONE process
-        (the 8-way partition of BASELINE configs[3] on a one-GPU box).  With world == 1 it never yields."""
+        (the 8-way partition of BASELINE configs[3] on a one-GPU box).  With world == 1 it never yields.  What its steps share is `c`."""
         L = N.lib()
         self._check_options(exp)
         pa, va = self.policy.arena, self.value_net.arena
         B, MB = self.batch_size, self.mini_batch_size
         n_slices = B // MB
-        max_norm = float(self.max_grad_norm)
-        stop_on = self.target_kl is not None        # the host's decision wait and the stop word: target_kl alone
-        adaptive = self.lr_schedule == "adaptive"
-        kl_on = stop_on or adaptive                 # KL armed: the slots, the exchange tail, the gate
-        stopped_at = None   # target_kl: the batch whose KL stopped this learn() (its step and every later one not applied)
-        gate_values = {}    # batch -> done value of its gate
-
-        # [r6] nothing is enqueued before the first pass that the pass does not need: the report sums were zeroed by the previous
-        # learn()'s report kernel, and the "before" copies of the parameters (ppo_learner.py:111-116) follow the first pass's launches
-        # in stream order -- the first optimiser step is still behind them
+        c = _LearnCall(self, rank, world)
+        # [r6] nothing is enqueued before the first pass that the pass does not need: the previous learn()'s report kernel zeroed the report
+        # sums, and the "before" copies of the parameters (ppo_learner.py:111-116) follow the first pass's launches (the first step is behind them)
         if not self._stats_clean:
             self._stats.zero_()
         self._stats_clean = False
         have_before = False
-        n_iterations = 0
-        n_minibatch_iterations = 0
-        n_passes = 0  # launches of rlppo_ppo_minibatch on this rank (each adds one mean to every report statistic)
         total = len(exp)
         n_batches = total // B if B > 0 else 0
-
         t1 = time.time()
-        grads_zero = False
         if n_batches > 0 and total > 0:
             if exp.ring()[0]["actions"][:1].reshape(1, -1).shape[1] != self._act_dim:
                 raise ValueError("experience buffer action width does not match the policy head")
-            args = self._minibatch_args(exp, rank, world)
-            st = stream_ptr()
-            runs = fuse_runs(slices_for_rank(n_slices, rank, world), self.max_fused_minibatches)
-            if self.value_clip_range is not None:
-                args.value_clip = float(self.value_clip_range)
-            if self.normalize_advantages or kl_on:
-                stride = int(L.rlppo_kl_slots_doubles(self._fused_rows))
-                o = self._option_state(stride * max(len(runs), 1) if kl_on else 0)
-                if self.normalize_advantages:
-                    args.adv_norm = o["adv"].data_ptr()
-                if kl_on:
-                    gate = N.KlGateArgs()
-                    gate.kl_slots, gate.slot_stride, gate.n_passes = o["kl"].data_ptr(), stride, len(runs)
-                    gate.exchange = self._grad_ex.data_ptr() + 4 * self._grad_all.numel()
-                if stop_on:
-                    o["stop"].zero_()
-                    args.stop_word = o["stop"].data_ptr()
-                    gate.threshold = 1.5 * float(self.target_kl)
-                    gate.stop_word = o["stop"].data_ptr()
-                if adaptive:   # the gate moves the two rates, the optimiser step reads them: the host takes no part until the report
-                    lr_dev = self._lr_state()
-                    adapt = N.LrAdaptArgs()
-                    adapt.lr, adapt.n_lr, adapt.desired_kl, adapt.factor = lr_dev.data_ptr(), 2, self.desired_kl, LRS.ADAPT_FACTOR
-                    adapt.lr_min, adapt.lr_max = self.lr_bounds
-                    run_gate = lambda: L.rlppo_kl_gate_lr(st, ctypes.byref(gate), ctypes.byref(adapt))
-                elif kl_on:
-                    run_gate = lambda: L.rlppo_kl_gate(st, ctypes.byref(gate))
-            # The legacy-MT19937 permutation is inherently serial host work.  The buffer's shuffle pipeline draws it on
-            # helper threads several epochs ahead (also across learn() calls) and uploads every index vector on its own
-            # stream (engine.LegacyPermutation / DeviceIndexRing): here an epoch only orders the stream after that copy.
-            # With 8 ranks the GPU share of an epoch is ~1.1 ms; the serial stream phase (~0.8 ms per 512k indices) is
-            # the only part of the shuffle that cannot be spread over threads.
+            args = c.args = self._minibatch_args(exp, rank, world)
+            st = c.st = stream_ptr()
+            runs = c.runs = fuse_runs(slices_for_rank(n_slices, rank, world), self.max_fused_minibatches)
+            self._arm_options(c)
+            # The legacy-MT19937 permutation is serial host work: the buffer's shuffle pipeline draws it on helper threads several
+            # epochs ahead (also across learn() calls) and uploads every index vector on its own stream (engine.LegacyPermutation /
+            # DeviceIndexRing), so here an epoch only orders the stream after that copy.
             for epoch in range(self.n_epochs):
-                if stopped_at is not None:   # a stopped learn() still consumes every epoch's permutation
+                if c.stopped_at is not None:   # a stopped learn() still consumes every epoch's permutation
                     exp.epoch_indices()
                     continue
                 idx_dev = exp.epoch_indices_device(refill=False)   # (the look-ahead is topped up behind the epoch's first launches)
                 refilled = False
                 for b in range(n_batches):
                     g = epoch * n_batches + b
-                    if stop_on and g >= 2:
-                        # at most one undecided batch beyond the executing one: batch g waits for the decision of batch g - 2
-                        v = self._kl_decision(g - 2, gate_values[g - 2])
-                        if v:
-                            stopped_at = v - 1
-                            break
-                    if not grads_zero:
+                    # at most one undecided batch beyond the executing one: batch g waits for the decision of batch g - 2
+                    if c.stop_on and g >= 2 and self._kl_decision(c, g - 2):
+                        break
+                    if not c.grads_zero:
                         self._grad_all.zero_()
-                    grads_zero = False
+                    c.grads_zero = False
                     pa.ensure_packed()
                     va.ensure_packed()
                     if self._bf16:  # re-round the master weights the optimiser step just moved (one small launch per net)
@@ -655,16 +620,15 @@ class PPOLearner(object):
                         N.check(L.rlppo_adv_stats(st, idx_dev.data_ptr() + 8 * b * B, B, args.advantages, args.ring_base, args.ring_cap,
                                                   args.adv_norm, self._opt["adv_ws"].data_ptr()))
                     for k, (j, cnt) in enumerate(runs):
-                        if kl_on:
-                            args.kl_slots = gate.kl_slots + 8 * k * stride
+                        if c.kl_on:
+                            args.kl_slots = c.gate.kl_slots + 8 * k * c.stride
                         args.slot = k % self.n_slots
                         args.workspace = self._slot_ws[args.slot]
-                        off = b * B + j * MB
-                        args.idx = idx_dev.data_ptr() + 8 * off
+                        args.idx = idx_dev.data_ptr() + 8 * (b * B + j * MB)
                         args.mb = cnt * MB                      # cnt consecutive minibatches in one pass
                         args.mb_ratio = float(cnt * MB / B)
                         N.check(self._pass(st, args))
-                        n_passes += 1
+                        c.n_passes += 1
                     N.check(L.rlppo_ppo_join(st))
                     if not refilled:
                         exp.refill_shuffle()
@@ -673,176 +637,207 @@ class PPOLearner(object):
                         self._before[0].copy_(pa.flat)
                         self._before[1].copy_(va.flat)
                         have_before = True
-                    n_minibatch_iterations += n_slices
-                    if stop_on:
+                    c.n_minibatch_iterations += n_slices
+                    if c.stop_on:
                         self._kl_seq = self._kl_seq % 0x7FFFFFFF + 1
-                        gate_values[g] = self._kl_seq
-                        gate.batch, gate.done_value = g, self._kl_seq
-                        gate.host_words = self._opt["host"].data_ptr() + 8 * (g % 4)
-                    if kl_on and world > 1:  # this rank's KL share rides in the tail of the ONE exchange of the step
-                        gate.phase = 1
-                        N.check(run_gate())
+                        c.gate_values[g] = self._kl_seq
+                        c.gate.batch, c.gate.done_value = g, self._kl_seq
+                        c.gate.host_words = self._opt["host"].data_ptr() + 8 * (g % 4)
+                    if c.kl_on and world > 1:  # this rank's KL share rides in the tail of the ONE exchange of the step
+                        c.gate.phase = 1
+                        N.check(c.run_gate())
                     if world > 1:
-                        yield self._grad_ex if kl_on else self._grad_all  # summed over the ranks (RCCL over xGMI) before clipping
-                    if kl_on:
-                        gate.phase = 2 if world > 1 else 0
-                        if adaptive:
-                            adapt.kl_out = lr_dev.data_ptr() + 16 if self.lr_probe is not None else None
-                        N.check(run_gate())
-                        if adaptive and self.lr_probe is not None:  # test hook: the rates this batch's step will use, the KL that set them
-                            self.lr_probe(lr_dev[:2], lr_dev[2:3])
+                        yield self._grad_ex if c.kl_on else self._grad_all  # summed over the ranks (RCCL over xGMI) before clipping
+                    if c.kl_on:
+                        c.gate.phase = 2 if world > 1 else 0
+                        if c.adaptive:
+                            c.adapt.kl_out = c.lr_dev.data_ptr() + 16 if self.lr_probe is not None else None
+                        N.check(c.run_gate())
+                        if c.adaptive and self.lr_probe is not None:  # test hook: the rates this batch's step will use, the KL that set them
+                            self.lr_probe(c.lr_dev[:2], c.lr_dev[2:3])
                     if self.grad_probe is not None:  # test hook: the batch gradient clip_grad_norm_ / Adam are about to see
                         self.grad_probe(self._grad_all)
-                    if self.fused_optimizer_step:
-                        # both clip + Adam steps, the re-pack of both weight copies and the next batch's zero_grad: 3 stream
-                        # operations instead of 9 (csrc/optim.hip)
-                        dv = self.value_optimizer.fused_descriptor(max_norm)
-                        dp_ = self.policy_optimizer.fused_descriptor(max_norm)
-                        if stop_on:   # (a step after the stop touches nothing: the gate's stop word)
-                            dv.skip_word = dp_.skip_word = gate.stop_word
-                        sync = ptr(self._opt_sync) if self.one_launch_optimizer else None
-                        if adaptive:   # both rates from the device doubles the gate has just left (descriptor order: critic, policy)
-                            N.check(L.rlppo_clip_adam_pack2_lr(st, ctypes.byref(dv), ctypes.byref(dp_), sync, va.n_tail, pa.n_tail,
-                                                               self.value_optimizer.lr_word.data_ptr(), self.policy_optimizer.lr_word.data_ptr()))
-                        elif va.n_tail or pa.n_tail:   # parameters behind a network's layers (log_std): same norm, same step, never packed
-                            N.check(L.rlppo_clip_adam_pack2_tail(st, ctypes.byref(dv), ctypes.byref(dp_), sync, va.n_tail, pa.n_tail))
-                        else:
-                            N.check(L.rlppo_clip_adam_pack2(st, ctypes.byref(dv), ctypes.byref(dp_), sync))
-                        va.mark_repacked()
-                        pa.mark_repacked()
-                        grads_zero = True
-                    else:
-                        self.value_optimizer.step(max_norm=max_norm)
-                        self.policy_optimizer.step(max_norm=max_norm)
-                    n_iterations += 1
+                    self._optimizer_step(c)
+                    c.n_iterations += 1
                 if not refilled:
                     exp.refill_shuffle()
-            if stop_on:
-                if stopped_at is None and n_iterations > 0:   # a trigger among the last two batches
-                    v = self._kl_decision(n_iterations - 1, gate_values[n_iterations - 1])
-                    stopped_at = v - 1 if v else None
-                if stopped_at is not None:
-                    # launches from the trigger on were skipped on the device: Adam's step counts rewind by them (as after a give-up),
-                    # the gradient arena holds the unapplied batches' sums, and only the evaluated batches' passes are in the report
-                    for opt in (self.policy_optimizer, self.value_optimizer):
-                        opt.step_count -= n_iterations - stopped_at
-                    n_iterations = stopped_at
-                    n_passes = len(runs) * (stopped_at + 1)
-                    n_minibatch_iterations = n_slices * (stopped_at + 1)
-                    self._grad_all.zero_()
-                    grads_zero = True
+            if c.stop_on:
+                self._settle_stop(c, n_slices)
         else:
             for _ in range(self.n_epochs):
                 exp.epoch_indices()  # the reference consumes one permutation per epoch even if no batch fits
-
-        # every pass added one mean to each report statistic; the number of passes travels with the sums, so the report is the
-        # mean over the passes of ALL ranks even when the slices do not divide evenly over them (3 slices on 2 ranks)
         if not have_before:   # (no batch fitted: nothing moved)
             self._before[0].copy_(pa.flat)
             self._before[1].copy_(va.flat)
+        return (yield from self._report(c, t1, lr_back=c.adaptive and self._lr_dev is not None and n_batches > 0 and total > 0))
+
+    def _arm_options(self, c):
+        """The options into c.args, their device state, and with KL armed the gate (+ adapt) struct and c.run_gate."""
+        L, args, st = N.lib(), c.args, c.st
+        if self.value_clip_range is not None:
+            args.value_clip = float(self.value_clip_range)
+        if not (self.normalize_advantages or c.kl_on):
+            return
+        c.stride = int(L.rlppo_kl_slots_doubles(self._fused_rows))
+        o = self._option_state(c.stride * max(len(c.runs), 1) if c.kl_on else 0)
+        if self.normalize_advantages:
+            args.adv_norm = o["adv"].data_ptr()
+        if c.kl_on:
+            gate = c.gate = N.KlGateArgs()
+            gate.kl_slots, gate.slot_stride, gate.n_passes = o["kl"].data_ptr(), c.stride, len(c.runs)
+            gate.exchange = self._grad_ex.data_ptr() + 4 * self._grad_all.numel()
+            c.run_gate = lambda: L.rlppo_kl_gate(st, ctypes.byref(gate))
+        if c.stop_on:
+            o["stop"].zero_()
+            args.stop_word = gate.stop_word = o["stop"].data_ptr()
+            gate.threshold = 1.5 * float(self.target_kl)
+        if c.adaptive:   # the gate moves the two rates, the optimiser step reads them: the host takes no part until the report
+            c.lr_dev = self._lr_state()
+            adapt = c.adapt = N.LrAdaptArgs()
+            adapt.lr, adapt.n_lr, adapt.desired_kl, adapt.factor = c.lr_dev.data_ptr(), 2, self.desired_kl, LRS.ADAPT_FACTOR
+            adapt.lr_min, adapt.lr_max = self.lr_bounds
+            c.run_gate = lambda: L.rlppo_kl_gate_lr(st, ctypes.byref(gate), ctypes.byref(adapt))
+
+    def _optimizer_step(self, c):
+        """clip + Adam of both networks: FusedAdam.step twice (RLPPO_FUSED_OPT=0), or the library's form -- both steps, the re-pack of
+        both weight copies and the next batch's zero_grad in 3 stream operations instead of 9 (csrc/optim.hip)."""
+        L, pa, va, max_norm = N.lib(), self.policy.arena, self.value_net.arena, float(self.max_grad_norm)
+        if not self.fused_optimizer_step:
+            self.value_optimizer.step(max_norm=max_norm)
+            self.policy_optimizer.step(max_norm=max_norm)
+            return
+        dv, dp_ = self.value_optimizer.fused_descriptor(max_norm), self.policy_optimizer.fused_descriptor(max_norm)
+        if c.stop_on:   # (a step after the stop touches nothing: the gate's stop word)
+            dv.skip_word = dp_.skip_word = c.gate.stop_word
+        call = (c.st, ctypes.byref(dv), ctypes.byref(dp_), ptr(self._opt_sync) if self.one_launch_optimizer else None)
+        if c.adaptive:   # both rates from the device doubles the gate has just left (descriptor order: critic, policy)
+            rc = L.rlppo_clip_adam_pack2_lr(*call, va.n_tail, pa.n_tail, self.value_optimizer.lr_word.data_ptr(),
+                                            self.policy_optimizer.lr_word.data_ptr())
+        elif va.n_tail or pa.n_tail:   # parameters behind a network's layers (log_std): same norm, same step, never packed
+            rc = L.rlppo_clip_adam_pack2_tail(*call, va.n_tail, pa.n_tail)
+        else:
+            rc = L.rlppo_clip_adam_pack2(*call)
+        N.check(rc)
+        va.mark_repacked()
+        pa.mark_repacked()
+        c.grads_zero = True
+
+    def _settle_stop(self, c, n_slices):
+        """target_kl, behind the last batch: the outstanding decision, and after a stop the counts of what was applied."""
+        if c.stopped_at is None and c.n_iterations > 0:   # a trigger among the last two batches
+            self._kl_decision(c, c.n_iterations - 1)
+        if c.stopped_at is None:
+            return
+        # launches from the trigger on were skipped on the device: Adam's step counts rewind by them (as after a give-up),
+        # the gradient arena holds the unapplied batches' sums, and only the evaluated batches' passes are in the report
+        for opt in (self.policy_optimizer, self.value_optimizer):
+            opt.step_count -= c.n_iterations - c.stopped_at
+        c.n_iterations = c.stopped_at
+        c.n_passes = len(c.runs) * (c.stopped_at + 1)
+        c.n_minibatch_iterations = n_slices * (c.stopped_at + 1)
+        self._grad_all.zero_()
+        c.grads_zero = True
+
+    def _report(self, c, t1, lr_back):
+        """[r6] update magnitudes (ppo_learner.py:214-222), the statistics and the give-up words in ONE launch that writes pinned
+        memory and releases a completion word (rlppo_learn_report): one device->host hand-over per learn(), no eager tail.
+        A sub-generator (the statistics' exchange, the recovery's) -> the report dictionary."""
+        pa, va = self.policy.arena, self.value_net.arena
         rep = N.ReportArgs()
         rep.pol_before, rep.pol_now, rep.n_pol = self._before[0].data_ptr(), pa.flat.data_ptr(), pa.n_flat
         rep.val_before, rep.val_now, rep.n_val = self._before[1].data_ptr(), va.flat.data_ptr(), va.n_flat
-        rep.stats, rep.add_passes = self._stats.data_ptr(), float(n_passes)
+        # every pass added one mean to each report statistic; the number of passes travels with the sums, so the report is the
+        # mean over the passes of ALL ranks even when the slices do not divide evenly over them (3 slices on 2 ranks)
+        rep.stats, rep.add_passes = self._stats.data_ptr(), float(c.n_passes)
         rep.timeout_word = self._opt_sync.data_ptr() + 4 * N.OPT_SYNC_TIMEOUT_WORD   # optimiser steps THIS rank's barrier skipped
-        to_all = None
-        if world > 1:
+        if c.world > 1:
             # the give-up count travels with the statistics: a give-up on ANY rank is known to EVERY rank after this exchange
-            self._stats[N.STAT_PASSES] += float(n_passes)
+            self._stats[N.STAT_PASSES] += float(c.n_passes)
             rep.add_passes = 0.0
             ex = torch.cat((self._stats, self._opt_sync[N.OPT_SYNC_TIMEOUT_WORD:N.OPT_SYNC_TIMEOUT_WORD + 1].double()))
             yield ex
             self._stats.copy_(ex[:N.N_STATS])
             to_all = ex[N.N_STATS:].contiguous()
             rep.extra = to_all.data_ptr()
-        # [r6] update magnitudes (ppo_learner.py:214-222), the statistics and the give-up words in ONE launch that writes pinned memory
-        # and releases a completion word (rlppo_learn_report): one device->host hand-over per learn(), no eager tail
-        lr_back = adaptive and self._lr_dev is not None and n_batches > 0 and total > 0
         if lr_back:   # the two rates ride to pinned memory in front of the report launch: its completion word covers them too
             self._lr_host.copy_(self._lr_dev[:2], non_blocking=True)
         self._report_seq = self._report_seq % 0x7FFFFFFF + 1
-        rep.out, rep.done_word, rep.done_value, rep.ws = (self._report_out.data_ptr(), self._report_done.data_ptr(), self._report_seq,
-                                                          self._report_ws.data_ptr())
-        N.check(L.rlppo_learn_report(stream_ptr(), ctypes.byref(rep)))
-        if L.rlppo_host_wait_words(self._report_done.data_ptr(), 1, self._report_seq, 5000) != 0:
-            torch.cuda.current_stream(self._dev).synchronize()   # (a long learn(): sleep instead of spinning)
-            if L.rlppo_host_wait_words(self._report_done.data_ptr(), 1, self._report_seq, 1000000) != 0:
-                raise RuntimeError("rlppo_learn_report: the completion word did not arrive")
+        rep.out, rep.done_word, rep.ws, rep.done_value = self._report_out.data_ptr(), self._report_done.data_ptr(), self._report_ws.data_ptr(), self._report_seq
+        N.check(N.lib().rlppo_learn_report(stream_ptr(), ctypes.byref(rep)))
+        self._wait_word(self._report_done.data_ptr(), self._report_seq, "rlppo_learn_report: the completion word did not arrive")
         self._stats_clean = True
         stats = self._report_out_np.copy()
         if lr_back:   # gate state, not step state: they stand whatever became of the steps (stopped, skipped, given up)
             self.policy_optimizer.param_groups[0]["lr"], self.value_optimizer.param_groups[0]["lr"] = (float(x) for x in self._lr_host.numpy())
         if stats[N.N_STATS + 3] != 0:
-            # A grid-barrier wait of the one-launch optimiser step gave up on some rank (GPU shared with a kernel that never yields,
-            # a partitioned device, or a defect).  Giving up is all or nothing (include/rlppo.h): on the rank it happened, that step
-            # and every later one of this call were SKIPPED -- its parameters and Adam moments are those of its last completed step,
-            # finite -- and its gradient arena still holds the skipped batches' sums.  Recover the state a caller can continue from
-            # (zero gradients, a re-armed block, the three-operation form from now on) and report loudly.
-            n_to = int(stats[N.N_STATS + 2])   # skipped optimiser steps of THIS rank (a launch counts itself once: csrc/optim.hip)
-            for opt in (self.policy_optimizer, self.value_optimizer):
-                opt.step_count = max(0, opt.step_count - n_to)   # Adam's bias corrections must not count steps that never happened
-            self.cumulative_model_updates += max(0, n_iterations - n_to)
-            self._grad_all.zero_()
-            self._opt_sync.zero_()
-            self.one_launch_optimizer = False
-            where = "the affected optimiser steps of this learn() were skipped -- parameters and Adam state are those of the last completed step, no NaN was written"
-            if world > 1:
-                # [r5, advisor] Data-parallel: the rank that gave up skipped steps the others applied, so the replicas have DIVERGED
-                # (parameters, moments, step counts).  The outcome is made collective: every rank takes this branch (the count was
-                # summed over the ranks above) and adopts rank 0's state -- one more exchange in which only rank 0 contributes, so
-                # the sum IS its state, bit for bit -- before raising on every rank.
-                opts = (self.policy_optimizer, self.value_optimizer)
-                pieces = [pa.flat, va.flat] + [t for o in opts for t in (o.exp_avg, o.exp_avg_sq)]
-                sync = torch.cat([t.reshape(-1) for t in pieces])
-                counts = torch.tensor([float(o.step_count) for o in opts] + [float(self.cumulative_model_updates)], dtype=torch.float64,
-                                      device=self._dev)
-                if rank != 0:
-                    sync.zero_()
-                    counts.zero_()
-                yield sync
-                yield counts
-                off = 0
-                for t in pieces:
-                    t.copy_(sync[off:off + t.numel()].view_as(t))
-                    off += t.numel()
-                c = counts.cpu().numpy()
-                self.policy_optimizer.step_count, self.value_optimizer.step_count = int(c[0]), int(c[1])
-                self.cumulative_model_updates = int(c[2])
-                pa.native_epoch += 1  # `flat` was rewritten behind torch's back: re-pack before the next kernel reads the weights
-                va.native_epoch += 1
-                pa.invalidate()
-                va.invalidate()
-                where = ("the rank(s) it happened on skipped optimiser steps the others applied; every rank has now adopted rank 0's "
-                         "parameters, Adam moments and step counts (bit-identical replicas again), no NaN was written")
-            raise OptimizerBarrierTimeout(
-                "rlppo_clip_adam_pack2: the optimiser's grid barrier gave up (%d skipped step(s) over all ranks); %s -- gradients are "
-                "zeroed and this learner now uses the three-operation optimiser tail: calling learn() again is safe"
-                % (int(stats[N.N_STATS + 3]), where))
-        elapsed = time.time() - t1
-        n_iter_r = max(n_iterations, 1)
-        n_mb_r = max(float(stats[N.STAT_PASSES]), 1.0)
-        policy_update_magnitude, critic_update_magnitude = float(stats[N.N_STATS]), float(stats[N.N_STATS + 1])
-        self.cumulative_model_updates += n_iterations if stop_on else n_iter_r   # (with target_kl: applied steps only)
-
+            yield from self._recover_barrier_timeout(c, stats)
+        elapsed, n_iter_r, n_mb_r = time.time() - t1, max(c.n_iterations, 1), max(float(stats[N.STAT_PASSES]), 1.0)
+        self.cumulative_model_updates += c.n_iterations if c.stop_on else n_iter_r   # (with target_kl: applied steps only)
         report = {
             "PPO Batch Consumption Time": elapsed / n_iter_r,
             "Cumulative Model Updates": self.cumulative_model_updates,
             "Policy Entropy": float(stats[N.STAT_ENTROPY]) / n_mb_r,
             "Mean KL Divergence": float(stats[N.STAT_KL]) / n_mb_r,
             "Value Function Loss": float(stats[N.STAT_VLOSS]) / n_mb_r,
-            "SB3 Clip Fraction": float(stats[N.STAT_CLIPFRAC]) / n_mb_r if n_minibatch_iterations else 0,
-            "Policy Update Magnitude": policy_update_magnitude,
-            "Value Function Update Magnitude": critic_update_magnitude,
+            "SB3 Clip Fraction": float(stats[N.STAT_CLIPFRAC]) / n_mb_r if c.n_minibatch_iterations else 0,
+            "Policy Update Magnitude": float(stats[N.N_STATS]),
+            "Value Function Update Magnitude": float(stats[N.N_STATS + 1]),
         }
-        if stop_on:
-            report["PPO Optimizer Steps"] = n_iterations
-            report["KL Early Stopped"] = 1.0 if stopped_at is not None else 0.0
+        if c.stop_on:
+            report["PPO Optimizer Steps"] = c.n_iterations
+            report["KL Early Stopped"] = 1.0 if c.stopped_at is not None else 0.0
         if self.report_learning_rates:   # the optimisers' rates after this learn() ("adaptive": as its last gate left them; "linear": this iteration's)
             report["Policy Learning Rate"] = float(self.policy_optimizer.param_groups[0]["lr"])
             report["Critic Learning Rate"] = float(self.value_optimizer.param_groups[0]["lr"])
-        if not grads_zero:  # the fused optimiser step leaves the arena zeroed
+        if not c.grads_zero:  # the fused optimiser step leaves the arena zeroed
             self._grad_all.zero_()
         return report
+
+    def _recover_barrier_timeout(self, c, stats):
+        """A grid-barrier wait of the one-launch optimiser step gave up on some rank (GPU shared with a kernel that never yields, a partitioned
+        device, or a defect).  Giving up is all or nothing (include/rlppo.h): on the rank it happened, that step and every later one of this
+        call were SKIPPED -- parameters and Adam moments are those of its last completed step, finite -- and its gradient arena holds the
+        skipped batches' sums.  Recovers a state to continue from (zero gradients, a re-armed block, the three-operation form) and raises."""
+        pa, va = self.policy.arena, self.value_net.arena
+        opts = (self.policy_optimizer, self.value_optimizer)
+        n_to = int(stats[N.N_STATS + 2])   # skipped optimiser steps of THIS rank (a launch counts itself once: csrc/optim.hip)
+        for opt in opts:
+            opt.step_count = max(0, opt.step_count - n_to)   # Adam's bias corrections must not count steps that never happened
+        self.cumulative_model_updates += max(0, c.n_iterations - n_to)
+        self._grad_all.zero_()
+        self._opt_sync.zero_()
+        self.one_launch_optimizer = False
+        where = "the affected optimiser steps of this learn() were skipped -- parameters and Adam state are those of the last completed step, no NaN was written"
+        if c.world > 1:
+            # [r5, advisor] Data-parallel: the rank that gave up skipped steps the others applied, so the replicas have DIVERGED (parameters,
+            # moments, step counts).  The outcome is made collective: every rank takes this branch (the count was summed over the ranks) and
+            # adopts rank 0's state -- one more exchange in which only rank 0 contributes, so the sum IS its state -- before raising.
+            pieces = [pa.flat, va.flat] + [t for o in opts for t in (o.exp_avg, o.exp_avg_sq)]
+            sync = torch.cat([t.reshape(-1) for t in pieces])
+            counts = torch.tensor([float(o.step_count) for o in opts] + [float(self.cumulative_model_updates)], dtype=torch.float64,
+                                  device=self._dev)
+            if c.rank != 0:
+                sync.zero_()
+                counts.zero_()
+            yield sync
+            yield counts
+            off = 0
+            for t in pieces:
+                t.copy_(sync[off:off + t.numel()].view_as(t))
+                off += t.numel()
+            n = counts.cpu().numpy()
+            self.policy_optimizer.step_count, self.value_optimizer.step_count = int(n[0]), int(n[1])
+            self.cumulative_model_updates = int(n[2])
+            pa.native_epoch += 1  # `flat` was rewritten behind torch's back: re-pack before the next kernel reads the weights
+            va.native_epoch += 1
+            pa.invalidate()
+            va.invalidate()
+            where = ("the rank(s) it happened on skipped optimiser steps the others applied; every rank has now adopted rank 0's "
+                     "parameters, Adam moments and step counts (bit-identical replicas again), no NaN was written")
+        raise OptimizerBarrierTimeout(
+            "rlppo_clip_adam_pack2: the optimiser's grid barrier gave up (%d skipped step(s) over all ranks); %s -- gradients are "
+            "zeroed and this learner now uses the three-operation optimiser tail: calling learn() again is safe"
+            % (int(stats[N.N_STATS + 3]), where))
 
     # ---------------------------------------------------------------------------------------- checkpoints
     def save_to(self, folder_path):
