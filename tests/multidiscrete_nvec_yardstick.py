@@ -88,44 +88,6 @@ def nvec_array(bins):
     return (ctypes.c_int32 * len(bins))(*[int(b) for b in bins])
 
 
-def run_minibatch_nvec(L, bins, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, ring=None, general=True):
-    """One fp32 pass of rlppo_ppo_minibatch_nvec with md_nvec / md_heads (general=False: NULL, the fixed kernel) over a workspace
-    prefilled with NaN bit patterns.  Returns (grad_policy, grad_value, stats, dz): dz = the policy's output buffer [mb][padded S]
-    after the pass -- the loss kernel's in-place gradient (the first region of the workspace plan: the policy's layer outputs)."""
-    from rlgym_ppo_amd import _native as N
-    from test_gpu_kernels import Net, check, dev, stream
-    if ring is not None:
-        rot = lambda x: np.roll(np.asarray(x), ring, axis=0)
-        obs_all, acts_all, old_all, tgt_all, adv_all = (rot(x) for x in (obs_all, acts_all, old_all, tgt_all, adv_all))
-    P_, V_ = Net(L, pol), Net(L, val)
-    states = P_.pad(obs_all)
-    acts = dev(np.asarray(acts_all, np.float32).reshape(len(obs_all), -1))
-    a = N.MinibatchArgs()
-    a.head, a.pol_layers, a.val_layers, a.act_dim = N.HEAD_MULTIDISCRETE, P_.nl, V_.nl, acts.shape[1]
-    a.pol_dims = ctypes.cast(P_.dims_c, ctypes.POINTER(ctypes.c_int32))
-    a.val_dims = ctypes.cast(V_.dims_c, ctypes.POINTER(ctypes.c_int32))
-    nvec = nvec_array(bins) if general else None
-    gp, gv = torch.zeros_like(P_.flat), torch.zeros_like(V_.flat)
-    old, tgt, adv = dev(old_all), dev(tgt_all), dev(adv_all)
-    idxd = dev(idx, torch.int64)
-    stats = torch.zeros(8, dtype=torch.float64, device="cuda")
-    mb = len(idx)
-    ws_bytes = int(L.rlppo_minibatch_workspace_bytes(P_.dims_c, P_.nl, V_.dims_c, V_.nl, mb))
-    ws = torch.full(((ws_bytes + 3) // 4,), -1, dtype=torch.int32, device="cuda")   # 0xFFFFFFFF: a NaN in every float
-    a.pol_packed, a.val_packed, a.pol_grad, a.val_grad = P_.packed.data_ptr(), V_.packed.data_ptr(), gp.data_ptr(), gv.data_ptr()
-    a.states, a.ld_states, a.n_rows, a.actions = states.data_ptr(), states.shape[1], states.shape[0], acts.data_ptr()
-    a.old_logp, a.targets, a.advantages, a.idx, a.mb = old.data_ptr(), tgt.data_ptr(), adv.data_ptr(), idxd.data_ptr(), mb
-    if ring is not None:
-        a.ring_base, a.ring_cap = ring, len(obs_all)
-    a.clip_range, a.ent_coef, a.mb_ratio = clip, ent, mb_ratio
-    a.stats, a.workspace, a.ws_bytes = stats.data_ptr(), ws.data_ptr(), ws_bytes
-    check(L, L.rlppo_ppo_minibatch_nvec(stream(), ctypes.byref(a), nvec, len(bins)))
-    torch.cuda.synchronize()
-    before = sum(int(L.rlppo_padded_out(d)) for d in P_.dims[1:-1])   # the hidden layers' outputs lie in front of the head's
-    dz = ws.view(torch.float32)[mb * before: mb * (before + P_.ld_out)].view(mb, P_.ld_out).cpu().numpy()
-    return nets.unflatten(gp.cpu(), pol), nets.unflatten(gv.cpu(), val), stats.cpu().numpy(), dz
-
-
 def check_output_gradient(dz, grad_policy, S):
     """dz is the loss kernel's in-place output: its column sums over the S logits are the head layer's bias gradient (so this IS the
     buffer), and every padded column >= S is exactly zero (not the NaN the workspace was prefilled with)."""

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import diag_gaussian_yardstick as Y
+import ppo_yardstick as PY
 import synthetic_env
 
 POL, VAL = [107, 256, 256, 8], [107, 256, 256, 1]
@@ -270,9 +271,9 @@ def test_yardstick_closed_forms_equal_torch_distributions():
     ls = rs.uniform(-1, 0.5, 3)
     obs = rs.randn(64, 13)
     _, acts, logp = Y.sample64(pol, ls, obs, rs.randn(64, 3))
-    args = (pol, ls, val, obs, acts, logp + 0.3 * rs.randn(64), rs.randn(64), rs.randn(64), 0.2, 0.005, 0.5)
-    r64, r32 = Y.minibatch(torch.float64, *args), Y.minibatch(torch.float32, *args)
-    assert Y.err(Y.tensors(r32), Y.tensors(r64)) < 1e-5
+    args = ("diag", pol, val, obs, acts, logp + 0.3 * rs.randn(64), rs.randn(64), rs.randn(64), 0.2, 0.005, 0.5)
+    r64, r32 = PY.minibatch(torch.float64, *args, log_std=ls), PY.minibatch(torch.float32, *args, log_std=ls)
+    assert PY.err(PY.tensors(r32), PY.tensors(r64)) < 1e-5
     assert abs(r64["entropy"] - float((Y.ENT_C + ls).sum())) < 1e-12
     # the hand-derived log_std gradient of the header, in float64
     f = lambda t: np.asarray(t, np.float64)

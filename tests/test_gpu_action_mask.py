@@ -12,29 +12,17 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import fp64_gate  # noqa: E402
+import ppo_yardstick as PY  # noqa: E402
 import synthetic_env  # noqa: E402
+from hip_pass import L, P, run_pass, stream, triple  # noqa: E402,F401
 from oracle import nets, ppo  # noqa: E402
 
 D = 107
-CLIP, ENT = 0.2, 0.005
-
-
-@pytest.fixture(scope="module")
-def L():
-    from rlgym_ppo_amd import _native as N
-    return N.lib()
+CLIP, ENT = PY.CLIP, PY.ENT
 
 
 def knob(L, key, value):
     assert L.rlppo_dbg_set(key, value) == 0
-
-
-def P(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def rand_mask(rs, n, A, p=0.66):
@@ -270,38 +258,6 @@ def test_one_launch_and_chain_agree_and_no_invalid_action_in_a_million_rows(L):
 
 
 # ----------------------------------------------------------------------------- 5: loss and gradient against float64 truth
-def masked_chain(pol, val, obs, acts, old, adv, tgt, mask, mb_ratio, dtype, mp=None, mv=None):
-    """The semantics of the masked update in torch autograd, float64 (under imposed ReLU decisions mp / mv) or float32 (the CPU
-    restatement, its own decisions): invalid logits -inf, softmax, clamp(1e-11, 1), log; entropy over valid actions."""
-    T = lambda x: torch.as_tensor(np.asarray(x), dtype=dtype)
-    Pp = [(T(w).requires_grad_(), T(b).requires_grad_()) for w, b in pol]
-    Vp = [(T(w).requires_grad_(), T(b).requires_grad_()) for w, b in val]
-
-    def fwd(ps, masks):
-        h = T(obs)
-        for l, (w, b) in enumerate(ps[:-1]):
-            pre = torch.nn.functional.linear(h, w, b)
-            h = torch.relu(pre) if masks is None else pre * T(masks[l])
-        return torch.nn.functional.linear(h, *ps[-1])
-
-    m = torch.as_tensor(np.asarray(mask, bool))
-    z = fwd(Pp, mp)
-    pc = torch.clamp(torch.softmax(z.masked_fill(~m, float("-inf")), -1), min=1e-11, max=1)
-    lp = torch.log(pc)
-    logp = lp.gather(1, torch.as_tensor(np.asarray(acts)).long().view(-1, 1)).view(-1)
-    entropy = -torch.where(m, lp * pc, torch.zeros_like(pc)).sum(-1).mean()
-    lr = logp - T(old)
-    ratio = torch.exp(lr)
-    A = T(adv)
-    ploss = -torch.min(ratio * A, torch.clamp(ratio, 1.0 - CLIP, 1.0 + CLIP) * A).mean()
-    vloss = ((fwd(Vp, mv).view(-1) - T(tgt)) ** 2).mean()
-    ((ploss - entropy * ENT) * mb_ratio).backward()
-    (vloss * mb_ratio).backward()
-    g = lambda ps: [(w.grad.detach().numpy().astype(np.float64), b.grad.detach().numpy().astype(np.float64)) for w, b in ps]
-    stats = [float(x.detach()) for x in (entropy, ((ratio - 1) - lr).mean(), vloss, ((ratio - 1).abs() > CLIP).double().mean(), ploss)]
-    return g(Pp), g(Vp), stats, ratio.detach().numpy().astype(np.float64)
-
-
 def make_problem(pol, val, n, A, seed):
     """Observations, random per-row masks, valid stored actions, and old log-probabilities that keep every ratio >= 5e-4 away from
     both clip edges (old = float64 masked log p of the action - d, d ~ N(0, 0.1^2) redrawn while |exp(d) - (1 +/- clip)| < 1e-3)."""
@@ -328,77 +284,9 @@ def make_problem(pol, val, n, A, seed):
                 redrawn=redrawn, outside=outside)
 
 
-class Net:
-    def __init__(self, L, ps):
-        from rlgym_ppo_amd import _native as N
-        self.dims = [ps[0][0].shape[1]] + [w.shape[0] for w, _ in ps]
-        self.nl = len(ps)
-        self.dims_c = N.dims_array(self.dims)
-        self.flat = nets.flatten(ps).cuda()
-        self.packed = torch.zeros(int(L.rlppo_packed_floats(self.dims_c, self.nl)), device="cuda")
-        N.check(L.rlppo_net_pack(stream(), self.dims_c, self.nl, P(self.flat), P(self.packed)))
-        self.ld_in = int(L.rlppo_padded_width(self.dims[0]))
-
-
-def run_minibatch(L, pol, val, pr, idx, mb_ratio=1.0, mask=True):
-    """rlppo_ppo_minibatch directly on the problem's rows (fp32) -> (grad_policy, grad_value, stats)."""
-    from rlgym_ppo_amd import _native as N
-    from rlgym_ppo_amd.util import action_mask as AM
-    Pn, Vn = Net(L, pol), Net(L, val)
-    n = pr["obs"].shape[0]
-    A = Pn.dims[-1]
-    src = torch.from_numpy(pr["obs"]).cuda()
-    states = torch.zeros(n, Pn.ld_in, device="cuda")
-    N.check(L.rlppo_pad_rows(stream(), P(src), 0, n, D, D, P(states), Pn.ld_in, 0, 0.0, 1.0))
-    dev = lambda x, dt=torch.float32: torch.as_tensor(np.asarray(x)).to("cuda", dt).contiguous()
-    acts, old, tgt, adv, idxd = dev(pr["acts"]).view(n, 1), dev(pr["old"]), dev(pr["tgt"]), dev(pr["adv"]), dev(idx, torch.int64)
-    words = AM.pack(pr["mask"], A, "cuda")
-    a = N.MinibatchArgs()
-    a.head, a.pol_layers, a.val_layers, a.act_dim = 0, Pn.nl, Vn.nl, 1
-    a.pol_dims = ctypes.cast(Pn.dims_c, ctypes.POINTER(ctypes.c_int32))
-    a.val_dims = ctypes.cast(Vn.dims_c, ctypes.POINTER(ctypes.c_int32))
-    gp, gv = torch.zeros_like(Pn.flat), torch.zeros_like(Vn.flat)
-    stats = torch.zeros(8, dtype=torch.float64, device="cuda")
-    mb = len(idx)
-    ws_bytes = int(L.rlppo_minibatch_workspace_bytes(Pn.dims_c, Pn.nl, Vn.dims_c, Vn.nl, mb))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
-    a.pol_packed, a.val_packed, a.pol_grad, a.val_grad = Pn.packed.data_ptr(), Vn.packed.data_ptr(), gp.data_ptr(), gv.data_ptr()
-    a.states, a.ld_states, a.n_rows, a.actions = states.data_ptr(), states.shape[1], n, acts.data_ptr()
-    a.old_logp, a.targets, a.advantages, a.idx, a.mb = old.data_ptr(), tgt.data_ptr(), adv.data_ptr(), idxd.data_ptr(), mb
-    a.clip_range, a.ent_coef, a.mb_ratio, a.var_m, a.var_b = CLIP, ENT, mb_ratio, 1.0, 0.0
-    a.stats, a.workspace, a.ws_bytes = stats.data_ptr(), ws.data_ptr(), ws_bytes
-    if mask:
-        a.action_mask, a.mask_words = words.data_ptr(), words.shape[1]
-    N.check(L.rlppo_ppo_minibatch(stream(), ctypes.byref(a)))
-    torch.cuda.synchronize()
-    return nets.unflatten(gp.cpu(), pol), nets.unflatten(gv.cpu(), val), stats.cpu().numpy()
-
-
-def masked_gate(L, pol, val, pr, got, label, mb_ratio=1.0):
-    """err(HIP, fp64 under the HIP's ReLU decisions) <= max(1e-5, 1.5 x err(CPU float32 restatement, fp64 under its own)), for
-    the gradients and for the five statistics; both printed."""
-    gp, gv, stats = got
-    args = (pr["obs"], pr["acts"], pr["old"], pr["adv"], pr["tgt"], pr["mask"], mb_ratio)
-    det = {}
-    ppo.minibatch_analytic("discrete", pol, val, pr["obs"], pr["acts"], pr["old"], pr["adv"], pr["tgt"], CLIP, ENT, mb_ratio, (0.1, 1.0),
-                           detail=det)   # (the hidden layers know no mask: their float64 pre-activations and rounding scales)
-    cp, cv, cstats, _ = masked_chain(pol, val, *args, torch.float32)
-    res = {}
-    for who, g_p, g_v, st, mp, mv in (("hip", gp, gv, stats, fp64_gate.hip_masks(L, pol, pr["obs"]), fp64_gate.hip_masks(L, val, pr["obs"])),
-                                      ("cpu", cp, cv, cstats, fp64_gate.cpu_masks(pol, pr["obs"]), fp64_gate.cpu_masks(val, pr["obs"]))):
-        flips = fp64_gate._check_flips(pol, mp, det["pol"], who) + fp64_gate._check_flips(val, mv, det["val"], who)
-        tp, tv, tstats, _ = masked_chain(pol, val, *args, torch.float64, mp, mv)
-        err = fp64_gate.grads_err(list(g_p) + list(g_v), tp + tv)
-        serr = None if st is None else [abs(float(st[k]) - tstats[k]) / max(abs(tstats[k]), 1e-12) for k in range(5)]
-        res[who] = (err, serr, flips)
-    print(f"[masked fp64 gate] {label}: err(HIP, fp64)={res['hip'][0]:.2e}  err(CPU fp32, fp64)={res['cpu'][0]:.2e}  ReLU flips HIP "
-          f"{res['hip'][2]} / CPU {res['cpu'][2]}  stats (entropy, kl, vloss, clipfrac, ploss) HIP {res['hip'][1]} CPU {res['cpu'][1]}  "
-          f"old log-probs redrawn {pr['redrawn']}, rows outside the clip interval {pr['outside']:.3f}")
-    assert res["hip"][0] <= max(1e-5, 1.5 * res["cpu"][0]), (label, res["hip"][0], res["cpu"][0])
-    if res["hip"][1] is not None:
-        for k in range(5):
-            assert res["hip"][1][k] <= max(1e-5, 1.5 * res["cpu"][1][k]), (label, "statistic", k, res["hip"][1][k], res["cpu"][1][k])
-    return res
+def rows_of(pr):
+    """A problem as hip_pass.run_pass takes it: (the five row arrays, keywords: rlppo_ppo_minibatch, fp32, under the problem's mask)."""
+    return (pr["obs"], pr["acts"], pr["old"], pr["tgt"], pr["adv"]), dict(head="discrete", clip=CLIP, ent=ENT, mask=pr["mask"])
 
 
 @pytest.mark.parametrize("hidden,A", [((128, 128), 90), ((256, 256, 256), 90), ((128, 128), 200)])
@@ -408,14 +296,16 @@ def test_masked_loss_and_gradient_against_float64(L, hidden, A):
     pol, val = nets.init_mlp(D, hidden, A), nets.init_mlp(D, hidden, 1)
     n = 4096
     pr = make_problem(pol, val, n, A, seed=A)
-    got = run_minibatch(L, pol, val, pr, np.random.RandomState(1).permutation(n))
-    masked_gate(L, pol, val, pr, got, f"{D} -> {hidden} -> {A}")
+    rows, kw = rows_of(pr)
+    got = triple(run_pass(L, pol, val, *rows, np.random.RandomState(1).permutation(n), **kw))
+    PY.masked_gate(L, "discrete", pol, val, pr, got, f"[masked fp64 gate] {D} -> {hidden} -> {A}")
     # a stored action its own mask marks invalid (a caller error) stays finite
     pr2 = dict(pr)
     pr2["mask"] = pr["mask"].copy()
     pr2["mask"][np.arange(0, n, 9), pr["acts"][::9].astype(int)] = False
     pr2["mask"][np.arange(0, n, 9), (pr["acts"][::9].astype(int) + 1) % A] = True
-    gp, gv, st = run_minibatch(L, pol, val, pr2, np.arange(n))
+    rows, kw = rows_of(pr2)
+    gp, gv, st = triple(run_pass(L, pol, val, *rows, np.arange(n), **kw))
     assert all(bool(torch.isfinite(w).all()) and bool(torch.isfinite(b).all()) for w, b in gp) and np.isfinite(st).all()
 
 
@@ -436,7 +326,8 @@ def test_column_constant_mask_is_the_narrower_network(L):
     old = (np.log(p[np.arange(n), acts_S]) + 0.1 * rs.randn(n)).astype(np.float32)
     pr = dict(obs=obs, mask=m, acts=S[acts_S].astype(np.float32), old=old, adv=rs.randn(n).astype(np.float32),
               tgt=rs.randn(n).astype(np.float32))
-    gp, gv, stats = run_minibatch(L, pol, val, pr, rs.permutation(n))
+    rows, kw = rows_of(pr)
+    gp, gv, stats = triple(run_pass(L, pol, val, *rows, rs.permutation(n), **kw))
     hw, hb = gp[-1]
     assert bool((hw[out_S] == 0.0).all()) and bool((hb[out_S] == 0.0).all())            # exactly zero outside S
     gp_S = list(gp[:-1]) + [(hw[S], hb[S])]
@@ -563,7 +454,7 @@ def test_every_pass_form_sees_the_right_rows_of_a_wrapped_ring(L):
         gp, o = split(g, pol)
         gv, _ = split(g[o:], val)
         if form in ("paired", "slots2"):
-            masked_gate(L, pol, val, pr, (gp, gv, None), f"wrapped ring, {form}")
+            PY.masked_gate(L, "discrete", pol, val, pr, (gp, gv, None), f"[masked fp64 gate] wrapped ring, {form}")
     # the two gather forms: bit for bit where the unmasked pass is
     unmasked = {}
     for form, k26 in (("separate", 0), ("rowtab", 2)):

@@ -8,7 +8,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import nets, ppo  # noqa: E402
 import fp64_gate  # noqa: E402
-from test_gpu_kernels import L, relerr, run_minibatch  # noqa: E402,F401
+from hip_pass import L, relerr, run_minibatch  # noqa: E402,F401
 
 
 def test_cfg5_shape_minibatch_and_sampling(L):

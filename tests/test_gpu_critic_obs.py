@@ -4,7 +4,7 @@ with critic_observations=True through the three collect paths of the vector mana
 
 Two kinds of claim.  Where the critic's matrix is a copy of the policy's, everything must equal the symmetric run BIT FOR BIT (same
 launches on the same numbers).  Where the widths differ (policy 13, critic 29) the pass is held to float64 under the project's rule,
-err(HIP, fp64) <= max(1e-5, 1.5 x err(float32 yardstick, fp64)): tanh / ELU against tests/critic_obs_yardstick.py; ReLU, whose two
+err(HIP, fp64) <= max(1e-5, 1.5 x err(float32 yardstick, fp64)): tanh / ELU against tests/ppo_yardstick.py; ReLU, whose two
 chains are independent, bit for bit against two symmetric passes (one per matrix, with a dummy partner) and per network through
 tests/fp64_gate.py under the pass's own ReLU decisions."""
 import contextlib
@@ -18,15 +18,15 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import nets  # noqa: E402
-import activation_yardstick as A  # noqa: E402
 import critic_obs_env as CE  # noqa: E402
-import critic_obs_yardstick as Y  # noqa: E402
 import fp64_gate  # noqa: E402
-from test_gpu_kernels import L, P, check, dev, stream  # noqa: E402,F401
+import ppo_yardstick as A  # noqa: E402
+from diag_gaussian_yardstick import assert_clear_of_clip_edges  # noqa: E402
+from hip_pass import L, P, check, dev, run_pass, stream  # noqa: E402,F401
 
 CLIP, ENT = 0.2, 0.005
 OBS, COBS = CE.OBS, CE.CRITIC_OBS
-C_PASS, C_PAIRED, C_FUSED, C_GROUP, C_CRITIC = 2, 3, 4, 5, Y.COUNTER
+C_PASS, C_PAIRED, C_FUSED, C_GROUP, C_CRITIC = 2, 3, 4, 5, 15   # 15 = rlppo_dbg_counter: passes with separate critic rows
 
 
 def counters(L, *keys):
@@ -112,7 +112,7 @@ def make_case(head, seed, act, pol_hidden=(64, 128), val_hidden=(32, 64), n=420,
     if mask is not None:
         z = z.masked_fill(~torch.as_tensor(mask), float("-inf"))
     ls64 = None if log_std is None else torch.as_tensor(log_std, dtype=torch.float64)
-    logp = A.head_terms(head, z, torch.as_tensor(act_, dtype=torch.float64), torch.float64, log_std=ls64)[0].numpy()
+    logp = A.head_terms(head, z, torch.as_tensor(act_, dtype=torch.float64), log_std=ls64)[0].numpy()
     cls = np.arange(n) % 3
     off = 0.05 * rs.randn(n) + np.where(cls == 1, -0.5, 0.0) + np.where(cls == 2, 0.5, 0.0)
     return dict(head=head, pol=pol, val=val, obs=obs, cobs=cobs, act=act_, log_std=log_std, mask=mask, act_name=act,
@@ -125,8 +125,10 @@ def run(L, c, idx, entry, mb_ratio=1.0, **kw):
     kw.setdefault("obs_all", c["obs"])
     kw.setdefault("cobs_all", c["cobs"])
     pol, val, obs_all, cobs_all = (kw.pop(k) for k in ("pol", "val", "obs_all", "cobs_all"))
-    return Y.run_pass(L, c["head"], c["act_name"], c["act_name"], pol, val, obs_all, c["act"], c["old"], c["tgt"], c["adv"], idx, CLIP, ENT, mb_ratio,
-                      cobs_all=cobs_all, log_std=c["log_std"], mask=c["mask"], entry=entry, **kw)
+    kw.setdefault("precision", "fp32")
+    return run_pass(L, pol, val, obs_all, c["act"], c["old"], c["tgt"], c["adv"], idx, head=c["head"], entry=entry, pol_act=c["act_name"],
+                    val_act=c["act_name"], clip=CLIP, ent=ENT, mb_ratio=mb_ratio, cobs=cobs_all, log_std=c["log_std"], mask=c["mask"],
+                    raise_rc=False, **kw)
 
 
 def same(a, b):
@@ -191,19 +193,19 @@ def test_alias_pass_never_pairs(L):
 @pytest.mark.parametrize("act", ["tanh", "elu"])
 @pytest.mark.parametrize("head", ["discrete", "diag"])
 def test_two_widths_against_float64(L, head, act):
-    """Policy width 13, critic width 29, tanh / ELU (no hidden decision is discrete: activation_yardstick's docstring); also from a
+    """Policy width 13, critic width 29, tanh / ELU (no hidden decision is discrete: ppo_yardstick's docstring); also from a
     ring-mapped buffer and with n_rows == 0, bit-identical."""
     c = make_case(head, 71, act, critic_width=COBS, masked=False)
     idx = c["rs"].permutation(len(c["obs"]))[:300]
-    args = (c["act_name"], c["act_name"], c["pol"], c["val"], c["obs"][idx], c["cobs"][idx], c["act"][idx], c["old"][idx], c["adv"][idx], c["tgt"][idx],
-            CLIP, ENT, 0.5)
-    r64, r32 = (Y.minibatch(dt, head, *args, log_std=c["log_std"]) for dt in (torch.float64, torch.float32))
-    A.assert_clear_of_clip_edges(r64["ratio"], CLIP)
+    args = (c["pol"], c["val"], c["obs"][idx], c["act"][idx], c["old"][idx], c["adv"][idx], c["tgt"][idx], CLIP, ENT, 0.5)
+    r64, r32 = (A.minibatch(dt, head, *args, pol_act=c["act_name"], val_act=c["act_name"], cobs=c["cobs"][idx], log_std=c["log_std"])
+                for dt in (torch.float64, torch.float32))
+    assert_clear_of_clip_edges(r64["ratio"], CLIP)
     c0 = counters(L, C_PASS, C_PAIRED, C_FUSED, C_CRITIC)
     got = run(L, c, idx, "critic", mb_ratio=0.5)
     assert got["rc"] == 0, got["msg"]
     assert [b - a for a, b in zip(c0, counters(L, C_PASS, C_PAIRED, C_FUSED, C_CRITIC))] == [1, 0, 0, 1]
-    Y.gate(got, r64, r32, f"critic rows 13 / 29, {head} {act}")
+    A.gate(got, r64, r32, f"[act fp64 gate] critic rows 13 / 29, {head} {act}")
     for kw in (dict(ring=137), dict(n_rows=0)):
         other = run(L, c, idx, "critic", mb_ratio=0.5, **kw)
         assert other["rc"] == 0 and same(other, got), kw
@@ -278,7 +280,7 @@ def learn_inputs(act, critic_width, seed=LEARN_SEED):
     cobs = np.concatenate([obs, np.clip(rs.randn(N_ROWS, critic_width - OBS) * 2 + 0.5, -5, 5).astype(np.float32)], 1) if critic_width != OBS else obs.copy()
     acts = rs.randint(0, 6, N_ROWS).astype(np.float32)
     z = torch.as_tensor(A.forward64(pol, obs, act))
-    logp = A.head_terms("discrete", z, torch.as_tensor(acts, dtype=torch.float64), torch.float64)[0].numpy()
+    logp = A.head_terms("discrete", z, torch.as_tensor(acts, dtype=torch.float64))[0].numpy()
     exp = dict(states=obs, critic_states=cobs, actions=acts, log_probs=(logp + 0.1 * rs.randn(N_ROWS)).astype(np.float32),
                values=rs.randn(N_ROWS).astype(np.float32), advantages=rs.randn(N_ROWS).astype(np.float32))
     return pol, val, exp
@@ -361,7 +363,7 @@ def learn_yardstick(pol, val, exp):
     """The float64 and float32 yardsticks of the width-29 tanh learn(): computed once, shared, left unchanged."""
     if "tanh" not in _YARD:
         weakest = {}
-        run_ = lambda dt, **kw: Y.learn(dt, "discrete", "tanh", pol, val, exp, B, MB, EPOCHS, CLIP, ENT, LR, LR, np.random.RandomState(LEARN_SEED), **kw)
+        run_ = lambda dt, **kw: A.learn(dt, "discrete", "tanh", pol, val, exp, B, MB, EPOCHS, CLIP, ENT, LR, LR, np.random.RandomState(LEARN_SEED), **kw)
         t = run_(torch.float64, weakest=weakest)
         _YARD["tanh"] = (t[0], t[1], *run_(torch.float32), weakest)
     return _YARD["tanh"]

@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 from oracle import nets  # noqa: E402
 import diag_gaussian_env as E  # noqa: E402
 import diag_gaussian_yardstick as Y  # noqa: E402
-from test_gpu_kernels import L, Net, P, check, dev, stream  # noqa: E402,F401
+import ppo_yardstick as PY  # noqa: E402
+from hip_pass import L, Net, P, check, dev, run_pass, stream  # noqa: E402,F401
 
 U32 = 2.0 ** -24
 CLIP, ENT = 0.2, 0.005
@@ -46,21 +47,23 @@ def make_case(seed, n, d, k, hidden=(), noise=True):
 
 def yard(c, idx, mb_ratio, **opt):
     """(float64, float32) yardstick results on rows idx, after the CPU assertions on the float64 one."""
-    args = (c["pol"], c["log_std"], c["val"], c["obs"][idx], c["act"][idx], c["old"][idx], c["adv"][idx], c["tgt"][idx], CLIP, ENT, mb_ratio)
-    r64 = Y.minibatch(torch.float64, *args, **opt)
+    args = ("diag", c["pol"], c["val"], c["obs"][idx], c["act"][idx], c["old"][idx], c["adv"][idx], c["tgt"][idx], CLIP, ENT, mb_ratio)
+    opt = dict(opt, log_std=c["log_std"])
+    r64 = PY.minibatch(torch.float64, *args, **opt)
     Y.assert_clear_of_clip_edges(r64["ratio"], CLIP)
     if len(c["pol"]) > 1:
         Y.assert_relu_clear(c["pol"], c["obs"][idx], "policy")
         Y.assert_relu_clear(c["val"], c["obs"][idx], "critic")
-    return r64, Y.minibatch(torch.float32, *args, **opt)
+    return r64, PY.minibatch(torch.float32, *args, **opt)
 
 
-def hip(L, c, idx, mb_ratio, **kw):
-    return Y.run_minibatch_diag(L, c["pol"], c["log_std"], c["val"], c["obs"], c["act"], c["old"], c["tgt"], c["adv"], idx, CLIP, ENT, mb_ratio, **kw)
+def hip(L, c, idx, mb_ratio, precision="fp32", **kw):
+    return run_pass(L, c["pol"], c["val"], c["obs"], c["act"], c["old"], c["tgt"], c["adv"], idx, head="diag", entry="diag", log_std=c["log_std"],
+                    clip=CLIP, ent=ENT, mb_ratio=mb_ratio, precision=precision, **kw)
 
 
 def got_tensors(r):
-    return Y.tensors(r)
+    return PY.tensors(r)
 
 
 # ------------------------------------------------------------------------------------------------ 1. rollout step
@@ -104,9 +107,9 @@ def check_logp(logp, act, mean64, c, label, mean32=None):
     a = torch.as_tensor(act)
     want = Y.logp_terms(a.double(), torch.as_tensor(mean64, dtype=torch.float64), torch.as_tensor(c["log_std"]).double()).sum(-1).numpy()
     if mean32 is None:
-        mean32 = Y.mlp(c["pol"], torch.as_tensor(c["obs"][:len(act)]))
+        mean32 = PY.mlp(c["pol"], torch.as_tensor(c["obs"][:len(act)]))
     f32 = Y.logp_terms(a, mean32, torch.as_tensor(c["log_std"])).sum(-1).numpy()
-    e_hip, e_32 = Y.rel(logp, want), Y.rel(f32, want)
+    e_hip, e_32 = PY.rel(logp, want), PY.rel(f32, want)
     print(f"[diag fp64 gate] {label}: logp err(HIP, fp64)={e_hip:.2e}  err(float32 yardstick, fp64)={e_32:.2e}")
     assert e_hip <= max(1e-5, 1.5 * e_32), (label, e_hip, e_32)
 
@@ -120,7 +123,7 @@ def test_rollout_step(L, n, k):
     mean64 = Y.sample64(c["pol"], c["log_std"], c["obs"], c["eps"])[0]
     net = Net(L, c["pol"])
     act, logp, mu = act_diag(L, net, c, n)
-    assert Y.rel(mu, mean64) <= 1e-5
+    assert PY.rel(mu, mean64) <= 1e-5
     check_actions(act, mu, c, n)
     check_logp(logp, act, mean64, c, f"rollout n={n} k={k}")
     # a changed log_std is seen by the next call
@@ -173,7 +176,7 @@ def test_policy_class_rollout_paths_follow_log_std():
         ae, le = pol.get_action(obs, noise=eps)           # the eager path
         assert torch.equal(ag, ae) and torch.equal(lg, le) and n_graphs == 1
         mean64, act64, logp64 = Y.sample64(params, ls, obs, eps.numpy())
-        assert Y.rel(ag, act64) <= 1e-5 and Y.rel(lg, logp64) <= 1e-5
+        assert PY.rel(ag, act64) <= 1e-5 and PY.rel(lg, logp64) <= 1e-5
         return ag
 
     a1 = both(np.full(k, -0.25))
@@ -185,14 +188,14 @@ def test_policy_class_rollout_paths_follow_log_std():
     assert a2.abs().max() > 1.0                                                    # nothing is clamped
     det, zero = pol.get_action(obs, deterministic=True)
     mean64 = Y.sample64(params, np.zeros(k), obs, np.zeros((40, k)))[0]
-    assert zero == 0 and det.shape == (40, k) and Y.rel(det, mean64) <= 1e-5 and not torch.equal(det[0], det[1])
+    assert zero == 0 and det.shape == (40, k) and PY.rel(det, mean64) <= 1e-5 and not torch.equal(det[0], det[1])
     mean, std = pol.get_output(obs)
     assert torch.equal(mean.cpu(), det) and torch.allclose(std.cpu(), torch.tensor([0.5, -1.0, 0.0]).exp())
     with pytest.raises(ValueError, match="Gaussian"):
         pol.get_action(obs, action_mask=np.ones((40, k), bool))
     # the stock-torch accessor agrees with the kernels
     lp, ent = pol.get_backprop_data(obs, a2)
-    assert Y.rel(lp.detach().cpu(), Y.sample64(params, [0.5, -1.0, 0.0], obs, eps.numpy())[2]) <= 1e-5
+    assert PY.rel(lp.detach().cpu(), Y.sample64(params, [0.5, -1.0, 0.0], obs, eps.numpy())[2]) <= 1e-5
     assert abs(ent.item() - (3 * Y.ENT_C - 0.5)) < 1e-5
     # a state dict round trip keeps the parameter where the kernels read it
     other = DiagGaussianPolicy(d, k, (32, 32), "cuda:0")
@@ -216,7 +219,7 @@ def test_minibatch_against_float64(L, mb, k):
         assert (r64["ratio"] < 0.8).sum() > 20 and (r64["ratio"] > 1.2).sum() > 20 and ((r64["ratio"] > 0.8) & (r64["ratio"] < 1.2)).sum() > 20
         assert (c["adv"][idx] > 0).sum() > 20 and (c["adv"][idx] < 0).sum() > 20
     got = hip(L, c, idx, 0.5)
-    Y.gate(got_tensors(got), got["stats"], r64, r32, f"one-layer mb={mb} k={k}")
+    PY.gate(got, r64, r32, f"[diag fp64 gate] one-layer mb={mb} k={k}")
     assert got["stats"][5:].tolist() == [0.0, 0.0, 0.0]
     again = hip(L, c, idx, 0.5)
     assert torch.equal(got["gp"], again["gp"]) and torch.equal(got["gv"], again["gv"])
@@ -232,7 +235,7 @@ def test_minibatch_ring_repeats_empty_and_accumulation(L):
     # a ring-mapped buffer with ring_base != 0 gives the plain buffer's bits; so does n_rows == 0 (rows gathered into the workspace)
     plain = hip(L, c, idx, 0.5)
     ring = hip(L, c, idx, 0.5, ring=123)
-    Y.gate(got_tensors(ring), ring["stats"], r64, r32, "ring_base=123, repeated rows")
+    PY.gate(ring, r64, r32, "[diag fp64 gate] ring_base=123, repeated rows")
     assert torch.equal(plain["gp"], ring["gp"]) and torch.equal(plain["gv"], ring["gv"])
     unknown = hip(L, c, idx, 0.5, n_rows=0)
     assert torch.equal(plain["gp"], unknown["gp"]) and torch.equal(plain["gv"], unknown["gv"])
@@ -245,7 +248,7 @@ def test_minibatch_ring_repeats_empty_and_accumulation(L):
     n_net = plain["gp"].numel() - 3
     assert torch.equal(ab["gp"][n_net:], plain["gp"][n_net:] + b["gp"][n_net:])
     for x, p_, q_ in ((ab["gp"], plain["gp"], b["gp"]), (ab["gv"], plain["gv"], b["gv"])):
-        assert Y.rel(x.cpu(), (p_.double() + q_.double()).cpu()) <= 1e-6
+        assert PY.rel(x.cpu(), (p_.double() + q_.double()).cpu()) <= 1e-6
     # an empty pass launches nothing and touches nothing
     from rlgym_ppo_amd import _native as N
     a = N.MinibatchArgs()
@@ -267,7 +270,7 @@ def test_minibatch_options(L):
     assert np.abs(dv - vclip).min() > 1e-5 and (dv < vclip).sum() > 20 and (dv > vclip).sum() > 20
     r64, r32 = yard(c, idx, 0.5, adv_norm=an, value_clip=vclip)
     got = hip(L, c, idx, 0.5, adv_norm=an, value_clip=vclip, kl_slots=True)
-    Y.gate(got_tensors(got), got["stats"], r64, r32, "adv_norm + value_clip + kl_slots")
+    PY.gate(got, r64, r32, "[diag fp64 gate] adv_norm + value_clip + kl_slots")
     grid = (700 + 255) // 256
     assert got["kl"][0] == grid and got["kl"][1] == 0.5
     assert abs(got["kl"][2:2 + grid].sum() - got["stats"][1]) <= 1e-12 * abs(got["stats"][1])
@@ -306,17 +309,17 @@ def test_three_layer_pass_in_the_paired_launch_form(L, k):
         assert L.rlppo_dbg_counter(3) == n_paired + 1
     finally:
         check(L, L.rlppo_dbg_set(29, 1))
-    Y.gate(got_tensors(paired), paired["stats"], r64, r32, "three layers, paired launches")
-    Y.gate(got_tensors(two_chains), two_chains["stats"], r64, r32, "three layers, two chains")
+    PY.gate(paired, r64, r32, "[diag fp64 gate] three layers, paired launches")
+    PY.gate(two_chains, r64, r32, "[diag fp64 gate] three layers, two chains")
     # (the policy's arena, tail included, bit for bit; the critic's one-output head may be summed in another order by the form)
-    assert torch.equal(paired["gp"], two_chains["gp"]) and Y.rel(paired["gv"].cpu(), two_chains["gv"].cpu()) <= 2e-6
+    assert torch.equal(paired["gp"], two_chains["gp"]) and PY.rel(paired["gv"].cpu(), two_chains["gv"].cpu()) <= 2e-6
     # one stream instead of two: the same bits
     check(L, L.rlppo_dbg_set(4, 0))
     try:
         one_stream = hip(L, c, idx, 1.0)
     finally:
         check(L, L.rlppo_dbg_set(4, 1))
-    assert torch.equal(one_stream["gp"], two_chains["gp"]) and Y.rel(one_stream["gv"].cpu(), two_chains["gv"].cpu()) <= 2e-6
+    assert torch.equal(one_stream["gp"], two_chains["gp"]) and PY.rel(one_stream["gv"].cpu(), two_chains["gv"].cpu()) <= 2e-6
 
 
 @pytest.mark.parametrize("precision", ["bf16", "x3"])
@@ -337,16 +340,16 @@ def test_other_update_precisions(L, precision):
     assert torch.equal(got["gp"], again["gp"]) and torch.equal(got["gv"], again["gv"])
     assert np.isfinite(got["gp"].cpu().numpy()).all() and np.isfinite(got["stats"]).all()
     if precision == "x3":
-        Y.gate(got_tensors(got), got["stats"], r64, r32, "three layers, x3")
+        PY.gate(got, r64, r32, "[diag fp64 gate] three layers, x3")
         return
-    args = (c["pol"], c["log_std"], c["val"], c["obs"][idx], c["act"][idx], c["old"][idx], c["adv"][idx], c["tgt"][idx], CLIP, ENT, 1.0)
+    args = ("diag", c["pol"], c["val"], c["obs"][idx], c["act"][idx], c["old"][idx], c["adv"][idx], c["tgt"][idx], CLIP, ENT, 1.0)
     with nets.bf16_operands():
-        ref = Y.minibatch(torch.float32, *args)
+        ref = PY.minibatch(torch.float32, *args, log_std=c["log_std"])
     with nets.bf16_operands(), nets.sum64():
-        ref2 = Y.minibatch(torch.float32, *args)
-    floor = Y.err(Y.tensors(ref2), Y.tensors(ref))
-    e_ref, e_true, e_ref_true = Y.err(got_tensors(got), Y.tensors(ref)), Y.err(got_tensors(got), Y.tensors(r64)), Y.err(Y.tensors(ref), Y.tensors(r64))
-    ls_ref, ls_true = Y.rel(got["grad_log_std"], ref["grad_log_std"]), Y.rel(got["grad_log_std"], r64["grad_log_std"])
+        ref2 = PY.minibatch(torch.float32, *args, log_std=c["log_std"])
+    floor = PY.err(PY.tensors(ref2), PY.tensors(ref))
+    e_ref, e_true, e_ref_true = PY.err(got_tensors(got), PY.tensors(ref)), PY.err(got_tensors(got), PY.tensors(r64)), PY.err(PY.tensors(ref), PY.tensors(r64))
+    ls_ref, ls_true = PY.rel(got["grad_log_std"], ref["grad_log_std"]), PY.rel(got["grad_log_std"], r64["grad_log_std"])
     print(f"[diag bf16 update] err(HIP bf16, CPU bf16 restatement)={e_ref:.2e}  summation-order floor of the restatement itself={floor:.2e}  "
           f"distance from float64 truth of the fp32 function: HIP {e_true:.2e}, restatement {e_ref_true:.2e}; log_std gradient alone: "
           f"against the restatement {ls_ref:.2e}, against float64 {ls_true:.2e}")
@@ -478,8 +481,8 @@ def learn_yardstick(pol, ls, val, exp):
     computed once, shared, left unchanged.  -> (t_pol, t_val, f_pol, f_val, weakest)."""
     if not _LEARN_YARD:
         weakest = {}
-        t_pol, t_val = Y.learn(torch.float64, pol, ls, val, exp, B, MB, EPOCHS, CLIP, ENT, LR, LR, np.random.RandomState(LEARN_SEED), weakest=weakest)
-        f_pol, f_val = Y.learn(torch.float32, pol, ls, val, exp, B, MB, EPOCHS, CLIP, ENT, LR, LR, np.random.RandomState(LEARN_SEED))
+        t_pol, t_val = PY.learn(torch.float64, "diag", "relu", pol, val, exp, B, MB, EPOCHS, CLIP, ENT, LR, LR, np.random.RandomState(LEARN_SEED), log_std=ls, weakest=weakest)
+        f_pol, f_val = PY.learn(torch.float32, "diag", "relu", pol, val, exp, B, MB, EPOCHS, CLIP, ENT, LR, LR, np.random.RandomState(LEARN_SEED), log_std=ls)
         _LEARN_YARD["r"] = (t_pol, t_val, f_pol, f_val, weakest)
         _LEARN_YARD["p0"] = np.concatenate([t.numpy().ravel() for wb in pol for t in wb])
     assert np.array_equal(_LEARN_YARD["p0"], np.concatenate([t.numpy().ravel() for wb in pol for t in wb]))   # the same learn()

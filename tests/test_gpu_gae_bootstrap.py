@@ -11,34 +11,12 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import gae_bootstrap_yardstick as Y  # noqa: E402
+from hip_pass import L, P, check, dev, stream  # noqa: E402,F401
 
 GAMMA, LMBDA = 0.99, 0.95
 CHUNK = 2048
 # single ragged chunk | exact chunk | chunk + 1 | n mod 4, 8, 512, 2048 all non-zero | three chunks and a ragged last wave
 SIZES = [1, 7, 2047, 2048, 2049, 5003, 3 * 2048 + 300]
-
-
-@pytest.fixture(scope="module")
-def L():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from rlgym_ppo_amd import _native as N
-    return N.lib()
-
-
-def dev(x):
-    return torch.as_tensor(np.asarray(x, np.float32)).to("cuda").contiguous()
-
-
-def P(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def check(L, rc):
-    assert rc == 0, L.rlppo_last_error()
 
 
 @pytest.fixture(params=[1, 0], ids=["lookback", "two_launch"])

@@ -14,7 +14,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import nets, ppo  # noqa: E402
 import fp64_gate  # noqa: E402
-from test_gpu_kernels import L, Net, P, check, dev, relerr, run_minibatch, stream  # noqa: E402,F401
+import ppo_yardstick as PY  # noqa: E402
+from hip_pass import L, Net, P, check, dev, relerr, run_minibatch, run_pass, stream, triple  # noqa: E402,F401
 
 D = 107
 
@@ -42,7 +43,7 @@ def make_case(head, seed, n, k=8, hidden=(256, 256, 256), var=(0.1, 1.0), noise=
     return pol, val, obs, acts, old, tgt, adv, rs
 
 
-def gate(L, head, pol, val, obs, acts, old, tgt, adv, idx, mb_ratio, got, var=(0.1, 1.0), label=""):
+def gate_rows(L, head, pol, val, obs, acts, old, tgt, adv, idx, mb_ratio, got, var=(0.1, 1.0), label=""):
     return fp64_gate.gate(L, head, pol, val, obs[idx], acts[idx], old[idx], adv[idx], tgt[idx], 0.2, 0.005, mb_ratio, got, var=var,
                           label=label)
 
@@ -99,7 +100,7 @@ def test_launch_forms_for_every_head(L, head, k):
     within(gp0 + gv0, gp3 + gv3, 2e-6, "per_layer_dw")
     runs["per_layer_dw"] = (gp3, gv3, st3)
     for key in ("fused", "two_chains", "folded_value_head", "per_layer_dw"):
-        gate(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.25, runs[key], label=f"{head} k={k} {key}, ragged 1500-row minibatch")
+        gate_rows(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.25, runs[key], label=f"{head} k={k} {key}, ragged 1500-row minibatch")
 
 
 # ------------------------------------------------------------------------------- 2. shapes and edges of the non-discrete heads
@@ -145,7 +146,7 @@ def test_gaussian_widths_and_edges(L, k, var, mb):
     ratio = np.exp(logp.numpy()[idx].astype(np.float64) - old[idx])
     assert (ratio < 0.8).sum() > 10 and (ratio > 1.2).sum() > 10
     got = run_minibatch(L, "gaussian", pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.5, var=var)
-    gate(L, "gaussian", pol, val, obs, acts, old, tgt, adv, idx, 0.5, got, var=var, label=f"gaussian k={k} var={var} mb={mb}")
+    gate_rows(L, "gaussian", pol, val, obs, acts, old, tgt, adv, idx, 0.5, got, var=var, label=f"gaussian k={k} var={var} mb={mb}")
 
 
 def test_multidiscrete_saturated_logits(L):
@@ -179,7 +180,7 @@ def test_multidiscrete_saturated_logits(L):
         assert set(np.unique(acts[idx, h]).astype(int)) == set(range(b)), h
     assert logp.numpy()[idx].min() < -50
     got = run_minibatch(L, "multidiscrete", pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.5)
-    gate(L, "multidiscrete", pol, val, obs, acts, old, tgt, adv, idx, 0.5, got, label="multi-discrete, +-30 logits, 2999 rows")
+    gate_rows(L, "multidiscrete", pol, val, obs, acts, old, tgt, adv, idx, 0.5, got, label="multi-discrete, +-30 logits, 2999 rows")
 
 
 @pytest.mark.parametrize("k,n", [(1, 700), (17, 513), (32, 300), (40, 611), (64, 333)])
@@ -266,7 +267,7 @@ def test_ring_resident_minibatch_is_bitwise_the_plain_one(L, head, k, k26):
     bit_equal(plain[0] + plain[1], ring[0] + ring[1], f"ring {head} 26={k26}")
     np.testing.assert_allclose(plain[2], ring[2], rtol=1e-12, atol=0)
     if k26 == 2:  # (one gate per head: the bit-equality above carries it to the other form)
-        gate(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.5, ring, label=f"{head} k={k}, ring-resident")
+        gate_rows(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.5, ring, label=f"{head} k={k}, ring-resident")
 
 
 # ------------------------------------------------------------------------------- 6. the paired pass at its default size
@@ -294,7 +295,7 @@ def test_paired_pass_default_size_other_heads(L, head):
         for i in (0, 1):
             assert relerr(whole[i], parts[i]) < 1e-5
     np.testing.assert_allclose(st[:5], st_sum / 4, rtol=1e-5, atol=1e-8)
-    gate(L, head, pol, val, obs, acts, old, tgt, adv, idx, 1.0, (gp, gv, st), label=f"{head}, paired pass, 262,144 rows")
+    gate_rows(L, head, pol, val, obs, acts, old, tgt, adv, idx, 1.0, (gp, gv, st), label=f"{head}, paired pass, 262,144 rows")
 
 
 # ------------------------------------------------------------------------------- 4. learn() with 40 action dimensions
@@ -451,8 +452,9 @@ def test_masked_loss_widest_rows(L, A):
     old = (logp - np.array([0.05, -0.3, 0.3, -0.05, 0.1])).astype(np.float32)
     pr = dict(obs=obs, mask=m, acts=acts, old=old, adv=rs.randn(n).astype(np.float32), tgt=rs.randn(n).astype(np.float32), redrawn=0,
               outside=0.4)
-    got = M.run_minibatch(L, pol, val, dict(pr, mask=torch.from_numpy(m).cuda()), np.array([4, 0, 3, 1, 2]))
-    M.masked_gate(L, pol, val, dict(pr, mask=eff), got, f"{D} -> (64,) -> {A}, 5 rows")
+    rows, kw = M.rows_of(dict(pr, mask=torch.from_numpy(m).cuda()))
+    got = triple(run_pass(L, pol, val, *rows, np.array([4, 0, 3, 1, 2]), **kw))
+    PY.masked_gate(L, "discrete", pol, val, dict(pr, mask=eff), got, f"[masked fp64 gate] {D} -> (64,) -> {A}, 5 rows")
 
 
 # ------------------------------------------------------------------ 5. one act_padded: the eager call, its launcher, the graph

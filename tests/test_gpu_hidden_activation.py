@@ -1,10 +1,10 @@
 """The hidden-activation choice on the GPU (include/rlppo.h, "[act]"; Learner(hidden_activation=...), ppo.LayerSizes): the three new
 GEMM epilogues, one update pass, the rollout entry points, PPOLearner.learn and the Learner loop with tanh / ELU (alpha = 1) hidden
-layers, against the float64 yardstick of tests/activation_yardstick.py under the project's tolerance rule:
+layers, against the float64 yardstick of tests/ppo_yardstick.py under the project's tolerance rule:
 err(HIP, float64) <= max(1e-5, 1.5 x err(float32 yardstick, float64)).
 
 Inputs are built on the CPU and checked there, from float64 alone, before anything runs on the GPU (no ratio near a clip edge; the
-cap on ill-conditioned Adam steps).  With tanh / ELU no hidden decision is discrete (activation_yardstick's docstring), so there is
+cap on ill-conditioned Adam steps).  With tanh / ELU no hidden decision is discrete (ppo_yardstick's docstring), so there is
 no counterpart of the ReLU tests' assert_relu_clear."""
 import ctypes
 import functools
@@ -16,9 +16,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import nets  # noqa: E402
-import activation_yardstick as A  # noqa: E402
+import ppo_yardstick as A  # noqa: E402
 import diag_gaussian_env as E  # noqa: E402
-from test_gpu_kernels import L, Net, P, check, dev, stream  # noqa: E402,F401
+from diag_gaussian_yardstick import assert_clear_of_clip_edges, logp_terms  # noqa: E402
+from hip_pass import L, Net, P, check, dev, run_pass, stream  # noqa: E402,F401
 
 U32 = 2.0 ** -24
 CLIP, ENT = 0.2, 0.005
@@ -156,7 +157,7 @@ def make_case(head, seed, n=420, d=13, pol_hidden=(64, 128), val_hidden=(32, 64)
     c = dict(head=head, pol=pol, val=val, obs=obs, act=act, log_std=log_std, mask=mask, hk=hk, pol_act=pol_act, val_act=val_act or pol_act)
     z = torch.as_tensor(A.forward64(pol, obs, pol_act, out_tanh=head == "gaussian"))
     ls64 = None if log_std is None else torch.as_tensor(log_std, dtype=torch.float64)
-    logp = A.head_terms(head, z, torch.as_tensor(act, dtype=torch.float64), torch.float64, log_std=ls64, **hk)[0].numpy()
+    logp = A.head_terms(head, z, torch.as_tensor(act, dtype=torch.float64), log_std=ls64, **hk)[0].numpy()
     cls = np.arange(n) % 3
     off = 0.05 * rs.randn(n) + np.where(cls == 1, -0.5, 0.0) + np.where(cls == 2, 0.5, 0.0)
     c.update(old=(logp + off).astype(np.float32), adv=rs.randn(n).astype(np.float32), tgt=rs.randn(n).astype(np.float32), rs=rs)
@@ -166,16 +167,17 @@ def make_case(head, seed, n=420, d=13, pol_hidden=(64, 128), val_hidden=(32, 64)
 def yard(c, idx, mb_ratio):
     m = c["mask"]
     hk = dict(c["hk"], mask=m[idx]) if m is not None else c["hk"]
-    args = (c["head"], c["pol_act"], c["val_act"], c["pol"], c["val"], c["obs"][idx], c["act"][idx], c["old"][idx], c["adv"][idx], c["tgt"][idx],
-            CLIP, ENT, mb_ratio)
-    r64 = A.minibatch(torch.float64, *args, log_std=c["log_std"], **hk)
-    A.assert_clear_of_clip_edges(r64["ratio"], CLIP)
-    return r64, A.minibatch(torch.float32, *args, log_std=c["log_std"], **hk)
+    args = (c["head"], c["pol"], c["val"], c["obs"][idx], c["act"][idx], c["old"][idx], c["adv"][idx], c["tgt"][idx], CLIP, ENT, mb_ratio)
+    hk = dict(hk, pol_act=c["pol_act"], val_act=c["val_act"], log_std=c["log_std"])
+    r64 = A.minibatch(torch.float64, *args, **hk)
+    assert_clear_of_clip_edges(r64["ratio"], CLIP)
+    return r64, A.minibatch(torch.float32, *args, **hk)
 
 
-def hip(L, c, idx, mb_ratio, **kw):
-    return A.run_pass(L, c["head"], c["pol_act"], c["val_act"], c["pol"], c["val"], c["obs"], c["act"], c["old"], c["tgt"], c["adv"], idx, CLIP, ENT,
-                      mb_ratio, log_std=c["log_std"], bins=c["hk"].get("bins"), mask=c["mask"], **kw)
+def hip(L, c, idx, mb_ratio, entry="ex", precision="fp32", **kw):
+    return run_pass(L, c["pol"], c["val"], c["obs"], c["act"], c["old"], c["tgt"], c["adv"], idx, head=c["head"], entry=entry, precision=precision,
+                    pol_act=c["pol_act"], val_act=c["val_act"], clip=CLIP, ent=ENT, mb_ratio=mb_ratio, log_std=c["log_std"],
+                    bins=c["hk"].get("bins"), mask=c["mask"], raise_rc=False, **kw)
 
 
 def pass_idx(c, mb=300):
@@ -199,7 +201,7 @@ def test_pass_against_float64(L, shape, act):
     after = counters(L, 2, 3, 4)
     assert got["rc"] == 0, got["msg"]
     assert [b - a for a, b in zip(before, after)] == [1, 0, 0]
-    A.gate(got, r64, r32, f"{shape} {act}")
+    A.gate(got, r64, r32, f"[act fp64 gate] {shape} {act}")
     # the paired / gather-fused forms forced "always" (switches 29 = 2, 26 = 2) still do not apply to a tanh / ELU pass
     check(L, L.rlppo_dbg_set(29, 2))
     check(L, L.rlppo_dbg_set(26, 2))
@@ -221,7 +223,7 @@ def test_pass_mixed_activations_ring_empty_buffer_rows_and_accumulation(L):
     r64, r32 = yard(c, idx, 1.0)
     got = hip(L, c, idx, 1.0)
     assert got["rc"] == 0, got["msg"]
-    A.gate(got, r64, r32, "tanh policy, ELU critic")
+    A.gate(got, r64, r32, "[act fp64 gate] tanh policy, ELU critic")
     for kw in (dict(ring=137), dict(n_rows=0)):
         other = hip(L, c, idx, 1.0, **kw)
         assert other["rc"] == 0 and torch.equal(other["gp"], got["gp"]) and torch.equal(other["gv"], got["gv"]), kw
@@ -243,7 +245,7 @@ def test_pass_other_heads(L, head):
     assert got["rc"] == 0, got["msg"]
     if head == "nvec":
         assert counters(L, 6)[0] == c6 + 1   # the general (any nvec) loss kernel ran
-    A.gate(got, r64, r32, f"{head} elu")
+    A.gate(got, r64, r32, f"[act fp64 gate] {head} elu")
 
 
 def test_zero_extension_is_the_plain_entry_point(L):
@@ -333,7 +335,7 @@ def head_of_output(kind, pol, y, noise, bins=None, mask=None):
         return act, nets.gauss_logpdf(act, mean, std).sum(1), None
     ls = pol.log_std.detach().cpu().to(dt)
     act = y + torch.exp(ls) * q
-    return act, A.DY.logp_terms(act, y, ls).sum(-1), None
+    return act, logp_terms(act, y, ls).sum(-1), None
 
 
 def check_rollout(kind, pol, act_name, obs, noise, got_act, got_logp, label, bins=None, mask=None):

@@ -13,35 +13,7 @@ pytestmark = pytest.mark.gpu
 from oracle import gae as ogae  # noqa: E402
 from oracle import nets, ppo  # noqa: E402
 import fp64_gate  # noqa: E402  (tests/fp64_gate.py: the parity gate against float64 truth)
-
-
-@pytest.fixture(scope="module")
-def L():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from rlgym_ppo_amd import _native as N
-    return N.lib()
-
-
-def dev(x, dtype=torch.float32):
-    return torch.as_tensor(np.asarray(x)).to("cuda", dtype=dtype).contiguous()
-
-
-def P(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def relerr(a, b):
-    a = np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, np.float64)
-    b = np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, np.float64)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
-
-
-def check(L, rc):
-    assert rc == 0, L.rlppo_last_error()
+from hip_pass import L, Net, P, check, dev, relerr, run_minibatch, stream  # noqa: E402,F401
 
 
 # ------------------------------------------------------------------------------------------------ GEMMs
@@ -587,32 +559,6 @@ def test_gae_empty(L):
     check(L, L.rlppo_gae(stream(), None, None, None, None, 0, 0.99, 0.95, 1.0, None, None, None, None, 0))
 
 
-# -------------------------------------------------------------------------------------- network plumbing
-class Net:
-    def __init__(self, L, params):
-        from rlgym_ppo_amd import _native as N
-        self.L = L
-        self.params = params
-        self.dims = [params[0][0].shape[1]] + [w.shape[0] for w, _ in params]
-        self.nl = len(params)
-        self.dims_c = N.dims_array(self.dims)
-        self.flat = dev(nets.flatten(params))
-        self.packed = torch.zeros(int(L.rlppo_packed_floats(self.dims_c, self.nl)), device="cuda")
-        check(L, L.rlppo_net_pack(stream(), self.dims_c, self.nl, P(self.flat), P(self.packed)))
-        self.ld_in = int(L.rlppo_padded_width(self.dims[0]))
-        self.ld_out = int(L.rlppo_padded_out(self.dims[-1]))
-
-    def pad(self, obs, f64=False):
-        src = dev(obs, torch.float64 if f64 else torch.float32)
-        n, d = src.shape
-        out = torch.full((n, self.ld_in), float("nan"), device="cuda")
-        check(self.L, self.L.rlppo_pad_rows(stream(), P(src), int(f64), n, d, d, P(out), self.ld_in, 0, 0.0, 1.0))
-        return out
-
-    def ws(self, n):
-        return torch.empty(int(self.L.rlppo_forward_workspace_bytes(self.dims_c, self.nl, n)), dtype=torch.uint8, device="cuda")
-
-
 def test_g2_value_forward(L, golden):
     g = golden("g2_value_forward")
     net = Net(L, nets.params_from_state(g, "v."))
@@ -1095,82 +1041,6 @@ def test_g9_gaussian_and_multidiscrete_act(L, golden):
 
 
 # ---------------------------------------------------------------------------------------- PPO minibatch
-CANARY_BYTES = 4096
-
-
-def run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var=(0.1, 1.0),
-                  precision="fp32", ring=None, canary=False):
-    """ring = base: the experience arrays are handed over as a ring of capacity len(obs_all) -- stored rotated so that logical row i
-    lives at physical row (i + base) % cap, with ring_base / ring_cap set; idx stays logical.
-    canary: the workspace allocation carries CANARY_BYTES of a fixed pattern behind the bytes the pass is given, and the pass must
-    leave them as they were."""
-    from rlgym_ppo_amd import _native as N
-    if ring is not None and precision in ("fp32", "bf16", "x3"):
-        rot = lambda x: np.roll(np.asarray(x), ring, axis=0)
-        obs_all, acts_all, old_all, tgt_all, adv_all = (rot(x) for x in (obs_all, acts_all, old_all, tgt_all, adv_all))
-    if precision == "bf16":  # the bf16-operand forward (rlppo_set_update_precision): same call with the rounded weight images
-        check(L, L.rlppo_set_update_precision(1))
-        try:
-            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "bf16*", ring,
-                                 canary)
-        finally:
-            check(L, L.rlppo_set_update_precision(0))
-    if precision == "x3":  # [r4] the split-bf16 hidden products (rlppo_set_update_precision(2)): same call with the three-plane images
-        check(L, L.rlppo_set_update_precision(2))
-        try:
-            return run_minibatch(L, head, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, clip, ent, mb_ratio, var, "x3*", ring,
-                                 canary)
-        finally:
-            check(L, L.rlppo_set_update_precision(0))
-    P_, V_ = Net(L, pol), Net(L, val)
-    states = P_.pad(obs_all)
-    acts = dev(np.asarray(acts_all, np.float32).reshape(len(obs_all), -1))
-    a = N.MinibatchArgs()
-    a.head = {"discrete": 0, "multidiscrete": 1, "gaussian": 2}[head]
-    a.pol_layers, a.val_layers, a.act_dim = P_.nl, V_.nl, acts.shape[1]
-    a.pol_dims = ctypes.cast(P_.dims_c, ctypes.POINTER(ctypes.c_int32))
-    a.val_dims = ctypes.cast(V_.dims_c, ctypes.POINTER(ctypes.c_int32))
-    gp = torch.zeros_like(P_.flat)
-    gv = torch.zeros_like(V_.flat)
-    old, tgt, adv = dev(old_all), dev(tgt_all), dev(adv_all)
-    idxd = dev(idx, torch.int64)
-    stats = torch.zeros(8, dtype=torch.float64, device="cuda")
-    mb = len(idx)
-    ws_bytes = int(L.rlppo_minibatch_workspace_bytes(P_.dims_c, P_.nl, V_.dims_c, V_.nl, mb))
-    ws = torch.empty(ws_bytes + (CANARY_BYTES if canary else 0), dtype=torch.uint8, device="cuda")
-    tail = (torch.arange(CANARY_BYTES) * 37 % 251).to(torch.uint8)
-    if canary:
-        ws[ws_bytes:] = tail.cuda()
-    a.pol_packed, a.val_packed, a.pol_grad, a.val_grad = P_.packed.data_ptr(), V_.packed.data_ptr(), gp.data_ptr(), gv.data_ptr()
-    if precision == "bf16*":
-        imgs = []
-        for net in (P_, V_):
-            pr = torch.zeros_like(net.packed)
-            wb = torch.zeros(int(L.rlppo_wb16_elems(net.dims_c, net.nl)), dtype=torch.bfloat16, device="cuda")
-            check(L, L.rlppo_net_pack_bf16(stream(), net.dims_c, net.nl, P(net.flat), P(pr), P(wb)))
-            imgs += [pr, wb]
-        a.pol_packed_r, a.pol_wb16, a.val_packed_r, a.val_wb16 = (t.data_ptr() for t in imgs)
-    if precision == "x3*":
-        imgs = []
-        for net in (P_, V_):
-            pl = torch.zeros(max(int(L.rlppo_x3_elems(net.dims_c, net.nl)), 8), dtype=torch.bfloat16, device="cuda")
-            check(L, L.rlppo_net_pack_x3(stream(), net.dims_c, net.nl, P(net.packed), P(pl)))
-            imgs.append(pl)
-        a.pol_wb16, a.val_wb16 = (t.data_ptr() for t in imgs)
-    a.states, a.ld_states, a.n_rows, a.actions = states.data_ptr(), states.shape[1], states.shape[0], acts.data_ptr()
-    a.old_logp, a.targets, a.advantages, a.idx, a.mb = old.data_ptr(), tgt.data_ptr(), adv.data_ptr(), idxd.data_ptr(), mb
-    if ring is not None:
-        a.ring_base, a.ring_cap = ring, len(obs_all)
-    a.clip_range, a.ent_coef, a.mb_ratio = clip, ent, mb_ratio
-    a.var_m, a.var_b = nets.var_map(*var)
-    a.stats, a.workspace, a.ws_bytes = stats.data_ptr(), ws.data_ptr(), ws_bytes
-    check(L, L.rlppo_ppo_minibatch(stream(), ctypes.byref(a)))
-    torch.cuda.synchronize()
-    if canary:
-        assert torch.equal(ws[ws_bytes:].cpu(), tail), "the pass wrote behind the workspace it was given"
-    return nets.unflatten(gp.cpu(), pol), nets.unflatten(gv.cpu(), val), stats.cpu().numpy()
-
-
 def test_float64_truth_is_guarded_on_the_gpu_box_too(golden):
     """Every GPU gate leans on oracle/ppo.py::minibatch_analytic (float64, hand-derived gradients = the formulas of csrc/heads.hip).
     What breaks the common mode between it and the kernels is its check against the AUTOGRAD form of the same minibatch -- a CPU
@@ -1325,9 +1195,9 @@ def test_fused_gather_and_paired_launches_are_bitwise_neutral(L):
 
 
 def test_minibatch_stays_inside_its_workspace(L):
-    """The workspace size the library asks for (rlppo_minibatch_workspace_bytes) bounds what a pass writes: a fixed pattern behind
-    the bytes handed over survives one pass of every form -- fused gather + paired launches, separate gather + two chains,
-    split-bf16, bf16 -- for the discrete and the Gaussian head, and the gradients equal those of the same call without it."""
+    """The workspace size the library asks for (rlppo_minibatch_workspace_bytes) bounds what a pass writes: the guard band
+    hip_pass.run_pass keeps behind the bytes handed over survives one pass of every form -- fused gather + paired launches, separate
+    gather + two chains, split-bf16, bf16 -- for the discrete and the Gaussian head, and a second call gives the same gradients."""
     rs = np.random.RandomState(17)
     d, n, mb, k = 107, 5000, 1500, 8
     forms = dict(fused_paired=(2, 2, "fp32"), separate_two_chains=(0, 0, "fp32"), x3=(1, 1, "x3"), bf16=(1, 1, "bf16"))
@@ -1350,14 +1220,14 @@ def test_minibatch_stays_inside_its_workspace(L):
             check(L, L.rlppo_dbg_set(26, k26))
             check(L, L.rlppo_dbg_set(29, k29))
             try:
-                plain = run_minibatch(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.25, precision=precision)
-                fenced = run_minibatch(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.25, precision=precision, canary=True)
+                first = run_minibatch(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.25, precision=precision)
+                again = run_minibatch(L, head, pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.25, precision=precision)
             finally:
                 check(L, L.rlppo_dbg_set(26, 1))
                 check(L, L.rlppo_dbg_set(29, 1))
             if form == "fused_paired":
                 assert L.rlppo_dbg_counter(3) == paired + 2 and L.rlppo_dbg_counter(4) == fused + 2, head
-            for (a, b), (c, e) in zip(plain[0] + plain[1], fenced[0] + fenced[1]):
+            for (a, b), (c, e) in zip(first[0] + first[1], again[0] + again[1]):
                 assert torch.equal(a, c) and torch.equal(b, e), (head, form)
 
 

@@ -14,28 +14,11 @@ pytestmark = pytest.mark.gpu
 
 import diag_gaussian_env as E  # noqa: E402
 from rlgym_ppo_amd.ppo.lr_schedule import adapt_lr, linear_lr  # noqa: E402
+from hip_pass import L, P, check, stream  # noqa: E402,F401
 
 D_KL, LO, HI = 0.01, 1e-5, 1e-2
 OBS, HID, ROWS, B, MB, EPOCHS = 24, (64, 64), 1024, 1024, 256, 6
 HEADS = {"discrete": (0, 6), "diag": (3, 3)}
-
-
-@pytest.fixture(scope="module")
-def L():
-    from rlgym_ppo_amd import _native as N
-    return N.lib()
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def P(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def check(L, rc):
-    assert rc == 0, L.rlppo_last_error()
 
 
 def f64(values):

@@ -13,27 +13,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from hip_pass import L, P, check, stream  # noqa: E402,F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = (1, 5, 16, 17, 80, 256)
-
-
-@pytest.fixture(scope="module")
-def L():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from rlgym_ppo_amd import _native as N
-    return N.lib()
-
-
-def P(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def check(L, rc):
-    assert rc == 0, L.rlppo_last_error()
 
 
 def policy(d, A, hidden, seed):

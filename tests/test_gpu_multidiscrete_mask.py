@@ -13,7 +13,8 @@ import fp64_gate  # noqa: E402
 import masked_multidiscrete_yardstick as M  # noqa: E402
 import multidiscrete_env as E  # noqa: E402
 import multidiscrete_nvec_yardstick as Y  # noqa: E402
-from test_gpu_kernels import L, Net, check  # noqa: E402,F401
+import ppo_yardstick as PY  # noqa: E402
+from hip_pass import L, Net, check, run_pass, triple  # noqa: E402,F401
 
 BINS = (2, 7, 3, 11, 2)
 
@@ -38,7 +39,8 @@ def test_all_valid_mask_is_the_unmasked_general_kernels_bit_for_bit(L, bins):
     out = []
     for mask in (None, np.ones((5000, S), bool)):
         c6 = L.rlppo_dbg_counter(6)
-        out.append(M.run_minibatch(L, bins, pol, val, pr, idx, 0.5, mask=mask))
+        rows, kw = M.pass_args(pr, bins, mask=mask)
+        out.append(triple(run_pass(L, pol, val, *rows, idx, mb_ratio=0.5, **kw)))
         assert L.rlppo_dbg_counter(6) == c6 + 1
     (gp0, gv0, st0, dz0), (gp1, gv1, st1, dz1) = out
     for (x, y), (u, v) in zip(gp0 + gv0, gp1 + gv1):
@@ -114,7 +116,7 @@ UPDATE_CASES = {
 
 @pytest.mark.parametrize("name", list(UPDATE_CASES))
 def test_masked_minibatch_nvec_against_float64(L, monkeypatch, name):
-    """The masked pass through M.masked_gate: err(HIP, fp64 under the HIP's ReLU decisions) <= max(1e-5, 1.5 x err(float32 torch
+    """The masked pass through ppo_yardstick.masked_gate: err(HIP, fp64 under the HIP's ReLU decisions) <= max(1e-5, 1.5 x err(float32 torch
     restatement, fp64 under its own)), statistics likewise; dz exactly 0 on invalid logits and on columns >= S, finite everywhere."""
     bins, n, mb, saturate = UPDATE_CASES[name]
     S = sum(bins)
@@ -130,7 +132,8 @@ def test_masked_minibatch_nvec_against_float64(L, monkeypatch, name):
     assert (ratio < 0.8).sum() > 10 and (ratio > 1.2).sum() > 10                        # both clip edges are crossed ...
     assert np.minimum(np.abs(ratio - 0.8), np.abs(ratio - 1.2)).min() >= 5e-4           # ... and no row sits on one
     c6 = L.rlppo_dbg_counter(6)
-    gp, gv, st, dz = M.run_minibatch(L, bins, pol, val, pr, idx, 0.5)
+    rows, kw = M.pass_args(pr, bins)
+    gp, gv, st, dz = triple(run_pass(L, pol, val, *rows, idx, mb_ratio=0.5, **kw))
     assert L.rlppo_dbg_counter(6) == c6 + 1
     Y.check_output_gradient(dz, gp, S)
     m = pr["mask"][idx]
@@ -140,7 +143,8 @@ def test_masked_minibatch_nvec_against_float64(L, monkeypatch, name):
     one = M.head_valid(m, bins).sum(-1) == 1   # heads with exactly one valid bin: zero gradient on it too
     for h, (s, b) in enumerate(zip(M.starts(bins), bins)):
         assert (dz[one[:, h], s:s + b] == 0).all(), h
-    M.masked_gate(L, monkeypatch, bins, pol, val, M.rows(pr, idx), (gp, gv, st), f"masked multi-discrete {name}, {mb} rows", 0.5)
+    Y.patch_oracle(monkeypatch, bins)
+    PY.masked_gate(L, "nvec", pol, val, M.rows(pr, idx), (gp, gv, st), f"[masked nvec fp64 gate] masked multi-discrete {name}, {mb} rows", 0.5, bins)
     # stored actions their own masks mark invalid, on every ninth row (a caller error): everything stays finite
     bad = dict(pr)
     bad["mask"] = pr["mask"].copy()
@@ -150,7 +154,8 @@ def test_masked_minibatch_nvec_against_float64(L, monkeypatch, name):
             a = pr["acts"][r, h].astype(int)
             bad["mask"][r, s + a] = False
             bad["mask"][r, s + (a + 1) % b] = True
-    gp, gv, st, dz = M.run_minibatch(L, bins, pol, val, bad, np.arange(n), 1.0)
+    rows, kw = M.pass_args(bad, bins)
+    gp, gv, st, dz = triple(run_pass(L, pol, val, *rows, np.arange(n), mb_ratio=1.0, **kw))
     assert finite(gp) and finite(gv) and np.isfinite(st).all() and np.isfinite(dz).all() and (dz[:, :S][~bad["mask"]] == 0).all()
 
 
@@ -191,8 +196,10 @@ def test_column_constant_mask_is_the_narrower_policy(L, monkeypatch):
     tgt, adv = rs.randn(n).astype(np.float32), rs.randn(n).astype(np.float32)
     idx = rs.permutation(n)[:1500]
     pr = dict(obs=obs, acts=a_full, old=old, tgt=tgt, adv=adv, mask=mask)
-    gp, gv, st, dz = M.run_minibatch(L, bins, pol, val, pr, idx, 0.5)
-    gpr, gvr, str_, dzr = Y.run_minibatch_nvec(L, REDUCED, narrow, val, obs, a_r.astype(np.float32), old, tgt, adv, idx, 0.2, 0.005, 0.5)
+    rows, kw = M.pass_args(pr, bins)
+    gp, gv, st, dz = triple(run_pass(L, pol, val, *rows, idx, mb_ratio=0.5, **kw))
+    gpr, gvr, str_, dzr = triple(run_pass(L, narrow, val, obs, a_r.astype(np.float32), old, tgt, adv, idx, head="nvec", entry="nvec",
+                                          bins=REDUCED, clip=0.2, ent=0.005, mb_ratio=0.5, dz=True))
     assert np.array_equal(dz[:, cols], dzr[:, :len(cols)]) and (dz[:, gone] == 0).all() and (dz[:, S:] == 0).all()
     hw, hb = gp[-1]
     assert bool((hw[gone] == 0).all()) and bool((hb[gone] == 0).all())
@@ -251,10 +258,12 @@ def test_masked_launch_forms_and_ring(L, monkeypatch):
             check(L, L.rlppo_dbg_set(knob, v))
         try:
             c3 = L.rlppo_dbg_counter(3)
-            runs[key] = M.run_minibatch(L, bins, pol, val, pr, idx, 0.25)
+            rows, kw = M.pass_args(pr, bins)
+            runs[key] = triple(run_pass(L, pol, val, *rows, idx, mb_ratio=0.25, **kw))
             paired[key] = L.rlppo_dbg_counter(3) - c3
             if key == "fused":
-                runs["ring"] = M.run_minibatch(L, bins, pol, val, pr, idx, 0.25, ring=base)
+                rows, kw = M.pass_args(pr, bins)
+                runs["ring"] = triple(run_pass(L, pol, val, *rows, idx, mb_ratio=0.25, ring=base, **kw))
         finally:
             for knob in (26, 29, 32, 33):
                 check(L, L.rlppo_dbg_set(knob, 1))
@@ -265,9 +274,12 @@ def test_masked_launch_forms_and_ring(L, monkeypatch):
             assert torch.equal(x, u) and torch.equal(y, v), key
         np.testing.assert_allclose(st0, st, rtol=1e-12, atol=0, err_msg=key)
     # (a pass that read another row's mask words would not be this one: the unmasked pass differs)
-    plain = M.run_minibatch(L, bins, pol, val, pr, idx, 0.25, mask=None)
+    rows, kw = M.pass_args(pr, bins, mask=None)
+    plain = triple(run_pass(L, pol, val, *rows, idx, mb_ratio=0.25, **kw))
     assert not torch.equal(plain[0][-1][0], gp0[-1][0])
-    M.masked_gate(L, monkeypatch, bins, pol, val, M.rows(pr, idx), runs["fused"][:3], "masked multi-discrete, launch forms, 1500 rows", 0.25)
+    Y.patch_oracle(monkeypatch, bins)
+    PY.masked_gate(L, "nvec", pol, val, M.rows(pr, idx), runs["fused"][:3], "[masked nvec fp64 gate] masked multi-discrete, launch forms, 1500 rows", 0.25,
+                   bins)
 
 
 # ------------------------------------------------------------------------------------------------ 6. policy class, learner loop

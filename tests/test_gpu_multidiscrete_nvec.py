@@ -10,11 +10,12 @@ pytestmark = pytest.mark.gpu
 from oracle import nets  # noqa: E402
 import fp64_gate  # noqa: E402
 import multidiscrete_nvec_yardstick as Y  # noqa: E402
-from test_gpu_kernels import L, Net, P, check, dev, stream  # noqa: E402,F401
+from hip_pass import L, Net, P, check, dev, run_pass, stream, triple  # noqa: E402,F401
 
 # ------------------------------------------------------------------------------------------------ 1. sampling
 # (bins, rows, observation width, hidden layers, seed).  The seeds were picked on the CPU, from the float64 reference alone, so that
 # the inputs hold at most 2 near-ties (check_sampled asserts that first).
+NVEC = dict(head="nvec", entry="nvec", dz=True)   # hip_pass.run_pass: rlppo_ppo_minibatch_nvec, the output gradient returned
 SAMPLING_CASES = {
     "one_head_of_5": ((5,), 601, 20, (64, 64), 1),
     "one_bin_head": ((1, 4), 577, 33, (64, 64), 1),
@@ -95,7 +96,7 @@ def update_case(bins, seed, n, d=107, hidden=(128, 128), noise=0.2, saturate=Fal
     return pol, val, obs, act.astype(np.float32), old, tgt, adv, rs, logp
 
 
-def gate(L, pol, val, obs, acts, old, tgt, adv, idx, mb_ratio, got, label):
+def gate_rows(L, pol, val, obs, acts, old, tgt, adv, idx, mb_ratio, got, label):
     return fp64_gate.gate(L, "multidiscrete", pol, val, obs[idx], acts[idx], old[idx], adv[idx], tgt[idx], 0.2, 0.005, mb_ratio, got,
                           label=label)
 
@@ -128,13 +129,13 @@ def test_minibatch_nvec_against_float64(L, monkeypatch, name):
     ratio = np.exp(logp[idx] - old[idx])
     assert (ratio < 0.8).sum() > 10 and (ratio > 1.2).sum() > 10
     c6 = L.rlppo_dbg_counter(6)
-    gp, gv, st, dz = Y.run_minibatch_nvec(L, bins, pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.5)
+    gp, gv, st, dz = triple(run_pass(L, pol, val, obs, acts, old, tgt, adv, idx, bins=bins, clip=0.2, ent=0.005, mb_ratio=0.5, **NVEC))
     assert L.rlppo_dbg_counter(6) == c6 + 1
     Y.check_output_gradient(dz, gp, sum(bins))
     if 1 in bins:   # a head of one bin: zero gradient in its column
         s = int(np.cumsum((0,) + tuple(bins))[bins.index(1)])
         assert (dz[:, s] == 0).all()
-    gate(L, pol, val, obs, acts, old, tgt, adv, idx, 0.5, (gp, gv, st), f"multi-discrete nvec {name}, {mb} rows")
+    gate_rows(L, pol, val, obs, acts, old, tgt, adv, idx, 0.5, (gp, gv, st), f"multi-discrete nvec {name}, {mb} rows")
 
 
 def test_general_kernel_on_the_reference_bins(L, golden, monkeypatch):
@@ -145,11 +146,12 @@ def test_general_kernel_on_the_reference_bins(L, golden, monkeypatch):
     pol, val = nets.params_from_state(g, "p."), nets.params_from_state(g, "v.")
     n = g["obs"].shape[0]
     acts, idx = g["act"].astype(np.float32), np.arange(n)
-    args = (pol, val, g["obs"], acts, g["old_logp"], g["targets"], g["adv"], idx, 0.2, 0.005, 0.5)
+    args = (L, pol, val, g["obs"], acts, g["old_logp"], g["targets"], g["adv"], idx)
+    kw = dict(NVEC, bins=Y.REFERENCE_BINS, clip=0.2, ent=0.005, mb_ratio=0.5)
     c6 = L.rlppo_dbg_counter(6)
-    fixed = Y.run_minibatch_nvec(L, Y.REFERENCE_BINS, *args, general=False)
+    fixed = triple(run_pass(*args, general=False, **kw))
     assert L.rlppo_dbg_counter(6) == c6
-    general = Y.run_minibatch_nvec(L, Y.REFERENCE_BINS, *args)
+    general = triple(run_pass(*args, **kw))
     assert L.rlppo_dbg_counter(6) == c6 + 1
     Y.check_output_gradient(general[3], general[0], 21)
     fp64_gate.gate(L, "multidiscrete", pol, val, g["obs"], acts, g["old_logp"], g["adv"], g["targets"], 0.2, 0.005, 0.5, general[:3],
@@ -187,10 +189,10 @@ def test_launch_forms_and_ring_for_nvec(L, monkeypatch):
             check(L, L.rlppo_dbg_set(knob, v))
         try:
             c3 = L.rlppo_dbg_counter(3)
-            runs[key] = Y.run_minibatch_nvec(L, bins, pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.25)
+            runs[key] = triple(run_pass(L, pol, val, obs, acts, old, tgt, adv, idx, bins=bins, clip=0.2, ent=0.005, mb_ratio=0.25, **NVEC))
             paired[key] = L.rlppo_dbg_counter(3) - c3
             if key == "fused":
-                runs["ring"] = Y.run_minibatch_nvec(L, bins, pol, val, obs, acts, old, tgt, adv, idx, 0.2, 0.005, 0.25, ring=base)
+                runs["ring"] = triple(run_pass(L, pol, val, obs, acts, old, tgt, adv, idx, bins=bins, clip=0.2, ent=0.005, mb_ratio=0.25, ring=base, **NVEC))
         finally:
             for knob in (26, 29, 32, 33):
                 check(L, L.rlppo_dbg_set(knob, 1))
@@ -201,4 +203,4 @@ def test_launch_forms_and_ring_for_nvec(L, monkeypatch):
             assert torch.equal(x, u) and torch.equal(y, v), key
         np.testing.assert_allclose(st0, st, rtol=1e-12, atol=0, err_msg=key)
     Y.patch_oracle(monkeypatch, bins)
-    gate(L, pol, val, obs, acts, old, tgt, adv, idx, 0.25, runs["fused"][:3], "multi-discrete nvec, launch forms, ragged 1500 rows")
+    gate_rows(L, pol, val, obs, acts, old, tgt, adv, idx, 0.25, runs["fused"][:3], "multi-discrete nvec, launch forms, ragged 1500 rows")

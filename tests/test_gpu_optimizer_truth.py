@@ -15,31 +15,9 @@ pytestmark = pytest.mark.gpu
 
 from oracle import nets  # noqa: E402
 import optim_yardstick as Y  # noqa: E402
+from hip_pass import L, P, check, dev, run_pass, stream  # noqa: E402,F401
 
 KEYS = ("g", "m", "v", "p")
-
-
-@pytest.fixture(scope="module")
-def L():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from rlgym_ppo_amd import _native as N
-    return N.lib()
-
-
-def dev(x, dtype=torch.float32):
-    return torch.as_tensor(np.asarray(x)).to("cuda", dtype=dtype).contiguous()
-
-
-def P(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def check(L, rc):
-    assert rc == 0, L.rlppo_last_error()
 
 
 def bits(x):
@@ -440,8 +418,6 @@ def test_kl_gate_decisions_are_strict(L, lr_entry):
 def armed_pass(L, head, mb, mb_ratio, seed, stop=None):
     """One rlppo_ppo_minibatch pass over mb rows (obs 20 -> (32,) -> 7 actions) with kl_slots armed and NaN-filled.
     -> (slots region, stats)."""
-    from rlgym_ppo_amd import _native as N
-    from test_gpu_kernels import Net
     torch.manual_seed(seed)
     rs = np.random.RandomState(seed)
     k = 7
@@ -452,34 +428,9 @@ def armed_pass(L, head, mb, mb_ratio, seed, stop=None):
         logp = nets.backprop(head, pol, torch.as_tensor(obs), torch.as_tensor(acts))[0].reshape(-1).numpy()
     old = (logp + 0.1 * rs.randn(mb)).astype(np.float32)
     adv, tgt = rs.randn(mb).astype(np.float32), rs.randn(mb).astype(np.float32)
-    P_, V_ = Net(L, pol), Net(L, val)
-    states, d_acts = P_.pad(obs), dev(acts.reshape(mb, -1))
-    a = N.MinibatchArgs()
-    a.head = N.HEAD_DISCRETE if head == "discrete" else N.HEAD_GAUSSIAN
-    a.pol_layers, a.val_layers, a.act_dim = P_.nl, V_.nl, d_acts.shape[1]
-    a.pol_dims = ctypes.cast(P_.dims_c, ctypes.POINTER(ctypes.c_int32))
-    a.val_dims = ctypes.cast(V_.dims_c, ctypes.POINTER(ctypes.c_int32))
-    gp, gv = torch.zeros_like(P_.flat), torch.zeros_like(V_.flat)
-    d_old, d_tgt, d_adv, d_idx = dev(old), dev(tgt), dev(adv), dev(np.arange(mb), torch.int64)
-    stats = torch.zeros(8, dtype=torch.float64, device="cuda")
-    ws_bytes = int(L.rlppo_minibatch_workspace_bytes(P_.dims_c, P_.nl, V_.dims_c, V_.nl, mb))
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device="cuda")
-    n_slots = int(L.rlppo_kl_slots_doubles(mb))
-    slots = torch.full((n_slots,), float("nan"), dtype=torch.float64, device="cuda")
-    a.pol_packed, a.val_packed, a.pol_grad, a.val_grad = P_.packed.data_ptr(), V_.packed.data_ptr(), gp.data_ptr(), gv.data_ptr()
-    a.states, a.ld_states, a.n_rows, a.actions = states.data_ptr(), states.shape[1], mb, d_acts.data_ptr()
-    a.old_logp, a.targets, a.advantages, a.idx, a.mb = d_old.data_ptr(), d_tgt.data_ptr(), d_adv.data_ptr(), d_idx.data_ptr(), mb
-    a.clip_range, a.ent_coef, a.mb_ratio = 0.2, 0.005, mb_ratio
-    a.var_m, a.var_b = nets.var_map(0.1, 1.0)
-    a.stats, a.workspace, a.ws_bytes = stats.data_ptr(), ws.data_ptr(), ws_bytes
-    a.kl_slots = slots.data_ptr()
-    if stop is not None:
-        stop_word = torch.tensor([stop], dtype=torch.int32, device="cuda")
-        a.stop_word = stop_word.data_ptr()
-    check(L, L.rlppo_ppo_minibatch(stream(), ctypes.byref(a)))
-    torch.cuda.synchronize()
+    r = run_pass(L, pol, val, obs, acts, old, tgt, adv, np.arange(mb), head=head, mb_ratio=mb_ratio, kl_slots=True, stop=stop)
     lr = logp.astype(np.float64) - old.astype(np.float64)
-    return slots.cpu().numpy(), stats.cpu().numpy(), float(np.mean(np.expm1(lr) - lr))
+    return r["kl"], r["stats"], float(np.mean(np.expm1(lr) - lr))
 
 
 @pytest.mark.parametrize("mb", [1, 255, 256, 257, 1000, 70001])

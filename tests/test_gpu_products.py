@@ -12,7 +12,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import gemm_yardstick as Y  # noqa: E402
-from test_gpu_kernels import L, P, b16_tiles, check, dev, stream  # noqa: E402,F401
+from hip_pass import L, P, check, dev, stream  # noqa: E402,F401
+from test_gpu_kernels import b16_tiles  # noqa: E402,F401
 
 G = Y.Guarded
 

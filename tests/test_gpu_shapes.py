@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import nets, ppo  # noqa: E402
 import fp64_gate  # noqa: E402
-from test_gpu_kernels import L, Net, P, check, dev, relerr, run_minibatch, stream  # noqa: E402,F401
+from hip_pass import L, Net, P, check, dev, relerr, run_minibatch, stream  # noqa: E402,F401
 
 
 @pytest.mark.parametrize("d,hidden,A,n,mb", [(50, (100, 40), 300, 700, 333), (7, (33,), 5, 64, 64), (300, (130, 257, 64), 1500, 400, 129),

@@ -12,34 +12,13 @@ pytestmark = pytest.mark.gpu
 
 import fp64_gate  # noqa: E402
 import gae_bootstrap_yardstick as GY  # noqa: E402
+import hip_pass as HP  # noqa: E402
 import value_norm_yardstick as VY  # noqa: E402
+from hip_pass import L, P, check, dev, stream  # noqa: E402,F401
 from oracle import nets  # noqa: E402
 
 GAMMA, LMBDA = 0.99, 0.95
 CHUNK = 2048
-
-
-@pytest.fixture(scope="module")
-def L():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from rlgym_ppo_amd import _native as N
-    return N.lib()
-
-
-def dev(x, dtype=torch.float32):
-    return torch.as_tensor(np.asarray(x)).to("cuda", dtype=dtype).contiguous()
-
-
-def P(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def check(L, rc):
-    assert rc == 0, L.rlppo_last_error()
 
 
 def ulp32(x):
@@ -302,59 +281,11 @@ def make_rows(n, seed, obs=OBS, cobs=None):
 
 
 def run_pass(L, pol, val, rows, idx, entry, scale=None, vclip=0.0, act="relu", tgt=None, adv=None):
-    """One pass over rows[idx].  entry: "plain" rlppo_ppo_minibatch | "ex" rlppo_ppo_minibatch_ex | "critic" rlppo_ppo_minibatch_critic
-    (with rows["cobs"] when present) | "vnorm" rlppo_ppo_minibatch_vnorm with the four floats `scale` (None: vnorm == NULL).
-    -> (pol_grad, val_grad, stats) on the host."""
-    from critic_obs_yardstick import ACT_CODE, pad_rows
-    from rlgym_ppo_amd import _native as N
-    from test_gpu_kernels import Net
-    P_, V_ = Net(L, pol), Net(L, val)
-    states = pad_rows(rows["obs"], P_.ld_in)
-    acts, old = dev(rows["acts"].reshape(-1, 1)), dev(rows["old"])
-    tgt_d, adv_d = dev(rows["tgt"] if tgt is None else tgt), dev(rows["adv"] if adv is None else adv)
-    idxd = dev(idx, torch.int64)
-    mb = len(idx)
-    a = N.MinibatchArgs()
-    a.head, a.pol_layers, a.val_layers, a.act_dim, a.precision = N.HEAD_DISCRETE, P_.nl, V_.nl, 1, N.PRECISION_FP32
-    a.pol_dims = ctypes.cast(P_.dims_c, ctypes.POINTER(ctypes.c_int32))
-    a.val_dims = ctypes.cast(V_.dims_c, ctypes.POINTER(ctypes.c_int32))
-    gp, gv = torch.zeros_like(P_.flat), torch.zeros_like(V_.flat)
-    stats = torch.zeros(8, dtype=torch.float64, device="cuda")
-    with_rows = "cobs" in rows and entry in ("critic", "vnorm")
-    ws_fn = L.rlppo_minibatch_workspace_bytes_critic if with_rows else L.rlppo_minibatch_workspace_bytes_for
-    ws_bytes = int(ws_fn(P_.dims_c, P_.nl, V_.dims_c, V_.nl, mb, a.precision))
-    guard = 1024
-    ws = torch.full(((ws_bytes + 3) // 4 + guard,), -1, dtype=torch.int32, device="cuda")
-    a.pol_packed, a.val_packed, a.pol_grad, a.val_grad = P_.packed.data_ptr(), V_.packed.data_ptr(), gp.data_ptr(), gv.data_ptr()
-    a.states, a.ld_states, a.n_rows, a.actions = states.data_ptr(), states.shape[1], states.shape[0], acts.data_ptr()
-    a.old_logp, a.targets, a.advantages, a.idx, a.mb = old.data_ptr(), tgt_d.data_ptr(), adv_d.data_ptr(), idxd.data_ptr(), mb
-    a.clip_range, a.ent_coef, a.mb_ratio, a.var_m, a.var_b, a.value_clip = 0.2, 0.005, 1.0, 1.0, 0.0, float(vclip)
-    a.stats, a.workspace, a.ws_bytes = stats.data_ptr(), ws.data_ptr(), ws_bytes
-    ext = N.MinibatchExt()
-    ext.pol_hidden_act = ext.val_hidden_act = ACT_CODE[act]
-    cr, cstates = N.CriticRows(), None
-    if with_rows:
-        cstates = pad_rows(rows["cobs"], V_.ld_in)
-        cr.states, cr.ld_states = cstates.data_ptr(), cstates.shape[1]
-    crp = ctypes.byref(cr) if with_rows else None
-    vn, sc = N.ValueNormArg(), None
-    if scale is not None:
-        sc = dev(scale)
-        vn.scale = sc.data_ptr()
-    if entry == "plain":
-        assert act == "relu"
-        rc = L.rlppo_ppo_minibatch(stream(), ctypes.byref(a))
-    elif entry == "ex":
-        rc = L.rlppo_ppo_minibatch_ex(stream(), ctypes.byref(a), ctypes.byref(ext))
-    elif entry == "critic":
-        rc = L.rlppo_ppo_minibatch_critic(stream(), ctypes.byref(a), ctypes.byref(ext), crp)
-    else:
-        rc = L.rlppo_ppo_minibatch_vnorm(stream(), ctypes.byref(a), ctypes.byref(ext), crp, None if scale is None else ctypes.byref(vn))
-    check(L, rc)
-    check(L, L.rlppo_ppo_join(stream()))
-    torch.cuda.synchronize()
-    assert (ws[(ws_bytes + 3) // 4:] == -1).all(), "the pass wrote behind its workspace"
-    return gp.cpu(), gv.cpu(), stats.cpu().numpy()
+    """hip_pass.run_pass over rows[idx] (the critic on rows["cobs"] when present) -> (pol_grad, val_grad, stats) on the host."""
+    r = HP.run_pass(L, pol, val, rows["obs"], rows["acts"], rows["old"], rows["tgt"] if tgt is None else tgt, rows["adv"] if adv is None else adv,
+                    idx, head="discrete", entry=entry, precision="fp32", pol_act=act, val_act=act, cobs=rows.get("cobs"), scale=scale,
+                    value_clip=vclip, join=True)
+    return r["gp"].cpu(), r["gv"].cpu(), r["stats"]
 
 
 def same_pass(a, b, what, policy=True):

@@ -10,6 +10,7 @@ import torch
 from oracle import nets
 import masked_multidiscrete_yardstick as M
 import multidiscrete_nvec_yardstick as Y
+import ppo_yardstick as PY
 
 BINS = (2, 7, 3, 11, 2)
 
@@ -143,7 +144,7 @@ def test_masked_chain_with_an_all_valid_mask_is_the_oracles_multidiscrete_miniba
     logp = M.masked_logp64(Y.logits64(pol, pr["obs"]), bins, pr["acts"], ones)
     old = (logp - 0.2 * rs.randn(200)).astype(np.float32)
     want = ppo.minibatch_analytic("multidiscrete", pol, val, pr["obs"], pr["acts"], old, pr["adv"], pr["tgt"], 0.2, 0.005, 0.5, (0.1, 1.0))
-    gp, gv, stats, _ = M.masked_chain(pol, val, pr["obs"], pr["acts"], old, pr["adv"], pr["tgt"], ones, bins, 0.5, torch.float64)
+    gp, gv, stats, _ = PY.masked_chain("nvec", pol, val, pr["obs"], pr["acts"], old, pr["adv"], pr["tgt"], ones, 0.5, torch.float64, bins=bins)
     import fp64_gate
     assert fp64_gate.grads_err(gp + gv, want["grad_policy"] + want["grad_value"]) < 1e-9
     for k, name in ((0, "entropy"), (1, "kl"), (2, "value_loss"), (4, "policy_loss")):
