@@ -910,7 +910,7 @@ int rlppo_welford_merge(void *stream, int32_t d, void *mean, void *m2, int64_t c
 
 /* ------------------------------------------------------------------- device-resident vector environments (csrc/rollout.hip)
  * The bookkeeping between two steps of an environment that lives on the GPU (batched_agents/vector_agent_manager.py,
- * _collect_device).  The three entry points below make LAUNCHES ONLY: none of them contains a stream synchronisation, a blocking
+ * the _DeviceEnv side of the collect loop).  The three entry points below make LAUNCHES ONLY: none of them contains a stream synchronisation, a blocking
  * copy or an allocation, so a host that enqueues a whole collect through them never waits for the device. */
 #define RLPPO_DT_F32 0
 #define RLPPO_DT_F64 1

@@ -1,5 +1,5 @@
 // rollout.hip -- the per-step bookkeeping of a DEVICE-RESIDENT vector environment (batched_agents/vector_agent_manager.py,
-// _collect_device): what _collect_fused keeps in numpy between two environment steps -- rewards / flags of the step, episode sums,
+// _DeviceEnv): what the host side (_HostEnv) keeps in numpy between two environment steps -- rewards / flags of the step, episode sums,
 // the 0.9 / 0.1 episode-reward average, the standardisation scalars -- kept on the device, so that a collect never waits for it.
 // Launches only: nothing in this file synchronises a stream, copies with the host or allocates.
 #include "common.hpp"

@@ -1,4 +1,4 @@
-"""Device-resident vector environments (VectorAgentManager._collect_device, csrc/rollout.hip): the three kernels through the C ABI
+"""Device-resident vector environments (the _DeviceEnv side of VectorAgentManager's collect loop, csrc/rollout.hip): the three kernels through the C ABI
 against numpy / torch restatements, bit for bit; a collect through the device interface against the same interaction through the
 host interface, bit for bit; no host wait inside a collect; the Learner end to end on both interfaces."""
 import contextlib
@@ -44,7 +44,7 @@ def bits(x):
 
 # ------------------------------------------------------------------------------------------------ 1. the record kernel
 def record_restated(r, d, tr, t, T, ep, avg, ended):
-    """One step as _collect_fused keeps it on the host: float32 planes, double episode sums, the average over the ended agents in
+    """One step as the host side (_HostEnv) keeps it: float32 planes, double episode sums, the average over the ended agents in
     agent order as Python floats (two multiplications and one addition per episode, each rounded)."""
     r32 = np.asarray(r).astype(np.float32)
     dn, trn = np.asarray(d) != 0, np.asarray(tr) != 0

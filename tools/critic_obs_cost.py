@@ -7,7 +7,7 @@ alternating, at the flagship shape (obs 107, 256 x 3, 90 discrete actions):
       critic_214           rlppo_ppo_minibatch_critic, a critic of input width 214 on its own matrix
     with the pass-form counters (passes / paired / gather-fused / separate critic rows) each variant moved;
   * one 4096-agent x 128-step collect of tests/device_vector_env.py::IntegerEnv with and without critic_observations() of width 214,
-    through the host interface (_collect_fused) and the device interface (_collect_device).
+    through the host interface and the device interface (the _HostEnv / _DeviceEnv sides of VectorAgentManager's collect loop).
 No target is fixed in advance: medians and spread ((max - min) / median) over the rounds are recorded, stamped with rlppo_build_id().
 --bench NAME=FILE ... : `bench.py --gpus 1 --steps 20 --warmup 5` result lines (this commit, its parent) to record beside them.
 usage: python tools/critic_obs_cost.py [--rounds R] [--out FILE.json] [--bench NAME=FILE ...]"""

@@ -1,10 +1,10 @@
 """What the device interface of VectorAgentManager costs and saves, on ONE build, alternating rounds:
   * a collect of tests/device_vector_env.py::IntegerEnv at 4096 agents x 128 steps (256 x 3 networks, 90 actions, device-drawn
-    noise) through the device interface (torch backend, _collect_device) and through the host interface (numpy backend,
-    _collect_fused): collect time, steps/s, and the host time per step (device interface: the host's enqueue time before its one
+    noise) through the device interface (torch backend: the _DeviceEnv side of VectorAgentManager's collect loop) and through the host
+    interface (numpy backend: the _HostEnv side), both with the one-launch DiscreteFF.step: collect time, steps/s, and the host time per step (device interface: the host's enqueue time before its one
     read, over the steps; host interface: the collect time over the steps -- its host waits for every step);
   * rlppo_rollout_record alone at 4096 agents, nobody ending and everybody ending (HIP events);
-  * the end-of-collect transposition: rlppo_rollout_to_trajectory_major against the torch copies of _collect_fused it replaces;
+  * the end-of-collect transposition: rlppo_rollout_to_trajectory_major against the torch copies the host side made before it;
   * the extra dense value pass of gae_bootstrap_truncated (all N next-state rows) against the 4096 rows of the flush;
   * (--parent DIR: a built checkout of the parent commit) the bench.py headline of this tree against the parent's and a byte
     comparison of `bench.py --dump-outputs` (tools/gae_bootstrap_cost.py::bench_leg).
@@ -101,7 +101,7 @@ def transpose_leg(rounds):
         N.check(L.rlppo_rollout_to_trajectory_major(ST(), P(S), P(acts), P(logp), P(rdt), NA, T, ld, 1, P(None), P(None), P(flat), P(nxt), P(a_o),
                                                     P(small[0]), P(small[1]), P(small[2]), P(small[3])))
 
-    def copies():   # the end of _collect_fused, with the flags already on the device
+    def copies():   # the host side's former end of a collect, with the flags already on the device
         flat[:N_].view(NA, T, ld).copy_(S[:T].transpose(0, 1))
         nxt.view(NA, T, ld).copy_(S[1:].transpose(0, 1))
         flat[N_].copy_(S[T][NA - 1])
