@@ -233,6 +233,10 @@ __host__ __device__ __forceinline__ int64_t ring_row(int64_t i, int64_t base, in
     const int64_t r = i + base;
     return r >= cap ? r - cap : r;
 }
+#ifdef __HIP__
+// the bf16 (round-to-nearest-even) of an fp32 value, as bits: what pack.hip's and rows.hip's rounding kernels store
+__device__ __forceinline__ unsigned short bf16_bits(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
+#endif
 // ring-resident experience: ring_cap == 0 means "not a ring" (logical row == physical row)
 inline int ring_window(const char *who, int64_t ring_base, int64_t ring_cap, int64_t *base, int64_t *cap) {
     *cap = ring_cap > 0 ? ring_cap : INT64_MAX;
@@ -337,29 +341,26 @@ void set_fused_test_hold(int v);
 int launch_gae(hipStream_t, const float *, const float *, const float *, const float *, const float *, int64_t, double, double, float,
                float *, float *, float *, void *, size_t, const float *value_scale = nullptr);
 
-// optim.hip -------------------------------------------------------------------------------------------
+// pack.hip: the kernels' weight copies ----------------------------------------------------------------
+struct PackJob {  // one layer: where its W / W^T / b live in the packed copy and in the flat arena
+    int in, out, pin, pout;
+    int64_t off_w, off_wt, off_b, off_flat_w, off_flat_b;
+    int64_t first;  // first global work item of this layer
+};
+struct PackJobs {  // a network's layers, by value in a kernel's arguments (pack.hip's kernels, optim.hip's re-packing update)
+    int n;
+    PackJob j[RLPPO_MAX_LAYERS];
+    int64_t total;
+};
+void fill_jobs(const NetLayout &net, PackJobs *jobs);
 int launch_pack(hipStream_t, const NetLayout &, const float *, float *);
 int launch_pack_bf16(hipStream_t st, const NetLayout &net, const float *flat, float *packed_r, unsigned short *wb16);
 int launch_round_rows(hipStream_t st, float *x, unsigned short *xb, int64_t n_elems);
 int launch_expand_rows(hipStream_t st, const unsigned short *xb, float *x, int64_t n_elems);
-int launch_gather_rows_round(hipStream_t st, const float *src, int64_t ld_src, const int64_t *idx, float *dst, unsigned short *dstb,
-                             int width, int64_t n, int64_t ring_base, int64_t ring_cap);
-int launch_clip_adam(hipStream_t, float *p, float *g, float *m, float *v, int64_t n, float max_norm, float step_size,
-                     float bc2_sqrt, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, double *gnorm2);
-int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *p, float *const *g, float *const *m, float *const *v,
-                           float *const *packed, double *const *gnorm2, const int64_t *n, const float *max_norm,
-                           const float *step_size, const float *bc2_sqrt, const float *omb1, const float *beta2, const float *omb2,
-                           const float *eps, void *sync_ws = nullptr, const unsigned *const *skip = nullptr,
-                           const int64_t *tail = nullptr,   // tail[k]: of the n[k] elements, the last tail[k] are not part of `packed`
-                           const double *const *lr = nullptr, const double *bc1 = nullptr);  // [lr] lr[k]: device rate of network k (NULL: step_size[k]), bc1[k] its divisor
-int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float *adv, int64_t ring_base, int64_t ring_cap, float *out,
-                     void *ws);                             // [ABI 7] rlppo_adv_stats
-int launch_value_norm_update(hipStream_t st, const float *targets, int64_t n, double *state, float *scale, void *ws);  // [vnorm] rlppo_value_norm_update
-int launch_kl_gate(hipStream_t st, const rlppo_kl_gate_args &a);  // [ABI 7] rlppo_kl_gate
-int launch_kl_gate_lr(hipStream_t st, const rlppo_kl_gate_args &a, const rlppo_lr_adapt_args &l);  // [lr] rlppo_kl_gate_lr
-int launch_welford(hipStream_t st, const float *x, int64_t ld, int64_t n, int d, void *mean, void *m2, long long count0, int state_f64);
-int launch_welford_merge(hipStream_t st, int d, void *mean, void *m2, long long count, const float *omean, const float *om2,
-                         long long ocount, int state_f64);
+
+// rows.hip: staging observation and experience rows ---------------------------------------------------
+int launch_pad_rows(hipStream_t, const void *, int, int64_t, int64_t, int64_t, float *, int64_t, int, float, float);
+int launch_pad_rows_vec(hipStream_t, const void *, int, int64_t, int64_t, int64_t, float *, int64_t, const float *, const float *);
 struct GatherMeta {  // [r5] the per-row scalars of gather_meta_kernel, gathered by gather_rows_kernel in the same launch
     const float *actions = nullptr, *old_logp = nullptr, *adv = nullptr, *targets = nullptr;
     float *g_act = nullptr, *g_old = nullptr, *g_adv = nullptr, *g_tgt = nullptr, *zero_n = nullptr;
@@ -380,11 +381,31 @@ struct GatherSide {  // [critic rows] one matrix of gather_rows2_kernel: dst[r][
 int launch_gather_rows2(hipStream_t st, const float *src_p, int64_t ld_p, float *dst_p, int width_p, const float *src_c, int64_t ld_c,
                         float *dst_c, int width_c, const int64_t *idx, int64_t n, int64_t ring_base = 0, int64_t ring_cap = INT64_MAX,
                         const GatherMeta *meta = nullptr);
+int launch_gather_rows_round(hipStream_t st, const float *src, int64_t ld_src, const int64_t *idx, float *dst, unsigned short *dstb,
+                             int width, int64_t n, int64_t ring_base, int64_t ring_cap);
+int launch_welford(hipStream_t st, const float *x, int64_t ld, int64_t n, int d, void *mean, void *m2, long long count0, int state_f64);
+int launch_welford_merge(hipStream_t st, int d, void *mean, void *m2, long long count, const float *omean, const float *om2,
+                         long long ocount, int state_f64);
 int launch_i64_to_f32(hipStream_t st, const int64_t *src, float *dst, int64_t n);
+
+// optim.hip: clip + Adam ------------------------------------------------------------------------------
+int launch_clip_adam(hipStream_t, float *p, float *g, float *m, float *v, int64_t n, float max_norm, float step_size,
+                     float bc2_sqrt, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, double *gnorm2);
+int launch_clip_adam_pack2(hipStream_t st, const NetLayout *nets, float *const *p, float *const *g, float *const *m, float *const *v,
+                           float *const *packed, double *const *gnorm2, const int64_t *n, const float *max_norm,
+                           const float *step_size, const float *bc2_sqrt, const float *omb1, const float *beta2, const float *omb2,
+                           const float *eps, void *sync_ws = nullptr, const unsigned *const *skip = nullptr,
+                           const int64_t *tail = nullptr,   // tail[k]: of the n[k] elements, the last tail[k] are not part of `packed`
+                           const double *const *lr = nullptr, const double *bc1 = nullptr);  // [lr] lr[k]: device rate of network k (NULL: step_size[k]), bc1[k] its divisor
+
+// stats.hip: the statistics launches around an optimiser step -----------------------------------------
 int launch_learn_report(hipStream_t st, const rlppo_report_args &r);  // [r6] the tail of a learn(): norms of the update, statistics out, one completion word
+int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float *adv, int64_t ring_base, int64_t ring_cap, float *out,
+                     void *ws);                             // [ABI 7] rlppo_adv_stats
+int launch_value_norm_update(hipStream_t st, const float *targets, int64_t n, double *state, float *scale, void *ws);  // [vnorm] rlppo_value_norm_update
+int launch_kl_gate(hipStream_t st, const rlppo_kl_gate_args &a);  // [ABI 7] rlppo_kl_gate
+int launch_kl_gate_lr(hipStream_t st, const rlppo_kl_gate_args &a, const rlppo_lr_adapt_args &l);  // [lr] rlppo_kl_gate_lr
 int launch_signal_words(hipStream_t st, unsigned *words, int count, unsigned value);  // words[0..count) <- value, released at system scope
-int launch_pad_rows(hipStream_t, const void *, int, int64_t, int64_t, int64_t, float *, int64_t, int, float, float);
-int launch_pad_rows_vec(hipStream_t, const void *, int, int64_t, int64_t, int64_t, float *, int64_t, const float *, const float *);
 // rollout.hip: the device-resident vector environment's bookkeeping (rlppo_rollout_record / rlppo_obs_scalars / rlppo_rollout_to_trajectory_major)
 int launch_rollout_record(hipStream_t st, const void *rewards, int r_dt, const void *dones, int d_dt, const void *truncated, int t_dt,
                           int64_t n, int64_t t, int64_t T, float *rdt, double *ep_sums, void *state, float *patch);

@@ -644,7 +644,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_b16p_kernel(const unsigned sho
 
 // Applicability of the bf16-in-memory forward: K a multiple of 64 (one LDS tile row = 64 k-values), hidden widths a multiple
 // of 128 (the bitmask tile geometry).  Everything else takes the fp32 kernels on the ROUNDED fp32 copies -- the same products
-// (a product of two bf16 values is exact in fp32), only slower -- followed by round_rows (optim.hip).
+// (a product of two bf16 values is exact in fp32), only slower -- followed by round_rows (pack.hip).
 static int g_b16_wide = 2;  // rlppo_dbg_set(23, .): hidden / dX products of the bf16 update precision on 128 x 128 tiles (0), 256 x 256 tiles,
                             // one workgroup per tile (1), or 256 x 256 tiles walked by persistent workgroups (2, default [r3])
 void set_b16_wide_tiles(int on) { g_b16_wide = on < 0 ? 0 : (on > 2 ? 2 : on); }
