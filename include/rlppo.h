@@ -393,7 +393,7 @@ int rlppo_gae_norm(void *stream, const float *rews, const float *dones, const fl
                    float *value_targets, float *advantages, float *returns, void *workspace, size_t ws_bytes);
 
 /* [vnorm] The running statistic of the value targets, advanced by one batch on the device (rl_games' normalize_value / RunningMeanStd;
- * PopArt without its weight-preserving step).  targets: DEVICE float[n].  state: DEVICE double[4] = {count, mean, M2, rejected},
+ * PopArt's statistic; its weight-preserving step is rlppo_value_norm_update_popart below).  targets: DEVICE float[n].  state: DEVICE double[4] = {count, mean, M2, rejected},
  * 8-byte aligned, zero for a fresh statistic.  scale: DEVICE float[4], 16-byte aligned, what rlppo_gae_norm and
  * rlppo_ppo_minibatch_vnorm read: {mu, 1/sigma, sigma, 0} with sigma = sqrt(M2 / count + 1e-5) (population variance), each entry
  * computed in double and rounded once; the owner of a fresh statistic fills it with {0, 1, 1, 0}.  ONE launch: every workgroup sums
@@ -405,6 +405,27 @@ int rlppo_gae_norm(void *stream, const float *rews, const float *dones, const fl
  * its owner (every call leaves it armed).  n <= 0, a NULL pointer or a misaligned one is RLPPO_ERR_ARG before any HIP call. */
 #define RLPPO_VALUE_NORM_WS_BYTES 4096
 int rlppo_value_norm_update(void *stream, const float *targets, int64_t n, double *state, float *scale, void *ws);
+
+/* [vnorm] rlppo_value_norm_update with PopArt's weight-preserving step (van Hasselt et al. 2016; an added entry point, the ABI version
+ * stays as it is): the critic's last layer -- w_last: DEVICE float[n_w], b_last: DEVICE float[1], each 4-byte aligned, anywhere inside
+ * the critic's flat arena -- is rescaled in the SAME launch, so that the critic's real-unit output is what it was:
+ *     sigma_1 v^' + mu_1 = sigma_0 v^ + mu_0     up to the rounding of w', b' and the forward itself.
+ * {mu_0, ., sigma_0, .} is `scale` as PUBLISHED before the update -- the floats the last scan and loss read --, read before they are
+ * overwritten and widened to double; a fresh statistic has {0, 1, 1, 0} and the formula applies to it as it stands.
+ * {mu_1, ., sigma_1, .} are the floats the same launch has just published, widened to double.  With r = sigma_0 / sigma_1 (ONE double
+ * division):
+ *     w'_i = (float)((double)w_i * r)                                         for each of the n_w weights
+ *     b'   = (float)(fma((double)b, sigma_0, mu_0 - mu_1) / sigma_1)
+ * every operation spelled out (a double multiplication, one fma, a double subtraction and two double divisions, each rounded to
+ * nearest): the build's contraction setting cannot change a bit.  State and scale after the call are, bit for bit, what
+ * rlppo_value_norm_update produces from the same state and batch.  A rejected batch (non-finite targets) moves no statistic, stores
+ * NOTHING into w_last or b_last and adds 1 to state[3]; the ticket is re-armed on every path.  The last-arriving workgroup does the
+ * merge in one thread and the rescale in all 256: no floating-point atomics, no spin-wait, plain vector stores, the same bits every
+ * run.  The caller owns what derives from the weights (packed images: rebuild them) and the optimiser's moments (left alone, as in
+ * PopArt).  w_last == NULL && b_last == NULL is exactly rlppo_value_norm_update; exactly one of them NULL, n_w < 1 with weights
+ * given, or a misaligned pointer is RLPPO_ERR_ARG, naming the argument, before any HIP call. */
+int rlppo_value_norm_update_popart(void *stream, const float *targets, int64_t n, double *state, float *scale, void *ws, float *w_last,
+                                   int64_t n_w, float *b_last);
 
 /* -------------------------------------------------------------------------------------- PPO update */
 

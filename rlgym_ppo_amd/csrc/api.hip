@@ -523,17 +523,35 @@ int rlppo_gae_norm(void *stream, const float *rews, const float *dones, const fl
                return_std, value_targets, advantages, returns, workspace, ws_bytes);
 }
 
+// the two forms of the statistic's update: one check.  who: the form's name in the error text
+static int value_norm_check(const char *who, const float *targets, int64_t n, double *state, float *scale, void *ws) {
+    RLPPO_CHECK_ARG(n >= 1, "%s: n=%ld < 1", who, (long)n);
+    RLPPO_CHECK_ARG(targets != nullptr, "%s: targets is NULL", who);
+    RLPPO_CHECK_ARG(state != nullptr, "%s: state is NULL", who);
+    RLPPO_CHECK_ARG(scale != nullptr, "%s: scale is NULL", who);
+    RLPPO_CHECK_ARG(ws != nullptr, "%s: ws is NULL", who);
+    RLPPO_CHECK_ARG((uintptr_t)targets % 4 == 0, "%s: targets must be 4-byte aligned", who);
+    RLPPO_CHECK_ARG((uintptr_t)state % 8 == 0, "%s: state must be 8-byte aligned", who);
+    RLPPO_CHECK_ARG((uintptr_t)scale % 16 == 0, "%s: scale must be 16-byte aligned", who);
+    RLPPO_CHECK_ARG((uintptr_t)ws % 8 == 0, "%s: ws must be 8-byte aligned", who);
+    return 0;
+}
 int rlppo_value_norm_update(void *stream, const float *targets, int64_t n, double *state, float *scale, void *ws) {
-    RLPPO_CHECK_ARG(n >= 1, "value_norm_update: n=%ld < 1", (long)n);
-    RLPPO_CHECK_ARG(targets != nullptr, "value_norm_update: targets is NULL");
-    RLPPO_CHECK_ARG(state != nullptr, "value_norm_update: state is NULL");
-    RLPPO_CHECK_ARG(scale != nullptr, "value_norm_update: scale is NULL");
-    RLPPO_CHECK_ARG(ws != nullptr, "value_norm_update: ws is NULL");
-    RLPPO_CHECK_ARG((uintptr_t)targets % 4 == 0, "value_norm_update: targets must be 4-byte aligned");
-    RLPPO_CHECK_ARG((uintptr_t)state % 8 == 0, "value_norm_update: state must be 8-byte aligned");
-    RLPPO_CHECK_ARG((uintptr_t)scale % 16 == 0, "value_norm_update: scale must be 16-byte aligned");
-    RLPPO_CHECK_ARG((uintptr_t)ws % 8 == 0, "value_norm_update: ws must be 8-byte aligned");
+    if (const int rc = value_norm_check("value_norm_update", targets, n, state, scale, ws)) return rc;
     return launch_value_norm_update((hipStream_t)stream, targets, n, state, scale, ws);
+}
+// [vnorm] ... with PopArt's weight-preserving step on the critic's last layer; no layer: rlppo_value_norm_update
+int rlppo_value_norm_update_popart(void *stream, const float *targets, int64_t n, double *state, float *scale, void *ws, float *w_last,
+                                   int64_t n_w, float *b_last) {
+    if (!w_last && !b_last) return rlppo_value_norm_update(stream, targets, n, state, scale, ws);
+    const char *who = "value_norm_update_popart";
+    if (const int rc = value_norm_check(who, targets, n, state, scale, ws)) return rc;
+    RLPPO_CHECK_ARG(w_last != nullptr, "%s: w_last is NULL but b_last is not (give both or neither)", who);
+    RLPPO_CHECK_ARG(b_last != nullptr, "%s: b_last is NULL but w_last is not (give both or neither)", who);
+    RLPPO_CHECK_ARG(n_w >= 1, "%s: n_w=%ld < 1", who, (long)n_w);
+    RLPPO_CHECK_ARG((uintptr_t)w_last % 4 == 0, "%s: w_last must be 4-byte aligned", who);
+    RLPPO_CHECK_ARG((uintptr_t)b_last % 4 == 0, "%s: b_last must be 4-byte aligned", who);
+    return launch_value_norm_update_popart((hipStream_t)stream, targets, n, state, scale, ws, w_last, n_w, b_last);
 }
 
 int rlppo_clip_adam(void *stream, float *params, float *grads, float *exp_avg, float *exp_avg_sq, int64_t n,

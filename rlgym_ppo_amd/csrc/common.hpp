@@ -403,6 +403,8 @@ int launch_learn_report(hipStream_t st, const rlppo_report_args &r);  // [r6] th
 int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float *adv, int64_t ring_base, int64_t ring_cap, float *out,
                      void *ws);                             // [ABI 7] rlppo_adv_stats
 int launch_value_norm_update(hipStream_t st, const float *targets, int64_t n, double *state, float *scale, void *ws);  // [vnorm] rlppo_value_norm_update
+int launch_value_norm_update_popart(hipStream_t st, const float *targets, int64_t n, double *state, float *scale, void *ws, float *w_last,
+                                    int64_t n_w, float *b_last);  // [vnorm] ... with the critic's last layer rescaled in the same launch
 int launch_kl_gate(hipStream_t st, const rlppo_kl_gate_args &a);  // [ABI 7] rlppo_kl_gate
 int launch_kl_gate_lr(hipStream_t st, const rlppo_kl_gate_args &a, const rlppo_lr_adapt_args &l);  // [lr] rlppo_kl_gate_lr
 int launch_signal_words(hipStream_t st, unsigned *words, int count, unsigned value);  // words[0..count) <- value, released at system scope

@@ -47,10 +47,13 @@ struct TicketWs {
 // The sum of s[0], s[1] over every thread of the launch (gridDim.x <= BLOCKS workgroups of 256 threads), without floating-point
 // atomics: each workgroup parks its pair in its slot of `ws` and takes a ticket; the threads of the LAST arriver fetch the slots
 // side by side (one thread walking 128 dependent loads took 19 of learn_report_kernel's 24 us) and its thread 0 adds them in slot
-// order.  Returns true in thread 0 of the last-arriving workgroup ONLY, with the totals in s[]; every other thread is done (false).
-// That thread writes its outputs and ends with ticket_rearm(ws).  This is the only place these kernels synchronise across workgroups.
+// order.  This is the only place these kernels synchronise across workgroups.
+//
+// ticket_pair_sum_together keeps the last arriver whole: it returns true in EVERY thread of the last-arriving workgroup (uniformly:
+// a __syncthreads() behind it is legal) and false in every thread of every other; the totals are in s[] of its thread 0 alone.  For an
+// epilogue with work for 256 threads (value_norm_update_popart_kernel's rescale); thread 0 ends with ticket_rearm(ws).
 template <int BLOCKS>
-__device__ __forceinline__ bool ticket_pair_sum(double (&s)[2], TicketWs<BLOCKS> *ws) {
+__device__ __forceinline__ bool ticket_pair_sum_together(double (&s)[2], TicketWs<BLOCKS> *ws) {
     __shared__ int last;
     __shared__ double slots[BLOCKS][2];
     block_sum_256(s);
@@ -66,13 +69,19 @@ __device__ __forceinline__ bool ticket_pair_sum(double (&s)[2], TicketWs<BLOCKS>
     if (threadIdx.x < 2 * gridDim.x)
         slots[threadIdx.x >> 1][threadIdx.x & 1] = __hip_atomic_load(&ws->partial[threadIdx.x >> 1][threadIdx.x & 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    if (threadIdx.x != 0) return false;
+    if (threadIdx.x != 0) return true;
     s[0] = s[1] = 0.0;
     for (unsigned b = 0; b < gridDim.x; ++b) {
         s[0] += slots[b][0];
         s[1] += slots[b][1];
     }
     return true;
+}
+// ... and the form of an epilogue of one thread: true in thread 0 of the last-arriving workgroup ONLY, with the totals in s[]; every
+// other thread is done (false).  That thread writes its outputs and ends with ticket_rearm(ws).
+template <int BLOCKS>
+__device__ __forceinline__ bool ticket_pair_sum(double (&s)[2], TicketWs<BLOCKS> *ws) {
+    return ticket_pair_sum_together(s, ws) && threadIdx.x == 0;
 }
 template <int BLOCKS>
 __device__ __forceinline__ void ticket_rearm(TicketWs<BLOCKS> *ws) {

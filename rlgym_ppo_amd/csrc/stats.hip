@@ -101,44 +101,99 @@ int launch_adv_stats(hipStream_t st, const int64_t *idx, int64_t n, const float 
 using VnormWs = TicketWs<ADV_BLOCKS>;  // (batch_stat_blocks: the same grid)
 static_assert(sizeof(VnormWs) <= RLPPO_VALUE_NORM_WS_BYTES, "value norm workspace");
 
-__global__ __launch_bounds__(256) void value_norm_update_kernel(const float *__restrict__ x, int64_t n, double *__restrict__ state,
-                                                                float *__restrict__ scale, VnormWs *__restrict__ ws) {
+// every thread's share of the batch's shifted sums: s = {sum (x - x_0), sum (x - x_0)^2}; returns the pivot x_0
+__device__ __forceinline__ double value_norm_sums(const float *__restrict__ x, int64_t n, double (&s)[2]) {
     const double k0 = (double)x[0];
-    double s[2] = {0.0, 0.0};
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double d = (double)x[i] - k0;
         s[0] += d;
         s[1] += d * d;
     }
-    if (!ticket_pair_sum(s, ws)) return;
+    return k0;
+}
+
+// the one thread that holds the batch's totals: merge and publish.  False for a rejected batch, which moves state[3] alone.
+__device__ __forceinline__ bool value_norm_merge(const double (&s)[2], double k0, int64_t n, double *__restrict__ state,
+                                                 float *__restrict__ scale) {
     // (a NaN / infinite target makes k0 or a sum non-finite: x - x = NaN covers an infinite pivot)
     if (!(fabs(s[0]) < INFINITY && fabs(s[1]) < INFINITY && fabs(k0) < INFINITY)) {
         state[3] += 1.0;
-    } else {
-        const double nb = (double)n;
-        const double m = s[0] / nb;
-        const double mean_b = k0 + m;
-        double m2_b = s[1] - s[0] * m;
-        m2_b = m2_b > 0.0 ? m2_b : 0.0;
-        const double count = state[0], mean = state[1], m2 = state[2];
-        const double delta = mean_b - mean, tot = count + nb;
-        const double mean_new = mean + delta * nb / tot;
-        const double m2_new = m2 + (m2_b + delta * delta * count * nb / tot);
-        state[0] = tot;
-        state[1] = mean_new;
-        state[2] = m2_new;
-        const double sd = sqrt(m2_new / tot + 1e-5);
-        scale[0] = (float)mean_new;
-        scale[1] = (float)(1.0 / sd);
-        scale[2] = (float)sd;
-        scale[3] = 0.f;
+        return false;
     }
+    const double nb = (double)n;
+    const double m = s[0] / nb;
+    const double mean_b = k0 + m;
+    double m2_b = s[1] - s[0] * m;
+    m2_b = m2_b > 0.0 ? m2_b : 0.0;
+    const double count = state[0], mean = state[1], m2 = state[2];
+    const double delta = mean_b - mean, tot = count + nb;
+    const double mean_new = mean + delta * nb / tot;
+    const double m2_new = m2 + (m2_b + delta * delta * count * nb / tot);
+    state[0] = tot;
+    state[1] = mean_new;
+    state[2] = m2_new;
+    const double sd = sqrt(m2_new / tot + 1e-5);
+    scale[0] = (float)mean_new;
+    scale[1] = (float)(1.0 / sd);
+    scale[2] = (float)sd;
+    scale[3] = 0.f;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void value_norm_update_kernel(const float *__restrict__ x, int64_t n, double *__restrict__ state,
+                                                                float *__restrict__ scale, VnormWs *__restrict__ ws) {
+    double s[2] = {0.0, 0.0};
+    const double k0 = value_norm_sums(x, n, s);
+    if (!ticket_pair_sum(s, ws)) return;
+    value_norm_merge(s, k0, n, state, scale);
     ticket_rearm(ws);
 }
 
 int launch_value_norm_update(hipStream_t st, const float *targets, int64_t n, double *state, float *scale, void *ws) {
     hipLaunchKernelGGL(value_norm_update_kernel, dim3(batch_stat_blocks(n)), dim3(256), 0, st, targets, n, state, scale,
                        reinterpret_cast<VnormWs *>(ws));
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same update with PopArt's weight-preserving step (rlppo_value_norm_update_popart; the arithmetic is the contract in
+// include/rlppo.h): the critic's last layer, n_w weights w and one bias b, is rescaled in the launch that moves the statistic, so that
+// sigma_1 v^' + mu_1 = sigma_0 v^ + mu_0 for every input.  The last arriver stays whole (ticket_pair_sum_together): its thread 0
+// reads {mu_0, sigma_0} as PUBLISHED -- the floats the last scan and loss read --, merges, and parks r = sigma_0 / sigma_1, sigma_0,
+// mu_0 - mu_1 and sigma_1 (doubles of the published floats) in LDS; behind one __syncthreads() the 256 threads rescale w
+// grid-stride-wise with scalar loads and stores (w is only 4-byte aligned inside its arena) and thread 0 writes b.  Every operation
+// is spelled out (__dmul_rn, fma, __ddiv_rn): no contraction setting can change a bit.  A rejected batch stores nothing into w or b.
+__global__ __launch_bounds__(256) void value_norm_update_popart_kernel(const float *__restrict__ x, int64_t n, double *__restrict__ state,
+                                                                       float *__restrict__ scale, VnormWs *__restrict__ ws,
+                                                                       float *__restrict__ w, int64_t n_w, float *__restrict__ b) {
+    __shared__ double park[4];   // r, sigma_0, mu_0 - mu_1, sigma_1
+    __shared__ int moved;
+    double s[2] = {0.0, 0.0};
+    const double k0 = value_norm_sums(x, n, s);
+    if (!ticket_pair_sum_together(s, ws)) return;
+    if (threadIdx.x == 0) {
+        const double mu0 = (double)scale[0], sd0 = (double)scale[2];
+        moved = value_norm_merge(s, k0, n, state, scale);
+        if (moved) {
+            const double mu1 = (double)scale[0], sd1 = (double)scale[2];   // (as published: this thread's own stores, rounded once)
+            park[0] = __ddiv_rn(sd0, sd1);
+            park[1] = sd0;
+            park[2] = __dsub_rn(mu0, mu1);
+            park[3] = sd1;
+        }
+        ticket_rearm(ws);
+    }
+    __syncthreads();
+    if (!moved) return;
+    const double r = park[0];
+    for (int64_t i = threadIdx.x; i < n_w; i += 256) w[i] = (float)__dmul_rn((double)w[i], r);
+    if (threadIdx.x == 0) b[0] = (float)__ddiv_rn(fma((double)b[0], park[1], park[2]), park[3]);
+}
+
+int launch_value_norm_update_popart(hipStream_t st, const float *targets, int64_t n, double *state, float *scale, void *ws, float *w_last,
+                                    int64_t n_w, float *b_last) {
+    hipLaunchKernelGGL(value_norm_update_popart_kernel, dim3(batch_stat_blocks(n)), dim3(256), 0, st, targets, n, state, scale,
+                       reinterpret_cast<VnormWs *>(ws), w_last, n_w, b_last);
     RLPPO_LAUNCH_CHECK();
     return 0;
 }

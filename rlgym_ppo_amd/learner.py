@@ -46,7 +46,7 @@ class Learner(object):
             hidden_activation: str = "relu",
             ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
             critic_observations: bool = False,
-            ppo_normalize_value: bool = False,
+            ppo_normalize_value: bool = False, ppo_value_norm_popart: bool = False,
             per_feature_obs_standardization: bool = False,
             ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
         assert env_create_function is not None, "MUST PROVIDE A FUNCTION TO CREATE RLGYM FUNCTIONS TO INITIALIZE RLGYM-PPO"
@@ -71,6 +71,12 @@ class Learner(object):
         # (VectorAgentManager.critic_value_input_rows, ExperienceBuffer.critic_states).  Vector mode only: the process-mode wire format
         # has no slot for the rows; and not together with gae_bootstrap_truncated, which would need FINAL critic observations.  Checked
         # here, before anything is built or spawned; False is the library as it was, launch for launch.
+        # not in the reference: ppo_value_norm_popart=True adds PopArt's weight-preserving step to ppo_normalize_value -- the launch that
+        # advances the statistic rescales the critic's last layer, so the critic's real-unit predictions are not moved by the
+        # book-keeping.  An option of ppo_normalize_value; checked here, before anything is built or spawned.
+        if ppo_value_norm_popart and not ppo_normalize_value:
+            raise ValueError("ppo_value_norm_popart=True needs ppo_normalize_value=True: there is no running statistic whose moves "
+                             "the critic's last layer could follow")
         self.critic_observations = bool(critic_observations)
         if self.critic_observations:
             if not vector_env:
@@ -209,8 +215,9 @@ class Learner(object):
         # PPOLearner.set_value_normalization).  The statistic is checkpoint state (value_norm_running_stats in the book).
         self.normalize_value = bool(ppo_normalize_value)
         self._value_norm_host = None   # (mu, sigma, rejected batches) as of the last add_new_experience: its one read-back
+        self.value_norm_popart = bool(ppo_value_norm_popart)
         if self.normalize_value:
-            self.ppo_learner.set_value_normalization(True)
+            self.ppo_learner.set_value_normalization(True, preserve_outputs=self.value_norm_popart)
         if ppo_lr_schedule == "adaptive":   # ("linear" is this loop's: the update runs the constant schedule's launches)
             self.ppo_learner.set_lr_schedule("adaptive", ppo_desired_kl, ppo_lr_bounds)
         self.ppo_learner.report_learning_rates = ppo_lr_schedule != "constant"
@@ -246,7 +253,7 @@ class Learner(object):
             "critic_lr": critic_lr, "shm_buffer_size": shm_buffer_size,
             "gae_bootstrap_truncated": self.gae_bootstrap_truncated,  # (a hyper-parameter, not checkpoint state)
             "critic_observations": self.critic_observations,
-            "ppo_normalize_value": self.normalize_value,
+            "ppo_normalize_value": self.normalize_value, "ppo_value_norm_popart": self.value_norm_popart,
         }
 
         self.wandb_run = wandb_run
@@ -351,7 +358,9 @@ class Learner(object):
         ppo_normalize_value: the value pass yields NORMALISED values; the scan takes every one of them (bootstrap values included) to
         real units under the statistic as it stands -- the one the critic was trained under -- so targets, advantages and returns are
         in real units as always; then the statistic advances with this call's N value targets (one launch) and learn() runs under
-        the new, fixed scale.  mu, sigma and the count of rejected batches ride in the call's one device-to-host read."""
+        the new, fixed scale.  mu, sigma and the count of rejected batches ride in the call's one device-to-host read.
+        ppo_value_norm_popart: that one launch also rescales the critic's last layer for the new scale (PPOLearner.update_value_norm),
+        so learn() starts from a critic whose real-unit predictions are the ones the scan just used; the order of steps is the same."""
         states, actions, log_probs, rewards, next_states, dones, truncated = experience
         value_net = self.ppo_learner.value_net
         n = states.shape[0]
@@ -409,8 +418,8 @@ class Learner(object):
             gae_kw["value_scale"] = value_norm.scale
         value_targets, advantages, returns, gae_timeouts = torch_functions.gae_device_deferred(
             rews_d, dones_d, trunc_d, val_preds, gamma=self.gae_gamma, lmbda=self.gae_lambda, return_std=ret_std, **gae_kw)
-        if value_norm is not None:
-            value_norm.update(value_targets)
+        if value_norm is not None:   # (ppo_value_norm_popart: the same launch rescales the critic's last layer for the new scale)
+            self.ppo_learner.update_value_norm(value_targets)
 
         # ONE device-to-host read per call: the scan's timeout counter travels with the min(150, N) returns the statistics need
         n_to_increment = min(self.max_returns_per_stats_increment, n) if self.standardize_returns else 0

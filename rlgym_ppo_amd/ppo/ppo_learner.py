@@ -37,8 +37,12 @@ reference parameter or is set after construction:
   * `set_value_normalization(True)` is rl_games' `normalize_value`: the critic regresses standardised value
     targets and puts out normalised values.  `self.value_norm` (a ValueNorm) owns the running statistic and the scale every pass
     reads (rlppo_ppo_minibatch_vnorm); the buffer keeps REAL-unit targets.  learn() never moves the statistic (`Learner` does, once per
-    iteration; a caller of a bare PPOLearner calls `value_norm.update(targets)`) and no collective is added for data-parallel use:
+    iteration; a caller of a bare PPOLearner calls `update_value_norm(targets)`) and no collective is added for data-parallel use:
     replicas see the same targets or are given one state (`value_norm_state()` / `load_value_norm_state()`).
+    `set_value_normalization(True, preserve_outputs=True)` adds PopArt's weight-preserving step: the launch that moves the statistic
+    rescales the critic's last layer, so its real-unit predictions are what they were (`ValueNorm.update(targets, preserve=critic)`,
+    rlppo_value_norm_update_popart).  No collective here either: the step is deterministic, so replicas that feed the same targets
+    stay bit-identical; replicas that are handed one state are handed the weights with it.
 """
 import ctypes
 import os
@@ -86,15 +90,33 @@ class ValueNorm(object):
         self.arg = N.ValueNormArg()
         self.arg.scale = self.scale.data_ptr()
 
-    def update(self, targets):
+    def update(self, targets, preserve=None):
         """Advance the statistic with a batch of real-unit value targets (fp32 device tensor) and publish the new scale: one launch,
-        no host wait.  A batch with a non-finite entry changes nothing but state[3]."""
+        no host wait.  A batch with a non-finite entry changes nothing but state[3].
+
+        preserve: a ValueEstimator (one output) whose real-unit predictions are to stay what they are -- PopArt's weight-preserving
+        step: the same launch rescales its last Linear's weight and bias for the new scale (rlppo_value_norm_update_popart), and the
+        arena's native_epoch is bumped, so the packed, bf16 and x3 images are rebuilt before anything reads them.  An optimiser's
+        moments for those parameters are left alone, as in PopArt.  No other network is touched."""
         t = targets.reshape(-1)
         assert t.dtype == torch.float32 and t.device == self.state.device
         if t.numel() == 0:
             return
         t = t.contiguous()
-        N.check(N.lib().rlppo_value_norm_update(stream_ptr(), ptr(t), t.numel(), ptr(self.state), ptr(self.scale), ptr(self._ws)))
+        if preserve is None:
+            N.check(N.lib().rlppo_value_norm_update(stream_ptr(), ptr(t), t.numel(), ptr(self.state), ptr(self.scale), ptr(self._ws)))
+            return
+        arena = getattr(preserve, "arena", None)
+        if arena is None or arena.d_out != 1:
+            raise ValueError("ValueNorm.update: preserve must be a ValueEstimator with one output, got "
+                             f"{type(preserve).__name__}" + ("" if arena is None else f" with {arena.d_out} outputs"))
+        assert arena.flat.device == self.state.device
+        if not arena.is_bound():
+            arena.bind()
+        last = arena.linears[-1]
+        N.check(N.lib().rlppo_value_norm_update_popart(stream_ptr(), ptr(t), t.numel(), ptr(self.state), ptr(self.scale), ptr(self._ws),
+                                                       ptr(last.weight), last.weight.numel(), ptr(last.bias)))
+        arena.native_epoch += 1
 
     def denormalize(self, v):
         """Real-unit values of the critic's normalised outputs (a torch op, for users; the scan does it itself)."""
@@ -343,14 +365,26 @@ class PPOLearner(object):
         self.lr_probe = None  # callable(rates [2] device doubles {policy, critic}, KL_b [1] device double) after every gate (tests)
         self._lr_dev = self._lr_host = None
         self.value_norm = None   # set_value_normalization(True): a ValueNorm; None = the critic regresses raw value targets
+        self.value_norm_preserve_outputs = False   # set_value_normalization(True, preserve_outputs=True): PopArt's weight-preserving step
 
-    def set_value_normalization(self, on=True):
+    def set_value_normalization(self, on=True, preserve_outputs=False):
         """Train the critic on standardised value targets from now on (module docstring), or stop doing so.  Switching it on keeps a
-        statistic that exists; a fresh one publishes {0, 1, 1, 0}: raw until its first update."""
+        statistic that exists; a fresh one publishes {0, 1, 1, 0}: raw until its first update.  preserve_outputs (the attribute
+        value_norm_preserve_outputs): update_value_norm rescales the critic's last layer with every move of the statistic."""
+        if preserve_outputs and not on:
+            raise ValueError("set_value_normalization: preserve_outputs=True needs on=True (there is no statistic to move with the option off)")
+        self.value_norm_preserve_outputs = bool(preserve_outputs)
         if not on:
             self.value_norm = None
         elif self.value_norm is None:
             self.value_norm = ValueNorm(self._dev)
+
+    def update_value_norm(self, targets):
+        """Advance the statistic with a batch of real-unit value targets: ValueNorm.update, with this learner's critic as `preserve`
+        where value_norm_preserve_outputs is set.  Never part of learn(); checkpoint loads and load_value_norm_state never rescale."""
+        if self.value_norm is None:
+            raise ValueError("update_value_norm: value normalisation is off (set_value_normalization(True) first)")
+        self.value_norm.update(targets, preserve=self.value_net if self.value_norm_preserve_outputs else None)
 
     def value_norm_state(self):
         """The statistic as a dictionary (ValueNorm.state_dict), None with the option off: what a replica or a checkpoint needs."""
