@@ -216,6 +216,21 @@ typedef struct rlppo_act_opts {
 #define RLPPO_ACT_RELU 0
 #define RLPPO_ACT_TANH 1
 #define RLPPO_ACT_ELU 2
+/* [norm] Layer normalisation of the hidden activations, without learnable parameters: RLPPO_ACT_NORM or-ed into an activation field
+ * (rlppo_act_opts.hidden_act, rlppo_minibatch_ext.pol_hidden_act / val_hidden_act; 0x100 .. 0x102 are valid, every other value is
+ * refused as before) makes every hidden layer of that network Linear -> activation -> LayerNorm(elementwise_affine = False) -> next
+ * Linear: y = (h - mean(h)) * rsqrt(var(h) + 1e-5) over the layer's TRUE width, torch's biased variance and epsilon.  (In this position a
+ * learnable gamma / beta would be absorbed exactly by the next Linear -- W' = W diag(gamma), b' = b + W beta -- so the function class
+ * loses nothing, and no parameter, weight image, optimiser state or checkpoint key changes.)  Without the bit a call is the one it
+ * was, launch for launch.  With it the layer chain is GEMM (bias + activation epilogue, unchanged) -> rlppo_row_norm_fwd per hidden
+ * layer; an update pass takes the PLAIN form (as for tanh / ELU: no bitmasks, pairing, folded value head or gather-fused first
+ * layer), keeps the activation h AND its normalised image, stores the dX product of the layer above plain and turns it into the
+ * gradient of the layer's pre-activation with rlppo_row_norm_bwd.  Policy and critic choose independently.  Refused with
+ * RLPPO_ERR_ARG before the first HIP call: update precisions bf16 and x3, the bf16 inference precision, and a hidden layer whose padded
+ * width exceeds RLPPO_NORM_MAX_WIDTH.  rlppo_discrete_step_one_launch answers 0 (rlppo_discrete_act / _step take their layer chain).
+ * A pass's workspace is rlppo_minibatch_workspace_bytes_norm; one sized by the other functions is RLPPO_ERR_WORKSPACE. */
+#define RLPPO_ACT_NORM 0x100
+#define RLPPO_NORM_MAX_WIDTH 2048
 #ifdef __cplusplus
 static_assert(sizeof(rlppo_act_opts) == 40 && offsetof(rlppo_act_opts, hidden_act) == 36, "rlppo_act_opts: hidden_act lives in the former tail padding");
 #else
@@ -567,6 +582,11 @@ typedef struct rlppo_minibatch_ext {
     size_t scratch_bytes;
 } rlppo_minibatch_ext;
 int rlppo_ppo_minibatch_ex(void *stream, const rlppo_minibatch_args *args, const rlppo_minibatch_ext *ext);
+/* [norm] The workspace of a pass whose ext carries RLPPO_ACT_NORM in pol_hidden_act and / or val_hidden_act: the plan of
+ * rlppo_minibatch_workspace_bytes_for (critic_rows != 0: of _critic), followed per normalised network by one [mb][padded width] matrix
+ * per hidden layer and one row of zeros.  Without the bit in either field it equals those functions; a bad field gives 0. */
+size_t rlppo_minibatch_workspace_bytes_norm(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
+                                            int64_t mb, int32_t precision, int32_t critic_rows, int32_t pol_hidden_act, int32_t val_hidden_act);
 
 /* [critic rows] The same pass with a critic that reads a row matrix of its own (asymmetric actor-critic: "privileged observations";
  * an added entry point: the structs and the ABI version stay as they are).  critic->states: DEVICE, 16-byte aligned, [N][ld_states]
@@ -915,6 +935,18 @@ typedef struct rlppo_gather2_args {
     float *g_act, *g_old, *g_adv, *g_tgt, *zero_n;
 } rlppo_gather2_args;
 int rlppo_gather_rows2(void *stream, const rlppo_gather2_args *args);
+/* [norm] The two row kernels of hidden layer normalisation on their own (csrc/norm.hip).  Matrices: DEVICE fp32, 16-byte aligned,
+ * leading dimensions multiples of 4 and at least P = rlppo_padded_out(width); P <= RLPPO_NORM_MAX_WIDTH (else RLPPO_ERR_ARG naming
+ * the limit, before any launch).  Rows at and beyond n are neither read nor written.  No allocation, no synchronisation, no atomics:
+ * capturable, and bit-reproducible from run to run.
+ *   fwd: y[r][c] = (h[r][c] - mu_r) * rstd_r for c < width, exact 0 for width <= c < P (whatever h and y held there); mu_r the mean and
+ *        rstd_r = 1 / sqrt(var_r + 1e-5), var_r the biased variance, of h[r][0 .. width).  y may be h.
+ *   bwd: with y^ the forward's output recomputed from h (nothing else is kept), dx[r][c] = f'(h[r][c]) * rstd_r * (dy[r][c] - mean_c(dy)
+ *        - y^[r][c] * mean_c(dy y^)) for c < width (means over c < width), exact 0 for width <= c < P.  f' is the derivative of activation
+ *        `act` (RLPPO_ACT_RELU / _TANH / _ELU) as a function of its saved OUTPUT h: h > 0; 1 - h^2; h > 0 ? 1 : h + 1.  dx may be dy. */
+int rlppo_row_norm_fwd(void *stream, const float *h, int64_t ld, int64_t n, int32_t width, float *y, int64_t ld_y);
+int rlppo_row_norm_bwd(void *stream, const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int32_t width, int32_t act,
+                       float *dx, int64_t ld_dx);
 
 /* WelfordRunningStat.increment(samples, n) (running_stats.py:28-46) on the device, bit-exact with the reference's sample-by-
  * sample update: mean[d], m2[d] (= running_mean, running_variance) are updated in place with the n rows of `samples` (fp32,

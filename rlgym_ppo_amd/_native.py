@@ -33,6 +33,8 @@ PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16, PRECISION_X3 = 0, 1, 2, 3  # 
 ACT_RELU, ACT_TANH, ACT_ELU = 0, 1, 2  # RLPPO_ACT_*: rlppo_act_opts.hidden_act, rlppo_minibatch_ext.{pol,val}_hidden_act
 COUNTER_CRITIC_ROWS_PASS = 15  # rlppo_dbg_counter key: passes with separate critic rows
 HIDDEN_ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "elu": ACT_ELU}
+ACT_NORM = 0x100  # RLPPO_ACT_NORM: or-ed into an activation code = layer normalisation behind every hidden activation
+NORM_MAX_WIDTH = 2048  # RLPPO_NORM_MAX_WIDTH
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -215,6 +217,7 @@ SIGNATURES = {
     "rlppo_ppo_minibatch_diag": (c_int32, [c_void_p, POINTER(MinibatchArgs), c_void_p, c_void_p, c_void_p, c_size_t]),
     "rlppo_ppo_minibatch_ex": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt)]),
     "rlppo_minibatch_workspace_bytes_critic": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
+    "rlppo_minibatch_workspace_bytes_norm": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32]),
     "rlppo_ppo_minibatch_critic": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows)]),
     "rlppo_ppo_minibatch_vnorm": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows), POINTER(ValueNormArg)]),
     "rlppo_ppo_join": (c_int32, [c_void_p]),
@@ -260,6 +263,8 @@ SIGNATURES = {
                                                     c_int32, c_int32, c_int32, c_void_p]),
     "rlppo_gather_rows": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64]),
     "rlppo_gather_rows2": (c_int32, [c_void_p, POINTER(Gather2Args)]),
+    "rlppo_row_norm_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64]),
+    "rlppo_row_norm_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64]),
     "rlppo_welford_increment": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32]),
     "rlppo_welford_merge": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32]),
     "rlppo_rollout_record": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p,

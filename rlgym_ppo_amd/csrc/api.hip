@@ -95,7 +95,8 @@ struct ActCtx {
     unsigned *noise_ctl = nullptr;
     const unsigned *mask = nullptr;  // [ABI 8] rlppo_act_opts.action_mask / mask_words
     int mask_words = 0;
-    int hidden_act = ACT_RELU;       // [act] rlppo_act_opts.hidden_act
+    int hidden_act = ACT_RELU;       // [act] rlppo_act_opts.hidden_act ...
+    int hidden_norm = 0;             // [norm] ... and its RLPPO_ACT_NORM bit
 };
 // One call of a rollout entry point: the network, the call's options and, once act_chain has run, the last layer's output
 struct ActCall {
@@ -114,11 +115,14 @@ static int act_open(ActCall *call, const int32_t *dims, int32_t n_layers, const 
     RLPPO_CHECK_ARG(o->precision == RLPPO_PRECISION_DEFAULT || o->precision == RLPPO_PRECISION_FP32 || o->precision == RLPPO_PRECISION_BF16,
                     "act options: inference precision %d (0 = process default, 1 = fp32, 2 = bf16 operands)", o->precision);
     if (o->precision != RLPPO_PRECISION_DEFAULT) c->bf16 = o->precision == RLPPO_PRECISION_BF16;
-    RLPPO_CHECK_ARG(hidden_act_ok(o->hidden_act), "act options: hidden_act %d (0 = ReLU, 1 = tanh, 2 = ELU)", o->hidden_act);
-    c->hidden_act = o->hidden_act;
+    RLPPO_CHECK_ARG(hidden_act_split(o->hidden_act, &c->hidden_act, &c->hidden_norm), "act options: hidden_act %d (0 = ReLU, 1 = tanh, 2 = ELU)", o->hidden_act);
     RLPPO_CHECK_ARG(!(c->bf16 && c->hidden_act != ACT_RELU),
                     "act options: hidden activation %s with the bf16 inference precision: the bf16-operand kernels are ReLU only",
                     hidden_act_name(c->hidden_act));
+    RLPPO_CHECK_ARG(!(c->bf16 && c->hidden_norm), "act options: hidden layer normalisation (RLPPO_ACT_NORM) with the bf16 inference precision: the "
+                    "bf16-operand kernels feed the next product without the row kernel");
+    RLPPO_CHECK_ARG(!c->hidden_norm || norm_width_ok(call->net), "act options: hidden layer normalisation of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded)",
+                    RLPPO_NORM_MAX_WIDTH);
     c->done = o->done_words;
     c->done_value = o->done_value;
     c->noise_ctl = o->noise_ctl;
@@ -152,6 +156,7 @@ static int act_chain(hipStream_t st, ActCall *call, const float *packed, const f
     c.n = n;
     c.out_tanh = out_tanh;
     c.hidden_act = call->cx.hidden_act;
+    c.hidden_norm = call->cx.hidden_norm;
     c.bf16_operands = call->cx.bf16;
     for (int l = 0; l < net.n_layers; ++l) c.b.act[l] = (l & 1) ? b1 : b0;
     if (final_out) c.b.act[net.n_layers - 1] = final_out;
@@ -256,7 +261,7 @@ int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     if (rc) return rc;
     // [r3] one launch for the whole step when the network has the form fused_act.hip covers (fp32 inference precision); the
     // layer-by-layer chain below otherwise -- bit-identical results either way
-    if (g_fused_act && !cx.bf16 && !cx.hidden_act && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS && ld_obs >= net.L[0].pin && ld_obs % 4 == 0 &&
+    if (g_fused_act && !cx.bf16 && !cx.hidden_act && !cx.hidden_norm && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS && ld_obs >= net.L[0].pin && ld_obs % 4 == 0 &&
         (reinterpret_cast<uintptr_t>(obs) & 15) == 0) {  // (the kernel stages the padded rows with 16-byte loads)
         FusedActIO io = fused_act_io(cx, noise_q, actions, logp);
         io.rows = obs;
@@ -308,7 +313,7 @@ int rlppo_host_window_free(void *ptr) {
 int rlppo_discrete_step_one_launch(const int32_t *dims, int32_t n_layers, int64_t n, const rlppo_act_opts *opts) {
     ActCall c;
     if (act_open(&c, dims, n_layers, opts, true, nullptr)) return -1;
-    return g_fused_act && !c.cx.bf16 && !c.cx.hidden_act && fused_act_ok(c.net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
+    return g_fused_act && !c.cx.bf16 && !c.cx.hidden_act && !c.cx.hidden_norm && fused_act_ok(c.net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
 }
 
 int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const void *obs, int32_t obs_is_f64,
@@ -329,7 +334,7 @@ int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, con
     rc = act_mask_check(cx, dims[n_layers]);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (g_fused_act && !cx.bf16 && !cx.hidden_act && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
+    if (g_fused_act && !cx.bf16 && !cx.hidden_act && !cx.hidden_norm && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
         FusedActIO io = fused_act_io(cx, noise_q, actions, logp);
         io.raw = obs;
         io.raw_is_f64 = obs_is_f64;

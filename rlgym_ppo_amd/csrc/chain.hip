@@ -86,6 +86,10 @@ int forward(Chain &c) {
         set_error("forward: hidden activation %s runs the plain fp32 layer chain only", hidden_act_name(c.hidden_act));
         return RLPPO_ERR_ARG;
     }
+    if (c.hidden_norm && (c.bf16_operands || any_bits || c.may_fold || c.x3 || c.in.rowtab)) {
+        set_error("forward: hidden layer normalisation runs the plain fp32 layer chain only");
+        return RLPPO_ERR_ARG;
+    }
     X3Layout xl;
     if (c.x3) x3_layout(net, &xl);
     for (int l = 0; l < net.n_layers; ++l) c.have_bits[l] = false;
@@ -126,6 +130,12 @@ int forward(Chain &c) {
         if (rc) return rc;
         x = c.b.act[l];
         ldx = L.pout;
+        if (c.hidden_norm) {  // [norm] (the chain's first launch also clears the zero bias its backward reads)
+            float *y = c.b.norm[l] ? c.b.norm[l] : c.b.act[l];
+            rc = launch_row_norm_fwd(c.st, c.b.act[l], L.pout, c.n, L.out, L.pout, y, L.pout, l == 0 ? c.b.zeros : nullptr, max_pout(net));
+            if (rc) return rc;
+            x = y;
+        }
     }
     RLPPO_CHECK_ARG(hl > 0 || !c.in.rowtab, "forward: the gathered first layer needs the bitmask form");
     return c.head_folded ? 0 : output_forward(c, x, ldx);
@@ -224,7 +234,7 @@ int layer_backward(Chain &c, int l, bool need_bits) {
     float *const *acts = c.b.act, *const *dx = c.b.dx;
     const float *dY = l == last ? acts[last] : dx[l];
     const int64_t ld_hy = c.head_folded ? 1 : L.pout;  // stride of a one-output head's dY (compact when it was folded, forward())
-    const RowSource X = l > 0 ? RowSource{acts[l - 1], net.L[l - 1].pout} : c.in;
+    const RowSource X = l > 0 ? RowSource{c.hidden_norm ? c.b.norm[l - 1] : acts[l - 1], net.L[l - 1].pout} : c.in;
     const bool gemv = l == last && l > 0 && gemv_head_ok(L.out, L.pin);  // one-output head (gemv.hip)
     const size_t floats = tn_layer_floats(net, l, mb, 0);  // (fp32 / split-bf16 precisions: the bf16 one has backward_b16)
     int rc = 0;
@@ -236,6 +246,13 @@ int layer_backward(Chain &c, int l, bool need_bits) {
         rc = launch_gemm_tn(st, dY, L.pout, L.pout, X.x, X.ld, L.pin, c.grad + L.off_flat_w, c.grad + L.off_flat_b, L.out, L.in, mb,
                             c.b.tn, floats, X.rowtab, X.src_rows);
     if (rc || l == 0) return rc;
+    if (c.hidden_norm) {  // [norm] the plain product (zero bias, stored as it is), then the normalisation's and the activation's backward
+        RLPPO_CHECK_ARG(c.b.norm[l - 1] && c.b.zeros, "backward: a normalised chain needs its normalised activations and zero bias");
+        if (gemv) rc = launch_gemv_dx(st, dY, ld_hy, c.w + L.off_w, nullptr, 0, dx[l - 1], L.pin, L.pin, mb, ACT_PLAIN);
+        else rc = launch_gemm_nt(st, dY, L.pout, c.w + L.off_wt, L.pout, c.b.zeros, nullptr, 0, dx[l - 1], L.pin, mb, L.pin, L.pout, EPI_BIAS);
+        if (rc) return rc;
+        return launch_row_norm_bwd(st, acts[l - 1], L.pin, dx[l - 1], L.pin, mb, net.L[l - 1].out, L.pin, c.hidden_act, dx[l - 1], L.pin);
+    }
     // dX[mb][pin] = (dY[mb][pout] . W[pout][pin]) masked by relu'(acts[l-1]); B operand = W^T [pin][pout].  The mask is the
     // bitmask the forward left when there is one (no re-read of the activation), else the saved activation itself.
     // [act] tanh / ELU: times f'(acts[l-1]), a function of the saved OUTPUT alone (1 - h^2; h > 0 ? 1 : h + 1) -- the same

@@ -49,6 +49,10 @@ struct NetWs {
     unsigned short *actb[RLPPO_MAX_LAYERS] = {};      // bf16 update precision: the hidden activations ...
     unsigned short *dxb[RLPPO_MAX_LAYERS] = {};       // ... and their gradients as bf16
     float *tn = nullptr;                              // the partial dW tiles of the net's chain
+    // [norm] a normalised network: the normalised output of every hidden layer, [mb][pout] (null: normalised in place -- inference),
+    // and max_pout zeros: the bias of the backward's plain dX products
+    float *norm[RLPPO_MAX_LAYERS] = {};
+    float *zeros = nullptr;
 };
 
 // What one network contributes to one pass or one inference call.  b.act[l] receives the output of layer l ([n][pout_l]): for
@@ -58,6 +62,9 @@ struct NetWs {
 // in.rowtab != nullptr: the first layer fetches its rows through the table (nt_gather_ok must hold for it).
 // [act] hidden_act (HiddenAct): the activation of every hidden layer.  tanh / ELU have the plain form only -- the callers give them no
 // bitmasks, no folded head, no row table, no bf16 operands and no split planes (all of those carry ReLU by construction).
+// [norm] hidden_norm: every hidden layer is GEMM (bias + activation epilogue) -> row_norm_fwd (norm.hip); the normalised output is the
+// next layer's A operand and its weight-gradient product's X operand, b.act[l] stays the saved activation.  backward(): the dX product
+// of layer l + 1 stores plain and row_norm_bwd turns it into b.dx[l].  The plain form only, like tanh / ELU.
 struct Chain {
     hipStream_t st = nullptr;
     const NetLayout *net = nullptr;
@@ -65,7 +72,7 @@ struct Chain {
     RowSource in = {nullptr, 0};
     const unsigned short *in_b = nullptr;  // bf16 update precision: the rows of `in` as bf16
     int64_t n = 0;
-    int out_tanh = 0, hidden_act = ACT_RELU;
+    int out_tanh = 0, hidden_act = ACT_RELU, hidden_norm = 0;
     int bf16_operands = 0;  // inference precision: fp32 data, bf16-rounded operands
     NetWs b;
     float *grad = nullptr;     // the gradient arena, and ...

@@ -105,10 +105,28 @@ enum Epilogue {
 constexpr bool epi_reads_act(int e) { return e == EPI_MASK || e == EPI_DTANH || e == EPI_DELU; }
 // [act] rlppo_act_opts.hidden_act / rlppo_minibatch_ext.*_hidden_act: 0 = ReLU, 1 = tanh, 2 = ELU (alpha = 1)
 enum HiddenAct { ACT_RELU = 0, ACT_TANH = 1, ACT_ELU = 2 };
+constexpr int ACT_PLAIN = -1;  // [norm] launch_gemv_dx alone: no derivative, no saved activation (mask may be null)
 inline bool hidden_act_ok(int a) { return a >= ACT_RELU && a <= ACT_ELU; }
 inline const char *hidden_act_name(int a) { return a == ACT_TANH ? "tanh" : a == ACT_ELU ? "elu" : "relu"; }
 inline int hidden_act_fwd_epi(int a) { return a == ACT_TANH ? EPI_BIAS_TANH : a == ACT_ELU ? EPI_BIAS_ELU : EPI_BIAS_RELU; }
 inline int hidden_act_dx_epi(int a) { return a == ACT_TANH ? EPI_DTANH : a == ACT_ELU ? EPI_DELU : EPI_MASK; }
+// [norm] the same fields carry RLPPO_ACT_NORM (0x100) as a high bit: layer normalisation behind every hidden activation.  Splits a
+// field into its activation and the flag; false for every value that is neither an activation nor one with the flag.
+inline bool hidden_act_split(int field, int *act, int *norm) {
+    *act = field & ~RLPPO_ACT_NORM;
+    *norm = field >= 0 && (field & RLPPO_ACT_NORM) != 0;
+    return field >= 0 && hidden_act_ok(*act);
+}
+
+// norm.hip: parameter-free layer normalisation of a hidden activation ----------------------------------
+// y[r][0:width) = (h - mean) * rsqrt(var + 1e-5) of row r, y[r][width:pout) = 0; y may be h.  zeros (optional): zero_n floats the
+// launch clears besides.
+int launch_row_norm_fwd(hipStream_t st, const float *h, int64_t ld, int64_t n, int width, int pout, float *y, int64_t ld_y,
+                        float *zeros = nullptr, int zero_n = 0);
+// dx = act'(h) * (the normalisation's backward of dy at h), padded columns 0; dx may be dy
+int launch_row_norm_bwd(hipStream_t st, const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int width, int pout, int act,
+                        float *dx, int64_t ld_dx);
+bool norm_width_ok(const NetLayout &net);  // every hidden layer's padded width is at most RLPPO_NORM_MAX_WIDTH
 
 // gemm.hip ------------------------------------------------------------------------------------------
 // C[m][0:N] = epi(A[m][0:K] . B[n][0:K]^T)   (K % 32 == 0, N = padded out in {32,64,96,128,k*128})

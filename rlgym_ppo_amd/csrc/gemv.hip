@@ -80,12 +80,14 @@ __global__ __launch_bounds__(256) void gemv_dx_kernel(const float *__restrict__ 
     const int c = (int)(t - row * cpr) * 4;
     if (row >= n) return;
     const float d = dy[row * ldy];
-    const f32x4 h = *reinterpret_cast<const f32x4 *>(mask + row * ldm + c);
+    f32x4 h = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (ACT != ACT_PLAIN) h = *reinterpret_cast<const f32x4 *>(mask + row * ldm + c);
     const f32x4 wv = *reinterpret_cast<const f32x4 *>(w + c);
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        if constexpr (ACT == ACT_TANH) o[e] = (d * wv[e]) * (1.f - h[e] * h[e]);
+        if constexpr (ACT == ACT_PLAIN) o[e] = d * wv[e];  // [norm] the plain product: the row kernel (norm.hip) applies the derivative
+        else if constexpr (ACT == ACT_TANH) o[e] = (d * wv[e]) * (1.f - h[e] * h[e]);
         else if constexpr (ACT == ACT_ELU) o[e] = (d * wv[e]) * (h[e] > 0.f ? 1.f : h[e] + 1.f);
         else o[e] = h[e] > 0.f ? d * wv[e] : 0.f;
     }
@@ -394,7 +396,8 @@ int launch_gemv_dx(hipStream_t st, const float *dy, int64_t ldy, const float *w,
     if (n <= 0) return 0;
     const int cpr = kp / 4;
     const dim3 grid((unsigned)cdiv(n * cpr, 256));
-    if (act == ACT_TANH) hipLaunchKernelGGL(gemv_dx_kernel<ACT_TANH>, grid, dim3(256), 0, st, dy, ldy, w, mask, ldm, dx, ldc, cpr, n);
+    if (act == ACT_PLAIN) hipLaunchKernelGGL(gemv_dx_kernel<ACT_PLAIN>, grid, dim3(256), 0, st, dy, ldy, w, mask, ldm, dx, ldc, cpr, n);
+    else if (act == ACT_TANH) hipLaunchKernelGGL(gemv_dx_kernel<ACT_TANH>, grid, dim3(256), 0, st, dy, ldy, w, mask, ldm, dx, ldc, cpr, n);
     else if (act == ACT_ELU) hipLaunchKernelGGL(gemv_dx_kernel<ACT_ELU>, grid, dim3(256), 0, st, dy, ldy, w, mask, ldm, dx, ldc, cpr, n);
     else hipLaunchKernelGGL(gemv_dx_kernel<ACT_RELU>, grid, dim3(256), 0, st, dy, ldy, w, mask, ldm, dx, ldc, cpr, n);
     RLPPO_LAUNCH_CHECK();

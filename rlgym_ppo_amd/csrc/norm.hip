@@ -1,0 +1,232 @@
+// norm.hip -- parameter-free layer normalisation of a hidden activation, as two row kernels between the products of a layer chain
+// (chain.hip): y = (h - mean(h)) * rsqrt(var(h) + 1e-5) over the TRUE width of the layer (torch's F.layer_norm without weight or
+// bias: biased variance, eps inside the root), and its backward multiplied by the activation's derivative in the same launch.
+//
+// Design.  A row lives in the registers of the lanes that own it: LPR lanes per row (16 for padded widths up to 128 -- four rows per
+// wave --, the whole wave from 256 on), lane i holding the 16-byte chunks i, i + LPR, ... of the row (consecutive lanes read
+// consecutive chunks: every load and store instruction of a wave covers whole runs of a row).  A lane adds its own elements in
+// column order, the lanes' sums meet in an xor butterfly of log2(LPR) shuffles -- every lane ends with the same bits, the order is
+// fixed by the shape alone, so results are reproducible from run to run and the backward recomputes the forward's statistics
+// exactly (row_stats is the one instruction sequence both kernels run; nothing but h is kept between them).  No LDS, no atomics, no
+// allocation, no synchronisation: the forward is one read and one write of the matrix, the backward two reads and one write.
+// The variance is centred (a second pass over the registers, never E[x^2] - mean^2), and the mean is refined once by the mean of
+// the centred values, so a row of mean 1e3 and spread 1 keeps the precision of its spread.  Columns [width, padded width) are
+// outside every sum and are STORED as exact zeros (the next layer's products and the dW product read them); rows at and beyond n
+// are neither read nor written.  The outputs may alias an input (y == h, dx == dy): a lane stores only after its last load, and only
+// the chunks it loaded.
+#include "common.hpp"
+
+namespace rlppo {
+
+namespace {
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr float NORM_EPS = 1e-5f;
+
+template <int LPR>
+__device__ __forceinline__ float group_sum(float v) {  // the sum over the LPR lanes of a row, in every one of them
+#pragma unroll
+    for (int m = LPR / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// A lane's share of one row: chunk j of the lane is columns 4 (j LPR + lane_in_row) .. + 3
+template <int LPR, int VPL>
+struct RowRegs {
+    f32x4 v[VPL];
+    __device__ __forceinline__ void load(const float *row, int sub, int cpr, bool live) {
+#pragma unroll
+        for (int j = 0; j < VPL; ++j) {
+            const int c = j * LPR + sub;
+            v[j] = live && c < cpr ? *reinterpret_cast<const f32x4 *>(row + 4 * c) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    __device__ __forceinline__ void store(float *row, int sub, int cpr, bool live) const {
+#pragma unroll
+        for (int j = 0; j < VPL; ++j) {
+            const int c = j * LPR + sub;
+            if (live && c < cpr) *reinterpret_cast<f32x4 *>(row + 4 * c) = v[j];
+        }
+    }
+};
+
+// mean and 1 / sqrt(var + eps) of the row whose share `h` is, over columns < width; on return h holds y^ = (h - mean) * rstd in
+// the valid columns and 0 in the others.  The forward's result and the backward's recomputation are this one sequence.
+template <int LPR, int VPL>
+__device__ __forceinline__ float row_stats(RowRegs<LPR, VPL> &h, int sub, int width) {
+    const float inv_w = 1.f / (float)width;
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s += 4 * (j * LPR + sub) + e < width ? h.v[j][e] : 0.f;
+    const float mu0 = group_sum<LPR>(s) * inv_w;
+    s = 0.f;  // the mean of the centred values: what rounding left of the mean (zero for a row that fp32 sums exactly)
+#pragma unroll
+    for (int j = 0; j < VPL; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s += 4 * (j * LPR + sub) + e < width ? h.v[j][e] - mu0 : 0.f;
+    const float mu = mu0 + group_sum<LPR>(s) * inv_w;
+    s = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float d = 4 * (j * LPR + sub) + e < width ? h.v[j][e] - mu : 0.f;
+            h.v[j][e] = d;
+            s += d * d;
+        }
+    const float rstd = 1.f / sqrtf(group_sum<LPR>(s) * inv_w + NORM_EPS);
+#pragma unroll
+    for (int j = 0; j < VPL; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) h.v[j][e] *= rstd;
+    return rstd;
+}
+
+// zeros (optional): zero_n floats that workgroup 0 clears -- the zero bias of the backward's plain dX products (chain.hip), written
+// by the chain's first forward launch instead of a fill of its own
+template <int LPR, int VPL>
+__global__ __launch_bounds__(256) void row_norm_fwd_kernel(const float *h, int64_t ld, int64_t n, int width, int cpr, float *y, int64_t ld_y,
+                                                           float *zeros, int zero_n) {
+    if (zeros && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < zero_n; i += 256) zeros[i] = 0.f;
+    const int64_t row = (int64_t)blockIdx.x * (256 / LPR) + threadIdx.x / LPR;
+    const int sub = threadIdx.x % LPR;
+    const bool live = row < n;
+    RowRegs<LPR, VPL> r;
+    r.load(h + row * ld, sub, cpr, live);
+    row_stats<LPR, VPL>(r, sub, width);
+    r.store(y + row * ld_y, sub, cpr, live);
+}
+
+// dx = act'(h) * rstd * (dy - mean(dy) - y^ mean(dy y^)), the means over columns < width; ACT's derivative from the saved OUTPUT h
+template <int LPR, int VPL, int ACT>
+__global__ __launch_bounds__(256) void row_norm_bwd_kernel(const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int width,
+                                                           int cpr, float *dx, int64_t ld_dx) {
+    const int64_t row = (int64_t)blockIdx.x * (256 / LPR) + threadIdx.x / LPR;
+    const int sub = threadIdx.x % LPR;
+    const bool live = row < n;
+    RowRegs<LPR, VPL> a, yh, g;
+    a.load(h + row * ld, sub, cpr, live);
+    g.load(dy + row * ld_dy, sub, cpr, live);
+    yh = a;
+    const float rstd = row_stats<LPR, VPL>(yh, sub, width);
+    const float inv_w = 1.f / (float)width;
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float d = 4 * (j * LPR + sub) + e < width ? g.v[j][e] : 0.f;
+            g.v[j][e] = d;
+            s1 += d;
+            s2 += d * yh.v[j][e];
+        }
+    const float m1 = group_sum<LPR>(s1) * inv_w, m2 = group_sum<LPR>(s2) * inv_w;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float hv = a.v[j][e];
+            const float dh = rstd * ((g.v[j][e] - m1) - yh.v[j][e] * m2);
+            float o;
+            if constexpr (ACT == ACT_TANH) o = dh * (1.f - hv * hv);
+            else if constexpr (ACT == ACT_ELU) o = dh * (hv > 0.f ? 1.f : hv + 1.f);
+            else o = hv > 0.f ? dh : 0.f;
+            g.v[j][e] = 4 * (j * LPR + sub) + e < width ? o : 0.f;
+        }
+    g.store(dx + row * ld_dx, sub, cpr, live);
+}
+
+// lanes per row and 16-byte chunks per lane of a padded width (a multiple of 32 up to RLPPO_NORM_MAX_WIDTH)
+struct NormShape {
+    int lpr, vpl;
+};
+NormShape norm_shape(int pout) {
+    if (pout <= 64) return {16, 1};
+    if (pout <= 128) return {16, 2};
+    const int v = (int)cdiv(pout, 256);
+    return {64, v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : 8};
+}
+int norm_check(const char *who, const void *a, int64_t lda, const void *b, int64_t ldb, const void *c, int64_t ldc, int width, int pout) {
+    RLPPO_CHECK_ARG(width >= 1 && width <= pout && pout % 4 == 0, "%s: width=%d, padded width=%d", who, width, pout);
+    RLPPO_CHECK_ARG(pout <= RLPPO_NORM_MAX_WIDTH, "%s: padded width %d: the row kernels hold a row of up to RLPPO_NORM_MAX_WIDTH = %d floats in registers",
+                    who, pout, RLPPO_NORM_MAX_WIDTH);
+    RLPPO_CHECK_ARG(lda >= pout && ldb >= pout && ldc >= pout && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0,
+                    "%s: leading dimensions %ld / %ld / %ld must be multiples of 4, at least the padded width %d", who, (long)lda, (long)ldb, (long)ldc, pout);
+    RLPPO_CHECK_ARG(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0,
+                    "%s: the matrices must be 16-byte aligned", who);
+    return 0;
+}
+}  // namespace
+
+bool norm_width_ok(const NetLayout &net) {
+    for (int l = 0; l + 1 < net.n_layers; ++l)
+        if (net.L[l].pout > RLPPO_NORM_MAX_WIDTH) return false;
+    return true;
+}
+
+int launch_row_norm_fwd(hipStream_t st, const float *h, int64_t ld, int64_t n, int width, int pout, float *y, int64_t ld_y, float *zeros, int zero_n) {
+    if (n <= 0) return 0;
+    if (int rc = norm_check("row_norm_fwd", h, ld, y, ld_y, zeros, ld, width, pout)) return rc;
+    const NormShape s = norm_shape(pout);
+    const dim3 grid((unsigned)cdiv(n, 256 / s.lpr));
+#define FWD(L, V) hipLaunchKernelGGL((row_norm_fwd_kernel<L, V>), grid, dim3(256), 0, st, h, ld, n, width, pout / 4, y, ld_y, zeros, zero_n)
+    if (s.lpr == 16) {
+        if (s.vpl == 1) FWD(16, 1); else FWD(16, 2);
+    } else if (s.vpl == 1) FWD(64, 1);
+    else if (s.vpl == 2) FWD(64, 2);
+    else if (s.vpl == 4) FWD(64, 4);
+    else FWD(64, 8);
+#undef FWD
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int ACT>
+static void launch_bwd(hipStream_t st, const NormShape s, dim3 grid, const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int width,
+                       int cpr, float *dx, int64_t ld_dx) {
+#define BWD(L, V) hipLaunchKernelGGL((row_norm_bwd_kernel<L, V, ACT>), grid, dim3(256), 0, st, h, ld, dy, ld_dy, n, width, cpr, dx, ld_dx)
+    if (s.lpr == 16) {
+        if (s.vpl == 1) BWD(16, 1); else BWD(16, 2);
+    } else if (s.vpl == 1) BWD(64, 1);
+    else if (s.vpl == 2) BWD(64, 2);
+    else if (s.vpl == 4) BWD(64, 4);
+    else BWD(64, 8);
+#undef BWD
+}
+
+int launch_row_norm_bwd(hipStream_t st, const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int width, int pout, int act,
+                        float *dx, int64_t ld_dx) {
+    if (n <= 0) return 0;
+    RLPPO_CHECK_ARG(hidden_act_ok(act), "row_norm_bwd: act %d (0 = ReLU, 1 = tanh, 2 = ELU)", act);
+    if (int rc = norm_check("row_norm_bwd", h, ld, dy, ld_dy, dx, ld_dx, width, pout)) return rc;
+    const NormShape s = norm_shape(pout);
+    const dim3 grid((unsigned)cdiv(n, 256 / s.lpr));
+    if (act == ACT_TANH) launch_bwd<ACT_TANH>(st, s, grid, h, ld, dy, ld_dy, n, width, pout / 4, dx, ld_dx);
+    else if (act == ACT_ELU) launch_bwd<ACT_ELU>(st, s, grid, h, ld, dy, ld_dy, n, width, pout / 4, dx, ld_dx);
+    else launch_bwd<ACT_RELU>(st, s, grid, h, ld, dy, ld_dy, n, width, pout / 4, dx, ld_dx);
+    RLPPO_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace rlppo
+
+using namespace rlppo;
+
+extern "C" {
+
+// the two launches on their own (the padded width is the library's: rlppo_padded_out(width))
+int rlppo_row_norm_fwd(void *stream, const float *h, int64_t ld, int64_t n, int32_t width, float *y, int64_t ld_y) {
+    if (n == 0) return 0;
+    RLPPO_CHECK_ARG(n > 0 && h && y && width >= 1, "row_norm_fwd: bad argument");
+    return launch_row_norm_fwd((hipStream_t)stream, h, ld, n, width, (int)rlppo_padded_out(width), y, ld_y, nullptr, 0);
+}
+int rlppo_row_norm_bwd(void *stream, const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int32_t width, int32_t act, float *dx,
+                       int64_t ld_dx) {
+    if (n == 0) return 0;
+    RLPPO_CHECK_ARG(n > 0 && h && dy && dx && width >= 1, "row_norm_bwd: bad argument");
+    return launch_row_norm_bwd((hipStream_t)stream, h, ld, dy, ld_dy, n, width, (int)rlppo_padded_out(width), act, dx, ld_dx);
+}
+
+}  // extern "C"

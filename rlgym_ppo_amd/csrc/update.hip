@@ -92,7 +92,10 @@ constexpr size_t BITS_PAD_RESERVE = 2, B16_PAD_RESERVE = 4;
 // Lays out the workspace of a pass from `base` into *w and returns its size in floats: the size the host is told and the layout
 // the pass uses come from this one walk.  critic_rows: the plan of a pass with separate critic rows (rlppo_ppo_minibatch_critic) -- the
 // critic's gathered rows follow the policy's, so they start on the boundary those do and every other plan is what it was.
-static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec, void *base, WsPlan *w, bool critic_rows) {
+// norm_nets: [norm] bit 0 / 1 = the policy / the critic is normalised -- its normalised activations and its zero bias FOLLOW everything else, so
+// every other region is where it was (rlppo_minibatch_workspace_bytes_norm sizes such a plan).
+static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec, void *base, WsPlan *w, bool critic_rows,
+                             int norm_nets = 0) {
     const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
     const size_t rows = (size_t)mb;
     size_t off = 0, slack = 0;  // floats from the base; the unused part of the pad reserves
@@ -143,6 +146,14 @@ static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t
             for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->actb[l] = take16(rows * nets[i]->L[l].pout);
         for (int i = 0; i < 2; ++i)
             for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->dxb[l] = take16(rows * nets[i]->L[l].pout);
+    }
+    if (norm_nets) {  // (16-byte loads: the row counts above need not be multiples of 4)
+        align(4, B16_PAD_RESERVE);
+        for (int i = 0; i < 2; ++i)
+            if (norm_nets >> i & 1) {
+                for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->norm[l] = take(rows * nets[i]->L[l].pout);
+                ws[i]->zeros = take((size_t)max_pout(*nets[i]));
+            }
     }
     return off + slack;
 }
@@ -226,6 +237,7 @@ struct Pass {
     // dX by the saved activation -- no bitmasks, no folded value head, no paired launches, no gather-fused first layer.  A pass with
     // a tanh / ELU network is plain (that machinery is ReLU by construction); rlppo_dbg_set(19, 0) makes a ReLU pass plain too.
     int pol_act = ACT_RELU, val_act = ACT_RELU;
+    int pol_norm = 0, val_norm = 0;  // [norm] layer normalisation behind every hidden activation of the network: a plain pass too
     bool plain = false;
 };
 
@@ -243,6 +255,7 @@ static Chain pass_chain(const Pass &p, bool critic) {
     c.n = p.mb;
     c.out_tanh = !critic && a.head == RLPPO_HEAD_GAUSSIAN;
     c.hidden_act = critic ? p.val_act : p.pol_act;
+    c.hidden_norm = critic ? p.val_norm : p.pol_norm;
     c.b = critic ? p.w.val : p.w.pol;
     if (p.plain)  // [act] the plain form: no bitmasks
         for (auto &bits : c.b.bits) bits = nullptr;
@@ -466,7 +479,7 @@ struct PassOpts {
     int32_t md_heads = 0;
     DiagHead diag;  // [diag] the diagonal-Gaussian head's parameter, gradient and scratch, when has_diag
     bool has_diag = false;
-    int pol_act = ACT_RELU, val_act = ACT_RELU;  // [act] the hidden activations
+    int pol_act = ACT_RELU, val_act = ACT_RELU;  // [act] the hidden activations, [norm] each with or without RLPPO_ACT_NORM
     const rlppo_critic_rows *critic = nullptr;   // [critic rows] the critic's own row matrix: non-null only with critic->states set
     const float *vnorm = nullptr;                // [vnorm] the value statistic's scale
 };
@@ -489,14 +502,18 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
     rc = resolve_precision(a->precision, &p.prec);
     if (rc) return rc;
     // [act] the hidden activations: tanh / ELU passes are fp32 (the bf16 and split-bf16 kernels carry the ReLU bitmask by construction)
-    RLPPO_CHECK_ARG(hidden_act_ok(o.pol_act) && hidden_act_ok(o.val_act), "ppo_minibatch: pol_hidden_act=%d val_hidden_act=%d (0 = ReLU, 1 = tanh, 2 = ELU)",
-                    o.pol_act, o.val_act);
-    p.pol_act = o.pol_act;
-    p.val_act = o.val_act;
-    const bool non_relu = o.pol_act != ACT_RELU || o.val_act != ACT_RELU;
+    RLPPO_CHECK_ARG(hidden_act_split(o.pol_act, &p.pol_act, &p.pol_norm) && hidden_act_split(o.val_act, &p.val_act, &p.val_norm),
+                    "ppo_minibatch: pol_hidden_act=%d val_hidden_act=%d (0 = ReLU, 1 = tanh, 2 = ELU)", o.pol_act, o.val_act);
+    const bool non_relu = p.pol_act != ACT_RELU || p.val_act != ACT_RELU;
     RLPPO_CHECK_ARG(!(non_relu && p.prec != 0), "ppo_minibatch: hidden activation %s with update precision %s: the %s kernels are ReLU only (use fp32)",
-                    hidden_act_name(o.pol_act != ACT_RELU ? o.pol_act : o.val_act), p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
-    p.plain = non_relu || (p.prec == 0 && !g_relu_bits);
+                    hidden_act_name(p.pol_act != ACT_RELU ? p.pol_act : p.val_act), p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
+    // [norm] a normalised network: fp32 passes in the plain form, rows of at most RLPPO_NORM_MAX_WIDTH floats
+    const bool normed = p.pol_norm || p.val_norm;
+    RLPPO_CHECK_ARG(!(normed && p.prec != 0), "ppo_minibatch: hidden layer normalisation (RLPPO_ACT_NORM) with update precision %s: the %s kernels have "
+                    "no place for the row kernels (use fp32)", p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
+    RLPPO_CHECK_ARG((!p.pol_norm || norm_width_ok(pol)) && (!p.val_norm || norm_width_ok(val)),
+                    "ppo_minibatch: hidden layer normalisation of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded)", RLPPO_NORM_MAX_WIDTH);
+    p.plain = non_relu || normed || (p.prec == 0 && !g_relu_bits);
     RLPPO_CHECK_ARG(mb > 0 && a->pol_packed && a->val_packed && a->pol_grad && a->val_grad && a->states && a->actions &&
                         a->old_logp && a->targets && a->advantages && a->idx && a->stats && a->workspace,
                     "ppo_minibatch: null pointer");
@@ -514,10 +531,12 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
     }
     RLPPO_CHECK_ARG(a->ld_states >= pol.L[0].pin && a->ld_states % 4 == 0, "ppo_minibatch: ld_states=%ld < %d",
                     (long)a->ld_states, pol.L[0].pin);
-    const size_t ws_bytes = plan_workspace(pol, val, mb, p.prec, a->workspace, &p.w, critic != nullptr) * sizeof(float);
+    const size_t ws_bytes = plan_workspace(pol, val, mb, p.prec, a->workspace, &p.w, critic != nullptr, p.pol_norm | p.val_norm << 1) * sizeof(float);
     if (a->ws_bytes < ws_bytes) {
         set_error("ppo_minibatch: workspace %zu < %zu bytes%s", a->ws_bytes, ws_bytes,
-                  critic ? " (separate critic rows: rlppo_minibatch_workspace_bytes_critic)" : "");
+                  normed   ? " (hidden layer normalisation: rlppo_minibatch_workspace_bytes_norm)"
+                  : critic ? " (separate critic rows: rlppo_minibatch_workspace_bytes_critic)"
+                           : "");
         return RLPPO_ERR_WORKSPACE;
     }
     // every head pins act_dim to at most the policy's output width (the gathered actions' slots); the loss kernel's width too
@@ -644,12 +663,12 @@ static int ppo_minibatch_opts(void *stream, const rlppo_minibatch_args *a, const
 }
 
 static size_t workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers, int64_t mb,
-                              int32_t precision, bool critic_rows) {
+                              int32_t precision, bool critic_rows, int norm_nets = 0) {
     NetLayout pol, val;
     int prec = 0;
     if (make_layout(pol_dims, pol_layers, &pol) || make_layout(val_dims, val_layers, &val) || resolve_precision(precision, &prec)) return 0;
     WsPlan unused;
-    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused, critic_rows) * sizeof(float) + 256;
+    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused, critic_rows, norm_nets) * sizeof(float) + 256;
 }
 
 extern "C" {
@@ -661,6 +680,13 @@ size_t rlppo_minibatch_workspace_bytes_for(const int32_t *pol_dims, int32_t pol_
 size_t rlppo_minibatch_workspace_bytes_critic(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
                                               int64_t mb, int32_t precision) {
     return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, true);
+}
+// [norm] the plan of _for / _critic (critic_rows != 0) + what the networks whose activation field carries RLPPO_ACT_NORM add; 0: a bad field
+size_t rlppo_minibatch_workspace_bytes_norm(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
+                                            int64_t mb, int32_t precision, int32_t critic_rows, int32_t pol_hidden_act, int32_t val_hidden_act) {
+    int pa, pn, va, vn;
+    if (!hidden_act_split(pol_hidden_act, &pa, &pn) || !hidden_act_split(val_hidden_act, &va, &vn)) return 0;
+    return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, critic_rows != 0, pn | vn << 1);
 }
 size_t rlppo_minibatch_workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims,
                                        int32_t val_layers, int64_t mb) {

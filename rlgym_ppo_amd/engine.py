@@ -912,3 +912,13 @@ def set_inference_precision(mode):
     fp32 accumulation; BASELINE configs[4]).  The PPO update always runs in fp32."""
     from . import _native as N
     N.check(N.lib().rlppo_set_inference_precision({"fp32": 0, "bf16": 1}[mode]))
+    global _inference_precision
+    _inference_precision = mode
+
+
+_inference_precision = "fp32"
+
+
+def inference_precision():
+    """What set_inference_precision chose for the process ("fp32" until it is called)."""
+    return _inference_precision

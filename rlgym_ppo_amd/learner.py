@@ -43,7 +43,7 @@ class Learner(object):
             n_checkpoints_to_keep: int = 5, shm_buffer_size: int = 8192, device: str = "auto",
             vector_env: bool = False, gae_bootstrap_truncated: bool = False, multi_discrete_bins=None,
             continuous_head: str = "reference", continuous_log_std_init: float = 0.0, continuous_action_clip="default",
-            hidden_activation: str = "relu",
+            hidden_activation: str = "relu", hidden_layer_norm=False,
             ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
             critic_observations: bool = False,
             ppo_normalize_value: bool = False, ppo_value_norm_popart: bool = False,
@@ -86,17 +86,38 @@ class Learner(object):
                 raise ValueError("critic_observations=True together with gae_bootstrap_truncated=True is not supported: bootstrapping a "
                                  "truncated step needs the critic's FINAL observation of the episode, which the environment interface "
                                  "does not carry yet")
+        # not in the reference: hidden_layer_norm = True | "policy" | "critic" puts layer normalisation without learnable parameters behind
+        # every hidden activation of both networks / the policy / the critic (rl_games' normalization: layer_norm, Brax's layer_norm=True;
+        # ppo._mlp.ActNorm).  It travels inside the layer sizes like the activation and follows the same agreement rule: sizes that already
+        # are a LayerSizes with norm="layer" keep it while the keyword is left at False, and must be among the networks the keyword names
+        # otherwise.  fp32 only: refused here, before anything is built, beside update precisions bf16 / x3 and the bf16 inference precision.
+        # self.hidden_norms says what was built.
         from .ppo._mlp import LayerSizes, check_activation
         hidden_activation = check_activation(hidden_activation)
+        if hidden_layer_norm not in (False, True, "policy", "critic"):
+            raise ValueError(f"hidden_layer_norm must be False, True, 'policy' or 'critic', got {hidden_layer_norm!r}")
 
         def with_activation(name, sizes):
             own = getattr(sizes, "activation", None)
             if own is not None and own != hidden_activation and hidden_activation != "relu":
                 raise ValueError(f"{name} is LayerSizes(..., {own!r}) but hidden_activation={hidden_activation!r}: give one of them")
-            return LayerSizes(sizes, own if own is not None else hidden_activation)
+            asked = "layer" if hidden_layer_norm is True or (hidden_layer_norm and name.startswith(hidden_layer_norm)) else None
+            own_norm = getattr(sizes, "norm", None)
+            if own_norm is not None and asked is None and hidden_layer_norm:
+                raise ValueError(f"{name} is LayerSizes(..., norm={own_norm!r}) but hidden_layer_norm={hidden_layer_norm!r}: give one of them")
+            return LayerSizes(sizes, own if own is not None else hidden_activation, own_norm or asked)
         sizes_given = (policy_layer_sizes, critic_layer_sizes)   # (what the config dict logs, as it always did)
         policy_layer_sizes = with_activation("policy_layer_sizes", policy_layer_sizes)
         critic_layer_sizes = with_activation("critic_layer_sizes", critic_layer_sizes)
+        self.hidden_norms = {"policy": policy_layer_sizes.norm, "critic": critic_layer_sizes.norm}
+        if any(self.hidden_norms.values()):
+            from . import engine
+            if engine.update_precision() != "fp32":
+                raise ValueError(f"hidden_layer_norm with update precision {engine.update_precision()!r}: the {engine.update_precision()} update "
+                                 "kernels have no place for the row kernels -- use engine.set_update_precision('fp32')")
+            if engine.inference_precision() == "bf16":
+                raise ValueError("hidden_layer_norm with the bf16 inference precision: the bf16-operand kernels feed the next product "
+                                 "without the row kernel -- use engine.set_inference_precision('fp32')")
         # what was built, per network; and as one name where both agree (the keyword's own type), None where they differ
         self.hidden_activations = {"policy": policy_layer_sizes.activation, "critic": critic_layer_sizes.activation}
         self.hidden_activation = policy_layer_sizes.activation if policy_layer_sizes.activation == critic_layer_sizes.activation else None

@@ -28,41 +28,71 @@ def check_activation(name):
     return name
 
 
+def check_norm(norm):
+    """The hidden normalisation the library runs: None or "layer"; ValueError otherwise."""
+    if norm is not None and norm != "layer":
+        raise ValueError(f"hidden normalisation must be None or 'layer', got {norm!r}")
+    return norm
+
+
 class LayerSizes(tuple):
     """Hidden layer sizes that carry the hidden activation ("relu", "tanh" or "elu", alpha = 1) of the network built from them -- the
     activation travels in an argument every constructor already has, the way multi-discrete bins travel in act_space_size.  A tuple
-    in every other respect (tuple(x) gives the plain sizes back); a plain tuple means "relu"."""
+    in every other respect (tuple(x) gives the plain sizes back); a plain tuple means "relu".
+    norm: None, or "layer" -- layer normalisation without learnable parameters behind every hidden activation (ActNorm)."""
 
-    def __new__(cls, sizes, activation="relu"):
+    def __new__(cls, sizes, activation="relu", norm=None):
         self = super().__new__(cls, tuple(sizes))
         self.activation = check_activation(activation)
+        self.norm = check_norm(norm)
         return self
 
     def __reduce__(self):
-        return (LayerSizes, (tuple(self), self.activation))
+        return (LayerSizes, (tuple(self), self.activation, self.norm))
 
     def __repr__(self):
-        return f"LayerSizes({tuple(self)!r}, {self.activation!r})"
+        return f"LayerSizes({tuple(self)!r}, {self.activation!r}" + (f", norm={self.norm!r})" if self.norm else ")")
+
+
+class ActNorm(nn.Module):
+    """A hidden activation followed by layer normalisation over the layer's `width` outputs, without weight or bias (eps = 1e-5):
+    Linear -> activation -> LayerNorm -> next Linear, the order in which rl_games builds its MLP.  ONE parameter-free module where the
+    activation alone would stand: a Sequential's indices and its state_dict keys are those of the un-normalised network."""
+
+    def __init__(self, act, width):
+        super().__init__()
+        self.act, self.width = act, int(width)
+
+    def forward(self, x):
+        return nn.functional.layer_norm(self.act(x), (self.width,), eps=1e-5)
 
 
 def activation_of(module):
     """The hidden activation's name of a body build_body made (index 1 of the Sequential is the first hidden activation)."""
+    first = module[1].act if isinstance(module[1], ActNorm) else module[1]
     for name, cls in HIDDEN_MODULES.items():
-        if type(module[1]) is cls:
+        if type(first) is cls:
             return name
-    raise ValueError(f"hidden activation {type(module[1]).__name__} has no kernels (build_body makes {sorted(HIDDEN_MODULES)})")
+    raise ValueError(f"hidden activation {type(first).__name__} has no kernels (build_body makes {sorted(HIDDEN_MODULES)})")
+
+
+def norm_of(module):
+    """The hidden normalisation of a body build_body made: "layer" or None."""
+    return "layer" if isinstance(module[1], ActNorm) else None
 
 
 def build_body(input_shape, layer_sizes, n_out, final_activation=None):
     assert len(layer_sizes) != 0, "AT LEAST ONE LAYER MUST BE SPECIFIED TO BUILD THE NEURAL NETWORK!"
     # the activation modules have no parameters and draw nothing: whichever is chosen, the Sequential's indices, its state_dict keys
     # and the CPU generator's consumption are the same, so a seeded run starts from the same weights
-    act = HIDDEN_MODULES[check_activation(getattr(layer_sizes, "activation", "relu"))]
-    layers = [nn.Linear(int(input_shape), int(layer_sizes[0])), act()]
+    act_cls = HIDDEN_MODULES[check_activation(getattr(layer_sizes, "activation", "relu"))]
+    normed = check_norm(getattr(layer_sizes, "norm", None)) is not None   # (ActNorm: still one parameter-free module per hidden layer)
+    act = lambda width: ActNorm(act_cls(), width) if normed else act_cls()
+    layers = [nn.Linear(int(input_shape), int(layer_sizes[0])), act(layer_sizes[0])]
     prev = int(layer_sizes[0])
     for size in layer_sizes[1:]:
         layers.append(nn.Linear(prev, int(size)))
-        layers.append(act())
+        layers.append(act(size))
         prev = int(size)
     layers.append(nn.Linear(prev, int(n_out)))
     if final_activation is not None:
@@ -382,8 +412,11 @@ class ArenaModule(nn.Module):
         self.model = self.model.to(dev)
         # (a head's parameters that are not a layer -- DiagGaussianPolicy.log_std -- ride in the arena's tail)
         self.hidden_activation = activation_of(self.model)
+        self.hidden_norm = norm_of(self.model)
+        if self.hidden_norm and max(l.out_features for l in linears_of(self.model)[:-1]) > N.NORM_MAX_WIDTH:
+            raise ValueError(f"hidden layer normalisation of a layer wider than {N.NORM_MAX_WIDTH} (RLPPO_NORM_MAX_WIDTH)")
         self.arena = NetArena(linears_of(self.model), dev, tail=getattr(self, "_arena_tail", ()),
-                              hidden_act=N.HIDDEN_ACTIVATIONS[self.hidden_activation])
+                              hidden_act=N.HIDDEN_ACTIVATIONS[self.hidden_activation] | (N.ACT_NORM if self.hidden_norm else 0))
         self.act_graphs = True  # get_action through a hipGraph per batch-size bucket (False: every call takes the general path)
         self.act_graph_max = 1024  # beyond that the explicit copies of the eager path are the better transport for the noise
         self._graphs = {}

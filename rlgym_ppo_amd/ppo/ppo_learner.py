@@ -451,6 +451,8 @@ class PPOLearner(object):
         runs = fuse_runs(slices_for_rank(max(1, n_slices), rank, world), self.max_fused_minibatches)
         self._fused_rows = self.mini_batch_size * max([cnt for _, cnt in runs] or [1])
         size_fn = N.lib().rlppo_minibatch_workspace_bytes_for if cr is None else N.lib().rlppo_minibatch_workspace_bytes_critic
+        if (pa.hidden_act | va.hidden_act) & N.ACT_NORM:   # a normalised network: the same plan + its normalised activations
+            size_fn = lambda *dims: N.lib().rlppo_minibatch_workspace_bytes_norm(*dims, int(cr is not None), pa.hidden_act, va.hidden_act)
         nbytes = int(size_fn(pa.dims_c, pa.n_layers, va.dims_c, va.n_layers, self._fused_rows, a.precision))
         nbytes = (nbytes + 255) // 256 * 256
         ws = self._ws.get(nbytes * self.n_slots)
@@ -531,6 +533,10 @@ class PPOLearner(object):
         if prec != "fp32":
             raise ValueError(f"hidden activation {sorted(acts)[0]!r} with update precision {prec!r}: the {prec} update kernels are ReLU "
                              "only -- use update_precision='fp32'")
+        # a normalised network updates in fp32 too: the bf16 and split-bf16 chains have no place for the row kernels
+        if any(getattr(m, "hidden_norm", None) for m in (self.policy, self.value_net)) and self._precision() != "fp32":
+            raise ValueError(f"hidden layer normalisation with update precision {self._precision()!r}: the {self._precision()} update kernels "
+                             "have no place for the row kernels -- use update_precision='fp32'")
         self.lr_schedule, self.desired_kl, self.lr_bounds = self._checked_schedule(self.lr_schedule, self.desired_kl, self.lr_bounds)
         if self.value_clip_range is not None and not float(self.value_clip_range) > 0:
             raise ValueError(f"value_clip_range must be > 0 or None, got {self.value_clip_range!r}")
