@@ -623,6 +623,39 @@ typedef struct rlppo_value_norm {
 int rlppo_ppo_minibatch_vnorm(void *stream, const rlppo_minibatch_args *args, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
                               const rlppo_value_norm *vnorm);
 
+/* [vbins] The categorical critic (added entry points: the structs above and the ABI version stay as they are).  The critic has n output
+ * logits over n equal bins of [vmin, vmax] (width w = (vmax - vmin) / n, edges e_i = vmin + i w, centres c_i = e_i + w / 2); its value is
+ * sum_i softmax(logits)_i c_i and it is trained by the cross-entropy -sum_i p_i log softmax(logits)_i against a histogram p of the
+ * target t clamped to [vmin, vmax]:
+ *   RLPPO_VALUE_BINS_HL_GAUSS  p_i = (Phi((e_{i+1} - t) / s) - Phi((e_i - t) / s)) / Z, s = sigma_ratio * w, Z = Phi((vmax - t) / s) - Phi((vmin - t) / s)
+ *   RLPPO_VALUE_BINS_TWO_HOT   u = clamp((t - c_0) / w, 0, n - 1), k = min(floor(u), n - 2), f = u - k: p_k = 1 - f, p_{k+1} = f
+ * Refused with RLPPO_ERR_ARG naming the field, before any HIP call: kind other than 1 / 2, n outside 2 .. RLPPO_VALUE_MAX_BINS, vmin or
+ * vmax not finite or vmin >= vmax, sigma_ratio outside (0, 2] for HL-Gauss (two-hot ignores it) -- so Z >= Phi(1) - 1/2 > 0.34.
+ *
+ * rlppo_value_bins_readout: values[r] = the value of row r of logits [n_rows][ld] (DEVICE, 16-byte aligned, ld a multiple of 8 with
+ * n <= ld <= 256: what a critic of rlppo_padded_out(n) columns puts out), contiguous.  With value normalisation the result is a
+ * normalised value, as the one-output critic's is.
+ *
+ * rlppo_ppo_minibatch_vbins: rlppo_ppo_minibatch_vnorm with such a critic.  bins == NULL is exactly that call.  Otherwise val_dims'
+ * last entry must equal bins->n, the pass takes the PLAIN form (as for tanh / ELU: two chains on gathered rows, no bitmasks, no folded
+ * or matrix-vector head, no paired launches), the critic's last layer runs the kernels that serve the policy's head, and where the
+ * one-output critic's squared-error launch stood the cross-entropy launch writes dL/dlogits = (softmax - p) * mb_ratio / mb in place
+ * (padded columns zero).  With a value scale the target is first t^ = (target - mu) * (1/sigma), as in rlppo_ppo_minibatch_vnorm, and
+ * the range is in normalised units.  RLPPO_STAT_VLOSS accumulates the mean cross-entropy.  The workspace is the one the other forms
+ * size for the same dims.  Besides the bins' own refusals: value_clip > 0 (clipping a distribution is undefined) and update precision
+ * bf16 / x3 (a plain pass is fp32) are RLPPO_ERR_ARG, before the first HIP call.  rlppo_dbg_counter(17) counts these passes. */
+#define RLPPO_VALUE_BINS_HL_GAUSS 1
+#define RLPPO_VALUE_BINS_TWO_HOT 2
+#define RLPPO_VALUE_MAX_BINS 256
+typedef struct rlppo_value_bins {
+    int32_t kind; /* 1 = HL-Gauss, 2 = two-hot */
+    int32_t n;
+    float vmin, vmax, sigma_ratio;
+} rlppo_value_bins;
+int rlppo_value_bins_readout(void *stream, const float *logits, int64_t ld, const rlppo_value_bins *bins, float *values, int64_t n_rows);
+int rlppo_ppo_minibatch_vbins(void *stream, const rlppo_minibatch_args *args, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
+                              const rlppo_value_norm *vnorm, const rlppo_value_bins *bins);
+
 /* Orders `stream` after every minibatch enqueued through non-zero slots since the last join (call it before the
  * gradient all-reduce / rlppo_clip_adam).  Independent minibatches of one batch only meet in the gradient arena
  * (one add per element and launch), so they may overlap; each launch is short (50-100 us at 65,536 rows), and overlapping
@@ -1097,7 +1130,8 @@ const int64_t *rlppo_selection_epoch_ptr(void);   /* the counter itself (a host 
  * launcher selected: 8 = rlppo_dbg_gemm_nt / layer-chain fp32 NT products by the few-row kernel, 9 = by the 128-row-tile kernel, 10 = bf16 hidden / dX product on
  * 256 x 256 tiles with one workgroup per tile, 11 = with persistent workgroups, 12 = split-bf16 product with persistent workgroups,
  * 13 = the one-output head's dW through fixed-order partials (not atomics); 15 = [critic rows] rlppo_ppo_minibatch passes with separate
- * critic rows (rlppo_ppo_minibatch_critic with a matrix); -1 for an unknown key (14 is none). */
+ * critic rows (rlppo_ppo_minibatch_critic with a matrix), 17 = [vbins] of them with a categorical critic (rlppo_ppo_minibatch_vbins with
+ * bins); -1 for an unknown key (14 and 16 are none). */
 int64_t rlppo_dbg_counter(int32_t key);
 /* Debug helper, like rlppo_dbg_counter: adds delta to counter `key` (6 only; anything else RLPPO_ERR_ARG).  The launchers count when
  * they are CALLED; a host that captures a call into a graph and replays it (rlgym_ppo_amd/ppo/_mlp.py::ActGraph, the masked
@@ -1165,6 +1199,11 @@ int rlppo_dbg_gemv_dw(void *stream, const float *dy, int64_t ldy, const float *x
 int rlppo_dbg_diag_loss(void *stream, float *y, int64_t ld, int32_t k, const float *actions, const float *old_logp, const float *advantages,
                         int64_t mb, float clip_range, float ent_coef, float mb_ratio, const float *log_std, float *log_std_grad, void *scratch,
                         size_t scratch_bytes, double *stats, int32_t part);
+/* [vbins] The categorical critic's loss launch on its own, on caller-supplied logits[mb][ld] (overwritten with dL/dlogits, rows as for
+ * rlppo_value_bins_readout) and contiguous real-unit targets[mb], as a pass has gathered them; value_scale: NULL, or the DEVICE
+ * {mu, 1/sigma, ...} of rlppo_value_norm_update; stats: the DEVICE double[RLPPO_N_STATS] a pass accumulates into. */
+int rlppo_dbg_value_bins_loss(void *stream, float *logits, int64_t ld, const rlppo_value_bins *bins, const float *targets, int64_t mb,
+                              float mb_ratio, const float *value_scale, double *stats);
 /* dW[out][in] += dY^T . X, db[out] += colsum(dY) through partial tiles in `ws` (rlppo_dbg_gemm_tn_workspace_bytes) and a
  * fixed-order reduction: the form rlppo_ppo_minibatch uses.  dY[M][ldy] is read over its first ny_valid columns and X[M][ldx] over its
  * first kx_valid (multiples of 4, out <= ny_valid <= ldy, in <= kx_valid <= ldx); nothing beyond them is read.  The padded columns

@@ -35,6 +35,9 @@ COUNTER_CRITIC_ROWS_PASS = 15  # rlppo_dbg_counter key: passes with separate cri
 HIDDEN_ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "elu": ACT_ELU}
 ACT_NORM = 0x100  # RLPPO_ACT_NORM: or-ed into an activation code = layer normalisation behind every hidden activation
 NORM_MAX_WIDTH = 2048  # RLPPO_NORM_MAX_WIDTH
+VALUE_BINS_KINDS = {"hl_gauss": 1, "two_hot": 2}  # RLPPO_VALUE_BINS_*
+VALUE_MAX_BINS = 256  # RLPPO_VALUE_MAX_BINS
+COUNTER_VBINS_PASS = 17  # rlppo_dbg_counter key: passes with a categorical critic
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -92,6 +95,11 @@ class CriticRows(ctypes.Structure):
 class ValueNormArg(ctypes.Structure):
     """struct rlppo_value_norm (include/rlppo.h, "[vnorm]")."""
     _fields_ = [("scale", c_void_p)]
+
+
+class ValueBinsArg(ctypes.Structure):
+    """struct rlppo_value_bins (include/rlppo.h, "[vbins]")."""
+    _fields_ = [("kind", c_int32), ("n", c_int32), ("vmin", c_float), ("vmax", c_float), ("sigma_ratio", c_float)]
 
 
 class Gather2Args(ctypes.Structure):
@@ -220,6 +228,9 @@ SIGNATURES = {
     "rlppo_minibatch_workspace_bytes_norm": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32]),
     "rlppo_ppo_minibatch_critic": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows)]),
     "rlppo_ppo_minibatch_vnorm": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows), POINTER(ValueNormArg)]),
+    "rlppo_value_bins_readout": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(ValueBinsArg), c_void_p, c_int64]),
+    "rlppo_ppo_minibatch_vbins": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows), POINTER(ValueNormArg),
+                                            POINTER(ValueBinsArg)]),
     "rlppo_ppo_join": (c_int32, [c_void_p]),
     "rlppo_kl_slots_doubles": (c_int64, [c_int64]),
     "rlppo_adv_stats": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
@@ -305,6 +316,7 @@ SIGNATURES = {
                                     c_size_t]),
     "rlppo_dbg_diag_loss": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_void_p,
                                       c_void_p, c_void_p, c_size_t, c_void_p, c_int32]),
+    "rlppo_dbg_value_bins_loss": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(ValueBinsArg), c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "rlppo_dbg_gemm_tn_group_workspace_bytes": (c_size_t, [POINTER(TnProduct), c_int32, c_int64]),
     "rlppo_dbg_gemm_tn_group": (c_int32, [c_void_p, POINTER(TnProduct), c_int32, c_int64, c_void_p, c_size_t]),
     "rlppo_dbg_gemm_tn_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int64]),

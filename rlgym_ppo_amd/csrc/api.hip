@@ -838,6 +838,7 @@ int64_t rlppo_dbg_counter(int32_t key) {
         case 7: return rollout_record_count();
         case 8: case 9: case 10: case 11: case 12: case 13: return g_form_launches[key - 8];
         case 15: return g_call_counts[CNT_CRITIC_ROWS_PASS];
+        case 17: return g_call_counts[CNT_VBINS_PASS];
         default: return -1;
     }
 }

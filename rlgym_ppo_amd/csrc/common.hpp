@@ -283,6 +283,17 @@ int launch_multidiscrete_sample(hipStream_t, const float *, int64_t, int64_t, co
                                 unsigned *done_words = nullptr, unsigned done_value = 0);
 int launch_value_loss(hipStream_t st, float *vout, int64_t ldv, const float *targets, const float *adv, int64_t mb, const LossCfg &cfg,
                       double *stats);
+// value_bins.hip: the categorical critic.  BinSpec: a validated rlppo_value_bins as the kernels take it, by value -- n equal bins over
+// [vmin, vmax], mid the middle of the range, hw half a bin width, inv_s_sqrt2 = 1 / (sigma_ratio * width * sqrt 2) (HL-Gauss)
+struct BinSpec {
+    int kind, n;
+    float vmin, vmax, mid, hw, inv_s_sqrt2;
+};
+int value_bins_make(const rlppo_value_bins *bins, const char *who, BinSpec *spec);  // every refusal names `who` and the field; no HIP call
+// logits [mb][ld] -> dL/dlogits in place (padded columns zero), RLPPO_STAT_VLOSS += the mean cross-entropy; targets: real-unit, [mb]
+int launch_value_bins_loss(hipStream_t st, float *logits, int64_t ld, const BinSpec &bins, const float *targets, int64_t mb, const LossCfg &cfg,
+                           double *stats);
+int launch_value_bins_readout(hipStream_t st, const float *logits, int64_t ld, const BinSpec &bins, float *values, int64_t n_rows);
 int64_t kl_slots_doubles(int64_t mb);  // rlppo_kl_slots_doubles
 constexpr int64_t DISCRETE_LOSS_MAX_LD = 64 * 32;  // padded logits per row of the widest discrete loss kernel (one wave, 32 per lane)
 // the policy loss of one head on its outputs [mb][ld], in place, from the gathered per-row actions, old log-probabilities and advantages
@@ -436,7 +447,7 @@ enum LaunchForm { FORM_NT_FEW_ROWS = 0, FORM_NT_TILED, FORM_B16_WIDE, FORM_B16_P
 extern long long g_form_launches[FORM_COUNT];
 // rlppo_dbg_counter(0 .. 6): which form a call took, counted where the call selects it (api.hip, update.hip); CNT_CRITIC_ROWS_PASS
 // (a pass with separate critic rows, rlppo_ppo_minibatch_critic) is rlppo_dbg_counter(15): keys 7 .. 13 were taken and 14 is pinned as no key
-enum CallCount { CNT_FUSED_ACT = 0, CNT_ACT_CHAIN, CNT_PASS, CNT_PAIRED_PASS, CNT_GATHER_FUSED_PASS, CNT_GROUP_DW, CNT_MD_NVEC, CNT_CRITIC_ROWS_PASS, CNT_COUNT };
+enum CallCount { CNT_FUSED_ACT = 0, CNT_ACT_CHAIN, CNT_PASS, CNT_PAIRED_PASS, CNT_GATHER_FUSED_PASS, CNT_GROUP_DW, CNT_MD_NVEC, CNT_CRITIC_ROWS_PASS, CNT_VBINS_PASS, CNT_COUNT };  // (CNT_VBINS_PASS: rlppo_dbg_counter(17), passes with a categorical critic; 16, like 14, is pinned as no key)
 extern std::atomic<long long> g_call_counts[CNT_COUNT];
 // update.hip: the switches of the PPO pass (rlppo_dbg_set 4 / 19 / 26 / 29 / 31 / 37, rlppo_set_update_precision)
 void set_two_streams(int v), set_relu_bits(int v), set_fused_gather(int v), set_paired(int v), set_head_order(int v), set_group_dw(int v);

@@ -239,6 +239,8 @@ struct Pass {
     int pol_act = ACT_RELU, val_act = ACT_RELU;
     int pol_norm = 0, val_norm = 0;  // [norm] layer normalisation behind every hidden activation of the network: a plain pass too
     bool plain = false;
+    bool has_bins = false;  // [vbins] a categorical critic (rlppo_ppo_minibatch_vbins): a plain pass whose critic ends in `bins.n` logits
+    BinSpec bins;
 };
 
 // One network's chain of a pass: the policy's on p.st, the critic's on p.side.  Only the critic's one-output head may be folded
@@ -464,7 +466,8 @@ static int two_chain_pass(const Pass &p) {
     // do not meet until the end of the minibatch.
     const int vlast = p.val.n_layers - 1;
     const int64_t ldv = val.head_folded ? 1 : p.val.L[vlast].pout;  // (a folded head's outputs are compact)
-    int rc = launch_value_loss(p.side, p.w.val.act[vlast], ldv, p.w.g_tgt, p.w.g_adv, p.mb, p.cfg, p.a->stats);
+    int rc = p.has_bins ? launch_value_bins_loss(p.side, p.w.val.act[vlast], p.val.L[vlast].pout, p.bins, p.w.g_tgt, p.mb, p.cfg, p.a->stats)
+                        : launch_value_loss(p.side, p.w.val.act[vlast], ldv, p.w.g_tgt, p.w.g_adv, p.mb, p.cfg, p.a->stats);
     if (rc) return rc;
     rc = policy_loss(p.st, p);
     if (rc) return rc;
@@ -482,6 +485,7 @@ struct PassOpts {
     int pol_act = ACT_RELU, val_act = ACT_RELU;  // [act] the hidden activations, [norm] each with or without RLPPO_ACT_NORM
     const rlppo_critic_rows *critic = nullptr;   // [critic rows] the critic's own row matrix: non-null only with critic->states set
     const float *vnorm = nullptr;                // [vnorm] the value statistic's scale
+    const rlppo_value_bins *bins = nullptr;      // [vbins] the categorical critic's bins
 };
 
 static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const PassOpts &o) {
@@ -513,11 +517,23 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
                     "no place for the row kernels (use fp32)", p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
     RLPPO_CHECK_ARG((!p.pol_norm || norm_width_ok(pol)) && (!p.val_norm || norm_width_ok(val)),
                     "ppo_minibatch: hidden layer normalisation of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded)", RLPPO_NORM_MAX_WIDTH);
-    p.plain = non_relu || normed || (p.prec == 0 && !g_relu_bits);
+    // [vbins] a categorical critic: its bins, and an fp32 pass in the plain form (no folded head, no matrix-vector head: an ordinary last layer)
+    if (o.bins) {
+        rc = value_bins_make(o.bins, "ppo_minibatch_vbins", &p.bins);
+        if (rc) return rc;
+        p.has_bins = true;
+        RLPPO_CHECK_ARG(p.prec == 0, "ppo_minibatch_vbins: a categorical critic (bins) with update precision %s: the %s kernels are ReLU only (use fp32)",
+                        p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
+        RLPPO_CHECK_ARG(!(a->value_clip > 0.f), "ppo_minibatch_vbins: value_clip=%g with a categorical critic (bins): clipping a distribution is undefined",
+                        (double)a->value_clip);
+    }
+    p.plain = non_relu || normed || p.has_bins || (p.prec == 0 && !g_relu_bits);
     RLPPO_CHECK_ARG(mb > 0 && a->pol_packed && a->val_packed && a->pol_grad && a->val_grad && a->states && a->actions &&
                         a->old_logp && a->targets && a->advantages && a->idx && a->stats && a->workspace,
                     "ppo_minibatch: null pointer");
-    RLPPO_CHECK_ARG(val.L[val.n_layers - 1].out == 1, "ppo_minibatch: critic must have one output");
+    RLPPO_CHECK_ARG(p.has_bins || val.L[val.n_layers - 1].out == 1, "ppo_minibatch: critic must have one output");
+    RLPPO_CHECK_ARG(!p.has_bins || val.L[val.n_layers - 1].out == p.bins.n, "ppo_minibatch_vbins: bins n=%d, but the critic has %d outputs (val_dims[val_layers])",
+                    p.bins.n, val.L[val.n_layers - 1].out);
     RLPPO_CHECK_ARG(a->value_clip >= 0.f && a->value_clip < INFINITY, "ppo_minibatch: value_clip=%g", (double)a->value_clip);
     RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(o.vnorm) & 15) == 0, "ppo_minibatch_vnorm: vnorm scale must be 16-byte aligned");
     RLPPO_CHECK_ARG(critic || pol.L[0].in == val.L[0].in, "ppo_minibatch: policy and critic observe different sizes");
@@ -631,6 +647,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
     if (twin) ++g_call_counts[CNT_PAIRED_PASS];
     if (p.rows[0].rowtab) ++g_call_counts[CNT_GATHER_FUSED_PASS];
     if (critic) ++g_call_counts[CNT_CRITIC_ROWS_PASS];
+    if (p.has_bins) ++g_call_counts[CNT_VBINS_PASS];
     rc = twin ? paired_pass(p, bk, slot) : two_chain_pass(p);
     if (rc) return rc;
     if (!twin && p.side != p.st) {  // (the paired pass has joined already)
@@ -651,14 +668,14 @@ static bool scratch_aligned(const void *scratch) { return (reinterpret_cast<uint
 // The optional parts of rlppo_ppo_minibatch_ex / _critic / _vnorm, decoded once: a NULL ext is the zeroed one, a critic struct without states
 // and a value norm without a scale are absent.  The call is named after the last part it brings, whichever of the three forms it came through.
 static int ppo_minibatch_opts(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
-                              const rlppo_value_norm *vnorm) {
+                              const rlppo_value_norm *vnorm, const rlppo_value_bins *bins = nullptr) {
     const rlppo_minibatch_ext none = {};
     if (!ext) ext = &none;
     const bool has_diag = ext->log_std || ext->log_std_grad || ext->scratch || ext->scratch_bytes;
     const PassOpts o{ext->md_nvec, ext->md_heads, diag_head(ext->log_std, ext->log_std_grad, ext->scratch, ext->scratch_bytes), has_diag,
-                     ext->pol_hidden_act, ext->val_hidden_act, critic && critic->states ? critic : nullptr, vnorm ? vnorm->scale : nullptr};
+                     ext->pol_hidden_act, ext->val_hidden_act, critic && critic->states ? critic : nullptr, vnorm ? vnorm->scale : nullptr, bins};
     RLPPO_CHECK_ARG(scratch_aligned(ext->scratch), "%s: scratch must be 8-byte aligned",
-                    o.vnorm ? "ppo_minibatch_vnorm" : o.critic ? "ppo_minibatch_critic" : "ppo_minibatch_ex");
+                    bins ? "ppo_minibatch_vbins" : o.vnorm ? "ppo_minibatch_vnorm" : o.critic ? "ppo_minibatch_critic" : "ppo_minibatch_ex");
     return ppo_minibatch(stream, a, o);
 }
 
@@ -715,6 +732,11 @@ int rlppo_ppo_minibatch_critic(void *stream, const rlppo_minibatch_args *a, cons
 int rlppo_ppo_minibatch_vnorm(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
                               const rlppo_value_norm *vnorm) {
     return ppo_minibatch_opts(stream, a, ext, critic, vnorm);
+}
+// [vbins] the same call with a categorical critic; no bins: rlppo_ppo_minibatch_vnorm
+int rlppo_ppo_minibatch_vbins(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
+                              const rlppo_value_norm *vnorm, const rlppo_value_bins *bins) {
+    return ppo_minibatch_opts(stream, a, ext, critic, vnorm, bins);
 }
 
 size_t rlppo_diag_scratch_bytes(int64_t mb, int32_t k) { return diag_scratch_bytes(mb, k); }

@@ -47,6 +47,7 @@ class Learner(object):
             ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
             critic_observations: bool = False,
             ppo_normalize_value: bool = False, ppo_value_norm_popart: bool = False,
+            ppo_value_head: str = "scalar", ppo_value_bins: int = 101, ppo_value_range=(-10.0, 10.0), ppo_value_sigma_ratio: float = 0.75,
             per_feature_obs_standardization: bool = False,
             ppo_normalize_advantages: bool = False, ppo_value_clip_range=None, ppo_target_kl=None, ppo_max_grad_norm: float = 0.5):
         assert env_create_function is not None, "MUST PROVIDE A FUNCTION TO CREATE RLGYM FUNCTIONS TO INITIALIZE RLGYM-PPO"
@@ -105,10 +106,43 @@ class Learner(object):
             own_norm = getattr(sizes, "norm", None)
             if own_norm is not None and asked is None and hidden_layer_norm:
                 raise ValueError(f"{name} is LayerSizes(..., norm={own_norm!r}) but hidden_layer_norm={hidden_layer_norm!r}: give one of them")
-            return LayerSizes(sizes, own if own is not None else hidden_activation, own_norm or asked)
+            return LayerSizes(sizes, own if own is not None else hidden_activation, own_norm or asked, getattr(sizes, "value_head", None))
         sizes_given = (policy_layer_sizes, critic_layer_sizes)   # (what the config dict logs, as it always did)
         policy_layer_sizes = with_activation("policy_layer_sizes", policy_layer_sizes)
         critic_layer_sizes = with_activation("critic_layer_sizes", critic_layer_sizes)
+        # not in the reference (whose critic has one output and a squared error): ppo_value_head = "hl_gauss" | "two_hot" is the critic
+        # trained by classification (ppo.ValueBins) -- ppo_value_bins logits over equal bins of ppo_value_range, a
+        # cross-entropy against the target's histogram, the value their expectation.  It travels inside the critic's layer sizes like the
+        # activation; sizes that already carry a value_head keep it while ppo_value_head is left at "scalar".  With ppo_normalize_value
+        # the range is in normalised units (-10 .. 10 is then a sensible default), without it in real value units.  Refused here,
+        # before anything is built or spawned: ppo_value_clip_range, ppo_value_norm_popart and update precisions bf16 / x3 beside it.
+        # "scalar" is the library as it was, launch for launch.  self.value_head says what was built (None: one output).
+        from .ppo._mlp import ValueBins
+        if ppo_value_head not in ("scalar", "hl_gauss", "two_hot"):
+            raise ValueError(f"ppo_value_head must be 'scalar', 'hl_gauss' or 'two_hot', got {ppo_value_head!r}")
+        if policy_layer_sizes.value_head is not None:
+            raise ValueError(f"policy_layer_sizes is LayerSizes(..., value_head={policy_layer_sizes.value_head!r}): the categorical head is "
+                             "the critic's (critic_layer_sizes)")
+        if ppo_value_head != "scalar":
+            if critic_layer_sizes.value_head is not None:
+                raise ValueError(f"critic_layer_sizes is LayerSizes(..., value_head=...) but ppo_value_head={ppo_value_head!r}: give one of them")
+            bins = ValueBins(ppo_value_bins, ppo_value_range, ppo_value_head, ppo_value_sigma_ratio)
+            critic_layer_sizes = LayerSizes(critic_layer_sizes, critic_layer_sizes.activation, critic_layer_sizes.norm, bins)
+            if not ppo_normalize_value and tuple(ppo_value_range) == (-10.0, 10.0):
+                warnings.warn(f"ppo_value_head={ppo_value_head!r} without ppo_normalize_value: ppo_value_range is in real value units and was "
+                              "left at its default (-10, 10) -- value targets outside it are clamped", RuntimeWarning, stacklevel=2)
+        self.value_head = critic_layer_sizes.value_head
+        if self.value_head is not None:
+            from . import engine
+            if ppo_value_clip_range is not None:
+                raise ValueError(f"ppo_value_clip_range={ppo_value_clip_range!r} with a categorical value head (ppo_value_head / value_head): "
+                                 "clipping a distribution is undefined")
+            if ppo_value_norm_popart:
+                raise ValueError("ppo_value_norm_popart=True with a categorical value head (ppo_value_head / value_head): rescaling a last "
+                                 "layer of logits preserves nothing")
+            if engine.update_precision() != "fp32":
+                raise ValueError(f"ppo_value_head with update precision {engine.update_precision()!r}: the {engine.update_precision()} update "
+                                 "kernels are ReLU only -- use engine.set_update_precision('fp32')")
         self.hidden_norms = {"policy": policy_layer_sizes.norm, "critic": critic_layer_sizes.norm}
         if any(self.hidden_norms.values()):
             from . import engine

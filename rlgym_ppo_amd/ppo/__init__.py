@@ -1,4 +1,4 @@
-from ._mlp import LayerSizes
+from ._mlp import LayerSizes, ValueBins
 from .continuous_policy import ContinuousPolicy
 from .diag_gaussian_policy import DiagGaussianPolicy
 from .multi_discrete_policy import MultiDiscreteFF

@@ -6,6 +6,7 @@ multi_discrete_policy.py:22-32, value_estimator.py:18-28): layers are built on t
 starts from the reference's weights bit for bit) and only then moved to the GPU arena.
 """
 import ctypes
+import gc
 import math
 import os
 
@@ -35,23 +36,71 @@ def check_norm(norm):
     return norm
 
 
+class ValueBins:
+    """The head of a categorical critic (include/rlppo.h, "[vbins]"): n logits over n equal bins of value_range, trained by
+    cross-entropy against an "hl_gauss" histogram (a Gaussian of sigma_ratio bin widths around the value target, integrated over each
+    bin) or a "two_hot" one (the mass split between the two neighbouring bin centres); the value is the expectation over the bin
+    centres.  A validated record: it travels as LayerSizes(..., value_head=bins) on the critic's layer sizes."""
+
+    __slots__ = ("n", "value_range", "kind", "sigma_ratio")
+
+    def __init__(self, n=101, value_range=(-10.0, 10.0), kind="hl_gauss", sigma_ratio=0.75):
+        if isinstance(n, bool) or int(n) != n or not 2 <= int(n) <= N.VALUE_MAX_BINS:
+            raise ValueError(f"ValueBins: n must be an integer in 2 .. {N.VALUE_MAX_BINS}, got {n!r}")
+        if kind not in N.VALUE_BINS_KINDS:
+            raise ValueError(f"ValueBins: kind must be one of {sorted(N.VALUE_BINS_KINDS)}, got {kind!r}")
+        try:
+            lo, hi = (float(v) for v in value_range)
+        except (TypeError, ValueError):
+            raise ValueError(f"ValueBins: value_range must be a pair (vmin, vmax), got {value_range!r}") from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+            raise ValueError(f"ValueBins: value_range must be finite with vmin < vmax, got {value_range!r}")
+        if not 0.0 < float(sigma_ratio) <= 2.0:
+            raise ValueError(f"ValueBins: sigma_ratio must be in (0, 2], got {sigma_ratio!r}")
+        self.n, self.value_range, self.kind, self.sigma_ratio = int(n), (lo, hi), kind, float(sigma_ratio)
+
+    def _key(self):
+        return (self.n, self.value_range, self.kind, self.sigma_ratio)
+
+    def __eq__(self, other):
+        return isinstance(other, ValueBins) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __reduce__(self):
+        return (ValueBins, self._key())
+
+    def __repr__(self):
+        return f"ValueBins(n={self.n}, value_range={self.value_range!r}, kind={self.kind!r}, sigma_ratio={self.sigma_ratio!r})"
+
+    def c_arg(self):
+        """The struct rlppo_value_bins of these bins."""
+        return N.ValueBinsArg(N.VALUE_BINS_KINDS[self.kind], self.n, self.value_range[0], self.value_range[1], self.sigma_ratio)
+
+
 class LayerSizes(tuple):
     """Hidden layer sizes that carry the hidden activation ("relu", "tanh" or "elu", alpha = 1) of the network built from them -- the
     activation travels in an argument every constructor already has, the way multi-discrete bins travel in act_space_size.  A tuple
     in every other respect (tuple(x) gives the plain sizes back); a plain tuple means "relu".
-    norm: None, or "layer" -- layer normalisation without learnable parameters behind every hidden activation (ActNorm)."""
+    norm: None, or "layer" -- layer normalisation without learnable parameters behind every hidden activation (ActNorm).
+    value_head: None, or the ValueBins of a categorical critic (the critic's sizes only: a policy refuses one)."""
 
-    def __new__(cls, sizes, activation="relu", norm=None):
+    def __new__(cls, sizes, activation="relu", norm=None, value_head=None):
         self = super().__new__(cls, tuple(sizes))
         self.activation = check_activation(activation)
         self.norm = check_norm(norm)
+        if value_head is not None and not isinstance(value_head, ValueBins):
+            raise ValueError(f"value_head must be None or a ValueBins, got {value_head!r}")
+        self.value_head = value_head
         return self
 
     def __reduce__(self):
-        return (LayerSizes, (tuple(self), self.activation, self.norm))
+        return (LayerSizes, (tuple(self), self.activation, self.norm, self.value_head))
 
     def __repr__(self):
-        return f"LayerSizes({tuple(self)!r}, {self.activation!r}" + (f", norm={self.norm!r})" if self.norm else ")")
+        tail = (f", norm={self.norm!r}" if self.norm else "") + (f", value_head={self.value_head!r}" if self.value_head else "")
+        return f"LayerSizes({tuple(self)!r}, {self.activation!r}{tail})"
 
 
 class ActNorm(nn.Module):
@@ -81,8 +130,11 @@ def norm_of(module):
     return "layer" if isinstance(module[1], ActNorm) else None
 
 
-def build_body(input_shape, layer_sizes, n_out, final_activation=None):
+def build_body(input_shape, layer_sizes, n_out, final_activation=None, critic=False):
     assert len(layer_sizes) != 0, "AT LEAST ONE LAYER MUST BE SPECIFIED TO BUILD THE NEURAL NETWORK!"
+    if getattr(layer_sizes, "value_head", None) is not None and not critic:   # (ValueEstimator alone builds with critic=True)
+        raise ValueError(f"value_head={layer_sizes.value_head!r} on a policy's layer sizes: the categorical head is the critic's "
+                         "(critic_layer_sizes)")
     # the activation modules have no parameters and draw nothing: whichever is chosen, the Sequential's indices, its state_dict keys
     # and the CPU generator's consumption are the same, so a seeded run starts from the same weights
     act_cls = HIDDEN_MODULES[check_activation(getattr(layer_sizes, "activation", "relu"))]
@@ -238,8 +290,17 @@ class ActGraph:
         side.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         # thread_local: the shuffle pipeline's helper threads may be issuing copies / events on their own stream right now
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            body()
+        # No cyclic collection inside the capture: one that starts at an allocation of body() may finalise a dead cycle's device objects
+        # (an earlier learner's policy with its ActGraphs and their hipGraphs), which is illegal on a capturing thread and ends the
+        # process (torch.cuda.graph no longer collects before it captures).  The collector is off for these few launches.
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                body()
+        finally:
+            if gc_was_on:
+                gc.enable()
         # Counter 6 of rlppo_dbg_counter (runs of the multi-discrete head's general kernels) is kept by the launchers when they are
         # CALLED, and a replay calls none.  The masked chain's body calls the general sampling launcher exactly once: the warm-up's and
         # the capture's counts are taken off again here and run() adds one per call, so that a masked small call counts as one run,

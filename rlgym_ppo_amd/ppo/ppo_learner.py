@@ -479,7 +479,11 @@ class PPOLearner(object):
             scratch, e.scratch_bytes = self._diag_scratch.data_ptr(), self._diag_scratch_bytes
         elif self.policy_type == 1 and (self.policy.md_nvec is not None or args.action_mask):
             e.md_nvec, e.md_heads = ctypes.cast(self.policy._nvec_c, ctypes.POINTER(ctypes.c_int32)), self.policy.n_heads
-        if vn is not None:      # the value loss reads the targets through the statistic's scale
+        if self.value_net.value_bins is not None:   # a categorical critic: the widest form + its bins (the statistic's scale, if any, rides along)
+            self._bins_arg = self.value_net.value_bins.c_arg()
+            fn, tail = L.rlppo_ppo_minibatch_vbins, (ctypes.byref(e), None if crit is None else ctypes.byref(crit),
+                                                     None if vn is None else ctypes.byref(vn.arg), ctypes.byref(self._bins_arg))
+        elif vn is not None:    # the value loss reads the targets through the statistic's scale
             fn, tail = L.rlppo_ppo_minibatch_vnorm, (ctypes.byref(e), None if crit is None else ctypes.byref(crit), ctypes.byref(vn.arg))
         elif crit is not None:  # the buffer holds critic_states: the critic reads its own matrix
             fn, tail = L.rlppo_ppo_minibatch_critic, (ctypes.byref(e), ctypes.byref(crit))
@@ -537,6 +541,18 @@ class PPOLearner(object):
         if any(getattr(m, "hidden_norm", None) for m in (self.policy, self.value_net)) and self._precision() != "fp32":
             raise ValueError(f"hidden layer normalisation with update precision {self._precision()!r}: the {self._precision()} update kernels "
                              "have no place for the row kernels -- use update_precision='fp32'")
+        # a categorical critic (LayerSizes(..., value_head=ValueBins)) updates in fp32 (its pass is the plain form), has nothing to clip
+        # and no last layer whose rescaling would preserve its outputs
+        if getattr(self.value_net, "value_bins", None) is not None:
+            if self._precision() != "fp32":
+                raise ValueError(f"a categorical critic (value_head) with update precision {self._precision()!r}: the {self._precision()} update "
+                                 "kernels are ReLU only -- use update_precision='fp32'")
+            if self.value_clip_range is not None:
+                raise ValueError(f"value_clip_range={self.value_clip_range!r} with a categorical critic (value_head): clipping a distribution "
+                                 "is undefined")
+            if self.value_norm_preserve_outputs:
+                raise ValueError("value normalisation with preserve_outputs=True (ppo_value_norm_popart) and a categorical critic (value_head): "
+                                 "rescaling a last layer of logits preserves nothing")
         self.lr_schedule, self.desired_kl, self.lr_bounds = self._checked_schedule(self.lr_schedule, self.desired_kl, self.lr_bounds)
         if self.value_clip_range is not None and not float(self.value_clip_range) > 0:
             raise ValueError(f"value_clip_range must be > 0 or None, got {self.value_clip_range!r}")
