@@ -231,6 +231,23 @@ typedef struct rlppo_act_opts {
  * A pass's workspace is rlppo_minibatch_workspace_bytes_norm; one sized by the other functions is RLPPO_ERR_WORKSPACE. */
 #define RLPPO_ACT_NORM 0x100
 #define RLPPO_NORM_MAX_WIDTH 2048
+/* [res] Residual hidden layers: RLPPO_ACT_RES or-ed into the same fields (with or without RLPPO_ACT_NORM: 0x200 .. 0x202 and 0x300 .. 0x302
+ * are valid besides) adds a skip stream over the hidden layers 0 .. H-1 of that network, the pre-LayerNorm residual with one-Linear blocks:
+ *     a_0 = f(W_0 x + b_0)          s_0 = a_0               u_0 = N(s_0)      (layer 0 embeds the observation: no skip)
+ *     a_l = f(W_l u_(l-1) + b_l)    s_l = s_(l-1) + a_l     u_l = N(s_l)      (1 <= l < H)
+ *     out = W_out u_(H-1) + b_out
+ * N is the normalisation above with RLPPO_ACT_NORM and the identity without it (then s_l = s_(l-1) + f(W_l s_(l-1) + b_l)); the stream s is
+ * never normalised.  No parameter, weight image, optimiser state or checkpoint key changes; without the bit a call is the one it was, launch
+ * for launch, and with H = 1 the bit changes nothing (the results are those of the call without it, bit for bit).  With it every GEMM keeps
+ * its kernel and its epilogue; rlppo_row_res_fwd follows the GEMM of every hidden layer l >= 1, an update pass takes the PLAIN form, keeps a_l
+ * and s_l (and u_l under a norm), stores the dX product of the layer above plain and finishes a hidden layer's backward with ONE
+ * rlppo_row_res_bwd.  Refused with RLPPO_ERR_ARG before the first HIP call, each by name: update precisions bf16 and x3, the bf16 inference
+ * precision, a hidden layer whose padded width exceeds RLPPO_NORM_MAX_WIDTH (with or without the norm: a row of the stream lives in
+ * registers), and hidden widths that are not all equal (the message names the first layer that differs).
+ * rlppo_discrete_step_one_launch answers 0.  The bare forward of such a network is rlppo_mlp_forward_res.  Workspaces: rlppo_minibatch_workspace_bytes_res for a pass, rlppo_forward_workspace_bytes_act /
+ * rlppo_discrete_step_workspace_bytes_act for the rollout entry points (inference keeps the stream in one buffer, the GEMM outputs in a
+ * second and, under a norm, the normalised stream in a third); one sized by the other functions is RLPPO_ERR_WORKSPACE where it is too small. */
+#define RLPPO_ACT_RES 0x200
 #ifdef __cplusplus
 static_assert(sizeof(rlppo_act_opts) == 40 && offsetof(rlppo_act_opts, hidden_act) == 36, "rlppo_act_opts: hidden_act lives in the former tail padding");
 #else
@@ -267,12 +284,21 @@ int rlppo_host_stage_rows(uint32_t *ctl, uint32_t sequence, uint32_t live_rows, 
 
 /* Bytes of workspace needed by the forward entry points for `n` rows. */
 size_t rlppo_forward_workspace_bytes(const int32_t *dims, int32_t n_layers, int64_t n);
+/* [res] ... of a call whose rlppo_act_opts carry `hidden_act` (equal to the function above unless the field carries RLPPO_ACT_RES and
+ * RLPPO_ACT_NORM on a network of two hidden layers or more); a bad field gives 0. */
+size_t rlppo_forward_workspace_bytes_act(const int32_t *dims, int32_t n_layers, int64_t n, int32_t hidden_act);
 
 /* MLP forward: out[n][ld_out] = Linear_L(relu(...relu(Linear_0(obs)))) (+ tanh if out_tanh).
  * Replaces nn.Sequential.forward of value_estimator.py:30-36 / the body of *_policy.get_output. */
 int rlppo_mlp_forward(void *stream, const int32_t *dims, int32_t n_layers, const float *packed,
                       const float *obs, int64_t ld_obs, int64_t n, int32_t out_tanh,
                       float *out, int64_t ld_out, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts);
+/* [res] The same forward for options that may carry RLPPO_ACT_RES (workspace: rlppo_forward_workspace_bytes_act).  rlppo_mlp_forward keeps
+ * the contract it had: its workspace is the two buffers of rlppo_forward_workspace_bytes and it answers hidden_act values from 0x200 on with
+ * RLPPO_ERR_ARG as before (the text now names this function); without the bit the two functions are one. */
+int rlppo_mlp_forward_res(void *stream, const int32_t *dims, int32_t n_layers, const float *packed,
+                          const float *obs, int64_t ld_obs, int64_t n, int32_t out_tanh,
+                          float *out, int64_t ld_out, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts);
 
 /* DiscreteFF.get_action (discrete_policy.py:44-62): forward, softmax, clamp(1e-11,1), action =
  * argmax_a(p_a / q_a) with the caller's Exp(1) noise q[n][n_actions] (== torch.multinomial(p,1,True), SURVEY
@@ -292,6 +318,7 @@ int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, cons
  * (optional: the padded, standardised rows [n][ld_rows_out] -- the policy-input rows a device-resident rollout stores).
  * workspace: rlppo_discrete_step_workspace_bytes(dims, n_layers, n). */
 size_t rlppo_discrete_step_workspace_bytes(const int32_t *dims, int32_t n_layers, int64_t n);
+size_t rlppo_discrete_step_workspace_bytes_act(const int32_t *dims, int32_t n_layers, int64_t n, int32_t hidden_act); /* [res] as above */
 /* 1: rlppo_discrete_step(dims, n rows, opts) runs as the one-launch kernel under the current switches; 0: as the chain; -1: bad argument */
 int rlppo_discrete_step_one_launch(const int32_t *dims, int32_t n_layers, int64_t n, const rlppo_act_opts *opts);
 int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const void *obs, int32_t obs_is_f64,
@@ -587,6 +614,12 @@ int rlppo_ppo_minibatch_ex(void *stream, const rlppo_minibatch_args *args, const
  * per hidden layer and one row of zeros.  Without the bit in either field it equals those functions; a bad field gives 0. */
 size_t rlppo_minibatch_workspace_bytes_norm(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
                                             int64_t mb, int32_t precision, int32_t critic_rows, int32_t pol_hidden_act, int32_t val_hidden_act);
+/* [res] The workspace of a pass whose ext may also carry RLPPO_ACT_RES: the plan of _norm, followed per residual network (two hidden layers
+ * or more) by its zero row (if it has none yet), one [mb][padded width] stream matrix per hidden layer but the first (s_0 is the saved
+ * activation of layer 0) and two matrices of the stream's gradient that alternate.  Without RLPPO_ACT_RES it equals _norm, which keeps
+ * answering 0 for a field that carries the bit. */
+size_t rlppo_minibatch_workspace_bytes_res(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
+                                           int64_t mb, int32_t precision, int32_t critic_rows, int32_t pol_hidden_act, int32_t val_hidden_act);
 
 /* [critic rows] The same pass with a critic that reads a row matrix of its own (asymmetric actor-critic: "privileged observations";
  * an added entry point: the structs and the ABI version stay as they are).  critic->states: DEVICE, 16-byte aligned, [N][ld_states]
@@ -980,6 +1013,17 @@ int rlppo_gather_rows2(void *stream, const rlppo_gather2_args *args);
 int rlppo_row_norm_fwd(void *stream, const float *h, int64_t ld, int64_t n, int32_t width, float *y, int64_t ld_y);
 int rlppo_row_norm_bwd(void *stream, const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int32_t width, int32_t act,
                        float *dx, int64_t ld_dx);
+/* [res] The two row kernels of the residual stream on their own (csrc/residual.hip): the same design, contract and limits as the two above.
+ *   fwd: s[r][c] = s_prev[r][c] + a[r][c] for c < width, exact 0 for width <= c < P; s may be s_prev.  norm != 0: also u = the forward above
+ *        of s (u must then be given; else it is ignored and may be NULL).  Two reads and one or two writes of the matrix.
+ *   bwd: the whole non-GEMM part of a hidden layer's backward.  a: the saved activation output; s: the saved stream (read with norm != 0
+ *        only, its statistics recomputed); p = dL/du, the plain dX product of the layer above; g_next = dL/ds of the layer above, or NULL.
+ *        g = (norm ? the normalisation's backward of p at s : p) + g_next, stored unless g is NULL; dz = g * f'(a), f' of activation `act`
+ *        from its saved output as above.  Padded columns of g and dz are exact 0.  dz may be p. */
+int rlppo_row_res_fwd(void *stream, const float *s_prev, int64_t ld_sp, const float *a, int64_t ld_a, int64_t n, int32_t width, int32_t norm, float *s,
+                      int64_t ld_s, float *u, int64_t ld_u);
+int rlppo_row_res_bwd(void *stream, const float *a, int64_t ld_a, const float *s, int64_t ld_s, const float *p, int64_t ld_p, const float *g_next,
+                      int64_t ld_gn, int64_t n, int32_t width, int32_t act, int32_t norm, float *g, int64_t ld_g, float *dz, int64_t ld_dz);
 
 /* WelfordRunningStat.increment(samples, n) (running_stats.py:28-46) on the device, bit-exact with the reference's sample-by-
  * sample update: mean[d], m2[d] (= running_mean, running_variance) are updated in place with the n rows of `samples` (fp32,

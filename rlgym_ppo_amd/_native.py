@@ -35,6 +35,7 @@ COUNTER_CRITIC_ROWS_PASS = 15  # rlppo_dbg_counter key: passes with separate cri
 HIDDEN_ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "elu": ACT_ELU}
 ACT_NORM = 0x100  # RLPPO_ACT_NORM: or-ed into an activation code = layer normalisation behind every hidden activation
 NORM_MAX_WIDTH = 2048  # RLPPO_NORM_MAX_WIDTH
+ACT_RES = 0x200  # RLPPO_ACT_RES: or-ed into an activation code = a skip stream over the hidden layers (residual hidden layers)
 VALUE_BINS_KINDS = {"hl_gauss": 1, "two_hot": 2}  # RLPPO_VALUE_BINS_*
 VALUE_MAX_BINS = 256  # RLPPO_VALUE_MAX_BINS
 COUNTER_VBINS_PASS = 17  # rlppo_dbg_counter key: passes with a categorical critic
@@ -178,11 +179,15 @@ SIGNATURES = {
     "rlppo_pad_rows_per_feature": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
                                              c_void_p]),
     "rlppo_forward_workspace_bytes": (c_size_t, [_P32, c_int32, c_int64]),
+    "rlppo_forward_workspace_bytes_act": (c_size_t, [_P32, c_int32, c_int64, c_int32]),
     "rlppo_mlp_forward": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
+                                    c_int64, c_void_p, c_size_t, _PACT]),
+    "rlppo_mlp_forward_res": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
                                     c_int64, c_void_p, c_size_t, _PACT]),
     "rlppo_discrete_act": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
     "rlppo_discrete_step_workspace_bytes": (c_size_t, [_P32, c_int32, c_int64]),
+    "rlppo_discrete_step_workspace_bytes_act": (c_size_t, [_P32, c_int32, c_int64, c_int32]),
     "rlppo_discrete_step": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int32, c_float, c_float,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, _PACT]),
     "rlppo_discrete_probs": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
@@ -226,6 +231,7 @@ SIGNATURES = {
     "rlppo_ppo_minibatch_ex": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt)]),
     "rlppo_minibatch_workspace_bytes_critic": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
     "rlppo_minibatch_workspace_bytes_norm": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "rlppo_minibatch_workspace_bytes_res": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32]),
     "rlppo_ppo_minibatch_critic": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows)]),
     "rlppo_ppo_minibatch_vnorm": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows), POINTER(ValueNormArg)]),
     "rlppo_value_bins_readout": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(ValueBinsArg), c_void_p, c_int64]),
@@ -276,6 +282,9 @@ SIGNATURES = {
     "rlppo_gather_rows2": (c_int32, [c_void_p, POINTER(Gather2Args)]),
     "rlppo_row_norm_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64]),
     "rlppo_row_norm_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64]),
+    "rlppo_row_res_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64]),
+    "rlppo_row_res_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                    c_int32, c_void_p, c_int64, c_void_p, c_int64]),
     "rlppo_welford_increment": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32]),
     "rlppo_welford_merge": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32]),
     "rlppo_rollout_record": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p,

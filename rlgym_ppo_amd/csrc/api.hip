@@ -97,6 +97,7 @@ struct ActCtx {
     int mask_words = 0;
     int hidden_act = ACT_RELU;       // [act] rlppo_act_opts.hidden_act ...
     int hidden_norm = 0;             // [norm] ... and its RLPPO_ACT_NORM bit
+    int hidden_res = 0;              // [res] ... and its RLPPO_ACT_RES bit, where the network has a skip at all (two hidden layers or more)
 };
 // One call of a rollout entry point: the network, the call's options and, once act_chain has run, the last layer's output
 struct ActCall {
@@ -115,7 +116,8 @@ static int act_open(ActCall *call, const int32_t *dims, int32_t n_layers, const 
     RLPPO_CHECK_ARG(o->precision == RLPPO_PRECISION_DEFAULT || o->precision == RLPPO_PRECISION_FP32 || o->precision == RLPPO_PRECISION_BF16,
                     "act options: inference precision %d (0 = process default, 1 = fp32, 2 = bf16 operands)", o->precision);
     if (o->precision != RLPPO_PRECISION_DEFAULT) c->bf16 = o->precision == RLPPO_PRECISION_BF16;
-    RLPPO_CHECK_ARG(hidden_act_split(o->hidden_act, &c->hidden_act, &c->hidden_norm), "act options: hidden_act %d (0 = ReLU, 1 = tanh, 2 = ELU)", o->hidden_act);
+    int res = 0;
+    RLPPO_CHECK_ARG(hidden_act_split(o->hidden_act, &c->hidden_act, &c->hidden_norm, &res), "act options: hidden_act %d (0 = ReLU, 1 = tanh, 2 = ELU)", o->hidden_act);
     RLPPO_CHECK_ARG(!(c->bf16 && c->hidden_act != ACT_RELU),
                     "act options: hidden activation %s with the bf16 inference precision: the bf16-operand kernels are ReLU only",
                     hidden_act_name(c->hidden_act));
@@ -123,6 +125,11 @@ static int act_open(ActCall *call, const int32_t *dims, int32_t n_layers, const 
                     "bf16-operand kernels feed the next product without the row kernel");
     RLPPO_CHECK_ARG(!c->hidden_norm || norm_width_ok(call->net), "act options: hidden layer normalisation of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded)",
                     RLPPO_NORM_MAX_WIDTH);
+    RLPPO_CHECK_ARG(!(c->bf16 && res), "act options: residual hidden layers (RLPPO_ACT_RES) with the bf16 inference precision: the bf16-operand "
+                    "kernels feed the next product without the row kernel");
+    if (res)
+        if (int rc = res_net_check("act options", call->net)) return rc;
+    c->hidden_res = res && res_applies(call->net);
     c->done = o->done_words;
     c->done_value = o->done_value;
     c->noise_ctl = o->noise_ctl;
@@ -134,14 +141,26 @@ static int act_open(ActCall *call, const int32_t *dims, int32_t n_layers, const 
                     "act options: noise_ctl needs done_words (a kernel that gives up on the noise reports it there) and done_value < 2^31");
     return 0;
 }
-static size_t forward_ws_floats(const NetLayout &net, int64_t n) { return (size_t)2 * (size_t)n * (size_t)max_pout(net); }
+// (bufs: two ping-pong buffers; [res] a residual chain with a norm keeps the stream, the GEMM output and the normalised stream: three)
+static size_t forward_ws_floats(const NetLayout &net, int64_t n, int bufs = 2) { return (size_t)bufs * (size_t)n * (size_t)max_pout(net); }
+static int forward_bufs(const ActCtx &c) { return c.hidden_res && c.hidden_norm ? 3 : 2; }
+// the workspace of a call whose options carry `hidden_act`: 0 for a bad field
+static size_t forward_ws_floats_act(const NetLayout &net, int64_t n, int32_t hidden_act, bool *ok) {
+    ActCtx c;
+    int res = 0;
+    *ok = hidden_act_split(hidden_act, &c.hidden_act, &c.hidden_norm, &res);
+    c.hidden_res = res && res_applies(net);
+    return forward_ws_floats(net, n, forward_bufs(c));
+}
 // runs the call's layer chain (inference: no bitmasks, nothing saved) with ping-pong buffers from the workspace; the last layer's
 // output goes to final_out when that is given; call->o / ldo find it
 static int act_chain(hipStream_t st, ActCall *call, const float *packed, const float *obs, int64_t ld_obs, int64_t n, int out_tanh, void *ws,
                      size_t ws_bytes, float *final_out) {
     const NetLayout &net = call->net;
-    if (ws_bytes < forward_ws_floats(net, n) * sizeof(float)) {
-        set_error("forward: workspace %zu < %zu bytes", ws_bytes, forward_ws_floats(net, n) * sizeof(float));
+    const ActCtx &cx = call->cx;
+    if (ws_bytes < forward_ws_floats(net, n, forward_bufs(cx)) * sizeof(float)) {
+        set_error("forward: workspace %zu < %zu bytes%s", ws_bytes, forward_ws_floats(net, n, forward_bufs(cx)) * sizeof(float),
+                  cx.hidden_res ? " (residual hidden layers: rlppo_forward_workspace_bytes_act)" : "");
         return RLPPO_ERR_WORKSPACE;
     }
     RLPPO_CHECK_ARG(ld_obs >= net.L[0].pin && ld_obs % 4 == 0, "forward: ld_obs=%ld must be >= %d (zero padded rows)",
@@ -157,8 +176,15 @@ static int act_chain(hipStream_t st, ActCall *call, const float *packed, const f
     c.out_tanh = out_tanh;
     c.hidden_act = call->cx.hidden_act;
     c.hidden_norm = call->cx.hidden_norm;
+    c.hidden_res = call->cx.hidden_res;
     c.bf16_operands = call->cx.bf16;
     for (int l = 0; l < net.n_layers; ++l) c.b.act[l] = (l & 1) ? b1 : b0;
+    if (c.hidden_res)  // [res] the stream lives in b0 (s += a in place), every GEMM output goes to b1, the normalised stream to a third buffer
+        for (int l = 0; l < net.n_layers; ++l) {
+            c.b.act[l] = l == 0 ? b0 : b1;
+            c.b.stream[l] = b0;
+            c.b.norm[l] = c.hidden_norm ? b1 + (size_t)n * max_pout(net) : nullptr;
+        }
     if (final_out) c.b.act[net.n_layers - 1] = final_out;
     call->o = c.b.act[net.n_layers - 1];
     call->ldo = net.L[net.n_layers - 1].pout;
@@ -233,9 +259,23 @@ size_t rlppo_forward_workspace_bytes(const int32_t *dims, int32_t n_layers, int6
     return forward_ws_floats(net, n > 0 ? n : 0) * sizeof(float) + 256;
 }
 
-int rlppo_mlp_forward(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
-                      int64_t ld_obs, int64_t n, int32_t out_tanh, float *out, int64_t ld_out, void *workspace,
-                      size_t ws_bytes, const rlppo_act_opts *opts) {
+// [res] the same for a call whose options carry hidden_act (a residual chain with a norm keeps a third buffer); 0: a bad field
+size_t rlppo_forward_workspace_bytes_act(const int32_t *dims, int32_t n_layers, int64_t n, int32_t hidden_act) {
+    NetLayout net;
+    bool ok = false;
+    if (make_layout(dims, n_layers, &net)) return 0;
+    const size_t f = forward_ws_floats_act(net, n > 0 ? n : 0, hidden_act, &ok);
+    return ok ? f * sizeof(float) + 256 : 0;
+}
+
+// res_entry: [res] rlppo_mlp_forward_res, whose workspace is rlppo_forward_workspace_bytes_act's.  rlppo_mlp_forward itself keeps its
+// contract -- the two buffers of rlppo_forward_workspace_bytes, hidden_act 0 .. 2 and 0x100 .. 0x102 -- and answers every other value as
+// it always did.
+static int mlp_forward(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs, int64_t ld_obs, int64_t n,
+                       int32_t out_tanh, float *out, int64_t ld_out, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts, bool res_entry) {
+    RLPPO_CHECK_ARG(res_entry || !opts || opts->hidden_act < 0 || !(opts->hidden_act & RLPPO_ACT_RES),
+                    "act options: hidden_act %d (0 = ReLU, 1 = tanh, 2 = ELU; a network with RLPPO_ACT_RES runs through rlppo_mlp_forward_res)",
+                    opts ? opts->hidden_act : 0);
     ActCall c;
     int rc = act_open(&c, dims, n_layers, opts, false, "rlppo_mlp_forward");
     if (rc) return rc;
@@ -245,6 +285,16 @@ int rlppo_mlp_forward(void *stream, const int32_t *dims, int32_t n_layers, const
                     (long)ld_out, c.net.L[n_layers - 1].pout);
     rc = act_chain((hipStream_t)stream, &c, packed, obs, ld_obs, n, out_tanh, workspace, ws_bytes, out);
     return rc ? rc : act_done((hipStream_t)stream, c.cx, n);
+}
+int rlppo_mlp_forward(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
+                      int64_t ld_obs, int64_t n, int32_t out_tanh, float *out, int64_t ld_out, void *workspace,
+                      size_t ws_bytes, const rlppo_act_opts *opts) {
+    return mlp_forward(stream, dims, n_layers, packed, obs, ld_obs, n, out_tanh, out, ld_out, workspace, ws_bytes, opts, false);
+}
+int rlppo_mlp_forward_res(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
+                          int64_t ld_obs, int64_t n, int32_t out_tanh, float *out, int64_t ld_out, void *workspace,
+                          size_t ws_bytes, const rlppo_act_opts *opts) {
+    return mlp_forward(stream, dims, n_layers, packed, obs, ld_obs, n, out_tanh, out, ld_out, workspace, ws_bytes, opts, true);
 }
 
 int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
@@ -261,7 +311,7 @@ int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     if (rc) return rc;
     // [r3] one launch for the whole step when the network has the form fused_act.hip covers (fp32 inference precision); the
     // layer-by-layer chain below otherwise -- bit-identical results either way
-    if (g_fused_act && !cx.bf16 && !cx.hidden_act && !cx.hidden_norm && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS && ld_obs >= net.L[0].pin && ld_obs % 4 == 0 &&
+    if (g_fused_act && !cx.bf16 && !cx.hidden_act && !cx.hidden_norm && !cx.hidden_res && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS && ld_obs >= net.L[0].pin && ld_obs % 4 == 0 &&
         (reinterpret_cast<uintptr_t>(obs) & 15) == 0) {  // (the kernel stages the padded rows with 16-byte loads)
         FusedActIO io = fused_act_io(cx, noise_q, actions, logp);
         io.rows = obs;
@@ -282,6 +332,15 @@ size_t rlppo_discrete_step_workspace_bytes(const int32_t *dims, int32_t n_layers
     if (make_layout(dims, n_layers, &net)) return 0;
     n = n > 0 ? n : 0;
     return forward_ws_floats(net, n) * sizeof(float) + ((size_t)n * net.L[0].pin * sizeof(float) + 255) / 256 * 256 + 512;
+}
+
+size_t rlppo_discrete_step_workspace_bytes_act(const int32_t *dims, int32_t n_layers, int64_t n, int32_t hidden_act) {
+    NetLayout net;
+    bool ok = false;
+    if (make_layout(dims, n_layers, &net)) return 0;
+    n = n > 0 ? n : 0;
+    const size_t f = forward_ws_floats_act(net, n, hidden_act, &ok);
+    return ok ? f * sizeof(float) + ((size_t)n * net.L[0].pin * sizeof(float) + 255) / 256 * 256 + 512 : 0;
 }
 
 static int g_window_mode = 0;  // rlppo_dbg_set(41, v), test hook: 1 = answer as a device without a large BAR, 2 = windows without a flush register
@@ -313,7 +372,7 @@ int rlppo_host_window_free(void *ptr) {
 int rlppo_discrete_step_one_launch(const int32_t *dims, int32_t n_layers, int64_t n, const rlppo_act_opts *opts) {
     ActCall c;
     if (act_open(&c, dims, n_layers, opts, true, nullptr)) return -1;
-    return g_fused_act && !c.cx.bf16 && !c.cx.hidden_act && !c.cx.hidden_norm && fused_act_ok(c.net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
+    return g_fused_act && !c.cx.bf16 && !c.cx.hidden_act && !c.cx.hidden_norm && !c.cx.hidden_res && fused_act_ok(c.net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
 }
 
 int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const void *obs, int32_t obs_is_f64,
@@ -334,7 +393,7 @@ int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, con
     rc = act_mask_check(cx, dims[n_layers]);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (g_fused_act && !cx.bf16 && !cx.hidden_act && !cx.hidden_norm && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
+    if (g_fused_act && !cx.bf16 && !cx.hidden_act && !cx.hidden_norm && !cx.hidden_res && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
         FusedActIO io = fused_act_io(cx, noise_q, actions, logp);
         io.raw = obs;
         io.raw_is_f64 = obs_is_f64;

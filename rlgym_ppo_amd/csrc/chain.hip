@@ -90,6 +90,15 @@ int forward(Chain &c) {
         set_error("forward: hidden layer normalisation runs the plain fp32 layer chain only");
         return RLPPO_ERR_ARG;
     }
+    const bool res = c.hidden_res && res_applies(net);  // [res]
+    if (res) {
+        if (c.bf16_operands || any_bits || c.may_fold || c.x3 || c.in.rowtab) {
+            set_error("forward: residual hidden layers run the plain fp32 layer chain only");
+            return RLPPO_ERR_ARG;
+        }
+        for (int l = 0; l < hl; ++l)
+            RLPPO_CHECK_ARG(c.b.stream[l] && (!c.hidden_norm || c.b.norm[l]), "forward: a residual chain needs its stream%s", c.hidden_norm ? " and its normalised stream" : "");
+    }
     X3Layout xl;
     if (c.x3) x3_layout(net, &xl);
     for (int l = 0; l < net.n_layers; ++l) c.have_bits[l] = false;
@@ -130,7 +139,13 @@ int forward(Chain &c) {
         if (rc) return rc;
         x = c.b.act[l];
         ldx = L.pout;
-        if (c.hidden_norm) {  // [norm] (the chain's first launch also clears the zero bias its backward reads)
+        if (res && l >= 1) {  // [res] s_l = s_{l-1} + a_l, u_l = N(s_l) (without a norm the first of these launches clears the zero bias)
+            float *u = c.hidden_norm ? c.b.norm[l] : nullptr;
+            rc = launch_row_res_fwd(c.st, c.b.stream[l - 1], L.pout, c.b.act[l], L.pout, c.n, L.out, L.pout, c.hidden_norm, c.b.stream[l], L.pout, u, L.pout,
+                                    !c.hidden_norm && l == 1 ? c.b.zeros : nullptr, max_pout(net));
+            if (rc) return rc;
+            x = u ? u : c.b.stream[l];
+        } else if (c.hidden_norm) {  // [norm] (the chain's first launch also clears the zero bias its backward reads)
             float *y = c.b.norm[l] ? c.b.norm[l] : c.b.act[l];
             rc = launch_row_norm_fwd(c.st, c.b.act[l], L.pout, c.n, L.out, L.pout, y, L.pout, l == 0 ? c.b.zeros : nullptr, max_pout(net));
             if (rc) return rc;
@@ -234,7 +249,8 @@ int layer_backward(Chain &c, int l, bool need_bits) {
     float *const *acts = c.b.act, *const *dx = c.b.dx;
     const float *dY = l == last ? acts[last] : dx[l];
     const int64_t ld_hy = c.head_folded ? 1 : L.pout;  // stride of a one-output head's dY (compact when it was folded, forward())
-    const RowSource X = l > 0 ? RowSource{c.hidden_norm ? c.b.norm[l - 1] : acts[l - 1], net.L[l - 1].pout} : c.in;
+    const bool res = c.hidden_res && res_applies(net);  // [res] the layer's input is the stream below it (normalised under hidden_norm)
+    const RowSource X = l > 0 ? RowSource{c.hidden_norm ? c.b.norm[l - 1] : res ? c.b.stream[l - 1] : acts[l - 1], net.L[l - 1].pout} : c.in;
     const bool gemv = l == last && l > 0 && gemv_head_ok(L.out, L.pin);  // one-output head (gemv.hip)
     const size_t floats = tn_layer_floats(net, l, mb, 0);  // (fp32 / split-bf16 precisions: the bf16 one has backward_b16)
     int rc = 0;
@@ -246,11 +262,17 @@ int layer_backward(Chain &c, int l, bool need_bits) {
         rc = launch_gemm_tn(st, dY, L.pout, L.pout, X.x, X.ld, L.pin, c.grad + L.off_flat_w, c.grad + L.off_flat_b, L.out, L.in, mb,
                             c.b.tn, floats, X.rowtab, X.src_rows);
     if (rc || l == 0) return rc;
-    if (c.hidden_norm) {  // [norm] the plain product (zero bias, stored as it is), then the normalisation's and the activation's backward
-        RLPPO_CHECK_ARG(c.b.norm[l - 1] && c.b.zeros, "backward: a normalised chain needs its normalised activations and zero bias");
+    if (c.hidden_norm || res) {  // [norm] the plain product (zero bias, stored as it is), then the normalisation's and the activation's backward
+        RLPPO_CHECK_ARG((!c.hidden_norm || c.b.norm[l - 1]) && c.b.zeros, "backward: a normalised chain needs its normalised activations and zero bias");
+        RLPPO_CHECK_ARG(!res || (c.b.stream[l - 1] && c.b.g[0] && c.b.g[1]), "backward: a residual chain needs its stream and its two stream gradients");
         if (gemv) rc = launch_gemv_dx(st, dY, ld_hy, c.w + L.off_w, nullptr, 0, dx[l - 1], L.pin, L.pin, mb, ACT_PLAIN);
         else rc = launch_gemm_nt(st, dY, L.pout, c.w + L.off_wt, L.pout, c.b.zeros, nullptr, 0, dx[l - 1], L.pin, mb, L.pin, L.pout, EPI_BIAS);
         if (rc) return rc;
+        if (res) {  // [res] hidden layer k = l - 1: g_k = (N's backward of the product) + g_{k+1}, dz_k = g_k f'(a_k), in one launch
+            const int k = l - 1;
+            return launch_row_res_bwd(st, acts[k], L.pin, c.b.stream[k], L.pin, dx[k], L.pin, l == last ? nullptr : c.b.g[l & 1], L.pin, mb, net.L[k].out,
+                                      L.pin, c.hidden_act, c.hidden_norm, k == 0 ? nullptr : c.b.g[k & 1], L.pin, dx[k], L.pin);
+        }
         return launch_row_norm_bwd(st, acts[l - 1], L.pin, dx[l - 1], L.pin, mb, net.L[l - 1].out, L.pin, c.hidden_act, dx[l - 1], L.pin);
     }
     // dX[mb][pin] = (dY[mb][pout] . W[pout][pin]) masked by relu'(acts[l-1]); B operand = W^T [pin][pout].  The mask is the

@@ -53,6 +53,10 @@ struct NetWs {
     // and max_pout zeros: the bias of the backward's plain dX products
     float *norm[RLPPO_MAX_LAYERS] = {};
     float *zeros = nullptr;
+    // [res] a residual network: the raw stream s_l behind every hidden layer, [mb][pout] (stream[0] is act[0]: layer 0 has no skip;
+    // inference: ONE buffer for all of them, the sum runs in place), and the two alternating buffers of dL/ds_l (training only)
+    float *stream[RLPPO_MAX_LAYERS] = {};
+    float *g[2] = {};
 };
 
 // What one network contributes to one pass or one inference call.  b.act[l] receives the output of layer l ([n][pout_l]): for
@@ -65,6 +69,10 @@ struct NetWs {
 // [norm] hidden_norm: every hidden layer is GEMM (bias + activation epilogue) -> row_norm_fwd (norm.hip); the normalised output is the
 // next layer's A operand and its weight-gradient product's X operand, b.act[l] stays the saved activation.  backward(): the dX product
 // of layer l + 1 stores plain and row_norm_bwd turns it into b.dx[l].  The plain form only, like tanh / ELU.
+// [res] hidden_res (two hidden layers or more, equal widths; with one it changes nothing): a_l = f(W_l u_{l-1} + b_l) is the unchanged GEMM
+// into b.act[l], row_res_fwd adds it to the stream -- s_l = s_{l-1} + a_l into b.stream[l] -- and with hidden_norm stores u_l = N(s_l) into
+// b.norm[l]; u_l (the stream itself without hidden_norm) is the next layer's A operand and its weight-gradient product's X operand.
+// backward(): the dX product of layer l + 1 stores plain into b.dx[l] and ONE row_res_bwd makes it dL/dz_l, passing dL/ds_l down in b.g.
 struct Chain {
     hipStream_t st = nullptr;
     const NetLayout *net = nullptr;
@@ -72,7 +80,7 @@ struct Chain {
     RowSource in = {nullptr, 0};
     const unsigned short *in_b = nullptr;  // bf16 update precision: the rows of `in` as bf16
     int64_t n = 0;
-    int out_tanh = 0, hidden_act = ACT_RELU, hidden_norm = 0;
+    int out_tanh = 0, hidden_act = ACT_RELU, hidden_norm = 0, hidden_res = 0;
     int bf16_operands = 0;  // inference precision: fp32 data, bf16-rounded operands
     NetWs b;
     float *grad = nullptr;     // the gradient arena, and ...

@@ -94,8 +94,11 @@ constexpr size_t BITS_PAD_RESERVE = 2, B16_PAD_RESERVE = 4;
 // critic's gathered rows follow the policy's, so they start on the boundary those do and every other plan is what it was.
 // norm_nets: [norm] bit 0 / 1 = the policy / the critic is normalised -- its normalised activations and its zero bias FOLLOW everything else, so
 // every other region is where it was (rlppo_minibatch_workspace_bytes_norm sizes such a plan).
+// res_nets: [res] the same bits for the residual networks (of two hidden layers or more): behind a network's normalised activations and zero
+// bias (it has one with or without a norm) come the stream of every hidden layer but the first (s_0 is act[0]) and the two alternating
+// buffers of the stream's gradient (rlppo_minibatch_workspace_bytes_res sizes such a plan).
 static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec, void *base, WsPlan *w, bool critic_rows,
-                             int norm_nets = 0) {
+                             int norm_nets = 0, int res_nets = 0) {
     const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
     const size_t rows = (size_t)mb;
     size_t off = 0, slack = 0;  // floats from the base; the unused part of the pad reserves
@@ -147,13 +150,19 @@ static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t
         for (int i = 0; i < 2; ++i)
             for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->dxb[l] = take16(rows * nets[i]->L[l].pout);
     }
-    if (norm_nets) {  // (16-byte loads: the row counts above need not be multiples of 4)
+    if (norm_nets | res_nets) {  // (16-byte loads: the row counts above need not be multiples of 4)
         align(4, B16_PAD_RESERVE);
-        for (int i = 0; i < 2; ++i)
-            if (norm_nets >> i & 1) {
+        for (int i = 0; i < 2; ++i) {
+            const bool normed = norm_nets >> i & 1, res = res_nets >> i & 1;
+            if (normed)
                 for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->norm[l] = take(rows * nets[i]->L[l].pout);
-                ws[i]->zeros = take((size_t)max_pout(*nets[i]));
+            if (normed || res) ws[i]->zeros = take((size_t)max_pout(*nets[i]));
+            if (res) {
+                ws[i]->stream[0] = ws[i]->act[0];
+                for (int l = 1; l + 1 < nets[i]->n_layers; ++l) ws[i]->stream[l] = take(rows * nets[i]->L[l].pout);
+                for (float *&g : ws[i]->g) g = take(rows * nets[i]->L[0].pout);
             }
+        }
     }
     return off + slack;
 }
@@ -238,6 +247,7 @@ struct Pass {
     // a tanh / ELU network is plain (that machinery is ReLU by construction); rlppo_dbg_set(19, 0) makes a ReLU pass plain too.
     int pol_act = ACT_RELU, val_act = ACT_RELU;
     int pol_norm = 0, val_norm = 0;  // [norm] layer normalisation behind every hidden activation of the network: a plain pass too
+    int pol_res = 0, val_res = 0;    // [res] the skip stream (a network of two hidden layers or more that carries RLPPO_ACT_RES): a plain pass too
     bool plain = false;
     bool has_bins = false;  // [vbins] a categorical critic (rlppo_ppo_minibatch_vbins): a plain pass whose critic ends in `bins.n` logits
     BinSpec bins;
@@ -258,6 +268,7 @@ static Chain pass_chain(const Pass &p, bool critic) {
     c.out_tanh = !critic && a.head == RLPPO_HEAD_GAUSSIAN;
     c.hidden_act = critic ? p.val_act : p.pol_act;
     c.hidden_norm = critic ? p.val_norm : p.pol_norm;
+    c.hidden_res = critic ? p.val_res : p.pol_res;
     c.b = critic ? p.w.val : p.w.pol;
     if (p.plain)  // [act] the plain form: no bitmasks
         for (auto &bits : c.b.bits) bits = nullptr;
@@ -506,7 +517,8 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
     rc = resolve_precision(a->precision, &p.prec);
     if (rc) return rc;
     // [act] the hidden activations: tanh / ELU passes are fp32 (the bf16 and split-bf16 kernels carry the ReLU bitmask by construction)
-    RLPPO_CHECK_ARG(hidden_act_split(o.pol_act, &p.pol_act, &p.pol_norm) && hidden_act_split(o.val_act, &p.val_act, &p.val_norm),
+    int pol_res = 0, val_res = 0;  // (the flag as given: what is refused goes by it, what runs by whether the network has a skip at all)
+    RLPPO_CHECK_ARG(hidden_act_split(o.pol_act, &p.pol_act, &p.pol_norm, &pol_res) && hidden_act_split(o.val_act, &p.val_act, &p.val_norm, &val_res),
                     "ppo_minibatch: pol_hidden_act=%d val_hidden_act=%d (0 = ReLU, 1 = tanh, 2 = ELU)", o.pol_act, o.val_act);
     const bool non_relu = p.pol_act != ACT_RELU || p.val_act != ACT_RELU;
     RLPPO_CHECK_ARG(!(non_relu && p.prec != 0), "ppo_minibatch: hidden activation %s with update precision %s: the %s kernels are ReLU only (use fp32)",
@@ -517,6 +529,14 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
                     "no place for the row kernels (use fp32)", p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
     RLPPO_CHECK_ARG((!p.pol_norm || norm_width_ok(pol)) && (!p.val_norm || norm_width_ok(val)),
                     "ppo_minibatch: hidden layer normalisation of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded)", RLPPO_NORM_MAX_WIDTH);
+    // [res] a residual network: the same, and hidden layers of one width (the checks name the option; before the first HIP call)
+    RLPPO_CHECK_ARG(!((pol_res || val_res) && p.prec != 0), "ppo_minibatch: residual hidden layers (RLPPO_ACT_RES) with update precision %s: the %s kernels "
+                    "have no place for the row kernels (use fp32)", p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
+    if (pol_res && (rc = res_net_check("ppo_minibatch: the policy", pol))) return rc;
+    if (val_res && (rc = res_net_check("ppo_minibatch: the critic", val))) return rc;
+    p.pol_res = pol_res && res_applies(pol);
+    p.val_res = val_res && res_applies(val);
+    const bool resid = p.pol_res || p.val_res;
     // [vbins] a categorical critic: its bins, and an fp32 pass in the plain form (no folded head, no matrix-vector head: an ordinary last layer)
     if (o.bins) {
         rc = value_bins_make(o.bins, "ppo_minibatch_vbins", &p.bins);
@@ -527,7 +547,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
         RLPPO_CHECK_ARG(!(a->value_clip > 0.f), "ppo_minibatch_vbins: value_clip=%g with a categorical critic (bins): clipping a distribution is undefined",
                         (double)a->value_clip);
     }
-    p.plain = non_relu || normed || p.has_bins || (p.prec == 0 && !g_relu_bits);
+    p.plain = non_relu || normed || resid || p.has_bins || (p.prec == 0 && !g_relu_bits);
     RLPPO_CHECK_ARG(mb > 0 && a->pol_packed && a->val_packed && a->pol_grad && a->val_grad && a->states && a->actions &&
                         a->old_logp && a->targets && a->advantages && a->idx && a->stats && a->workspace,
                     "ppo_minibatch: null pointer");
@@ -547,10 +567,12 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
     }
     RLPPO_CHECK_ARG(a->ld_states >= pol.L[0].pin && a->ld_states % 4 == 0, "ppo_minibatch: ld_states=%ld < %d",
                     (long)a->ld_states, pol.L[0].pin);
-    const size_t ws_bytes = plan_workspace(pol, val, mb, p.prec, a->workspace, &p.w, critic != nullptr, p.pol_norm | p.val_norm << 1) * sizeof(float);
+    const size_t ws_bytes = plan_workspace(pol, val, mb, p.prec, a->workspace, &p.w, critic != nullptr, p.pol_norm | p.val_norm << 1,
+                                           p.pol_res | p.val_res << 1) * sizeof(float);
     if (a->ws_bytes < ws_bytes) {
         set_error("ppo_minibatch: workspace %zu < %zu bytes%s", a->ws_bytes, ws_bytes,
-                  normed   ? " (hidden layer normalisation: rlppo_minibatch_workspace_bytes_norm)"
+                  resid    ? " (residual hidden layers: rlppo_minibatch_workspace_bytes_res)"
+                  : normed ? " (hidden layer normalisation: rlppo_minibatch_workspace_bytes_norm)"
                   : critic ? " (separate critic rows: rlppo_minibatch_workspace_bytes_critic)"
                            : "");
         return RLPPO_ERR_WORKSPACE;
@@ -680,12 +702,14 @@ static int ppo_minibatch_opts(void *stream, const rlppo_minibatch_args *a, const
 }
 
 static size_t workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers, int64_t mb,
-                              int32_t precision, bool critic_rows, int norm_nets = 0) {
+                              int32_t precision, bool critic_rows, int norm_nets = 0, int res_nets = 0) {
     NetLayout pol, val;
     int prec = 0;
     if (make_layout(pol_dims, pol_layers, &pol) || make_layout(val_dims, val_layers, &val) || resolve_precision(precision, &prec)) return 0;
     WsPlan unused;
-    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused, critic_rows, norm_nets) * sizeof(float) + 256;
+    if (!res_applies(pol)) res_nets &= ~1;
+    if (!res_applies(val)) res_nets &= ~2;
+    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused, critic_rows, norm_nets, res_nets) * sizeof(float) + 256;
 }
 
 extern "C" {
@@ -701,9 +725,16 @@ size_t rlppo_minibatch_workspace_bytes_critic(const int32_t *pol_dims, int32_t p
 // [norm] the plan of _for / _critic (critic_rows != 0) + what the networks whose activation field carries RLPPO_ACT_NORM add; 0: a bad field
 size_t rlppo_minibatch_workspace_bytes_norm(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
                                             int64_t mb, int32_t precision, int32_t critic_rows, int32_t pol_hidden_act, int32_t val_hidden_act) {
-    int pa, pn, va, vn;
-    if (!hidden_act_split(pol_hidden_act, &pa, &pn) || !hidden_act_split(val_hidden_act, &va, &vn)) return 0;
+    int pa, pn, pr, va, vn, vr;
+    if (!hidden_act_split(pol_hidden_act, &pa, &pn, &pr) || !hidden_act_split(val_hidden_act, &va, &vn, &vr) || pr || vr) return 0;
     return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, critic_rows != 0, pn | vn << 1);
+}
+// [res] ... + what the networks whose field carries RLPPO_ACT_RES add (without the bit in either field it equals _norm)
+size_t rlppo_minibatch_workspace_bytes_res(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
+                                           int64_t mb, int32_t precision, int32_t critic_rows, int32_t pol_hidden_act, int32_t val_hidden_act) {
+    int pa, pn, pr, va, vn, vr;
+    if (!hidden_act_split(pol_hidden_act, &pa, &pn, &pr) || !hidden_act_split(val_hidden_act, &va, &vn, &vr)) return 0;
+    return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, critic_rows != 0, pn | vn << 1, pr | vr << 1);
 }
 size_t rlppo_minibatch_workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims,
                                        int32_t val_layers, int64_t mb) {

@@ -43,7 +43,7 @@ class Learner(object):
             n_checkpoints_to_keep: int = 5, shm_buffer_size: int = 8192, device: str = "auto",
             vector_env: bool = False, gae_bootstrap_truncated: bool = False, multi_discrete_bins=None,
             continuous_head: str = "reference", continuous_log_std_init: float = 0.0, continuous_action_clip="default",
-            hidden_activation: str = "relu", hidden_layer_norm=False,
+            hidden_activation: str = "relu", hidden_layer_norm=False, hidden_residual=False,
             ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
             critic_observations: bool = False,
             ppo_normalize_value: bool = False, ppo_value_norm_popart: bool = False,
@@ -93,8 +93,14 @@ class Learner(object):
         # are a LayerSizes with norm="layer" keep it while the keyword is left at False, and must be among the networks the keyword names
         # otherwise.  fp32 only: refused here, before anything is built, beside update precisions bf16 / x3 and the bf16 inference precision.
         # self.hidden_norms says what was built.
+        # not in the reference: hidden_residual = True | "policy" | "critic" runs a skip stream over the hidden layers of both networks / the
+        # policy / the critic (ppo._mlp.ResidualBody: the pre-LayerNorm residual with one-Linear blocks beside hidden_layer_norm, the plain
+        # s + f(W s + b) without it).  It travels inside the layer sizes and follows hidden_layer_norm's agreement rule; the hidden widths
+        # of such a network must all be equal.  fp32 only, refused here like hidden_layer_norm.  self.hidden_residuals says what was built.
         from .ppo._mlp import LayerSizes, check_activation
         hidden_activation = check_activation(hidden_activation)
+        if hidden_residual not in (False, True, "policy", "critic"):
+            raise ValueError(f"hidden_residual must be False, True, 'policy' or 'critic', got {hidden_residual!r}")
         if hidden_layer_norm not in (False, True, "policy", "critic"):
             raise ValueError(f"hidden_layer_norm must be False, True, 'policy' or 'critic', got {hidden_layer_norm!r}")
 
@@ -106,7 +112,12 @@ class Learner(object):
             own_norm = getattr(sizes, "norm", None)
             if own_norm is not None and asked is None and hidden_layer_norm:
                 raise ValueError(f"{name} is LayerSizes(..., norm={own_norm!r}) but hidden_layer_norm={hidden_layer_norm!r}: give one of them")
-            return LayerSizes(sizes, own if own is not None else hidden_activation, own_norm or asked, getattr(sizes, "value_head", None))
+            asked_res = hidden_residual is True or bool(hidden_residual and name.startswith(hidden_residual))
+            own_res = getattr(sizes, "residual", False)
+            if own_res and not asked_res and hidden_residual:
+                raise ValueError(f"{name} is LayerSizes(..., residual=True) but hidden_residual={hidden_residual!r}: give one of them")
+            return LayerSizes(sizes, own if own is not None else hidden_activation, own_norm or asked, getattr(sizes, "value_head", None),
+                              own_res or asked_res)
         sizes_given = (policy_layer_sizes, critic_layer_sizes)   # (what the config dict logs, as it always did)
         policy_layer_sizes = with_activation("policy_layer_sizes", policy_layer_sizes)
         critic_layer_sizes = with_activation("critic_layer_sizes", critic_layer_sizes)
@@ -127,7 +138,7 @@ class Learner(object):
             if critic_layer_sizes.value_head is not None:
                 raise ValueError(f"critic_layer_sizes is LayerSizes(..., value_head=...) but ppo_value_head={ppo_value_head!r}: give one of them")
             bins = ValueBins(ppo_value_bins, ppo_value_range, ppo_value_head, ppo_value_sigma_ratio)
-            critic_layer_sizes = LayerSizes(critic_layer_sizes, critic_layer_sizes.activation, critic_layer_sizes.norm, bins)
+            critic_layer_sizes = LayerSizes(critic_layer_sizes, critic_layer_sizes.activation, critic_layer_sizes.norm, bins, critic_layer_sizes.residual)
             if not ppo_normalize_value and tuple(ppo_value_range) == (-10.0, 10.0):
                 warnings.warn(f"ppo_value_head={ppo_value_head!r} without ppo_normalize_value: ppo_value_range is in real value units and was "
                               "left at its default (-10, 10) -- value targets outside it are clamped", RuntimeWarning, stacklevel=2)
@@ -151,6 +162,15 @@ class Learner(object):
                                  "kernels have no place for the row kernels -- use engine.set_update_precision('fp32')")
             if engine.inference_precision() == "bf16":
                 raise ValueError("hidden_layer_norm with the bf16 inference precision: the bf16-operand kernels feed the next product "
+                                 "without the row kernel -- use engine.set_inference_precision('fp32')")
+        self.hidden_residuals = {"policy": policy_layer_sizes.residual, "critic": critic_layer_sizes.residual}
+        if any(self.hidden_residuals.values()):
+            from . import engine
+            if engine.update_precision() != "fp32":
+                raise ValueError(f"hidden_residual with update precision {engine.update_precision()!r}: the {engine.update_precision()} update "
+                                 "kernels have no place for the row kernels -- use engine.set_update_precision('fp32')")
+            if engine.inference_precision() == "bf16":
+                raise ValueError("hidden_residual with the bf16 inference precision: the bf16-operand kernels feed the next product "
                                  "without the row kernel -- use engine.set_inference_precision('fp32')")
         # what was built, per network; and as one name where both agree (the keyword's own type), None where they differ
         self.hidden_activations = {"policy": policy_layer_sizes.activation, "critic": critic_layer_sizes.activation}

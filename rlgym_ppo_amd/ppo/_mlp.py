@@ -36,6 +36,17 @@ def check_norm(norm):
     return norm
 
 
+def check_residual_widths(sizes):
+    """Residual hidden layers add into one stream: every hidden width equals the first and fits a row kernel; ValueError otherwise."""
+    for l, size in enumerate(sizes):
+        if int(size) != int(sizes[0]):
+            raise ValueError(f"residual hidden layers need equal hidden widths: hidden layer {l} has {int(size)} outputs, hidden layer 0 has "
+                             f"{int(sizes[0])}")
+    if len(sizes) and int(sizes[0]) > N.NORM_MAX_WIDTH:
+        raise ValueError(f"residual hidden layers of a layer wider than {N.NORM_MAX_WIDTH} (RLPPO_NORM_MAX_WIDTH): the row kernels hold a row "
+                         "of the stream in registers")
+
+
 class ValueBins:
     """The head of a categorical critic (include/rlppo.h, "[vbins]"): n logits over n equal bins of value_range, trained by
     cross-entropy against an "hl_gauss" histogram (a Gaussian of sigma_ratio bin widths around the value target, integrated over each
@@ -84,22 +95,29 @@ class LayerSizes(tuple):
     activation travels in an argument every constructor already has, the way multi-discrete bins travel in act_space_size.  A tuple
     in every other respect (tuple(x) gives the plain sizes back); a plain tuple means "relu".
     norm: None, or "layer" -- layer normalisation without learnable parameters behind every hidden activation (ActNorm).
-    value_head: None, or the ValueBins of a categorical critic (the critic's sizes only: a policy refuses one)."""
+    value_head: None, or the ValueBins of a categorical critic (the critic's sizes only: a policy refuses one).
+    residual: a skip stream over the hidden layers (ResidualBody); the hidden widths must then all be equal."""
 
-    def __new__(cls, sizes, activation="relu", norm=None, value_head=None):
+    def __new__(cls, sizes, activation="relu", norm=None, value_head=None, residual=False):
         self = super().__new__(cls, tuple(sizes))
         self.activation = check_activation(activation)
         self.norm = check_norm(norm)
         if value_head is not None and not isinstance(value_head, ValueBins):
             raise ValueError(f"value_head must be None or a ValueBins, got {value_head!r}")
         self.value_head = value_head
+        if residual not in (False, True):
+            raise ValueError(f"residual must be False or True, got {residual!r}")
+        self.residual = bool(residual)
+        if self.residual:
+            check_residual_widths(self)
         return self
 
     def __reduce__(self):
-        return (LayerSizes, (tuple(self), self.activation, self.norm, self.value_head))
+        return (LayerSizes, (tuple(self), self.activation, self.norm, self.value_head, self.residual))
 
     def __repr__(self):
         tail = (f", norm={self.norm!r}" if self.norm else "") + (f", value_head={self.value_head!r}" if self.value_head else "")
+        tail += ", residual=True" if self.residual else ""
         return f"LayerSizes({tuple(self)!r}, {self.activation!r}{tail})"
 
 
@@ -130,6 +148,33 @@ def norm_of(module):
     return "layer" if isinstance(module[1], ActNorm) else None
 
 
+class ResidualBody(nn.Sequential):
+    """The body build_body makes -- the same modules under the same indices, so the same state_dict -- run with a skip stream over its
+    hidden layers 0 .. H-1 (the pre-LayerNorm residual with one-Linear blocks; include/rlppo.h, "[res]"):
+        a_0 = f(W_0 x + b_0), s_0 = a_0;    a_l = f(W_l u_(l-1) + b_l), s_l = s_(l-1) + a_l;    u_l = N(s_l);    out = W_out u_(H-1) + b_out
+    with N the layer normalisation of an ActNorm body and the identity otherwise: every block reads the normalised stream and writes into
+    the raw one, which is never normalised.  With one hidden layer it is the plain Sequential."""
+
+    def forward(self, x):
+        mods = list(self)
+        hidden = sum(isinstance(m, nn.Linear) for m in mods) - 1
+        s = None
+        for l in range(hidden):
+            linear, act = mods[2 * l], mods[2 * l + 1]
+            normed = isinstance(act, ActNorm)
+            a = (act.act if normed else act)(linear(x))
+            s = a if s is None else s + a
+            x = nn.functional.layer_norm(s, (act.width,), eps=1e-5) if normed else s
+        for m in mods[2 * hidden:]:
+            x = m(x)
+        return x
+
+
+def residual_of(module):
+    """Whether a body build_body made runs the skip stream."""
+    return isinstance(module, ResidualBody)
+
+
 def build_body(input_shape, layer_sizes, n_out, final_activation=None, critic=False):
     assert len(layer_sizes) != 0, "AT LEAST ONE LAYER MUST BE SPECIFIED TO BUILD THE NEURAL NETWORK!"
     if getattr(layer_sizes, "value_head", None) is not None and not critic:   # (ValueEstimator alone builds with critic=True)
@@ -149,6 +194,9 @@ def build_body(input_shape, layer_sizes, n_out, final_activation=None, critic=Fa
     layers.append(nn.Linear(prev, int(n_out)))
     if final_activation is not None:
         layers.append(final_activation)
+    if getattr(layer_sizes, "residual", False):   # (the same modules, indices and draws: only forward() differs)
+        check_residual_widths(tuple(layer_sizes))
+        return ResidualBody(*layers)
     return nn.Sequential(*layers)
 
 
@@ -201,7 +249,7 @@ class ActGraph:
         self.act_pin = pol._action_buffer(cap).zero_().pin_memory()
         self.logp_pin = torch.zeros(cap, dtype=torch.float32).pin_memory()
         L = N.lib()
-        ws_bytes = max(int(L.rlppo_forward_workspace_bytes(a.dims_c, a.n_layers, cap)), raw(None, cap) if raw is not None else 0)
+        ws_bytes = max(a.forward_ws_bytes(cap), raw(None, cap) if raw is not None else 0)
         self.ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
 
         # [r5] completion by words the call's last kernel stores into pinned memory behind the results (rlppo_act_opts): run()
@@ -476,8 +524,12 @@ class ArenaModule(nn.Module):
         self.hidden_norm = norm_of(self.model)
         if self.hidden_norm and max(l.out_features for l in linears_of(self.model)[:-1]) > N.NORM_MAX_WIDTH:
             raise ValueError(f"hidden layer normalisation of a layer wider than {N.NORM_MAX_WIDTH} (RLPPO_NORM_MAX_WIDTH)")
+        self.hidden_residual = residual_of(self.model)
+        if self.hidden_residual:   # (a body built by hand: build_body has checked its own)
+            check_residual_widths([l.out_features for l in linears_of(self.model)[:-1]])
         self.arena = NetArena(linears_of(self.model), dev, tail=getattr(self, "_arena_tail", ()),
-                              hidden_act=N.HIDDEN_ACTIVATIONS[self.hidden_activation] | (N.ACT_NORM if self.hidden_norm else 0))
+                              hidden_act=N.HIDDEN_ACTIVATIONS[self.hidden_activation] | (N.ACT_NORM if self.hidden_norm else 0)
+                              | (N.ACT_RES if self.hidden_residual else 0))
         self.act_graphs = True  # get_action through a hipGraph per batch-size bucket (False: every call takes the general path)
         self.act_graph_max = 1024  # beyond that the explicit copies of the eager path are the better transport for the noise
         self._graphs = {}

@@ -142,7 +142,7 @@ class DiscreteFF(ArenaModule):
             logp = logp_out if logp_out is not None else torch.empty(n, dtype=torch.float32, device=a.device)
         elif logp_out is not None:
             raise ValueError("step: logp_out needs to_host=False or to_host='actions'")
-        ws = a.ws.get(L.rlppo_discrete_step_workspace_bytes(a.dims_c, a.n_layers, n))
+        ws = a.ws.get(a.step_ws_bytes(n))
         N.check(L.rlppo_discrete_step(stream_ptr(), a.dims_c, a.n_layers, ptr(a.packed), ptr(t), int(t.dtype == torch.float64), d, n,
                                       mode, mean0, std0, ptr(mean_v), ptr(std_v), ptr(q), ptr(actions), ptr(actions_f32), ptr(logp),
                                       ptr(rows_out), rows_out.stride(0) if rows_out is not None else 0, ptr(ws), ws.numel(),
@@ -186,7 +186,7 @@ class DiscreteFF(ArenaModule):
         a = self.arena
         L = N.lib()
         if g is None:
-            return int(L.rlppo_discrete_step_workspace_bytes(a.dims_c, a.n_layers, cap))
+            return a.step_ws_bytes(cap)
         # (a masked graph's opts carry action_mask / mask_words: the words' region of its window, or of pinned memory)
         args = getattr(g, "_raw_args", None)
         if args is None or args[0] is not opts:  # every pointer of the call is fixed for the graph's lifetime: built once

@@ -453,6 +453,8 @@ class PPOLearner(object):
         size_fn = N.lib().rlppo_minibatch_workspace_bytes_for if cr is None else N.lib().rlppo_minibatch_workspace_bytes_critic
         if (pa.hidden_act | va.hidden_act) & N.ACT_NORM:   # a normalised network: the same plan + its normalised activations
             size_fn = lambda *dims: N.lib().rlppo_minibatch_workspace_bytes_norm(*dims, int(cr is not None), pa.hidden_act, va.hidden_act)
+        if (pa.hidden_act | va.hidden_act) & N.ACT_RES:    # a residual network: + its stream and the stream's two gradient buffers
+            size_fn = lambda *dims: N.lib().rlppo_minibatch_workspace_bytes_res(*dims, int(cr is not None), pa.hidden_act, va.hidden_act)
         nbytes = int(size_fn(pa.dims_c, pa.n_layers, va.dims_c, va.n_layers, self._fused_rows, a.precision))
         nbytes = (nbytes + 255) // 256 * 256
         ws = self._ws.get(nbytes * self.n_slots)
@@ -540,6 +542,9 @@ class PPOLearner(object):
         # a normalised network updates in fp32 too: the bf16 and split-bf16 chains have no place for the row kernels
         if any(getattr(m, "hidden_norm", None) for m in (self.policy, self.value_net)) and self._precision() != "fp32":
             raise ValueError(f"hidden layer normalisation with update precision {self._precision()!r}: the {self._precision()} update kernels "
+                             "have no place for the row kernels -- use update_precision='fp32'")
+        if any(getattr(m, "hidden_residual", False) for m in (self.policy, self.value_net)) and self._precision() != "fp32":
+            raise ValueError(f"residual hidden layers with update precision {self._precision()!r}: the {self._precision()} update kernels "
                              "have no place for the row kernels -- use update_precision='fp32'")
         # a categorical critic (LayerSizes(..., value_head=ValueBins)) updates in fp32 (its pass is the plain form), has nothing to clip
         # and no last layer whose rescaling would preserve its outputs

@@ -46,8 +46,10 @@ def switched(fn, switches):
     return run
 
 
-def pass_legs(mb, n_buf):
+def pass_legs(mb, n_buf, configs=None, size_fn=None):
+    """configs: the legs (default CONFIGS); size_fn: what sizes the one workspace of all of them (default rlppo_minibatch_workspace_bytes_for)."""
     L = N.lib()
+    configs, size_fn = configs or CONFIGS, size_fn or L.rlppo_minibatch_workspace_bytes_for
     rs = np.random.RandomState(0)
     pol, val = Net([OBS, *HIDDEN, A]), Net([OBS, *HIDDEN, 1])
     states = torch.zeros(n_buf, val.ld_in, device="cuda")
@@ -62,7 +64,7 @@ def pass_legs(mb, n_buf):
     a.head, a.pol_layers, a.val_layers, a.act_dim, a.precision = N.HEAD_DISCRETE, pol.nl, val.nl, 1, N.PRECISION_FP32
     a.pol_dims = ctypes.cast(pol.dims_c, ctypes.POINTER(ctypes.c_int32))
     a.val_dims = ctypes.cast(val.dims_c, ctypes.POINTER(ctypes.c_int32))
-    ws_bytes = int(L.rlppo_minibatch_workspace_bytes_for(pol.dims_c, pol.nl, val.dims_c, val.nl, mb, a.precision))
+    ws_bytes = int(size_fn(pol.dims_c, pol.nl, val.dims_c, val.nl, mb, a.precision))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
     a.pol_packed, a.val_packed, a.pol_grad, a.val_grad = pol.packed.data_ptr(), val.packed.data_ptr(), gp.data_ptr(), gv.data_ptr()
     a.states, a.ld_states, a.n_rows, a.actions = states.data_ptr(), states.shape[1], n_buf, acts.data_ptr()
@@ -71,7 +73,7 @@ def pass_legs(mb, n_buf):
     a.stats, a.workspace, a.ws_bytes = stats.data_ptr(), ws.data_ptr(), ws_bytes
     st = bench_stream()
     legs, keep = {}, [pol, val, states, acts, old, tgt, adv, idx, stats, gp, gv, ws, a]
-    for name, code, plain in CONFIGS:
+    for name, code, plain in configs:
         ext = N.MinibatchExt()
         ext.pol_hidden_act = ext.val_hidden_act = code
         keep.append(ext)
@@ -80,17 +82,18 @@ def pass_legs(mb, n_buf):
     return legs, keep
 
 
-def rollout_legs(n):
+def rollout_legs(n, configs=None, size_fn=None):
     L = N.lib()
+    configs, size_fn = configs or CONFIGS, size_fn or L.rlppo_forward_workspace_bytes
     pol = Net([OBS, *HIDDEN, A])
     rows = torch.zeros(n, pol.ld_in, device="cuda")
     rows[:, :OBS] = torch.randn(n, OBS, device="cuda").clamp_(-5, 5)
     q = torch.empty(n, A, device="cuda").exponential_(1)
     act, logp = torch.empty(n, dtype=torch.int64, device="cuda"), torch.empty(n, device="cuda")
-    ws = torch.empty(int(L.rlppo_forward_workspace_bytes(pol.dims_c, pol.nl, n)), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(int(size_fn(pol.dims_c, pol.nl, n)), dtype=torch.uint8, device="cuda")
     st = bench_stream()
     legs, keep = {}, [pol, rows, q, act, logp, ws]
-    for name, code, plain in CONFIGS:
+    for name, code, plain in configs:
         o = N.ActOpts()
         o.hidden_act = code
         keep.append(o)
