@@ -95,10 +95,16 @@ struct ActCtx {
     unsigned *noise_ctl = nullptr;
     const unsigned *mask = nullptr;  // [ABI 8] rlppo_act_opts.action_mask / mask_words
     int mask_words = 0;
-    int hidden_act = ACT_RELU;       // [act] rlppo_act_opts.hidden_act ...
-    int hidden_norm = 0;             // [norm] ... and its RLPPO_ACT_NORM bit
-    int hidden_res = 0;              // [res] ... and its RLPPO_ACT_RES bit, where the network has a skip at all (two hidden layers or more)
+    HiddenSpec hidden;               // rlppo_act_opts.hidden_act
 };
+// the bf16 inference precision multiplies bf16-rounded operands in the ReLU kernels alone
+static int act_bf16_check(const HiddenSpec &h) {
+    RLPPO_CHECK_ARG(h.act == ACT_RELU, "act options: hidden activation %s with the bf16 inference precision: the bf16-operand kernels are ReLU only",
+                    hidden_act_name(h.act));
+    RLPPO_CHECK_ARG(!h.norm && !h.res_asked, "act options: %s with the bf16 inference precision: the bf16-operand kernels feed the next product without "
+                    "the row kernel", h.norm ? "hidden layer normalisation (RLPPO_ACT_NORM)" : "residual hidden layers (RLPPO_ACT_RES)");
+    return 0;
+}
 // One call of a rollout entry point: the network, the call's options and, once act_chain has run, the last layer's output
 struct ActCall {
     NetLayout net;
@@ -116,20 +122,11 @@ static int act_open(ActCall *call, const int32_t *dims, int32_t n_layers, const 
     RLPPO_CHECK_ARG(o->precision == RLPPO_PRECISION_DEFAULT || o->precision == RLPPO_PRECISION_FP32 || o->precision == RLPPO_PRECISION_BF16,
                     "act options: inference precision %d (0 = process default, 1 = fp32, 2 = bf16 operands)", o->precision);
     if (o->precision != RLPPO_PRECISION_DEFAULT) c->bf16 = o->precision == RLPPO_PRECISION_BF16;
-    int res = 0;
-    RLPPO_CHECK_ARG(hidden_act_split(o->hidden_act, &c->hidden_act, &c->hidden_norm, &res), "act options: hidden_act %d (0 = ReLU, 1 = tanh, 2 = ELU)", o->hidden_act);
-    RLPPO_CHECK_ARG(!(c->bf16 && c->hidden_act != ACT_RELU),
-                    "act options: hidden activation %s with the bf16 inference precision: the bf16-operand kernels are ReLU only",
-                    hidden_act_name(c->hidden_act));
-    RLPPO_CHECK_ARG(!(c->bf16 && c->hidden_norm), "act options: hidden layer normalisation (RLPPO_ACT_NORM) with the bf16 inference precision: the "
-                    "bf16-operand kernels feed the next product without the row kernel");
-    RLPPO_CHECK_ARG(!c->hidden_norm || norm_width_ok(call->net), "act options: hidden layer normalisation of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded)",
-                    RLPPO_NORM_MAX_WIDTH);
-    RLPPO_CHECK_ARG(!(c->bf16 && res), "act options: residual hidden layers (RLPPO_ACT_RES) with the bf16 inference precision: the bf16-operand "
-                    "kernels feed the next product without the row kernel");
-    if (res)
-        if (int rc = res_net_check("act options", call->net)) return rc;
-    c->hidden_res = res && res_applies(call->net);
+    RLPPO_CHECK_ARG(hidden_spec_decode(o->hidden_act, call->net, &c->hidden), "act options: hidden_act %d (0 = ReLU, 1 = tanh, 2 = ELU)", o->hidden_act);
+    if (c->bf16)
+        if (int rc = act_bf16_check(c->hidden)) return rc;
+    const HiddenNet hn{c->hidden, call->net, "act options"};
+    if (int rc = hidden_spec_widths("act options", &hn, 1)) return rc;
     c->done = o->done_words;
     c->done_value = o->done_value;
     c->noise_ctl = o->noise_ctl;
@@ -143,14 +140,12 @@ static int act_open(ActCall *call, const int32_t *dims, int32_t n_layers, const 
 }
 // (bufs: two ping-pong buffers; [res] a residual chain with a norm keeps the stream, the GEMM output and the normalised stream: three)
 static size_t forward_ws_floats(const NetLayout &net, int64_t n, int bufs = 2) { return (size_t)bufs * (size_t)n * (size_t)max_pout(net); }
-static int forward_bufs(const ActCtx &c) { return c.hidden_res && c.hidden_norm ? 3 : 2; }
+static int forward_bufs(const HiddenSpec &h) { return h.res && h.norm ? 3 : 2; }
 // the workspace of a call whose options carry `hidden_act`: 0 for a bad field
 static size_t forward_ws_floats_act(const NetLayout &net, int64_t n, int32_t hidden_act, bool *ok) {
-    ActCtx c;
-    int res = 0;
-    *ok = hidden_act_split(hidden_act, &c.hidden_act, &c.hidden_norm, &res);
-    c.hidden_res = res && res_applies(net);
-    return forward_ws_floats(net, n, forward_bufs(c));
+    HiddenSpec h;
+    *ok = hidden_spec_decode(hidden_act, net, &h);
+    return forward_ws_floats(net, n, forward_bufs(h));
 }
 // runs the call's layer chain (inference: no bitmasks, nothing saved) with ping-pong buffers from the workspace; the last layer's
 // output goes to final_out when that is given; call->o / ldo find it
@@ -158,9 +153,9 @@ static int act_chain(hipStream_t st, ActCall *call, const float *packed, const f
                      size_t ws_bytes, float *final_out) {
     const NetLayout &net = call->net;
     const ActCtx &cx = call->cx;
-    if (ws_bytes < forward_ws_floats(net, n, forward_bufs(cx)) * sizeof(float)) {
-        set_error("forward: workspace %zu < %zu bytes%s", ws_bytes, forward_ws_floats(net, n, forward_bufs(cx)) * sizeof(float),
-                  cx.hidden_res ? " (residual hidden layers: rlppo_forward_workspace_bytes_act)" : "");
+    if (ws_bytes < forward_ws_floats(net, n, forward_bufs(cx.hidden)) * sizeof(float)) {
+        set_error("forward: workspace %zu < %zu bytes%s", ws_bytes, forward_ws_floats(net, n, forward_bufs(cx.hidden)) * sizeof(float),
+                  cx.hidden.res ? " (residual hidden layers: rlppo_forward_workspace_bytes_act)" : "");
         return RLPPO_ERR_WORKSPACE;
     }
     RLPPO_CHECK_ARG(ld_obs >= net.L[0].pin && ld_obs % 4 == 0, "forward: ld_obs=%ld must be >= %d (zero padded rows)",
@@ -174,16 +169,14 @@ static int act_chain(hipStream_t st, ActCall *call, const float *packed, const f
     c.in = RowSource{obs, ld_obs};
     c.n = n;
     c.out_tanh = out_tanh;
-    c.hidden_act = call->cx.hidden_act;
-    c.hidden_norm = call->cx.hidden_norm;
-    c.hidden_res = call->cx.hidden_res;
+    c.hidden = cx.hidden;
     c.bf16_operands = call->cx.bf16;
     for (int l = 0; l < net.n_layers; ++l) c.b.act[l] = (l & 1) ? b1 : b0;
-    if (c.hidden_res)  // [res] the stream lives in b0 (s += a in place), every GEMM output goes to b1, the normalised stream to a third buffer
+    if (c.hidden.res)  // [res] the stream lives in b0 (s += a in place), every GEMM output goes to b1, the normalised stream to a third buffer
         for (int l = 0; l < net.n_layers; ++l) {
             c.b.act[l] = l == 0 ? b0 : b1;
             c.b.stream[l] = b0;
-            c.b.norm[l] = c.hidden_norm ? b1 + (size_t)n * max_pout(net) : nullptr;
+            c.b.norm[l] = c.hidden.norm ? b1 + (size_t)n * max_pout(net) : nullptr;
         }
     if (final_out) c.b.act[net.n_layers - 1] = final_out;
     call->o = c.b.act[net.n_layers - 1];
@@ -311,7 +304,7 @@ int rlppo_discrete_act(void *stream, const int32_t *dims, int32_t n_layers, cons
     if (rc) return rc;
     // [r3] one launch for the whole step when the network has the form fused_act.hip covers (fp32 inference precision); the
     // layer-by-layer chain below otherwise -- bit-identical results either way
-    if (g_fused_act && !cx.bf16 && !cx.hidden_act && !cx.hidden_norm && !cx.hidden_res && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS && ld_obs >= net.L[0].pin && ld_obs % 4 == 0 &&
+    if (g_fused_act && !cx.bf16 && !cx.hidden.plain_only() && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS && ld_obs >= net.L[0].pin && ld_obs % 4 == 0 &&
         (reinterpret_cast<uintptr_t>(obs) & 15) == 0) {  // (the kernel stages the padded rows with 16-byte loads)
         FusedActIO io = fused_act_io(cx, noise_q, actions, logp);
         io.rows = obs;
@@ -372,7 +365,7 @@ int rlppo_host_window_free(void *ptr) {
 int rlppo_discrete_step_one_launch(const int32_t *dims, int32_t n_layers, int64_t n, const rlppo_act_opts *opts) {
     ActCall c;
     if (act_open(&c, dims, n_layers, opts, true, nullptr)) return -1;
-    return g_fused_act && !c.cx.bf16 && !c.cx.hidden_act && !c.cx.hidden_norm && !c.cx.hidden_res && fused_act_ok(c.net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
+    return g_fused_act && !c.cx.bf16 && !c.cx.hidden.plain_only() && fused_act_ok(c.net) && n <= FUSED_ACT_MAX_ROWS ? 1 : 0;
 }
 
 int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const void *obs, int32_t obs_is_f64,
@@ -393,7 +386,7 @@ int rlppo_discrete_step(void *stream, const int32_t *dims, int32_t n_layers, con
     rc = act_mask_check(cx, dims[n_layers]);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (g_fused_act && !cx.bf16 && !cx.hidden_act && !cx.hidden_norm && !cx.hidden_res && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
+    if (g_fused_act && !cx.bf16 && !cx.hidden.plain_only() && fused_act_ok(net) && n <= FUSED_ACT_MAX_ROWS) {
         FusedActIO io = fused_act_io(cx, noise_q, actions, logp);
         io.raw = obs;
         io.raw_is_f64 = obs_is_f64;

@@ -10,6 +10,28 @@ int max_pout(const NetLayout &net) {
     return m;
 }
 
+// ---- HiddenSpec (common.hpp): the widths the row kernels of norm.hip / residual.hip accept
+static bool norm_width_ok(const NetLayout &net) {  // every hidden layer's padded width is at most RLPPO_NORM_MAX_WIDTH
+    for (int l = 0; l + 1 < net.n_layers; ++l)
+        if (net.L[l].pout > RLPPO_NORM_MAX_WIDTH) return false;
+    return true;
+}
+int hidden_spec_widths(const char *who, const HiddenNet *nets, int n) {
+    for (int i = 0; i < n; ++i)
+        RLPPO_CHECK_ARG(!nets[i].spec.norm || norm_width_ok(nets[i].net), "%s: hidden layer normalisation of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded)",
+                        who, RLPPO_NORM_MAX_WIDTH);
+    for (int i = 0; i < n; ++i) {
+        const NetLayout &net = nets[i].net;
+        if (!nets[i].spec.res_asked) continue;
+        RLPPO_CHECK_ARG(norm_width_ok(net), "%s: residual hidden layers (RLPPO_ACT_RES) of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded): the row "
+                        "kernels hold a row of the stream in registers", nets[i].res_who, RLPPO_NORM_MAX_WIDTH);
+        for (int l = 1; l + 1 < net.n_layers; ++l)
+            RLPPO_CHECK_ARG(net.L[l].out == net.L[0].out, "%s: residual hidden layers (RLPPO_ACT_RES) need equal hidden widths: hidden layer %d has %d "
+                            "outputs, hidden layer 0 has %d", nets[i].res_who, l, net.L[l].out, net.L[0].out);
+    }
+    return 0;
+}
+
 void x3_layout(const NetLayout &net, X3Layout *o) {
     int64_t off = 0;
     const int last = net.n_layers - 1;
@@ -82,23 +104,15 @@ int forward(Chain &c) {
     const int hl = net.n_layers - 1;
     bool any_bits = false;
     for (int l = 0; l < hl; ++l) any_bits |= c.b.bits[l] != nullptr;
-    if (c.hidden_act != ACT_RELU && (c.bf16_operands || any_bits || c.may_fold || c.x3 || c.in.rowtab)) {
-        set_error("forward: hidden activation %s runs the plain fp32 layer chain only", hidden_act_name(c.hidden_act));
+    const HiddenSpec &h = c.hidden;
+    if (h.plain_only() && (c.bf16_operands || any_bits || c.may_fold || c.x3 || c.in.rowtab)) {
+        if (h.act != ACT_RELU) set_error("forward: hidden activation %s runs the plain fp32 layer chain only", hidden_act_name(h.act));
+        else set_error("forward: %s the plain fp32 layer chain only", h.norm ? "hidden layer normalisation runs" : "residual hidden layers run");
         return RLPPO_ERR_ARG;
     }
-    if (c.hidden_norm && (c.bf16_operands || any_bits || c.may_fold || c.x3 || c.in.rowtab)) {
-        set_error("forward: hidden layer normalisation runs the plain fp32 layer chain only");
-        return RLPPO_ERR_ARG;
-    }
-    const bool res = c.hidden_res && res_applies(net);  // [res]
-    if (res) {
-        if (c.bf16_operands || any_bits || c.may_fold || c.x3 || c.in.rowtab) {
-            set_error("forward: residual hidden layers run the plain fp32 layer chain only");
-            return RLPPO_ERR_ARG;
-        }
+    if (h.res)
         for (int l = 0; l < hl; ++l)
-            RLPPO_CHECK_ARG(c.b.stream[l] && (!c.hidden_norm || c.b.norm[l]), "forward: a residual chain needs its stream%s", c.hidden_norm ? " and its normalised stream" : "");
-    }
+            RLPPO_CHECK_ARG(c.b.stream[l] && (!h.norm || c.b.norm[l]), "forward: a residual chain needs its stream%s", h.norm ? " and its normalised stream" : "");
     X3Layout xl;
     if (c.x3) x3_layout(net, &xl);
     for (int l = 0; l < net.n_layers; ++l) c.have_bits[l] = false;
@@ -135,17 +149,17 @@ int forward(Chain &c) {
         }
         if (rc == -1)
             rc = launch_gemm_nt(c.st, x, ldx, c.w + L.off_w, L.pin, c.w + L.off_b, nullptr, 0, c.b.act[l], L.pout, c.n, L.pout, L.pin,
-                                hidden_act_fwd_epi(c.hidden_act), c.bf16_operands);
+                                hidden_act_fwd_epi(h.act), c.bf16_operands);
         if (rc) return rc;
         x = c.b.act[l];
         ldx = L.pout;
-        if (res && l >= 1) {  // [res] s_l = s_{l-1} + a_l, u_l = N(s_l) (without a norm the first of these launches clears the zero bias)
-            float *u = c.hidden_norm ? c.b.norm[l] : nullptr;
-            rc = launch_row_res_fwd(c.st, c.b.stream[l - 1], L.pout, c.b.act[l], L.pout, c.n, L.out, L.pout, c.hidden_norm, c.b.stream[l], L.pout, u, L.pout,
-                                    !c.hidden_norm && l == 1 ? c.b.zeros : nullptr, max_pout(net));
+        if (h.res && l >= 1) {  // [res] s_l = s_{l-1} + a_l, u_l = N(s_l) (without a norm the first of these launches clears the zero bias)
+            float *u = h.norm ? c.b.norm[l] : nullptr;
+            rc = launch_row_res_fwd(c.st, c.b.stream[l - 1], L.pout, c.b.act[l], L.pout, c.n, L.out, L.pout, h.norm, c.b.stream[l], L.pout, u, L.pout,
+                                    !h.norm && l == 1 ? c.b.zeros : nullptr, max_pout(net));
             if (rc) return rc;
             x = u ? u : c.b.stream[l];
-        } else if (c.hidden_norm) {  // [norm] (the chain's first launch also clears the zero bias its backward reads)
+        } else if (h.norm) {  // [norm] (the chain's first launch also clears the zero bias its backward reads)
             float *y = c.b.norm[l] ? c.b.norm[l] : c.b.act[l];
             rc = launch_row_norm_fwd(c.st, c.b.act[l], L.pout, c.n, L.out, L.pout, y, L.pout, l == 0 ? c.b.zeros : nullptr, max_pout(net));
             if (rc) return rc;
@@ -249,8 +263,8 @@ int layer_backward(Chain &c, int l, bool need_bits) {
     float *const *acts = c.b.act, *const *dx = c.b.dx;
     const float *dY = l == last ? acts[last] : dx[l];
     const int64_t ld_hy = c.head_folded ? 1 : L.pout;  // stride of a one-output head's dY (compact when it was folded, forward())
-    const bool res = c.hidden_res && res_applies(net);  // [res] the layer's input is the stream below it (normalised under hidden_norm)
-    const RowSource X = l > 0 ? RowSource{c.hidden_norm ? c.b.norm[l - 1] : res ? c.b.stream[l - 1] : acts[l - 1], net.L[l - 1].pout} : c.in;
+    const HiddenSpec &h = c.hidden;  // [res] the layer's input is the stream below it (normalised under h.norm)
+    const RowSource X = l > 0 ? RowSource{h.norm ? c.b.norm[l - 1] : h.res ? c.b.stream[l - 1] : acts[l - 1], net.L[l - 1].pout} : c.in;
     const bool gemv = l == last && l > 0 && gemv_head_ok(L.out, L.pin);  // one-output head (gemv.hip)
     const size_t floats = tn_layer_floats(net, l, mb, 0);  // (fp32 / split-bf16 precisions: the bf16 one has backward_b16)
     int rc = 0;
@@ -262,18 +276,18 @@ int layer_backward(Chain &c, int l, bool need_bits) {
         rc = launch_gemm_tn(st, dY, L.pout, L.pout, X.x, X.ld, L.pin, c.grad + L.off_flat_w, c.grad + L.off_flat_b, L.out, L.in, mb,
                             c.b.tn, floats, X.rowtab, X.src_rows);
     if (rc || l == 0) return rc;
-    if (c.hidden_norm || res) {  // [norm] the plain product (zero bias, stored as it is), then the normalisation's and the activation's backward
-        RLPPO_CHECK_ARG((!c.hidden_norm || c.b.norm[l - 1]) && c.b.zeros, "backward: a normalised chain needs its normalised activations and zero bias");
-        RLPPO_CHECK_ARG(!res || (c.b.stream[l - 1] && c.b.g[0] && c.b.g[1]), "backward: a residual chain needs its stream and its two stream gradients");
+    if (h.norm || h.res) {  // [norm] the plain product (zero bias, stored as it is), then the normalisation's and the activation's backward
+        RLPPO_CHECK_ARG((!h.norm || c.b.norm[l - 1]) && c.b.zeros, "backward: a normalised chain needs its normalised activations and zero bias");
+        RLPPO_CHECK_ARG(!h.res || (c.b.stream[l - 1] && c.b.g[0] && c.b.g[1]), "backward: a residual chain needs its stream and its two stream gradients");
         if (gemv) rc = launch_gemv_dx(st, dY, ld_hy, c.w + L.off_w, nullptr, 0, dx[l - 1], L.pin, L.pin, mb, ACT_PLAIN);
         else rc = launch_gemm_nt(st, dY, L.pout, c.w + L.off_wt, L.pout, c.b.zeros, nullptr, 0, dx[l - 1], L.pin, mb, L.pin, L.pout, EPI_BIAS);
         if (rc) return rc;
-        if (res) {  // [res] hidden layer k = l - 1: g_k = (N's backward of the product) + g_{k+1}, dz_k = g_k f'(a_k), in one launch
+        if (h.res) {  // [res] hidden layer k = l - 1: g_k = (N's backward of the product) + g_{k+1}, dz_k = g_k f'(a_k), in one launch
             const int k = l - 1;
             return launch_row_res_bwd(st, acts[k], L.pin, c.b.stream[k], L.pin, dx[k], L.pin, l == last ? nullptr : c.b.g[l & 1], L.pin, mb, net.L[k].out,
-                                      L.pin, c.hidden_act, c.hidden_norm, k == 0 ? nullptr : c.b.g[k & 1], L.pin, dx[k], L.pin);
+                                      L.pin, h.act, h.norm, k == 0 ? nullptr : c.b.g[k & 1], L.pin, dx[k], L.pin);
         }
-        return launch_row_norm_bwd(st, acts[l - 1], L.pin, dx[l - 1], L.pin, mb, net.L[l - 1].out, L.pin, c.hidden_act, dx[l - 1], L.pin);
+        return launch_row_norm_bwd(st, acts[l - 1], L.pin, dx[l - 1], L.pin, mb, net.L[l - 1].out, L.pin, h.act, dx[l - 1], L.pin);
     }
     // dX[mb][pin] = (dY[mb][pout] . W[pout][pin]) masked by relu'(acts[l-1]); B operand = W^T [pin][pout].  The mask is the
     // bitmask the forward left when there is one (no re-read of the activation), else the saved activation itself.
@@ -295,10 +309,10 @@ int layer_backward(Chain &c, int l, bool need_bits) {
         set_error("paired pass: the output layer's dX needs the bitmask form");
         return RLPPO_ERR_ARG;
     }
-    if (rc == -1 && gemv) rc = launch_gemv_dx(st, dY, ld_hy, c.w + L.off_w, acts[l - 1], L.pin, dx[l - 1], L.pin, L.pin, mb, c.hidden_act);
+    if (rc == -1 && gemv) rc = launch_gemv_dx(st, dY, ld_hy, c.w + L.off_w, acts[l - 1], L.pin, dx[l - 1], L.pin, L.pin, mb, h.act);
     else if (rc == -1)
         rc = launch_gemm_nt(st, dY, L.pout, c.w + L.off_wt, L.pout, nullptr, acts[l - 1], L.pin, dx[l - 1], L.pin, mb, L.pin, L.pout,
-                            hidden_act_dx_epi(c.hidden_act));
+                            hidden_act_dx_epi(h.act));
     return rc;
 }
 

@@ -64,14 +64,14 @@ struct NetWs {
 // Training only: b.bits[l] (may be null) receives the ReLU bitmask of hidden layer l and have_bits[l] says whether it was written
 // (csrc/gemm.hip, launch_gemm_nt_bits); backward() then masks dX with it instead of re-reading b.act[l].
 // in.rowtab != nullptr: the first layer fetches its rows through the table (nt_gather_ok must hold for it).
-// [act] hidden_act (HiddenAct): the activation of every hidden layer.  tanh / ELU have the plain form only -- the callers give them no
-// bitmasks, no folded head, no row table, no bf16 operands and no split planes (all of those carry ReLU by construction).
-// [norm] hidden_norm: every hidden layer is GEMM (bias + activation epilogue) -> row_norm_fwd (norm.hip); the normalised output is the
+// hidden (HiddenSpec, common.hpp): what the hidden layers are.  Anything but plain ReLU layers has the plain form only -- the callers give
+// it no bitmasks, no folded head, no row table, no bf16 operands and no split planes.
+// [norm] hidden.norm: every hidden layer is GEMM (bias + activation epilogue) -> row_norm_fwd (norm.hip); the normalised output is the
 // next layer's A operand and its weight-gradient product's X operand, b.act[l] stays the saved activation.  backward(): the dX product
-// of layer l + 1 stores plain and row_norm_bwd turns it into b.dx[l].  The plain form only, like tanh / ELU.
-// [res] hidden_res (two hidden layers or more, equal widths; with one it changes nothing): a_l = f(W_l u_{l-1} + b_l) is the unchanged GEMM
-// into b.act[l], row_res_fwd adds it to the stream -- s_l = s_{l-1} + a_l into b.stream[l] -- and with hidden_norm stores u_l = N(s_l) into
-// b.norm[l]; u_l (the stream itself without hidden_norm) is the next layer's A operand and its weight-gradient product's X operand.
+// of layer l + 1 stores plain and row_norm_bwd turns it into b.dx[l].
+// [res] hidden.res (two hidden layers or more, equal widths): a_l = f(W_l u_{l-1} + b_l) is the unchanged GEMM
+// into b.act[l], row_res_fwd adds it to the stream -- s_l = s_{l-1} + a_l into b.stream[l] -- and with hidden.norm stores u_l = N(s_l) into
+// b.norm[l]; u_l (the stream itself without hidden.norm) is the next layer's A operand and its weight-gradient product's X operand.
 // backward(): the dX product of layer l + 1 stores plain into b.dx[l] and ONE row_res_bwd makes it dL/dz_l, passing dL/ds_l down in b.g.
 struct Chain {
     hipStream_t st = nullptr;
@@ -80,7 +80,8 @@ struct Chain {
     RowSource in = {nullptr, 0};
     const unsigned short *in_b = nullptr;  // bf16 update precision: the rows of `in` as bf16
     int64_t n = 0;
-    int out_tanh = 0, hidden_act = ACT_RELU, hidden_norm = 0, hidden_res = 0;
+    int out_tanh = 0;
+    HiddenSpec hidden;
     int bf16_operands = 0;  // inference precision: fp32 data, bf16-rounded operands
     NetWs b;
     float *grad = nullptr;     // the gradient arena, and ...

@@ -110,15 +110,33 @@ inline bool hidden_act_ok(int a) { return a >= ACT_RELU && a <= ACT_ELU; }
 inline const char *hidden_act_name(int a) { return a == ACT_TANH ? "tanh" : a == ACT_ELU ? "elu" : "relu"; }
 inline int hidden_act_fwd_epi(int a) { return a == ACT_TANH ? EPI_BIAS_TANH : a == ACT_ELU ? EPI_BIAS_ELU : EPI_BIAS_RELU; }
 inline int hidden_act_dx_epi(int a) { return a == ACT_TANH ? EPI_DTANH : a == ACT_ELU ? EPI_DELU : EPI_MASK; }
-// [norm] the same fields carry RLPPO_ACT_NORM (0x100) as a high bit: layer normalisation behind every hidden activation, [res] and
-// RLPPO_ACT_RES (0x200): the skip stream.  Splits a field into its activation and the flags; false for every value that is not an
-// activation with or without them.
-inline bool hidden_act_split(int field, int *act, int *norm, int *res) {
-    *act = field & ~(RLPPO_ACT_NORM | RLPPO_ACT_RES);
-    *norm = field >= 0 && (field & RLPPO_ACT_NORM) != 0;
-    *res = field >= 0 && (field & RLPPO_ACT_RES) != 0;
-    return field >= 0 && hidden_act_ok(*act);
+// What the hidden layers of one network are, decoded once from the wire field (rlppo_act_opts.hidden_act / rlppo_minibatch_ext.*_hidden_act):
+// the activation, [norm] RLPPO_ACT_NORM (0x100): layer normalisation behind every hidden activation, [res] RLPPO_ACT_RES (0x200): the skip
+// stream -- res_asked is the flag as given (what is refused goes by it), res whether the network has a skip at all (what runs goes by it).
+// Everything but a ReLU body without either flag is plain_only(): it runs the plain fp32 layer chain only -- no bitmasks, no folded head, no row table,
+// no bf16 operands, no split planes (all of those carry ReLU by construction and feed the next product without a row kernel).
+struct HiddenSpec {
+    int act = ACT_RELU;
+    bool norm = false, res_asked = false, res = false;
+    bool plain_only() const { return act != ACT_RELU || norm || res; }
+};
+// false for every value that is not an activation with or without the flags (the caller words that refusal: its text names its own fields)
+inline bool hidden_spec_decode(int field, const NetLayout &net, HiddenSpec *s) {
+    s->act = field & ~(RLPPO_ACT_NORM | RLPPO_ACT_RES);
+    s->norm = field >= 0 && (field & RLPPO_ACT_NORM) != 0;
+    s->res_asked = field >= 0 && (field & RLPPO_ACT_RES) != 0;
+    s->res = s->res_asked && net.n_layers >= 3;  // one hidden layer: no skip, the flag changes nothing
+    return field >= 0 && hidden_act_ok(s->act);
 }
+// What every entry point refuses of the networks themselves, in the order it always did: first a normalised hidden layer wider than
+// RLPPO_NORM_MAX_WIDTH in any of them (`who` names the call), then per network that carries RLPPO_ACT_RES such a layer or unequal hidden
+// widths (res_who names the call and the network).  chain.hip
+struct HiddenNet {
+    const HiddenSpec &spec;
+    const NetLayout &net;
+    const char *res_who;
+};
+int hidden_spec_widths(const char *who, const HiddenNet *nets, int n);
 
 // norm.hip: parameter-free layer normalisation of a hidden activation ----------------------------------
 // y[r][0:width) = (h - mean) * rsqrt(var + 1e-5) of row r, y[r][width:pout) = 0; y may be h.  zeros (optional): zero_n floats the
@@ -128,7 +146,6 @@ int launch_row_norm_fwd(hipStream_t st, const float *h, int64_t ld, int64_t n, i
 // dx = act'(h) * (the normalisation's backward of dy at h), padded columns 0; dx may be dy
 int launch_row_norm_bwd(hipStream_t st, const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int width, int pout, int act,
                         float *dx, int64_t ld_dx);
-bool norm_width_ok(const NetLayout &net);  // every hidden layer's padded width is at most RLPPO_NORM_MAX_WIDTH
 // [res] s[r] = s_prev[r] + a[r] (s may be s_prev) and, with norm, u = the normalisation of s; padded columns 0.  zeros: as above.
 int launch_row_res_fwd(hipStream_t st, const float *s_prev, int64_t ld_sp, const float *a, int64_t ld_a, int64_t n, int width, int pout, int norm,
                        float *s, int64_t ld_s, float *u, int64_t ld_u, float *zeros = nullptr, int zero_n = 0);
@@ -136,9 +153,6 @@ int launch_row_res_fwd(hipStream_t st, const float *s_prev, int64_t ld_sp, const
 // dz = g * act'(a) from the saved activation output a; padded columns 0; dz may be p
 int launch_row_res_bwd(hipStream_t st, const float *a, int64_t ld_a, const float *s, int64_t ld_s, const float *p, int64_t ld_p, const float *g_next,
                        int64_t ld_gn, int64_t n, int width, int pout, int act, int norm, float *g, int64_t ld_g, float *dz, int64_t ld_dz);
-// what every entry point refuses of a network that carries RLPPO_ACT_RES: a hidden layer wider than RLPPO_NORM_MAX_WIDTH, unequal hidden widths
-int res_net_check(const char *who, const NetLayout &net);
-inline bool res_applies(const NetLayout &net) { return net.n_layers >= 3; }  // one hidden layer: no skip, the flag changes nothing
 
 // gemm.hip ------------------------------------------------------------------------------------------
 // C[m][0:N] = epi(A[m][0:K] . B[n][0:K]^T)   (K % 32 == 0, N = padded out in {32,64,96,128,k*128})

@@ -14,7 +14,8 @@
 // outside every sum and are STORED as exact zeros (the next layer's products and the dW product read them); rows at and beyond n
 // are neither read nor written.  The outputs may alias an input (y == h, dx == dy): a lane stores only after its last load, and only
 // the chunks it loaded.
-// RowRegs / group_sum / row_stats / the launch shape live in norm_rows.hpp: residual.hip's kernels are the same design on the same code.
+// RowRegs / group_sum / row_stats / row_norm_bwd / act_bwd / the launch shape live in norm_rows.hpp: residual.hip's kernels are the same
+// design on the same code.
 #include "norm_rows.hpp"
 
 namespace rlppo {
@@ -48,69 +49,24 @@ __global__ __launch_bounds__(256) void row_norm_bwd_kernel(const float *h, int64
     g.load(dy + row * ld_dy, sub, cpr, live);
     yh = a;
     const float rstd = row_stats<LPR, VPL>(yh, sub, width);
-    const float inv_w = 1.f / (float)width;
-    float s1 = 0.f, s2 = 0.f;
+    row_norm_bwd<LPR, VPL>(g, yh, rstd, width, sub);
 #pragma unroll
     for (int j = 0; j < VPL; ++j)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = 4 * (j * LPR + sub) + e < width ? g.v[j][e] : 0.f;
-            g.v[j][e] = d;
-            s1 += d;
-            s2 += d * yh.v[j][e];
-        }
-    const float m1 = group_sum<LPR>(s1) * inv_w, m2 = group_sum<LPR>(s2) * inv_w;
-#pragma unroll
-    for (int j = 0; j < VPL; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float hv = a.v[j][e];
-            const float dh = rstd * ((g.v[j][e] - m1) - yh.v[j][e] * m2);
-            float o;
-            if constexpr (ACT == ACT_TANH) o = dh * (1.f - hv * hv);
-            else if constexpr (ACT == ACT_ELU) o = dh * (hv > 0.f ? 1.f : hv + 1.f);
-            else o = hv > 0.f ? dh : 0.f;
-            g.v[j][e] = 4 * (j * LPR + sub) + e < width ? o : 0.f;
-        }
+        for (int e = 0; e < 4; ++e) g.v[j][e] = 4 * (j * LPR + sub) + e < width ? act_bwd<ACT>(g.v[j][e], a.v[j][e]) : 0.f;
     g.store(dx + row * ld_dx, sub, cpr, live);
 }
 
 }  // namespace
 
-bool norm_width_ok(const NetLayout &net) {
-    for (int l = 0; l + 1 < net.n_layers; ++l)
-        if (net.L[l].pout > RLPPO_NORM_MAX_WIDTH) return false;
-    return true;
-}
-
 int launch_row_norm_fwd(hipStream_t st, const float *h, int64_t ld, int64_t n, int width, int pout, float *y, int64_t ld_y, float *zeros, int zero_n) {
     if (n <= 0) return 0;
     if (int rc = norm_check("row_norm_fwd", h, ld, y, ld_y, zeros, ld, width, pout)) return rc;
-    const NormShape s = norm_shape(pout);
-    const dim3 grid((unsigned)cdiv(n, 256 / s.lpr));
-#define FWD(L, V) hipLaunchKernelGGL((row_norm_fwd_kernel<L, V>), grid, dim3(256), 0, st, h, ld, n, width, pout / 4, y, ld_y, zeros, zero_n)
-    if (s.lpr == 16) {
-        if (s.vpl == 1) FWD(16, 1); else FWD(16, 2);
-    } else if (s.vpl == 1) FWD(64, 1);
-    else if (s.vpl == 2) FWD(64, 2);
-    else if (s.vpl == 4) FWD(64, 4);
-    else FWD(64, 8);
-#undef FWD
+    with_row_shape(pout, [&](auto L, auto V) {
+        hipLaunchKernelGGL((row_norm_fwd_kernel<L.value, V.value>), row_grid<L.value>(n), dim3(256), 0, st, h, ld, n, width, pout / 4, y, ld_y, zeros, zero_n);
+    });
     RLPPO_LAUNCH_CHECK();
     return 0;
-}
-
-template <int ACT>
-static void launch_bwd(hipStream_t st, const NormShape s, dim3 grid, const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int width,
-                       int cpr, float *dx, int64_t ld_dx) {
-#define BWD(L, V) hipLaunchKernelGGL((row_norm_bwd_kernel<L, V, ACT>), grid, dim3(256), 0, st, h, ld, dy, ld_dy, n, width, cpr, dx, ld_dx)
-    if (s.lpr == 16) {
-        if (s.vpl == 1) BWD(16, 1); else BWD(16, 2);
-    } else if (s.vpl == 1) BWD(64, 1);
-    else if (s.vpl == 2) BWD(64, 2);
-    else if (s.vpl == 4) BWD(64, 4);
-    else BWD(64, 8);
-#undef BWD
 }
 
 int launch_row_norm_bwd(hipStream_t st, const float *h, int64_t ld, const float *dy, int64_t ld_dy, int64_t n, int width, int pout, int act,
@@ -118,11 +74,12 @@ int launch_row_norm_bwd(hipStream_t st, const float *h, int64_t ld, const float 
     if (n <= 0) return 0;
     RLPPO_CHECK_ARG(hidden_act_ok(act), "row_norm_bwd: act %d (0 = ReLU, 1 = tanh, 2 = ELU)", act);
     if (int rc = norm_check("row_norm_bwd", h, ld, dy, ld_dy, dx, ld_dx, width, pout)) return rc;
-    const NormShape s = norm_shape(pout);
-    const dim3 grid((unsigned)cdiv(n, 256 / s.lpr));
-    if (act == ACT_TANH) launch_bwd<ACT_TANH>(st, s, grid, h, ld, dy, ld_dy, n, width, pout / 4, dx, ld_dx);
-    else if (act == ACT_ELU) launch_bwd<ACT_ELU>(st, s, grid, h, ld, dy, ld_dy, n, width, pout / 4, dx, ld_dx);
-    else launch_bwd<ACT_RELU>(st, s, grid, h, ld, dy, ld_dy, n, width, pout / 4, dx, ld_dx);
+    with_hidden_act(act, [&](auto A) {
+        with_row_shape(pout, [&](auto L, auto V) {
+            hipLaunchKernelGGL((row_norm_bwd_kernel<L.value, V.value, A.value>), row_grid<L.value>(n), dim3(256), 0, st, h, ld, dy, ld_dy, n, width, pout / 4, dx,
+                               ld_dx);
+        });
+    });
     RLPPO_LAUNCH_CHECK();
     return 0;
 }

@@ -1,7 +1,10 @@
 // norm_rows.hpp -- what the row kernels of norm.hip (layer normalisation) and residual.hip (the residual stream) share: a row in the registers of
-// the lanes that own it, the fixed-order sums over those lanes, the statistics of a row, the launch shape of a padded width and the
-// argument checks.  One definition each: both files run the same instruction sequences (norm.hip's header describes the design).
+// the lanes that own it, the fixed-order sums over those lanes, the statistics of a row, the normalisation's backward, the activation's
+// derivative, the launch shape of a padded width and the argument checks.  One definition each: both files run the same instruction
+// sequences (norm.hip's header describes the design).
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace rlppo {
@@ -70,15 +73,58 @@ __device__ __forceinline__ float row_stats(RowRegs<LPR, VPL> &h, int sub, int wi
     return rstd;
 }
 
-// lanes per row and 16-byte chunks per lane of a padded width (a multiple of 32 up to RLPPO_NORM_MAX_WIDTH)
-struct NormShape {
-    int lpr, vpl;
-};
-inline NormShape norm_shape(int pout) {
-    if (pout <= 64) return {16, 1};
-    if (pout <= 128) return {16, 2};
-    const int v = (int)cdiv(pout, 256);
-    return {64, v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : 8};
+// The normalisation's backward on a row: g (the gradient of y^, cleared beyond width on the way) becomes
+// rstd * (g - mean(g) - y^ mean(g y^)), the means over columns < width; yh and rstd are row_stats' of the same row
+template <int LPR, int VPL>
+__device__ __forceinline__ void row_norm_bwd(RowRegs<LPR, VPL> &g, const RowRegs<LPR, VPL> &yh, float rstd, int width, int sub) {
+    const float inv_w = 1.f / (float)width;
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float d = 4 * (j * LPR + sub) + e < width ? g.v[j][e] : 0.f;
+            g.v[j][e] = d;
+            s1 += d;
+            s2 += d * yh.v[j][e];
+        }
+    const float m1 = group_sum<LPR>(s1) * inv_w, m2 = group_sum<LPR>(s2) * inv_w;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g.v[j][e] = rstd * ((g.v[j][e] - m1) - yh.v[j][e] * m2);
+}
+
+// g times the derivative of the hidden activation ACT (HiddenAct), from the activation's saved OUTPUT h
+template <int ACT>
+__device__ __forceinline__ float act_bwd(float g, float h) {
+    if constexpr (ACT == ACT_TANH) return g * (1.f - h * h);
+    else if constexpr (ACT == ACT_ELU) return g * (h > 0.f ? 1.f : h + 1.f);
+    else return h > 0.f ? g : 0.f;
+}
+
+// The launch shape of a padded width (a multiple of 32 up to RLPPO_NORM_MAX_WIDTH): LPR lanes per row (16 up to 128 columns, the whole
+// wave beyond) and VPL 16-byte chunks per lane.  f(Int<LPR>, Int<VPL>) launches the caller's kernel of that shape on row_grid<LPR>(n):
+// every launcher of norm.hip and residual.hip selects its instantiation here.
+template <int N>
+using Int = std::integral_constant<int, N>;
+template <class F>
+inline void with_row_shape(int pout, F &&f) {
+    if (pout <= 64) f(Int<16>{}, Int<1>{});
+    else if (pout <= 128) f(Int<16>{}, Int<2>{});
+    else if (pout <= 256) f(Int<64>{}, Int<1>{});
+    else if (pout <= 512) f(Int<64>{}, Int<2>{});
+    else if (pout <= 1024) f(Int<64>{}, Int<4>{});
+    else f(Int<64>{}, Int<8>{});
+}
+template <int LPR>
+inline dim3 row_grid(int64_t n) { return dim3((unsigned)cdiv(n, 256 / LPR)); }
+// ... and f(Int<ACT>) the instantiation of a hidden activation (hidden_act_ok holds)
+template <class F>
+inline void with_hidden_act(int act, F &&f) {
+    if (act == ACT_TANH) f(Int<ACT_TANH>{});
+    else if (act == ACT_ELU) f(Int<ACT_ELU>{});
+    else f(Int<ACT_RELU>{});
 }
 inline int norm_check(const char *who, const void *a, int64_t lda, const void *b, int64_t ldb, const void *c, int64_t ldc, int width, int pout) {
     RLPPO_CHECK_ARG(width >= 1 && width <= pout && pout % 4 == 0, "%s: width=%d, padded width=%d", who, width, pout);

@@ -1,4 +1,4 @@
-// residual.hip -- the skip stream of residual hidden layers (chain.hip: hidden_res; include/rlppo.h, "[res]") as two row kernels between the
+// residual.hip -- the skip stream of residual hidden layers (common.hpp: HiddenSpec::res; include/rlppo.h, "[res]") as two row kernels between the
 // products of a layer chain, beside norm.hip's and of the same design (norm_rows.hpp: a row in the registers of its 16 lanes or of a whole
 // wave, 16-byte chunks interleaved over the lanes, shuffle butterflies in a fixed order, no LDS, no atomics, bit-reproducible; padded
 // columns stored as exact zeros, rows at and beyond n neither read nor written).
@@ -53,22 +53,7 @@ __global__ __launch_bounds__(256) void row_res_bwd_kernel(const float *a, int64_
         RowRegs<LPR, VPL> yh;
         yh.load(s + row * ld_s, sub, cpr, live);
         const float rstd = row_stats<LPR, VPL>(yh, sub, width);
-        const float inv_w = 1.f / (float)width;
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < VPL; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = 4 * (j * LPR + sub) + e < width ? g.v[j][e] : 0.f;
-                g.v[j][e] = d;
-                s1 += d;
-                s2 += d * yh.v[j][e];
-            }
-        const float m1 = group_sum<LPR>(s1) * inv_w, m2 = group_sum<LPR>(s2) * inv_w;
-#pragma unroll
-        for (int j = 0; j < VPL; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) g.v[j][e] = rstd * ((g.v[j][e] - m1) - yh.v[j][e] * m2);
+        row_norm_bwd<LPR, VPL>(g, yh, rstd, width, sub);
     }
     if (g_next) {  // (the same for every lane of the launch)
         RowRegs<LPR, VPL> t;
@@ -86,42 +71,11 @@ __global__ __launch_bounds__(256) void row_res_bwd_kernel(const float *a, int64_
 #pragma unroll
     for (int j = 0; j < VPL; ++j)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float hv = av.v[j][e], gv = g.v[j][e];
-            float o;
-            if constexpr (ACT == ACT_TANH) o = gv * (1.f - hv * hv);
-            else if constexpr (ACT == ACT_ELU) o = gv * (hv > 0.f ? 1.f : hv + 1.f);
-            else o = hv > 0.f ? gv : 0.f;
-            g.v[j][e] = 4 * (j * LPR + sub) + e < width ? o : 0.f;
-        }
+        for (int e = 0; e < 4; ++e) g.v[j][e] = 4 * (j * LPR + sub) + e < width ? act_bwd<ACT>(g.v[j][e], av.v[j][e]) : 0.f;
     g.store(dz + row * ld_dz, sub, cpr, live);
 }
 
 }  // namespace
-
-// ---- [res]
-int res_net_check(const char *who, const NetLayout &net) {
-    RLPPO_CHECK_ARG(norm_width_ok(net), "%s: residual hidden layers (RLPPO_ACT_RES) of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded): the row "
-                    "kernels hold a row of the stream in registers", who, RLPPO_NORM_MAX_WIDTH);
-    for (int l = 1; l + 1 < net.n_layers; ++l)
-        RLPPO_CHECK_ARG(net.L[l].out == net.L[0].out, "%s: residual hidden layers (RLPPO_ACT_RES) need equal hidden widths: hidden layer %d has %d "
-                        "outputs, hidden layer 0 has %d", who, l, net.L[l].out, net.L[0].out);
-    return 0;
-}
-
-template <bool NORM>
-static void launch_res_fwd(hipStream_t st, const NormShape sh, dim3 grid, const float *s_prev, int64_t ld_sp, const float *a, int64_t ld_a, int64_t n,
-                           int width, int cpr, float *s, int64_t ld_s, float *u, int64_t ld_u, float *zeros, int zero_n) {
-#define FWD(L, V) \
-    hipLaunchKernelGGL((row_res_fwd_kernel<L, V, NORM>), grid, dim3(256), 0, st, s_prev, ld_sp, a, ld_a, n, width, cpr, s, ld_s, u, ld_u, zeros, zero_n)
-    if (sh.lpr == 16) {
-        if (sh.vpl == 1) FWD(16, 1); else FWD(16, 2);
-    } else if (sh.vpl == 1) FWD(64, 1);
-    else if (sh.vpl == 2) FWD(64, 2);
-    else if (sh.vpl == 4) FWD(64, 4);
-    else FWD(64, 8);
-#undef FWD
-}
 
 int launch_row_res_fwd(hipStream_t st, const float *s_prev, int64_t ld_sp, const float *a, int64_t ld_a, int64_t n, int width, int pout, int norm,
                        float *s, int64_t ld_s, float *u, int64_t ld_u, float *zeros, int zero_n) {
@@ -131,38 +85,17 @@ int launch_row_res_fwd(hipStream_t st, const float *s_prev, int64_t ld_sp, const
     if (norm)
         if (int rc = norm_check("row_res_fwd", u, ld_u, u, ld_u, u, ld_u, width, pout)) return rc;
     RLPPO_CHECK_ARG((reinterpret_cast<uintptr_t>(zeros) & 3) == 0, "row_res_fwd: the zero row must be a float pointer");
-    const NormShape sh = norm_shape(pout);
-    const dim3 grid((unsigned)cdiv(n, 256 / sh.lpr));
-    if (norm) launch_res_fwd<true>(st, sh, grid, s_prev, ld_sp, a, ld_a, n, width, pout / 4, s, ld_s, u, ld_u, zeros, zero_n);
-    else launch_res_fwd<false>(st, sh, grid, s_prev, ld_sp, a, ld_a, n, width, pout / 4, s, ld_s, nullptr, 0, zeros, zero_n);
+    with_row_shape(pout, [&](auto L, auto V) {
+        const dim3 grid = row_grid<L.value>(n);
+        if (norm)
+            hipLaunchKernelGGL((row_res_fwd_kernel<L.value, V.value, true>), grid, dim3(256), 0, st, s_prev, ld_sp, a, ld_a, n, width, pout / 4, s, ld_s, u, ld_u,
+                               zeros, zero_n);
+        else
+            hipLaunchKernelGGL((row_res_fwd_kernel<L.value, V.value, false>), grid, dim3(256), 0, st, s_prev, ld_sp, a, ld_a, n, width, pout / 4, s, ld_s, nullptr,
+                               0, zeros, zero_n);
+    });
     RLPPO_LAUNCH_CHECK();
     return 0;
-}
-
-struct ResBwdArgs {
-    const float *a, *s, *p, *g_next;
-    int64_t ld_a, ld_s, ld_p, ld_gn, n;
-    int width, cpr;
-    float *g, *dz;
-    int64_t ld_g, ld_dz;
-};
-template <int ACT, bool NORM>
-static void launch_res_bwd(hipStream_t st, const NormShape sh, dim3 grid, const ResBwdArgs &q) {
-#define BWD(L, V)                                                                                                                                  \
-    hipLaunchKernelGGL((row_res_bwd_kernel<L, V, ACT, NORM>), grid, dim3(256), 0, st, q.a, q.ld_a, q.s, q.ld_s, q.p, q.ld_p, q.g_next, q.ld_gn, q.n, \
-                       q.width, q.cpr, q.g, q.ld_g, q.dz, q.ld_dz)
-    if (sh.lpr == 16) {
-        if (sh.vpl == 1) BWD(16, 1); else BWD(16, 2);
-    } else if (sh.vpl == 1) BWD(64, 1);
-    else if (sh.vpl == 2) BWD(64, 2);
-    else if (sh.vpl == 4) BWD(64, 4);
-    else BWD(64, 8);
-#undef BWD
-}
-template <int ACT>
-static void launch_res_bwd(hipStream_t st, const NormShape sh, dim3 grid, const ResBwdArgs &q, int norm) {
-    if (norm) launch_res_bwd<ACT, true>(st, sh, grid, q);
-    else launch_res_bwd<ACT, false>(st, sh, grid, q);
 }
 
 int launch_row_res_bwd(hipStream_t st, const float *a, int64_t ld_a, const float *s, int64_t ld_s, const float *p, int64_t ld_p, const float *g_next,
@@ -174,12 +107,18 @@ int launch_row_res_bwd(hipStream_t st, const float *a, int64_t ld_a, const float
     if (int rc = norm_check("row_res_bwd", norm ? s : a, norm ? ld_s : ld_a, g_next ? g_next : a, g_next ? ld_gn : ld_a, g ? g : dz, g ? ld_g : ld_dz,
                             width, pout))
         return rc;
-    const NormShape sh = norm_shape(pout);
-    const dim3 grid((unsigned)cdiv(n, 256 / sh.lpr));
-    const ResBwdArgs q{a, norm ? s : nullptr, p, g_next, ld_a, ld_s, ld_p, ld_gn, n, width, pout / 4, g, dz, ld_g, ld_dz};
-    if (act == ACT_TANH) launch_res_bwd<ACT_TANH>(st, sh, grid, q, norm);
-    else if (act == ACT_ELU) launch_res_bwd<ACT_ELU>(st, sh, grid, q, norm);
-    else launch_res_bwd<ACT_RELU>(st, sh, grid, q, norm);
+    if (!norm) s = nullptr;
+    with_hidden_act(act, [&](auto A) {
+        with_row_shape(pout, [&](auto L, auto V) {
+            const dim3 grid = row_grid<L.value>(n);
+            if (norm)
+                hipLaunchKernelGGL((row_res_bwd_kernel<L.value, V.value, A.value, true>), grid, dim3(256), 0, st, a, ld_a, s, ld_s, p, ld_p, g_next, ld_gn, n, width,
+                                   pout / 4, g, ld_g, dz, ld_dz);
+            else
+                hipLaunchKernelGGL((row_res_bwd_kernel<L.value, V.value, A.value, false>), grid, dim3(256), 0, st, a, ld_a, s, ld_s, p, ld_p, g_next, ld_gn, n, width,
+                                   pout / 4, g, ld_g, dz, ld_dz);
+        });
+    });
     RLPPO_LAUNCH_CHECK();
     return 0;
 }

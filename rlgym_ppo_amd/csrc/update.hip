@@ -92,13 +92,12 @@ constexpr size_t BITS_PAD_RESERVE = 2, B16_PAD_RESERVE = 4;
 // Lays out the workspace of a pass from `base` into *w and returns its size in floats: the size the host is told and the layout
 // the pass uses come from this one walk.  critic_rows: the plan of a pass with separate critic rows (rlppo_ppo_minibatch_critic) -- the
 // critic's gathered rows follow the policy's, so they start on the boundary those do and every other plan is what it was.
-// norm_nets: [norm] bit 0 / 1 = the policy / the critic is normalised -- its normalised activations and its zero bias FOLLOW everything else, so
-// every other region is where it was (rlppo_minibatch_workspace_bytes_norm sizes such a plan).
-// res_nets: [res] the same bits for the residual networks (of two hidden layers or more): behind a network's normalised activations and zero
-// bias (it has one with or without a norm) come the stream of every hidden layer but the first (s_0 is act[0]) and the two alternating
+// ph / vh: the policy's / the critic's hidden layers.  [norm] A normalised network's normalised activations and its zero bias FOLLOW everything
+// else, so every other region is where it was (rlppo_minibatch_workspace_bytes_norm sizes such a plan).  [res] Behind them (a residual network
+// has the zero bias with or without a norm) come the stream of every hidden layer but the first (s_0 is act[0]) and the two alternating
 // buffers of the stream's gradient (rlppo_minibatch_workspace_bytes_res sizes such a plan).
 static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t mb, int prec, void *base, WsPlan *w, bool critic_rows,
-                             int norm_nets = 0, int res_nets = 0) {
+                             const HiddenSpec &ph = {}, const HiddenSpec &vh = {}) {
     const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
     const size_t rows = (size_t)mb;
     size_t off = 0, slack = 0;  // floats from the base; the unused part of the pad reserves
@@ -150,10 +149,11 @@ static size_t plan_workspace(const NetLayout &pol, const NetLayout &val, int64_t
         for (int i = 0; i < 2; ++i)
             for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->dxb[l] = take16(rows * nets[i]->L[l].pout);
     }
-    if (norm_nets | res_nets) {  // (16-byte loads: the row counts above need not be multiples of 4)
+    if (ph.norm || ph.res || vh.norm || vh.res) {  // (16-byte loads: the row counts above need not be multiples of 4)
         align(4, B16_PAD_RESERVE);
+        const HiddenSpec *hidden[2] = {&ph, &vh};
         for (int i = 0; i < 2; ++i) {
-            const bool normed = norm_nets >> i & 1, res = res_nets >> i & 1;
+            const bool normed = hidden[i]->norm, res = hidden[i]->res;
             if (normed)
                 for (int l = 0; l + 1 < nets[i]->n_layers; ++l) ws[i]->norm[l] = take(rows * nets[i]->L[l].pout);
             if (normed || res) ws[i]->zeros = take((size_t)max_pout(*nets[i]));
@@ -242,12 +242,10 @@ struct Pass {
     const float *pol_w, *val_w;  // the packed weights the products read (bf16 precision: their rounded images)
     hipStream_t st, side;        // the policy's and the critic's chain (one stream: rlppo_dbg_set(4, 0))
     DwList *defer;               // [r5] the grouped weight gradients, or null
-    // [act] the hidden activation of each network (HiddenAct), and whether the pass is the PLAIN form: two chains on gathered rows,
-    // dX by the saved activation -- no bitmasks, no folded value head, no paired launches, no gather-fused first layer.  A pass with
-    // a tanh / ELU network is plain (that machinery is ReLU by construction); rlppo_dbg_set(19, 0) makes a ReLU pass plain too.
-    int pol_act = ACT_RELU, val_act = ACT_RELU;
-    int pol_norm = 0, val_norm = 0;  // [norm] layer normalisation behind every hidden activation of the network: a plain pass too
-    int pol_res = 0, val_res = 0;    // [res] the skip stream (a network of two hidden layers or more that carries RLPPO_ACT_RES): a plain pass too
+    // the hidden layers of each network, and whether the pass is the PLAIN form: two chains on gathered rows, dX by the saved activation --
+    // no bitmasks, no folded value head, no paired launches, no gather-fused first layer.  A pass with a network that is not plain ReLU
+    // layers (HiddenSpec::plain_only) or with a categorical critic is plain; rlppo_dbg_set(19, 0) makes a ReLU pass plain too.
+    HiddenSpec pol_h, val_h;
     bool plain = false;
     bool has_bins = false;  // [vbins] a categorical critic (rlppo_ppo_minibatch_vbins): a plain pass whose critic ends in `bins.n` logits
     BinSpec bins;
@@ -266,11 +264,9 @@ static Chain pass_chain(const Pass &p, bool critic) {
     c.in_b = p.w.states_b;
     c.n = p.mb;
     c.out_tanh = !critic && a.head == RLPPO_HEAD_GAUSSIAN;
-    c.hidden_act = critic ? p.val_act : p.pol_act;
-    c.hidden_norm = critic ? p.val_norm : p.pol_norm;
-    c.hidden_res = critic ? p.val_res : p.pol_res;
+    c.hidden = critic ? p.val_h : p.pol_h;
     c.b = critic ? p.w.val : p.w.pol;
-    if (p.plain)  // [act] the plain form: no bitmasks
+    if (p.plain)  // the plain form: no bitmasks
         for (auto &bits : c.b.bits) bits = nullptr;
     c.grad = critic ? a.val_grad : a.pol_grad;
     c.defer = p.defer;
@@ -493,11 +489,22 @@ struct PassOpts {
     int32_t md_heads = 0;
     DiagHead diag;  // [diag] the diagonal-Gaussian head's parameter, gradient and scratch, when has_diag
     bool has_diag = false;
-    int pol_act = ACT_RELU, val_act = ACT_RELU;  // [act] the hidden activations, [norm] each with or without RLPPO_ACT_NORM
+    int pol_act = ACT_RELU, val_act = ACT_RELU;  // the hidden layers' wire fields (HiddenSpec)
     const rlppo_critic_rows *critic = nullptr;   // [critic rows] the critic's own row matrix: non-null only with critic->states set
     const float *vnorm = nullptr;                // [vnorm] the value statistic's scale
     const rlppo_value_bins *bins = nullptr;      // [vbins] the categorical critic's bins
 };
+
+// the bf16 and split-bf16 update precisions carry the ReLU bitmask by construction and have no place for the row kernels
+static int fp32_only_check(const HiddenSpec &ph, const HiddenSpec &vh, int prec) {
+    const char *name = prec == 1 ? "bf16" : "x3", *kernels = prec == 1 ? "bf16" : "split-bf16";
+    RLPPO_CHECK_ARG(ph.act == ACT_RELU && vh.act == ACT_RELU, "ppo_minibatch: hidden activation %s with update precision %s: the %s kernels are ReLU only (use fp32)",
+                    hidden_act_name(ph.act != ACT_RELU ? ph.act : vh.act), name, kernels);
+    const bool normed = ph.norm || vh.norm;
+    RLPPO_CHECK_ARG(!normed && !ph.res_asked && !vh.res_asked, "ppo_minibatch: %s with update precision %s: the %s kernels have no place for the row kernels (use fp32)",
+                    normed ? "hidden layer normalisation (RLPPO_ACT_NORM)" : "residual hidden layers (RLPPO_ACT_RES)", name, kernels);
+    return 0;
+}
 
 static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const PassOpts &o) {
     // ---- validation: every argument error is reported here, before the first HIP call
@@ -516,27 +523,12 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
     // [r5] the precision is an argument of the call (two learners of one process may differ); the process-wide switch is its default
     rc = resolve_precision(a->precision, &p.prec);
     if (rc) return rc;
-    // [act] the hidden activations: tanh / ELU passes are fp32 (the bf16 and split-bf16 kernels carry the ReLU bitmask by construction)
-    int pol_res = 0, val_res = 0;  // (the flag as given: what is refused goes by it, what runs by whether the network has a skip at all)
-    RLPPO_CHECK_ARG(hidden_act_split(o.pol_act, &p.pol_act, &p.pol_norm, &pol_res) && hidden_act_split(o.val_act, &p.val_act, &p.val_norm, &val_res),
+    RLPPO_CHECK_ARG(hidden_spec_decode(o.pol_act, pol, &p.pol_h) && hidden_spec_decode(o.val_act, val, &p.val_h),
                     "ppo_minibatch: pol_hidden_act=%d val_hidden_act=%d (0 = ReLU, 1 = tanh, 2 = ELU)", o.pol_act, o.val_act);
-    const bool non_relu = p.pol_act != ACT_RELU || p.val_act != ACT_RELU;
-    RLPPO_CHECK_ARG(!(non_relu && p.prec != 0), "ppo_minibatch: hidden activation %s with update precision %s: the %s kernels are ReLU only (use fp32)",
-                    hidden_act_name(p.pol_act != ACT_RELU ? p.pol_act : p.val_act), p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
-    // [norm] a normalised network: fp32 passes in the plain form, rows of at most RLPPO_NORM_MAX_WIDTH floats
-    const bool normed = p.pol_norm || p.val_norm;
-    RLPPO_CHECK_ARG(!(normed && p.prec != 0), "ppo_minibatch: hidden layer normalisation (RLPPO_ACT_NORM) with update precision %s: the %s kernels have "
-                    "no place for the row kernels (use fp32)", p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
-    RLPPO_CHECK_ARG((!p.pol_norm || norm_width_ok(pol)) && (!p.val_norm || norm_width_ok(val)),
-                    "ppo_minibatch: hidden layer normalisation of a layer wider than RLPPO_NORM_MAX_WIDTH = %d (padded)", RLPPO_NORM_MAX_WIDTH);
-    // [res] a residual network: the same, and hidden layers of one width (the checks name the option; before the first HIP call)
-    RLPPO_CHECK_ARG(!((pol_res || val_res) && p.prec != 0), "ppo_minibatch: residual hidden layers (RLPPO_ACT_RES) with update precision %s: the %s kernels "
-                    "have no place for the row kernels (use fp32)", p.prec == 1 ? "bf16" : "x3", p.prec == 1 ? "bf16" : "split-bf16");
-    if (pol_res && (rc = res_net_check("ppo_minibatch: the policy", pol))) return rc;
-    if (val_res && (rc = res_net_check("ppo_minibatch: the critic", val))) return rc;
-    p.pol_res = pol_res && res_applies(pol);
-    p.val_res = val_res && res_applies(val);
-    const bool resid = p.pol_res || p.val_res;
+    if (p.prec != 0 && (rc = fp32_only_check(p.pol_h, p.val_h, p.prec))) return rc;
+    const HiddenNet hidden[2] = {{p.pol_h, pol, "ppo_minibatch: the policy"}, {p.val_h, val, "ppo_minibatch: the critic"}};
+    if ((rc = hidden_spec_widths("ppo_minibatch", hidden, 2))) return rc;
+    const bool normed = p.pol_h.norm || p.val_h.norm, resid = p.pol_h.res || p.val_h.res;
     // [vbins] a categorical critic: its bins, and an fp32 pass in the plain form (no folded head, no matrix-vector head: an ordinary last layer)
     if (o.bins) {
         rc = value_bins_make(o.bins, "ppo_minibatch_vbins", &p.bins);
@@ -547,7 +539,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
         RLPPO_CHECK_ARG(!(a->value_clip > 0.f), "ppo_minibatch_vbins: value_clip=%g with a categorical critic (bins): clipping a distribution is undefined",
                         (double)a->value_clip);
     }
-    p.plain = non_relu || normed || resid || p.has_bins || (p.prec == 0 && !g_relu_bits);
+    p.plain = p.pol_h.plain_only() || p.val_h.plain_only() || p.has_bins || (p.prec == 0 && !g_relu_bits);
     RLPPO_CHECK_ARG(mb > 0 && a->pol_packed && a->val_packed && a->pol_grad && a->val_grad && a->states && a->actions &&
                         a->old_logp && a->targets && a->advantages && a->idx && a->stats && a->workspace,
                     "ppo_minibatch: null pointer");
@@ -567,8 +559,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
     }
     RLPPO_CHECK_ARG(a->ld_states >= pol.L[0].pin && a->ld_states % 4 == 0, "ppo_minibatch: ld_states=%ld < %d",
                     (long)a->ld_states, pol.L[0].pin);
-    const size_t ws_bytes = plan_workspace(pol, val, mb, p.prec, a->workspace, &p.w, critic != nullptr, p.pol_norm | p.val_norm << 1,
-                                           p.pol_res | p.val_res << 1) * sizeof(float);
+    const size_t ws_bytes = plan_workspace(pol, val, mb, p.prec, a->workspace, &p.w, critic != nullptr, p.pol_h, p.val_h) * sizeof(float);
     if (a->ws_bytes < ws_bytes) {
         set_error("ppo_minibatch: workspace %zu < %zu bytes%s", a->ws_bytes, ws_bytes,
                   resid    ? " (residual hidden layers: rlppo_minibatch_workspace_bytes_res)"
@@ -701,15 +692,16 @@ static int ppo_minibatch_opts(void *stream, const rlppo_minibatch_args *a, const
     return ppo_minibatch(stream, a, o);
 }
 
+// pol_field / val_field: the hidden layers' wire fields; res_ok: the form sizes residual networks (else RLPPO_ACT_RES is a bad field).  0: a bad field
 static size_t workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers, int64_t mb,
-                              int32_t precision, bool critic_rows, int norm_nets = 0, int res_nets = 0) {
+                              int32_t precision, bool critic_rows, int32_t pol_field = ACT_RELU, int32_t val_field = ACT_RELU, bool res_ok = true) {
     NetLayout pol, val;
+    HiddenSpec ph, vh;
     int prec = 0;
     if (make_layout(pol_dims, pol_layers, &pol) || make_layout(val_dims, val_layers, &val) || resolve_precision(precision, &prec)) return 0;
+    if (!hidden_spec_decode(pol_field, pol, &ph) || !hidden_spec_decode(val_field, val, &vh) || (!res_ok && (ph.res_asked || vh.res_asked))) return 0;
     WsPlan unused;
-    if (!res_applies(pol)) res_nets &= ~1;
-    if (!res_applies(val)) res_nets &= ~2;
-    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused, critic_rows, norm_nets, res_nets) * sizeof(float) + 256;
+    return plan_workspace(pol, val, mb > 0 ? mb : 0, prec, nullptr, &unused, critic_rows, ph, vh) * sizeof(float) + 256;
 }
 
 extern "C" {
@@ -725,16 +717,12 @@ size_t rlppo_minibatch_workspace_bytes_critic(const int32_t *pol_dims, int32_t p
 // [norm] the plan of _for / _critic (critic_rows != 0) + what the networks whose activation field carries RLPPO_ACT_NORM add; 0: a bad field
 size_t rlppo_minibatch_workspace_bytes_norm(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
                                             int64_t mb, int32_t precision, int32_t critic_rows, int32_t pol_hidden_act, int32_t val_hidden_act) {
-    int pa, pn, pr, va, vn, vr;
-    if (!hidden_act_split(pol_hidden_act, &pa, &pn, &pr) || !hidden_act_split(val_hidden_act, &va, &vn, &vr) || pr || vr) return 0;
-    return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, critic_rows != 0, pn | vn << 1);
+    return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, critic_rows != 0, pol_hidden_act, val_hidden_act, false);
 }
 // [res] ... + what the networks whose field carries RLPPO_ACT_RES add (without the bit in either field it equals _norm)
 size_t rlppo_minibatch_workspace_bytes_res(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims, int32_t val_layers,
                                            int64_t mb, int32_t precision, int32_t critic_rows, int32_t pol_hidden_act, int32_t val_hidden_act) {
-    int pa, pn, pr, va, vn, vr;
-    if (!hidden_act_split(pol_hidden_act, &pa, &pn, &pr) || !hidden_act_split(val_hidden_act, &va, &vn, &vr)) return 0;
-    return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, critic_rows != 0, pn | vn << 1, pr | vr << 1);
+    return workspace_bytes(pol_dims, pol_layers, val_dims, val_layers, mb, precision, critic_rows != 0, pol_hidden_act, val_hidden_act);
 }
 size_t rlppo_minibatch_workspace_bytes(const int32_t *pol_dims, int32_t pol_layers, const int32_t *val_dims,
                                        int32_t val_layers, int64_t mb) {

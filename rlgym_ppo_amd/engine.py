@@ -259,17 +259,14 @@ class NetArena:
         opts.hidden_act = self.hidden_act
         return opts
 
+    # (the _act / _res forms equal the plain ones for an arena without RLPPO_ACT_RES: tests/test_hidden_spec_host.py)
     def forward_ws_bytes(self, n):
-        """The workspace of a layer-chain call on n rows (a residual arena: sized by the function that knows the flag)."""
-        if self.hidden_act & N.ACT_RES:
-            return int(N.lib().rlppo_forward_workspace_bytes_act(self.dims_c, self.n_layers, n, self.hidden_act))
-        return int(N.lib().rlppo_forward_workspace_bytes(self.dims_c, self.n_layers, n))
+        """The workspace of a layer-chain call on n rows."""
+        return int(N.lib().rlppo_forward_workspace_bytes_act(self.dims_c, self.n_layers, n, self.hidden_act))
 
     def step_ws_bytes(self, n):
         """... of rlppo_discrete_step."""
-        if self.hidden_act & N.ACT_RES:
-            return int(N.lib().rlppo_discrete_step_workspace_bytes_act(self.dims_c, self.n_layers, n, self.hidden_act))
-        return int(N.lib().rlppo_discrete_step_workspace_bytes(self.dims_c, self.n_layers, n))
+        return int(N.lib().rlppo_discrete_step_workspace_bytes_act(self.dims_c, self.n_layers, n, self.hidden_act))
 
     def forward_ws(self, n):
         return self.ws.get(self.forward_ws_bytes(n))
@@ -280,10 +277,8 @@ class NetArena:
         n = obs_padded.shape[0]
         out = torch.empty((n, self.ld_out), dtype=torch.float32, device=self.device)
         ws = self.forward_ws(n)
-        # (a residual arena: the entry point whose workspace forward_ws_bytes sized -- rlppo_mlp_forward keeps refusing the flag)
-        fwd = N.lib().rlppo_mlp_forward_res if self.hidden_act & N.ACT_RES else N.lib().rlppo_mlp_forward
-        N.check(fwd(stream_ptr(), self.dims_c, self.n_layers, ptr(self.packed), ptr(obs_padded),
-                    obs_padded.shape[1], n, int(out_tanh), ptr(out), self.ld_out, ptr(ws), ws.numel(), self.act_opts()))
+        N.check(N.lib().rlppo_mlp_forward_res(stream_ptr(), self.dims_c, self.n_layers, ptr(self.packed), ptr(obs_padded),
+                                              obs_padded.shape[1], n, int(out_tanh), ptr(out), self.ld_out, ptr(ws), ws.numel(), self.act_opts()))
         return out
 
 

@@ -104,20 +104,21 @@ class Learner(object):
         if hidden_layer_norm not in (False, True, "policy", "critic"):
             raise ValueError(f"hidden_layer_norm must be False, True, 'policy' or 'critic', got {hidden_layer_norm!r}")
 
+        def agreed(name, own, shown, asked, keyword, value):   # value: the keyword as given, false at its default; asked: what it asks of `name`
+            # the sizes keep their own setting while the keyword is at its default, and otherwise must agree with what it asks of them
+            if own and value and own != asked:
+                raise ValueError(f"{name} is LayerSizes(..., {shown}{own!r}) but {keyword}={value!r}: give one of them")
+            return own or asked
+
         def with_activation(name, sizes):
-            own = getattr(sizes, "activation", None)
-            if own is not None and own != hidden_activation and hidden_activation != "relu":
-                raise ValueError(f"{name} is LayerSizes(..., {own!r}) but hidden_activation={hidden_activation!r}: give one of them")
-            asked = "layer" if hidden_layer_norm is True or (hidden_layer_norm and name.startswith(hidden_layer_norm)) else None
-            own_norm = getattr(sizes, "norm", None)
-            if own_norm is not None and asked is None and hidden_layer_norm:
-                raise ValueError(f"{name} is LayerSizes(..., norm={own_norm!r}) but hidden_layer_norm={hidden_layer_norm!r}: give one of them")
-            asked_res = hidden_residual is True or bool(hidden_residual and name.startswith(hidden_residual))
-            own_res = getattr(sizes, "residual", False)
-            if own_res and not asked_res and hidden_residual:
-                raise ValueError(f"{name} is LayerSizes(..., residual=True) but hidden_residual={hidden_residual!r}: give one of them")
-            return LayerSizes(sizes, own if own is not None else hidden_activation, own_norm or asked, getattr(sizes, "value_head", None),
-                              own_res or asked_res)
+            asks = lambda value: value is True or bool(value and name.startswith(value))   # True | "policy" | "critic": this network?
+            return LayerSizes(sizes,
+                              # (the default IS "relu": only another name counts as given)
+                              agreed(name, getattr(sizes, "activation", None), "", hidden_activation, "hidden_activation",
+                                     None if hidden_activation == "relu" else hidden_activation),
+                              agreed(name, getattr(sizes, "norm", None), "norm=", "layer" if asks(hidden_layer_norm) else None, "hidden_layer_norm", hidden_layer_norm),
+                              getattr(sizes, "value_head", None),
+                              agreed(name, getattr(sizes, "residual", False), "residual=", asks(hidden_residual), "hidden_residual", hidden_residual))
         sizes_given = (policy_layer_sizes, critic_layer_sizes)   # (what the config dict logs, as it always did)
         policy_layer_sizes = with_activation("policy_layer_sizes", policy_layer_sizes)
         critic_layer_sizes = with_activation("critic_layer_sizes", critic_layer_sizes)
@@ -144,34 +145,20 @@ class Learner(object):
                               "left at its default (-10, 10) -- value targets outside it are clamped", RuntimeWarning, stacklevel=2)
         self.value_head = critic_layer_sizes.value_head
         if self.value_head is not None:
-            from . import engine
             if ppo_value_clip_range is not None:
                 raise ValueError(f"ppo_value_clip_range={ppo_value_clip_range!r} with a categorical value head (ppo_value_head / value_head): "
                                  "clipping a distribution is undefined")
             if ppo_value_norm_popart:
                 raise ValueError("ppo_value_norm_popart=True with a categorical value head (ppo_value_head / value_head): rescaling a last "
                                  "layer of logits preserves nothing")
-            if engine.update_precision() != "fp32":
-                raise ValueError(f"ppo_value_head with update precision {engine.update_precision()!r}: the {engine.update_precision()} update "
-                                 "kernels are ReLU only -- use engine.set_update_precision('fp32')")
         self.hidden_norms = {"policy": policy_layer_sizes.norm, "critic": critic_layer_sizes.norm}
-        if any(self.hidden_norms.values()):
-            from . import engine
-            if engine.update_precision() != "fp32":
-                raise ValueError(f"hidden_layer_norm with update precision {engine.update_precision()!r}: the {engine.update_precision()} update "
-                                 "kernels have no place for the row kernels -- use engine.set_update_precision('fp32')")
-            if engine.inference_precision() == "bf16":
-                raise ValueError("hidden_layer_norm with the bf16 inference precision: the bf16-operand kernels feed the next product "
-                                 "without the row kernel -- use engine.set_inference_precision('fp32')")
         self.hidden_residuals = {"policy": policy_layer_sizes.residual, "critic": critic_layer_sizes.residual}
-        if any(self.hidden_residuals.values()):
-            from . import engine
-            if engine.update_precision() != "fp32":
-                raise ValueError(f"hidden_residual with update precision {engine.update_precision()!r}: the {engine.update_precision()} update "
-                                 "kernels have no place for the row kernels -- use engine.set_update_precision('fp32')")
-            if engine.inference_precision() == "bf16":
-                raise ValueError("hidden_residual with the bf16 inference precision: the bf16-operand kernels feed the next product "
-                                 "without the row kernel -- use engine.set_inference_precision('fp32')")
+        from . import engine
+        from .ppo._mlp import check_precisions
+        # (the dict's order is the precedence of the refusals, its values this constructor's names for the options)
+        check_precisions([(s.activation, s.norm, s.residual) for s in (policy_layer_sizes, critic_layer_sizes)], self.value_head, engine.update_precision,
+                         engine.inference_precision, {"value_head": "ppo_value_head", "norm": "hidden_layer_norm", "residual": "hidden_residual"},
+                         "engine.set_update_precision('fp32')")
         # what was built, per network; and as one name where both agree (the keyword's own type), None where they differ
         self.hidden_activations = {"policy": policy_layer_sizes.activation, "critic": critic_layer_sizes.activation}
         self.hidden_activation = policy_layer_sizes.activation if policy_layer_sizes.activation == critic_layer_sizes.activation else None

@@ -36,8 +36,13 @@ def check_norm(norm):
     return norm
 
 
-def check_residual_widths(sizes):
-    """Residual hidden layers add into one stream: every hidden width equals the first and fits a row kernel; ValueError otherwise."""
+def check_row_widths(sizes, norm, residual):
+    """The hidden widths a row kernel accepts; ValueError otherwise.  norm: every width fits a row kernel.  residual: the layers add into
+    one stream -- every width equals the first, and that one fits."""
+    if norm and max(int(size) for size in sizes) > N.NORM_MAX_WIDTH:
+        raise ValueError(f"hidden layer normalisation of a layer wider than {N.NORM_MAX_WIDTH} (RLPPO_NORM_MAX_WIDTH)")
+    if not residual:
+        return
     for l, size in enumerate(sizes):
         if int(size) != int(sizes[0]):
             raise ValueError(f"residual hidden layers need equal hidden widths: hidden layer {l} has {int(size)} outputs, hidden layer 0 has "
@@ -45,6 +50,35 @@ def check_residual_widths(sizes):
     if len(sizes) and int(sizes[0]) > N.NORM_MAX_WIDTH:
         raise ValueError(f"residual hidden layers of a layer wider than {N.NORM_MAX_WIDTH} (RLPPO_NORM_MAX_WIDTH): the row kernels hold a row "
                          "of the stream in registers")
+
+
+def act_code(activation, norm, residual):
+    """The RLPPO_ACT_* code of hidden layers: what rlppo_act_opts.hidden_act and rlppo_minibatch_ext.*_hidden_act carry."""
+    return N.HIDDEN_ACTIVATIONS[activation] | (N.ACT_NORM if norm else 0) | (N.ACT_RES if residual else 0)
+
+
+def check_precisions(specs, value_head, update_precision, inference_precision, subjects, use):
+    """What the options of a pair of networks refuse of the precisions; ValueError in the caller's words and order of precedence.
+    specs: (activation, norm, residual) per network; value_head: the critic's ValueBins or None.  update_precision / inference_precision:
+    () -> name, asked only where an option is present; inference_precision None: not this caller's to check.  subjects: option
+    ("activation", "norm", "residual", "value_head") -> how the caller names it ({act!r}: the first activation that is not ReLU), in its
+    order of precedence.  use: the remedy the caller names for the update precision.  A tanh / ELU network and a categorical critic
+    update in fp32 (the bf16 and split-bf16 kernels carry the ReLU bitmask by construction); a normalised or residual one besides runs
+    its rollout in fp32 (the other chains have no place for the row kernels)."""
+    acts = sorted({a for a, _, _ in specs} - {"relu"})
+    present = {"activation": bool(acts), "norm": any(n for _, n, _ in specs), "residual": any(r for _, _, r in specs),
+               "value_head": value_head is not None}
+    for option, subject in subjects.items():
+        if not present[option]:
+            continue
+        subject, rows = subject.format(act=acts[0] if acts else None), option in ("norm", "residual")
+        prec = update_precision()
+        if prec != "fp32":
+            raise ValueError(f"{subject} with update precision {prec!r}: the {prec} update kernels "
+                             f"{'have no place for the row kernels' if rows else 'are ReLU only'} -- use {use}")
+        if rows and inference_precision is not None and inference_precision() == "bf16":
+            raise ValueError(f"{subject} with the bf16 inference precision: the bf16-operand kernels feed the next product without the row kernel "
+                             "-- use engine.set_inference_precision('fp32')")
 
 
 class ValueBins:
@@ -108,12 +142,15 @@ class LayerSizes(tuple):
         if residual not in (False, True):
             raise ValueError(f"residual must be False or True, got {residual!r}")
         self.residual = bool(residual)
-        if self.residual:
-            check_residual_widths(self)
+        check_row_widths(self, None, self.residual)
         return self
 
     def __reduce__(self):
         return (LayerSizes, (tuple(self), self.activation, self.norm, self.value_head, self.residual))
+
+    def act_code(self):
+        """The RLPPO_ACT_* code of these hidden layers: what rlppo_act_opts.hidden_act and rlppo_minibatch_ext.*_hidden_act carry."""
+        return act_code(self.activation, self.norm, self.residual)
 
     def __repr__(self):
         tail = (f", norm={self.norm!r}" if self.norm else "") + (f", value_head={self.value_head!r}" if self.value_head else "")
@@ -134,18 +171,20 @@ class ActNorm(nn.Module):
         return nn.functional.layer_norm(self.act(x), (self.width,), eps=1e-5)
 
 
-def activation_of(module):
-    """The hidden activation's name of a body build_body made (index 1 of the Sequential is the first hidden activation)."""
-    first = module[1].act if isinstance(module[1], ActNorm) else module[1]
+def body_spec(module):
+    """(activation name, "layer" or None, whether it runs the skip stream) of a body build_body made (index 1 of the Sequential is the
+    first hidden activation)."""
+    normed = isinstance(module[1], ActNorm)
+    first = module[1].act if normed else module[1]
     for name, cls in HIDDEN_MODULES.items():
         if type(first) is cls:
-            return name
+            return name, "layer" if normed else None, isinstance(module, ResidualBody)
     raise ValueError(f"hidden activation {type(first).__name__} has no kernels (build_body makes {sorted(HIDDEN_MODULES)})")
 
 
-def norm_of(module):
-    """The hidden normalisation of a body build_body made: "layer" or None."""
-    return "layer" if isinstance(module[1], ActNorm) else None
+def activation_of(module): return body_spec(module)[0]   # (the three readers body_spec replaced, by their old names)
+def norm_of(module): return body_spec(module)[1]
+def residual_of(module): return body_spec(module)[2]
 
 
 class ResidualBody(nn.Sequential):
@@ -170,11 +209,6 @@ class ResidualBody(nn.Sequential):
         return x
 
 
-def residual_of(module):
-    """Whether a body build_body made runs the skip stream."""
-    return isinstance(module, ResidualBody)
-
-
 def build_body(input_shape, layer_sizes, n_out, final_activation=None, critic=False):
     assert len(layer_sizes) != 0, "AT LEAST ONE LAYER MUST BE SPECIFIED TO BUILD THE NEURAL NETWORK!"
     if getattr(layer_sizes, "value_head", None) is not None and not critic:   # (ValueEstimator alone builds with critic=True)
@@ -195,7 +229,7 @@ def build_body(input_shape, layer_sizes, n_out, final_activation=None, critic=Fa
     if final_activation is not None:
         layers.append(final_activation)
     if getattr(layer_sizes, "residual", False):   # (the same modules, indices and draws: only forward() differs)
-        check_residual_widths(tuple(layer_sizes))
+        check_row_widths(tuple(layer_sizes), None, True)
         return ResidualBody(*layers)
     return nn.Sequential(*layers)
 
@@ -520,16 +554,11 @@ class ArenaModule(nn.Module):
         dev = require_gpu(device)
         self.model = self.model.to(dev)
         # (a head's parameters that are not a layer -- DiagGaussianPolicy.log_std -- ride in the arena's tail)
-        self.hidden_activation = activation_of(self.model)
-        self.hidden_norm = norm_of(self.model)
-        if self.hidden_norm and max(l.out_features for l in linears_of(self.model)[:-1]) > N.NORM_MAX_WIDTH:
-            raise ValueError(f"hidden layer normalisation of a layer wider than {N.NORM_MAX_WIDTH} (RLPPO_NORM_MAX_WIDTH)")
-        self.hidden_residual = residual_of(self.model)
-        if self.hidden_residual:   # (a body built by hand: build_body has checked its own)
-            check_residual_widths([l.out_features for l in linears_of(self.model)[:-1]])
+        self.hidden_activation, self.hidden_norm, self.hidden_residual = body_spec(self.model)
+        widths = [l.out_features for l in linears_of(self.model)[:-1]]   # (a body built by hand: build_body has checked its own)
+        check_row_widths(widths, self.hidden_norm, self.hidden_residual)
         self.arena = NetArena(linears_of(self.model), dev, tail=getattr(self, "_arena_tail", ()),
-                              hidden_act=N.HIDDEN_ACTIVATIONS[self.hidden_activation] | (N.ACT_NORM if self.hidden_norm else 0)
-                              | (N.ACT_RES if self.hidden_residual else 0))
+                              hidden_act=act_code(self.hidden_activation, self.hidden_norm, self.hidden_residual))
         self.act_graphs = True  # get_action through a hipGraph per batch-size bucket (False: every call takes the general path)
         self.act_graph_max = 1024  # beyond that the explicit copies of the eager path are the better transport for the noise
         self._graphs = {}

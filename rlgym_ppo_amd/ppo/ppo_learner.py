@@ -56,6 +56,7 @@ from ..dp import all_reduce_sum, dist_info, fuse_runs, slices_for_rank
 from ..engine import Workspace, ptr, require_gpu, stream_ptr
 from ..util import action_mask as AM
 from . import lr_schedule as LRS
+from ._mlp import check_precisions
 from .continuous_policy import ContinuousPolicy
 from .diag_gaussian_policy import DiagGaussianPolicy
 from .discrete_policy import DiscreteFF
@@ -450,12 +451,9 @@ class PPOLearner(object):
         n_slices = self.batch_size // self.mini_batch_size
         runs = fuse_runs(slices_for_rank(max(1, n_slices), rank, world), self.max_fused_minibatches)
         self._fused_rows = self.mini_batch_size * max([cnt for _, cnt in runs] or [1])
-        size_fn = N.lib().rlppo_minibatch_workspace_bytes_for if cr is None else N.lib().rlppo_minibatch_workspace_bytes_critic
-        if (pa.hidden_act | va.hidden_act) & N.ACT_NORM:   # a normalised network: the same plan + its normalised activations
-            size_fn = lambda *dims: N.lib().rlppo_minibatch_workspace_bytes_norm(*dims, int(cr is not None), pa.hidden_act, va.hidden_act)
-        if (pa.hidden_act | va.hidden_act) & N.ACT_RES:    # a residual network: + its stream and the stream's two gradient buffers
-            size_fn = lambda *dims: N.lib().rlppo_minibatch_workspace_bytes_res(*dims, int(cr is not None), pa.hidden_act, va.hidden_act)
-        nbytes = int(size_fn(pa.dims_c, pa.n_layers, va.dims_c, va.n_layers, self._fused_rows, a.precision))
+        # (the widest form: without the bits it is the plan of _norm, and of _for / _critic -- tests/test_hidden_spec_host.py)
+        nbytes = int(N.lib().rlppo_minibatch_workspace_bytes_res(pa.dims_c, pa.n_layers, va.dims_c, va.n_layers, self._fused_rows, a.precision,
+                                                                 int(cr is not None), pa.hidden_act, va.hidden_act))
         nbytes = (nbytes + 255) // 256 * 256
         ws = self._ws.get(nbytes * self.n_slots)
         self._slot_ws = [ws.data_ptr() + i * nbytes for i in range(self.n_slots)]
@@ -533,25 +531,15 @@ class PPOLearner(object):
         if critic_rows and self._precision() == "bf16":
             raise ValueError("update_precision='bf16' with separate critic observations (ObsSizes / critic_states): the "
                              "bf16 gather writes one bf16 image, of the policy's rows -- use 'fp32' or 'x3'")
-        # a tanh / ELU network updates in fp32: the bf16 and split-bf16 kernels carry the ReLU bitmask by construction
-        acts = {m.hidden_activation for m in (self.policy, self.value_net)} - {"relu"}
-        prec = self._precision() if acts else "fp32"
-        if prec != "fp32":
-            raise ValueError(f"hidden activation {sorted(acts)[0]!r} with update precision {prec!r}: the {prec} update kernels are ReLU "
-                             "only -- use update_precision='fp32'")
-        # a normalised network updates in fp32 too: the bf16 and split-bf16 chains have no place for the row kernels
-        if any(getattr(m, "hidden_norm", None) for m in (self.policy, self.value_net)) and self._precision() != "fp32":
-            raise ValueError(f"hidden layer normalisation with update precision {self._precision()!r}: the {self._precision()} update kernels "
-                             "have no place for the row kernels -- use update_precision='fp32'")
-        if any(getattr(m, "hidden_residual", False) for m in (self.policy, self.value_net)) and self._precision() != "fp32":
-            raise ValueError(f"residual hidden layers with update precision {self._precision()!r}: the {self._precision()} update kernels "
-                             "have no place for the row kernels -- use update_precision='fp32'")
-        # a categorical critic (LayerSizes(..., value_head=ValueBins)) updates in fp32 (its pass is the plain form), has nothing to clip
-        # and no last layer whose rescaling would preserve its outputs
-        if getattr(self.value_net, "value_bins", None) is not None:
-            if self._precision() != "fp32":
-                raise ValueError(f"a categorical critic (value_head) with update precision {self._precision()!r}: the {self._precision()} update "
-                                 "kernels are ReLU only -- use update_precision='fp32'")
+        # what the hidden layers and a categorical critic (LayerSizes(..., value_head=ValueBins)) refuse of the update precision
+        # (the dict's order is the precedence of the refusals)
+        bins = getattr(self.value_net, "value_bins", None)
+        check_precisions([(m.hidden_activation, getattr(m, "hidden_norm", None), getattr(m, "hidden_residual", False)) for m in (self.policy, self.value_net)],
+                         bins, self._precision, None, {"activation": "hidden activation {act!r}", "norm": "hidden layer normalisation",
+                                                       "residual": "residual hidden layers", "value_head": "a categorical critic (value_head)"},
+                         "update_precision='fp32'")
+        # a categorical critic has nothing to clip and no last layer whose rescaling would preserve its outputs
+        if bins is not None:
             if self.value_clip_range is not None:
                 raise ValueError(f"value_clip_range={self.value_clip_range!r} with a categorical critic (value_head): clipping a distribution "
                                  "is undefined")

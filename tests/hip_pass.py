@@ -172,7 +172,7 @@ def run_pass(L, pol, val, obs_all, acts_all, old_all, tgt_all, adv_all, idx, *, 
         scratch[sb:] = canary = (torch.arange(SCRATCH_CANARY, device="cuda") * 37 % 251).to(torch.uint8)
     ext = N.MinibatchExt()
     if entry not in ("ex_zero", "ex_null"):
-        ext.pol_hidden_act, ext.val_hidden_act = ACT_CODE[pol_act], ACT_CODE[val_act]
+        ext.pol_hidden_act, ext.val_hidden_act = ACT_CODE.get(pol_act, pol_act), ACT_CODE.get(val_act, val_act)   # (a name, or an RLPPO_ACT_* code with its flags)
         if head == "nvec":
             ext.md_nvec, ext.md_heads = ctypes.cast(nvec, ctypes.POINTER(ctypes.c_int32)), len(bins)
         if head == "diag":
