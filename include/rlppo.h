@@ -434,6 +434,38 @@ int rlppo_gae_norm(void *stream, const float *rews, const float *dones, const fl
                    const float *boot_values, const float *value_scale, int64_t n, double gamma, double lmbda, float return_std,
                    float *value_targets, float *advantages, float *returns, void *workspace, size_t ws_bytes);
 
+/* The V-trace form of the scan (IMPALA's truncated importance weights inside the advantage recurrence; the V-trace option of
+ * rl_games' and Sample Factory's PPO): advantages and value targets of steps drawn by an OLDER policy, under the current critic.
+ * Per step t, with nd = 1 - done[t], nt = 1 - truncated[t] (flags exactly 0.0 or 1.0) and vnext chosen as rlppo_gae_boot chooses it:
+ *     ratio            = expf(logp_new[t] - logp_old[t])                               (float32, in the kernel)
+ *     rho              = min(rho_bar, ratio) ,  c = lambda * min(c_bar, ratio)
+ *     delta            = rho * (clip(r/sigma) + gamma * vnext * nd - values[t])
+ *     adv[t]           = delta + gamma * c * nd * nt * adv[t + 1]                      (adv[n] = 0)
+ *     value_targets[t] = values[t] + adv[t]
+ * logp_new, logp_old: float[n], the log-probability of the step's action under the current policy and under the policy that drew it;
+ * each is read once, the two coefficient arrays are never materialised.  A NaN ratio gives NaN outputs (it is not clipped away).
+ * boot_values (float[n], used at truncated-and-not-done steps only) and value_scale (DEVICE float[4], rlppo_gae_norm's) may each be
+ * NULL.  No returns: the buffer's returns feed the running return statistics only.  logp_new == logp_old with rho_bar = c_bar = 1
+ * has the per-step coefficients of rlppo_gae_boot exactly; the carries are composed in another order, so the outputs agree to
+ * rounding of the float64 recurrence, not bit for bit.
+ * Arithmetic: float32 reward scaling and expf, float64 recurrence, one rounding to float32 at the store.  One launch (chunk scans of
+ * 2048 steps + decoupled look-back over general affine carries (a, b): x -> a*x + b; per-launch record tags shared with rlppo_gae:
+ * the scans may alternate on one workspace); under stream capture, or when the scan has more chunks than workgroups can be resident,
+ * the stateless two-launch form.  A chunk's carry is the in-order composition of the aggregates to its right, whichever form
+ * evaluates it: no floating-point atomics, nothing that depends on timing -- the same inputs give the same bits on every run and in
+ * both forms.  Same workspace (rlppo_gae_workspace_bytes), alignment rules, bounded look-back wait and timeout word as rlppo_gae.
+ * RLPPO_ERR_ARG with a message naming the argument, before any HIP call: rho_bar or c_bar not finite or not positive, n < 0, a NULL
+ * array or workspace, an array that is not 16-byte aligned.  n == 0 does nothing. */
+int rlppo_gae_vtrace(void *stream, const float *rews, const float *dones, const float *truncated, const float *values,
+                     const float *boot_values, const float *value_scale, const float *logp_new, const float *logp_old, int64_t n,
+                     double gamma, double lmbda, double rho_bar, double c_bar, float return_std,
+                     float *value_targets, float *advantages, void *workspace, size_t ws_bytes);
+
+/* How rlppo_gae_vtrace splits the steps: consecutive steps per lane (level 0), per wave (1), per workgroup (2); -1 otherwise.  A
+ * carry crosses one of these boundaries by registers, shuffles and LDS, and look-back records respectively (tests place their
+ * trajectory ends there). */
+int32_t rlppo_gae_vtrace_span(int32_t level);
+
 /* [vnorm] The running statistic of the value targets, advanced by one batch on the device (rl_games' normalize_value / RunningMeanStd;
  * PopArt's statistic; its weight-preserving step is rlppo_value_norm_update_popart below).  targets: DEVICE float[n].  state: DEVICE double[4] = {count, mean, M2, rejected},
  * 8-byte aligned, zero for a fresh statistic.  scale: DEVICE float[4], 16-byte aligned, what rlppo_gae_norm and

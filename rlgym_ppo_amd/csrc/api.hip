@@ -580,6 +580,27 @@ int rlppo_gae_norm(void *stream, const float *rews, const float *dones, const fl
                return_std, value_targets, advantages, returns, workspace, ws_bytes);
 }
 
+int32_t rlppo_gae_vtrace_span(int32_t level) { return gae_vtrace_span(level); }
+
+// the V-trace scan (gae_vtrace.hip): every argument is checked here, by name, before any HIP call
+int rlppo_gae_vtrace(void *stream, const float *rews, const float *dones, const float *truncated, const float *values,
+                     const float *boot_values, const float *value_scale, const float *logp_new, const float *logp_old, int64_t n,
+                     double gamma, double lmbda, double rho_bar, double c_bar, float return_std, float *value_targets, float *advantages,
+                     void *workspace, size_t ws_bytes) {
+    RLPPO_CHECK_ARG(rho_bar > 0.0 && rho_bar <= 1.7976931348623157e308, "gae_vtrace: rho_bar=%g must be finite and positive", rho_bar);
+    RLPPO_CHECK_ARG(c_bar > 0.0 && c_bar <= 1.7976931348623157e308, "gae_vtrace: c_bar=%g must be finite and positive", c_bar);
+    RLPPO_CHECK_ARG(n >= 0, "gae_vtrace: n=%ld < 0", (long)n);
+    if (n == 0) return 0;
+    const struct {
+        const void *p;
+        const char *name;
+    } need[] = {{rews, "rews"}, {dones, "dones"}, {truncated, "truncated"}, {values, "values"}, {logp_new, "logp_new"},
+                {logp_old, "logp_old"}, {value_targets, "value_targets"}, {advantages, "advantages"}, {workspace, "workspace"}};
+    for (const auto &a : need) RLPPO_CHECK_ARG(a.p != nullptr, "gae_vtrace: %s is NULL", a.name);
+    VtraceIO io{rews, dones, truncated, values, logp_new, logp_old, boot_values, value_scale, value_targets, advantages, n};
+    return launch_gae_vtrace((hipStream_t)stream, io, gamma, lmbda, rho_bar, c_bar, return_std, workspace, ws_bytes);
+}
+
 // the two forms of the statistic's update: one check.  who: the form's name in the error text
 static int value_norm_check(const char *who, const float *targets, int64_t n, double *state, float *scale, void *ws) {
     RLPPO_CHECK_ARG(n >= 1, "%s: n=%ld < 1", who, (long)n);

@@ -395,6 +395,21 @@ void set_fused_test_hold(int v);
 //  value_scale or null: [vnorm] the values are normalised ones, V = fmaf(v, value_scale[2], value_scale[0]))
 int launch_gae(hipStream_t, const float *, const float *, const float *, const float *, const float *, int64_t, double, double, float,
                float *, float *, float *, void *, size_t, const float *value_scale = nullptr);
+unsigned gae_next_tag();    // per-launch record tag of a look-back scan: one counter for every scan on a GAE workspace
+int gae_algo();             // rlppo_dbg_set(1, v): 0 = the stateless two-launch form always
+unsigned gae_spin_limit();  // rlppo_dbg_set(21, v): bound of a look-back wait
+
+// gae_vtrace.hip: the V-trace scan (per-step data-dependent decay) --------------------------------------
+struct VtraceIO {
+    const float *rews, *dones, *trunc, *values, *logp_new, *logp_old;
+    const float *boot;    // null: no step takes a bootstrap value of its own
+    const float *vscale;  // null: `values` / `boot` are real-unit values
+    float *vt, *adv;
+    int64_t n;
+};
+int launch_gae_vtrace(hipStream_t st, const VtraceIO &io, double gamma, double lmbda, double rho_bar, double c_bar, float ret_std,
+                      void *ws, size_t ws_bytes);
+int gae_vtrace_span(int level);  // steps per lane / wave / workgroup of that scan
 
 // pack.hip: the kernels' weight copies ----------------------------------------------------------------
 struct PackJob {  // one layer: where its W / W^T / b live in the packed copy and in the flat arena

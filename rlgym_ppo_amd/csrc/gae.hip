@@ -665,6 +665,21 @@ static std::atomic<unsigned> g_tag{0};  // per-launch record tags (launch_gae_fo
 static unsigned g_gae_spin_limit = LB_SPIN_LIMIT;  // rlppo_dbg_set(21, v): tests set 0 to force the timeout path
 void set_gae_spin_limit(int v) { g_gae_spin_limit = v < 0 ? LB_SPIN_LIMIT : (unsigned)v; }
 
+// One tag counter and one set of debug settings for every scan that keeps look-back records in a GAE workspace (gae_vtrace.hip
+// draws from them too: two scans may follow each other on one workspace and must never take each other's records for their own).
+unsigned gae_next_tag() {
+    if (g_tag.load(std::memory_order_relaxed) == 0) {
+        unsigned expect = 0;
+        const unsigned seed = (unsigned)std::chrono::steady_clock::now().time_since_epoch().count() | 1u;
+        g_tag.compare_exchange_strong(expect, seed);
+    }
+    unsigned tag = g_tag.fetch_add(1, std::memory_order_relaxed) + 1;
+    if (tag == 0) tag = g_tag.fetch_add(1, std::memory_order_relaxed) + 1;
+    return tag;
+}
+int gae_algo() { return g_gae_algo; }
+unsigned gae_spin_limit() { return g_gae_spin_limit; }
+
 // workspace: [0,16) header: word 1 = number of look-back waits that timed out (their chunks' outputs are NaN; never reset by
 // the library) | look-back state (128 B per chunk) ; the two-launch path uses the same
 // region for its per-chunk composites (32 B per chunk)
@@ -728,13 +743,7 @@ static int launch_gae_form(hipStream_t st, const float *rews, const float *dones
         int grid = (nb <= resident || g_gae_oversubscribe) ? nb : loop_grid;
         // per-launch tag: process-wide counter seeded from the clock (a recycled workspace may hold records of another
         // process's launches), never 0 (zero-filled memory)
-        if (g_tag.load(std::memory_order_relaxed) == 0) {
-            unsigned expect = 0;
-            const unsigned seed = (unsigned)std::chrono::steady_clock::now().time_since_epoch().count() | 1u;
-            g_tag.compare_exchange_strong(expect, seed);
-        }
-        unsigned tag = g_tag.fetch_add(1, std::memory_order_relaxed) + 1;
-        if (tag == 0) tag = g_tag.fetch_add(1, std::memory_order_relaxed) + 1;
+        const unsigned tag = gae_next_tag();
         auto *kern = grid == nb ? gae_lookback_kernel<false, BOOT, NORM> : gae_lookback_kernel<true, BOOT, NORM>;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(GAE_THREADS), 0, st, rews, dones, trunc, values, n, p, state, tag, g_gae_spin_limit,
                            hdr + 1, nb, vt, adv, ret, boot, vscale);

@@ -46,6 +46,7 @@ class Learner(object):
             hidden_activation: str = "relu", hidden_layer_norm=False, hidden_residual=False,
             ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
             critic_observations: bool = False,
+            gae_vtrace: bool = False, gae_vtrace_rho_bar: float = 1.0, gae_vtrace_c_bar: float = 1.0,
             ppo_normalize_value: bool = False, ppo_value_norm_popart: bool = False,
             ppo_value_head: str = "scalar", ppo_value_bins: int = 101, ppo_value_range=(-10.0, 10.0), ppo_value_sigma_ratio: float = 0.75,
             per_feature_obs_standardization: bool = False,
@@ -78,6 +79,17 @@ class Learner(object):
         if ppo_value_norm_popart and not ppo_normalize_value:
             raise ValueError("ppo_value_norm_popart=True needs ppo_normalize_value=True: there is no running statistic whose moves "
                              "the critic's last layer could follow")
+        # not in the reference (whose buffer keeps the advantages and value targets every row was submitted with, computed under the critic
+        # of that iteration): gae_vtrace=True recomputes both for EVERY buffer row before each learn() -- one value pass of the current
+        # critic over the buffer, the current policy's log-probabilities of the stored actions, and one V-trace scan in ring order
+        # (rlppo_gae_vtrace: delta and decay weighted by min(rho_bar, ratio) / min(c_bar, ratio), ratio = pi_now / pi_then;
+        # _recompute_buffer_targets).  The PPO ratio itself still runs against the stored log-probabilities.  Checked here, before
+        # anything is built or spawned; False is the library as it was, launch for launch.
+        self.gae_vtrace = bool(gae_vtrace)
+        self.gae_vtrace_clips = (float(gae_vtrace_rho_bar), float(gae_vtrace_c_bar))
+        if not all(np.isfinite(c) and c > 0 for c in self.gae_vtrace_clips):
+            raise ValueError(f"gae_vtrace_rho_bar and gae_vtrace_c_bar must be finite and positive, got {gae_vtrace_rho_bar!r}, {gae_vtrace_c_bar!r}")
+        self._vtrace_host = None   # (mean rho, clipped fraction) of the last recompute: they ride in add_new_experience's one read-back
         self.critic_observations = bool(critic_observations)
         if self.critic_observations:
             if not vector_env:
@@ -315,6 +327,7 @@ class Learner(object):
             "critic_lr": critic_lr, "shm_buffer_size": shm_buffer_size,
             "gae_bootstrap_truncated": self.gae_bootstrap_truncated,  # (a hyper-parameter, not checkpoint state)
             "critic_observations": self.critic_observations,
+            "gae_vtrace": self.gae_vtrace, "gae_vtrace_rho_bar": self.gae_vtrace_clips[0], "gae_vtrace_c_bar": self.gae_vtrace_clips[1],
             "ppo_normalize_value": self.normalize_value, "ppo_value_norm_popart": self.value_norm_popart,
         }
 
@@ -384,6 +397,8 @@ class Learner(object):
             report["Collected Steps per Second"] = steps_collected / collection_time
             report["Overall Steps per Second"] = steps_collected / epoch_time
             report["Policy Reward"] = self.agent.average_reward if self.agent.average_reward is not None else np.nan
+            if self.gae_vtrace and self._vtrace_host is not None:
+                report["V-trace Mean Rho"], report["V-trace Clipped Fraction"] = self._vtrace_host
             if self.normalize_value and self._value_norm_host is not None:   # ("Value Function Loss" is in normalised units then)
                 report["Value Norm Mean"], report["Value Norm Std"] = self._value_norm_host[0], self._value_norm_host[1]
             self.ts_since_last_save += steps_collected
@@ -427,7 +442,7 @@ class Learner(object):
         value_net = self.ppo_learner.value_net
         n = states.shape[0]
         on_device = isinstance(states, torch.Tensor) and states.is_cuda   # VectorAgentManager: rollout already in HBM
-        boot_values = boot_idx = dense_boot = None
+        boot_values = boot_idx = dense_boot = critic_rows = None
         if on_device:
             rows = self.agent.value_input_rows               # [N+1, ld]: states ++ the last next_state, padded
             assert rows.shape[0] == n + 1 and rows.data_ptr() == states.data_ptr()
@@ -460,6 +475,7 @@ class Learner(object):
                 boot_idx = torch.from_numpy(boot_idx).to(rows.device)
                 rows = rows[:n + 1]
 
+        self._d_logical = d_logical
         dev = rows.device
         if boot_values is not None:   # scatter the m values to their steps; the other entries are never used (include/rlppo.h)
             m, boot = boot_values.shape[0], torch.empty(n, dtype=torch.float32, device=dev)
@@ -480,6 +496,12 @@ class Learner(object):
             gae_kw["value_scale"] = value_norm.scale
         value_targets, advantages, returns, gae_timeouts = torch_functions.gae_device_deferred(
             rews_d, dones_d, trunc_d, val_preds, gamma=self.gae_gamma, lmbda=self.gae_lambda, return_std=ret_std, **gae_kw)
+        # gae_vtrace: the new rows join the buffer first and every row's targets are recomputed -- before the statistic moves, so the value
+        # pass over the buffer reads the critic and the scale the scan above read
+        vtrace_parts = []
+        if self.gae_vtrace:
+            self._submit(rows[:n], critic_rows, experience, rews_d, dones_d, trunc_d, value_targets, advantages)
+            vtrace_parts = [self._recompute_buffer_targets(val_preds[n:n + 1], ret_std, value_norm)]
         if value_norm is not None:   # (ppo_value_norm_popart: the same launch rescales the critic's last layer for the new scale)
             self.ppo_learner.update_value_norm(value_targets)
 
@@ -489,9 +511,12 @@ class Learner(object):
         n_head = n_to_increment + (1 if gae_timeouts is not None else 0)
         if value_norm is not None:   # mu, sigma, rejected batches (a count: exact in float32 far beyond any run)
             parts += [value_norm.scale[0:1], value_norm.scale[2:3], value_norm.state[3:4].float()]
-        host = torch.cat(parts).cpu().numpy()
+        host = torch.cat(parts + vtrace_parts).cpu().numpy()
         if gae_timeouts is not None:
             torch_functions.raise_if_timed_out(host[n_head - 1])   # GAETimeout: NaN advantages must never reach the buffer
+        if vtrace_parts:   # (its rows ARE in the buffer: the exception is what keeps learn() from running on them)
+            torch_functions.raise_if_timed_out(host[-3])
+            self._vtrace_host = (float(host[-2]), float(host[-1]))
         if value_norm is not None:
             before = self._value_norm_host[2] if self._value_norm_host is not None else 0.0
             self._value_norm_host = tuple(float(x) for x in host[n_head:n_head + 3])
@@ -504,20 +529,64 @@ class Learner(object):
                 raise RuntimeError("GAE produced NaN returns (NaN inputs): refusing to train on them")
             self.return_stats.increment(head, n_to_increment)
 
-        self.experience_buffer._d = d_logical  # logical width of the padded rows
+        if not self.gae_vtrace:
+            self._submit(rows[:n], critic_rows, experience, rews_d, dones_d, trunc_d, value_targets, advantages)
+
+    def _submit(self, rows, critic_rows, experience, rews_d, dones_d, trunc_d, value_targets, advantages):
+        """The buffer submit of add_new_experience: the padded device rows and the device copies of the small fields as they are."""
+        _states, actions, log_probs, _rewards, next_states, _dones, _truncated = experience
+        n = rows.shape[0]
+        self.experience_buffer._d = self._d_logical  # logical width of the padded rows
         extra = {}
-        if on_device and self.critic_observations:
-            self.experience_buffer._dc = int(value_net.arena.d_in)
+        if critic_rows is not None:
+            self.experience_buffer._dc = int(self.ppo_learner.value_net.arena.d_in)
             extra["critic_states"] = critic_rows[:n]
         # invalid-action masking (an environment with action_masks(), either collection mode): the masks the actions were sampled
         # under -- packed device words from the vector manager, bool host rows [N, n_actions] from process-mode collection
         masks = getattr(self.agent, "action_mask_rows", None)
         if masks is not None:
-            self.experience_buffer.submit_experience(rows[:n], actions, log_probs, rews_d, next_states, dones_d, trunc_d,
+            self.experience_buffer.submit_experience(rows, actions, log_probs, rews_d, next_states, dones_d, trunc_d,
                                                      value_targets, advantages, action_masks=masks, **extra)
             return
-        self.experience_buffer.submit_experience(rows[:n], actions, log_probs, rews_d, next_states, dones_d, trunc_d,
+        self.experience_buffer.submit_experience(rows, actions, log_probs, rews_d, next_states, dones_d, trunc_d,
                                                  value_targets, advantages, **extra)
+
+    def _recompute_buffer_targets(self, last_value, ret_std, value_norm, chunk=32768):
+        """gae_vtrace: advantages and value targets of EVERY buffer row, in ring order (oldest first, as the buffer concatenates its
+        iterations), under the critic and the policy as they stand, written over the stored ones in place.  One value pass over the
+        buffer's rows (critic_states where the critic has its own) + `last_value`, V of the newest step's next state; with
+        gae_bootstrap_truncated a second one over the buffer's next-state rows (which steps are truncated is known on the device only:
+        the scan selects by the flags); the current policy's log-probabilities of the stored actions through get_backprop_data, `chunk`
+        rows at a time; one rlppo_gae_vtrace.  The oldest trajectory is cut at the ring's head and is simply shorter; an iteration's
+        last steps are truncated by the flush and treated as the plain scan treats them.
+        -> device float32 [3]: the scan's timeout counter, mean rho, fraction of rows whose ratio the rho clip cut."""
+        buf, policy, value_net = self.experience_buffer, self.ppo_learner.policy, self.ppo_learner.value_net
+        count, rows_of = len(buf), buf._logical
+        values = torch.empty(count + 1, dtype=torch.float32, device=last_value.device)
+        values[:count] = value_net.forward_padded(rows_of("critic_states" if self.critic_observations else "states"))
+        values[count:] = last_value
+        boot = value_net.forward_padded(rows_of("next_states")).contiguous() if self.gae_bootstrap_truncated else None
+        obs, acts, masks = rows_of("states")[:, :buf._d], rows_of("actions"), buf.action_masks
+        acts = acts.view(-1, 1) if acts.dim() == 1 else acts   # (one action per row stored flat)
+        logp_old = rows_of("log_probs").reshape(-1).contiguous()
+        logp_new = torch.empty_like(logp_old)
+        for i in range(0, count, chunk):
+            j = min(count, i + chunk)
+            kw = {} if masks is None else {"action_mask": masks[i:j]}
+            logp_new[i:j] = policy.get_backprop_data(obs[i:j], acts[i:j], **kw)[0].reshape(j - i)
+        rho_bar, c_bar = self.gae_vtrace_clips
+        flat = lambda k: rows_of(k).reshape(-1).contiguous()
+        value_targets, advantages, _none, timeouts = torch_functions.gae_device_deferred(
+            flat("rewards"), flat("dones"), flat("truncated"), values, gamma=self.gae_gamma, lmbda=self.gae_lambda, return_std=ret_std,
+            boot_values=boot, value_scale=None if value_norm is None else value_norm.scale, vtrace=(logp_new, logp_old, rho_bar, c_bar))
+        store, base, cap = buf.ring()
+        first = min(count, cap - base)   # logical row i = physical row (base + i) mod cap
+        for k, x in (("values", value_targets), ("advantages", advantages)):
+            store[k][base:base + first].copy_(x[:first].view_as(store[k][base:base + first]))
+            if first < count:
+                store[k][:count - first].copy_(x[first:].view_as(store[k][:count - first]))
+        ratio = torch.exp(logp_new - logp_old)
+        return torch.stack((timeouts[0].float(), ratio.clamp(max=rho_bar).mean(), (ratio > rho_bar).float().mean()))
 
     # ------------------------------------------------------------------------------------------ checkpoints
     def save(self, cumulative_timesteps):

@@ -36,7 +36,8 @@ def raise_if_timed_out(timeouts):
                          f"and must not be trained on (GPU shared with a long-running kernel, or a defect)")
 
 
-def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, boot_values=None, value_scale=None):
+def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, boot_values=None, value_scale=None,
+                        vtrace=None):
     """gae_device without its synchronisation: returns (value_targets, advantages, returns, timeouts) where `timeouts` is a
     one-element int32 DEVICE tensor -- this call's own snapshot of the workspace header's counter, taken on the stream right
     behind the scan -- that the caller MUST hand to raise_if_timed_out() once it has the value on the host (e.g. folded into a
@@ -50,7 +51,12 @@ def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, 
     `value_scale` (default None: the calls above, launch for launch): fp32 device tensor of 4 floats {mu, 1/sigma, sigma, 0}
     (ppo.ValueNorm.scale).  `values` and `boot_values` are then NORMALISED values; the scan reads each as fmaf(v, sigma, mu) and its
     three outputs are in real units as always (rlppo_gae_norm, include/rlppo.h).  The scan reads the tensor when it runs: a captured
-    call replays with the tensor's contents of that moment."""
+    call replays with the tensor's contents of that moment.
+
+    `vtrace` (default None: the calls above, launch for launch): (logp_new, logp_old, rho_bar, c_bar) -- two fp32 device tensors [n], the
+    log-probability of every step's action under the current policy and under the policy that drew it, and the two clips.  The V-trace
+    scan (rlppo_gae_vtrace, include/rlppo.h): delta and the decay of every step are weighted by the truncated importance ratio, computed
+    in the kernel.  It produces no returns: the third result is None."""
     n = rews.shape[0]
     dev = rews.device
     assert values.shape[0] == n + 1 and dones.shape[0] == n and truncated.shape[0] == n
@@ -59,9 +65,13 @@ def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, 
         boot_values = boot_values.contiguous()
     if value_scale is not None:
         assert value_scale.dtype == torch.float32 and value_scale.device == dev and value_scale.numel() == 4 and value_scale.is_contiguous()
+    if vtrace is not None:
+        logp_new, logp_old, rho_bar, c_bar = vtrace
+        for lp in (logp_new, logp_old):
+            assert lp.shape == (n,) and lp.dtype == torch.float32 and lp.device == dev and lp.is_contiguous()
     vt = torch.empty(n, dtype=torch.float32, device=dev)
     adv = torch.empty(n, dtype=torch.float32, device=dev)
-    ret = torch.empty(n, dtype=torch.float32, device=dev)
+    ret = torch.empty(n, dtype=torch.float32, device=dev) if vtrace is None else None
     if n == 0:
         return vt, adv, ret, None
     std = float("nan") if return_std is None else float(np.float32(return_std))
@@ -70,7 +80,12 @@ def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, 
     hdr = ws[:16].view(torch.int32)
     if not capturing:
         hdr.zero_()  # word 1 = look-back waits that timed out (a grown / recycled workspace holds anything)
-    if value_scale is not None:
+    if vtrace is not None:
+        N.check(N.lib().rlppo_gae_vtrace(stream_ptr(), ptr(rews), ptr(dones), ptr(truncated), ptr(values),
+                                         None if boot_values is None else ptr(boot_values), None if value_scale is None else ptr(value_scale),
+                                         ptr(logp_new), ptr(logp_old), n, float(gamma), float(lmbda), float(rho_bar), float(c_bar), std,
+                                         ptr(vt), ptr(adv), ptr(ws), ws.numel()))
+    elif value_scale is not None:
         N.check(N.lib().rlppo_gae_norm(stream_ptr(), ptr(rews), ptr(dones), ptr(truncated), ptr(values),
                                        None if boot_values is None else ptr(boot_values), ptr(value_scale), n, float(gamma), float(lmbda),
                                        std, ptr(vt), ptr(adv), ptr(ret), ptr(ws), ws.numel()))
@@ -83,7 +98,8 @@ def gae_device_deferred(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, 
     return vt, adv, ret, (None if capturing else hdr[1:2].clone())
 
 
-def gae_device(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, check=True, boot_values=None, value_scale=None):
+def gae_device(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_std=1, check=True, boot_values=None, value_scale=None,
+               vtrace=None):
     """All inputs fp32 device tensors (values has N+1 entries).  Returns (value_targets, advantages, returns) as
     fp32 device tensors.  return_std=None disables reward scaling (torch_functions.py:62-65).
 
@@ -95,9 +111,9 @@ def gae_device(rews, dones, truncated, values, gamma=0.99, lmbda=0.95, return_st
     caller looks at.  check=False leaves the call asynchronous (timing loops); a caller with a device-to-host read of its own
     uses gae_device_deferred and folds the counter into it (Learner.add_new_experience).
 
-    `boot_values`, `value_scale`: see gae_device_deferred."""
+    `boot_values`, `value_scale`, `vtrace`: see gae_device_deferred."""
     vt, adv, ret, timeouts = gae_device_deferred(rews, dones, truncated, values, gamma, lmbda, return_std, boot_values=boot_values,
-                                                 value_scale=value_scale)
+                                                 value_scale=value_scale, vtrace=vtrace)
     if check and timeouts is not None:
         raise_if_timed_out(timeouts.item())
     return vt, adv, ret
