@@ -721,6 +721,54 @@ int rlppo_value_bins_readout(void *stream, const float *logits, int64_t ld, cons
 int rlppo_ppo_minibatch_vbins(void *stream, const rlppo_minibatch_args *args, const rlppo_minibatch_ext *ext, const rlppo_critic_rows *critic,
                               const rlppo_value_norm *vnorm, const rlppo_value_bins *bins);
 
+/* [mirror] Mirror-symmetry augmentation of a pass (rsl_rl's symmetry_cfg / use_data_augmentation; added entry points: the structs above
+ * and the ABI version stay as they are).  rlppo_mirror_batch gathers the args->mb rows of a pass -- row idx[r] through the ring map, as the
+ * pass itself would -- and writes 2 mb PLAIN rows into the caller's staging region in ONE launch: rows [0, mb) are the gathered originals,
+ * bit for bit, rows [mb, 2 mb) their mirror images.  The pass then runs unchanged on the staged arrays (idx = identity, ring_cap = 0,
+ * n_rows = mb = 2 mb, the same mb_ratio): every row is trained on a second time as its mirror image under its stored old log-probability,
+ * advantage and value target.  Read of args: head, act_dim, states / ld_states, actions, old_logp, targets, advantages, action_mask /
+ * mask_words, idx, mb, ring_base, ring_cap; critic (optional) is the critic's own matrix as rlppo_ppo_minibatch_critic takes it.
+ *   states    column j of a mirrored row = sign[j] * x[perm[j]], the sign applied as an xor of bit 31 (exact, also for 0 and NaN); the
+ *             padded columns d <= j < ld_states are written as exact +0.  obs_tab: DEVICE, 16-byte aligned, obs_ld == ld_states entries:
+ *             perm[j] | (sign[j] < 0 ? 0x80000000 : 0) for j < d, RLPPO_MIRROR_ZERO beyond.  The critic's matrix likewise under
+ *             critic_tab / critic_ld.  Leading dimensions: multiples of 4 up to 2048 floats.
+ *   actions   float-encoded as the buffer holds them, act_tab DEVICE by head:
+ *               discrete        n_actions entries amap[a]: the mirrored action is amap[a];
+ *               multi-discrete  H = act_dim components, S = n_actions logits: [hperm[H] | first[H] | bins[H] | maps[S]] -- component h of the
+ *                               mirror is maps[first[h] + a[hperm[h]]], bins[h] the bin count of component h (== that of hperm[h]);
+ *               Gaussian heads  act_dim entries aperm[j] | sign bit: asign[j] * a[aperm[j]] (both RLPPO_HEAD_GAUSSIAN and _DIAG_GAUSSIAN).
+ *             A stored index is data, not a table: it is clamped into its table before it indexes it.
+ *   mask      with args->action_mask: bit c of a mirrored row is bit mask_tab[c] of the source row, c < 32 * mask_words; entries at and
+ *             beyond n_actions are RLPPO_MIRROR_ZERO and give 0.  mask_tab[c] = amap^-1(c) for the discrete head; for the multi-discrete head
+ *             the head permutation and the bin maps composed into one logit permutation.  A permutation of the valid bits: a row without
+ *             a valid action stays without one.  At most 16 words (512 logits).
+ *   scalars   old_logp, targets and advantages are copied twice.
+ * The kernel TRUSTS the tables: the host range-checks every entry before the first launch (rlgym_ppo_amd.ppo.Symmetry).  No atomics; the
+ * same inputs give the same bits.  rlppo_mirror_staging_bytes sizes the region for a pass of mb rows and, with offsets != NULL, stores
+ * the byte offsets of its seven arrays, each a multiple of 256: {states [2 mb][ld_states], critic rows [2 mb][ld_critic], actions
+ * [2 mb][act_dim], old_logp, targets, advantages [2 mb] each, mask words [2 mb][mask_words]}; ld_critic == 0 / mask_words == 0: none
+ * (the array is empty).  A bad argument gives 0.  Nothing outside those arrays is written.
+ * RLPPO_ERR_ARG with a message naming the argument, before any HIP call: a NULL table or array, a pointer that is not aligned (rows and
+ * tables 16 bytes, staging 256), mb <= 0, a leading dimension outside the range above, and a description that does not fit the pass
+ * (head, act_dim, obs_ld / critic_ld against the leading dimensions, mask_words); a staging region that is too small is
+ * RLPPO_ERR_WORKSPACE. */
+#define RLPPO_MIRROR_ZERO 0xFFFFFFFFu
+typedef struct rlppo_symmetry {
+    int32_t head;         /* RLPPO_HEAD_* the action tables were built for */
+    int32_t act_dim;      /* floats per action row */
+    int32_t n_actions;    /* discrete: actions; multi-discrete: logits (sum of the bins); Gaussian heads: 0 */
+    int32_t mask_words;   /* words per mask row that mask_tab covers; 0 without one */
+    int64_t obs_ld;       /* entries of obs_tab == the rows' leading dimension */
+    int64_t critic_ld;    /* entries of critic_tab; 0 without one */
+    const uint32_t *obs_tab;
+    const uint32_t *critic_tab;
+    const uint32_t *act_tab;
+    const uint32_t *mask_tab;
+} rlppo_symmetry;
+size_t rlppo_mirror_staging_bytes(int64_t mb, int64_t ld_states, int64_t ld_critic, int32_t act_dim, int32_t mask_words, int64_t *offsets);
+int rlppo_mirror_batch(void *stream, const rlppo_minibatch_args *args, const rlppo_critic_rows *critic, const rlppo_symmetry *sym,
+                       void *staging, size_t staging_bytes);
+
 /* Orders `stream` after every minibatch enqueued through non-zero slots since the last join (call it before the
  * gradient all-reduce / rlppo_clip_adam).  Independent minibatches of one batch only meet in the gradient arena
  * (one add per element and launch), so they may overlap; each launch is short (50-100 us at 65,536 rows), and overlapping

@@ -103,6 +103,12 @@ class ValueBinsArg(ctypes.Structure):
     _fields_ = [("kind", c_int32), ("n", c_int32), ("vmin", c_float), ("vmax", c_float), ("sigma_ratio", c_float)]
 
 
+class SymmetryArg(ctypes.Structure):
+    """struct rlppo_symmetry (include/rlppo.h, "[mirror]")."""
+    _fields_ = [("head", c_int32), ("act_dim", c_int32), ("n_actions", c_int32), ("mask_words", c_int32), ("obs_ld", c_int64),
+                ("critic_ld", c_int64), ("obs_tab", c_void_p), ("critic_tab", c_void_p), ("act_tab", c_void_p), ("mask_tab", c_void_p)]
+
+
 class Gather2Args(ctypes.Structure):
     """struct rlppo_gather2_args (include/rlppo.h, "[critic rows]")."""
     _fields_ = [("src", c_void_p), ("ld_src", c_int64), ("dst", c_void_p), ("width", c_int32),
@@ -240,6 +246,8 @@ SIGNATURES = {
     "rlppo_value_bins_readout": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(ValueBinsArg), c_void_p, c_int64]),
     "rlppo_ppo_minibatch_vbins": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt), POINTER(CriticRows), POINTER(ValueNormArg),
                                             POINTER(ValueBinsArg)]),
+    "rlppo_mirror_staging_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int64)]),
+    "rlppo_mirror_batch": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(CriticRows), POINTER(SymmetryArg), c_void_p, c_size_t]),
     "rlppo_ppo_join": (c_int32, [c_void_p]),
     "rlppo_kl_slots_doubles": (c_int64, [c_int64]),
     "rlppo_adv_stats": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),

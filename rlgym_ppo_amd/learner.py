@@ -47,6 +47,7 @@ class Learner(object):
             ppo_lr_schedule: str = "constant", ppo_desired_kl: float = 0.01, ppo_lr_bounds=(1e-5, 1e-2),
             critic_observations: bool = False,
             gae_vtrace: bool = False, gae_vtrace_rho_bar: float = 1.0, gae_vtrace_c_bar: float = 1.0,
+            symmetry=None,
             ppo_normalize_value: bool = False, ppo_value_norm_popart: bool = False,
             ppo_value_head: str = "scalar", ppo_value_bins: int = 101, ppo_value_range=(-10.0, 10.0), ppo_value_sigma_ratio: float = 0.75,
             per_feature_obs_standardization: bool = False,
@@ -292,6 +293,19 @@ class Learner(object):
         self.value_norm_popart = bool(ppo_value_norm_popart)
         if self.normalize_value:
             self.ppo_learner.set_value_normalization(True, preserve_outputs=self.value_norm_popart)
+        # not in the reference: symmetry = a ppo.Symmetry, or a callable env -> Symmetry (given the vector environment of this process,
+        # None in process mode), is rsl_rl's mirror-symmetry data augmentation -- every pass of the update trains on its rows and on their
+        # mirror images (PPOLearner.set_symmetry).  With critic_observations its critic tables are required.  The
+        # description is checked against the networks here; None is the library as it was, launch for launch.
+        if symmetry is not None:
+            from .ppo import Symmetry
+            try:
+                if not isinstance(symmetry, Symmetry) and callable(symmetry):
+                    symmetry = symmetry(getattr(self.agent, "env", None))
+                self.ppo_learner.set_symmetry(symmetry)
+            except Exception:
+                self.agent.cleanup()
+                raise
         if ppo_lr_schedule == "adaptive":   # ("linear" is this loop's: the update runs the constant schedule's launches)
             self.ppo_learner.set_lr_schedule("adaptive", ppo_desired_kl, ppo_lr_bounds)
         self.ppo_learner.report_learning_rates = ppo_lr_schedule != "constant"

@@ -6,3 +6,4 @@ from .discrete_policy import DiscreteFF
 from .value_estimator import ValueEstimator
 from .ppo_learner import ObsSizes, PPOLearner, ValueNorm
 from .experience_buffer import ExperienceBuffer
+from .symmetry import Symmetry

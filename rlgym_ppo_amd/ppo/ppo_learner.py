@@ -43,6 +43,12 @@ reference parameter or is set after construction:
     rescales the critic's last layer, so its real-unit predictions are what they were (`ValueNorm.update(targets, preserve=critic)`,
     rlppo_value_norm_update_popart).  No collective here either: the step is deterministic, so replicas that feed the same targets
     stay bit-identical; replicas that are handed one state are handed the weights with it.
+  * `set_symmetry(Symmetry(...))` (ppo/symmetry.py) is rsl_rl's mirror-symmetry data augmentation: every pass is
+    preceded by ONE launch of rlppo_mirror_batch (csrc/mirror.hip), which gathers the pass's rows and writes them and their mirror images
+    -- observation permuted and sign-flipped, action mapped, mask bits moved, old log-probability / advantage / value target copied --
+    as 2 mb plain rows into a staging region this learner owns; the pass then runs on those arrays (idx = identity, no ring, the same
+    mb_ratio and options), its kernels untouched.  The report's means are over the doubled rows; everything in front of learn() and the
+    advantage statistics see the buffer as stored.  No collective is added: each rank augments its own slice.
 """
 import ctypes
 import os
@@ -367,6 +373,26 @@ class PPOLearner(object):
         self._lr_dev = self._lr_host = None
         self.value_norm = None   # set_value_normalization(True): a ValueNorm; None = the critic regresses raw value targets
         self.value_norm_preserve_outputs = False   # set_value_normalization(True, preserve_outputs=True): PopArt's weight-preserving step
+        self.symmetry = None   # set_symmetry(Symmetry): every pass trains on its rows and their mirror images
+        self._sym = self._sym_staging = self._sym_identity = None   # its device tables; the staging region and idx = identity, sized once
+
+    def set_symmetry(self, symmetry=None):
+        """Train every later learn() on each minibatch row and its mirror image under `symmetry` (a ppo.Symmetry; module docstring), or
+        stop doing so (None: the update as it was, launch for launch).  The description is checked against this learner's networks and
+        head here, on the host alone -- a ValueError names the field and leaves the learner as it was -- and its packed tables are
+        built and uploaded once.  Whether it is a true symmetry of the environment is the caller's responsibility."""
+        from .symmetry import BoundSymmetry, Symmetry
+        if symmetry is None:
+            self.symmetry = self._sym = None
+            return
+        if not isinstance(symmetry, Symmetry):
+            raise ValueError(f"set_symmetry: expected a ppo.Symmetry or None, got {type(symmetry).__name__}")
+        pa, va = self.policy.arena, self.value_net.arena
+        kw = {0: dict(n_actions=pa.d_out), 1: dict(bins=getattr(self.policy, "splits", None))}.get(self.policy_type, dict(act_dim=self._act_dim))
+        if self.critic_obs_space_size is not None or symmetry.critic_obs_perm is not None:
+            kw.update(critic_dim=va.d_in, critic_ld=va.ld_in)
+        host = symmetry.host_tables(self.policy_type, pa.d_in, pa.ld_in, **kw)
+        self.symmetry, self._sym = symmetry, BoundSymmetry(symmetry, host, self.policy_type, self._dev)
 
     def set_value_normalization(self, on=True, preserve_outputs=False):
         """Train the critic on standardised value targets from now on (module docstring), or stop doing so.  Switching it on keeps a
@@ -451,6 +477,9 @@ class PPOLearner(object):
         n_slices = self.batch_size // self.mini_batch_size
         runs = fuse_runs(slices_for_rank(max(1, n_slices), rank, world), self.max_fused_minibatches)
         self._fused_rows = self.mini_batch_size * max([cnt for _, cnt in runs] or [1])
+        if self._sym is not None:   # the staging region of the largest pass, once; the pass itself then sees twice the rows
+            self._size_symmetry_staging(a, cr, self._fused_rows)
+            self._fused_rows *= 2
         # (the widest form: without the bits it is the plan of _norm, and of _for / _critic -- tests/test_hidden_spec_host.py)
         nbytes = int(N.lib().rlppo_minibatch_workspace_bytes_res(pa.dims_c, pa.n_layers, va.dims_c, va.n_layers, self._fused_rows, a.precision,
                                                                  int(cr is not None), pa.hidden_act, va.hidden_act))
@@ -504,6 +533,45 @@ class PPOLearner(object):
             e.scratch = scratch + args.slot * e.scratch_bytes
         return fn(st, ctypes.byref(args), *((e.log_std, e.log_std_grad, e.scratch, e.scratch_bytes) if tail is None else tail))
 
+    def _size_symmetry_staging(self, a, crit, rows):
+        """The staging region of rlppo_mirror_batch for passes of up to `rows` buffer rows (grown only when a larger pass comes) and the
+        identity index vector of the doubled pass; the buffer's row layout against the tables'."""
+        d = self._sym.desc
+        if a.ld_states != d.obs_ld or (crit is not None and crit.ld_states != d.critic_ld):
+            raise ValueError(f"symmetry: the experience buffer's rows have leading dimensions {a.ld_states}"
+                             + (f" / {crit.ld_states} (critic_states)" if crit is not None else "") + f", the tables were built for {d.obs_ld}"
+                             + (f" / {d.critic_ld}" if crit is not None else ""))
+        if crit is not None and self._sym.critic is None:
+            raise ValueError("symmetry: the experience buffer holds critic_states, but the Symmetry has no critic_obs_perm / critic_obs_sign")
+        self._sym_shape = (a.ld_states, 0 if crit is None else crit.ld_states, self._act_dim, a.mask_words if a.action_mask else 0)
+        nbytes = int(N.lib().rlppo_mirror_staging_bytes(rows, *self._sym_shape, None))
+        if self._sym_staging is None or self._sym_staging.numel() < nbytes:
+            self._sym_staging = torch.empty(nbytes, dtype=torch.uint8, device=self._dev)
+        if self._sym_identity is None or self._sym_identity.numel() < 2 * rows:
+            self._sym_identity = torch.arange(2 * rows, dtype=torch.int64, device=self._dev)
+        self._sym_offsets = {}
+
+    def _mirror_pass(self, st, args):
+        """One pass with a symmetry set: rlppo_mirror_batch stages the pass's rows and their mirror images, then the pass's own entry
+        point runs on the staged plain arrays -- twice the rows, idx = identity, no ring, everything else as `args` has it."""
+        L, mb, crit = N.lib(), args.mb, args.call[4]
+        base, nbytes = self._sym_staging.data_ptr(), self._sym_staging.numel()
+        N.check(L.rlppo_mirror_batch(st, ctypes.byref(args), None if crit is None else ctypes.byref(crit), ctypes.byref(self._sym.desc), base, nbytes))
+        off = self._sym_offsets.get(mb)
+        if off is None:
+            off = self._sym_offsets[mb] = (ctypes.c_int64 * 7)()
+            L.rlppo_mirror_staging_bytes(mb, *self._sym_shape, off)
+        s = N.MinibatchArgs.from_buffer_copy(args)
+        s.states, s.actions, s.old_logp, s.targets, s.advantages = (base + off[i] for i in (0, 2, 3, 4, 5))
+        s.action_mask = base + off[6] if args.action_mask else None
+        s.idx, s.mb, s.n_rows, s.ring_base, s.ring_cap = self._sym_identity.data_ptr(), 2 * mb, 2 * mb, 0, 0
+        scrit = None
+        if crit is not None:
+            scrit = N.CriticRows()
+            scrit.states, scrit.ld_states = base + off[1], crit.ld_states
+        s.call = self._pass_call(s, scrit)
+        return self._pass(st, s)
+
     _ADAPTIVE_NEEDS_FUSED = ("lr_schedule='adaptive' needs the library's optimiser step (RLPPO_FUSED_OPT=1): the FusedAdam.step form takes "
                              "its rate from the host and cannot read one the gate wrote on the device")
 
@@ -546,6 +614,10 @@ class PPOLearner(object):
             if self.value_norm_preserve_outputs:
                 raise ValueError("value normalisation with preserve_outputs=True (ppo_value_norm_popart) and a categorical critic (value_head): "
                                  "rescaling a last layer of logits preserves nothing")
+        # a symmetry stages every pass in ONE region: passes kept in flight side by side (slots) would share it
+        if getattr(self, "_sym", None) is not None and self.n_slots > 1:
+            raise ValueError(f"symmetry with n_slots={self.n_slots} (RLPPO_SLOTS): the staged rows of a pass live in one region per learner -- "
+                             "use n_slots=1")
         self.lr_schedule, self.desired_kl, self.lr_bounds = self._checked_schedule(self.lr_schedule, self.desired_kl, self.lr_bounds)
         if self.value_clip_range is not None and not float(self.value_clip_range) > 0:
             raise ValueError(f"value_clip_range must be > 0 or None, got {self.value_clip_range!r}")
@@ -676,7 +748,7 @@ class PPOLearner(object):
                         args.idx = idx_dev.data_ptr() + 8 * (b * B + j * MB)
                         args.mb = cnt * MB                      # cnt consecutive minibatches in one pass
                         args.mb_ratio = float(cnt * MB / B)
-                        N.check(self._pass(st, args))
+                        N.check(self._pass(st, args) if self._sym is None else self._mirror_pass(st, args))
                         c.n_passes += 1
                     N.check(L.rlppo_ppo_join(st))
                     if not refilled:
