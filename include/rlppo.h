@@ -113,6 +113,27 @@ extern "C" {
  *                  never written into `packed`. */
 #define RLPPO_HEAD_DIAG_GAUSSIAN 3
 #define RLPPO_DIAG_MAX_K 256
+/* [hybrid] The hybrid head: k diagonal-Gaussian dimensions AND H independent categoricals in one action (a controller's analog axes
+ * and its buttons; Gymnasium's Tuple(Box, MultiDiscrete); parametrised actions): opt-in, a fifth head (added entry points:
+ * rlppo_hybrid_act, rlppo_ppo_minibatch_hybrid; no struct changes, the ABI version stays 8).  The policy network has
+ * dims {obs, hidden.., k + S}, S = sum(nvec), its last layer plain bias.  1 <= k <= RLPPO_DIAG_MAX_K, nvec within RLPPO_MD_MAX_*; both
+ * halves are non-empty; anything else is RLPPO_ERR_ARG naming the field, before any HIP call.
+ *   outputs        columns [0, k): the unbounded means of the "[diag]" head, log_std its k-float DEVICE parameter in the arena's tail;
+ *                  columns [k, k + S): the logits of the "[nvec]" construction, head h owning [k + s_h, k + s_h + b_h)
+ *   action row     k + H floats: the k samples as drawn (not clamped), then the H bin indices, float-encoded as the multi-discrete
+ *                  head's are
+ *   sample         a_j = mu_j + sigma_j eps_j, eps[n][k] ~ N(0, 1); head h: the first arg-max over c < b_h of
+ *                  softmax(z_h)_c / noise_q[(row * H + h) * B + c], B = max(nvec), noise_q[n * H][B] ~ Exp(1).  On the same outputs
+ *                  and noise the samples are rlppo_diag_gaussian_act's and the indices rlppo_multidiscrete_act_nvec's, bit for bit
+ *   deterministic  the means, and each head's arg-max of its logits (rlppo_mlp_forward with out_tanh = 0)
+ *   log p          the "[diag]" sum over the k dimensions + sum_h log_softmax(z_h)[a_h], of the sample as stored: the float terms of
+ *                  both halves are summed in double and rounded once
+ *   entropy        of one row: sum_j (1.4189385332046727 + log_std_j) + sum_h H(z_h); no division by k or H
+ *   gradients      through the shared surrogate: dL/dmu as "[diag]", dL/dz per head segment as "[nvec]", in place over the head output,
+ *                  exact zeros in the padded columns >= k + S and behind a head of one bin; dL/dlog_std as "[diag]", through the same
+ *                  scratch (rlppo_diag_scratch_bytes(mb, k)) and the same fixed-order finish: no atomics inside the sum
+ *   masks          refused (RLPPO_ERR_ARG), as are the symmetry tables of rlppo_mirror_batch for this head. */
+#define RLPPO_HEAD_HYBRID 4
 
 /* precision of a call (rlppo_act_opts.precision, rlppo_minibatch_args.precision): 0 = the process default set with
  * rlppo_set_inference_precision / rlppo_set_update_precision, else 1 + that setter's mode */
@@ -357,6 +378,14 @@ int rlppo_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, cons
 int rlppo_diag_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs, int64_t ld_obs,
                             int64_t n, const float *noise_eps, const float *log_std, float *actions, float *logp, void *workspace,
                             size_t ws_bytes, const rlppo_act_opts *opts);
+
+/* [hybrid] The rollout step of the hybrid head ("[hybrid]" above): the layer chain with out_tanh = 0, then the sampling kernel.
+ * dims[n_layers] == k + sum(nvec); nvec: HOST, n_heads entries, read during the call; noise_eps[n][k] ~ N(0, 1);
+ * noise_q[n * n_heads][max(nvec)] ~ Exp(1); log_std: DEVICE, k floats, read when the kernel runs.  actions: float[n][k + n_heads];
+ * logp: float[n].  opts as rlppo_diag_gaussian_act: bf16 inference precision and completion words work, an action mask is refused. */
+int rlppo_hybrid_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs, int64_t ld_obs, int64_t n,
+                     int32_t k, const int32_t *nvec, int32_t n_heads, const float *noise_eps, const float *noise_q, const float *log_std,
+                     float *actions, float *logp, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts);
 
 /* MultiDiscreteFF.get_action (multi_discrete_policy.py:46-74, torch_functions.py:93-122): 21 logits -> 8
  * categoricals (5x3 + 3x2); noise_q[n*8][3] as Categorical.sample draws it; actions int64[n][8]; logp[n]. */
@@ -621,6 +650,15 @@ int rlppo_ppo_minibatch_nvec(void *stream, const rlppo_minibatch_args *args, con
 size_t rlppo_diag_scratch_bytes(int64_t mb, int32_t k);
 int rlppo_ppo_minibatch_diag(void *stream, const rlppo_minibatch_args *args, const float *log_std, float *log_std_grad, void *scratch,
                              size_t scratch_bytes);
+
+/* [hybrid] The same pass with the hybrid head ("[hybrid]" above; an added entry point).  args->head must be RLPPO_HEAD_HYBRID,
+ * pol_dims[pol_layers] == k + sum(nvec) and args->act_dim == k + n_heads, where k = act_dim - n_heads; nvec: HOST, read during the
+ * call; log_std / log_std_grad: DEVICE k floats; scratch: DEVICE, 8-byte aligned, rlppo_diag_scratch_bytes(args->mb, k) bytes, as
+ * rlppo_ppo_minibatch_diag's.  An action mask is RLPPO_ERR_ARG.  rlppo_ppo_minibatch, _nvec and _diag answer head 4 with
+ * RLPPO_ERR_ARG naming this entry point; rlppo_ppo_minibatch_ex and the forms behind it take the head with md_nvec / md_heads AND the
+ * four log_std fields of the ext set.  Every argument check happens before the first HIP call. */
+int rlppo_ppo_minibatch_hybrid(void *stream, const rlppo_minibatch_args *args, const int32_t *nvec, int32_t n_heads, const float *log_std,
+                               float *log_std_grad, void *scratch, size_t scratch_bytes);
 
 /* [act] The same pass for every head, with the hidden activation of each network (an added entry point: rlppo_minibatch_args and the
  * ABI version stay as they are).  ext == NULL or all-zero is exactly rlppo_ppo_minibatch.  md_nvec / md_heads: as
@@ -1323,6 +1361,21 @@ int rlppo_dbg_gemv_dw(void *stream, const float *dy, int64_t ldy, const float *x
 int rlppo_dbg_diag_loss(void *stream, float *y, int64_t ld, int32_t k, const float *actions, const float *old_logp, const float *advantages,
                         int64_t mb, float clip_range, float ent_coef, float mb_ratio, const float *log_std, float *log_std_grad, void *scratch,
                         size_t scratch_bytes, double *stats, int32_t part);
+/* [hybrid] The hybrid head's two kernels on their own, on caller-supplied head outputs y[rows][ld] (16-byte aligned rows, ld a multiple
+ * of 4 and >= k + sum(nvec)): the loss step with the parts of rlppo_dbg_diag_loss (y overwritten with dL/dy over all ld columns,
+ * actions[mb][k + n_heads]), and the sampling step of rlppo_hybrid_act behind its layer chain.  Argument errors are RLPPO_ERR_ARG
+ * before any HIP call.  tests/test_gpu_hybrid_head.py runs them at leading dimensions a pass does not produce;
+ * tools/hybrid_head_cost.py times them. */
+int rlppo_dbg_hybrid_loss(void *stream, float *y, int64_t ld, int32_t k, const int32_t *nvec, int32_t n_heads, const float *actions,
+                          const float *old_logp, const float *advantages, int64_t mb, float clip_range, float ent_coef, float mb_ratio,
+                          const float *log_std, float *log_std_grad, void *scratch, size_t scratch_bytes, double *stats, int32_t part);
+/* ... and the [nvec] head's general loss launch on its own, on logits[mb][ld] (ld >= sum(nvec); dL/dz in place, columns [sum(nvec), ld)
+ * zeroed) and actions[mb][n_heads]: the thread-per-row leg tools/hybrid_head_cost.py times beside the hybrid kernel. */
+int rlppo_dbg_nvec_loss(void *stream, float *logits, int64_t ld, const int32_t *nvec, int32_t n_heads, const float *actions,
+                        const float *old_logp, const float *advantages, int64_t mb, float clip_range, float ent_coef, float mb_ratio,
+                        double *stats);
+int rlppo_dbg_hybrid_sample(void *stream, const float *y, int64_t ld, int64_t n, int32_t k, const int32_t *nvec, int32_t n_heads,
+                            const float *noise_eps, const float *noise_q, const float *log_std, float *actions, float *logp);
 /* [vbins] The categorical critic's loss launch on its own, on caller-supplied logits[mb][ld] (overwritten with dL/dlogits, rows as for
  * rlppo_value_bins_readout) and contiguous real-unit targets[mb], as a pass has gathered them; value_scale: NULL, or the DEVICE
  * {mu, 1/sigma, ...} of rlppo_value_norm_update; stats: the DEVICE double[RLPPO_N_STATS] a pass accumulates into. */

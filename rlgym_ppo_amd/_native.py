@@ -29,6 +29,7 @@ STAT_PASSES = 7  # host-side: passes of rlppo_ppo_minibatch behind the sums abov
 HEAD_DISCRETE, HEAD_MULTIDISCRETE, HEAD_GAUSSIAN = 0, 1, 2
 HEAD_DIAG_GAUSSIAN = 3  # RLPPO_HEAD_DIAG_GAUSSIAN: learnable state-independent log_std, unbounded mean (include/rlppo.h, "[diag]")
 DIAG_MAX_K = 256  # RLPPO_DIAG_MAX_K
+HEAD_HYBRID = 4  # RLPPO_HEAD_HYBRID: k diag-Gaussian dimensions + multi-discrete heads in one action (include/rlppo.h, "[hybrid]")
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16, PRECISION_X3 = 0, 1, 2, 3  # rlppo_minibatch_args.precision (1 + mode)
 ACT_RELU, ACT_TANH, ACT_ELU = 0, 1, 2  # RLPPO_ACT_*: rlppo_act_opts.hidden_act, rlppo_minibatch_ext.{pol,val}_hidden_act
 COUNTER_CRITIC_ROWS_PASS = 15  # rlppo_dbg_counter key: passes with separate critic rows
@@ -203,6 +204,8 @@ SIGNATURES = {
                                      c_float, c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
     "rlppo_diag_gaussian_act": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
+    "rlppo_hybrid_act": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int32, _P32, c_int32, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
     "rlppo_multidiscrete_act": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_size_t, _PACT]),
     "rlppo_multidiscrete_act_nvec": (c_int32, [c_void_p, _P32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
@@ -237,6 +240,7 @@ SIGNATURES = {
     "rlppo_ppo_minibatch_nvec": (c_int32, [c_void_p, POINTER(MinibatchArgs), _P32, c_int32]),
     "rlppo_diag_scratch_bytes": (c_size_t, [c_int64, c_int32]),
     "rlppo_ppo_minibatch_diag": (c_int32, [c_void_p, POINTER(MinibatchArgs), c_void_p, c_void_p, c_void_p, c_size_t]),
+    "rlppo_ppo_minibatch_hybrid": (c_int32, [c_void_p, POINTER(MinibatchArgs), _P32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t]),
     "rlppo_ppo_minibatch_ex": (c_int32, [c_void_p, POINTER(MinibatchArgs), POINTER(MinibatchExt)]),
     "rlppo_minibatch_workspace_bytes_critic": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32]),
     "rlppo_minibatch_workspace_bytes_norm": (c_size_t, [_P32, c_int32, _P32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32]),
@@ -336,6 +340,12 @@ SIGNATURES = {
                                     c_size_t]),
     "rlppo_dbg_diag_loss": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_void_p,
                                       c_void_p, c_void_p, c_size_t, c_void_p, c_int32]),
+    "rlppo_dbg_hybrid_loss": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, _P32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
+                                        c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int32]),
+    "rlppo_dbg_nvec_loss": (c_int32, [c_void_p, c_void_p, c_int64, _P32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
+                                      c_void_p]),
+    "rlppo_dbg_hybrid_sample": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, _P32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
     "rlppo_dbg_value_bins_loss": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(ValueBinsArg), c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "rlppo_dbg_gemm_tn_group_workspace_bytes": (c_size_t, [POINTER(TnProduct), c_int32, c_int64]),
     "rlppo_dbg_gemm_tn_group": (c_int32, [c_void_p, POINTER(TnProduct), c_int32, c_int64, c_void_p, c_size_t]),

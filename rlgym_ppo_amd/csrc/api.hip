@@ -489,6 +489,34 @@ int rlppo_diag_gaussian_act(void *stream, const int32_t *dims, int32_t n_layers,
                                        c.cx.done_value);
 }
 
+// [hybrid] k Gaussian dimensions + the categoricals of nvec in one row: the layer chain WITHOUT tanh, then hybrid.hip's sampling kernel
+int rlppo_hybrid_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs, int64_t ld_obs, int64_t n,
+                     int32_t k, const int32_t *nvec, int32_t n_heads, const float *noise_eps, const float *noise_q, const float *log_std,
+                     float *actions, float *logp, void *workspace, size_t ws_bytes, const rlppo_act_opts *opts) {
+    ActCall c;
+    int rc = act_open(&c, dims, n_layers, opts, false, "the hybrid head (rlppo_hybrid_act)");
+    if (rc) return rc;
+    RLPPO_CHECK_ARG(k >= 1 && k <= RLPPO_DIAG_MAX_K, "hybrid_act: k=%d Gaussian dimensions, RLPPO_DIAG_MAX_K allows 1 .. %d", k, RLPPO_DIAG_MAX_K);
+    MdSpec spec;
+    rc = md_spec_make(nvec, n_heads, "hybrid_act: nvec / n_heads", &spec);
+    if (rc) return rc;
+    RLPPO_CHECK_ARG(dims[n_layers] == k + spec.S, "hybrid_act: output width %d, but k + sum(nvec) = %d + %d", dims[n_layers], k, spec.S);
+    if (n == 0) return 0;
+    RLPPO_CHECK_ARG(n > 0 && packed && obs && noise_eps && noise_q && log_std && actions && logp && workspace, "hybrid_act: bad argument");
+    rc = act_chain((hipStream_t)stream, &c, packed, obs, ld_obs, n, 0, workspace, ws_bytes, nullptr);
+    if (rc) return rc;
+    // (the completion words ride in the sampling kernel: a block of it holds 256 whole rows)
+    return launch_hybrid_sample((hipStream_t)stream, c.o, c.ldo, n, k, spec, noise_eps, noise_q, log_std, actions, logp, c.cx.done, c.cx.done_value);
+}
+int rlppo_dbg_hybrid_sample(void *stream, const float *y, int64_t ld, int64_t n, int32_t k, const int32_t *nvec, int32_t n_heads,
+                            const float *noise_eps, const float *noise_q, const float *log_std, float *actions, float *logp) {
+    MdSpec spec;
+    int rc = md_spec_make(nvec, n_heads, "dbg_hybrid_sample: nvec / n_heads", &spec);
+    if (rc) return rc;
+    RLPPO_CHECK_ARG(n > 0 && y && noise_eps && noise_q && log_std && actions && logp, "dbg_hybrid_sample: bad argument");
+    return launch_hybrid_sample((hipStream_t)stream, y, ld, n, k, spec, noise_eps, noise_q, log_std, actions, logp);
+}
+
 int rlppo_multidiscrete_act(void *stream, const int32_t *dims, int32_t n_layers, const float *packed, const float *obs,
                             int64_t ld_obs, int64_t n, const float *noise_q, int64_t *actions, float *logp,
                             void *workspace, size_t ws_bytes, const rlppo_act_opts *opts) {

@@ -355,6 +355,13 @@ int launch_multidiscrete_nvec_sample(hipStream_t, const float *, int64_t, int64_
                                      int mask_words = 0);
 int launch_multidiscrete_nvec_loss(hipStream_t, float *, int64_t, const float *, const float *, const float *, int64_t, const LossCfg &, double *,
                                    const MdSpec &, const MaskRows *mask_rows = nullptr);
+int launch_diag_logstd_finish(hipStream_t st, const double *partials, int nblocks, int k, float *grad);
+// hybrid.hip [hybrid]: k diagonal-Gaussian dimensions + the categoricals of `spec` in one row of k + spec.S outputs (rows 16-byte
+// aligned, ld a multiple of 4); actions [n][k + H] floats; DiagHead and its scratch as the diag head's (diag_scratch_bytes(mb, k))
+int launch_hybrid_sample(hipStream_t, const float *y, int64_t ld, int64_t n, int k, const MdSpec &spec, const float *eps, const float *noise_q,
+                         const float *log_std, float *actions, float *logp, unsigned *done_words = nullptr, unsigned done_value = 0);
+int launch_hybrid_loss(hipStream_t, float *y, int64_t ld, int k, const MdSpec &spec, const float *actions, const float *old_logp,
+                       const float *adv, int64_t mb, const LossCfg &, double *stats, const DiagHead &, int part = 0);
 
 // fused_act.hip: the whole rollout step of the discrete policy in one launch ----------------
 struct FusedActIO {

@@ -18,6 +18,7 @@
 // (MaskRows below) -- the workspace plan and the gather launches of a pass are the same with and without a mask.
 #include <type_traits>
 
+#include "head_steps.hpp"  // the steps every head shares: the PPO surrogate, the completion words, the diag / nvec terms
 #include "row_layout.hpp"  // the wave / 16-lane reductions, the row layouts (WaveRow, Lanes16) and block_stats_add
 
 namespace rlppo {
@@ -223,42 +224,6 @@ int launch_discrete_probs(hipStream_t st, const float *logits, int64_t ld, int64
     return 0;
 }
 
-// ------------------------------------------------------------------------------------ shared loss pieces
-// d/d(ratio) of min(ratio*A, clamp(ratio)*A), divided by A
-__device__ __forceinline__ float surrogate_weight(float ratio, float adv, const LossCfg &c, float &s_min) {
-    const float s1 = ratio * adv;
-    const float cl = fminf(fmaxf(ratio, c.clip_lo), c.clip_hi);
-    const float s2 = cl * adv;
-    const float inr = (ratio >= c.clip_lo && ratio <= c.clip_hi) ? 1.f : 0.f;
-    s_min = fminf(s1, s2);
-    return s1 < s2 ? 1.f : (s1 > s2 ? inr : 0.5f + 0.5f * inr);
-}
-
-// [ABI 7] the advantage the surrogate sees: the stored one, or (A - mean) * scale of the batch (rlppo_adv_stats)
-__device__ __forceinline__ float surrogate_adv(float adv, const LossCfg &c) { return c.adv_norm ? (adv - c.adv_norm[0]) * c.adv_norm[1] : adv; }
-
-// The PPO surrogate of one row, the tail of every policy loss kernel: from the row's log-probability, the stored one and the stored
-// advantage to the log-ratio, the ratio, the surrogate min(s1, s2) and dL/d(log p)
-struct Surrogate {
-    float lr, ratio, smin, g_logp;
-};
-__device__ __forceinline__ Surrogate surrogate_row(float lp, float old_logp, float stored_adv, const LossCfg &c) {
-    const float adv = surrogate_adv(stored_adv, c);
-    Surrogate t;
-    t.lr = lp - old_logp;
-    t.ratio = expf(t.lr);
-    const float w = surrogate_weight(t.ratio, adv, c, t.smin);
-    t.g_logp = c.mb_ratio * (-(adv * w * t.ratio) * c.inv_mb);
-    return t;
-}
-// ... and the row's share of the four report statistics of the policy loss; `entropy` is the row's term of the mean entropy
-__device__ __forceinline__ void surrogate_stats_add(float (&st)[5], float entropy, const Surrogate &t, const LossCfg &c) {
-    st[RLPPO_STAT_ENTROPY] += entropy;
-    st[RLPPO_STAT_KL] += ((t.ratio - 1.f) - t.lr) * c.inv_mb;
-    st[RLPPO_STAT_CLIPFRAC] += (fabsf(t.ratio - 1.f) > c.clip ? 1.f : 0.f) * c.inv_mb;
-    st[RLPPO_STAT_PLOSS] += -t.smin * c.inv_mb;
-}
-
 // The grids of the policy loss launches: block b's KL sum lands in kl_slots[2 + b], so kl_slots_doubles sizes the slots from them.
 constexpr int64_t DISCRETE_LOSS_MAX_BLOCKS = 2048;  // the discrete loss strides its grid over the rows
 static unsigned discrete_loss_grid(int64_t mb, int rows_per_block) {
@@ -411,17 +376,6 @@ __device__ __forceinline__ float gauss_logpdf(float x, float mean, float sd) {
     return t1 + t2 + t3 + t4;
 }
 
-// [r5] completion words of a sampling kernel that gives a block 256 whole rows = the 16 words 16 b .. 16 b + 15 (rlppo_act_opts.done_words):
-// every thread releases its stores at system scope, a barrier, sixteen stores -- the words ride in the call's last kernel instead of
-// a launch of their own behind it (one graph node fewer of the small call's eight)
-__device__ __forceinline__ void block_done_words(unsigned *done_words, unsigned done_value, int64_t n) {
-    if (!done_words) return;  // (uniform)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    __syncthreads();
-    const int64_t w = (int64_t)blockIdx.x * 16 + threadIdx.x;
-    if (threadIdx.x < 16 && w < (n + 15) / 16) __hip_atomic_store(done_words + w, done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // y[row][0:2k] holds tanh outputs.  action = clamp(mean + sd*eps, -1, 1); logp = sum logpdf(action)
 __global__ __launch_bounds__(256) void gaussian_sample_kernel(const float *__restrict__ y, int64_t ld, int64_t n, int k,
                                                                const float *__restrict__ eps, float var_m, float var_b,
@@ -522,8 +476,6 @@ int launch_gaussian_loss(hipStream_t st, float *y, int64_t ld, int k, const floa
 // network's output as it is (no tanh) = the mean; sigma_j = exp(log_std_j) with log_std a k-float PARAMETER read from device memory
 // at run time (a block keeps log_std and sigma in LDS).  Nothing is clamped; log p is Normal.log_prob's three terms in its order;
 // the float terms are summed as the Gaussian head above sums its (FLOAT_SUM_K).  One thread per row, no per-row array.
-constexpr float DIAG_HALF_LOG_2PI = 0.9189385332046727f;  // log(sqrt(2 pi))
-__device__ __forceinline__ float diag_logp_term(float d, float sd, float ls) { return -(d * d) / (2.f * (sd * sd)) - ls - DIAG_HALF_LOG_2PI; }
 // (every thread of the block, before anything diverges: the fill ends in a barrier)
 __device__ __forceinline__ void diag_fill_lds(const float *__restrict__ log_std, int k, float *s_ls, float *s_sd) {
     for (int j = threadIdx.x; j < k; j += blockDim.x) {
@@ -647,6 +599,13 @@ __global__ __launch_bounds__(256) void diag_logstd_finish_kernel(const double *_
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(grad + j, (float)((red[0] + red[1]) + (red[2] + red[3])));
+}
+
+// (the finish on its own, for a head whose loss kernel writes the same [grid][k] partial sums: hybrid.hip)
+int launch_diag_logstd_finish(hipStream_t st, const double *partials, int nblocks, int k, float *grad) {
+    hipLaunchKernelGGL(diag_logstd_finish_kernel, dim3((unsigned)k), dim3(256), 0, st, partials, nblocks, k, grad);
+    RLPPO_LAUNCH_CHECK();
+    return 0;
 }
 
 size_t diag_scratch_bytes(int64_t mb, int k) { return (size_t)thread_per_row_grid(mb > 0 ? mb : 1) * (size_t)(k > 0 ? k : 1) * sizeof(double); }
@@ -925,13 +884,6 @@ __device__ __forceinline__ float md_head_entropy(const float *z, int b, float ls
     }
     return e;
 }
-// the stored action of head h, float-encoded; clamped into [0, b) BEFORE it indexes anything (a value outside its head's range is a
-// caller error: the row then trains on the nearest valid action, and no address outside the row is ever formed)
-__device__ __forceinline__ int md_action(float a, int b) {
-    const int i = (int)a;
-    return i < 0 ? 0 : (i >= b ? b - 1 : i);
-}
-
 // The gradient multidiscrete_loss_kernel writes, per head segment; columns >= S of the padded row are zeroed.  First walk: log p
 // and the entropy of the row (float terms summed in double, rounded once: see the sampling kernel); second walk: each head's log-sum-exp and entropy again, then its gradient in place (a head's logits
 // are overwritten only after the head's own reads).  MASKED: the row's words are those of the buffer's physical row of idx[row]

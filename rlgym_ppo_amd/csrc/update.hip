@@ -305,6 +305,8 @@ static int policy_loss(hipStream_t st, const Pass &p) {
         return launch_discrete_loss(st, w.pol.act[last], L.pout, L.out, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, a.action_mask ? &mr : nullptr);
     if (a.head == RLPPO_HEAD_GAUSSIAN)
         return launch_gaussian_loss(st, w.pol.act[last], L.pout, L.out / 2, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats);
+    if (a.head == RLPPO_HEAD_HYBRID)  // [hybrid] act_dim = k + H: k Gaussian dimensions in front of the md heads' logits
+        return launch_hybrid_loss(st, w.pol.act[last], L.pout, a.act_dim - p.md.H, p.md, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, *p.diag);
     if (a.head == RLPPO_HEAD_DIAG_GAUSSIAN)  // [diag] + the fixed-order finish of the log_std gradient, behind it on the same stream
         return launch_diag_gaussian_loss(st, w.pol.act[last], L.pout, L.out, w.g_act, w.g_old, w.g_adv, p.mb, p.cfg, a.stats, *p.diag);
     if (p.md_general) {  // [nvec] any nvec: the general kernel, also on the reference's bins
@@ -493,6 +495,7 @@ struct PassOpts {
     const rlppo_critic_rows *critic = nullptr;   // [critic rows] the critic's own row matrix: non-null only with critic->states set
     const float *vnorm = nullptr;                // [vnorm] the value statistic's scale
     const rlppo_value_bins *bins = nullptr;      // [vbins] the categorical critic's bins
+    bool hybrid_entry = false;                   // [hybrid] rlppo_ppo_minibatch_hybrid: the hybrid head and no other
 };
 
 // the bf16 and split-bf16 update precisions carry the ReLU bitmask by construction and have no place for the row kernels
@@ -571,11 +574,16 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
     // every head pins act_dim to at most the policy's output width (the gathered actions' slots); the loss kernel's width too
     const int n_out = pol.L[pol.n_layers - 1].out;
     RLPPO_CHECK_ARG(a->head == RLPPO_HEAD_DISCRETE || a->head == RLPPO_HEAD_GAUSSIAN || a->head == RLPPO_HEAD_MULTIDISCRETE ||
-                        a->head == RLPPO_HEAD_DIAG_GAUSSIAN, "ppo_minibatch: unknown head %d", a->head);
+                        a->head == RLPPO_HEAD_DIAG_GAUSSIAN || a->head == RLPPO_HEAD_HYBRID, "ppo_minibatch: unknown head %d", a->head);
+    // [hybrid] the hybrid head needs both what _nvec and what _diag bring: rlppo_ppo_minibatch_hybrid (or an ext with both parts)
+    const bool hybrid = a->head == RLPPO_HEAD_HYBRID;
+    RLPPO_CHECK_ARG(!hybrid || (diag && o.md_nvec),
+                    "ppo_minibatch: head %d (RLPPO_HEAD_HYBRID) needs nvec, log_std, its gradient and scratch: rlppo_ppo_minibatch_hybrid", a->head);
+    RLPPO_CHECK_ARG(!o.hybrid_entry || hybrid, "ppo_minibatch_hybrid: head %d, but the entry point runs RLPPO_HEAD_HYBRID (%d) only", a->head, RLPPO_HEAD_HYBRID);
     // [diag] the diagonal-Gaussian head has a parameter of its own: only rlppo_ppo_minibatch_diag brings it (and nothing else does)
     RLPPO_CHECK_ARG(a->head != RLPPO_HEAD_DIAG_GAUSSIAN || diag,
                     "ppo_minibatch: head %d (RLPPO_HEAD_DIAG_GAUSSIAN) needs log_std, its gradient and scratch: rlppo_ppo_minibatch_diag", a->head);
-    RLPPO_CHECK_ARG(!diag || a->head == RLPPO_HEAD_DIAG_GAUSSIAN, "ppo_minibatch_diag: head %d, but the entry point runs RLPPO_HEAD_DIAG_GAUSSIAN (%d) only",
+    RLPPO_CHECK_ARG(!diag || hybrid || a->head == RLPPO_HEAD_DIAG_GAUSSIAN, "ppo_minibatch_diag: head %d, but the entry point runs RLPPO_HEAD_DIAG_GAUSSIAN (%d) only",
                     a->head, RLPPO_HEAD_DIAG_GAUSSIAN);
     // [ABI 8] action masks: the discrete head, and [nvec, masked] the multi-discrete head's general kernels (md_nvec given, also for
     // the reference's bins): one bit per output, ceil(n_out / 32) words per buffer row
@@ -583,6 +591,7 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
                     "ppo_minibatch: action_mask is an option of the discrete head, not of the %s head",
                     a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian"
                     : a->head == RLPPO_HEAD_DIAG_GAUSSIAN ? "diagonal-Gaussian"
+                    : hybrid                              ? "hybrid"
                                                           : "multi-discrete (without md_nvec: the fixed-bin kernels take no mask)");
     if (int rc_mask = mask_words_check(a->action_mask, a->mask_words, n_out, "ppo_minibatch", false)) return rc_mask;
     if (a->head == RLPPO_HEAD_DISCRETE) {
@@ -601,7 +610,20 @@ static int ppo_minibatch(void *stream, const rlppo_minibatch_args *a, const Pass
                         diag_scratch_bytes(mb, n_out));
     }
     // [nvec] md_nvec: the multi-discrete head alone; NULL = the reference's 21 outputs / 8 heads and the fixed kernel
-    RLPPO_CHECK_ARG(!o.md_nvec || a->head == RLPPO_HEAD_MULTIDISCRETE, "ppo_minibatch: md_nvec is an option of the multi-discrete head, not of the %s head",
+    if (hybrid) {  // [hybrid] k = act_dim - H Gaussian dimensions, then the heads of nvec
+        rc = md_spec_make(o.md_nvec, o.md_heads, "hybrid head: nvec / n_heads", &p.md);
+        if (rc) return rc;
+        const int k = a->act_dim - p.md.H;
+        RLPPO_CHECK_ARG(k >= 1 && k <= RLPPO_DIAG_MAX_K, "hybrid head: act_dim=%d with n_heads=%d leaves k=%d Gaussian dimensions, RLPPO_DIAG_MAX_K allows 1 .. %d",
+                        a->act_dim, p.md.H, k, RLPPO_DIAG_MAX_K);
+        RLPPO_CHECK_ARG(n_out == k + p.md.S, "hybrid head: act_dim=%d gives k=%d and nvec sums to %d, but the policy has %d outputs (pol_dims[pol_layers])",
+                        a->act_dim, k, p.md.S, n_out);
+        RLPPO_CHECK_ARG(diag->log_std && diag->log_std_grad, "ppo_minibatch_hybrid: log_std / log_std_grad is NULL");
+        RLPPO_CHECK_ARG(diag->scratch && diag->scratch_bytes >= diag_scratch_bytes(mb, k),
+                        "ppo_minibatch_hybrid: scratch of %zu bytes, rlppo_diag_scratch_bytes(%ld, %d) = %zu needed", diag->scratch_bytes, (long)mb, k,
+                        diag_scratch_bytes(mb, k));
+    }
+    RLPPO_CHECK_ARG(hybrid || !o.md_nvec || a->head == RLPPO_HEAD_MULTIDISCRETE, "ppo_minibatch: md_nvec is an option of the multi-discrete head, not of the %s head",
                     a->head == RLPPO_HEAD_GAUSSIAN ? "Gaussian" : a->head == RLPPO_HEAD_DIAG_GAUSSIAN ? "diagonal-Gaussian" : "discrete");
     if (a->head == RLPPO_HEAD_MULTIDISCRETE && o.md_nvec) {
         rc = md_spec_make(o.md_nvec, o.md_heads, "multi-discrete head: md_nvec / md_heads", &p.md);
@@ -739,6 +761,15 @@ int rlppo_ppo_minibatch_diag(void *stream, const rlppo_minibatch_args *a, const 
     RLPPO_CHECK_ARG(scratch_aligned(scratch), "ppo_minibatch_diag: scratch must be 8-byte aligned");
     return ppo_minibatch(stream, a, PassOpts{nullptr, 0, diag_head(log_std, log_std_grad, scratch, scratch_bytes), true});
 }
+// [hybrid] what _nvec and _diag bring, together, for the head that needs both
+int rlppo_ppo_minibatch_hybrid(void *stream, const rlppo_minibatch_args *a, const int32_t *nvec, int32_t n_heads, const float *log_std,
+                               float *log_std_grad, void *scratch, size_t scratch_bytes) {
+    RLPPO_CHECK_ARG(scratch_aligned(scratch), "ppo_minibatch_hybrid: scratch must be 8-byte aligned");
+    RLPPO_CHECK_ARG(nvec != nullptr, "ppo_minibatch_hybrid: nvec is NULL");
+    PassOpts o{nvec, n_heads, diag_head(log_std, log_std_grad, scratch, scratch_bytes), true};
+    o.hybrid_entry = true;
+    return ppo_minibatch(stream, a, o);
+}
 // [act] every head through one call: the hidden activations + what the _nvec / _diag entry points bring.  NULL / zeroed ext: rlppo_ppo_minibatch
 int rlppo_ppo_minibatch_ex(void *stream, const rlppo_minibatch_args *a, const rlppo_minibatch_ext *ext) {
     return ppo_minibatch_opts(stream, a, ext, nullptr, nullptr);
@@ -771,6 +802,39 @@ int rlppo_dbg_diag_loss(void *stream, float *y, int64_t ld, int32_t k, const flo
     a.mb = mb;
     return launch_diag_gaussian_loss((hipStream_t)stream, y, ld, k, actions, old_logp, advantages, mb, loss_cfg(a), stats,
                                      diag_head(log_std, log_std_grad, scratch, scratch_bytes), part);
+}
+
+// [hybrid] the hybrid head's loss launch and the finish of its log_std reduction on their own (tools/hybrid_head_cost.py, the kernel tests)
+int rlppo_dbg_hybrid_loss(void *stream, float *y, int64_t ld, int32_t k, const int32_t *nvec, int32_t n_heads, const float *actions,
+                          const float *old_logp, const float *advantages, int64_t mb, float clip_range, float ent_coef, float mb_ratio,
+                          const float *log_std, float *log_std_grad, void *scratch, size_t scratch_bytes, double *stats, int32_t part) {
+    MdSpec spec;
+    int rc = md_spec_make(nvec, n_heads, "dbg_hybrid_loss: nvec / n_heads", &spec);
+    if (rc) return rc;
+    RLPPO_CHECK_ARG(mb > 0 && y && actions && old_logp && advantages && stats && part >= 0 && part <= 2 && scratch_aligned(scratch),
+                    "dbg_hybrid_loss: bad argument");
+    rlppo_minibatch_args a = {};
+    a.clip_range = clip_range;
+    a.ent_coef = ent_coef;
+    a.mb_ratio = mb_ratio;
+    a.mb = mb;
+    return launch_hybrid_loss((hipStream_t)stream, y, ld, k, spec, actions, old_logp, advantages, mb, loss_cfg(a), stats,
+                              diag_head(log_std, log_std_grad, scratch, scratch_bytes), part);
+}
+
+// [nvec] the general multi-discrete loss launch on its own: the thread-per-row leg tools/hybrid_head_cost.py times beside the hybrid head's
+int rlppo_dbg_nvec_loss(void *stream, float *logits, int64_t ld, const int32_t *nvec, int32_t n_heads, const float *actions, const float *old_logp,
+                        const float *advantages, int64_t mb, float clip_range, float ent_coef, float mb_ratio, double *stats) {
+    MdSpec spec;
+    int rc = md_spec_make(nvec, n_heads, "dbg_nvec_loss: nvec / n_heads", &spec);
+    if (rc) return rc;
+    RLPPO_CHECK_ARG(mb > 0 && logits && actions && old_logp && advantages && stats, "dbg_nvec_loss: bad argument");
+    rlppo_minibatch_args a = {};
+    a.clip_range = clip_range;
+    a.ent_coef = ent_coef;
+    a.mb_ratio = mb_ratio;
+    a.mb = mb;
+    return launch_multidiscrete_nvec_loss((hipStream_t)stream, logits, ld, actions, old_logp, advantages, mb, loss_cfg(a), stats, spec);
 }
 
 int rlppo_ppo_join(void *stream) {

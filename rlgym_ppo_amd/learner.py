@@ -183,8 +183,21 @@ class Learner(object):
         if ppo_lr_schedule == "adaptive" and os.environ.get("RLPPO_FUSED_OPT", "1") == "0":   # (here: nothing is spawned yet)
             raise ValueError(PPOLearner._ADAPTIVE_NEEDS_FUSED)
         self.lr_schedule, self._lr0 = ppo_lr_schedule, [policy_lr, critic_lr]
-        if continuous_head not in ("reference", "diag"):
-            raise ValueError(f"continuous_head must be 'reference' or 'diag', got {continuous_head!r}")
+        if continuous_head not in ("reference", "diag", "hybrid"):
+            raise ValueError(f"continuous_head must be 'reference', 'diag' or 'hybrid', got {continuous_head!r}")
+        # not in the reference: continuous_head="hybrid" with multi_discrete_bins=nvec is the hybrid head (ppo/hybrid_policy.py) -- the
+        # environment takes action rows of k + len(nvec) floats, k Gaussian axes (clipped like "diag"'s) and then the bin indices
+        hybrid = continuous_head == "hybrid"
+        if hybrid:
+            from .ppo.multi_discrete_policy import check_bins
+            if multi_discrete_bins is None:
+                raise ValueError("continuous_head='hybrid' needs multi_discrete_bins: the nvec of the action row's categorical components")
+            multi_discrete_bins = check_bins(multi_discrete_bins)
+            if not vector_env:
+                raise ValueError("continuous_head='hybrid' needs vector_env=True: process-mode collection is not supported (its shapes reply "
+                                 "has no action-space type for a mixed action row)")
+            if symmetry is not None:
+                raise ValueError("continuous_head='hybrid': symmetry is not supported (no tables for the mixed action row)")
         from .ppo.diag_gaussian_policy import check_log_std_init
         from .util.action_clip import ClippedEnvFactory, check_clip
         continuous_log_std_init = check_log_std_init(continuous_log_std_init)
@@ -197,7 +210,9 @@ class Learner(object):
         else:
             continuous_action_clip = check_clip((-1.0, 1.0) if default_clip else continuous_action_clip)
             if continuous_action_clip is not None:   # one mechanism for both collection modes: the environment is built wrapped
-                env_create_function = ClippedEnvFactory(env_create_function, *continuous_action_clip)
+                # (the hybrid head: the clip covers the Gaussian columns alone -- all but the last len(nvec))
+                env_create_function = ClippedEnvFactory(env_create_function, *continuous_action_clip,
+                                                        *((-len(multi_discrete_bins),) if hybrid else ()))
         self.continuous_head, self.continuous_action_clip = continuous_head, continuous_action_clip
         if checkpoints_save_folder is None:
             checkpoints_save_folder = os.path.join("data", "checkpoints", "rlgym-ppo-run")
@@ -260,7 +275,19 @@ class Learner(object):
         print("Initializing PPO...")
         if ppo_minibatch_size is None:
             ppo_minibatch_size = ppo_batch_size
-        if multi_discrete_bins is not None:   # the nvec of the environment's MultiDiscrete space (PPOLearner takes it as act_space_size)
+        if hybrid:   # k = what the environment's action rows hold beyond the len(nvec) indices
+            from .ppo import HybridSpace
+            k = int(act_space_size) - len(multi_discrete_bins)
+            if action_space_type != 2 or k < 1:
+                self.agent.cleanup()
+                raise ValueError(f"continuous_head='hybrid': the environment reports an action width of {int(act_space_size)} (action space type "
+                                 f"{int(action_space_type)}) and multi_discrete_bins has {len(multi_discrete_bins)} entries: a Box of k + "
+                                 f"{len(multi_discrete_bins)} floats with k >= 1 is needed")
+            if hasattr(getattr(self.agent, "env", None), "action_masks"):
+                self.agent.cleanup()
+                raise ValueError("continuous_head='hybrid': action masks are not supported (the environment has action_masks())")
+            act_space_size, action_space_type = HybridSpace(k, multi_discrete_bins), 4   # PPOLearner's policy_type of the hybrid head
+        elif multi_discrete_bins is not None:   # the nvec of the environment's MultiDiscrete space (PPOLearner takes it as act_space_size)
             from .ppo.multi_discrete_policy import check_bins
             if action_space_type != 1:
                 raise ValueError(f"multi_discrete_bins is an option of the multi-discrete policy (action space type 1), not of type {action_space_type}")
@@ -309,7 +336,7 @@ class Learner(object):
         if ppo_lr_schedule == "adaptive":   # ("linear" is this loop's: the update runs the constant schedule's launches)
             self.ppo_learner.set_lr_schedule("adaptive", ppo_desired_kl, ppo_lr_bounds)
         self.ppo_learner.report_learning_rates = ppo_lr_schedule != "constant"
-        if continuous_head == "diag":   # (a constant fill before the first step and before a checkpoint is loaded: no generator use)
+        if continuous_head in ("diag", "hybrid"):   # (a constant fill before the first step and before a checkpoint is loaded: no generator use)
             self.ppo_learner.policy.fill_log_std(continuous_log_std_init)
         self.agent.policy = self.ppo_learner.policy
         if not vector_env and self.agent.masked:

@@ -4,6 +4,7 @@ from .diag_gaussian_policy import DiagGaussianPolicy
 from .multi_discrete_policy import MultiDiscreteFF
 from .discrete_policy import DiscreteFF
 from .value_estimator import ValueEstimator
-from .ppo_learner import ObsSizes, PPOLearner, ValueNorm
+from .hybrid_policy import HybridPolicy
+from .ppo_learner import HybridSpace, ObsSizes, PPOLearner, ValueNorm
 from .experience_buffer import ExperienceBuffer
 from .symmetry import Symmetry

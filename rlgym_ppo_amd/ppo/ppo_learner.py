@@ -49,7 +49,11 @@ reference parameter or is set after construction:
     as 2 mb plain rows into a staging region this learner owns; the pass then runs on those arrays (idx = identity, no ring, the same
     mb_ratio and options), its kernels untouched.  The report's means are over the doubled rows; everything in front of learn() and the
     advantage statistics see the buffer as stored.  No collective is added: each rank augments its own slice.
+  * policy_type 4 is the hybrid head (ppo/hybrid_policy.py, csrc/hybrid.hip): `act_space_size=HybridSpace(k, nvec)`, an action row of
+    k Gaussian samples and len(nvec) bin indices.  log_std is the tail of the policy's arena, so the optimiser step, the gradient
+    exchange and checkpoints treat it as policy_type 3's; action masks and set_symmetry are refused.
 """
+import collections
 import ctypes
 import os
 import time
@@ -66,6 +70,7 @@ from ._mlp import check_precisions
 from .continuous_policy import ContinuousPolicy
 from .diag_gaussian_policy import DiagGaussianPolicy
 from .discrete_policy import DiscreteFF
+from .hybrid_policy import HybridPolicy
 from .multi_discrete_policy import MultiDiscreteFF, check_bins
 from .value_estimator import ValueEstimator
 
@@ -81,6 +86,18 @@ class ObsSizes(object):
 
     def __repr__(self):
         return f"ObsSizes(policy={self.policy}, critic={self.critic})"
+
+
+class HybridSpace(collections.namedtuple("HybridSpace", ("k", "nvec"))):
+    """PPOLearner(act_space_size=HybridSpace(k, nvec), policy_type=4): k Gaussian dimensions and the categoricals of nvec in one
+    action (ppo/hybrid_policy.py); an action row is k + len(nvec) floats."""
+    __slots__ = ()
+
+    def __new__(cls, k, nvec):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= N.DIAG_MAX_K:
+            raise ValueError(f"HybridSpace: k must be an integer in 1 .. {N.DIAG_MAX_K} (RLPPO_DIAG_MAX_K), got {k!r}")
+        return super().__new__(cls, int(k), tuple(check_bins(nvec)))
+
 
 MAX_GRAD_NORM = 0.5  # ppo_learner.py:187-190
 
@@ -258,7 +275,11 @@ class PPOLearner(object):
         # act_space_size as a sequence: the nvec of a MultiDiscrete action space (a hyper-parameter like the layer sizes: not
         # checkpoint state); checked before anything needs the GPU
         multi_discrete_bins = None
-        if not isinstance(act_space_size, (int, float, np.integer, np.floating)) and np.ndim(act_space_size) > 0:
+        hybrid = isinstance(act_space_size, HybridSpace)
+        if hybrid != (int(policy_type) == 4):
+            raise ValueError(f"policy_type 4 (the hybrid head) and act_space_size=ppo.HybridSpace(k, nvec) go together: got policy_type "
+                             f"{policy_type} with act_space_size={act_space_size!r}")
+        if not hybrid and not isinstance(act_space_size, (int, float, np.integer, np.floating)) and np.ndim(act_space_size) > 0:
             if int(policy_type) != 1:
                 raise ValueError(f"act_space_size={act_space_size!r}: multi-discrete bins are an option of the multi-discrete policy "
                                  f"(policy_type 1), not of policy_type {policy_type}")
@@ -280,7 +301,10 @@ class PPOLearner(object):
         self.policy_type = int(policy_type)
         # construction order (policy, then critic) fixes the CPU-generator consumption and therefore the initial
         # weights (ppo_learner.py:34-53)
-        if policy_type == 3:   # the diagonal-Gaussian head: k means from the network + a learnable log_std (continuous_var_range unused)
+        if hybrid:   # k means + the logits of nvec from one network, a learnable log_std in the arena's tail as for policy_type 3
+            self.policy = HybridPolicy(obs_space_size, act_space_size.k, act_space_size.nvec, policy_layer_sizes, device).to(device)
+            self._act_dim = self.policy.act_dim
+        elif policy_type == 3:   # the diagonal-Gaussian head: k means from the network + a learnable log_std (continuous_var_range unused)
             self.policy = DiagGaussianPolicy(obs_space_size, act_space_size, policy_layer_sizes, device).to(device)
             self._act_dim = int(act_space_size)
         elif policy_type == 2:
@@ -387,6 +411,8 @@ class PPOLearner(object):
             return
         if not isinstance(symmetry, Symmetry):
             raise ValueError(f"set_symmetry: expected a ppo.Symmetry or None, got {type(symmetry).__name__}")
+        if self.policy_type == 4:
+            raise ValueError("set_symmetry: the hybrid head (policy_type 4) has no symmetry tables for its mixed action row")
         pa, va = self.policy.arena, self.value_net.arena
         kw = {0: dict(n_actions=pa.d_out), 1: dict(bins=getattr(self.policy, "splits", None))}.get(self.policy_type, dict(act_dim=self._act_dim))
         if self.critic_obs_space_size is not None or symmetry.critic_obs_perm is not None:
@@ -487,8 +513,8 @@ class PPOLearner(object):
         ws = self._ws.get(nbytes * self.n_slots)
         self._slot_ws = [ws.data_ptr() + i * nbytes for i in range(self.n_slots)]
         a.workspace, a.ws_bytes = self._slot_ws[0], nbytes
-        if self.policy_type == 3:   # allocated once per slot (grown only when a larger pass comes)
-            sb = (int(N.lib().rlppo_diag_scratch_bytes(self._fused_rows, self._act_dim)) + 255) // 256 * 256
+        if self.policy_type in (3, 4):   # allocated once per slot (grown only when a larger pass comes)
+            sb = (int(N.lib().rlppo_diag_scratch_bytes(self._fused_rows, self.policy.log_std.numel())) + 255) // 256 * 256
             if self._diag_scratch is None or self._diag_scratch.numel() < sb * self.n_slots:
                 self._diag_scratch = torch.empty(sb * self.n_slots, dtype=torch.uint8, device=self._dev)
             self._diag_scratch_bytes = sb
@@ -503,9 +529,13 @@ class PPOLearner(object):
         L, pa, va, vn = N.lib(), self.policy.arena, self.value_net.arena, self.value_norm
         e, scratch = N.MinibatchExt(), 0
         e.pol_hidden_act, e.val_hidden_act = pa.hidden_act, va.hidden_act
-        if self.policy_type == 3:   # log_std and its gradient: the tail of the policy's arena, behind the layers; one scratch region per slot
+        if self.policy_type in (3, 4):   # log_std and its gradient: the tail of the policy's arena, behind the layers; one scratch region per slot
             e.log_std, e.log_std_grad = pa.flat.data_ptr() + 4 * pa.n_net, pa.grad.data_ptr() + 4 * pa.n_net
             scratch, e.scratch_bytes = self._diag_scratch.data_ptr(), self._diag_scratch_bytes
+        if self.policy_type == 4:   # ... and the hybrid head's bins beside it
+            e.md_nvec, e.md_heads = ctypes.cast(self.policy._nvec_c, ctypes.POINTER(ctypes.c_int32)), self.policy.n_heads
+        elif self.policy_type == 3:
+            pass
         elif self.policy_type == 1 and (self.policy.md_nvec is not None or args.action_mask):
             e.md_nvec, e.md_heads = ctypes.cast(self.policy._nvec_c, ctypes.POINTER(ctypes.c_int32)), self.policy.n_heads
         if self.value_net.value_bins is not None:   # a categorical critic: the widest form + its bins (the statistic's scale, if any, rides along)
@@ -517,6 +547,8 @@ class PPOLearner(object):
         elif crit is not None:  # the buffer holds critic_states: the critic reads its own matrix
             fn, tail = L.rlppo_ppo_minibatch_critic, (ctypes.byref(e), ctypes.byref(crit))
         elif pa.hidden_act or va.hidden_act:
+            fn, tail = L.rlppo_ppo_minibatch_ex, (ctypes.byref(e),)
+        elif self.policy_type == 4:   # (every form above takes the head from the ext's two parts; the scratch moves with the slot there too)
             fn, tail = L.rlppo_ppo_minibatch_ex, (ctypes.byref(e),)
         elif self.policy_type == 3:
             fn, tail = L.rlppo_ppo_minibatch_diag, None   # (the ext's four diag fields, read per pass: the scratch moves with the slot)

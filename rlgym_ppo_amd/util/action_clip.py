@@ -26,31 +26,42 @@ def check_clip(clip):
 class ActionClipEnv:
     """env with step(clip(actions, lo, hi)); every other attribute (spaces, reset, action_masks, close, ...) is the environment's."""
 
-    def __init__(self, env, lo, hi):
+    def __init__(self, env, lo, hi, columns=None):
         self._env, self._lo, self._hi = env, np.float32(lo), np.float32(hi)
+        self._columns = None if columns is None else int(columns)   # the hybrid head: clip the first `columns` only, the rest are indices (negative: all but the last -columns)
 
     def step(self, actions):
+        k = self.__dict__.get("_columns")
+        if k is not None:   # out of place, the columns behind the first k as they came
+            if isinstance(actions, torch.Tensor):
+                return self._env.step(torch.cat([torch.clamp(actions[..., :k], float(self._lo), float(self._hi)), actions[..., k:]], dim=-1))
+            a = np.array(actions, dtype=np.float32)
+            a[..., :k] = np.clip(a[..., :k], self._lo, self._hi)
+            return self._env.step(a)
         if isinstance(actions, torch.Tensor):   # a device-resident vector environment: out of place, dtype and device kept
             return self._env.step(torch.clamp(actions, float(self._lo), float(self._hi)))
         return self._env.step(np.clip(np.asarray(actions, dtype=np.float32), self._lo, self._hi))
 
     def __getattr__(self, name):   # (only reached for what the wrapper does not define itself)
-        if name.startswith("__") or name in ("_env", "_lo", "_hi"):   # copy / pickle probe before __init__ has run
+        if name.startswith("__") or name in ("_env", "_lo", "_hi", "_columns"):   # copy / pickle probe before __init__ has run
             raise AttributeError(name)
         return getattr(self._env, name)
 
     def __getstate__(self):
-        return {"_env": self._env, "_lo": self._lo, "_hi": self._hi}
+        state = {"_env": self._env, "_lo": self._lo, "_hi": self._hi}
+        if self._columns is not None:
+            state["_columns"] = self._columns
+        return state
 
     def __setstate__(self, state):
         self.__dict__.update(state)
 
 
 class ClippedEnvFactory:
-    """() -> ActionClipEnv(build_env_fn(), lo, hi)."""
+    """() -> ActionClipEnv(build_env_fn(), lo, hi[, columns])."""
 
-    def __init__(self, build_env_fn, lo, hi):
-        self.build_env_fn, self.lo, self.hi = build_env_fn, float(lo), float(hi)
+    def __init__(self, build_env_fn, lo, hi, columns=None):
+        self.build_env_fn, self.lo, self.hi, self.columns = build_env_fn, float(lo), float(hi), columns
 
     def __call__(self):
-        return ActionClipEnv(self.build_env_fn(), self.lo, self.hi)
+        return ActionClipEnv(self.build_env_fn(), self.lo, self.hi, self.columns)
